@@ -15,6 +15,10 @@ final reductions.
 
 Prints ONE JSON line on rank 0 (metric/value/... + "roofline" + "cpu_baseline"; with N > 1 also "c4": the 3840x2160 spp=256
 depth=8 frame BASELINE.json's 8-GPU target is quoted on, timed the same way).
+
+--dump-outputs DIR writes what the last timed step delivered to rank 0 — the six G-buffer planes — as DIR/<plane>.npy (float32,
+one row per pixel), for comparing two builds output for output.  Frames larger than DUMP_MAX_PIXELS pixels are sampled: the same
+seeded set of pixel indices for the same arguments, written beside the planes as DIR/pixel_index.npy (float64).
 """
 import argparse
 import hashlib
@@ -32,12 +36,14 @@ import numpy as np  # noqa: E402
 COUNTERS_FILE = "r4_counters.json"   # written by tools/pmc_to_json.py on the GPU box (tools/profile_r4.sh)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
 KERNEL_NAMES = {"paths": "k_paths", "persistent": "k_persist", "frame": "k_frame", "wavefront": "k_trace", "mega": "k_mega"}
+DUMP_MAX_PIXELS = 1 << 19   # 18 float32 channels per pixel over the six planes: at most 36 MiB of planes + 4 MiB of indices
+DUMP_SAMPLE_SEED = 0x5EED
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (frames); ms_per_step = their wall time / steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -70,7 +76,12 @@ def parse_args():
     ap.add_argument("--share-of", default=None, metavar="r/N",
                     help="diagnostic, N = 1 only: render rank r's tiles of an N-rank run on this one GPU (tools/scale_emulation.py); "
                          "the line's value then counts that share's rays only and config.share_of says so")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's G-buffer planes (rank 0) to DIR/<plane>.npy as float32")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(mats, mine, noise, u, width, height, spp, depth, gpu_rays_per_frame, target_s=12.0, region=256):
@@ -339,10 +350,12 @@ def main():
         rec["gather_ms"], rec["gathers"] = gt
         # content hash of the finished (last) frame on rank 0, outside the timed region: equal for every N
         sha = None
+        planes = None
         if rank == 0:
+            planes = {b: frames[b].cpu().numpy() if dist_on else ctx.readback(b) for b in gather_ids}
             hsh = hashlib.sha256()
             for b in gather_ids:
-                hsh.update(frames[b].cpu().numpy().tobytes() if dist_on else ctx.readback(b).tobytes())
+                hsh.update(planes[b].tobytes())
             sha = hsh.hexdigest()[:16]
         ctx.destroy()
         # whole-job figures: MAX of the ranks' times, SUM of their counts
@@ -364,6 +377,7 @@ def main():
         rec["rank_rays"] = [int(-sp[3]), int(sp[2])]
         rec["rays_total"], rec["trace_bytes_total"], rec["balg_total"], rec["ref_rays_total"] = [float(x) for x in sums.tolist()]
         rec["sha"] = sha
+        rec["planes"] = planes
         return rec
 
     def roofline_of(r, steps, W_, H_, SPP_, D_):
@@ -473,6 +487,9 @@ def main():
 
     W, H, SPP, D = args.width, args.height, args.spp, args.depth
     rec = measure(W, H, SPP, D, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, rec["planes"])
+    rec.pop("planes")
     c4 = None
     if world > 1 and not args.no_c4 and REGION == 256:
         # the configuration BASELINE.json's ">= 6x at 8 GPUs" is quoted on
@@ -535,6 +552,29 @@ def main():
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, planes):
+    """Rank 0's planes of the last timed step -> out_dir/<plane>.npy, float32 [pixels, channels] (the integer planes' values are
+    exact in float32).  Pixels in row-major frame order (tile order for a --share-of run); above DUMP_MAX_PIXELS a fixed seeded
+    sample of them, whose indices go to pixel_index.npy."""
+    from raytrace_amd import abi
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {}
+    for b, a in planes.items():
+        dt, ch = abi.BUFFER_FORMATS[b]
+        flat[abi.BUFFER_NAMES[b]] = np.ascontiguousarray(a).reshape(-1).view(dt).reshape(-1, ch)
+    pixels = {a.shape[0] for a in flat.values()}
+    assert len(pixels) == 1, pixels
+    n = pixels.pop()
+    idx = None
+    if n > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_MAX_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    elif os.path.exists(os.path.join(out_dir, "pixel_index.npy")):
+        os.remove(os.path.join(out_dir, "pixel_index.npy"))      # left by an earlier, sampled dump into the same directory
+    for name, a in flat.items():
+        np.save(os.path.join(out_dir, name + ".npy"), (a if idx is None else a[idx]).astype(np.float32))
 
 
 class _DevArray:
