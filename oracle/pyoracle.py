@@ -87,6 +87,25 @@ def render(materials, minefield, noise, uniforms, width, height, spp=1, depth=2,
     return planes, cn
 
 
+def fetch_histogram(materials, minefield, noise, uniforms, width, height, spp=1, depth=2, bricks=None):
+    """render() on a 256 region, single-threaded, with the oracle's fetch statistics on (rt_oracle_fetch_stats_begin/_end).
+    Returns (planes, RtCounters, hist u64[2, 32]): hist[1][v] counts the minefield fetches of value v that landed in a 4^3 brick
+    whose 64 values are all equal, hist[0][v] those that landed in a brick holding differing values.  `bricks` (u8[64^3], brick
+    (z, y, x) at z * 4096 + y * 64 + x) replaces "all equal" by another set of bricks: hist[1] then counts the fetches there."""
+    if bricks is None:
+        mine = np.ascontiguousarray(minefield, dtype=np.uint8).reshape(64, 4, 64, 4, 64, 4)
+        bricks = (mine.min(axis=(1, 3, 5)) == mine.max(axis=(1, 3, 5))).astype(np.uint8)
+    uniform4 = np.ascontiguousarray(bricks, dtype=np.uint8).reshape(-1)
+    assert uniform4.size == 64 ** 3
+    hist = np.zeros((2, 32), dtype=np.uint64)
+    lib().rt_oracle_fetch_stats_begin(_p(uniform4))
+    try:
+        planes, cn = render(materials, minefield, noise, uniforms, width, height, spp, depth, threads=1)
+    finally:
+        lib().rt_oracle_fetch_stats_end(_p(hist))
+    return planes, cn, hist
+
+
 def camera_uniforms(origin, heading, pitch, sun_angle=0.0, seed=1, lr=(0, 0, 0)):
     u = RtUniforms()
     o = (C.c_float * 3)(*origin)

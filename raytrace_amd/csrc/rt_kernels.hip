@@ -266,7 +266,8 @@ __global__ __launch_bounds__(1024, 4) void k_trace(Scene sc, Frame f, TraceArgs 
                     else if (nrm == 2) py += off; else if (nrm == 3) py -= off;
                     else if (nrm == 4) pz += off; else pz -= off;
                     a.hx[path] = px; a.hy[path] = py; a.hz[path] = pz;
-                    a.hinfo[path] = material | (nrm << 24) | (kind == EXIT_AIR ? 0x80000000u : 0u) |
+                    // only the albedo bits travel: a material word is any u32, its bits 21..31 must not reach the flags
+                    a.hinfo[path] = (material & 0x1FFFFFu) | (nrm << 24) | (kind == EXIT_AIR ? 0x80000000u : 0u) |
                                     (kind == EXIT_LIMIT ? 0x40000000u : 0u);
                 }
             }

@@ -6,7 +6,7 @@ import pytest
 
 from raytrace_amd import abi, render, world
 from oracle import pyoracle as po
-from tests import scenes
+from tests import adversarial_worlds, scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -25,13 +25,17 @@ def _cases(rng, n):
     return out
 
 
-@pytest.mark.parametrize("scene_name", ["procedural", "blocks", "stairs"])
+@pytest.mark.parametrize("scene_name", ["procedural", "blocks", "stairs", "arbitrary", "pyramid"])
 def test_random_cases_match_oracle(scene_name, procedural_region, blue_noise):
     if scene_name == "procedural":
         mats, mine = procedural_region
+    elif scene_name == "arbitrary":
+        mats, mine = adversarial_worlds.arbitrary_world(256)[:2]
+    elif scene_name == "pyramid":
+        mats, mine = adversarial_worlds.pyramid_world(256)[:2]
     else:
         mats, mine = world.region_from_ids({"blocks": scenes.random_blocks_ids, "stairs": scenes.staircase_ids}[scene_name]())
-    rng = np.random.default_rng({"procedural": 101, "blocks": 202, "stairs": 303}[scene_name])
+    rng = np.random.default_rng({"procedural": 101, "blocks": 202, "stairs": 303, "arbitrary": 404, "pyramid": 505}[scene_name])
     for case in _cases(rng, 10):
         if scene_name == "procedural" and case["origin"][2] < 0 and rng.random() < 0.7:
             case["origin"] = (case["origin"][0], case["origin"][1], abs(case["origin"][2]))   # mostly above ground
