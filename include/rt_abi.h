@@ -127,6 +127,23 @@ typedef enum RtKernel {
                                        rt_gather_gbuffer act on the frame drawn last and are ordered after it; rt_sync waits for
                                        every frame.  Persistent kernels (DEFAULT / PERSISTENT / PATHS) on the context's own stream
                                        only: ignored elsewhere and after rt_set_stream(non-NULL).                          */
+#define RT_FLAG_ACCUMULATE 0x40u /* (ABI 1.3, additive) progressive accumulation while the camera holds still: the context keeps a
+                                       per-pixel fp32 running sum of the lighting (npix_pad x 16 B of device memory, RtInfo.device_bytes,
+                                       shared by the frame slots, untouched by rt_denoise / rt_finalize) and, on the host, the number
+                                       of samples it holds.  A frame CONTINUES the accumulation when a frame was drawn before and its
+                                       live uniforms other than seed (sun_angle, origin, forward, up, right, lr) are bitwise equal to
+                                       that frame's, none of rt_upload_world / rt_upload_slice / rt_upload_noise / rt_reset_accumulation
+                                       was called since, and samples + spp <= 2^24; otherwise it starts from zero and is bit-identical to
+                                       the same frame without the flag.  The dead uniform fields are ignored and seed is not checked: a
+                                       host that advances seed by spp per frame (mod RT_NOISE_BYTES; spp 1: the reference's own +1)
+                                       gets after K frames of spp samples exactly the frame of K x spp samples from the first seed
+                                       (RtConfig.spp: the ordered fp32 sum continues where the previous frame left it).  Then
+                                       lighting_f32 / lighting_rgba16 = sum of all the samples / n / 16; the other planes and RtCounters
+                                       are the frame's own.  One-sample frames run as before plus one bandwidth pass (k_accumulate_frame);
+                                       frames of more samples do not run on RT_KERNEL_FRAME's k_frame (small ones lose its speed-up)
+                                       but on the persistent kernels, whose prepass and accumulate launch continue the sum.
+                                       RT_KERNEL_DEFAULT / FRAME / PATHS / PERSISTENT; rt_create rejects it on MEGA and WAVEFRONT
+                                       (RT_ERR_UNIMPLEMENTED).  See rt_reset_accumulation / rt_get_accumulation.             */
 
 /*
  * RtConfig — replaces the compile-time window constants (constants.rs:9-10) and adds the
@@ -366,6 +383,13 @@ int rt_kernel_in_use(RtContext* ctx);
 #define RT_SELFTEST_DENOISE_DIVISION 1
 int rt_selftest(RtContext* ctx, int which, uint64_t* result);
 
+/* (ABI 1.3, additive; hosts detect the feature by this symbol) RT_FLAG_ACCUMULATE: the next rt_draw_frame starts the running sum
+ * from zero.  No effect on a context without the flag. */
+int rt_reset_accumulation(RtContext* ctx);
+/* Frames and samples the lighting planes of the frame drawn last hold: (k, k x spp) after k frames of an accumulation; 1 and spp
+ * on a context without RT_FLAG_ACCUMULATE; 0 and 0 before the first frame.  Host-side state only: does not synchronise. */
+int rt_get_accumulation(RtContext* ctx, uint32_t* frames, uint32_t* samples);
+
 int rt_get_counters(RtContext* ctx, RtCounters* out);
 int rt_reset_counters(RtContext* ctx);
 int rt_get_timing(RtContext* ctx, RtTiming* out);
@@ -385,7 +409,8 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        rt_samples_per_launch, rt_get_gather_timing; RtKernel value 6 (SEQ) rejected by rt_create; the sample batches of a multi-launch frame run on two
  *        streams of the library (results unchanged; rt_set_stream(non-NULL) keeps everything on the caller's stream).
  *   1.3  round 4: RtKernel value 7 (RT_KERNEL_FRAME); RT_KERNEL_DEFAULT runs frames with little work on it (rt_kernel_in_use tells);
- *        results unchanged. */
+ *        results unchanged.
+ *        Additive, same minor version: RT_FLAG_ACCUMULATE, rt_reset_accumulation, rt_get_accumulation (progressive accumulation). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

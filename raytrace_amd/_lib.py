@@ -19,6 +19,7 @@ ABI_SYMBOLS = (
     "rt_abi_version",
     "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer", "rt_frame_ptr",
     "rt_frame_readback", "rt_selftest", "rt_get_info", "rt_samples_per_launch", "rt_get_gather_timing",
+    "rt_reset_accumulation", "rt_get_accumulation",
 )
 
 _amd = None
@@ -95,6 +96,10 @@ def amd():
         lib.rt_frame_readback.restype = C.c_int
         lib.rt_selftest.argtypes = [P, C.c_int, C.POINTER(C.c_uint64)]
         lib.rt_selftest.restype = C.c_int
+        lib.rt_reset_accumulation.argtypes = [P]
+        lib.rt_reset_accumulation.restype = C.c_int
+        lib.rt_get_accumulation.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.rt_get_accumulation.restype = C.c_int
         for name in ("rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer"):
             getattr(lib, name).restype = C.c_int
         for name in ("rt_upload_world", "rt_upload_slice", "rt_slice_staging", "rt_upload_noise", "rt_draw_frame", "rt_sync", "rt_readback",

@@ -181,6 +181,17 @@ struct RtContext {
     std::vector<void*> allocs;
     uint64_t device_bytes = 0;       // sum of the context's device allocations (rt_get_info)
     uint64_t light_budget_bytes = 0; // what the per-path light records were sized for
+
+    // progressive accumulation (RT_FLAG_ACCUMULATE): per-pixel running sum of the lighting by plane index (PixelId::out_index),
+    // shared by the frame slots; what it holds is host-side state
+    float4* d_accum = nullptr;
+    bool accum_valid = false;           // the next frame may continue the sum (a frame was drawn and nothing reset it since)
+    uint32_t accum_key[16] = {};        // live uniforms other than seed of the frame drawn last (bit patterns)
+    uint64_t accum_frames = 0, accum_samples = 0;   // frames and samples the planes of the frame drawn last hold
+    bool drawn = false;                 // a frame was drawn (rt_get_accumulation of a context without the flag)
+    hipEvent_t ev_accum = nullptr;      // the last step of the frame drawn last that touched d_accum (two lanes only) ...
+    hipStream_t accum_stream = nullptr; // ... recorded on this stream
+    bool accum_recorded = false;
 };
 
 constexpr size_t kMaxTimerEvents = 2 * 4096;   // LaunchTimer pool cap: pairs beyond it are not timed (counted in timer_overflow)
@@ -251,6 +262,13 @@ void sun_constants(float a, float* sunangle, float* sunlight) {
     for (int k = 0; k < 3; k++)
         sunlight[k] = v.z >= 0.0f ? rtm_mix(sunset_color[k], main_color[k], sun_amount)
                                   : rtm_mix(sunset_color[k], 0.0f, sun_amount * 2);
+}
+
+// RT_FLAG_ACCUMULATE: the uniforms a frame continues the accumulation under — every live field but seed, bit for bit
+void accum_key_of(const RtUniforms* u, uint32_t key[16]) {
+    memcpy(&key[0], &u->sun_angle, 4);
+    memcpy(&key[1], u->origin, 12); memcpy(&key[4], u->forward, 12); memcpy(&key[7], u->up, 12); memcpy(&key[10], u->right, 12);
+    memcpy(&key[13], u->lr, 12);
 }
 
 rtd::Frame frame_of(const RtContext* c, const RtUniforms* u) {
@@ -424,6 +442,8 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
     if (cfg->kernel < RT_KERNEL_DEFAULT || cfg->kernel > RT_KERNEL_FRAME || cfg->kernel == 4 /* RT_KERNEL_PERSISTENT2, retired in round 3 */ ||
         cfg->kernel == 6 /* RT_KERNEL_SEQ, retired in round 4 */)
         return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: unknown kernel");
+    if ((cfg->flags & RT_FLAG_ACCUMULATE) && (cfg->kernel == RT_KERNEL_MEGA || cfg->kernel == RT_KERNEL_WAVEFRONT))
+        return fail(nullptr, RT_ERR_UNIMPLEMENTED, "rt_create: RT_FLAG_ACCUMULATE needs RT_KERNEL_DEFAULT, FRAME, PATHS or PERSISTENT (not the baselines)");
 
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -580,6 +600,10 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
             }
             c->persist_batch = (uint32_t)B;
         }
+        if (cfg->flags & RT_FLAG_ACCUMULATE) {
+            RT_HIP_CREATE(dev_alloc(c, &c->d_accum, (size_t)c->npix_pad));
+            RT_HIP_CREATE(hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming));
+        }
         RT_HIP_CREATE(rtd::launch_sphere_lut(c->sphere_lut, c->own_stream));
         RT_HIP_CREATE(rtd::launch_dif_lut(c->sphere_lut, c->dif_lut, c->own_stream));
         RT_HIP_CREATE(hipStreamSynchronize(c->own_stream));
@@ -621,7 +645,7 @@ void rt_destroy(RtContext* ctx) {
     if (ctx->lanes[1].stream) { (void)hipStreamSynchronize(ctx->lanes[1].stream); (void)hipStreamDestroy(ctx->lanes[1].stream); }
     for (Lane& ln : ctx->lanes) if (ln.ev_join) (void)hipEventDestroy(ln.ev_join);
     for (FrameSlot& fs : ctx->slots) for (hipEvent_t e : {fs.ev_prepass, fs.ev_acc, fs.ev_tail}) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->ev_fence, ctx->ev_gather}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->ev_fence, ctx->ev_gather, ctx->ev_accum}) if (e) (void)hipEventDestroy(e);
     if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); (void)hipStreamDestroy(ctx->upload_stream); }
     for (int k = 0; k < 2; k++) {
         if (ctx->ev_slab_copied[k]) (void)hipEventDestroy(ctx->ev_slab_copied[k]);
@@ -651,12 +675,14 @@ int rt_set_stream(RtContext* ctx, void* hip_stream) {
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
     ctx->lanes[0].stream = ctx->stream;
     ctx->user_stream = hip_stream != nullptr;
+    ctx->accum_recorded = false;   // (everything before has finished)
     return RT_OK;
 }
 
 int rt_upload_world(RtContext* ctx, const uint32_t* materials, const uint8_t* minefield) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_world: null pointer");
+    ctx->accum_valid = false;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, sync_lanes(ctx));
     // the caller-layout copy lives for the duration of this call only (it used to stay resident — 160 MiB at
@@ -714,6 +740,7 @@ int rt_slice_staging(RtContext* ctx, uint32_t** materials, uint8_t** minefield) 
 int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* materials, const uint8_t* minefield) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: null pointer");
+    ctx->accum_valid = false;
     const size_t kR = (size_t)ctx->region;
     if (axis < 0 || axis > 2 || texel_offset < 0 || texel_offset + RT_SLICE_SIZE > ctx->region || texel_offset % RT_SLICE_SIZE != 0)
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: bad axis or offset");
@@ -762,6 +789,7 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
 int rt_upload_noise(RtContext* ctx, const uint8_t* rgba8) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!rgba8) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_noise: null pointer");
+    ctx->accum_valid = false;
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, sync_lanes(ctx));
     RT_HIP(ctx, hipMemcpy(ctx->d_noise, rgba8, RT_NOISE_BYTES, hipMemcpyHostToDevice));
@@ -808,11 +836,28 @@ int rt_draw_frame(RtContext* ctx, const RtUniforms* u) {
         uint32_t* const wlc = fs.wl_count + 32 * fs.wl_parity;
         uint32_t* const wln = fs.wl_count + 32 * (fs.wl_parity ^ 1);
         const bool prepass_clears = cache && ctx->primary_version == 2 && ctx->npix_pad != 0;
+        // RT_FLAG_ACCUMULATE: does this frame continue the running sum, and how many samples will it hold (the lighting's divisor)?
+        // One-sample frames add theirs in k_accumulate_frame after the frame's launches.  Frames of more samples continue the ordered
+        // sum from the running one: k_accumulate_frame for the pixels the prepass finishes, k_accumulate_paths<.., ACCUM> for the
+        // paths' (its first batch starts from the running sum, its last stores it back) — so they do not run on k_frame, whose
+        // workgroups add a pixel's samples from 0.  The step that touches the sum follows the previous frame's (ev_accum), not the
+        // whole previous frame.
+        const bool accum = ctx->d_accum != nullptr;
+        const uint32_t spp_u = (uint32_t)ctx->cfg.spp;
+        uint32_t key[16];
+        accum_key_of(u, key);
+        const bool accum_cont = accum && ctx->accum_valid && memcmp(key, ctx->accum_key, sizeof(key)) == 0 &&
+                                ctx->accum_samples + spp_u <= (1ull << 24);
+        const uint64_t accum_n = accum_cont ? ctx->accum_samples + spp_u : spp_u;
+        float4* const accum_multi = accum && spp_u > 1u ? ctx->d_accum : nullptr;
+        auto accum_wait = [&](hipStream_t st) {
+            return ctx->accum_recorded && ctx->accum_stream != st ? hipStreamWaitEvent(st, ctx->ev_accum, 0) : hipSuccess;
+        };
         // k_frame: the whole frame in one launch (cached primaries by construction; frames it does not cover go the persistent way)
         // (with one sample per pixel "cached primaries" is what every kernel does anyway: the flag is not needed)
         // (more than one sample: the paths' light records go to the lane's array, which must hold the whole frame's)
         const bool one_launch = (cache || ctx->cfg.spp == 1) && rtd::launch_frame_ok(f) && (ctx->cfg.spp == 1 || (uint32_t)ctx->cfg.spp <= ctx->persist_batch) &&
-                                (ctx->frame_mode == 2 || (ctx->frame_mode == 1 && frame_by_size(ctx)));
+                                (ctx->frame_mode == 2 || (ctx->frame_mode == 1 && frame_by_size(ctx))) && accum_multi == nullptr;
         if (e == hipSuccess && cache && !one_launch) {
             if (!fs.wl_clean[fs.wl_parity]) e = hipMemsetAsync(wlc, 0, sizeof(uint32_t), st0);
             fs.wl_clean[fs.wl_parity] = false;
@@ -824,7 +869,14 @@ int rt_draw_frame(RtContext* ctx, const RtUniforms* u) {
             // worklist counter (the slot's next frame) and the path cursors of the lane it runs on (this frame's first launch)
             pr.zero_words = prepass_clears ? wln : nullptr; pr.zero_count = 1u;
             pr.zero_words2 = prepass_clears ? L0->cursor : nullptr; pr.zero_count2 = (uint32_t)kCursorWords;
-            if (e == hipSuccess) e = rtd::launch_primary(scene_of(ctx), f, fpl, pr, count, ctx->primary_version, ctx->num_cus, st0);
+            // accumulating: the prepass runs as a one-sample frame, so the light of a pixel it finishes is 16 x its lighting_f32 exactly;
+            // k_accumulate_frame then adds it spp times to the pixel's running sum (the prepass adds it spp times to 0 otherwise)
+            rtd::Frame fpre = f;
+            if (accum_multi) fpre.spp = 1;
+            if (e == hipSuccess) e = rtd::launch_primary(scene_of(ctx), fpre, fpl, pr, count, ctx->primary_version, ctx->num_cus, st0);
+            if (e == hipSuccess && accum_multi) e = accum_wait(st0);
+            if (e == hipSuccess && accum_multi)
+                e = rtd::launch_accumulate_frame(f, fpl, ctx->d_accum, ctx->npix_pad, accum_cont, (int)accum_n, (int)spp_u, true, st0);
             if (prepass_clears && e == hipSuccess) { fs.wl_clean[fs.wl_parity ^ 1] = true; L0->cursor_clean = true; }
             fs.wl_parity ^= 1;
         }
@@ -914,11 +966,13 @@ int rt_draw_frame(RtContext* ctx, const RtUniforms* u) {
                 if (e == hipSuccess && !direct) {
                     // a pixel's samples are added in sample order: batch b's accumulate follows batch b - 1's, whichever lane that ran on
                     if (nl == 2 && s0 != 0) e = hipStreamWaitEvent(st, fs.ev_acc, 0);
+                    // (with cached primaries the prepass, which came first, has waited for the previous frame's running sums)
+                    if (e == hipSuccess && accum_multi && !cache && s0 == 0) e = accum_wait(st);
                     {
                         LaunchTimer t(ctx, 1, st);
                         if (e == hipSuccess)
                             e = rtd::launch_accumulate_paths(f, fpl, L->ppl, fs.worklist, wlc, ctx->npix_pad, ns, s0 == 0, s0 + B >= spp, cache, stream_ld,
-                                                             fs.pacc, st);
+                                                             fs.pacc, accum_multi, accum_cont, (int)accum_n, st);
                     }
                     if (e == hipSuccess && nl == 2 && s0 + B < spp) e = hipEventRecord(fs.ev_acc, st);
                 }
@@ -926,6 +980,22 @@ int rt_draw_frame(RtContext* ctx, const RtUniforms* u) {
             }
         }
         // (no resolve launch: the prepass and the last accumulate of the frame store the lighting planes themselves)
+        if (e == hipSuccess && accum && spp_u == 1u) {
+            e = accum_wait(tail);
+            LaunchTimer t(ctx, 1, tail);
+            if (e == hipSuccess) e = rtd::launch_accumulate_frame(f, fpl, ctx->d_accum, ctx->npix_pad, accum_cont, (int)accum_n, 1, false, tail);
+        }
+        if (e == hipSuccess && accum && nl == 2) {
+            e = hipEventRecord(ctx->ev_accum, tail);
+            ctx->accum_recorded = e == hipSuccess;
+            ctx->accum_stream = tail;
+        }
+        if (accum) {
+            ctx->accum_valid = e == hipSuccess;
+            ctx->accum_frames = accum_cont ? ctx->accum_frames + 1u : 1u;
+            ctx->accum_samples = accum_n;
+            memcpy(ctx->accum_key, key, sizeof(key));
+        }
         if (e != hipSuccess) rc = fail(ctx, RT_ERR_HIP, std::string("persistent path: ") + hipGetErrorString(e));
         // the frame ends on `tail`: post passes, gather and readback of THIS frame follow it there; its planes are the context's
         ctx->stream = tail;
@@ -939,8 +1009,24 @@ int rt_draw_frame(RtContext* ctx, const RtUniforms* u) {
     }
     if (frame_events) RT_HIP(ctx, hipEventRecord(ctx->ev_frame1, ctx->stream));
     ctx->frame_recorded = true;
+    if (rc == RT_OK) ctx->drawn = true;
     if (count) { ctx->host_noise_base += (uint64_t)ctx->cfg.spp; ctx->host_frames++; }
     return rc;
+}
+
+int rt_reset_accumulation(RtContext* ctx) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    ctx->accum_valid = false;
+    return RT_OK;
+}
+
+int rt_get_accumulation(RtContext* ctx, uint32_t* frames, uint32_t* samples) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!frames || !samples) return fail(ctx, RT_ERR_INVALID_ARG, "rt_get_accumulation: null pointer");
+    if (!ctx->drawn) { *frames = 0; *samples = 0; }
+    else if (ctx->d_accum) { *frames = (uint32_t)ctx->accum_frames; *samples = (uint32_t)ctx->accum_samples; }
+    else { *frames = 1; *samples = (uint32_t)ctx->cfg.spp; }
+    return RT_OK;
 }
 
 int rt_sync(RtContext* ctx) {

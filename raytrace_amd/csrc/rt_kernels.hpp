@@ -99,7 +99,14 @@ bool launch_frame_ok(const Frame& f);   // does k_frame cover this frame (depth 
 hipError_t launch_frame(const Scene& sc, const Frame& f, const Planes& pl, FrameArgs a, bool count, int num_cus, hipStream_t st);
 hipError_t launch_accumulate_paths(const Frame& f, const Planes& planes, const PathLight* pl, const uint32_t* worklist,
                                    const uint32_t* wl_count, uint32_t npix_pad, uint32_t nsamples, bool first_batch, bool last_batch,
-                                   bool cache, bool stream, float4* acc, hipStream_t st);
+                                   bool cache, bool stream, float4* acc, float4* accum, bool accum_continue, int accum_div,
+                                   hipStream_t st);
+// (accum: RT_FLAG_ACCUMULATE's running sums by out_index, null without; see k_accumulate_paths)
+// RT_FLAG_ACCUMULATE: accum[out] = (accum_continue ? accum[out] : 0) + reps x (16 x lighting_f32[out], a one-sample light, exactly),
+// and the two lighting planes become that sum / n / 16 — for every pixel (one-sample frames, after the frame's launches) or only
+// for the pixels a one-sample prepass finished (finished_only: sky pixels, or all of them at depth 0)
+hipError_t launch_accumulate_frame(const Frame& f, const Planes& planes, float4* accum, uint32_t npix_pad, bool accum_continue, int n,
+                                   int reps, bool finished_only, hipStream_t st);
 hipError_t launch_sphere_lut(float4* lut, hipStream_t st);
 hipError_t launch_dif_lut(const float4* sphere, float4* lut, hipStream_t st);
 hipError_t launch_sun_lut(const Frame& f, float4* lut, hipStream_t st);

@@ -593,16 +593,24 @@ __global__ __launch_bounds__(1024, 4) void k_persist(Scene sc, Frame f, Planes p
 // sample per frame, the sum over frames is the build's spp extension).  The last batch of a frame writes the pixel's
 // lighting planes itself (sum / spp / 16, raytrace.comp:352-356) — the prepass has done that for the pixels it finished —
 // so no separate resolve launch is needed.
-template <bool CACHE, bool STREAM>
+// ACCUM (RT_FLAG_ACCUMULATE): the first batch starts from the context's running sum of the pixel (accum_continue) or from 0, the
+// last one stores the sum back there and divides by accum_div, the samples the sum holds.  (A template parameter: the
+// instantiations without it compile to what they were before the feature.)
+template <bool CACHE, bool STREAM, bool ACCUM>
 __global__ __launch_bounds__(256) void k_accumulate_paths(Frame f, Planes planes, const PathLight* __restrict__ pl,
                                                           const uint32_t* __restrict__ worklist,
                                                           const uint32_t* __restrict__ wl_count, uint32_t npix_pad,
-                                                          uint32_t nsamples, int first_batch, int last_batch, float4* __restrict__ acc) {
+                                                          uint32_t nsamples, int first_batch, int last_batch, float4* __restrict__ acc,
+                                                          float4* __restrict__ accum, int accum_continue, int accum_div) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
     const uint32_t nwork = CACHE ? *wl_count : npix_pad;
     if (w >= nwork) return;
     const uint32_t lp = CACHE ? worklist[w] : w;
     float4 v = first_batch ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : acc[lp];
+    if (ACCUM && first_batch && accum_continue) {
+        const PixelId pix = pixel_of_local(f, lp);
+        if (pix.inside) v = accum[pix.out_index];
+    }
     for (uint32_t b = 0; b < nsamples; b++) {
         // STREAM: read once and too many to have stayed in the caches — streaming loads, like k_paths' stores of them (headline frame
         // 4.29 -> 4.25 ms with both; a launch whose records fit the Infinity Cache is better off with plain loads)
@@ -613,20 +621,65 @@ __global__ __launch_bounds__(256) void k_accumulate_paths(Frame f, Planes planes
     }
     if (last_batch) {
         const PixelId pix = pixel_of_local(f, lp);
-        if (pix.inside) store_lighting(planes, pix.out_index, v3(v.x, v.y, v.z), f.spp);
+        if (pix.inside) {
+            if (ACCUM) accum[pix.out_index] = v;
+            store_lighting(planes, pix.out_index, v3(v.x, v.y, v.z), ACCUM ? accum_div : f.spp);
+        }
     } else {
         acc[lp] = v;
     }
 }
 
+// k_accumulate_frame — RT_FLAG_ACCUMULATE.  A pixel whose lighting_f32 was stored from ONE sample holds ((0 + light) / 1) / 16, so
+// 16 x lighting_f32 is that light exactly, and adding it `reps` times to the running sum (or to 0) continues the ordered sum of
+// the frames before, in sample order, as a frame of all their samples adds them.  Two uses:
+//   finished_only = 0: one-sample frames, every pixel, after the frame's own launches (reps = 1);
+//   finished_only = 1: frames of `reps` samples with cached primaries, right after a prepass that ran as a one-sample frame: only the
+//                      pixels it finished (sky, or depth 0: every sample has the same light), which no path launch touches; the
+//                      others are k_accumulate_paths<.., ACCUM = true>'s.
+// A bandwidth pass: 16-byte loads of lighting_f32 and accum (continue only), a 16-byte store of accum and the two lighting stores
+// per pixel; padding pixels of the tiles are skipped.
+__global__ __launch_bounds__(256) void k_accumulate_frame(Frame f, Planes planes, float4* __restrict__ accum, uint32_t npix_pad,
+                                                          int accum_continue, int n, int reps, int finished_only) {
+    const float4* __restrict__ lf = reinterpret_cast<const float4*>(planes.lighting_f32);
+    for (uint32_t lp = blockIdx.x * 256u + threadIdx.x; lp < npix_pad; lp += gridDim.x * 256u) {
+        const PixelId pix = pixel_of_local(f, lp);
+        if (!pix.inside) continue;
+        if (finished_only && f.depth >= 1 && planes.normal_r8[pix.out_index] != (uint8_t)RT_NORMAL_AIR) continue;
+        const float4 l = lf[pix.out_index];
+        const vec3 light = v3(l.x * RT_LIGHTING_SCALE, l.y * RT_LIGHTING_SCALE, l.z * RT_LIGHTING_SCALE);
+        vec3 sum = v3(0.0f, 0.0f, 0.0f);
+        if (accum_continue) { const float4 p = accum[pix.out_index]; sum = v3(p.x, p.y, p.z); }
+        for (int s = 0; s < reps; s++) sum = vadd(sum, light);
+        accum[pix.out_index] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+        store_lighting(planes, pix.out_index, sum, n);
+    }
+}
+
+hipError_t launch_accumulate_frame(const Frame& f, const Planes& planes, float4* accum, uint32_t npix_pad, bool accum_continue, int n,
+                                   int reps, bool finished_only, hipStream_t st) {
+    if (npix_pad == 0) return hipSuccess;
+    const uint32_t blocks = (npix_pad + 255u) / 256u;
+    hipLaunchKernelGGL(k_accumulate_frame, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, st, f, planes, accum, npix_pad,
+                       accum_continue ? 1 : 0, n, reps, finished_only ? 1 : 0);
+    return hipGetLastError();
+}
+
 hipError_t launch_accumulate_paths(const Frame& f, const Planes& planes, const PathLight* pl, const uint32_t* worklist,
                                    const uint32_t* wl_count, uint32_t npix_pad, uint32_t nsamples, bool first_batch, bool last_batch,
-                                   bool cache, bool stream, float4* acc, hipStream_t st) {
+                                   bool cache, bool stream, float4* acc, float4* accum, bool accum_continue, int accum_div,
+                                   hipStream_t st) {
     if (npix_pad == 0) return hipSuccess;
     dim3 grid((npix_pad + 255u) / 256u), block(256);
-#define RT_LAUNCH_ACC(C, S) hipLaunchKernelGGL((k_accumulate_paths<C, S>), grid, block, 0, st, f, planes, pl, worklist, wl_count, npix_pad, nsamples, first_batch ? 1 : 0, last_batch ? 1 : 0, acc)
-    if (cache) { if (stream) RT_LAUNCH_ACC(true, true); else RT_LAUNCH_ACC(true, false); }
-    else { if (stream) RT_LAUNCH_ACC(false, true); else RT_LAUNCH_ACC(false, false); }
+#define RT_LAUNCH_ACC(C, S, A) hipLaunchKernelGGL((k_accumulate_paths<C, S, A>), grid, block, 0, st, f, planes, pl, worklist, wl_count, npix_pad, nsamples, first_batch ? 1 : 0, last_batch ? 1 : 0, acc, \
+                                                  accum, accum_continue ? 1 : 0, accum_div)
+    if (accum != nullptr) {
+        if (cache) { if (stream) RT_LAUNCH_ACC(true, true, true); else RT_LAUNCH_ACC(true, false, true); }
+        else { if (stream) RT_LAUNCH_ACC(false, true, true); else RT_LAUNCH_ACC(false, false, true); }
+    } else {
+        if (cache) { if (stream) RT_LAUNCH_ACC(true, true, false); else RT_LAUNCH_ACC(true, false, false); }
+        else { if (stream) RT_LAUNCH_ACC(false, true, false); else RT_LAUNCH_ACC(false, false, false); }
+    }
 #undef RT_LAUNCH_ACC
     return hipGetLastError();
 }

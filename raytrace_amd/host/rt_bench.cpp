@@ -5,7 +5,7 @@
 // asks of the bench binary (config, rays, ms, Mrays/s).
 //
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
-//            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post]
+//            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -13,6 +13,10 @@
 // --gpus N (one host thread per device, ncclCommInitAll through rt_comm_init_all): device i renders the tiles t % N == i and
 // every frame ends with rt_gather_gbuffer to device 0, which assembles the full frame in the library's own planes.
 // --gather runs that frame-end step with N = 1 too (a one-rank communicator).
+//
+// --accumulate: the contexts are created with RT_FLAG_ACCUMULATE.  The camera stays where it is and the mirror's draw_frame
+// advances the seed by spp per frame, so every frame continues the accumulation; the JSON line adds the samples the last frame's
+// lighting holds (rt_get_accumulation).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -85,7 +89,7 @@ class ThreadBarrier {
 int main(int argc, char** argv) {
     int width = 1024, height = 1024;   // WINDOW_WIDTH / WINDOW_HEIGHT, src/render/constants.rs:9-10
     int spp = 1, depth = 2, frames = 240, device = 0, gpus = 1;
-    bool gather = false, overlap = false, post = false;
+    bool gather = false, overlap = false, post = false, accumulate = false;
     std::string noise_path = "tests/golden/blue_noise_512.rgba";
     std::vector<const char*> positional = {argv[0]};
     for (int i = 1; i < argc; i++) {
@@ -101,6 +105,7 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--gather") == 0) gather = true;
         else if (std::strcmp(argv[i], "--overlap") == 0) overlap = true;
         else if (std::strcmp(argv[i], "--post") == 0) post = true;
+        else if (std::strcmp(argv[i], "--accumulate") == 0) accumulate = true;
         else positional.push_back(argv[i]);
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
@@ -142,7 +147,7 @@ int main(int argc, char** argv) {
     std::vector<int> devices((size_t)gpus);
     for (int g = 0; g < gpus; g++) devices[(size_t)g] = device + g;
     for (int g = 0; g < gpus; g++) {
-        RtConfig cfg = make_config(width, height, spp, depth, devices[(size_t)g], g, gpus, RT_FLAG_CACHE_PRIMARY);
+        RtConfig cfg = make_config(width, height, spp, depth, devices[(size_t)g], g, gpus, RT_FLAG_CACHE_PRIMARY | (accumulate ? RT_FLAG_ACCUMULATE : 0u));
         pipes[(size_t)g] = rt::render::create_instance(cfg, noise.data(), game, &err);
         if (!pipes[(size_t)g]) {
             std::fprintf(stderr, "create_instance failed on device %d: %s\n", devices[(size_t)g], err.c_str());
@@ -222,14 +227,17 @@ int main(int argc, char** argv) {
                 for (uint8_t v : final_plane) final_checksum += v;
             else { std::fprintf(stderr, "rt_readback(final) failed: %s\n", pipes[0]->last_error()); exit_code = 1; }
         }
+        uint32_t acc_frames = 0, acc_samples = 0;   // what the last frame's lighting holds (spp without --accumulate)
+        if (rt_get_accumulation(pipes[0]->context(), &acc_frames, &acc_samples) != RT_OK) exit_code = 1;
         const double ms = total_ms / frames;
         std::printf("{\"binary\": \"rt_bench\", \"config\": {\"width\": %d, \"height\": %d, \"spp\": %d, \"depth\": %d, \"gpus\": %d, "
                     "\"gather\": \"%s\", \"post_passes\": %s, \"pose\": [%g, %g, %g, %g, %g], \"sun_angle\": %g}, \"frames\": %d, \"rays_per_frame\": %llu, "
                     "\"ms_per_frame\": %.4f, \"avg_ms_last_120\": %.4f, \"max_ms_last_120\": %.4f, \"mrays_per_s\": %.2f, "
-                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu}\n",
+                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"samples\": %u}\n",
                     width, height, spp, depth, gpus, gather ? (overlap ? "rccl-overlapped" : "rccl-serial") : "none", post ? "true" : "false",
                     game.camera.origin[0], game.camera.origin[1], game.camera.origin[2], game.camera.heading, game.camera.pitch,
-                    game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum);
+                    game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum,
+                    accumulate ? "true" : "false", acc_samples);
     }
     for (int g = 0; g < gpus; g++) {
         if (comms[(size_t)g]) rt_comm_destroy(comms[(size_t)g]);

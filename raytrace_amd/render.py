@@ -243,6 +243,16 @@ class Context:
     def reset_counters(self):
         self._check(self._lib.rt_reset_counters(self._h))
 
+    def reset_accumulation(self):
+        """rt_reset_accumulation: the next frame of an RT_FLAG_ACCUMULATE context starts its running sum from zero."""
+        self._check(self._lib.rt_reset_accumulation(self._h))
+
+    def accumulation(self):
+        """rt_get_accumulation: (frames, samples) the lighting planes of the frame drawn last hold (host-side state, no wait)."""
+        frames, samples = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.rt_get_accumulation(self._h, C.byref(frames), C.byref(samples)))
+        return int(frames.value), int(samples.value)
+
     def info(self):
         i = RtInfo()
         i.struct_size = C.sizeof(RtInfo)

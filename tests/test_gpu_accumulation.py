@@ -1,0 +1,297 @@
+"""Progressive accumulation (RT_FLAG_ACCUMULATE) on the GPU.  K frames of M samples with seeds s, s + M, s + 2M, ... drawn while
+the camera holds still ARE, by the definition of RtConfig.spp, the frame of K*M samples with seed s: every comparison here is
+against the oracle's frame of that many samples, on all nine planes, bit for bit.  What resets the accumulation (a live uniform
+other than seed, an upload, rt_reset_accumulation) makes the next frame the oracle's single frame again."""
+import numpy as np
+import pytest
+
+from raytrace_amd import abi, render, tiles
+from oracle import pyoracle as po
+
+pytestmark = pytest.mark.gpu
+
+W, H, DEPTH = 104, 56, 4          # a partial tile in x and y
+ACC = abi.RT_FLAG_ACCUMULATE
+CACHE = abi.RT_FLAG_CACHE_PRIMARY
+SEED0 = abi.NOISE_BYTES - 5       # runs of frames cross the RT_NOISE_BYTES wrap
+POSE = dict(origin=(-30.0, -128.0, 100.0), heading=np.pi / 2, pitch=-0.02, sun_angle=0.3, lr=(0, 0, 0))
+
+
+def _u(seed, **kw):
+    p = dict(POSE)
+    p.update(kw)
+    return po.camera_uniforms(p["origin"], p["heading"], p["pitch"], p["sun_angle"], seed % abi.NOISE_BYTES, p["lr"])
+
+
+_oracle_cache = {}
+
+
+def _oracle(region, noise, u, spp, depth=DEPTH, W=W, H=H, r=256):
+    key = (bytes(u), spp, depth, W, H, r)
+    if key not in _oracle_cache:
+        mats, mine = region
+        _oracle_cache[key] = po.render(mats, mine, noise, u, W, H, spp, depth, region=r)
+    return _oracle_cache[key]
+
+
+def _same(gpu, cpu, what=""):
+    for name in cpu:
+        assert np.array_equal(gpu[name], cpu[name], equal_nan=True), "%s: plane %s differs at %d values" % (
+            what, name, int(np.count_nonzero(gpu[name] != cpu[name])))
+
+
+def _ctx(scene, noise, spp, kernel=abi.RT_KERNEL_DEFAULT, flags=ACC | CACHE, depth=DEPTH, W=W, H=H, **kw):
+    ctx = render.Context(render.make_config(W, H, spp=spp, depth=depth, kernel=kernel, flags=flags, **kw))
+    ctx.upload_world(*scene)
+    ctx.upload_noise(noise)
+    return ctx
+
+
+def _accumulate(ctx, spp, K, seed0=SEED0, check_counts=True, **pose):
+    for k in range(K):
+        ctx.draw_frame(_u(seed0 + k * spp, **pose))
+        if check_counts:
+            assert ctx.accumulation() == (k + 1, (k + 1) * spp)
+
+
+KERNEL_FLAGS = [(abi.RT_KERNEL_DEFAULT, ACC | CACHE), (abi.RT_KERNEL_DEFAULT, ACC), (abi.RT_KERNEL_FRAME, ACC | CACHE),
+                (abi.RT_KERNEL_FRAME, ACC), (abi.RT_KERNEL_PATHS, ACC | CACHE), (abi.RT_KERNEL_PATHS, ACC),
+                (abi.RT_KERNEL_PERSISTENT, ACC | CACHE), (abi.RT_KERNEL_PERSISTENT, ACC)]
+
+
+@pytest.mark.parametrize("spp,K", [(1, 6), (3, 4)])
+@pytest.mark.parametrize("kernel,flags", KERNEL_FLAGS)
+def test_k_frames_of_m_samples_are_the_frame_of_k_times_m(procedural_region, blue_noise, kernel, flags, spp, K):
+    with _ctx(procedural_region, blue_noise, spp, kernel, flags) as ctx:
+        _accumulate(ctx, spp, 1)
+        ctx.sync()
+        _same(ctx.readback_all(), _oracle(procedural_region, blue_noise, _u(SEED0), spp)[0], "first frame")
+        _accumulate(ctx, spp, K - 1, seed0=SEED0 + spp, check_counts=False)
+        assert ctx.accumulation() == (K, K * spp)
+        ctx.sync()
+        got = ctx.readback_all()
+    _same(got, _oracle(procedural_region, blue_noise, _u(SEED0), K * spp)[0], "after %d frames" % K)
+
+
+@pytest.mark.parametrize("kernel,flags", [(abi.RT_KERNEL_DEFAULT, ACC | CACHE), (abi.RT_KERNEL_PATHS, ACC | CACHE),
+                                          (abi.RT_KERNEL_PERSISTENT, ACC)])
+def test_sample_batches_on_two_lanes(procedural_region, blue_noise, kernel, flags, monkeypatch):
+    """RT_PERSIST_BATCH=2: every frame of 5 samples is three launches (2 + 2 + 1) alternating between the lanes."""
+    monkeypatch.setenv("RT_PERSIST_BATCH", "2")
+    spp, K = 5, 3
+    with _ctx(procedural_region, blue_noise, spp, kernel, flags) as ctx:
+        assert ctx.info().samples_per_launch == 2
+        _accumulate(ctx, spp, K)
+        ctx.sync()
+        got = ctx.readback_all()
+    _same(got, _oracle(procedural_region, blue_noise, _u(SEED0), K * spp)[0])
+
+
+@pytest.fixture(scope="module")
+def region512(native_built):
+    from raytrace_amd import world
+    return world.generate_region(world.DEFAULT_SEED, region=512)
+
+
+@pytest.mark.parametrize("spp,K", [(1, 4), (2, 3)])
+def test_region_512_with_a_rotation(region512, blue_noise, spp, K):
+    lr = (1, -2, 0)
+    w, h = 64, 40
+    with _ctx(region512, blue_noise, spp, W=w, H=h, region=512) as ctx:
+        _accumulate(ctx, spp, K, lr=lr)
+        ctx.sync()
+        got = ctx.readback_all()
+    _same(got, _oracle(region512, blue_noise, _u(SEED0, lr=lr), K * spp, W=w, H=h, r=512)[0])
+
+
+RESETS = ["origin", "forward", "sun_angle", "lr", "upload_slice", "upload_world", "upload_noise", "reset"]
+
+
+@pytest.mark.parametrize("spp", [1, 2])
+@pytest.mark.parametrize("what", RESETS)
+def test_what_restarts_the_accumulation(procedural_region, blue_noise, what, spp):
+    mats, mine = procedural_region
+    pose = {}
+    with _ctx(procedural_region, blue_noise, spp) as ctx:
+        _accumulate(ctx, spp, 2)
+        if what == "origin":
+            pose = dict(origin=(-29.0, -128.0, 100.0))
+        elif what == "forward":
+            pose = dict(heading=np.pi / 2 + 0.05)
+        elif what == "sun_angle":
+            pose = dict(sun_angle=0.7)
+        elif what == "lr":
+            pose = dict(lr=(0, 1, 0))
+        elif what == "upload_slice":
+            ctx.upload_slice(2, 128, mats[128:144], mine[128:144])     # the same voxels: the world does not change
+        elif what == "upload_world":
+            ctx.upload_world(mats, mine)
+        elif what == "upload_noise":
+            ctx.upload_noise(blue_noise)
+        else:
+            ctx.reset_accumulation()
+        u = _u(SEED0 + 2 * spp, **pose)
+        ctx.draw_frame(u)
+        assert ctx.accumulation() == (1, spp)
+        ctx.sync()
+        got = ctx.readback_all()
+        _same(got, _oracle(procedural_region, blue_noise, u, spp)[0], "after %s" % what)
+        # ... and the accumulation goes on from there
+        ctx.draw_frame(_u(SEED0 + 3 * spp, **pose))
+        assert ctx.accumulation() == (2, 2 * spp)
+        ctx.sync()
+        got = ctx.readback_all()
+    _same(got, _oracle(procedural_region, blue_noise, u, 2 * spp)[0], "second frame after %s" % what)
+
+
+@pytest.mark.parametrize("spp", [1, 2])
+def test_seed_and_dead_fields_do_not_restart_it(procedural_region, blue_noise, spp):
+    with _ctx(procedural_region, blue_noise, spp) as ctx:
+        _accumulate(ctx, spp, 2)
+        u = _u(SEED0 + 2 * spp)
+        u.old_origin[0] = 5.0
+        u.old_transform_c1[2] = -1.0
+        u.region_offset[1] = 64
+        u.lso[0] = -64
+        ctx.draw_frame(u)
+        assert ctx.accumulation() == (3, 3 * spp)
+        ctx.sync()
+        got = ctx.readback_all()
+        _same(got, _oracle(procedural_region, blue_noise, _u(SEED0), 3 * spp)[0])
+        ctx.draw_frame(_u(12345))                       # a seed the host did not advance by spp: still the same accumulation
+        assert ctx.accumulation() == (4, 4 * spp)
+
+
+def test_samples_stop_at_two_to_the_24(procedural_region, blue_noise):
+    """The fp32 divisor stays exact: a frame that would take the count past 2^24 starts a new accumulation (spp 2^20, the
+    largest rt_create takes, on one tile at depth 0: sixteen frames reach 2^24)."""
+    spp = 1 << 20
+    with render.Context(render.make_config(8, 8, spp=spp, depth=0, flags=ACC | CACHE)) as ctx:
+        ctx.upload_world(*procedural_region)
+        ctx.upload_noise(blue_noise)
+        for k in range(16):
+            ctx.draw_frame(_u(SEED0))
+            assert ctx.accumulation() == (k + 1, (k + 1) * spp)
+        ctx.draw_frame(_u(SEED0))
+        assert ctx.accumulation() == (1, spp)
+        ctx.sync()
+
+
+def _peek(ptrs, W, H):
+    """Planes behind device pointers captured earlier (the slot of a frame that is no longer the context's current one)."""
+    import torch
+    import bench
+    out = {}
+    for b, ptr in ptrs.items():
+        dt, ch = abi.BUFFER_FORMATS[b]
+        n = W * H * ch * np.dtype(dt).itemsize
+        raw = torch.as_tensor(bench._DevArray(ptr, n), device=torch.device("cuda", 0)).cpu().numpy()
+        out[abi.BUFFER_NAMES[b]] = raw.view(dt).reshape((H, W, ch) if ch > 1 else (H, W))
+    return out
+
+
+@pytest.mark.parametrize("spp", [1, 3])
+@pytest.mark.parametrize("kernel", [abi.RT_KERNEL_DEFAULT, abi.RT_KERNEL_PATHS, abi.RT_KERNEL_PERSISTENT])
+def test_two_frames_in_flight_share_the_sums(procedural_region, blue_noise, kernel, spp):
+    """Six frames enqueued without a wait into two frame slots: the slot drawn last holds 6 * spp samples, the other 5 * spp."""
+    with _ctx(procedural_region, blue_noise, spp, kernel, ACC | CACHE | abi.RT_FLAG_FRAMES_IN_FLIGHT_2) as ctx:
+        assert ctx.info().frames_in_flight == 2
+        seen = []
+        for k in range(6):
+            ctx.draw_frame(_u(SEED0 + k * spp))
+            seen.append({b: ctx.device_ptr(b) for b in range(abi.RT_BUF_FINAL_BGRA8)})
+        assert ctx.accumulation() == (6, 6 * spp)
+        ctx.sync()
+        assert seen[4] != seen[5]
+        last = ctx.readback_all()
+        before = _peek(seen[4], W, H)
+    _same(last, _oracle(procedural_region, blue_noise, _u(SEED0), 6 * spp)[0], "last slot")
+    _same(before, _oracle(procedural_region, blue_noise, _u(SEED0), 5 * spp)[0], "other slot")
+
+
+@pytest.mark.parametrize("spp", [1, 2])
+def test_caller_stream_part_way(procedural_region, blue_noise, spp):
+    import torch
+    s = torch.cuda.Stream(device=0)
+    with _ctx(procedural_region, blue_noise, spp) as ctx:
+        _accumulate(ctx, spp, 2)
+        ctx.set_stream(s.cuda_stream)
+        _accumulate(ctx, spp, 2, seed0=SEED0 + 2 * spp, check_counts=False)
+        ctx.set_stream(0)
+        _accumulate(ctx, spp, 2, seed0=SEED0 + 4 * spp, check_counts=False)
+        assert ctx.accumulation() == (6, 6 * spp)
+        ctx.sync()
+        got = ctx.readback_all()
+    _same(got, _oracle(procedural_region, blue_noise, _u(SEED0), 6 * spp)[0])
+
+
+@pytest.mark.parametrize("spp", [1, 2])
+def test_post_passes_between_frames_leave_the_sums_alone(procedural_region, blue_noise, spp):
+    with _ctx(procedural_region, blue_noise, spp) as ctx:
+        for k in range(4):
+            ctx.draw_frame(_u(SEED0 + k * spp))
+            ctx.denoise(True)
+            ctx.finalize()
+        _accumulate(ctx, spp, 1, seed0=SEED0 + 4 * spp, check_counts=False)
+        ctx.sync()
+        got = ctx.readback_all()
+    _same(got, _oracle(procedural_region, blue_noise, _u(SEED0), 5 * spp)[0])
+
+
+@pytest.mark.parametrize("spp", [1, 2])
+def test_counters_are_each_frames_own(procedural_region, blue_noise, spp):
+    """Without a primary cache the counters equal the oracle's exactly: every frame's are those of its own seed and spp."""
+    with _ctx(procedural_region, blue_noise, spp, abi.RT_KERNEL_PERSISTENT, ACC | abi.RT_FLAG_COUNTERS) as ctx:
+        for k in range(3):
+            ctx.reset_counters()
+            u = _u(SEED0 + k * spp)
+            ctx.draw_frame(u)
+            ctx.sync()
+            assert ctx.counters().as_dict() == _oracle(procedural_region, blue_noise, u, spp)[1].as_dict(), k
+        got = ctx.readback_all()
+    _same(got, _oracle(procedural_region, blue_noise, _u(SEED0), 3 * spp)[0])
+
+
+@pytest.mark.parametrize("spp,K", [(1, 4), (2, 3)])
+def test_tile_split_contexts_accumulate_their_own_tiles(procedural_region, blue_noise, spp, K):
+    cpu = _oracle(procedural_region, blue_noise, _u(SEED0), K * spp)[0]
+    world_ = 2
+    for rank in range(world_):
+        with _ctx(procedural_region, blue_noise, spp, tile_rank=rank, tile_world=world_) as ctx:
+            _accumulate(ctx, spp, K)
+            ctx.sync()
+            got = ctx.readback_all()
+        n = tiles.tile_count(W, H, rank, world_) * 64
+        inside = tiles.tile_major_from_frame(np.ones((H, W), dtype=np.uint8), rank, world_)[:n].astype(bool)
+        for name in cpu:
+            exp = tiles.tile_major_from_frame(cpu[name], rank, world_)
+            px = got[name].reshape((-1,) + exp.shape[1:])[:n]
+            assert np.array_equal(px[inside], exp[:n][inside], equal_nan=True), (name, rank)
+
+
+@pytest.mark.parametrize("kernel", [abi.RT_KERNEL_MEGA, abi.RT_KERNEL_WAVEFRONT])
+def test_baselines_reject_the_flag(kernel):
+    with pytest.raises(render.RtError) as ei:
+        render.Context(render.make_config(64, 64, kernel=kernel, flags=ACC))
+    assert ei.value.code == abi.RT_ERR_UNIMPLEMENTED
+
+
+@pytest.mark.parametrize("spp", [1, 3])
+def test_without_the_flag_every_frame_stands_alone(procedural_region, blue_noise, spp):
+    with _ctx(procedural_region, blue_noise, spp, flags=CACHE) as ctx:
+        assert ctx.accumulation() == (0, 0)
+        for k in range(3):
+            u = _u(SEED0 + k * spp)
+            ctx.draw_frame(u)
+            assert ctx.accumulation() == (1, spp)
+        ctx.sync()
+        got = ctx.readback_all()
+    _same(got, _oracle(procedural_region, blue_noise, u, spp)[0])
+
+
+def test_accumulation_is_zero_before_the_first_frame(procedural_region, blue_noise):
+    with _ctx(procedural_region, blue_noise, 2) as ctx:
+        assert ctx.accumulation() == (0, 0)
+        inf = ctx.info()
+    with _ctx(procedural_region, blue_noise, 2, flags=CACHE) as plain:
+        assert inf.device_bytes - plain.info().device_bytes == ((W + 7) // 8) * ((H + 7) // 8) * 64 * 16
