@@ -133,7 +133,7 @@ typedef enum RtKernel {
                                        of samples it holds.  A frame CONTINUES the accumulation when a frame was drawn before and its
                                        live uniforms other than seed (sun_angle, origin, forward, up, right, lr) are bitwise equal to
                                        that frame's, none of rt_upload_world / rt_upload_slice / rt_upload_noise / rt_reset_accumulation
-                                       was called since, and samples + spp <= 2^24; otherwise it starts from zero and is bit-identical to
+                                       / rt_edit_voxels (count > 0) was called since, and samples + spp <= 2^24; otherwise it starts from zero and is bit-identical to
                                        the same frame without the flag.  The dead uniform fields are ignored and seed is not checked: a
                                        host that advances seed by spp per frame (mod RT_NOISE_BYTES; spp 1: the reference's own +1)
                                        gets after K frames of spp samples exactly the frame of K x spp samples from the first seed
@@ -277,6 +277,42 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset,
  * (the call waits until the slab before last has left the buffer); it must not be touched afterwards and is freed by rt_destroy. */
 int rt_slice_staging(RtContext* ctx, uint32_t** materials, uint8_t** minefield);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Sparse voxel edits: a game that places and breaks blocks.  One
+ * record per edited voxel, 16 bytes: */
+typedef struct RtVoxelEdit {
+    uint16_t x, y, z;             /* texel coordinates, < R (the space of rt_upload_slice's texel_offset: texel = world + R/2)  */
+    uint16_t solid;               /* 1: the voxel is occupied (minefield 0); 0: air (any other non-zero value counts as 1)      */
+    uint32_t material;            /* packed material word written to the voxel as is                                            */
+    uint32_t reserved;            /* must be 0                                                                                  */
+} RtVoxelEdit;
+/* rt_edit_voxels — change `count` voxels of the resident region (the reference has no editing: it repacks whole chunks,
+ * src/world/chunk.rs:125-184, and uploads slabs).
+ *   Materials: each edited voxel gets the edit's `material` word.  Duplicates within one call are resolved by batch order: the
+ *     last edit of a voxel wins.  No other material word changes.
+ *   Minefield: each 64^3 chunk (texel-aligned) that holds at least one edit gets its whole minefield rebuilt with pack_into's
+ *     rule.  Occupancy of an edited voxel is its `solid` field; for every other voxel it is "current minefield value == 0", the
+ *     shader's hit test (raytrace.comp:146).  An occupied voxel gets 0; any other voxel gets the first level L in 1..6 whose
+ *     aligned 2^L cube inside the chunk is occupied; a chunk with nothing occupied gets 6 everywhere.  Chunks without an edit are
+ *     not touched: on a world that was not built by pack_into (arbitrary minefield values 0..30) the edited chunks become
+ *     pack_into-consistent and the other chunks keep their values.
+ *   Nibble maps: the coarse and (R > 256) brick nibble-map words that cover the touched chunks are rebuilt; the other words stay.
+ *   Validation: everything is checked on the host before anything is enqueued.  A coordinate >= R, reserved != 0 or count > 2^24
+ *     returns RT_ERR_INVALID_ARG and changes nothing.  No world resident (rt_upload_world not called): RT_ERR_NOT_READY.
+ *     count == 0 is a no-op (edits may then be NULL) and does not reset the accumulation.
+ *   Ordering: asynchronous and stream-ordered like rt_upload_slice.  Frames already submitted read the old region; later frames,
+ *     on every lane and frame slot and on a stream set with rt_set_stream, read the new one.  Edits and slabs apply in call order.
+ *     The caller's array is free once the call returns: the binned batch is staged in pinned memory (two staging sets used in
+ *     turn, grown when a batch needs more; the call waits on the host only until the batch before last has left its set).
+ *   Accumulation: a call with count > 0 resets RT_FLAG_ACCUMULATE's running sum, as the uploads do.
+ * Device work per call: one launch that scatters the material words and rebuilds the touched chunks (one workgroup per chunk), one
+ * that rebuilds their nibble-map words (counted by RT_FLAG_TIMING_ALL). */
+int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count);
+/* Un-tile the box [x0, x0 + ex) x [y0, y0 + ey) x [z0, z0 + ez) of the resident region (texel coordinates) into the caller's layout:
+ * materials u32[ex ey ez], minefield u8[ex ey ez], x fastest; either pointer may be NULL.  Waits for everything submitted before
+ * (the region as the next frame would see it), then synchronises.  A box outside the region (or an extent < 1) returns
+ * RT_ERR_INVALID_ARG; no world resident: RT_ERR_NOT_READY.  For tests and for a host that saves an edited world. */
+int rt_read_box(RtContext* ctx, int x0, int y0, int z0, int ex, int ey, int ez, uint32_t* materials, uint8_t* minefield);
+
 /* Allocation figures of the context (see RtInfo). */
 int rt_get_info(RtContext* ctx, RtInfo* out);
 
@@ -381,6 +417,9 @@ int rt_kernel_in_use(RtContext* ctx);
  * (bilateral_denoise.comp:31) with a reciprocal and one residual correction; *result = number of quotients, over the complete
  * domain of that expression (37 weights x 131072 denominators), that differ from IEEE division on this device (expected 0). */
 #define RT_SELFTEST_DENOISE_DIVISION 1
+/* (ABI 1.3, additive) RT_SELFTEST_SCENE_MAPS: rebuilds every word of the coarse nibble map (and of the brick map above R = 256) from the
+ * resident minefield; *result = number of words that differ from the resident maps (expected 0; RT_ERR_NOT_READY without a world). */
+#define RT_SELFTEST_SCENE_MAPS 2
 int rt_selftest(RtContext* ctx, int which, uint64_t* result);
 
 /* (ABI 1.3, additive; hosts detect the feature by this symbol) RT_FLAG_ACCUMULATE: the next rt_draw_frame starts the running sum
@@ -410,7 +449,8 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        streams of the library (results unchanged; rt_set_stream(non-NULL) keeps everything on the caller's stream).
  *   1.3  round 4: RtKernel value 7 (RT_KERNEL_FRAME); RT_KERNEL_DEFAULT runs frames with little work on it (rt_kernel_in_use tells);
  *        results unchanged.
- *        Additive, same minor version: RT_FLAG_ACCUMULATE, rt_reset_accumulation, rt_get_accumulation (progressive accumulation). */
+ *        Additive, same minor version: RT_FLAG_ACCUMULATE, rt_reset_accumulation, rt_get_accumulation (progressive accumulation).
+ *        Additive, same minor version: RtVoxelEdit, rt_edit_voxels, rt_read_box, RT_SELFTEST_SCENE_MAPS (sparse voxel edits). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

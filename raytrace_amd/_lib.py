@@ -3,7 +3,7 @@ import fails loudly (build it with `python -m raytrace_amd.build`)."""
 import ctypes as C
 import os
 
-from .abi import RtConfig, RtCounters, RtInfo, RtTiming, RtUniforms
+from .abi import RtConfig, RtCounters, RtInfo, RtTiming, RtUniforms, RtVoxelEdit
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_AMD_LIB: load another build of the same library (same-box A/B timing of two kernel variants, tools/ab.sh)
@@ -19,7 +19,7 @@ ABI_SYMBOLS = (
     "rt_abi_version",
     "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer", "rt_frame_ptr",
     "rt_frame_readback", "rt_selftest", "rt_get_info", "rt_samples_per_launch", "rt_get_gather_timing",
-    "rt_reset_accumulation", "rt_get_accumulation",
+    "rt_reset_accumulation", "rt_get_accumulation", "rt_edit_voxels", "rt_read_box",
 )
 
 _amd = None
@@ -100,6 +100,10 @@ def amd():
         lib.rt_reset_accumulation.restype = C.c_int
         lib.rt_get_accumulation.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.rt_get_accumulation.restype = C.c_int
+        lib.rt_edit_voxels.argtypes = [P, C.POINTER(RtVoxelEdit), C.c_uint32]
+        lib.rt_edit_voxels.restype = C.c_int
+        lib.rt_read_box.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]
+        lib.rt_read_box.restype = C.c_int
         for name in ("rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer"):
             getattr(lib, name).restype = C.c_int
         for name in ("rt_upload_world", "rt_upload_slice", "rt_slice_staging", "rt_upload_noise", "rt_draw_frame", "rt_sync", "rt_readback",

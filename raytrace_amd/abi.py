@@ -24,6 +24,8 @@ RT_KERNEL_DEFAULT, RT_KERNEL_MEGA, RT_KERNEL_WAVEFRONT, RT_KERNEL_PERSISTENT, RT
 RT_FLAG_FRAMES_IN_FLIGHT_2 = 0x20
 RT_FLAG_ACCUMULATE = 0x40     # ABI 1.3, additive: progressive accumulation while the camera holds still
 RT_FLAG_COUNTERS = 0x1
+RT_SELFTEST_DENOISE_DIVISION = 1
+RT_SELFTEST_SCENE_MAPS = 2    # ABI 1.3, additive: rebuild the nibble maps from the resident minefield, count differing words
 RT_FLAG_CACHE_PRIMARY = 0x2
 RT_FLAG_TIMING = 0x4
 RT_FLAG_TIMING_ALL = 0xC
@@ -103,3 +105,12 @@ class RtInfo(C.Structure):
 class RtTiming(C.Structure):
     _fields_ = [("frame_ms", C.c_float), ("trace_ms", C.c_float), ("shade_ms", C.c_float),
                 ("trace_launches", C.c_uint32), ("other_launches", C.c_uint32), ("rays_traced", C.c_uint64)]
+
+
+class RtVoxelEdit(C.Structure):
+    """rt_edit_voxels record (ABI 1.3, additive): one edited voxel, 16 bytes."""
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("z", C.c_uint16), ("solid", C.c_uint16), ("material", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RtVoxelEdit) == 16

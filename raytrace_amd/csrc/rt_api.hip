@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is dlopen'ed on first use (rt_comm_* / rt_gather_gbuffer)
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -99,6 +100,15 @@ struct RtContext {
     hipStream_t upload_stream = nullptr;
     hipEvent_t ev_slab_copied[2] = {nullptr, nullptr}, ev_slab_applied[2] = {nullptr, nullptr};   // per set: host staging read / device staging consumed
     bool slab_copy_pending[2] = {false, false}, slab_apply_recorded[2] = {false, false};
+    // rt_edit_voxels: a binned batch (touched chunks, per-chunk edit ranges, records) travels pinned host staging -> device staging
+    // (upload stream) -> k_rebuild_chunks (render stream), like a slab; two staging sets used in turn, grown when a batch needs more
+    uint8_t* h_edit[2] = {nullptr, nullptr}; uint8_t* d_edit[2] = {nullptr, nullptr};   // hipHostMalloc / hipMalloc
+    size_t edit_cap[2] = {0, 0};
+    uint64_t edit_batches = 0;            // batches submitted: the next one uses set edit_batches & 1
+    hipEvent_t ev_edit_copied[2] = {nullptr, nullptr}, ev_edit_applied[2] = {nullptr, nullptr};
+    bool edit_copy_pending[2] = {false, false}, edit_apply_recorded[2] = {false, false};
+    std::vector<uint32_t> edit_chunk, edit_order, edit_start, edit_stamp;   // host binning scratch, kept between calls
+    uint32_t edit_gen = 0;                // edit_stamp generation: a voxel's slot holds the generation of the chunk run that kept it
 
     // tiling
     int tiles_x = 0, tiles_y = 0, ntiles_total = 0, ntiles_local = 0, tile_capacity = 0;
@@ -648,6 +658,12 @@ void rt_destroy(RtContext* ctx) {
     for (hipEvent_t e : {ctx->ev_fence, ctx->ev_gather, ctx->ev_accum}) if (e) (void)hipEventDestroy(e);
     if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); (void)hipStreamDestroy(ctx->upload_stream); }
     for (int k = 0; k < 2; k++) {
+        if (ctx->ev_edit_copied[k]) (void)hipEventDestroy(ctx->ev_edit_copied[k]);
+        if (ctx->ev_edit_applied[k]) (void)hipEventDestroy(ctx->ev_edit_applied[k]);
+        if (ctx->h_edit[k]) (void)hipHostFree(ctx->h_edit[k]);
+        if (ctx->d_edit[k]) (void)hipFree(ctx->d_edit[k]);
+    }
+    for (int k = 0; k < 2; k++) {
         if (ctx->ev_slab_copied[k]) (void)hipEventDestroy(ctx->ev_slab_copied[k]);
         if (ctx->ev_slab_applied[k]) (void)hipEventDestroy(ctx->ev_slab_applied[k]);
         if (ctx->h_slab_mat[k]) (void)hipHostFree(ctx->h_slab_mat[k]);
@@ -783,6 +799,143 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
     RT_HIP(ctx, hipEventRecord(ctx->ev_slab_applied[k], ctx->stream));
     ctx->slab_apply_recorded[k] = true;
     RT_HIP(ctx, fence_lanes_after(ctx, ctx->stream));   // ... and later frames, whichever lane they start on, see the slab
+    return RT_OK;
+}
+
+namespace {
+size_t align16(size_t n) { return (n + 15u) & ~(size_t)15u; }
+}  // namespace
+
+int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (count > (1u << 24)) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_voxels: more than 2^24 edits in one call; nothing was applied");
+    if (count == 0) return RT_OK;
+    if (!edits) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_voxels: null edits");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_edit_voxels: upload the full region first");
+    // Binning on the host, all of it before anything is enqueued: validate every edit, then one stable counting pass by chunk.
+    const uint32_t R = (uint32_t)ctx->region;
+    const int nl = ctx->logr - 6;
+    const uint32_t nchunks = 1u << (3 * nl);
+    std::vector<uint32_t>& chunk = ctx->edit_chunk;
+    std::vector<uint32_t>& start = ctx->edit_start;
+    chunk.resize(count);
+    start.assign((size_t)nchunks + 1u, 0u);
+    for (uint32_t i = 0; i < count; i++) {
+        const RtVoxelEdit& e = edits[i];
+        if (e.x >= R || e.y >= R || e.z >= R || e.reserved != 0u)
+            return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_voxels: edit " + std::to_string(i) +
+                                                     " has a coordinate outside the region or reserved != 0; nothing was applied");
+        const uint32_t c = ((uint32_t)(e.z >> 6) << (2 * nl)) | ((uint32_t)(e.y >> 6) << nl) | (uint32_t)(e.x >> 6);
+        chunk[i] = c;
+        start[c + 1u]++;
+    }
+    uint32_t touched = 0;
+    for (uint32_t c = 0; c < nchunks; c++) { touched += start[c + 1u] != 0u; start[c + 1u] += start[c]; }
+    std::vector<uint32_t>& order = ctx->edit_order;   // edit indices grouped by chunk, batch order within a chunk
+    order.resize(count);
+    for (uint32_t i = 0; i < count; i++) order[start[chunk[i]]++] = i;   // afterwards start[c] = end of chunk c's range
+    const size_t off_offs = align16((size_t)touched * 4u), off_recs = off_offs + align16(((size_t)touched + 1u) * 4u);
+    const size_t need = off_recs + (size_t)count * 8u;
+
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->upload_stream) RT_HIP(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
+    const int k = (int)(ctx->edit_batches & 1u);
+    for (hipEvent_t* ev : {&ctx->ev_edit_copied[k], &ctx->ev_edit_applied[k]})
+        if (!*ev) RT_HIP(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    if (ctx->edit_copy_pending[k]) { RT_HIP(ctx, hipEventSynchronize(ctx->ev_edit_copied[k])); ctx->edit_copy_pending[k] = false; }   // the batch before last has left it
+    if (need > ctx->edit_cap[k]) {   // grow the set: its device twin may still be read by the batch before last's rebuild
+        if (ctx->edit_apply_recorded[k]) RT_HIP(ctx, hipEventSynchronize(ctx->ev_edit_applied[k]));
+        if (ctx->h_edit[k]) { (void)hipHostFree(ctx->h_edit[k]); ctx->h_edit[k] = nullptr; }
+        if (ctx->d_edit[k]) { (void)hipFree(ctx->d_edit[k]); ctx->d_edit[k] = nullptr; }
+        ctx->edit_cap[k] = 0;
+        size_t cap = need < ((size_t)64 << 10) ? ((size_t)64 << 10) : need;
+        if (cap < need + need / 2u) cap = align16(need + need / 2u);
+        RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_edit[k], cap, hipHostMallocDefault));
+        RT_HIP(ctx, hipMalloc((void**)&ctx->d_edit[k], cap));
+        ctx->edit_cap[k] = cap;
+    }
+    // Staging: touched chunk ids, their edit ranges, and per chunk one record per edited voxel — its last edit in the batch (the
+    // range is walked backwards; edit_stamp marks the voxels a chunk's run has kept).
+    uint8_t* h = ctx->h_edit[k];
+    uint32_t* h_chunks = reinterpret_cast<uint32_t*>(h);
+    uint32_t* h_offs = reinterpret_cast<uint32_t*>(h + off_offs);
+    uint32_t* h_recs = reinterpret_cast<uint32_t*>(h + off_recs);
+    std::vector<uint32_t>& stamp = ctx->edit_stamp;
+    if (stamp.size() != (size_t)RT_CHUNK_SIZE * RT_CHUNK_SIZE * RT_CHUNK_SIZE) stamp.assign((size_t)RT_CHUNK_SIZE * RT_CHUNK_SIZE * RT_CHUNK_SIZE, 0u);
+    uint32_t t = 0, nrec = 0;
+    for (uint32_t c = 0; c < nchunks; c++) {
+        const uint32_t b = c ? start[c - 1u] : 0u, e = start[c];
+        if (b == e) continue;
+        if (++ctx->edit_gen == 0u) { std::fill(stamp.begin(), stamp.end(), 0u); ctx->edit_gen = 1u; }
+        const uint32_t gen = ctx->edit_gen;
+        h_chunks[t] = c;
+        h_offs[t++] = nrec;
+        for (uint32_t j = e; j-- > b;) {
+            const RtVoxelEdit& ed = edits[order[j]];
+            const uint32_t local = ((uint32_t)(ed.z & 63u) << 12) | ((uint32_t)(ed.y & 63u) << 6) | (uint32_t)(ed.x & 63u);
+            if (stamp[local] == gen) continue;
+            stamp[local] = gen;
+            h_recs[2u * nrec] = local | (ed.solid ? 1u << 18 : 0u);
+            h_recs[2u * nrec + 1u] = ed.material;
+            nrec++;
+        }
+    }
+    h_offs[t] = nrec;
+    // Transfer on the upload stream, then the rebuild on the render stream after the frames already submitted (every lane), and
+    // later frames after the rebuild — the ordering of rt_upload_slice.
+    if (ctx->edit_apply_recorded[k]) RT_HIP(ctx, hipStreamWaitEvent(ctx->upload_stream, ctx->ev_edit_applied[k], 0));
+    RT_HIP(ctx, hipMemcpyAsync(ctx->d_edit[k], h, off_recs + (size_t)nrec * 8u, hipMemcpyHostToDevice, ctx->upload_stream));
+    RT_HIP(ctx, hipEventRecord(ctx->ev_edit_copied[k], ctx->upload_stream));
+    ctx->edit_copy_pending[k] = true;
+    ctx->edit_batches++;
+    ctx->accum_valid = false;
+    RT_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_edit_copied[k], 0));
+    RT_HIP(ctx, join_lanes_into(ctx, ctx->stream));
+    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(ctx->d_edit[k]);
+    const uint32_t* d_offs = reinterpret_cast<const uint32_t*>(ctx->d_edit[k] + off_offs);
+    const uint2* d_recs = reinterpret_cast<const uint2*>(ctx->d_edit[k] + off_recs);
+    {
+        LaunchTimer lt(ctx, 1);
+        RT_HIP(ctx, rtd::launch_rebuild_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, d_offs, d_recs, touched, ctx->logr, ctx->stream));
+    }
+    {
+        LaunchTimer lt(ctx, 1);
+        RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, touched, ctx->logr, ctx->stream));
+    }
+    RT_HIP(ctx, hipEventRecord(ctx->ev_edit_applied[k], ctx->stream));
+    ctx->edit_apply_recorded[k] = true;
+    RT_HIP(ctx, fence_lanes_after(ctx, ctx->stream));
+    return RT_OK;
+}
+
+int rt_read_box(RtContext* ctx, int x0, int y0, int z0, int ex, int ey, int ez, uint32_t* materials, uint8_t* minefield) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const int R = ctx->region;
+    if (x0 < 0 || y0 < 0 || z0 < 0 || ex < 1 || ey < 1 || ez < 1 || ex > R - x0 || ey > R - y0 || ez > R - z0)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_read_box: box outside the region");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_read_box: no region uploaded");
+    if (!materials && !minefield) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, sync_lanes(ctx));
+    // z-slabs of at most 2^24 voxels through a temporary device buffer (80 MiB)
+    const size_t plane = (size_t)ex * (size_t)ey;
+    const int nz = (int)(((size_t)1 << 24) / plane >= (size_t)ez ? (size_t)ez : (((size_t)1 << 24) / plane > 0 ? ((size_t)1 << 24) / plane : 1));
+    uint32_t* d_mat = nullptr; uint8_t* d_mine = nullptr;
+    hipError_t e = hipSuccess;
+    if (materials) e = hipMalloc((void**)&d_mat, plane * (size_t)nz * sizeof(uint32_t));
+    if (e == hipSuccess && minefield) e = hipMalloc((void**)&d_mine, plane * (size_t)nz);
+    for (int z = 0; z < ez && e == hipSuccess; z += nz) {
+        const int n = ez - z < nz ? ez - z : nz;
+        e = rtd::launch_read_box(ctx->d_mine_sw, ctx->d_mat_sw, ctx->logr, x0, y0, z0 + z, ex, ey, n, d_mat, d_mine, ctx->stream);
+        if (e == hipSuccess && materials)
+            e = hipMemcpyAsync(materials + plane * (size_t)z, d_mat, plane * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && minefield)
+            e = hipMemcpyAsync(minefield + plane * (size_t)z, d_mine, plane * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    if (d_mat) (void)hipFree(d_mat);
+    if (d_mine) (void)hipFree(d_mine);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_read_box: ") + hipGetErrorString(e));
     return RT_OK;
 }
 
@@ -1335,12 +1488,14 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls) {
 
 int rt_selftest(RtContext* ctx, int which, uint64_t* result) {
     if (!ctx || !result) return RT_ERR_INVALID_ARG;
-    if (which != RT_SELFTEST_DENOISE_DIVISION) return fail(ctx, RT_ERR_INVALID_ARG, "rt_selftest: unknown test");
+    if (which != RT_SELFTEST_DENOISE_DIVISION && which != RT_SELFTEST_SCENE_MAPS) return fail(ctx, RT_ERR_INVALID_ARG, "rt_selftest: unknown test");
+    if (which == RT_SELFTEST_SCENE_MAPS && !ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_selftest: no region uploaded");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->d_selftest) RT_HIP(ctx, dev_alloc(ctx, &ctx->d_selftest, 1));   // one word, allocated once
     unsigned long long* d = ctx->d_selftest;
     RT_HIP(ctx, hipMemsetAsync(d, 0, sizeof(*d), ctx->stream));
-    RT_HIP(ctx, rtd::launch_selftest_dn_div(d, ctx->stream));
+    if (which == RT_SELFTEST_DENOISE_DIVISION) RT_HIP(ctx, rtd::launch_selftest_dn_div(d, ctx->stream));
+    else RT_HIP(ctx, rtd::launch_check_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, ctx->logr, d, ctx->stream));
     unsigned long long h = 0;
     RT_HIP(ctx, hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));

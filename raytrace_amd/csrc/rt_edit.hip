@@ -1,0 +1,298 @@
+// rt_edit.hip — gfx950 kernels of rt_edit_voxels, rt_read_box and rt_selftest(RT_SELFTEST_SCENE_MAPS).
+//
+//   k_rebuild_chunks   : one workgroup per touched 64^3 chunk: scatters the chunk's edited material words, loads its occupancy
+//                        (minefield == 0) into an LDS bitmap, applies the edits' solid bits, builds the OR pyramid of levels 1..6
+//                        and writes the chunk's whole minefield back with pack_into's rule (src/world/chunk.rs:125-184)
+//   k_rebuild_chunk_maps: the coarse (and, above R = 256, brick) nibble-map words that cover the touched chunks
+//   k_check_maps       : recomputes every nibble-map word from the resident minefield and counts the ones that differ
+//   k_read_box         : un-tiles a box of the swizzled region into the caller's layout (x fastest)
+#include <hip/hip_runtime.h>
+
+#include "rt_device.hpp"
+#include "rt_kernels.hpp"
+
+namespace rtd {
+
+namespace {
+
+// Occupancy rows of level 0: row (z, y) of the chunk is 64 bits (x = bit), two dwords at 2 * (z * 65 + y).  The pad of one row per
+// z keeps the four z-layers a wave reads in the write-back pass (rows 65 * 2 dwords apart) on different banks.
+constexpr int kRow0Stride = 65;
+// Level 1 (32^3 cells of 2^3 voxels): row (Z, Y) is 32 bits at Z * 33 + Y.
+constexpr int kRow1Stride = 33;
+
+__device__ __forceinline__ uint64_t occ_row0(const uint32_t* occ0, int z, int y) {
+    const int w = 2 * (z * kRow0Stride + y);
+    return (uint64_t)occ0[w] | ((uint64_t)occ0[w + 1] << 32);
+}
+
+// bit X of the result = bit 2X | bit 2X + 1 of v (64 -> 32 bits)
+__device__ __forceinline__ uint32_t or_pairs64(uint64_t v) {
+    uint64_t t = (v | (v >> 1)) & 0x5555555555555555ull;
+    t = (t | (t >> 1)) & 0x3333333333333333ull;
+    t = (t | (t >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    t = (t | (t >> 4)) & 0x00FF00FF00FF00FFull;
+    t = (t | (t >> 8)) & 0x0000FFFF0000FFFFull;
+    t = (t | (t >> 16)) & 0x00000000FFFFFFFFull;
+    return (uint32_t)t;
+}
+
+// nibble of 64 bytes of the swizzled minefield (one 4^3 brick): the common value if all are equal and below 15, else 15
+__device__ __forceinline__ uint32_t brick_nibble(const uint8_t* mine_sw, size_t brick) {
+    const uint4* src = reinterpret_cast<const uint4*>(mine_sw + (brick << 6));
+    const uint4 a = src[0], q = src[1], d = src[2], e = src[3];
+    const uint32_t first = a.x & 0xFFu, splat = first * 0x01010101u;
+    const uint32_t diff = (a.x ^ splat) | (a.y ^ splat) | (a.z ^ splat) | (a.w ^ splat) | (q.x ^ splat) | (q.y ^ splat) |
+                          (q.z ^ splat) | (q.w ^ splat) | (d.x ^ splat) | (d.y ^ splat) | (d.z ^ splat) | (d.w ^ splat) |
+                          (e.x ^ splat) | (e.y ^ splat) | (e.z ^ splat) | (e.w ^ splat);
+    return (diff == 0u && first < kNibMixed) ? first : kNibMixed;
+}
+
+// Coarse nibble-map word w (8 x-adjacent cubes of edge R/64): the value k_build_coarse (rt_kernels.hip) stores there.
+__device__ uint32_t coarse_word(const uint8_t* mine_sw, uint32_t w, int logr) {
+    const int lb = logr - 2, sub = logr - 8;
+    const uint32_t nsub = 1u << sub;
+    uint32_t word = 0;
+    for (uint32_t b = 0; b < 8u; b++) {
+        const uint32_t c = w * 8u + b;
+        const uint32_t cx = c & 63u, cy = (c >> 6) & 63u, cz = c >> 12;
+        uint32_t nib = 0, first = 0;
+        bool mixed = false;
+        for (uint32_t bz = 0; bz < nsub && !mixed; bz++)
+            for (uint32_t by = 0; by < nsub && !mixed; by++)
+                for (uint32_t bx = 0; bx < nsub && !mixed; bx++) {
+                    const size_t brick = (((((size_t)(cz << sub) + bz) << lb) + ((cy << sub) + by)) << lb) + ((cx << sub) + bx);
+                    const uint32_t n = brick_nibble(mine_sw, brick);
+                    if ((bz | by | bx) == 0u) first = n;
+                    mixed = n == kNibMixed || n != first;
+                }
+        nib = mixed ? kNibMixed : first;
+        word |= nib << (4 * b);
+    }
+    return word;
+}
+
+// Per-brick nibble-map word w (R > 256; 8 x-adjacent bricks): the value k_build_brick stores there.
+__device__ __forceinline__ uint32_t brick_word(const uint8_t* mine_sw, uint32_t w) {
+    uint32_t word = 0;
+    for (uint32_t b = 0; b < 8u; b++) word |= brick_nibble(mine_sw, (size_t)w * 8u + b) << (4 * b);
+    return word;
+}
+
+}  // namespace
+
+// One workgroup (16 waves) per touched chunk.  chunks[blockIdx.x] = (cz * n + cy) * n + cx with n = R / 64 chunks per axis; the
+// chunk's edits are recs[offs[i] .. offs[i + 1]): .x = local index (z << 12 | y << 6 | x) | solid << 18, .y = material word, each
+// voxel at most once (the host keeps the last edit of a voxel).  Chunks are distinct, so workgroups never touch the same bytes.
+__global__ __launch_bounds__(1024) void k_rebuild_chunks(uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ mat_sw,
+                                                         const uint32_t* __restrict__ chunks, const uint32_t* __restrict__ offs,
+                                                         const uint2* __restrict__ recs, int logr) {
+    __shared__ uint32_t occ0[2 * 64 * kRow0Stride];   // 33280 B: level 0 bitmap
+    __shared__ uint32_t occ1[32 * kRow1Stride];       //  4224 B: level 1 rows
+    __shared__ uint8_t occ2[16 * 16 * 16];            //  4096 B: levels 2..5, one byte per cell
+    __shared__ uint8_t occ3[8 * 8 * 8];
+    __shared__ uint8_t occ4[4 * 4 * 4];
+    __shared__ uint8_t occ5[2 * 2 * 2];
+    __shared__ uint8_t bval[16 * 16 * 16];            //  4096 B: per 4^3 brick (= level 2 cell): first level 2..6 that is occupied
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lb = logr - 2, nl = logr - 6;
+    const uint32_t cid = chunks[blockIdx.x], cmask = (1u << nl) - 1u;
+    const uint32_t cx = cid & cmask, cy = (cid >> nl) & cmask, cz = cid >> (2 * nl);
+    // a wave covers one row of 16 x-adjacent bricks (1 KiB contiguous): lane = brick bx * 4 + z-layer zl, 16 bytes each
+    const int bx = lane >> 2, zl = lane & 3;
+
+    // ---- load: occupancy of the resident minefield, 16 ballots per 1 KiB row ---------------------------------------------
+    for (int q = wave; q < 256; q += 16) {
+        const int bz = q >> 4, by = q & 15;
+        const size_t brick = ((size_t)(cz * 16u + bz) << (2 * lb)) | ((size_t)(cy * 16u + by) << lb) | (size_t)(cx * 16u + bx);
+        const uint4 v = *reinterpret_cast<const uint4*>(mine_sw + (brick << 6) + zl * 16);
+        const uint32_t dw[4] = {v.x, v.y, v.z, v.w};
+        uint64_t ball[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) ball[k] = __ballot(((dw[k >> 2] >> (8 * (k & 3))) & 0xFFu) == 0u);
+        // byte k = y&3 * 4 + x&3 of lane (bx, zl) -> bit 4 bx + x&3 of row (4 bz + zl, 4 by + y&3)
+        if (lane < 16) {
+            const int rz = lane >> 2, r = lane & 3;
+            uint64_t row = 0;
+#pragma unroll
+            for (int xi = 0; xi < 4; xi++) {   // (selects with constant indices: a lane-dependent index would put ball[] in scratch)
+                const uint64_t b = r == 0 ? ball[xi] : r == 1 ? ball[4 + xi] : r == 2 ? ball[8 + xi] : ball[12 + xi];
+                row |= ((b >> rz) & 0x1111111111111111ull) << xi;
+            }
+            const int w = 2 * ((4 * bz + rz) * kRow0Stride + 4 * by + r);
+            occ0[w] = (uint32_t)row;
+            occ0[w + 1] = (uint32_t)(row >> 32);
+        }
+    }
+    __syncthreads();
+
+    // ---- edits: material words to the region, solid bits to the bitmap -------------------------------------------------
+    const uint32_t e0 = offs[blockIdx.x], e1 = offs[blockIdx.x + 1];
+    for (uint32_t e = e0 + tid; e < e1; e += 1024u) {
+        const uint2 rec = recs[e];
+        const int x = rec.x & 63u, y = (rec.x >> 6) & 63u, z = (rec.x >> 12) & 63u;
+        const int w = 2 * (z * kRow0Stride + y) + (x >> 5);
+        const uint32_t bit = 1u << (x & 31);
+        if (rec.x & (1u << 18)) atomicOr(&occ0[w], bit);
+        else atomicAnd(&occ0[w], ~bit);
+        mat_sw[swizzled_index((int)(cx * 64u) + x, (int)(cy * 64u) + y, (int)(cz * 64u) + z, lb)] = rec.y;
+    }
+    __syncthreads();
+
+    // ---- OR pyramid ----------------------------------------------------------------------------------------------------
+    {   // level 1: 32 x 32 rows, one per thread
+        const int Z = tid >> 5, Y = tid & 31;
+        const uint64_t v = occ_row0(occ0, 2 * Z, 2 * Y) | occ_row0(occ0, 2 * Z, 2 * Y + 1) | occ_row0(occ0, 2 * Z + 1, 2 * Y) |
+                           occ_row0(occ0, 2 * Z + 1, 2 * Y + 1);
+        occ1[Z * kRow1Stride + Y] = or_pairs64(v);
+    }
+    __syncthreads();
+    for (int c = tid; c < 4096; c += 1024) {   // level 2
+        const int X = c & 15, Y = (c >> 4) & 15, Z = c >> 8;
+        const uint32_t v = occ1[(2 * Z) * kRow1Stride + 2 * Y] | occ1[(2 * Z) * kRow1Stride + 2 * Y + 1] |
+                           occ1[(2 * Z + 1) * kRow1Stride + 2 * Y] | occ1[(2 * Z + 1) * kRow1Stride + 2 * Y + 1];
+        occ2[c] = ((v >> (2 * X)) & 3u) != 0u;
+    }
+    __syncthreads();
+    if (tid < 512) {   // level 3
+        const int X = tid & 7, Y = (tid >> 3) & 7, Z = tid >> 6;
+        uint32_t any = 0;
+        for (int k = 0; k < 8; k++) any |= occ2[((2 * Z + (k >> 2)) << 8) | ((2 * Y + ((k >> 1) & 1)) << 4) | (2 * X + (k & 1))];
+        occ3[tid] = any != 0u;
+    }
+    __syncthreads();
+    if (tid < 64) {    // level 4
+        const int X = tid & 3, Y = (tid >> 2) & 3, Z = tid >> 4;
+        uint32_t any = 0;
+        for (int k = 0; k < 8; k++) any |= occ3[((2 * Z + (k >> 2)) << 6) | ((2 * Y + ((k >> 1) & 1)) << 3) | (2 * X + (k & 1))];
+        occ4[tid] = any != 0u;
+    }
+    __syncthreads();
+    if (tid < 8) {     // level 5 (level 6 needs no table: it is the fallback value below)
+        const int X = tid & 1, Y = (tid >> 1) & 1, Z = tid >> 2;
+        uint32_t any = 0;
+        for (int k = 0; k < 8; k++) any |= occ4[((2 * Z + (k >> 2)) << 4) | ((2 * Y + ((k >> 1) & 1)) << 2) | (2 * X + (k & 1))];
+        occ5[tid] = any != 0u;
+    }
+    __syncthreads();
+    for (int c = tid; c < 4096; c += 1024) {   // a brick's voxels that are not within a level-1 cell of a solid one
+        const int X = c & 15, Y = (c >> 4) & 15, Z = c >> 8;
+        uint32_t v = 6;
+        if (occ5[((Z >> 3) << 2) | ((Y >> 3) << 1) | (X >> 3)]) v = 5;
+        if (occ4[((Z >> 2) << 4) | ((Y >> 2) << 2) | (X >> 2)]) v = 4;
+        if (occ3[((Z >> 1) << 6) | ((Y >> 1) << 3) | (X >> 1)]) v = 3;
+        if (occ2[c]) v = 2;
+        bval[c] = (uint8_t)v;
+    }
+    __syncthreads();
+
+    // ---- write-back: the whole chunk's minefield, one dword4 (a z-layer of a brick) per lane -----------------------------
+    for (int q = wave; q < 256; q += 16) {
+        const int bz = q >> 4, by = q & 15;
+        const int z = 4 * bz + zl;
+        const uint32_t bv = bval[(bz << 8) | (by << 4) | bx];
+        uint32_t dw[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int y = 4 * by + r;
+            const uint32_t l0 = (uint32_t)(occ_row0(occ0, z, y) >> (4 * bx)) & 0xFu;
+            const uint32_t l1 = (occ1[(z >> 1) * kRow1Stride + (y >> 1)] >> (2 * bx)) & 3u;
+            uint32_t d = 0;
+#pragma unroll
+            for (int xi = 0; xi < 4; xi++) {
+                const uint32_t b = ((l0 >> xi) & 1u) ? 0u : (((l1 >> (xi >> 1)) & 1u) ? 1u : bv);
+                d |= b << (8 * xi);
+            }
+            dw[r] = d;
+        }
+        const size_t brick = ((size_t)(cz * 16u + bz) << (2 * lb)) | ((size_t)(cy * 16u + by) << lb) | (size_t)(cx * 16u + bx);
+        *reinterpret_cast<uint4*>(mine_sw + (brick << 6) + zl * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+    }
+}
+
+// The nibble-map words over the touched chunks, after k_rebuild_chunks: one workgroup per chunk.  A coarse cube has edge R/64, so a
+// chunk holds 4096/R cubes per axis (16, 8, 4); at R = 1024 a word's 8 cubes span two chunks along x and the other chunk's half is
+// recomputed from its unchanged bytes (two touched neighbours both write the same value).  R > 256: the chunk's 16^3 bricks as well.
+__global__ __launch_bounds__(512) void k_rebuild_chunk_maps(const uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ coarse,
+                                                            uint32_t* __restrict__ brick_words, const uint32_t* __restrict__ chunks,
+                                                            int logr) {
+    const int nl = logr - 6, lb = logr - 2;
+    const uint32_t cid = chunks[blockIdx.x], cmask = (1u << nl) - 1u;
+    const uint32_t cx = cid & cmask, cy = (cid >> nl) & cmask, cz = cid >> (2 * nl);
+    const uint32_t cpa = 4096u >> logr;                   // coarse cubes per chunk edge
+    const uint32_t nwx = cpa >= 8u ? cpa / 8u : 1u;        // words per cube row of the chunk
+    const uint32_t wx0 = (cx * cpa) / 8u;
+    const uint32_t ncw = nwx * cpa * cpa;
+    const uint32_t nbw = brick_words ? 2u * 16u * 16u : 0u;
+    for (uint32_t t = threadIdx.x; t < ncw + nbw; t += 512u) {
+        if (t < ncw) {
+            const uint32_t wx = wx0 + t % nwx, yy = cy * cpa + (t / nwx) % cpa, zz = cz * cpa + t / (nwx * cpa);
+            const uint32_t w = (zz << 9) | (yy << 3) | wx;
+            coarse[w] = coarse_word(mine_sw, w, logr);
+        } else {
+            const uint32_t u = t - ncw;
+            const uint32_t wx = 2u * cx + (u & 1u), by = cy * 16u + ((u >> 1) & 15u), bz = cz * 16u + (u >> 5);
+            const uint32_t w = (((bz << lb) + by) << (lb - 3)) + wx;
+            brick_words[w] = brick_word(mine_sw, w);
+        }
+    }
+}
+
+// rt_selftest(RT_SELFTEST_SCENE_MAPS): thread t recomputes coarse word t (t < 32768) or brick word t - 32768 and counts a difference.
+__global__ __launch_bounds__(256) void k_check_maps(const uint8_t* __restrict__ mine_sw, const uint32_t* __restrict__ coarse,
+                                                    const uint32_t* __restrict__ brick_words, uint32_t nbrick_words, int logr,
+                                                    unsigned long long* __restrict__ mismatches) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    bool differs = false;
+    if (t < (uint32_t)kCoarseWords) differs = coarse_word(mine_sw, t, logr) != coarse[t];
+    else if (t - (uint32_t)kCoarseWords < nbrick_words) differs = brick_word(mine_sw, t - kCoarseWords) != brick_words[t - kCoarseWords];
+    const uint64_t m = __ballot(differs);
+    if ((threadIdx.x & 63u) == 0u && m) atomicAdd(mismatches, (unsigned long long)__popcll(m));
+}
+
+// rt_read_box: out[i] for i over the box (x0, y0, z0) + [0, ex) x [0, ey) x [0, nz), x fastest.  Either output may be null.
+__global__ __launch_bounds__(256) void k_read_box(const uint8_t* __restrict__ mine_sw, const uint32_t* __restrict__ mat_sw, int logr,
+                                                  int x0, int y0, int z0, int ex, int ey, uint64_t n, uint32_t* __restrict__ mat_out,
+                                                  uint8_t* __restrict__ mine_out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int x = x0 + (int)(i % (uint64_t)ex), y = y0 + (int)((i / (uint64_t)ex) % (uint64_t)ey), z = z0 + (int)(i / ((uint64_t)ex * ey));
+    const uint32_t s = swizzled_index(x, y, z, logr - 2);
+    if (mat_out) mat_out[i] = mat_sw[s];
+    if (mine_out) mine_out[i] = mine_sw[s];
+}
+
+hipError_t launch_rebuild_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const uint32_t* offs, const uint2* recs,
+                                 uint32_t nchunks, int logr, hipStream_t st) {
+    if (nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rebuild_chunks, dim3(nchunks), dim3(1024), 0, st, mine_sw, mat_sw, chunks, offs, recs, logr);
+    return hipGetLastError();
+}
+
+hipError_t launch_rebuild_chunk_maps(const uint8_t* mine_sw, uint32_t* coarse, uint32_t* brick, const uint32_t* chunks, uint32_t nchunks,
+                                     int logr, hipStream_t st) {
+    if (nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rebuild_chunk_maps, dim3(nchunks), dim3(512), 0, st, mine_sw, coarse, logr > 8 ? brick : nullptr, chunks, logr);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_maps(const uint8_t* mine_sw, const uint32_t* coarse, const uint32_t* brick, int logr,
+                             unsigned long long* mismatches, hipStream_t st) {
+    const uint32_t nbw = (logr > 8 && brick) ? (1u << (3 * (logr - 2))) / 8u : 0u;
+    const uint32_t n = (uint32_t)kCoarseWords + nbw;
+    hipLaunchKernelGGL(k_check_maps, dim3((n + 255u) / 256u), dim3(256), 0, st, mine_sw, coarse, nbw ? brick : nullptr, nbw, logr,
+                       mismatches);
+    return hipGetLastError();
+}
+
+hipError_t launch_read_box(const uint8_t* mine_sw, const uint32_t* mat_sw, int logr, int x0, int y0, int z0, int ex, int ey, int nz,
+                           uint32_t* mat_out, uint8_t* mine_out, hipStream_t st) {
+    const uint64_t n = (uint64_t)ex * (uint64_t)ey * (uint64_t)nz;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_read_box, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, mine_sw, mat_sw, logr, x0, y0, z0, ex, ey, n,
+                       mat_out, mine_out);
+    return hipGetLastError();
+}
+
+}  // namespace rtd

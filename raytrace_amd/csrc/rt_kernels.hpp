@@ -125,6 +125,16 @@ hipError_t launch_flatten(const uint8_t* mine_lin, const uint32_t* mat_lin, uint
                           uint32_t* coarse, uint32_t* brick /* R > 256: the per-brick map, else null */, uint32_t* bad_flag, int logr, hipStream_t st);
 hipError_t launch_flatten_slab(const uint8_t* mine_slab, const uint32_t* mat_slab, uint8_t* mine_sw, uint32_t* mat_sw, uint32_t* coarse,
                                uint32_t* brick, int logr, int axis, int offset, hipStream_t st);
+// rt_edit.hip: rt_edit_voxels (chunk list, per-chunk edit ranges offs[0..n] and records as rt_edit.hip's k_rebuild_chunks
+// describes), rt_read_box, rt_selftest(RT_SELFTEST_SCENE_MAPS)
+hipError_t launch_rebuild_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const uint32_t* offs, const uint2* recs,
+                                 uint32_t nchunks, int logr, hipStream_t st);
+hipError_t launch_rebuild_chunk_maps(const uint8_t* mine_sw, uint32_t* coarse, uint32_t* brick, const uint32_t* chunks, uint32_t nchunks,
+                                     int logr, hipStream_t st);
+hipError_t launch_check_maps(const uint8_t* mine_sw, const uint32_t* coarse, const uint32_t* brick, int logr,
+                             unsigned long long* mismatches, hipStream_t st);
+hipError_t launch_read_box(const uint8_t* mine_sw, const uint32_t* mat_sw, int logr, int x0, int y0, int z0, int ex, int ey, int nz,
+                           uint32_t* mat_out, uint8_t* mine_out, hipStream_t st);
 hipError_t launch_mega(const Scene& sc, const Frame& f, const Planes& pl, DevCounters* cn, bool count, hipStream_t st);
 hipError_t launch_trace(const Scene& sc, const Frame& f, const TraceArgs& a, bool primary, bool count, int nworkgroups, hipStream_t st);
 hipError_t launch_shade0(const Scene& sc, const Frame& f, const ShadeArgs& a, const Planes& pl, bool count, hipStream_t st);

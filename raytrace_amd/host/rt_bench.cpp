@@ -6,6 +6,7 @@
 //
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
 //            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
+//            [--edits N [--edit-spread]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -17,6 +18,12 @@
 // --accumulate: the contexts are created with RT_FLAG_ACCUMULATE.  The camera stays where it is and the mirror's draw_frame
 // advances the seed by spp per frame, so every frame continues the accumulation; the JSON line adds the samples the last frame's
 // lighting holds (rt_get_accumulation).
+//
+// --edits N: before every frame, rt_edit_voxels places or breaks (alternating from frame to frame) N voxels of a deterministic brush
+// near the camera — a cube of voxels centred 16 texels ahead of it — or, with --edit-spread, N voxels dealt round every 64^3 chunk
+// of the region.  After the timed loop the same batches run alone on a second pipeline created with RT_FLAG_TIMING_ALL: the JSON
+// line adds the device time of the edit launches per call (rt_get_timing's shade_ms: the rebuild and nibble-map launches, each
+// bracketed by events), the launches per call, the host time spent inside rt_edit_voxels and the wall time per call.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -84,12 +91,35 @@ class ThreadBarrier {
     unsigned long gen_ = 0;
 };
 
+// --edits: the brush of frame-independent voxel positions (texel coordinates of the 256 region)
+std::vector<RtVoxelEdit> edit_brush(int n, bool spread, const float origin[3]) {
+    const int R = RT_ROOT_BLOCK_SIZE;
+    std::vector<RtVoxelEdit> v((size_t)n);
+    const int c[3] = {(int)origin[0] + R / 2, (int)origin[1] + R / 2 + 16, (int)origin[2] + R / 2};
+    for (int i = 0; i < n; i++) {
+        int p[3];
+        if (spread) {   // chunk i % 64, then a position inside it that moves with i / 64
+            const int ch = i % 64, k = i / 64;
+            p[0] = (ch & 3) * 64 + (k * 7) % 64; p[1] = ((ch >> 2) & 3) * 64 + (k * 13) % 64; p[2] = (ch >> 4) * 64 + (k * 29) % 64;
+        } else {        // a cube of edge 16 around the centre, further cubes stacked above it for N > 4096
+            p[0] = c[0] - 8 + i % 16; p[1] = c[1] - 8 + (i / 16) % 16; p[2] = c[2] - 8 + (i / 256) % 16 + 16 * (i / 4096);
+        }
+        for (int a = 0; a < 3; a++) p[a] = std::min(std::max(p[a], 0), R - 1);
+        RtVoxelEdit& e = v[(size_t)i];
+        e.x = (uint16_t)p[0]; e.y = (uint16_t)p[1]; e.z = (uint16_t)p[2];
+        e.solid = 1; e.material = (1u << 15) | (90u << 14) | (60u << 7) | 30u; e.reserved = 0;
+    }
+    return v;
+}
+void set_solid(std::vector<RtVoxelEdit>& v, int frame) { for (RtVoxelEdit& e : v) e.solid = (uint16_t)((frame & 1) == 0); }
+
 }  // namespace
 
 int main(int argc, char** argv) {
     int width = 1024, height = 1024;   // WINDOW_WIDTH / WINDOW_HEIGHT, src/render/constants.rs:9-10
     int spp = 1, depth = 2, frames = 240, device = 0, gpus = 1;
-    bool gather = false, overlap = false, post = false, accumulate = false;
+    bool gather = false, overlap = false, post = false, accumulate = false, edit_spread = false;
+    int edits = 0;
     std::string noise_path = "tests/golden/blue_noise_512.rgba";
     std::vector<const char*> positional = {argv[0]};
     for (int i = 1; i < argc; i++) {
@@ -106,9 +136,12 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--overlap") == 0) overlap = true;
         else if (std::strcmp(argv[i], "--post") == 0) post = true;
         else if (std::strcmp(argv[i], "--accumulate") == 0) accumulate = true;
+        else if (want("--edits")) edits = std::atoi(argv[++i]);
+        else if (std::strcmp(argv[i], "--edit-spread") == 0) edit_spread = true;
         else positional.push_back(argv[i]);
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
+    if (edits < 0 || edits > (1 << 24)) { std::fprintf(stderr, "--edits must be in 0..2^24\n"); return 2; }
     if (gpus > 1) gather = true;
     if (post && gpus > 1) { std::fprintf(stderr, "--post needs the whole frame on one device (gather first on several)\n"); return 2; }
     rt::game::Game game((int)positional.size(), positional.data());
@@ -161,6 +194,7 @@ int main(int argc, char** argv) {
     }
     std::printf("Created in %fs.\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());   // main.rs:13
 
+    std::vector<std::vector<RtVoxelEdit>> brushes((size_t)gpus, edit_brush(edits, edit_spread, game.camera.origin));
     RingBufferAverage perf(120);                                      // main.rs:16
     ThreadBarrier frame_barrier(gpus);
     std::atomic<int> failed{0};
@@ -177,7 +211,13 @@ int main(int argc, char** argv) {
                 frame_timer = now;
                 if (f > 0) perf.push_sample(millis);
             }
-            int rc = p->draw_frame(game);                             // main.rs:52
+            int rc = RT_OK;
+            if (edits > 0) {
+                set_solid(brushes[(size_t)g], f);
+                rc = rt_edit_voxels(p->context(), brushes[(size_t)g].data(), (uint32_t)edits);
+                if (rc != RT_OK) std::fprintf(stderr, "rt_edit_voxels failed on device %d (%d): %s\n", devices[(size_t)g], rc, rt_last_error(p->context()));
+            }
+            if (rc == RT_OK) rc = p->draw_frame(game);                // main.rs:52
             if (rc != RT_OK) {
                 std::fprintf(stderr, "frame %d failed on device %d (%d): %s\n", f, devices[(size_t)g], rc, p->last_error());
                 failed.store(1);
@@ -209,6 +249,34 @@ int main(int argc, char** argv) {
     for (auto& t : threads) t.join();
 
     int exit_code = failed.load() ? 1 : 0;
+    // --edits: the edit batches alone, on a pipeline whose launches are timed
+    double edit_dev_ms = 0.0, edit_host_ms = 0.0, edit_wall_ms = 0.0, edit_launches = 0.0;
+    if (!exit_code && edits > 0) {
+        RtConfig tcfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
+        rt::render::Pipeline* tp = rt::render::create_instance(tcfg, noise.data(), game, &err);
+        RtTiming tm{};
+        if (!tp || tp->draw_frame(game) != RT_OK || tp->wait() != RT_OK || rt_get_timing(tp->context(), &tm) != RT_OK) {
+            std::fprintf(stderr, "edit timing pipeline failed: %s\n", tp ? tp->last_error() : err.c_str());
+            exit_code = 1;
+        } else {
+            std::vector<RtVoxelEdit> brush = edit_brush(edits, edit_spread, game.camera.origin);
+            const auto w0 = std::chrono::steady_clock::now();
+            for (int f = 0; f < frames && !exit_code; f++) {
+                set_solid(brush, f);
+                const auto h0 = std::chrono::steady_clock::now();
+                if (rt_edit_voxels(tp->context(), brush.data(), (uint32_t)edits) != RT_OK) exit_code = 1;
+                edit_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
+            }
+            if (rt_sync(tp->context()) != RT_OK) exit_code = 1;
+            edit_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count() / frames;
+            if (rt_get_timing(tp->context(), &tm) != RT_OK) exit_code = 1;
+            edit_dev_ms = tm.shade_ms / frames;
+            edit_launches = (double)tm.other_launches / frames;
+            edit_host_ms /= frames;
+            if (exit_code) std::fprintf(stderr, "edit timing failed: %s\n", rt_last_error(tp->context()));
+        }
+        delete tp;
+    }
     if (exit_code && gpus > 1) { std::fflush(nullptr); std::_Exit(1); }   // communicators may hold unmatched operations: no orderly teardown
     if (!exit_code) {
         std::printf("%.3fms / %.3fms\n", perf.average(), perf.max());    // main.rs:45-46: average / max
@@ -233,11 +301,14 @@ int main(int argc, char** argv) {
         std::printf("{\"binary\": \"rt_bench\", \"config\": {\"width\": %d, \"height\": %d, \"spp\": %d, \"depth\": %d, \"gpus\": %d, "
                     "\"gather\": \"%s\", \"post_passes\": %s, \"pose\": [%g, %g, %g, %g, %g], \"sun_angle\": %g}, \"frames\": %d, \"rays_per_frame\": %llu, "
                     "\"ms_per_frame\": %.4f, \"avg_ms_last_120\": %.4f, \"max_ms_last_120\": %.4f, \"mrays_per_s\": %.2f, "
-                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"samples\": %u}\n",
+                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"samples\": %u, "
+                    "\"edits\": %d, \"edit_spread\": %s, \"edit_device_ms_per_call\": %.4f, \"edit_launches_per_call\": %.1f, "
+                    "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f}\n",
                     width, height, spp, depth, gpus, gather ? (overlap ? "rccl-overlapped" : "rccl-serial") : "none", post ? "true" : "false",
                     game.camera.origin[0], game.camera.origin[1], game.camera.origin[2], game.camera.heading, game.camera.pitch,
                     game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum,
-                    accumulate ? "true" : "false", acc_samples);
+                    accumulate ? "true" : "false", acc_samples, edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
+                    edit_host_ms, edit_wall_ms);
     }
     for (int g = 0; g < gpus; g++) {
         if (comms[(size_t)g]) rt_comm_destroy(comms[(size_t)g]);

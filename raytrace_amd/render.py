@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RtConfig, RtCounters, RtInfo, RtTiming,
-                  RtUniforms)
+                  RtUniforms, RtVoxelEdit)
 
 
 class RtError(RuntimeError):
@@ -120,6 +120,40 @@ class Context:
         finally:
             self._retire_staging_views()
 
+    def edit_voxels(self, xyz, materials, solid):
+        """rt_edit_voxels: xyz int[N, 3] texel coordinates (x, y, z), materials u32[N] packed words, solid bool/int[N].  Later rows
+        win over earlier rows for the same voxel; the touched 64^3 chunks get pack_into's minefield (see include/rt_abi.h)."""
+        xyz = np.asarray(xyz).reshape(-1, 3)
+        materials = np.asarray(materials, dtype=np.uint32).reshape(-1)
+        solid = np.asarray(solid).reshape(-1)
+        n = xyz.shape[0]
+        if materials.size != n or solid.size != n:
+            raise ValueError("xyz, materials and solid must describe the same number of edits")
+        if n and (xyz.min() < 0 or xyz.max() > 0xFFFF):
+            raise ValueError("coordinates must fit uint16 (the library checks them against the region)")
+        recs = np.zeros(n, dtype=[("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("solid", "<u2"), ("material", "<u4"), ("reserved", "<u4")])
+        recs["x"], recs["y"], recs["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+        recs["solid"] = solid != 0
+        recs["material"] = materials
+        self.edit_records(recs)
+
+    def edit_records(self, recs):
+        """rt_edit_voxels on a ready array of RtVoxelEdit records (numpy structured array of 16-byte rows, reserved included)."""
+        recs = np.ascontiguousarray(recs)
+        assert recs.dtype.itemsize == C.sizeof(RtVoxelEdit)
+        self._check(self._lib.rt_edit_voxels(self._h, recs.ctypes.data_as(C.POINTER(RtVoxelEdit)), int(recs.size)))
+
+    def read_box(self, origin, extent):
+        """rt_read_box: (materials u32[ez, ey, ex], minefield u8[ez, ey, ex]) of the resident region's box at texel `origin` (x, y, z)
+        of `extent` (ex, ey, ez).  Synchronises."""
+        x0, y0, z0 = (int(v) for v in origin)
+        ex, ey, ez = (int(v) for v in extent)
+        shape = (max(ez, 0), max(ey, 0), max(ex, 0))
+        mats = np.empty(shape, dtype=np.uint32)
+        mine = np.empty(shape, dtype=np.uint8)
+        self._check(self._lib.rt_read_box(self._h, x0, y0, z0, ex, ey, ez, _p(mats), _p(mine)))
+        return mats, mine
+
     def upload_noise(self, rgba8):
         rgba8 = np.ascontiguousarray(rgba8, dtype=np.uint8).reshape(-1)
         if rgba8.size != 512 * 512 * 4:
@@ -198,7 +232,8 @@ class Context:
         self._check(self._lib.rt_gather_gbuffer(self._h, C.c_void_p(comm) if comm else None, int(root), arr, 1 if overlapped else 0))
 
     def selftest(self, which=1):
-        """rt_selftest: RT_SELFTEST_DENOISE_DIVISION (1) -> number of inexact quotients over the denoise division's domain."""
+        """rt_selftest: RT_SELFTEST_DENOISE_DIVISION (1) -> number of inexact quotients over the denoise division's domain;
+        RT_SELFTEST_SCENE_MAPS (2) -> number of nibble-map words that differ from a rebuild from the resident minefield."""
         out = C.c_uint64(0)
         self._check(self._lib.rt_selftest(self._h, int(which), C.byref(out)))
         return int(out.value)
