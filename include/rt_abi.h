@@ -408,9 +408,10 @@ int rt_denoise_planes(RtContext* ctx, void* lighting_rgba16, const void* depth_r
 int rt_finalize_planes(RtContext* ctx, const void* albedo_rgba8, const void* emission_rgba8, const void* fog_rgba8,
                        const void* lighting_rgba16, const void* depth_r16, void* out_bgra8);
 
-/* The traversal implementation the context runs: after a frame, the kernel its path launches actually ran on (RT_KERNEL_DEFAULT
- * and RT_KERNEL_PATHS choose per frame: launch size, lr, primary cache, region); before the first frame, what the
- * configuration resolved to.  Negative RtStatus on a null context. */
+/* The traversal implementation the context runs: the kernel of a frame's last launch, the same before the first frame and after
+ * it.  The choice is fixed per context when it is created (launch size, primary cache, region, depth, accumulation); a cached
+ * frame of depth 0, which has no path launch, reports RT_KERNEL_PATHS or RT_KERNEL_PERSISTENT as configured.  Negative RtStatus on
+ * a null context. */
 int rt_kernel_in_use(RtContext* ctx);
 
 /* Device self-tests.  RT_SELFTEST_DENOISE_DIVISION: the denoise passes compute weight / (distance + normal + 1)

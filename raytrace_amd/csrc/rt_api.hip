@@ -30,15 +30,14 @@ const size_t kBytesPerPixel[RT_BUF_COUNT] = {8, 2, 1, 4, 4, 4, 16, 16, 4, 4};
 }  // namespace
 
 constexpr size_t kCursorWords = 8 * 32;   // path cursors of the persistent kernels: one word per XCD group, each on its own 128-byte line
-// RT_KERNEL_DEFAULT: launches of at least this many pixel-samples run on k_paths, smaller ones on k_persist — unless the whole
-// frame is small enough for k_frame (kFrameCrossover, kFrameCrossoverMulti below) — (measured crossover,
-// round 3, same box: 1080p spp 1 (2.1 M) 0.351 against 0.348 ms per frame, spp 2 (4.1 M) 0.409 against 0.442; 1024^2 spp 1 0.252 against 0.229)
-constexpr uint64_t kPathsCrossover = 3ull << 20;
-// ... and ONE-sample frames of fewer pixels than this run on k_frame — the whole frame in one launch, no prepass, worklist or
-// accumulate (rt_frame.hip; RT_FRAME_CROSSOVER overrides).  Measured (profiles/r4_frame_kernel.txt), k_frame against prepass +
-// k_persist, ms per frame: 256^2 0.084 / 0.186, 1024^2 (the reference's frame) 0.163 / 0.225, 1280x720 0.155 / 0.218, 1920x1080
-// 0.275 / 0.297, 2048x1440 0.355 / 0.360 (k_paths: 0.353); with more than one sample per pixel a lane walks them one after the
-// other and the persistent kernels win (256^2 spp 4: 0.200 / 0.188).
+// light records of one launch above which k_paths streams them out and k_accumulate_paths streams them in (see draw_path_batches)
+constexpr uint64_t kStreamRecordBytes = 384ull << 20;
+
+// ---- the route: which kernel each launch of a frame runs on (Route, resolve_route) --------------------------------------------
+// RT_KERNEL_DEFAULT: ONE-sample frames of fewer pixels than this run on k_frame — the whole frame in one launch, no prepass,
+// worklist or accumulate (rt_frame.hip; RT_FRAME_CROSSOVER overrides).  Measured (profiles/r4_frame_kernel.txt), k_frame against
+// prepass + k_persist, ms per frame: 256^2 0.084 / 0.186, 1024^2 (the reference's frame) 0.163 / 0.225, 1280x720 0.155 / 0.218,
+// 1920x1080 0.275 / 0.297, 2048x1440 0.355 / 0.360 (k_paths: 0.353).
 constexpr uint64_t kFrameCrossover = 5ull << 19;
 // More than one sample per pixel: k_frame deals the (pixel, sample) paths of a workgroup's pixels to its lanes and adds a pixel's
 // samples in order itself.  It wins while the frame is so small that the persistent kernels' ~0.14 ms per launch dominates — measured
@@ -46,8 +45,35 @@ constexpr uint64_t kFrameCrossover = 5ull << 19;
 // 256^2 spp 16 depth 4 0.246 / 0.211, 512^2 spp 4 depth 4 0.234 / 0.217, 1024^2 spp 2 depth 4 0.352 / 0.290 — i.e. below about 1.5 M
 // pixel-sample-levels (pixels x spp x depth; RT_FRAME_CROSSOVER_MULTI overrides).
 constexpr uint64_t kFrameCrossoverMulti = 3ull << 19;
-// light records of one launch above which k_paths streams them out and k_accumulate_paths streams them in (see rt_draw_frame)
-constexpr uint64_t kStreamRecordBytes = 384ull << 20;
+// RT_KERNEL_DEFAULT, frames k_frame does not take: path launches of at least this many pixel-samples run on k_paths, smaller ones on
+// k_persist.  k_paths pays for its two contexts per lane once there is enough work to keep them filled: measured crossover against
+// k_persist (tools/kernel_crossover.sh) between 4 M and 8 M paths per launch — 1080p spp 1: 0.28 against 0.22 ms, 256^2 spp 64: 0.35
+// against 0.32, 1080p spp 4: 0.47 against 0.50, spp 16: 1.29 against 1.65; the reference's own 1024^2 1-spp frame: 0.20 against 0.14;
+// round 3, same box: 1080p spp 1 (2.1 M) 0.351 against 0.348 ms per frame, spp 2 (4.1 M) 0.409 against 0.442; 1024^2 spp 1 0.252
+// against 0.229.  (RT_KERNEL_PATHS and RT_KERNEL_FRAME ask for k_paths whatever the size.)
+constexpr uint64_t kPathsCrossover = 3ull << 20;
+
+struct Route {
+    int family = RT_KERNEL_PERSISTENT;   // RT_KERNEL_MEGA, RT_KERNEL_WAVEFRONT, or RT_KERNEL_PERSISTENT (k_frame, k_persist and k_paths)
+    bool frame = false;                  // every frame is one k_frame launch
+    uint32_t paths_from = UINT32_MAX;    // path launches of at least this many samples run on k_paths, smaller ones on k_persist
+    uint32_t threshold_persist = 0, threshold_paths = 0;   // PersistArgs::threshold of a k_persist / k_paths launch
+    bool direct = false;                 // one-sample launches store the pixel's lighting themselves: no light records, no accumulate
+    int in_use = RT_KERNEL_PERSISTENT;   // rt_kernel_in_use: the kernel of a frame's last launch
+    bool on_paths(uint32_t ns) const { return ns >= paths_from; }
+};
+
+// Pinned host staging -> device twin (upload stream) -> the launch that applies it (render stream): rt_upload_slice's slabs and
+// rt_edit_voxels' batches.  Each kind has TWO sets used in turn: transfer n waits for the launch of n - 2, not of n - 1,
+// which sits behind the frames on the render stream — a host that sends one slab or batch per frame never waits for a frame.
+struct StagingSet {
+    uint8_t* host = nullptr;           // hipHostMalloc
+    uint8_t* dev = nullptr;            // hipMalloc (counted in device_bytes)
+    size_t cap = 0;                    // bytes of each block
+    hipEvent_t ev_copied = nullptr;    // the transfer has read the host block
+    hipEvent_t ev_applied = nullptr;   // the launch has read the device block
+    bool copy_pending = false, apply_recorded = false;
+};
 
 struct Lane {
     hipStream_t stream = nullptr;      // lane 0: the context's stream (its own or the caller's, rt_set_stream); lane 1: the library's second stream
@@ -91,22 +117,11 @@ struct RtContext {
     uint8_t* d_mine_sw = nullptr; uint32_t* d_mat_sw = nullptr;
     uint32_t* d_coarse = nullptr; uint32_t* d_noise = nullptr; uint32_t* d_flag = nullptr;
     uint32_t* d_brick = nullptr;          // R > 256: per-brick nibble map (rtd::Scene::brick), R^3 / 128 bytes
-    // rt_upload_slice: a 16-thick slab travels pinned host staging -> device staging (own stream) -> re-tile (render stream).
-    // TWO staging sets used in turn: slab n's transfer waits for slab n - 2's re-tile, not for slab n - 1's, which sits
-    // behind the frames on the render stream — a host that uploads one slab per frame never waits for a frame
-    uint8_t* d_slab_mine[2] = {nullptr, nullptr}; uint32_t* d_slab_mat[2] = {nullptr, nullptr};
-    uint8_t* h_slab_mine[2] = {nullptr, nullptr}; uint32_t* h_slab_mat[2] = {nullptr, nullptr};   // hipHostMalloc
-    uint64_t slabs = 0;                   // slabs submitted: the next one uses set slabs & 1
+    // staging (StagingSet): rt_upload_slice's 16-thick slab (materials, then minefield at 4 x 16 R^2) is re-tiled, rt_edit_voxels'
+    // binned batch (touched chunks, per-chunk edit ranges, records) rebuilds its chunks; the edit sets grow when a batch needs more
     hipStream_t upload_stream = nullptr;
-    hipEvent_t ev_slab_copied[2] = {nullptr, nullptr}, ev_slab_applied[2] = {nullptr, nullptr};   // per set: host staging read / device staging consumed
-    bool slab_copy_pending[2] = {false, false}, slab_apply_recorded[2] = {false, false};
-    // rt_edit_voxels: a binned batch (touched chunks, per-chunk edit ranges, records) travels pinned host staging -> device staging
-    // (upload stream) -> k_rebuild_chunks (render stream), like a slab; two staging sets used in turn, grown when a batch needs more
-    uint8_t* h_edit[2] = {nullptr, nullptr}; uint8_t* d_edit[2] = {nullptr, nullptr};   // hipHostMalloc / hipMalloc
-    size_t edit_cap[2] = {0, 0};
-    uint64_t edit_batches = 0;            // batches submitted: the next one uses set edit_batches & 1
-    hipEvent_t ev_edit_copied[2] = {nullptr, nullptr}, ev_edit_applied[2] = {nullptr, nullptr};
-    bool edit_copy_pending[2] = {false, false}, edit_apply_recorded[2] = {false, false};
+    StagingSet slab_sets[2], edit_sets[2];
+    uint64_t slabs = 0, edit_batches = 0;   // submitted so far: the next one uses set slabs & 1 / edit_batches & 1
     std::vector<uint32_t> edit_chunk, edit_order, edit_start, edit_stamp;   // host binning scratch, kept between calls
     uint32_t edit_gen = 0;                // edit_stamp generation: a voxel's slot holds the generation of the chunk run that kept it
 
@@ -130,8 +145,9 @@ struct RtContext {
     hipEvent_t ev_gather = nullptr;     // the previous rt_gather_gbuffer (gathers share staging: they run one after the other)
     bool gather_recorded = false;
 
+    Route route;
+
     // wavefront pipeline state
-    int kernel = RT_KERNEL_PERSISTENT;
     uint32_t batch_samples = 1;   // samples per batch
     uint32_t cap = 0;             // paths per batch (allocation)
     uint32_t refill_threshold = 24;
@@ -151,15 +167,11 @@ struct RtContext {
     uint32_t persist_batch = 1;
     int pl_stream_mode = -1;      // RT_PL_STREAM: -1 = by size (kStreamRecordBytes); bit 0 streaming stores, bit 1 streaming loads
     uint32_t persist_chunk = 0;   // RT_PERSIST_CHUNK: paths per cursor atomic (multiple of 64); 0 = automatic
-    uint32_t persist_threshold = 0, persist_rmin = 12;   // threshold 0 = the kernel version's default
-    int persist_version = 1;      // 1 = k_persist, 3 = k_paths (RT_KERNEL_PATHS)
-    bool paths_by_size = false;   // RT_KERNEL_DEFAULT: k_paths for launches with enough work, k_persist for small ones
-    int frame_mode = 0;           // k_frame: 0 = never, 1 = one-sample frames below frame_crossover pixels (RT_KERNEL_DEFAULT), 2 = every frame it covers (RT_KERNEL_FRAME)
+    uint32_t persist_threshold = 0, persist_rmin = 12;   // RT_PERSIST_THRESHOLD: 0 = the route's default per kernel
     uint64_t frame_crossover = kFrameCrossover;
     uint64_t frame_crossover_multi = kFrameCrossoverMulti;   // ... and frames of more than one sample per pixel below this many pixel-sample-levels
     uint32_t frame_threshold = 0; // RT_FRAME_THRESHOLD: parked lanes per wave that trigger k_frame's pass; 0 = the default
     uint32_t frame_tiles = 0;     // RT_FRAME_TILES (per wave, 1..4) / RT_FRAME_GROUP_TILES (1..16): tiles per four-wave workgroup of k_frame; 0 = by frame size and spp
-    int last_path_kernel = 0;     // RtKernel the most recent frame's path launches ran on (0 = no frame yet)
     float lut_key[6] = {0, 0, 0, 0, 0, 0};   // sun vector + colour the per-frame tables were built for
     bool lut_valid = false;
     int primary_version = 2;      // 1 = k_primary (thread per pixel), 2 = k_primary2 (nibble map in LDS); RT_PRIMARY_V
@@ -230,10 +242,45 @@ hipError_t dev_alloc(RtContext* c, T** p, size_t count) {
     return e;
 }
 
-// RT_KERNEL_DEFAULT: is this context's frame small enough for k_frame (one launch per frame)?
-bool frame_by_size(const RtContext* c) {
-    if (c->cfg.spp == 1) return (uint64_t)c->npix_pad < c->frame_crossover;
-    return (uint64_t)c->npix_pad * (uint64_t)c->cfg.spp * (uint64_t)(c->cfg.depth > 1 ? c->cfg.depth : 1) < c->frame_crossover_multi;
+// Every input to the route is fixed when the context is created (kernel, primary cache, accumulation, spp, depth, region, frame size,
+// samples per launch and the crossover knobs), so rt_create decides it once, after persist_batch; rt_draw_frame, rt_kernel_in_use
+// and rt_get_info read the result.  The baselines run their own kernel.
+void resolve_route(RtContext* c) {
+    Route& r = c->route;
+    if (r.family != RT_KERNEL_PERSISTENT) { r.in_use = r.family; return; }
+    const RtConfig& cfg = c->cfg;
+    const int kernel = cfg.kernel;
+    const bool cache = (cfg.flags & RT_FLAG_CACHE_PRIMARY) != 0;
+    const uint32_t spp = (uint32_t)cfg.spp, B = c->persist_batch;
+    const uint64_t npix = c->npix_pad;
+    rtd::Frame f{};   // (launch_frame_ok and launch_paths_direct_ok read depth and logr only)
+    f.depth = cfg.depth; f.logr = c->logr;
+    // k_frame takes whatever it covers of RT_KERNEL_FRAME and the small frames of RT_KERNEL_DEFAULT.  It caches primaries by
+    // construction (with one sample per pixel every kernel does: the flag is not needed); more samples than one need the whole
+    // frame's light records in one lane's array; and it adds a pixel's samples from 0, so an accumulating frame of more than one
+    // sample continues the running sum on the persistent kernels instead.
+    const bool small = spp == 1u ? npix < c->frame_crossover
+                                 : npix * spp * (uint64_t)(cfg.depth > 1 ? cfg.depth : 1) < c->frame_crossover_multi;
+    r.frame = (cache || spp == 1u) && rtd::launch_frame_ok(f) && spp <= B && !((cfg.flags & RT_FLAG_ACCUMULATE) && spp > 1u) &&
+              (kernel == RT_KERNEL_FRAME || (kernel == RT_KERNEL_DEFAULT && small));
+    // k_paths needs cached primaries; RT_KERNEL_DEFAULT gives it the launches of at least kPathsCrossover pixel-samples
+    if (cache && kernel != RT_KERNEL_PERSISTENT)
+        r.paths_from = kernel != RT_KERNEL_DEFAULT ? 0u : npix == 0 ? UINT32_MAX : (uint32_t)((kPathsCrossover + npix - 1) / npix);
+    // one sample per pixel (the reference's own frames): k_persist and k_paths store the pixel's lighting themselves, no light
+    // records and no accumulate launch (raytrace.comp:352-356 has no accumulation either)
+    r.direct = spp == 1u && (!r.on_paths(1) || rtd::launch_paths_direct_ok(f));
+    // parked lanes that trigger a pass (RT_PERSIST_THRESHOLD overrides): measured optima per kernel.  k_persist 32.  k_paths (lanes
+    // with a parked context, three steps between looks), round 3, same box: 24 4.28 ms per headline launch, 28 4.22, 32 4.17, 36
+    // 4.06-4.15, 40 4.08-4.14, 44 4.12, 48 4.27; deeper frames at region 256 (depth 5..8: longer paths, fewer new ones per pass) like
+    // 40 — 3840x2160 spp 256 depth 8 launch 51.2 ms at 28, 50.7 at 32, 50.0 at 36, 49.6 at 40 and 44 —, the 1024^3 frame stays at 36
+    // (20.74 against 20.86 at 40, 21.2 at 44)
+    r.threshold_persist = c->persist_threshold ? c->persist_threshold : 32u;
+    r.threshold_paths = c->persist_threshold ? c->persist_threshold : (cfg.depth > 4 && c->region == 256) ? 40u : 36u;
+    // the last launch of a frame covers the samples left after the full batches; a cached frame of depth 0 is its prepass alone
+    // and reports the kernel the configuration names
+    if (r.frame) r.in_use = RT_KERNEL_FRAME;
+    else if (cache && cfg.depth == 0) r.in_use = kernel == RT_KERNEL_PERSISTENT ? RT_KERNEL_PERSISTENT : RT_KERNEL_PATHS;
+    else r.in_use = r.on_paths((spp - 1u) % B + 1u) ? RT_KERNEL_PATHS : RT_KERNEL_PERSISTENT;
 }
 
 rtd::Scene scene_of(const RtContext* c) {
@@ -348,6 +395,51 @@ hipError_t sync_lanes(RtContext* c) {
     return e;
 }
 
+// ---- staging (StagingSet) ---------------------------------------------------------------------------------------------------
+// the upload stream and the set's events, created on first use
+hipError_t staging_create(RtContext* c, StagingSet& s) {
+    hipError_t e = hipSuccess;
+    if (!c->upload_stream) e = hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking);
+    for (hipEvent_t* ev : {&s.ev_copied, &s.ev_applied})
+        if (e == hipSuccess && !*ev) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    return e;
+}
+// the host may write `need` bytes to the set: its previous transfer has left the host block; a smaller set is replaced by one of
+// `alloc` bytes once its device block has been applied
+hipError_t staging_claim(RtContext* c, StagingSet& s, size_t need, size_t alloc) {
+    hipError_t e = staging_create(c, s);
+    if (e == hipSuccess && s.copy_pending) { e = hipEventSynchronize(s.ev_copied); if (e == hipSuccess) s.copy_pending = false; }
+    if (e != hipSuccess || need <= s.cap) return e;
+    if (s.apply_recorded) e = hipEventSynchronize(s.ev_applied);
+    if (e != hipSuccess) return e;
+    if (s.host) { (void)hipHostFree(s.host); s.host = nullptr; }
+    if (s.dev) { (void)hipFree(s.dev); s.dev = nullptr; c->device_bytes -= s.cap; }
+    s.cap = 0;
+    e = hipHostMalloc((void**)&s.host, alloc, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&s.dev, alloc);
+    if (e == hipSuccess) { s.cap = alloc; c->device_bytes += alloc; }
+    return e;
+}
+// the first `bytes` of the host block to the device block on the upload stream, after the set's previous launch has read it; the
+// render stream waits for the transfer, and for the frames in flight on the other lane (they read what the launch changes)
+hipError_t staging_send(RtContext* c, StagingSet& s, size_t bytes) {
+    hipError_t e = s.apply_recorded ? hipStreamWaitEvent(c->upload_stream, s.ev_applied, 0) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, c->upload_stream);
+    if (e == hipSuccess) e = hipEventRecord(s.ev_copied, c->upload_stream);
+    if (e != hipSuccess) return e;
+    s.copy_pending = true;
+    e = hipStreamWaitEvent(c->stream, s.ev_copied, 0);
+    if (e == hipSuccess) e = join_lanes_into(c, c->stream);
+    return e;
+}
+// after the launch that read the device block: later frames, whichever lane they start on, see what it changed
+hipError_t staging_applied(RtContext* c, StagingSet& s) {
+    hipError_t e = hipEventRecord(s.ev_applied, c->stream);
+    if (e != hipSuccess) return e;
+    s.apply_recorded = true;
+    return fence_lanes_after(c, c->stream);
+}
+
 int reflatten(RtContext* c, const uint8_t* d_mine_lin, const uint32_t* d_mat_lin) {
     RT_HIP(c, hipMemsetAsync(c->d_flag, 0, sizeof(uint32_t), c->stream));
     RT_HIP(c, rtd::launch_flatten(d_mine_lin, d_mat_lin, c->d_mine_sw, c->d_mat_sw, c->d_coarse, c->d_brick, c->d_flag, c->logr, c->stream));
@@ -404,6 +496,228 @@ int draw_wavefront(RtContext* c, const rtd::Frame& f) {
     return RT_OK;
 }
 
+// ---- a frame of the persistent family (k_frame, or prepass + path launches on k_persist / k_paths) ----------------------------
+// The steps below run in this order, each only if the ones before it enqueued without error; draw_persistent then publishes the
+// frame whatever happened (later frames depend on the slot, lane and accumulation state it leaves).
+struct PersistFrame {
+    const rtd::Frame& f;
+    bool count = false, cache = false;
+    int nl = 1, nsl = 1;                // lanes and frame slots in use (one each on a caller's stream)
+    int si = 0;                         // the frame's slot
+    FrameSlot* fs = nullptr;
+    rtd::Planes pl{};                   // the slot's planes
+    bool one_lane = false;              // every launch of the frame on lane 0
+    Lane* L0 = nullptr;                 // the lane of the prepass and the first launch ...
+    hipStream_t st0 = nullptr;          // ... and its stream
+    hipStream_t tail = nullptr;         // the stream the frame ends on
+    uint32_t* wlc = nullptr;            // the frame's worklist counter (the slot has two: the other is its next frame's)
+    // RT_FLAG_ACCUMULATE
+    bool accum = false, accum_cont = false;   // the context accumulates; this frame continues the running sum
+    uint32_t key[16] = {};
+    uint64_t accum_n = 0;               // samples the sum holds after this frame
+    float4* accum_multi = nullptr;      // d_accum for frames of more than one sample
+};
+
+// the step that touches the running sum follows the previous frame's (ev_accum), not the whole previous frame
+hipError_t accum_wait(RtContext* c, hipStream_t st) {
+    return c->accum_recorded && c->accum_stream != st ? hipStreamWaitEvent(st, c->ev_accum, 0) : hipSuccess;
+}
+
+// The frame's slot and first lane, its accumulation key; then the slot's previous frame has finished with the slot.
+hipError_t frame_begin(RtContext* c, PersistFrame& p, const RtUniforms* u, bool frame_events) {
+    p.count = (c->cfg.flags & RT_FLAG_COUNTERS) != 0;
+    p.cache = (c->cfg.flags & RT_FLAG_CACHE_PRIMARY) != 0;
+    p.nl = c->user_stream ? 1 : c->nlanes;
+    p.nsl = c->user_stream ? 1 : c->nslots;
+    hipError_t e = hipSuccess;
+    // What the host put behind the previous frame since (post passes, gather, a slab) belongs to that frame's use of its slot.
+    FrameSlot& prev = c->slots[c->cur_slot];
+    if (c->frame_recorded) { e = hipEventRecord(prev.ev_tail, c->stream); prev.tail_recorded = e == hipSuccess; }
+    // This frame's slot, and the lane its prepass and first path launch go to (launches alternate between the lanes).
+    p.si = p.nsl == 2 ? (int)(c->frames_drawn & 1u) : 0;
+    p.fs = &c->slots[p.si];
+    p.pl = planes_of(p.fs->planes);
+    // (a one-slot context whose frames are one launch each stays on lane 0: frame k + 1 cannot start before frame k has finished
+    // with the slot, so alternating would only put an event wait between two streams in front of every frame)
+    p.one_lane = p.nsl == 1 && (uint32_t)c->cfg.spp <= c->persist_batch;
+    p.L0 = &c->lanes[p.one_lane ? 0u : c->path_launches % (uint64_t)p.nl];
+    p.st0 = p.tail = p.L0->stream;
+    // worklist counter of this frame: clean already if the slot's previous frame's prepass cleared it, otherwise cleared there
+    p.wlc = p.fs->wl_count + 32 * p.fs->wl_parity;
+    // RT_FLAG_ACCUMULATE: does this frame continue the running sum, and how many samples will it hold (the lighting's divisor)?
+    // One-sample frames add theirs in k_accumulate_frame after the frame's launches.  Frames of more samples continue the ordered
+    // sum from the running one: k_accumulate_frame for the pixels the prepass finishes, k_accumulate_paths<.., ACCUM> for the
+    // paths' (its first batch starts from the running sum, its last stores it back).
+    const uint32_t spp = (uint32_t)c->cfg.spp;
+    p.accum = c->d_accum != nullptr;
+    accum_key_of(u, p.key);
+    p.accum_cont = p.accum && c->accum_valid && memcmp(p.key, c->accum_key, sizeof(p.key)) == 0 && c->accum_samples + spp <= (1ull << 24);
+    p.accum_n = p.accum_cont ? c->accum_samples + spp : spp;
+    p.accum_multi = p.accum && spp > 1u ? c->d_accum : nullptr;
+    // the frame that used the slot before (frame k - 2 with two slots, k - 1 with one) has finished with it
+    if (e == hipSuccess && p.fs->tail_recorded) e = hipStreamWaitEvent(p.st0, p.fs->ev_tail, 0);
+    if (e == hipSuccess && frame_events) e = hipEventRecord(c->ev_frame0, p.st0);
+    return e;
+}
+
+// Cached primaries, frames k_frame does not take: the prepass traces the primary rays and queues the pixels that go on.
+hipError_t frame_prepass(RtContext* c, PersistFrame& p) {
+    FrameSlot& fs = *p.fs;
+    const bool prepass_clears = c->primary_version == 2 && c->npix_pad != 0;
+    hipError_t e = hipSuccess;
+    if (!fs.wl_clean[fs.wl_parity]) e = hipMemsetAsync(p.wlc, 0, sizeof(uint32_t), p.st0);
+    fs.wl_clean[fs.wl_parity] = false;
+    LaunchTimer t(c, 1, p.st0);
+    rtd::PrimaryArgs pr{};
+    pr.phit = fs.phit;
+    pr.worklist = fs.worklist; pr.wl_count = p.wlc; pr.acc = fs.pacc; pr.counters = c->d_counters;
+    // the prepass clears what the NEXT users need zeroed instead of a memset of its own in front of them: the slot's other
+    // worklist counter (the slot's next frame) and the path cursors of the lane it runs on (this frame's first launch)
+    pr.zero_words = prepass_clears ? fs.wl_count + 32 * (fs.wl_parity ^ 1) : nullptr; pr.zero_count = 1u;
+    pr.zero_words2 = prepass_clears ? p.L0->cursor : nullptr; pr.zero_count2 = (uint32_t)kCursorWords;
+    // accumulating: the prepass runs as a one-sample frame, so the light of a pixel it finishes is 16 x its lighting_f32 exactly;
+    // k_accumulate_frame then adds it spp times to the pixel's running sum (the prepass adds it spp times to 0 otherwise)
+    rtd::Frame fpre = p.f;
+    if (p.accum_multi) fpre.spp = 1;
+    if (e == hipSuccess) e = rtd::launch_primary(scene_of(c), fpre, p.pl, pr, p.count, c->primary_version, c->num_cus, p.st0);
+    if (e == hipSuccess && p.accum_multi) e = accum_wait(c, p.st0);
+    if (e == hipSuccess && p.accum_multi)
+        e = rtd::launch_accumulate_frame(p.f, p.pl, c->d_accum, c->npix_pad, p.accum_cont, (int)p.accum_n, c->cfg.spp, true, p.st0);
+    if (prepass_clears && e == hipSuccess) { fs.wl_clean[fs.wl_parity ^ 1] = true; p.L0->cursor_clean = true; }
+    fs.wl_parity ^= 1;
+    return e;
+}
+
+// The two per-frame tables depend on the sun vector and colour only: rebuilt when those change (bit compare) — after every launch
+// that reads the old ones, on either lane, and before any launch that follows.
+hipError_t frame_tables(RtContext* c, PersistFrame& p) {
+    const float lut_key[6] = {p.f.sunangle[0], p.f.sunangle[1], p.f.sunangle[2], p.f.sunlight[0], p.f.sunlight[1], p.f.sunlight[2]};
+    if (c->cfg.depth < 1 || (c->lut_valid && memcmp(lut_key, c->lut_key, sizeof(lut_key)) == 0)) return hipSuccess;
+    hipError_t e = p.nl == 2 ? join_lanes_into(c, p.st0) : hipSuccess;
+    {
+        LaunchTimer t(c, 1, p.st0);
+        if (e == hipSuccess) e = rtd::launch_sun_lut(p.f, c->sun_lut, p.st0);
+        if (e == hipSuccess) e = rtd::launch_sky_lut(p.f, c->dif_lut, p.st0);
+    }
+    if (e == hipSuccess && p.nl == 2) e = fence_lanes_after(c, p.st0);
+    c->lut_valid = e == hipSuccess;
+    memcpy(c->lut_key, lut_key, sizeof(lut_key));
+    return e;
+}
+
+// k_frame: the whole frame in one launch.  With two frame slots consecutive frames go to the two streams in turn (frame k + 1
+// starts while frame k's last workgroups finish); with one slot a frame follows the previous one anyway, and staying on one
+// stream spares the cross-stream event wait between them.
+hipError_t frame_one_launch(RtContext* c, PersistFrame& p) {
+    if (p.nsl == 2) c->path_launches++;
+    rtd::FrameArgs fa{};
+    fa.threshold = c->frame_threshold; fa.tiles_per_group = c->frame_tiles; fa.sun_lut = c->sun_lut; fa.dif_lut = c->dif_lut; fa.pl = p.L0->ppl; fa.counters = c->d_counters;
+    if (getenv("RT_DEBUG_WAVE_DUMP") && (size_t)c->ntiles_local * 32u <= (size_t)4 * c->num_cus * 1024 * sizeof(uint32_t))
+        fa.dbg_waves = reinterpret_cast<unsigned long long*>(c->lanes[0].pstack);   // (idle while k_frame runs)
+    LaunchTimer t(c, 0, p.st0);
+    return rtd::launch_frame(scene_of(c), p.f, p.pl, fa, p.count, c->num_cus, p.st0);
+}
+
+// The path launches, persist_batch samples each, on the kernels the route gives their size, each with its accumulate launch.
+hipError_t frame_path_batches(RtContext* c, PersistFrame& p) {
+    const Route& r = c->route;
+    FrameSlot& fs = *p.fs;
+    const uint32_t spp = (uint32_t)c->cfg.spp, B = c->persist_batch;
+    hipError_t e = hipSuccess;
+    if (p.nl == 2 && spp > B) e = hipEventRecord(fs.ev_prepass, p.st0);   // launches on the other lane wait for the prepass
+    for (uint32_t s0 = 0; s0 < spp && e == hipSuccess; s0 += B) {
+        const uint32_t ns = spp - s0 < B ? spp - s0 : B;
+        // the sample batches of a frame alternate between the lanes: batch b + 1 starts on the CUs batch b's workgroups leave
+        Lane* L = &c->lanes[p.one_lane ? 0u : c->path_launches % (uint64_t)p.nl];
+        const hipStream_t st = L->stream;
+        if (!p.one_lane) c->path_launches++;
+        if (st != p.st0 && s0 == B) e = hipStreamWaitEvent(st, fs.ev_prepass, 0);   // (later batches on that lane follow by stream order)
+        if (e == hipSuccess && !L->cursor_clean) e = hipMemsetAsync(L->cursor, 0, kCursorWords * sizeof(uint32_t), st);
+        L->cursor_clean = false;
+        const bool to_paths = r.on_paths(ns);
+        rtd::PersistArgs pa{};
+        pa.cursor = L->cursor; pa.worklist = fs.worklist; pa.wl_count = p.wlc; pa.direct = r.direct ? 1u : 0u;
+        pa.npix_pad = c->npix_pad; pa.sample0 = s0; pa.nsamples = ns; pa.rmin = c->persist_rmin; pa.chunk = c->persist_chunk;
+        pa.threshold = to_paths ? r.threshold_paths : r.threshold_persist;
+        pa.nthreads = (uint32_t)c->num_cus * 1024u; pa.stack = L->pstack;
+        pa.phit = fs.phit;
+        pa.sun_lut = c->sun_lut; pa.dif_lut = c->dif_lut;
+        pa.pl = L->ppl; pa.counters = c->d_counters;
+        // light records of this launch: streamed past the caches when there are more of them than would stay there until the
+        // accumulate launch reads them (the Infinity Cache holds 256 MB; RT_PL_STREAM = 0 / 1 / 2 / 3 forces never / stores /
+        // loads / both)
+        const uint64_t record_bytes = (uint64_t)c->npix_pad * ns * sizeof(rtd::PathLight);
+        const bool big_records = record_bytes > kStreamRecordBytes;
+        const bool stream_st = c->pl_stream_mode < 0 ? big_records : (c->pl_stream_mode & 1) != 0;
+        const bool stream_ld = c->pl_stream_mode < 0 ? big_records : (c->pl_stream_mode & 2) != 0;
+        pa.pl_stream = stream_st ? 1u : 0u;
+        if (e == hipSuccess) {
+            LaunchTimer t(c, 0, st);
+            e = to_paths ? rtd::launch_paths(scene_of(c), p.f, p.pl, pa, p.count, c->num_cus, st)
+                         : rtd::launch_persist(scene_of(c), p.f, p.pl, pa, p.count, p.cache, 1, c->num_cus, st);
+        }
+        if (e == hipSuccess && !r.direct) {
+            // a pixel's samples are added in sample order: batch b's accumulate follows batch b - 1's, whichever lane that ran on
+            if (p.nl == 2 && s0 != 0) e = hipStreamWaitEvent(st, fs.ev_acc, 0);
+            // (with cached primaries the prepass, which came first, has waited for the previous frame's running sums)
+            if (e == hipSuccess && p.accum_multi && !p.cache && s0 == 0) e = accum_wait(c, st);
+            {
+                LaunchTimer t(c, 1, st);
+                if (e == hipSuccess)
+                    e = rtd::launch_accumulate_paths(p.f, p.pl, L->ppl, fs.worklist, p.wlc, c->npix_pad, ns, s0 == 0, s0 + B >= spp, p.cache,
+                                                     stream_ld, fs.pacc, p.accum_multi, p.accum_cont, (int)p.accum_n, st);
+            }
+            if (e == hipSuccess && p.nl == 2 && s0 + B < spp) e = hipEventRecord(fs.ev_acc, st);
+        }
+        p.tail = st;
+    }
+    return e;
+}
+
+// RT_FLAG_ACCUMULATE after the frame's launches: a one-sample frame adds its light to the running sum; with two lanes, ev_accum
+// marks the last step that touched the sum.  (No resolve launch: the prepass and the frame's last accumulate store the lighting.)
+hipError_t frame_accumulate_tail(RtContext* c, PersistFrame& p) {
+    hipError_t e = hipSuccess;
+    if (c->cfg.spp == 1) {
+        e = accum_wait(c, p.tail);
+        LaunchTimer t(c, 1, p.tail);
+        if (e == hipSuccess) e = rtd::launch_accumulate_frame(p.f, p.pl, c->d_accum, c->npix_pad, p.accum_cont, (int)p.accum_n, 1, false, p.tail);
+    }
+    if (e == hipSuccess && p.nl == 2) {
+        e = hipEventRecord(c->ev_accum, p.tail);
+        c->accum_recorded = e == hipSuccess;
+        c->accum_stream = p.tail;
+    }
+    return e;
+}
+
+// The frame ends on `tail`: post passes, gather and readback of THIS frame follow it there; its planes are the context's.
+void frame_publish(RtContext* c, const PersistFrame& p, hipError_t e) {
+    if (p.accum) {
+        c->accum_valid = e == hipSuccess;
+        c->accum_frames = p.accum_cont ? c->accum_frames + 1u : 1u;
+        c->accum_samples = p.accum_n;
+        memcpy(c->accum_key, p.key, sizeof(p.key));
+    }
+    c->stream = p.tail;
+    c->cur_slot = p.si;
+    c->gbuffer = p.fs->gbuffer;
+    for (int b = 0; b < RT_BUF_COUNT; b++) c->planes[b] = p.fs->planes[b];
+    c->frames_drawn++;
+}
+
+int draw_persistent(RtContext* c, const rtd::Frame& f, const RtUniforms* u, bool frame_events) {
+    PersistFrame p{f};
+    hipError_t e = frame_begin(c, p, u, frame_events);
+    if (e == hipSuccess && p.cache && !c->route.frame) e = frame_prepass(c, p);
+    if (e == hipSuccess) e = frame_tables(c, p);
+    if (e == hipSuccess && c->route.frame) e = frame_one_launch(c, p);
+    else if (e == hipSuccess && (!p.cache || c->cfg.depth >= 1)) e = frame_path_batches(c, p);   // (cached depth 0: the prepass is the frame)
+    if (e == hipSuccess && p.accum) e = frame_accumulate_tail(c, p);
+    frame_publish(c, p, e);
+    return e == hipSuccess ? RT_OK : fail(c, RT_ERR_HIP, std::string("persistent path: ") + hipGetErrorString(e));
+}
+
 }  // namespace
 
 // Light-record budget of a context (all lanes together): RT_PERSIST_LIGHT_GIB, else min(kDefaultLightBytes, a tenth of the free
@@ -428,6 +742,150 @@ extern "C" uint64_t rt_samples_per_launch(uint64_t lane_bytes, uint64_t npix, ui
     if (B > spp) B = spp;
     return B;
 }
+
+namespace {
+// rt_create's steps, in allocation order: each reports a failure through c->err; rt_create hands it on and destroys the context
+
+// the device, the context's stream and frame events, and the scene
+int create_device(RtContext* c) {
+    RT_HIP(c, hipSetDevice(c->device));
+    hipDeviceProp_t prop;
+    RT_HIP(c, hipGetDeviceProperties(&prop, c->device));
+    c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // RT_RESERVE_CUS=n: the persistent kernels (one workgroup per CU) leave n CUs free, e.g. for an RCCL kernel running
+    // beside them (bench.py's overlapped gather)
+    if (const char* s = getenv("RT_RESERVE_CUS")) { int v = atoi(s); if (v > 0 && v < c->num_cus) c->num_cus -= v; }
+    RT_HIP(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    c->stream = c->own_stream;
+    c->lanes[0].stream = c->own_stream;
+    RT_HIP(c, hipEventCreate(&c->ev_frame0));
+    RT_HIP(c, hipEventCreate(&c->ev_frame1));
+    RT_HIP(c, dev_alloc(c, &c->d_mine_sw, c->vox)); RT_HIP(c, dev_alloc(c, &c->d_mat_sw, c->vox));
+    RT_HIP(c, dev_alloc(c, &c->d_coarse, (size_t)rtd::kCoarseWords));
+    // (the per-brick map of a -DRT_PATHS_BRICK_MAP=1 build of k_paths: an experiment that lost, profiles/r4_c5_brick_map.txt)
+    if (c->logr > 8 && getenv("RT_BRICK_MAP")) RT_HIP(c, dev_alloc(c, &c->d_brick, c->vox / 128u / 4u));
+    RT_HIP(c, dev_alloc(c, &c->d_noise, (size_t)RT_NOISE_SIZE * RT_NOISE_SIZE));
+    RT_HIP(c, dev_alloc(c, &c->d_flag, 4));
+    RT_HIP(c, dev_alloc(c, &c->d_counters, 1));
+    RT_HIP(c, hipMemset(c->d_counters, 0, sizeof(rtd::DevCounters)));
+    return RT_OK;
+}
+
+// the lanes' second stream and events, and the frame slots' planes and events
+int create_slots(RtContext* c) {
+    if (c->nlanes == 2) RT_HIP(c, hipStreamCreateWithFlags(&c->lanes[1].stream, hipStreamNonBlocking));
+    for (int l = 0; l < c->nlanes; l++) RT_HIP(c, hipEventCreateWithFlags(&c->lanes[l].ev_join, hipEventDisableTiming));
+    RT_HIP(c, hipEventCreateWithFlags(&c->ev_fence, hipEventDisableTiming));
+    RT_HIP(c, hipEventCreateWithFlags(&c->ev_gather, hipEventDisableTiming));
+    // the six reference-format planes of a slot live in ONE block (each padded to 256 B) so a multi-GPU host can gather them
+    // with a single collective; the other planes are separate allocations
+    size_t off = 0;
+    for (int b = 0; b <= RT_BUF_FOG_RGBA8; b++) {
+        c->gbuffer_offset[b] = off;
+        off += (c->plane_pixels * kBytesPerPixel[b] + 255) / 256 * 256;
+    }
+    c->gbuffer_bytes = off;
+    for (int sl = 0; sl < c->nslots; sl++) {
+        FrameSlot& fs = c->slots[sl];
+        uint8_t* block = nullptr;
+        RT_HIP(c, dev_alloc(c, &block, off));
+        RT_HIP(c, hipMemset(block, 0, off));
+        fs.gbuffer = block;
+        for (int b = 0; b <= RT_BUF_FOG_RGBA8; b++) fs.planes[b] = block + c->gbuffer_offset[b];
+        for (int b = RT_BUF_FOG_RGBA8 + 1; b < RT_BUF_COUNT; b++) {
+            uint8_t* p = nullptr;
+            RT_HIP(c, dev_alloc(c, &p, c->plane_pixels * kBytesPerPixel[b]));
+            RT_HIP(c, hipMemset(p, 0, c->plane_pixels * kBytesPerPixel[b]));
+            fs.planes[b] = p;
+        }
+        RT_HIP(c, hipEventCreateWithFlags(&fs.ev_prepass, hipEventDisableTiming));
+        RT_HIP(c, hipEventCreateWithFlags(&fs.ev_acc, hipEventDisableTiming));
+        RT_HIP(c, hipEventCreateWithFlags(&fs.ev_tail, hipEventDisableTiming));
+    }
+    c->cur_slot = 0;
+    c->gbuffer = c->slots[0].gbuffer;
+    for (int b = 0; b < RT_BUF_COUNT; b++) c->planes[b] = c->slots[0].planes[b];
+    return RT_OK;
+}
+
+// the persistent family's per-lane and per-slot buffers, tables and light records (sets persist_batch)
+int create_persistent(RtContext* c) {
+    const RtConfig& cfg = c->cfg;
+    const size_t stack_words = (size_t)4 * c->num_cus * 1024 * (size_t)(cfg.depth > 1 ? cfg.depth - 1 : 1);   // up to 3 paths per lane
+    for (int l = 0; l < c->nlanes; l++) {
+        Lane& ln = c->lanes[l];
+        RT_HIP(c, dev_alloc(c, &ln.cursor, kCursorWords));
+        RT_HIP(c, hipMemset(ln.cursor, 0, kCursorWords * sizeof(uint32_t)));
+        ln.cursor_clean = true;
+        RT_HIP(c, dev_alloc(c, &ln.pstack, stack_words));
+    }
+    for (int sl = 0; sl < c->nslots; sl++) {
+        FrameSlot& fs = c->slots[sl];
+        RT_HIP(c, dev_alloc(c, &fs.wl_count, (size_t)64));   // two counters, 128 bytes apart
+        RT_HIP(c, hipMemset(fs.wl_count, 0, 64 * sizeof(uint32_t)));
+        fs.wl_clean[0] = fs.wl_clean[1] = true;
+        RT_HIP(c, dev_alloc(c, &fs.worklist, (size_t)c->npix_pad));
+        RT_HIP(c, dev_alloc(c, &fs.phit, (size_t)c->npix_pad));
+        RT_HIP(c, dev_alloc(c, &fs.pacc, (size_t)c->npix_pad));
+    }
+    RT_HIP(c, dev_alloc(c, &c->sphere_lut, (size_t)65536));
+    RT_HIP(c, dev_alloc(c, &c->sun_lut, (size_t)2 * 65536));
+    RT_HIP(c, dev_alloc(c, &c->dif_lut, (size_t)4 * 6 * 65536));
+    // Samples per path-kernel launch: bounded by 2^31 work items and by the memory given to the per-path light records, which is
+    // split between the lanes (a launch's records live until its accumulate launch has read them, and two launches are in flight).
+    // Round 3 sized one launch for 16 GiB because every launch paid its ramp-up and its drain (3840x2160 spp 256 depth 8: 114.1 ms
+    // per frame with 1 GiB, 109.3 with 2, 107.0 with 4, 105.6 with 8 and beyond); with the next launch taking the CUs the draining
+    // one frees, a launch's size matters far less (see kDefaultLightBytes).  Halved until the allocation succeeds.
+    const uint64_t np = c->npix_pad ? c->npix_pad : 1;
+    c->light_budget_bytes = rt_light_budget_bytes(getenv("RT_PERSIST_LIGHT_GIB"));
+    uint64_t B = rt_samples_per_launch(c->light_budget_bytes / (uint64_t)c->nlanes, np, (uint64_t)cfg.spp, getenv("RT_PERSIST_BATCH"));
+    for (int l = 0; l < c->nlanes; l++) {
+        for (;;) {
+            const hipError_t e = dev_alloc(c, &c->lanes[l].ppl, (size_t)np * B);
+            if (e == hipSuccess) break;
+            if (e != hipErrorOutOfMemory || B == 1 || l > 0) RT_HIP(c, e);   // (the lanes' buffers have one size)
+            (void)hipGetLastError();
+            B = (B + 1) / 2;
+        }
+    }
+    c->persist_batch = (uint32_t)B;
+    if (cfg.flags & RT_FLAG_ACCUMULATE) {
+        RT_HIP(c, dev_alloc(c, &c->d_accum, (size_t)c->npix_pad));
+        RT_HIP(c, hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming));
+    }
+    RT_HIP(c, rtd::launch_sphere_lut(c->sphere_lut, c->own_stream));
+    RT_HIP(c, rtd::launch_dif_lut(c->sphere_lut, c->dif_lut, c->own_stream));
+    RT_HIP(c, hipStreamSynchronize(c->own_stream));
+    return RT_OK;
+}
+
+// the wavefront baseline's queues
+int create_wavefront(RtContext* c) {
+    uint64_t target = 4u << 20;   // paths per batch
+    if (const char* s = getenv("RT_BATCH_PATHS")) { long long v = atoll(s); if (v > 0) target = (uint64_t)v; }
+    uint64_t B = c->npix_pad ? target / c->npix_pad : 1;
+    if (B < 1) B = 1;
+    if (B > (uint64_t)c->cfg.spp) B = (uint64_t)c->cfg.spp;
+    c->batch_samples = (uint32_t)B;
+    uint64_t cap64 = (uint64_t)c->npix_pad * B;
+    if (cap64 >= (1ull << 31)) return fail(c, RT_ERR_INVALID_ARG, "rt_create: batch too large");
+    c->cap = (uint32_t)cap64;
+    const size_t cap = c->cap;
+    RT_HIP(c, dev_alloc(c, &c->qox, cap)); RT_HIP(c, dev_alloc(c, &c->qoy, cap)); RT_HIP(c, dev_alloc(c, &c->qoz, cap));
+    RT_HIP(c, dev_alloc(c, &c->qdx, 2 * cap)); RT_HIP(c, dev_alloc(c, &c->qdy, 2 * cap)); RT_HIP(c, dev_alloc(c, &c->qdz, 2 * cap));
+    RT_HIP(c, dev_alloc(c, &c->qid, cap));
+    RT_HIP(c, dev_alloc(c, &c->hx, cap)); RT_HIP(c, dev_alloc(c, &c->hy, cap)); RT_HIP(c, dev_alloc(c, &c->hz, cap));
+    RT_HIP(c, dev_alloc(c, &c->hinfo, cap));
+    RT_HIP(c, dev_alloc(c, &c->sunres, cap)); RT_HIP(c, dev_alloc(c, &c->pnormal, cap)); RT_HIP(c, dev_alloc(c, &c->pstate, cap));
+    RT_HIP(c, dev_alloc(c, &c->pdx, cap)); RT_HIP(c, dev_alloc(c, &c->pdy, cap)); RT_HIP(c, dev_alloc(c, &c->pdz, cap));
+    RT_HIP(c, dev_alloc(c, &c->plx, cap)); RT_HIP(c, dev_alloc(c, &c->ply, cap)); RT_HIP(c, dev_alloc(c, &c->plz, cap));
+    RT_HIP(c, dev_alloc(c, &c->sunbits, cap));
+    RT_HIP(c, dev_alloc(c, &c->stack, cap * (size_t)(c->cfg.depth > 1 ? c->cfg.depth - 1 : 1)));
+    RT_HIP(c, dev_alloc(c, &c->acc, (size_t)c->npix_pad));
+    RT_HIP(c, dev_alloc(c, &c->ctrl, (size_t)2 * (RT_MAX_DEPTH + 2)));
+    return RT_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -463,42 +921,15 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
 
     RtContext* c = new (std::nothrow) RtContext();
     if (!c) return fail(nullptr, RT_ERR_OOM, "rt_create: host allocation failed");
-    auto bail = [&](int code, const std::string& msg) { g_create_error = msg; rt_destroy(c); return code; };
-#define RT_HIP_CREATE(call)                                                                                        \
-    do { hipError_t e_ = (call); if (e_ != hipSuccess)                                                             \
-        return bail(e_ == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
     c->cfg = *cfg;
     c->device = cfg->device;
     c->region = cfg->region;
     c->logr = cfg->region == 256 ? 8 : (cfg->region == 512 ? 9 : 10);
     c->vox = (size_t)cfg->region * cfg->region * cfg->region;
-    {
-        // RT_KERNEL_DEFAULT = k_paths (two paths, four ray slots per lane, branch-free step loop); the frames it does not
-        // cover run on k_persist (rt_draw_frame decides per frame: lr is a per-frame uniform)
-        c->paths_by_size = cfg->kernel == RT_KERNEL_DEFAULT;
-        // k_frame (one launch per frame) takes the small frames of RT_KERNEL_DEFAULT and whatever it covers of RT_KERNEL_FRAME; the
-        // rest of those contexts' frames go the persistent way, so they hold its buffers as well
-        c->frame_mode = cfg->kernel == RT_KERNEL_FRAME ? 2 : (cfg->kernel == RT_KERNEL_DEFAULT ? 1 : 0);
-        if (const char* s = getenv("RT_FRAME_CROSSOVER")) { long long v = atoll(s); if (v >= 0) c->frame_crossover = (uint64_t)v; }
-        if (const char* s = getenv("RT_FRAME_CROSSOVER_MULTI")) { long long v = atoll(s); if (v >= 0) c->frame_crossover_multi = (uint64_t)v; }
-        if (const char* s = getenv("RT_FRAME_THRESHOLD")) { int v = atoi(s); if (v >= 1 && v <= 64) c->frame_threshold = (uint32_t)v; }
-        if (const char* s = getenv("RT_FRAME_TILES")) { int v = atoi(s); if (v >= 1 && v <= 4) c->frame_tiles = 4u * (uint32_t)v; }           // per wave
-        if (const char* s = getenv("RT_FRAME_GROUP_TILES")) { int v = atoi(s); if (v >= 1 && v <= 16) c->frame_tiles = (uint32_t)v; }     // per four-wave workgroup
-        c->kernel = (cfg->kernel == RT_KERNEL_DEFAULT || cfg->kernel == RT_KERNEL_FRAME) ? RT_KERNEL_PATHS : cfg->kernel;
-        if (c->kernel == RT_KERNEL_PATHS) { c->kernel = RT_KERNEL_PERSISTENT; c->persist_version = 3; }
-    }
-    RT_HIP_CREATE(hipSetDevice(c->device));
-    hipDeviceProp_t prop;
-    RT_HIP_CREATE(hipGetDeviceProperties(&prop, c->device));
-    c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    // RT_RESERVE_CUS=n: the persistent kernels (one workgroup per CU) leave n CUs free, e.g. for an RCCL kernel running
-    // beside them (bench.py's overlapped gather)
-    if (const char* s = getenv("RT_RESERVE_CUS")) { int v = atoi(s); if (v > 0 && v < c->num_cus) c->num_cus -= v; }
-    RT_HIP_CREATE(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
-    RT_HIP_CREATE(hipEventCreate(&c->ev_frame0));
-    RT_HIP_CREATE(hipEventCreate(&c->ev_frame1));
+    // RT_KERNEL_DEFAULT, FRAME, PATHS and PERSISTENT all run the persistent family (k_frame, k_persist, k_paths): resolve_route
+    // decides which kernel takes what once the samples per launch are known
+    c->route.family = (cfg->kernel == RT_KERNEL_MEGA || cfg->kernel == RT_KERNEL_WAVEFRONT) ? cfg->kernel : RT_KERNEL_PERSISTENT;
+    const bool persistent = c->route.family == RT_KERNEL_PERSISTENT;
 
     // tiling: 8x8-pixel tiles dealt round-robin over tile_world contexts
     c->tiles_x = (cfg->width + 7) / 8; c->tiles_y = (cfg->height + 7) / 8;
@@ -509,140 +940,36 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
     c->npix_pad = (uint32_t)c->ntiles_local * 64u;
     c->plane_pixels = cfg->tile_world == 1 ? (size_t)cfg->width * cfg->height : (size_t)c->tile_capacity * 64;
 
-    // scene
-    RT_HIP_CREATE(dev_alloc(c, &c->d_mine_sw, c->vox)); RT_HIP_CREATE(dev_alloc(c, &c->d_mat_sw, c->vox));
-    RT_HIP_CREATE(dev_alloc(c, &c->d_coarse, (size_t)rtd::kCoarseWords));
-    // (the per-brick map of a -DRT_PATHS_BRICK_MAP=1 build of k_paths: an experiment that lost, profiles/r4_c5_brick_map.txt)
-    if (c->logr > 8 && getenv("RT_BRICK_MAP")) RT_HIP_CREATE(dev_alloc(c, &c->d_brick, c->vox / 128u / 4u));
-    RT_HIP_CREATE(dev_alloc(c, &c->d_noise, (size_t)RT_NOISE_SIZE * RT_NOISE_SIZE));
-    RT_HIP_CREATE(dev_alloc(c, &c->d_flag, 4));
-    RT_HIP_CREATE(dev_alloc(c, &c->d_counters, 1));
-    RT_HIP_CREATE(hipMemset(c->d_counters, 0, sizeof(rtd::DevCounters)));
-
     // lanes and frame slots (see Lane / FrameSlot).  Two lanes for the persistent kernels; two slots when the host asks for two
-    // frames in flight.  RT_LANES=1 / RT_FRAMES_IN_FLIGHT=1|2 override (experiments, A/B timing).
-    const bool persistent = cfg->kernel == RT_KERNEL_DEFAULT || cfg->kernel == RT_KERNEL_PERSISTENT || cfg->kernel == RT_KERNEL_PATHS || cfg->kernel == RT_KERNEL_FRAME;
+    // frames in flight.
     c->nlanes = persistent ? 2 : 1;
     c->nslots = (persistent && (cfg->flags & RT_FLAG_FRAMES_IN_FLIGHT_2)) ? 2 : 1;
+    // environment knobs (experiments, A/B timing); those that size allocations are read where the allocation is made
     if (const char* s = getenv("RT_LANES")) { int v = atoi(s); if (v == 1 || (v == 2 && persistent)) c->nlanes = v; }
     if (const char* s = getenv("RT_FRAMES_IN_FLIGHT")) { int v = atoi(s); if (v == 1 || (v == 2 && persistent)) c->nslots = v; }
     if (c->nlanes < 2) c->nslots = 1;
-    c->lanes[0].stream = c->own_stream;
-    if (c->nlanes == 2) RT_HIP_CREATE(hipStreamCreateWithFlags(&c->lanes[1].stream, hipStreamNonBlocking));
-    for (int l = 0; l < c->nlanes; l++) RT_HIP_CREATE(hipEventCreateWithFlags(&c->lanes[l].ev_join, hipEventDisableTiming));
-    RT_HIP_CREATE(hipEventCreateWithFlags(&c->ev_fence, hipEventDisableTiming));
-    RT_HIP_CREATE(hipEventCreateWithFlags(&c->ev_gather, hipEventDisableTiming));
-
-    {   // the six reference-format planes of a slot live in ONE block (each padded to 256 B) so a multi-GPU host can gather them
-        // with a single collective; the other planes are separate allocations
-        size_t off = 0;
-        for (int b = 0; b <= RT_BUF_FOG_RGBA8; b++) {
-            c->gbuffer_offset[b] = off;
-            off += (c->plane_pixels * kBytesPerPixel[b] + 255) / 256 * 256;
-        }
-        c->gbuffer_bytes = off;
-        for (int sl = 0; sl < c->nslots; sl++) {
-            FrameSlot& fs = c->slots[sl];
-            uint8_t* block = nullptr;
-            RT_HIP_CREATE(dev_alloc(c, &block, off));
-            RT_HIP_CREATE(hipMemset(block, 0, off));
-            fs.gbuffer = block;
-            for (int b = 0; b <= RT_BUF_FOG_RGBA8; b++) fs.planes[b] = block + c->gbuffer_offset[b];
-            for (int b = RT_BUF_FOG_RGBA8 + 1; b < RT_BUF_COUNT; b++) {
-                uint8_t* p = nullptr;
-                RT_HIP_CREATE(dev_alloc(c, &p, c->plane_pixels * kBytesPerPixel[b]));
-                RT_HIP_CREATE(hipMemset(p, 0, c->plane_pixels * kBytesPerPixel[b]));
-                fs.planes[b] = p;
-            }
-            RT_HIP_CREATE(hipEventCreateWithFlags(&fs.ev_prepass, hipEventDisableTiming));
-            RT_HIP_CREATE(hipEventCreateWithFlags(&fs.ev_acc, hipEventDisableTiming));
-            RT_HIP_CREATE(hipEventCreateWithFlags(&fs.ev_tail, hipEventDisableTiming));
-        }
-        c->cur_slot = 0;
-        c->gbuffer = c->slots[0].gbuffer;
-        for (int b = 0; b < RT_BUF_COUNT; b++) c->planes[b] = c->slots[0].planes[b];
-    }
-
+    if (const char* s = getenv("RT_FRAME_CROSSOVER")) { long long v = atoll(s); if (v >= 0) c->frame_crossover = (uint64_t)v; }
+    if (const char* s = getenv("RT_FRAME_CROSSOVER_MULTI")) { long long v = atoll(s); if (v >= 0) c->frame_crossover_multi = (uint64_t)v; }
+    if (const char* s = getenv("RT_FRAME_THRESHOLD")) { int v = atoi(s); if (v >= 1 && v <= 64) c->frame_threshold = (uint32_t)v; }
+    if (const char* s = getenv("RT_FRAME_TILES")) { int v = atoi(s); if (v >= 1 && v <= 4) c->frame_tiles = 4u * (uint32_t)v; }           // per wave
+    if (const char* s = getenv("RT_FRAME_GROUP_TILES")) { int v = atoi(s); if (v >= 1 && v <= 16) c->frame_tiles = (uint32_t)v; }     // per four-wave workgroup
     if (const char* s = getenv("RT_REFILL_THRESHOLD")) { int v = atoi(s); if (v >= 1 && v <= 64) c->refill_threshold = (uint32_t)v; }
     if (const char* s = getenv("RT_PRIMARY_V")) { int v = atoi(s); if (v == 1 || v == 2) c->primary_version = v; }
     if (const char* s = getenv("RT_PERSIST_THRESHOLD")) { int v = atoi(s); if (v >= 1 && v <= 64) c->persist_threshold = (uint32_t)v; }
     if (const char* s = getenv("RT_PL_STREAM")) { int v = atoi(s); if (v >= 0 && v <= 3) c->pl_stream_mode = v; }
     if (const char* s = getenv("RT_PERSIST_CHUNK")) { int v = atoi(s); if (v >= 64 && v <= 4096) c->persist_chunk = (uint32_t)v & ~63u; }
     if (const char* s = getenv("RT_PERSIST_RMIN")) { int v = atoi(s); if (v >= 1 && v <= 128) c->persist_rmin = (uint32_t)v; }
-    if (c->kernel == RT_KERNEL_PERSISTENT) {
-        const size_t stack_words = (size_t)4 * c->num_cus * 1024 * (size_t)(cfg->depth > 1 ? cfg->depth - 1 : 1);   // up to 3 paths per lane
-        for (int l = 0; l < c->nlanes; l++) {
-            Lane& ln = c->lanes[l];
-            RT_HIP_CREATE(dev_alloc(c, &ln.cursor, kCursorWords));
-            RT_HIP_CREATE(hipMemset(ln.cursor, 0, kCursorWords * sizeof(uint32_t)));
-            ln.cursor_clean = true;
-            RT_HIP_CREATE(dev_alloc(c, &ln.pstack, stack_words));
-        }
-        for (int sl = 0; sl < c->nslots; sl++) {
-            FrameSlot& fs = c->slots[sl];
-            RT_HIP_CREATE(dev_alloc(c, &fs.wl_count, (size_t)64));   // two counters, 128 bytes apart
-            RT_HIP_CREATE(hipMemset(fs.wl_count, 0, 64 * sizeof(uint32_t)));
-            fs.wl_clean[0] = fs.wl_clean[1] = true;
-            RT_HIP_CREATE(dev_alloc(c, &fs.worklist, (size_t)c->npix_pad));
-            RT_HIP_CREATE(dev_alloc(c, &fs.phit, (size_t)c->npix_pad));
-            RT_HIP_CREATE(dev_alloc(c, &fs.pacc, (size_t)c->npix_pad));
-        }
-        RT_HIP_CREATE(dev_alloc(c, &c->sphere_lut, (size_t)65536));
-        RT_HIP_CREATE(dev_alloc(c, &c->sun_lut, (size_t)2 * 65536));
-        RT_HIP_CREATE(dev_alloc(c, &c->dif_lut, (size_t)4 * 6 * 65536));
-        {   // Samples per path-kernel launch: bounded by 2^31 work items and by the memory given to the per-path light records, which
-            // is split between the lanes (a launch's records live until its accumulate launch has read them, and two launches are in
-            // flight).  Round 3 sized one launch for 16 GiB because every launch paid its ramp-up and its drain (3840x2160 spp 256
-            // depth 8: 114.1 ms per frame with 1 GiB, 109.3 with 2, 107.0 with 4, 105.6 with 8 and beyond); with the next launch
-            // taking the CUs the draining one frees, a launch's size matters far less (see kDefaultLightBytes).  Halved until the
-            // allocation succeeds.
-            uint64_t np = c->npix_pad ? c->npix_pad : 1;
-            c->light_budget_bytes = rt_light_budget_bytes(getenv("RT_PERSIST_LIGHT_GIB"));
-            uint64_t B = rt_samples_per_launch(c->light_budget_bytes / (uint64_t)c->nlanes, np, (uint64_t)cfg->spp, getenv("RT_PERSIST_BATCH"));
-            for (int l = 0; l < c->nlanes; l++) {
-                for (;;) {
-                    const hipError_t e = dev_alloc(c, &c->lanes[l].ppl, (size_t)np * B);
-                    if (e == hipSuccess) break;
-                    if (e != hipErrorOutOfMemory || B == 1 || l > 0) RT_HIP_CREATE(e);   // (the lanes' buffers have one size)
-                    (void)hipGetLastError();
-                    B = (B + 1) / 2;
-                }
-            }
-            c->persist_batch = (uint32_t)B;
-        }
-        if (cfg->flags & RT_FLAG_ACCUMULATE) {
-            RT_HIP_CREATE(dev_alloc(c, &c->d_accum, (size_t)c->npix_pad));
-            RT_HIP_CREATE(hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming));
-        }
-        RT_HIP_CREATE(rtd::launch_sphere_lut(c->sphere_lut, c->own_stream));
-        RT_HIP_CREATE(rtd::launch_dif_lut(c->sphere_lut, c->dif_lut, c->own_stream));
-        RT_HIP_CREATE(hipStreamSynchronize(c->own_stream));
+
+    int rc = create_device(c);
+    if (rc == RT_OK) rc = create_slots(c);
+    if (rc == RT_OK && persistent) rc = create_persistent(c);
+    if (rc == RT_OK && c->route.family == RT_KERNEL_WAVEFRONT) rc = create_wavefront(c);
+    if (rc != RT_OK) {
+        g_create_error = c->err;
+        rt_destroy(c);
+        return rc;
     }
-    if (c->kernel == RT_KERNEL_WAVEFRONT) {
-        uint64_t target = 4u << 20;   // paths per batch
-        if (const char* s = getenv("RT_BATCH_PATHS")) { long long v = atoll(s); if (v > 0) target = (uint64_t)v; }
-        uint64_t B = c->npix_pad ? target / c->npix_pad : 1;
-        if (B < 1) B = 1;
-        if (B > (uint64_t)cfg->spp) B = (uint64_t)cfg->spp;
-        c->batch_samples = (uint32_t)B;
-        uint64_t cap64 = (uint64_t)c->npix_pad * B;
-        if (cap64 >= (1ull << 31)) return bail(RT_ERR_INVALID_ARG, "rt_create: batch too large");
-        c->cap = (uint32_t)cap64;
-        const size_t cap = c->cap;
-        RT_HIP_CREATE(dev_alloc(c, &c->qox, cap)); RT_HIP_CREATE(dev_alloc(c, &c->qoy, cap)); RT_HIP_CREATE(dev_alloc(c, &c->qoz, cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->qdx, 2 * cap)); RT_HIP_CREATE(dev_alloc(c, &c->qdy, 2 * cap)); RT_HIP_CREATE(dev_alloc(c, &c->qdz, 2 * cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->qid, cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->hx, cap)); RT_HIP_CREATE(dev_alloc(c, &c->hy, cap)); RT_HIP_CREATE(dev_alloc(c, &c->hz, cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->hinfo, cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->sunres, cap)); RT_HIP_CREATE(dev_alloc(c, &c->pnormal, cap)); RT_HIP_CREATE(dev_alloc(c, &c->pstate, cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->pdx, cap)); RT_HIP_CREATE(dev_alloc(c, &c->pdy, cap)); RT_HIP_CREATE(dev_alloc(c, &c->pdz, cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->plx, cap)); RT_HIP_CREATE(dev_alloc(c, &c->ply, cap)); RT_HIP_CREATE(dev_alloc(c, &c->plz, cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->sunbits, cap));
-        RT_HIP_CREATE(dev_alloc(c, &c->stack, cap * (size_t)(cfg->depth > 1 ? cfg->depth - 1 : 1)));
-        RT_HIP_CREATE(dev_alloc(c, &c->acc, (size_t)c->npix_pad));
-        RT_HIP_CREATE(dev_alloc(c, &c->ctrl, (size_t)2 * (RT_MAX_DEPTH + 2)));
-    }
-#undef RT_HIP_CREATE
+    resolve_route(c);
     *out = c;
     return RT_OK;
 }
@@ -657,17 +984,10 @@ void rt_destroy(RtContext* ctx) {
     for (FrameSlot& fs : ctx->slots) for (hipEvent_t e : {fs.ev_prepass, fs.ev_acc, fs.ev_tail}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {ctx->ev_fence, ctx->ev_gather, ctx->ev_accum}) if (e) (void)hipEventDestroy(e);
     if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); (void)hipStreamDestroy(ctx->upload_stream); }
-    for (int k = 0; k < 2; k++) {
-        if (ctx->ev_edit_copied[k]) (void)hipEventDestroy(ctx->ev_edit_copied[k]);
-        if (ctx->ev_edit_applied[k]) (void)hipEventDestroy(ctx->ev_edit_applied[k]);
-        if (ctx->h_edit[k]) (void)hipHostFree(ctx->h_edit[k]);
-        if (ctx->d_edit[k]) (void)hipFree(ctx->d_edit[k]);
-    }
-    for (int k = 0; k < 2; k++) {
-        if (ctx->ev_slab_copied[k]) (void)hipEventDestroy(ctx->ev_slab_copied[k]);
-        if (ctx->ev_slab_applied[k]) (void)hipEventDestroy(ctx->ev_slab_applied[k]);
-        if (ctx->h_slab_mat[k]) (void)hipHostFree(ctx->h_slab_mat[k]);
-        if (ctx->h_slab_mine[k]) (void)hipHostFree(ctx->h_slab_mine[k]);
+    for (StagingSet* s : {&ctx->slab_sets[0], &ctx->slab_sets[1], &ctx->edit_sets[0], &ctx->edit_sets[1]}) {
+        for (hipEvent_t e : {s->ev_copied, s->ev_applied}) if (e) (void)hipEventDestroy(e);
+        if (s->host) (void)hipHostFree(s->host);
+        if (s->dev) (void)hipFree(s->dev);
     }
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -723,33 +1043,17 @@ int rt_upload_world(RtContext* ctx, const uint32_t* materials, const uint8_t* mi
     return RT_OK;
 }
 
-namespace {
-// staging of rt_upload_slice, created on first use: pinned host memory for one slab (the reference's upload buffers are
-// host-visible mapped Vulkan buffers, terrain_upload.rs:65-82), its device twin, a stream for the transfer and two events
-int slab_resources(RtContext* ctx) {
-    const size_t n = (size_t)RT_SLICE_SIZE * (size_t)ctx->region * (size_t)ctx->region;
-    for (int k = 0; k < 2; k++) {
-        if (!ctx->d_slab_mat[k]) RT_HIP(ctx, dev_alloc(ctx, &ctx->d_slab_mat[k], n));
-        if (!ctx->d_slab_mine[k]) RT_HIP(ctx, dev_alloc(ctx, &ctx->d_slab_mine[k], n));
-        if (!ctx->h_slab_mat[k]) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_slab_mat[k], n * sizeof(uint32_t), hipHostMallocDefault));
-        if (!ctx->h_slab_mine[k]) RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_slab_mine[k], n, hipHostMallocDefault));
-        if (!ctx->ev_slab_copied[k]) RT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_slab_copied[k], hipEventDisableTiming));
-        if (!ctx->ev_slab_applied[k]) RT_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_slab_applied[k], hipEventDisableTiming));
-    }
-    if (!ctx->upload_stream) RT_HIP(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
-    return RT_OK;
-}
-}  // namespace
-
 int rt_slice_staging(RtContext* ctx, uint32_t** materials, uint8_t** minefield) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_slice_staging: null pointer");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = slab_resources(ctx);
-    if (rc != RT_OK) return rc;
-    const int k = (int)(ctx->slabs & 1u);   // the set the NEXT rt_upload_slice uses
-    if (ctx->slab_copy_pending[k]) { RT_HIP(ctx, hipEventSynchronize(ctx->ev_slab_copied[k])); ctx->slab_copy_pending[k] = false; }   // the slab before last has left it
-    *materials = ctx->h_slab_mat[k]; *minefield = ctx->h_slab_mine[k];
+    // staging of one slab: pinned host memory (the reference's upload buffers are host-visible mapped Vulkan buffers,
+    // terrain_upload.rs:65-82) holding the materials, then the minefield, and its device twin
+    const size_t n = (size_t)RT_SLICE_SIZE * (size_t)ctx->region * (size_t)ctx->region;
+    StagingSet& s = ctx->slab_sets[ctx->slabs & 1u];   // the set the NEXT rt_upload_slice uses: the slab before last has left it
+    RT_HIP(ctx, staging_claim(ctx, s, 5 * n, 5 * n));
+    *materials = reinterpret_cast<uint32_t*>(s.host);
+    *minefield = s.host + 4 * n;
     return RT_OK;
 }
 
@@ -762,16 +1066,14 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: bad axis or offset");
     if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_upload_slice: upload the full region first");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = slab_resources(ctx);
-    if (rc != RT_OK) return rc;
     // Incremental and asynchronous.  The slab goes pinned host staging -> device staging (5 bytes x 16 x R^2) on the upload
     // stream; the render stream waits for that event (not the host), then ONE launch re-tiles the slab's 16 R^2 voxels into the
     // brick-swizzled arrays and a second rebuilds the nibble-map words it touches.  Frames in flight keep reading the region
     // until then by stream order — the host waits for nothing on the device (the reference blocks on vkQueueWaitIdle here,
     // pipeline.rs:181-189); only a previous slab still leaving the pinned staging is waited for.
     const size_t n = (size_t)RT_SLICE_SIZE * kR * kR;
-    const int k = (int)(ctx->slabs & 1u);
-    if (ctx->slab_copy_pending[k]) { RT_HIP(ctx, hipEventSynchronize(ctx->ev_slab_copied[k])); ctx->slab_copy_pending[k] = false; }
+    StagingSet& s = ctx->slab_sets[ctx->slabs & 1u];
+    RT_HIP(ctx, staging_claim(ctx, s, 5 * n, 5 * n));
     if ((ctx->cfg.flags & RT_FLAG_TRUSTED_WORLD) == 0) {
         // values above 30 are rejected as in rt_upload_world — BEFORE anything is written or transferred: a rejected slab leaves
         // the region (and what can be drawn) as it was.  The bytes are in host memory, so the check is a host loop over 16 R^2
@@ -781,24 +1083,18 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
         if (worst > rtd::kMaxStepValue)
             return fail(ctx, RT_ERR_INVALID_ARG, "minefield slab holds a value above 30 (the reference writes 0..6, src/world/chunk.rs:163-183); the region is unchanged");
     }
-    if (materials != ctx->h_slab_mat[k]) memcpy(ctx->h_slab_mat[k], materials, n * sizeof(uint32_t));   // borrowed buffers are released at return;
-    if (minefield != ctx->h_slab_mine[k]) memcpy(ctx->h_slab_mine[k], minefield, n);                     // rt_slice_staging's pointers need no copy
-    if (ctx->slab_apply_recorded[k]) RT_HIP(ctx, hipStreamWaitEvent(ctx->upload_stream, ctx->ev_slab_applied[k], 0));   // the re-tile of the slab before last has read this device staging
-    RT_HIP(ctx, hipMemcpyAsync(ctx->d_slab_mine[k], ctx->h_slab_mine[k], n, hipMemcpyHostToDevice, ctx->upload_stream));
-    RT_HIP(ctx, hipMemcpyAsync(ctx->d_slab_mat[k], ctx->h_slab_mat[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->upload_stream));
-    RT_HIP(ctx, hipEventRecord(ctx->ev_slab_copied[k], ctx->upload_stream));
-    ctx->slab_copy_pending[k] = true;
+    uint32_t* h_mat = reinterpret_cast<uint32_t*>(s.host);
+    uint8_t* h_mine = s.host + 4 * n;
+    if (materials != h_mat) memcpy(h_mat, materials, n * sizeof(uint32_t));   // borrowed buffers are released at return;
+    if (minefield != h_mine) memcpy(h_mine, minefield, n);                     // rt_slice_staging's pointers need no copy
     ctx->slabs++;
-    RT_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_slab_copied[k], 0));
-    RT_HIP(ctx, join_lanes_into(ctx, ctx->stream));   // frames in flight on the other lane read the region too
+    RT_HIP(ctx, staging_send(ctx, s, 5 * n));
     {
         LaunchTimer t(ctx, 1);
-        RT_HIP(ctx, rtd::launch_flatten_slab(ctx->d_slab_mine[k], ctx->d_slab_mat[k], ctx->d_mine_sw, ctx->d_mat_sw, ctx->d_coarse,
-                                             ctx->d_brick, ctx->logr, axis, texel_offset, ctx->stream));
+        RT_HIP(ctx, rtd::launch_flatten_slab(s.dev + 4 * n, reinterpret_cast<const uint32_t*>(s.dev), ctx->d_mine_sw, ctx->d_mat_sw,
+                                             ctx->d_coarse, ctx->d_brick, ctx->logr, axis, texel_offset, ctx->stream));
     }
-    RT_HIP(ctx, hipEventRecord(ctx->ev_slab_applied[k], ctx->stream));
-    ctx->slab_apply_recorded[k] = true;
-    RT_HIP(ctx, fence_lanes_after(ctx, ctx->stream));   // ... and later frames, whichever lane they start on, see the slab
+    RT_HIP(ctx, staging_applied(ctx, s));
     return RT_OK;
 }
 
@@ -838,25 +1134,13 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
     const size_t need = off_recs + (size_t)count * 8u;
 
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->upload_stream) RT_HIP(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
-    const int k = (int)(ctx->edit_batches & 1u);
-    for (hipEvent_t* ev : {&ctx->ev_edit_copied[k], &ctx->ev_edit_applied[k]})
-        if (!*ev) RT_HIP(ctx, hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    if (ctx->edit_copy_pending[k]) { RT_HIP(ctx, hipEventSynchronize(ctx->ev_edit_copied[k])); ctx->edit_copy_pending[k] = false; }   // the batch before last has left it
-    if (need > ctx->edit_cap[k]) {   // grow the set: its device twin may still be read by the batch before last's rebuild
-        if (ctx->edit_apply_recorded[k]) RT_HIP(ctx, hipEventSynchronize(ctx->ev_edit_applied[k]));
-        if (ctx->h_edit[k]) { (void)hipHostFree(ctx->h_edit[k]); ctx->h_edit[k] = nullptr; }
-        if (ctx->d_edit[k]) { (void)hipFree(ctx->d_edit[k]); ctx->d_edit[k] = nullptr; }
-        ctx->edit_cap[k] = 0;
-        size_t cap = need < ((size_t)64 << 10) ? ((size_t)64 << 10) : need;
-        if (cap < need + need / 2u) cap = align16(need + need / 2u);
-        RT_HIP(ctx, hipHostMalloc((void**)&ctx->h_edit[k], cap, hipHostMallocDefault));
-        RT_HIP(ctx, hipMalloc((void**)&ctx->d_edit[k], cap));
-        ctx->edit_cap[k] = cap;
-    }
+    StagingSet& s = ctx->edit_sets[ctx->edit_batches & 1u];
+    size_t cap = need < ((size_t)64 << 10) ? ((size_t)64 << 10) : need;   // (if the set must grow)
+    if (cap < need + need / 2u) cap = align16(need + need / 2u);
+    RT_HIP(ctx, staging_claim(ctx, s, need, cap));
     // Staging: touched chunk ids, their edit ranges, and per chunk one record per edited voxel — its last edit in the batch (the
     // range is walked backwards; edit_stamp marks the voxels a chunk's run has kept).
-    uint8_t* h = ctx->h_edit[k];
+    uint8_t* h = s.host;
     uint32_t* h_chunks = reinterpret_cast<uint32_t*>(h);
     uint32_t* h_offs = reinterpret_cast<uint32_t*>(h + off_offs);
     uint32_t* h_recs = reinterpret_cast<uint32_t*>(h + off_recs);
@@ -883,17 +1167,12 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
     h_offs[t] = nrec;
     // Transfer on the upload stream, then the rebuild on the render stream after the frames already submitted (every lane), and
     // later frames after the rebuild — the ordering of rt_upload_slice.
-    if (ctx->edit_apply_recorded[k]) RT_HIP(ctx, hipStreamWaitEvent(ctx->upload_stream, ctx->ev_edit_applied[k], 0));
-    RT_HIP(ctx, hipMemcpyAsync(ctx->d_edit[k], h, off_recs + (size_t)nrec * 8u, hipMemcpyHostToDevice, ctx->upload_stream));
-    RT_HIP(ctx, hipEventRecord(ctx->ev_edit_copied[k], ctx->upload_stream));
-    ctx->edit_copy_pending[k] = true;
     ctx->edit_batches++;
     ctx->accum_valid = false;
-    RT_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_edit_copied[k], 0));
-    RT_HIP(ctx, join_lanes_into(ctx, ctx->stream));
-    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(ctx->d_edit[k]);
-    const uint32_t* d_offs = reinterpret_cast<const uint32_t*>(ctx->d_edit[k] + off_offs);
-    const uint2* d_recs = reinterpret_cast<const uint2*>(ctx->d_edit[k] + off_recs);
+    RT_HIP(ctx, staging_send(ctx, s, off_recs + (size_t)nrec * 8u));
+    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
+    const uint32_t* d_offs = reinterpret_cast<const uint32_t*>(s.dev + off_offs);
+    const uint2* d_recs = reinterpret_cast<const uint2*>(s.dev + off_recs);
     {
         LaunchTimer lt(ctx, 1);
         RT_HIP(ctx, rtd::launch_rebuild_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, d_offs, d_recs, touched, ctx->logr, ctx->stream));
@@ -902,9 +1181,7 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
         LaunchTimer lt(ctx, 1);
         RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, touched, ctx->logr, ctx->stream));
     }
-    RT_HIP(ctx, hipEventRecord(ctx->ev_edit_applied[k], ctx->stream));
-    ctx->edit_apply_recorded[k] = true;
-    RT_HIP(ctx, fence_lanes_after(ctx, ctx->stream));
+    RT_HIP(ctx, staging_applied(ctx, s));
     return RT_OK;
 }
 
@@ -961,201 +1238,13 @@ int rt_draw_frame(RtContext* ctx, const RtUniforms* u) {
     // the last kernel of one frame and the first of the next is 4-5 us during which the GPU idles (profiles/r3_frame_timeline.txt)
     const bool frame_events = (ctx->cfg.flags & RT_FLAG_TIMING_ALL) == RT_FLAG_TIMING_ALL;
     int rc = RT_OK;
-    if (ctx->kernel == RT_KERNEL_MEGA) {
+    if (ctx->route.family == RT_KERNEL_MEGA) {
         if (frame_events) RT_HIP(ctx, hipEventRecord(ctx->ev_frame0, ctx->stream));
         LaunchTimer t(ctx, 0);
         hipError_t e = rtd::launch_mega(scene_of(ctx), f, planes_of(ctx), ctx->d_counters, count, ctx->stream);
         if (e != hipSuccess) rc = fail(ctx, RT_ERR_HIP, std::string("launch_mega: ") + hipGetErrorString(e));
-    } else if (ctx->kernel == RT_KERNEL_PERSISTENT) {
-        const bool cache = (ctx->cfg.flags & RT_FLAG_CACHE_PRIMARY) != 0;
-        const int nl = ctx->user_stream ? 1 : ctx->nlanes, nsl = ctx->user_stream ? 1 : ctx->nslots;
-        hipError_t e = hipSuccess;
-        // What the host put behind the previous frame since (post passes, gather, a slab) belongs to that frame's use of its slot.
-        FrameSlot& prev = ctx->slots[ctx->cur_slot];
-        if (ctx->frame_recorded) { e = hipEventRecord(prev.ev_tail, ctx->stream); prev.tail_recorded = e == hipSuccess; }
-        // This frame's slot, and the lane its prepass and first path launch go to (launches alternate between the lanes).
-        const int si = nsl == 2 ? (int)(ctx->frames_drawn & 1u) : 0;
-        FrameSlot& fs = ctx->slots[si];
-        // (a one-slot context whose frames are one launch each stays on lane 0: frame k + 1 cannot start before frame k has finished
-        // with the slot, so alternating would only put an event wait between two streams in front of every frame)
-        const bool one_lane = nsl == 1 && (uint32_t)ctx->cfg.spp <= ctx->persist_batch;
-        Lane* L0 = &ctx->lanes[one_lane ? 0u : ctx->path_launches % (uint64_t)nl];
-        const hipStream_t st0 = L0->stream;
-        // the frame that used the slot before (frame k - 2 with two slots, k - 1 with one) has finished with it
-        if (e == hipSuccess && fs.tail_recorded) e = hipStreamWaitEvent(st0, fs.ev_tail, 0);
-        if (e == hipSuccess && frame_events) e = hipEventRecord(ctx->ev_frame0, st0);
-        const rtd::Planes fpl = planes_of(fs.planes);
-        // worklist counter of this frame: clean already if the slot's previous frame's prepass cleared it, otherwise cleared here
-        uint32_t* const wlc = fs.wl_count + 32 * fs.wl_parity;
-        uint32_t* const wln = fs.wl_count + 32 * (fs.wl_parity ^ 1);
-        const bool prepass_clears = cache && ctx->primary_version == 2 && ctx->npix_pad != 0;
-        // RT_FLAG_ACCUMULATE: does this frame continue the running sum, and how many samples will it hold (the lighting's divisor)?
-        // One-sample frames add theirs in k_accumulate_frame after the frame's launches.  Frames of more samples continue the ordered
-        // sum from the running one: k_accumulate_frame for the pixels the prepass finishes, k_accumulate_paths<.., ACCUM> for the
-        // paths' (its first batch starts from the running sum, its last stores it back) — so they do not run on k_frame, whose
-        // workgroups add a pixel's samples from 0.  The step that touches the sum follows the previous frame's (ev_accum), not the
-        // whole previous frame.
-        const bool accum = ctx->d_accum != nullptr;
-        const uint32_t spp_u = (uint32_t)ctx->cfg.spp;
-        uint32_t key[16];
-        accum_key_of(u, key);
-        const bool accum_cont = accum && ctx->accum_valid && memcmp(key, ctx->accum_key, sizeof(key)) == 0 &&
-                                ctx->accum_samples + spp_u <= (1ull << 24);
-        const uint64_t accum_n = accum_cont ? ctx->accum_samples + spp_u : spp_u;
-        float4* const accum_multi = accum && spp_u > 1u ? ctx->d_accum : nullptr;
-        auto accum_wait = [&](hipStream_t st) {
-            return ctx->accum_recorded && ctx->accum_stream != st ? hipStreamWaitEvent(st, ctx->ev_accum, 0) : hipSuccess;
-        };
-        // k_frame: the whole frame in one launch (cached primaries by construction; frames it does not cover go the persistent way)
-        // (with one sample per pixel "cached primaries" is what every kernel does anyway: the flag is not needed)
-        // (more than one sample: the paths' light records go to the lane's array, which must hold the whole frame's)
-        const bool one_launch = (cache || ctx->cfg.spp == 1) && rtd::launch_frame_ok(f) && (ctx->cfg.spp == 1 || (uint32_t)ctx->cfg.spp <= ctx->persist_batch) &&
-                                (ctx->frame_mode == 2 || (ctx->frame_mode == 1 && frame_by_size(ctx))) && accum_multi == nullptr;
-        if (e == hipSuccess && cache && !one_launch) {
-            if (!fs.wl_clean[fs.wl_parity]) e = hipMemsetAsync(wlc, 0, sizeof(uint32_t), st0);
-            fs.wl_clean[fs.wl_parity] = false;
-            LaunchTimer t(ctx, 1, st0);
-            rtd::PrimaryArgs pr{};
-            pr.phit = fs.phit;
-            pr.worklist = fs.worklist; pr.wl_count = wlc; pr.acc = fs.pacc; pr.counters = ctx->d_counters;
-            // the prepass clears what the NEXT users need zeroed instead of a memset of its own in front of them: the slot's other
-            // worklist counter (the slot's next frame) and the path cursors of the lane it runs on (this frame's first launch)
-            pr.zero_words = prepass_clears ? wln : nullptr; pr.zero_count = 1u;
-            pr.zero_words2 = prepass_clears ? L0->cursor : nullptr; pr.zero_count2 = (uint32_t)kCursorWords;
-            // accumulating: the prepass runs as a one-sample frame, so the light of a pixel it finishes is 16 x its lighting_f32 exactly;
-            // k_accumulate_frame then adds it spp times to the pixel's running sum (the prepass adds it spp times to 0 otherwise)
-            rtd::Frame fpre = f;
-            if (accum_multi) fpre.spp = 1;
-            if (e == hipSuccess) e = rtd::launch_primary(scene_of(ctx), fpre, fpl, pr, count, ctx->primary_version, ctx->num_cus, st0);
-            if (e == hipSuccess && accum_multi) e = accum_wait(st0);
-            if (e == hipSuccess && accum_multi)
-                e = rtd::launch_accumulate_frame(f, fpl, ctx->d_accum, ctx->npix_pad, accum_cont, (int)accum_n, (int)spp_u, true, st0);
-            if (prepass_clears && e == hipSuccess) { fs.wl_clean[fs.wl_parity ^ 1] = true; L0->cursor_clean = true; }
-            fs.wl_parity ^= 1;
-        }
-        // the two per-frame tables depend on the sun vector and colour only: rebuilt when those change (bit compare) — after every
-        // launch that reads the old ones, on either lane, and before any launch that follows
-        float lut_key[6] = {f.sunangle[0], f.sunangle[1], f.sunangle[2], f.sunlight[0], f.sunlight[1], f.sunlight[2]};
-        if (e == hipSuccess && ctx->cfg.depth >= 1 && (!ctx->lut_valid || memcmp(lut_key, ctx->lut_key, sizeof(lut_key)) != 0)) {
-            if (nl == 2) e = join_lanes_into(ctx, st0);
-            {
-                LaunchTimer t(ctx, 1, st0);
-                if (e == hipSuccess) e = rtd::launch_sun_lut(f, ctx->sun_lut, st0);
-                if (e == hipSuccess) e = rtd::launch_sky_lut(f, ctx->dif_lut, st0);
-            }
-            if (e == hipSuccess && nl == 2) e = fence_lanes_after(ctx, st0);
-            ctx->lut_valid = e == hipSuccess;
-            memcpy(ctx->lut_key, lut_key, sizeof(lut_key));
-        }
-        hipStream_t tail = st0;
-        if (e == hipSuccess && one_launch) {
-            // with two frame slots consecutive frames go to the two streams in turn (frame k + 1 starts while frame k's last
-            // workgroups finish); with one slot a frame follows the previous one anyway, and staying on one stream spares the
-            // cross-stream event wait between them
-            if (nsl == 2) ctx->path_launches++;
-            rtd::FrameArgs fa{};
-            fa.threshold = ctx->frame_threshold; fa.tiles_per_group = ctx->frame_tiles; fa.sun_lut = ctx->sun_lut; fa.dif_lut = ctx->dif_lut; fa.pl = L0->ppl; fa.counters = ctx->d_counters;
-            if (getenv("RT_DEBUG_WAVE_DUMP") && (size_t)ctx->ntiles_local * 32u <= (size_t)4 * ctx->num_cus * 1024 * sizeof(uint32_t))
-                fa.dbg_waves = reinterpret_cast<unsigned long long*>(ctx->lanes[0].pstack);   // (idle while k_frame runs)
-            LaunchTimer t(ctx, 0, st0);
-            ctx->last_path_kernel = RT_KERNEL_FRAME;
-            e = rtd::launch_frame(scene_of(ctx), f, fpl, fa, count, ctx->num_cus, st0);
-        } else if (e == hipSuccess && (!cache || ctx->cfg.depth >= 1)) {
-            const uint32_t spp = (uint32_t)ctx->cfg.spp, B = ctx->persist_batch;
-            if (nl == 2 && spp > B) e = hipEventRecord(fs.ev_prepass, st0);   // launches on the other lane wait for the prepass
-            // one sample per pixel (the reference's own frames): k_persist and k_paths store the pixel's lighting themselves, no
-            // light records and no accumulate launch (raytrace.comp:352-356 has no accumulation either)
-            const bool small1 = ctx->paths_by_size && (uint64_t)ctx->npix_pad < kPathsCrossover;   // spp 1: the launch goes to k_persist
-            const bool on_paths = ctx->persist_version == 3 && cache && !small1;
-            const bool direct = spp == 1u && (!on_paths || rtd::launch_paths_direct_ok(f));
-            for (uint32_t s0 = 0; s0 < spp && e == hipSuccess; s0 += B) {
-                const uint32_t ns = spp - s0 < B ? spp - s0 : B;
-                // the sample batches of a frame alternate between the lanes: batch b + 1 starts on the CUs batch b's workgroups leave
-                Lane* L = &ctx->lanes[one_lane ? 0u : ctx->path_launches % (uint64_t)nl];
-                const hipStream_t st = L->stream;
-                if (!one_lane) ctx->path_launches++;
-                if (st != st0 && s0 == B) e = hipStreamWaitEvent(st, fs.ev_prepass, 0);   // (later batches on that lane follow by stream order)
-                if (e == hipSuccess && !L->cursor_clean) e = hipMemsetAsync(L->cursor, 0, kCursorWords * sizeof(uint32_t), st);
-                L->cursor_clean = false;
-                rtd::PersistArgs pa{};
-                pa.cursor = L->cursor; pa.worklist = fs.worklist; pa.wl_count = wlc; pa.direct = direct ? 1u : 0u;
-                pa.npix_pad = ctx->npix_pad; pa.sample0 = s0; pa.nsamples = ns; pa.threshold = ctx->persist_threshold; pa.rmin = ctx->persist_rmin; pa.chunk = ctx->persist_chunk;
-                pa.nthreads = (uint32_t)ctx->num_cus * 1024u; pa.stack = L->pstack;
-                pa.phit = fs.phit;
-                pa.sun_lut = ctx->sun_lut; pa.dif_lut = ctx->dif_lut;
-                pa.pl = L->ppl; pa.counters = ctx->d_counters;
-                // light records of this launch: streamed past the caches when there are more of them than would stay there until the
-                // accumulate launch reads them (the Infinity Cache holds 256 MB; RT_PL_STREAM = 0 / 1 / 2 / 3 forces never / stores /
-                // loads / both)
-                const uint64_t record_bytes = (uint64_t)ctx->npix_pad * ns * sizeof(rtd::PathLight);
-                const bool big_records = record_bytes > kStreamRecordBytes;
-                const bool stream_st = ctx->pl_stream_mode < 0 ? big_records : (ctx->pl_stream_mode & 1) != 0;
-                const bool stream_ld = ctx->pl_stream_mode < 0 ? big_records : (ctx->pl_stream_mode & 2) != 0;
-                pa.pl_stream = stream_st ? 1u : 0u;
-                if (e == hipSuccess) {
-                    LaunchTimer t(ctx, 0, st);
-                    // k_paths pays for its two contexts per lane once there is enough work to keep them filled: measured
-                    // crossover against k_persist (tools/kernel_crossover.sh) between 4 M and 8 M paths per launch — 1080p spp 1:
-                    // 0.28 against 0.22 ms, 256^2 spp 64: 0.35 against 0.32, 1080p spp 4: 0.47 against 0.50, spp 16: 1.29 against
-                    // 1.65; the reference's own 1024^2 1-spp frame: 0.20 against 0.14.  The worklist length lives on the device;
-                    // the pixel count bounds it.  (RT_KERNEL_PATHS asks for k_paths whatever the size.)
-                    const bool big = !ctx->paths_by_size || (uint64_t)ctx->npix_pad * ns >= kPathsCrossover;
-                    // parked lanes that trigger a pass (RT_PERSIST_THRESHOLD overrides): measured optima per kernel.  k_persist 32.
-                    // k_paths (lanes with a parked context, three steps between looks), round 3, same box: 24 4.28 ms per
-                    // headline launch, 28 4.22, 32 4.17, 36 4.06-4.15, 40 4.08-4.14, 44 4.12, 48 4.27; deeper frames at region 256 (depth
-                    // 5..8: longer paths, fewer new ones per pass) like 40 — 3840x2160 spp 256 depth 8 launch 51.2 ms at 28, 50.7 at 32, 50.0
-                    // at 36, 49.6 at 40 and 44 —, the 1024^3 frame stays at 36 (20.74 against 20.86 at 40, 21.2 at 44)
-                    const bool to_paths = ctx->persist_version == 3 && cache && big;
-                    if (ctx->persist_threshold == 0)
-                        pa.threshold = !to_paths ? 32u : ((ctx->cfg.depth > 4 && ctx->region == 256) ? 40u : 36u);
-                    if (to_paths) {
-                        ctx->last_path_kernel = RT_KERNEL_PATHS;
-                        e = rtd::launch_paths(scene_of(ctx), f, fpl, pa, count, ctx->num_cus, st);
-                    } else {
-                        ctx->last_path_kernel = RT_KERNEL_PERSISTENT;
-                        e = rtd::launch_persist(scene_of(ctx), f, fpl, pa, count, cache, 1, ctx->num_cus, st);
-                    }
-                }
-                if (e == hipSuccess && !direct) {
-                    // a pixel's samples are added in sample order: batch b's accumulate follows batch b - 1's, whichever lane that ran on
-                    if (nl == 2 && s0 != 0) e = hipStreamWaitEvent(st, fs.ev_acc, 0);
-                    // (with cached primaries the prepass, which came first, has waited for the previous frame's running sums)
-                    if (e == hipSuccess && accum_multi && !cache && s0 == 0) e = accum_wait(st);
-                    {
-                        LaunchTimer t(ctx, 1, st);
-                        if (e == hipSuccess)
-                            e = rtd::launch_accumulate_paths(f, fpl, L->ppl, fs.worklist, wlc, ctx->npix_pad, ns, s0 == 0, s0 + B >= spp, cache, stream_ld,
-                                                             fs.pacc, accum_multi, accum_cont, (int)accum_n, st);
-                    }
-                    if (e == hipSuccess && nl == 2 && s0 + B < spp) e = hipEventRecord(fs.ev_acc, st);
-                }
-                tail = st;
-            }
-        }
-        // (no resolve launch: the prepass and the last accumulate of the frame store the lighting planes themselves)
-        if (e == hipSuccess && accum && spp_u == 1u) {
-            e = accum_wait(tail);
-            LaunchTimer t(ctx, 1, tail);
-            if (e == hipSuccess) e = rtd::launch_accumulate_frame(f, fpl, ctx->d_accum, ctx->npix_pad, accum_cont, (int)accum_n, 1, false, tail);
-        }
-        if (e == hipSuccess && accum && nl == 2) {
-            e = hipEventRecord(ctx->ev_accum, tail);
-            ctx->accum_recorded = e == hipSuccess;
-            ctx->accum_stream = tail;
-        }
-        if (accum) {
-            ctx->accum_valid = e == hipSuccess;
-            ctx->accum_frames = accum_cont ? ctx->accum_frames + 1u : 1u;
-            ctx->accum_samples = accum_n;
-            memcpy(ctx->accum_key, key, sizeof(key));
-        }
-        if (e != hipSuccess) rc = fail(ctx, RT_ERR_HIP, std::string("persistent path: ") + hipGetErrorString(e));
-        // the frame ends on `tail`: post passes, gather and readback of THIS frame follow it there; its planes are the context's
-        ctx->stream = tail;
-        ctx->cur_slot = si;
-        ctx->gbuffer = fs.gbuffer;
-        for (int b = 0; b < RT_BUF_COUNT; b++) ctx->planes[b] = fs.planes[b];
-        ctx->frames_drawn++;
+    } else if (ctx->route.family == RT_KERNEL_PERSISTENT) {
+        rc = draw_persistent(ctx, f, u, frame_events);
     } else {
         if (frame_events) RT_HIP(ctx, hipEventRecord(ctx->ev_frame0, ctx->stream));
         rc = draw_wavefront(ctx, f);
@@ -1523,11 +1612,12 @@ int rt_get_info(RtContext* ctx, RtInfo* out) {
     if (!ctx || !out) return RT_ERR_INVALID_ARG;
     if (out->struct_size != sizeof(RtInfo)) return fail(ctx, RT_ERR_INVALID_ARG, "rt_get_info: RtInfo.struct_size mismatch");
     out->num_cus = ctx->num_cus;
-    out->samples_per_launch = ctx->kernel == RT_KERNEL_PERSISTENT ? ctx->persist_batch : ctx->batch_samples;
+    const bool persistent = ctx->route.family == RT_KERNEL_PERSISTENT;
+    out->samples_per_launch = persistent ? ctx->persist_batch : ctx->batch_samples;
     out->launches_in_flight = (uint16_t)(ctx->user_stream ? 1 : ctx->nlanes);
     out->frames_in_flight = (uint16_t)(ctx->user_stream ? 1 : ctx->nslots);
     out->light_record_budget_bytes = ctx->light_budget_bytes;
-    out->light_record_bytes = ctx->kernel == RT_KERNEL_PERSISTENT
+    out->light_record_bytes = persistent
         ? (uint64_t)sizeof(rtd::PathLight) * (ctx->npix_pad ? ctx->npix_pad : 1) * ctx->persist_batch * (uint64_t)ctx->nlanes : 0;
     out->device_bytes = ctx->device_bytes;
     return RT_OK;
@@ -1535,12 +1625,7 @@ int rt_get_info(RtContext* ctx, RtInfo* out) {
 
 int rt_kernel_in_use(RtContext* ctx) {
     if (!ctx) return RT_ERR_INVALID_ARG;
-    if (ctx->kernel == RT_KERNEL_PERSISTENT && ctx->last_path_kernel != 0) return ctx->last_path_kernel;   // what the last frame ran
-    if (ctx->kernel == RT_KERNEL_PERSISTENT && ((ctx->cfg.flags & RT_FLAG_CACHE_PRIMARY) || ctx->cfg.spp == 1) && ctx->cfg.depth <= 8 &&
-        (ctx->cfg.spp == 1 || (uint32_t)ctx->cfg.spp <= ctx->persist_batch) && (ctx->frame_mode == 2 || (ctx->frame_mode == 1 && frame_by_size(ctx))))
-        return RT_KERNEL_FRAME;
-    if (ctx->kernel == RT_KERNEL_PERSISTENT && ctx->persist_version == 3) return RT_KERNEL_PATHS;
-    return ctx->kernel;
+    return ctx->route.in_use;
 }
 
 int rt_get_counters(RtContext* ctx, RtCounters* out) {
@@ -1556,7 +1641,7 @@ int rt_get_counters(RtContext* ctx, RtCounters* out) {
     out->pixels = d.pixels; out->frames = ctx->host_frames;
     if (const char* path = getenv("RT_DEBUG_WAVE_DUMP")) {   // -DRT_DIAG_WAVE_TIMES builds of k_paths: per-wave (start, out of paths, end, workgroup)
         if (ctx->lanes[0].pstack) {
-            std::vector<unsigned long long> rec(ctx->last_path_kernel == RT_KERNEL_FRAME ? ((size_t)ctx->ntiles_local + 3u) / 4u * 16u : (size_t)ctx->num_cus * 16u * 4u);
+            std::vector<unsigned long long> rec(ctx->route.frame ? ((size_t)ctx->ntiles_local + 3u) / 4u * 16u : (size_t)ctx->num_cus * 16u * 4u);
             if (hipMemcpy(rec.data(), ctx->lanes[0].pstack, rec.size() * sizeof(rec[0]), hipMemcpyDeviceToHost) == hipSuccess)
                 if (FILE* fp = fopen(path, "wb")) { fwrite(rec.data(), sizeof(rec[0]), rec.size(), fp); fclose(fp); }
         }

@@ -136,13 +136,18 @@ def test_the_reference_frame_runs_on_the_frame_kernel_by_default(procedural_regi
     gpu, gcn = _render_frame_kernel(mats, mine, blue_noise, u, W, H, 1, 2, frames=2, kernel=abi.RT_KERNEL_DEFAULT)
     _compare(gpu, cpu)
     assert gcn.as_dict() == _cached_counters(mats, mine, blue_noise, u, W, H, 1, 2, ccn)
-    for (w, h, spp, want) in ((2304, 1152, 1, abi.RT_KERNEL_PERSISTENT), (512, 512, 4, abi.RT_KERNEL_PERSISTENT), (256, 256, 2, abi.RT_KERNEL_FRAME),
-                               (256, 256, 1, abi.RT_KERNEL_FRAME), (1920, 1080, 1, abi.RT_KERNEL_FRAME)):
-        with render.Context(render.make_config(w, h, spp=spp, depth=2, flags=CACHE)) as ctx:
+    D, P = abi.RT_KERNEL_DEFAULT, abi.RT_KERNEL_PERSISTENT
+    for (w, h, spp, depth, kernel, flags, want) in (
+            (2304, 1152, 1, 2, D, CACHE, abi.RT_KERNEL_PERSISTENT), (512, 512, 4, 2, D, CACHE, abi.RT_KERNEL_PERSISTENT),
+            (256, 256, 2, 2, D, CACHE, abi.RT_KERNEL_FRAME), (256, 256, 1, 2, D, CACHE, abi.RT_KERNEL_FRAME),
+            (1920, 1080, 1, 2, D, CACHE, abi.RT_KERNEL_FRAME),
+            (256, 256, 2, 2, D, CACHE | abi.RT_FLAG_ACCUMULATE, abi.RT_KERNEL_PERSISTENT),   # k_frame adds a pixel's samples from 0
+            (2304, 1152, 1, 2, D, 0, abi.RT_KERNEL_PERSISTENT),                               # k_paths needs cached primaries
+            (256, 256, 1, 0, P, CACHE, abi.RT_KERNEL_PERSISTENT)):                            # the prepass alone: no path launch
+        with render.Context(render.make_config(w, h, spp=spp, depth=depth, kernel=kernel, flags=flags)) as ctx:
             ctx.upload_world(mats, mine)
             ctx.upload_noise(blue_noise)
-            if want == abi.RT_KERNEL_FRAME:
-                assert ctx.kernel_in_use() == want     # before the first frame: what it will run
+            assert ctx.kernel_in_use() == want     # before the first frame: what its last launch will run
             ctx.draw_frame(u)
             ctx.sync()
             assert ctx.kernel_in_use() == want

@@ -298,6 +298,9 @@ def test_rejected_edits_change_nothing(procedural_region, native_built):
         gm, gf = ctx.read_box((0, 0, 0), (256, 256, 256))
         assert np.array_equal(gf, mine) and np.array_equal(gm, mats)
         assert ctx.selftest(MAPS) == 0
+        before = ctx.info().device_bytes
+        ctx.edit_records(good)
+        assert ctx.info().device_bytes == before + (64 << 10)   # the first batch's staging set (64 KiB at least) counts
         ctx.edit_records(good)
         gm, gf = ctx.read_box((0, 0, 0), (64, 64, 64))
         assert gm[5, 4, 3] == 7 and gf[5, 4, 3] == 0
