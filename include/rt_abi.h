@@ -313,6 +313,55 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count);
  * RT_ERR_INVALID_ARG; no world resident: RT_ERR_NOT_READY.  For tests and for a host that saves an edited world. */
 int rt_read_box(RtContext* ctx, int x0, int y0, int z0, int ex, int ey, int ez, uint32_t* materials, uint8_t* minefield);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Ray queries against the resident region: what a ray hits, for
+ * picking the block under the cursor (then rt_edit_voxels), line of sight, collision and light probes.  One ray, 32 bytes: */
+typedef struct RtRay {
+    float origin[3];     uint32_t reserved0;   /* reserved words are ignored                                                  */
+    float direction[3];  uint32_t reserved1;   /* need not be normalized: trace_ray normalizes it (raytrace.comp:83)          */
+} RtRay;
+#define RT_HIT_AIR   0   /* left the region (raytrace.comp:138-145)                                                        */
+#define RT_HIT_SOLID 1   /* a texel whose minefield value is 0 (:146-160), or the border value 0 of a fetch outside the texture */
+#define RT_HIT_LIMIT 2   /* the loop ran out (:109; Q8)                                                                    */
+/* One hit, 48 bytes: */
+typedef struct RtRayHit {
+    float    position[3];    /*  0  as trace_ray returns it: after the 0.001 offset off the face (:166-180)                   */
+    float    distance;       /* 12  length(origin - position before the offset) (:164)                                       */
+    int32_t  texel[3];       /* 16  texel whose material word was fetched (:150-154), the space of RtVoxelEdit; -1,-1,-1 for
+                                    air, limit exits and fetches that fell outside the texture (border value, NaN positions)  */
+    uint32_t material;       /* 28  packed material word (0 for air, limit and border)                                       */
+    uint32_t normal;         /* 32  the shader's normal code 0..5 of the last face crossed (:89-93)                          */
+    uint32_t kind;           /* 36  RT_HIT_AIR / RT_HIT_SOLID / RT_HIT_LIMIT                                                 */
+    uint32_t iterations;     /* 40  loop iterations (:113)                                                                   */
+    uint32_t border_fetches; /* 44  minefield fetches outside [0,R)^3 or at NaN (Q7)                                          */
+} RtRayHit;
+/* Contract of the three calls:
+ *   Results: every field equals the CPU oracle's trace_ray with the same `lr` and region, bit for bit (NaN positions and
+ *     distances of rays that never moved are NaN).  `lr` is the uniform block's lr (raytrace.comp:104): the window of world
+ *     coordinates the region covers is lr - R/2 .. lr + R/2.
+ *   Which world: a query sees the region as left by every earlier rt_upload_world, rt_upload_slice and rt_edit_voxels on the
+ *     context; later calls do not disturb it (an edit after rt_trace_rays_async waits on the device for the query).
+ *   No waiting on frames: a query is not ordered after frames drawn before it unless a world change sits between them (queries
+ *     run on a stream of their own, at the device's highest priority; a frame kernel that occupies every CU still delays its start
+ *     until CUs free up — DESIGN.md "Ray queries").  After rt_set_stream(non-NULL) everything runs on the caller's stream, in order.
+ *   No side effects: no output plane, accumulation sum or count, RtCounters or RtTiming changes.
+ *   Errors: no world resident: RT_ERR_NOT_READY (no noise needed).  A NULL pointer with count > 0, count > 2^26 or a pixel
+ *     outside width x height: RT_ERR_INVALID_ARG, checked before anything is enqueued.  count == 0: RT_OK, nothing enqueued.
+ *   Tile contexts (tile_world > 1) answer for whole-frame pixels: they hold the whole region.  Every RtKernel answers the same.
+ *   Device work per call: one launch, one lane per ray (DESIGN.md "Ray queries"); the synchronous calls add a transfer each way.
+ * Arbitrary rays; host pointers; returns when the hits are in host memory. */
+int rt_trace_rays(RtContext* ctx, const RtRay* rays, uint32_t count, const int32_t lr[3], RtRayHit* hits);
+/* Same with device pointers, enqueued: the hits are valid after rt_sync (or, after rt_set_stream, in the caller's stream order).
+ * Both pointers must be 16-byte aligned memory of the context's device (hipMalloc) or managed memory; anything else (a host
+ * address, another device's memory, a misaligned pointer) returns RT_ERR_INVALID_ARG before anything is enqueued.  The rays must
+ * be complete on the device when the call is made: the query runs on the library's query stream, which is ordered after neither
+ * the caller's streams nor the frames — unless rt_set_stream gave the caller's stream, where stream order holds.  The hits buffer
+ * must not be read or reused before rt_sync (or the caller's stream) says the query is done. */
+int rt_trace_rays_async(RtContext* ctx, const RtRay* rays_dev, uint32_t count, const int32_t lr[3], RtRayHit* hits_dev);
+/* Primary rays of whole-frame pixels xy[2 i], xy[2 i + 1] = (x, y), row 0 = the bottom row, of the camera in `u`
+ * (raytrace.comp:296-297,306-315, including the move of a start below the region).  Only origin, forward, up, right and lr of `u`
+ * are read.  Host pointers, synchronous. */
+int rt_pick_pixels(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint32_t count, RtRayHit* hits);
+
 /* Allocation figures of the context (see RtInfo). */
 int rt_get_info(RtContext* ctx, RtInfo* out);
 
@@ -451,7 +500,8 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *   1.3  round 4: RtKernel value 7 (RT_KERNEL_FRAME); RT_KERNEL_DEFAULT runs frames with little work on it (rt_kernel_in_use tells);
  *        results unchanged.
  *        Additive, same minor version: RT_FLAG_ACCUMULATE, rt_reset_accumulation, rt_get_accumulation (progressive accumulation).
- *        Additive, same minor version: RtVoxelEdit, rt_edit_voxels, rt_read_box, RT_SELFTEST_SCENE_MAPS (sparse voxel edits). */
+ *        Additive, same minor version: RtVoxelEdit, rt_edit_voxels, rt_read_box, RT_SELFTEST_SCENE_MAPS (sparse voxel edits).
+ *        Additive, same minor version: RtRay, RtRayHit, RT_HIT_*, rt_trace_rays, rt_trace_rays_async, rt_pick_pixels (ray queries). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -20,6 +20,7 @@ ABI_SYMBOLS = (
     "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer", "rt_frame_ptr",
     "rt_frame_readback", "rt_selftest", "rt_get_info", "rt_samples_per_launch", "rt_get_gather_timing",
     "rt_reset_accumulation", "rt_get_accumulation", "rt_edit_voxels", "rt_read_box",
+    "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels",
 )
 
 _amd = None
@@ -104,6 +105,12 @@ def amd():
         lib.rt_edit_voxels.restype = C.c_int
         lib.rt_read_box.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]
         lib.rt_read_box.restype = C.c_int
+        lib.rt_trace_rays.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
+        lib.rt_trace_rays.restype = C.c_int
+        lib.rt_trace_rays_async.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
+        lib.rt_trace_rays_async.restype = C.c_int
+        lib.rt_pick_pixels.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P]
+        lib.rt_pick_pixels.restype = C.c_int
         for name in ("rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer"):
             getattr(lib, name).restype = C.c_int
         for name in ("rt_upload_world", "rt_upload_slice", "rt_slice_staging", "rt_upload_noise", "rt_draw_frame", "rt_sync", "rt_readback",
@@ -190,5 +197,7 @@ def host():
         lib.rth_pipeline_enable_post_passes.restype = C.c_int
         lib.rth_pipeline_last_error.argtypes = [P]
         lib.rth_pipeline_last_error.restype = C.c_char_p
+        lib.rth_pipeline_pick.argtypes = [P, C.c_int, C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        lib.rth_pipeline_pick.restype = C.c_int
         _host = lib
     return _host

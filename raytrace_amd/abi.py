@@ -114,3 +114,20 @@ class RtVoxelEdit(C.Structure):
 
 
 assert C.sizeof(RtVoxelEdit) == 16
+
+
+RT_HIT_AIR, RT_HIT_SOLID, RT_HIT_LIMIT = 0, 1, 2   # RtRayHit.kind (ABI 1.3, additive: ray queries)
+
+
+class RtRay(C.Structure):
+    """rt_trace_rays input (ABI 1.3, additive): 32 bytes; the reserved words are ignored."""
+    _fields_ = [("origin", C.c_float * 3), ("reserved0", C.c_uint32), ("direction", C.c_float * 3), ("reserved1", C.c_uint32)]
+
+
+class RtRayHit(C.Structure):
+    """rt_trace_rays / rt_pick_pixels result (ABI 1.3, additive): 48 bytes."""
+    _fields_ = [("position", C.c_float * 3), ("distance", C.c_float), ("texel", C.c_int32 * 3), ("material", C.c_uint32),
+                ("normal", C.c_uint32), ("kind", C.c_uint32), ("iterations", C.c_uint32), ("border_fetches", C.c_uint32)]
+
+
+assert C.sizeof(RtRay) == 32 and C.sizeof(RtRayHit) == 48

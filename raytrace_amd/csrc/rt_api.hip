@@ -214,6 +214,14 @@ struct RtContext {
     hipEvent_t ev_accum = nullptr;      // the last step of the frame drawn last that touched d_accum (two lanes only) ...
     hipStream_t accum_stream = nullptr; // ... recorded on this stream
     bool accum_recorded = false;
+
+    // ray queries (rt_trace_rays, rt_pick_pixels): a stream of their own (the device's highest priority), so that a query waits for
+    // the world changes before it (ev_world) and not for the frames; the world changes wait for the queries before them (ev_query)
+    hipStream_t query_stream = nullptr;
+    hipEvent_t ev_world = nullptr, ev_query = nullptr;
+    bool world_recorded = false, query_recorded = false;
+    uint8_t *q_host = nullptr, *q_dev = nullptr;   // the synchronous calls' pinned and device staging (inputs, then hits), grown on demand
+    size_t q_cap = 0;
 };
 
 constexpr size_t kMaxTimerEvents = 2 * 4096;   // LaunchTimer pool cap: pairs beyond it are not timed (counted in timer_overflow)
@@ -390,6 +398,7 @@ hipError_t fence_lanes_after(RtContext* c, hipStream_t st) {
 // host-side wait for every stream of the context that renders
 hipError_t sync_lanes(RtContext* c) {
     hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && c->query_stream) e = hipStreamSynchronize(c->query_stream);
     for (int l = 0; l < c->nlanes && e == hipSuccess; l++)
         if (c->lanes[l].stream && c->lanes[l].stream != c->stream) e = hipStreamSynchronize(c->lanes[l].stream);
     return e;
@@ -430,6 +439,7 @@ hipError_t staging_send(RtContext* c, StagingSet& s, size_t bytes) {
     s.copy_pending = true;
     e = hipStreamWaitEvent(c->stream, s.ev_copied, 0);
     if (e == hipSuccess) e = join_lanes_into(c, c->stream);
+    if (e == hipSuccess && c->query_recorded) e = hipStreamWaitEvent(c->stream, c->ev_query, 0);   // queries still reading the region
     return e;
 }
 // after the launch that read the device block: later frames, whichever lane they start on, see what it changed
@@ -437,6 +447,7 @@ hipError_t staging_applied(RtContext* c, StagingSet& s) {
     hipError_t e = hipEventRecord(s.ev_applied, c->stream);
     if (e != hipSuccess) return e;
     s.apply_recorded = true;
+    if (c->ev_world) { e = hipEventRecord(c->ev_world, c->stream); if (e != hipSuccess) return e; c->world_recorded = true; }
     return fence_lanes_after(c, c->stream);
 }
 
@@ -776,6 +787,8 @@ int create_slots(RtContext* c) {
     if (c->nlanes == 2) RT_HIP(c, hipStreamCreateWithFlags(&c->lanes[1].stream, hipStreamNonBlocking));
     for (int l = 0; l < c->nlanes; l++) RT_HIP(c, hipEventCreateWithFlags(&c->lanes[l].ev_join, hipEventDisableTiming));
     RT_HIP(c, hipEventCreateWithFlags(&c->ev_fence, hipEventDisableTiming));
+    RT_HIP(c, hipEventCreateWithFlags(&c->ev_world, hipEventDisableTiming));
+    RT_HIP(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
     RT_HIP(c, hipEventCreateWithFlags(&c->ev_gather, hipEventDisableTiming));
     // the six reference-format planes of a slot live in ONE block (each padded to 256 B) so a multi-GPU host can gather them
     // with a single collective; the other planes are separate allocations
@@ -984,6 +997,10 @@ void rt_destroy(RtContext* ctx) {
     for (FrameSlot& fs : ctx->slots) for (hipEvent_t e : {fs.ev_prepass, fs.ev_acc, fs.ev_tail}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {ctx->ev_fence, ctx->ev_gather, ctx->ev_accum}) if (e) (void)hipEventDestroy(e);
     if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); (void)hipStreamDestroy(ctx->upload_stream); }
+    if (ctx->query_stream) { (void)hipStreamSynchronize(ctx->query_stream); (void)hipStreamDestroy(ctx->query_stream); }
+    for (hipEvent_t e : {ctx->ev_world, ctx->ev_query}) if (e) (void)hipEventDestroy(e);
+    if (ctx->q_host) (void)hipHostFree(ctx->q_host);
+    if (ctx->q_dev) (void)hipFree(ctx->q_dev);
     for (StagingSet* s : {&ctx->slab_sets[0], &ctx->slab_sets[1], &ctx->edit_sets[0], &ctx->edit_sets[1]}) {
         for (hipEvent_t e : {s->ev_copied, s->ev_applied}) if (e) (void)hipEventDestroy(e);
         if (s->host) (void)hipHostFree(s->host);
@@ -1040,6 +1057,7 @@ int rt_upload_world(RtContext* ctx, const uint32_t* materials, const uint8_t* mi
     if (rc != RT_OK) return rc;
     ctx->has_world = true;
     ctx->world_resident = true;
+    ctx->world_recorded = false;   // (the region is complete on the device: reflatten synchronised)
     return RT_OK;
 }
 
@@ -1214,6 +1232,118 @@ int rt_read_box(RtContext* ctx, int x0, int y0, int z0, int ex, int ey, int ez, 
     if (d_mine) (void)hipFree(d_mine);
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_read_box: ") + hipGetErrorString(e));
     return RT_OK;
+}
+
+// ---- ray queries ----------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kMaxQueryRays = 1u << 26;
+
+// checks shared by the three calls; returns RT_OK when there is work to enqueue, 1 for count == 0
+int query_check(RtContext* c, const char* fn, uint32_t count, const void* in, const void* more, const void* out) {
+    if (count > kMaxQueryRays) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^26 rays in one call");
+    if (count == 0) return 1;
+    if (!in || !more || !out) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": null pointer");
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    return RT_OK;
+}
+
+// The stream a query runs on, after the world changes before it: the context's query stream (not ordered after the frames), or the
+// caller's stream after rt_set_stream(non-NULL).
+int query_stream_of(RtContext* c, hipStream_t* st) {
+    RT_HIP(c, hipSetDevice(c->device));
+    if (!c->query_stream) {
+        int least = 0, greatest = 0;
+        RT_HIP(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        RT_HIP(c, hipStreamCreateWithPriority(&c->query_stream, hipStreamNonBlocking, greatest));
+    }
+    if (c->user_stream) { *st = c->stream; return RT_OK; }
+    *st = c->query_stream;
+    if (c->world_recorded) RT_HIP(c, hipStreamWaitEvent(*st, c->ev_world, 0));
+    return RT_OK;
+}
+
+int query_launch(RtContext* c, hipStream_t st, const rtd::Frame& f, const void* rays_dev, const void* xy_dev, void* hits_dev, uint32_t count) {
+    rtd::QueryArgs a;
+    a.rays = reinterpret_cast<const float4*>(rays_dev);
+    a.xy = reinterpret_cast<const int2*>(xy_dev);
+    a.hits = reinterpret_cast<uint4*>(hits_dev);
+    a.count = count;
+    RT_HIP(c, rtd::launch_query(scene_of(c), f, a, st));
+    if (!c->user_stream) { RT_HIP(c, hipEventRecord(c->ev_query, st)); c->query_recorded = true; }   // (a caller's stream orders itself)
+    return RT_OK;
+}
+
+// rt_trace_rays_async's pointers: 16-byte aligned (the kernel's float4 / uint4 accesses) and memory of the context's device (or
+// managed memory).  A host address would fault the kernel: pageable memory is not mapped for the device with XNACK off.
+bool query_device_ptr(const RtContext* c, const void* p) {
+    if (((uintptr_t)p & 15u) != 0u) return false;
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (clears the error it set)
+    if (a.type == hipMemoryTypeManaged || a.isManaged) return true;
+    return a.type == hipMemoryTypeDevice && a.device == c->device;
+}
+
+rtd::Frame query_frame(const RtContext* c, const int32_t lr[3]) {
+    RtUniforms u{};
+    for (int k = 0; k < 3; k++) u.lr[k] = lr[k];
+    return frame_of(c, &u);
+}
+
+// The synchronous calls: `in_bytes` of input through pinned and device staging, the launch, the hits back; waits for them.
+int query_sync(RtContext* c, const rtd::Frame& f, const void* in, size_t in_bytes, bool picks, RtRayHit* hits, uint32_t count) {
+    hipStream_t st;
+    int rc = query_stream_of(c, &st);
+    if (rc != RT_OK) return rc;
+    const size_t off = align16(in_bytes), need = off + (size_t)count * sizeof(RtRayHit);
+    if (need > c->q_cap) {   // the previous synchronous call has finished with the staging (it waited for its hits)
+        if (c->q_host) { (void)hipHostFree(c->q_host); c->q_host = nullptr; }
+        if (c->q_dev) { (void)hipFree(c->q_dev); c->q_dev = nullptr; c->device_bytes -= c->q_cap; }
+        c->q_cap = 0;
+        const size_t cap = need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(need + need / 2u);
+        RT_HIP(c, hipHostMalloc((void**)&c->q_host, cap, hipHostMallocDefault));
+        RT_HIP(c, hipMalloc((void**)&c->q_dev, cap));
+        c->q_cap = cap;
+        c->device_bytes += cap;
+    }
+    memcpy(c->q_host, in, in_bytes);
+    RT_HIP(c, hipMemcpyAsync(c->q_dev, c->q_host, in_bytes, hipMemcpyHostToDevice, st));
+    rc = query_launch(c, st, f, picks ? nullptr : c->q_dev, picks ? c->q_dev : nullptr, c->q_dev + off, count);
+    if (rc != RT_OK) return rc;
+    RT_HIP(c, hipMemcpyAsync(c->q_host + off, c->q_dev + off, (size_t)count * sizeof(RtRayHit), hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipStreamSynchronize(st));
+    memcpy(hits, c->q_host + off, (size_t)count * sizeof(RtRayHit));
+    return RT_OK;
+}
+}  // namespace
+
+int rt_trace_rays(RtContext* ctx, const RtRay* rays, uint32_t count, const int32_t lr[3], RtRayHit* hits) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = query_check(ctx, "rt_trace_rays", count, rays, lr, hits);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    return query_sync(ctx, query_frame(ctx, lr), rays, (size_t)count * sizeof(RtRay), false, hits, count);
+}
+
+int rt_trace_rays_async(RtContext* ctx, const RtRay* rays_dev, uint32_t count, const int32_t lr[3], RtRayHit* hits_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = query_check(ctx, "rt_trace_rays_async", count, rays_dev, lr, hits_dev);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, rays_dev) || !query_device_ptr(ctx, hits_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_trace_rays_async: rays and hits must be 16-byte aligned memory of the context's device");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    return query_launch(ctx, st, query_frame(ctx, lr), rays_dev, nullptr, hits_dev, count);
+}
+
+int rt_pick_pixels(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint32_t count, RtRayHit* hits) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = query_check(ctx, "rt_pick_pixels", count, u, xy, hits);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    for (uint32_t i = 0; i < count; i++)
+        if (xy[2 * i] < 0 || xy[2 * i] >= ctx->cfg.width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= ctx->cfg.height)
+            return fail(ctx, RT_ERR_INVALID_ARG, "rt_pick_pixels: pixel " + std::to_string(i) + " is outside the frame");
+    return query_sync(ctx, frame_of(ctx, u), xy, (size_t)count * 8u, true, hits, count);
 }
 
 int rt_upload_noise(RtContext* ctx, const uint8_t* rgba8) {

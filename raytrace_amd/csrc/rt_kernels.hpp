@@ -147,6 +147,15 @@ hipError_t launch_untile_strided(const void* gathered, size_t rank_stride, void*
 hipError_t launch_untile(const void* gathered, void* frame, int world, int capacity, int tiles_x, int tiles_y, int width,
                          int height, int bpp, hipStream_t st);
 
+// rt_query.hip: ray queries against the resident region (rt_trace_rays, rt_pick_pixels)
+struct QueryArgs {
+    const float4* rays;   // RtRay[count] (two float4 each), or
+    const int2* xy;       // non-null: pixel (x, y) of the frame's camera per query (primary_ray)
+    uint4* hits;          // RtRayHit[count] (three uint4 each)
+    uint32_t count;
+};
+hipError_t launch_query(const Scene& sc, const Frame& f, const QueryArgs& a, hipStream_t st);
+
 // rt_post.hip: the reference's post passes
 hipError_t launch_denoise_prepare(const void* lighting, const void* depth, const void* normal, int W, int H, void* work,
                                   hipStream_t st);

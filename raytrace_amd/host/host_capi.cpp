@@ -222,5 +222,14 @@ void rth_pipeline_enable_streaming(void* p, uint64_t seed, const char* dir) {
 }
 int rth_pipeline_enable_post_passes(void* p, int faithful) { return static_cast<render::Pipeline*>(p)->enable_post_passes(faithful != 0); }
 const char* rth_pipeline_last_error(void* p) { return static_cast<render::Pipeline*>(p)->last_error(); }
+// Pipeline::pick: hit (RtRayHit), adjacent and world (int32[3] each)
+int rth_pipeline_pick(void* p, int x, int y_from_top, RtRayHit* hit, int32_t* adjacent, int32_t* world) {
+    render::Pipeline::PickResult r;
+    const int rc = static_cast<render::Pipeline*>(p)->pick(x, y_from_top, &r);
+    if (rc != RT_OK) return rc;
+    *hit = r.hit;
+    for (int a = 0; a < 3; a++) { adjacent[a] = r.adjacent[a]; world[a] = r.world[a]; }
+    return RT_OK;
+}
 
 }  // extern "C"

@@ -47,6 +47,7 @@ Pipeline* create_instance(const RtConfig& cfg, const uint8_t* blue_noise_rgba8, 
     p->spp_ = cfg.spp > 0 ? cfg.spp : 1;
     p->region_ = cfg.region;
     p->tile_world_ = cfg.tile_world;
+    p->height_ = cfg.height;
     std::memset(&p->uniforms_, 0, sizeof(p->uniforms_));
     p->uniforms_.lr[0] = -64; p->uniforms_.lr[1] = -64;    // create_raytrace_uniform_data, render_data.rs:146-147;
     p->uniforms_.lso[0] = -64; p->uniforms_.lso[1] = -64;  // overwritten on the first draw_frame (pipeline.rs:203-207)
@@ -68,6 +69,24 @@ int Pipeline::enable_post_passes(bool faithful) {
 }
 
 const char* Pipeline::last_error() const { return rt_last_error(ctx_); }
+
+int Pipeline::pick(int x, int y_from_top, PickResult* out) {
+    const int32_t xy[2] = {x, (int32_t)height_ - 1 - y_from_top};
+    int rc = rt_pick_pixels(ctx_, &uniforms_, xy, 1, &out->hit);
+    if (rc != RT_OK) return rc;
+    // face normal code n (raytrace.comp:89-93): the ray crossed the face on the side it came from, so the empty neighbour lies
+    // one texel back along the axis: +1 for even codes (the ray moved towards -axis), -1 for odd ones
+    const int R = region_;
+    const int axis = (int)out->hit.normal / 2, step = out->hit.normal % 2 == 0 ? 1 : -1;
+    for (int a = 0; a < 3; a++) {
+        const int t = out->hit.texel[a];
+        out->adjacent[a] = ((t + (a == axis ? step : 0)) % R + R) % R;
+        // texel = world + R/2 (mod R); the world coordinate inside [lr - R/2, lr + R/2)
+        const int lr = uniforms_.lr[a];
+        out->world[a] = lr - R / 2 + (((t - lr) % R) + R) % R;
+    }
+    return RT_OK;
+}
 
 int Pipeline::wait() { return rt_sync(ctx_); }
 

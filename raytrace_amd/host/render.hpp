@@ -80,6 +80,15 @@ class Pipeline {
     // Off by default (the G-buffer planes are then the ray-trace dispatch's own output, which the parity tests compare);
     // whole-frame contexts only (RT_ERR_UNIMPLEMENTED on a tile-split one: the passes need a halo, gather first).
     int enable_post_passes(bool faithful);
+    // The block under a pixel of the frame drawn last (its uniforms, the `lr` terrain streaming moved included): rt_pick_pixels on
+    // pixel (x, height - 1 - y_from_top), the texel in front of the face it crossed (where a placed block goes) and the hit texel's
+    // world coordinate in the lr window.  A game breaks the block with rt_edit_voxels on `hit.texel`, places one on `adjacent`.
+    struct PickResult {
+        RtRayHit hit;
+        int32_t adjacent[3];   // meaningful for kind == RT_HIT_SOLID with texel >= 0
+        int32_t world[3];
+    };
+    int pick(int x, int y_from_top, PickResult* out);
     bool post_passes() const { return post_; }
 
  private:
@@ -91,6 +100,7 @@ class Pipeline {
     int region_ = RT_ROOT_BLOCK_SIZE;
     int render_offset_[3] = {0, 0, 0}; // TerrainUploadManager::get_render_offset (terrain_upload.rs:30-47)
     int tile_world_ = 1;
+    int height_ = 0;                   // frame height (Pipeline::pick counts rows from the top)
     bool post_ = false, post_faithful_ = true;
     std::unique_ptr<TerrainUploadManager> tum_;
     std::unique_ptr<world::ChunkStorage> chunks_;

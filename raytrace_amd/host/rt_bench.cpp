@@ -6,7 +6,7 @@
 //
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
 //            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
-//            [--edits N [--edit-spread]]
+//            [--edits N [--edit-spread]] [--rays N [--rays-coherent]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -24,6 +24,12 @@
 // of the region.  After the timed loop the same batches run alone on a second pipeline created with RT_FLAG_TIMING_ALL: the JSON
 // line adds the device time of the edit launches per call (rt_get_timing's shade_ms: the rebuild and nibble-map launches, each
 // bracketed by events), the launches per call, the host time spent inside rt_edit_voxels and the wall time per call.
+//
+// --rays N: instead of the frame loop, ray queries against the generated world.  rt_trace_rays on N rays — seeded origins in the
+// region with random directions, or with --rays-coherent the primary rays of a --width x --height camera at the default pose handed
+// over as arbitrary rays — timed call to return (the transfers both ways included; the kernel alone: rocprofv3 --kernel-trace
+// --stats, or tools/ray_query_bench.py's device events), then the call-to-return latency of one-pixel rt_pick_pixels, idle and
+// right behind a --width x --height --spp --depth frame still in flight.  One JSON line.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -113,6 +119,73 @@ std::vector<RtVoxelEdit> edit_brush(int n, bool spread, const float origin[3]) {
 }
 void set_solid(std::vector<RtVoxelEdit>& v, int frame) { for (RtVoxelEdit& e : v) e.solid = (uint16_t)((frame & 1) == 0); }
 
+// --rays: see the head of the file
+int run_rays(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device,
+             uint32_t n, bool coherent) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    // the camera's uniforms, from one drawn frame
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    std::vector<RtRay> rays(n);
+    std::vector<RtRayHit> hits(n);
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    for (uint32_t i = 0; i < n; i++) {
+        RtRay& r = rays[i];
+        r = RtRay{};
+        if (coherent) {
+            const uint32_t px = i % (uint32_t)width, py = (i / (uint32_t)width) % (uint32_t)height;
+            const float sx = ((float)px / (float)width) * 2.0f - 1.0f, sy = ((float)py / (float)height) * 2.0f - 1.0f;
+            for (int a = 0; a < 3; a++) { r.origin[a] = u.origin[a]; r.direction[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; }
+        } else {
+            for (int a = 0; a < 3; a++) { r.origin[a] = (rnd() - 0.5f) * 254.0f; r.direction[a] = rnd() * 2.0f - 1.0f; }
+        }
+    }
+    const int32_t lr[3] = {u.lr[0], u.lr[1], u.lr[2]};
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    int rc = rt_trace_rays(ctx, rays.data(), n, lr, hits.data());   // warm-up (staging grows once)
+    const int reps = n >= (1u << 20) ? 5 : 50;
+    auto t = std::chrono::steady_clock::now();
+    for (int i = 0; i < reps && rc == RT_OK; i++) rc = rt_trace_rays(ctx, rays.data(), n, lr, hits.data());
+    const double ms = ms_since(t) / reps;
+    uint64_t solid = 0;
+    for (const RtRayHit& h : hits) solid += h.kind == RT_HIT_SOLID;
+    const int32_t xy[2] = {width / 2, height / 2};
+    RtRayHit one{};
+    std::vector<double> idle, busy;
+    for (int i = 0; i < 220 && rc == RT_OK; i++) {
+        t = std::chrono::steady_clock::now();
+        rc = rt_pick_pixels(ctx, &u, xy, 1, &one);
+        if (i >= 20) idle.push_back(ms_since(t));
+    }
+    double frame_ms = 0;
+    for (int i = 0; i < 21 && rc == RT_OK; i++) {
+        const auto tf = std::chrono::steady_clock::now();
+        rc = rt_draw_frame(ctx, &u);
+        t = std::chrono::steady_clock::now();
+        if (rc == RT_OK) rc = rt_pick_pixels(ctx, &u, xy, 1, &one);
+        if (i > 0) busy.push_back(ms_since(t));
+        if (rc == RT_OK) rc = rt_sync(ctx);
+        if (i > 0) frame_ms += ms_since(tf) / 20.0;
+    }
+    if (rc != RT_OK) { std::fprintf(stderr, "ray queries failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    std::sort(idle.begin(), idle.end());
+    std::sort(busy.begin(), busy.end());
+    std::printf("{\"rays\": %u, \"coherent\": %s, \"trace_rays_ms\": %.4f, \"grays_call_to_return\": %.3f, \"solid_hits\": %llu, "
+                "\"pick_ms_idle_median\": %.4f, \"pick_ms_in_flight_median\": %.4f, \"pick_ms_in_flight_max\": %.4f, "
+                "\"frame\": \"%dx%d spp %d depth %d\", \"frame_ms\": %.3f}\n",
+                n, coherent ? "true" : "false", ms, (double)n / (ms * 1e-3) / 1e9, (unsigned long long)solid, idle[idle.size() / 2],
+                busy[busy.size() / 2], busy.back(), width, height, spp, depth, frame_ms);
+    delete p;
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -120,6 +193,8 @@ int main(int argc, char** argv) {
     int spp = 1, depth = 2, frames = 240, device = 0, gpus = 1;
     bool gather = false, overlap = false, post = false, accumulate = false, edit_spread = false;
     int edits = 0;
+    long long rays = 0;
+    bool rays_coherent = false;
     std::string noise_path = "tests/golden/blue_noise_512.rgba";
     std::vector<const char*> positional = {argv[0]};
     for (int i = 1; i < argc; i++) {
@@ -138,10 +213,13 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--accumulate") == 0) accumulate = true;
         else if (want("--edits")) edits = std::atoi(argv[++i]);
         else if (std::strcmp(argv[i], "--edit-spread") == 0) edit_spread = true;
+        else if (want("--rays")) rays = std::atoll(argv[++i]);
+        else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
         else positional.push_back(argv[i]);
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
     if (edits < 0 || edits > (1 << 24)) { std::fprintf(stderr, "--edits must be in 0..2^24\n"); return 2; }
+    if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
     if (gpus > 1) gather = true;
     if (post && gpus > 1) { std::fprintf(stderr, "--post needs the whole frame on one device (gather first on several)\n"); return 2; }
     rt::game::Game game((int)positional.size(), positional.data());
@@ -157,6 +235,7 @@ int main(int argc, char** argv) {
     std::printf("Creating renderer (and world.)\n");                 // main.rs:10
     auto t0 = std::chrono::steady_clock::now();
     game.generate_world(0x5EED);
+    if (rays > 0) return run_rays(game, noise, width, height, spp, depth, device, (uint32_t)rays, rays_coherent);
     std::string err;
 
     // exact ray count of one frame (a counting context, outside the timed loop): the JSON line's Mrays/s is rays actually traced

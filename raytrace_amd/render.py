@@ -13,8 +13,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RtConfig, RtCounters, RtInfo, RtTiming,
-                  RtUniforms, RtVoxelEdit)
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RtConfig, RtCounters, RtInfo, RtRayHit,
+                  RtTiming, RtUniforms, RtVoxelEdit)
 
 
 class RtError(RuntimeError):
@@ -36,6 +36,36 @@ def make_config(width, height, spp=1, depth=2, device=0, tile_rank=0, tile_world
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# numpy view of RtRayHit (include/rt_abi.h)
+HIT_DTYPE = np.dtype([("position", "<f4", 3), ("distance", "<f4"), ("texel", "<i4", 3), ("material", "<u4"), ("normal", "<u4"),
+                      ("kind", "<u4"), ("iterations", "<u4"), ("border_fetches", "<u4")])
+assert HIT_DTYPE.itemsize == C.sizeof(RtRayHit)
+
+# Texel step from a hit voxel to the empty neighbour in front of the face the ray crossed, per normal code (raytrace.comp:89-93): an
+# even code means the ray travelled towards -axis, so it came from +axis.
+FACE_STEP = np.array([(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)], dtype=np.int64)
+
+
+def adjacent_texel(texel, normal, region=256):
+    """Texel in front of face `normal` of `texel` (where a placed block goes), wrapped mod R."""
+    t = np.asarray(texel, dtype=np.int64)
+    return (t + FACE_STEP[np.asarray(normal, dtype=np.int64)]) % int(region)
+
+
+def texel_to_world(texel, lr=(0, 0, 0), region=256):
+    """World coordinate of `texel` inside the window the region covers for render offset `lr`: texel = world + R/2 (mod R) and
+    lr - R/2 <= world < lr + R/2 (raytrace.comp:104-105,138-145)."""
+    t = np.asarray(texel, dtype=np.int64)
+    lr = np.asarray(lr, dtype=np.int64)
+    R = int(region)
+    return lr - R // 2 + (t - lr) % R
+
+
+def row_from_bottom(y_from_top, height):
+    """Frame row of a screen row counted from the top: the planes' row 0 is the bottom of the view."""
+    return int(height) - 1 - np.asarray(y_from_top)
 
 
 class Context:
@@ -159,6 +189,36 @@ class Context:
         if rgba8.size != 512 * 512 * 4:
             raise ValueError("noise must be 512x512 RGBA8")
         self._check(self._lib.rt_upload_noise(self._h, _p(rgba8)))
+
+    # -- ray queries -------------------------------------------------------------------------------------
+    def trace_rays(self, origins, directions, lr=(0, 0, 0)):
+        """rt_trace_rays: float[N, 3] origins and directions -> numpy array of HIT_DTYPE (RtRayHit) per ray.  Synchronous."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("origins and directions must have the same shape [N, 3]")
+        rays = np.zeros((o.shape[0], 8), dtype=np.float32)
+        rays[:, 0:3], rays[:, 4:7] = o, d
+        hits = np.zeros(o.shape[0], dtype=HIT_DTYPE)
+        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
+        self._check(self._lib.rt_trace_rays(self._h, _p(rays), int(o.shape[0]), lr3, _p(hits)))
+        return hits
+
+    def trace_rays_async(self, rays, hits, lr=(0, 0, 0)):
+        """rt_trace_rays_async on torch device tensors: `rays` float32[N, 8] (origin, pad, direction, pad per row), `hits` any
+        contiguous tensor of N * 48 bytes (e.g. uint8[N, 48] or int32[N, 12]).  Enqueued: valid after sync(), or in the order of a
+        stream given to set_stream().  `rays` must be complete on the device when the call is made (the query is not ordered
+        after the caller's stream unless that stream was given to set_stream())."""
+        n = check_query_tensors(rays, hits, self.cfg.device if self.cfg is not None else 0)
+        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
+        self._check(self._lib.rt_trace_rays_async(self._h, C.c_void_p(rays.data_ptr()), n, lr3, C.c_void_p(hits.data_ptr())))
+
+    def pick_pixels(self, uniforms, xy):
+        """rt_pick_pixels: int[N, 2] whole-frame pixels (x, y), row 0 = bottom, of the camera in `uniforms` -> HIT_DTYPE[N]."""
+        xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        hits = np.zeros(xy.shape[0], dtype=HIT_DTYPE)
+        self._check(self._lib.rt_pick_pixels(self._h, C.byref(uniforms), _p(xy), int(xy.shape[0]), _p(hits)))
+        return hits
 
     # -- frames ------------------------------------------------------------------------------------------
     def draw_frame(self, uniforms):
@@ -439,6 +499,21 @@ class Pipeline:
         if rc != 0:
             raise RtError(rc, "enable_post_passes: whole-frame contexts only (tile_world == 1)")
 
+    def pick(self, game, x, y_from_top):
+        """The block under screen pixel (x, y_from_top) of the frame drawn last for `game` (Pipeline::pick: the pipeline's current
+        uniforms, the `lr` terrain streaming moved included).  Returns a dict: `hit` (HIT_DTYPE record), `texel`, `normal`, `kind`,
+        `adjacent` (the texel in front of the face, where a placed block goes) and `world` (the hit texel's world coordinate)."""
+        del game   # the pick is of the frame the pipeline drew for it: its uniforms hold the camera
+        hit = np.zeros(1, dtype=HIT_DTYPE)
+        adj = (C.c_int32 * 3)()
+        wld = (C.c_int32 * 3)()
+        rc = _lib.host().rth_pipeline_pick(self._h, int(x), int(y_from_top), _p(hit), adj, wld)
+        if rc != 0:
+            raise RtError(rc, _lib.host().rth_pipeline_last_error(self._h).decode())
+        h = hit[0]
+        return {"hit": h, "texel": tuple(int(v) for v in h["texel"]), "normal": int(h["normal"]), "kind": int(h["kind"]),
+                "adjacent": tuple(adj[:]), "world": tuple(wld[:])}
+
     def close(self):
         if self._h:
             _lib.host().rth_pipeline_free(self._h)   # impl Drop for Pipeline, pipeline.rs:258-277
@@ -482,6 +557,26 @@ def camera_uniforms(origin, heading, pitch, sun_angle=0.0, seed=1, lr=(0, 0, 0))
 
 
 DEFAULT_POSE = dict(origin=(-30.0, -128.0, 100.0), heading=math.pi / 2, pitch=0.0, sun_angle=0.0)  # game/mod.rs:53-55
+
+
+def check_query_tensors(rays, hits, device):
+    """Context.trace_rays_async's arguments: `rays` a contiguous float32[N, 8] tensor and `hits` a contiguous tensor of N * 48
+    bytes, both on GPU `device` and 16-byte aligned.  Returns N; raises ValueError otherwise (a host tensor's address handed to the
+    kernel would fault the device)."""
+    import torch
+    if not isinstance(rays, torch.Tensor) or not isinstance(hits, torch.Tensor):
+        raise ValueError("rays and hits must be torch tensors")
+    for name, t in (("rays", rays), ("hits", hits)):
+        if not t.is_cuda or t.device.index != int(device):
+            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+        raise ValueError("rays must be a contiguous float32 tensor of shape [N, 8]")
+    n = int(rays.shape[0])
+    if not hits.is_contiguous() or hits.numel() * hits.element_size() != n * HIT_DTYPE.itemsize:
+        raise ValueError("hits must be a contiguous tensor of N * 48 bytes")
+    return n
 
 
 def comm_unique_id():
