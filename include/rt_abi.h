@@ -362,6 +362,30 @@ int rt_trace_rays_async(RtContext* ctx, const RtRay* rays_dev, uint32_t count, c
  * are read.  Host pointers, synchronous. */
 int rt_pick_pixels(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint32_t count, RtRayHit* hits);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Terrain generated on the device: the project's deterministic
+ * procedural world (raytrace_amd/host/world.cpp: generate_chunk + pack_into per world chunk, MATERIALS[id].pack()) written straight
+ * into the resident region, byte for byte what the host generator assembles — no host bytes, no staging, no transfer.
+ *   Window: the world box each call writes.  rt_generate_world writes [lo, lo + R) on every axis (window_lo NULL = (-R/2, -R/2, -R/2),
+ *     the region of world.generate_region); rt_generate_slice writes [lo_m, lo_m + 16) on `axis` m (0/1/2 = x/y/z) and [lo_a, lo_a + R)
+ *     on the other two.  World voxel v lands at texel (v + R/2) mod R on each axis: the addressing of rt_upload_slice and
+ *     TerrainUploadManager (a streamer's request origin[a]*64 + num_slices[a]*16 is its window_lo).  Each voxel takes the minefield of
+ *     its own world chunk, also where a window that is not 64-aligned puts pieces of two chunks in one 64-texel block.
+ *   Content: rt_generate_world(seed, NULL) equals rt_upload_world of world.generate_region(seed, R); any window equals rt_upload_world
+ *     of world.toroidal_region(lo + R/2, seed, R); rt_generate_slice leaves the region as rt_upload_slice of the host manager's slab.
+ *     Heights are FP64 with the host's operations in the host's order (DESIGN.md "Terrain on the device": the margin of pow).
+ *   Nibble maps: rt_generate_world rebuilds every word; rt_generate_slice the words its slab touches, as rt_upload_slice does.
+ *   Validation, before anything is enqueued (a rejected call changes nothing): window_lo not a multiple of 16, a window voxel outside
+ *     int32 (RtUniforms.lr is int32), axis outside 0..2 or window_lo NULL (slice): RT_ERR_INVALID_ARG.  rt_generate_slice without a
+ *     resident world: RT_ERR_NOT_READY.
+ *   Ordering: asynchronous and stream-ordered like rt_upload_slice — after every frame already submitted on every lane and frame slot
+ *     and after earlier queries; later frames, queries and edits see the new region; the host waits for nothing.  Works on a stream
+ *     set with rt_set_stream and on tile-split contexts.  Resets RT_FLAG_ACCUMULATE's running sum.  rt_generate_world makes the world
+ *     resident: a context may start from it with no rt_upload_world at all.
+ * Device work per call: heights of the window's chunk columns, one workgroup per world chunk in the window that writes its voxels, one
+ * launch that rebuilds the nibble-map words (counted by RT_FLAG_TIMING_ALL as one launch); scratch of (R + 64)^2 int32 on first use. */
+int rt_generate_world(RtContext* ctx, uint64_t seed, const int64_t window_lo[3]);
+int rt_generate_slice(RtContext* ctx, uint64_t seed, int axis, const int64_t window_lo[3]);
+
 /* Allocation figures of the context (see RtInfo). */
 int rt_get_info(RtContext* ctx, RtInfo* out);
 
@@ -501,7 +525,8 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        results unchanged.
  *        Additive, same minor version: RT_FLAG_ACCUMULATE, rt_reset_accumulation, rt_get_accumulation (progressive accumulation).
  *        Additive, same minor version: RtVoxelEdit, rt_edit_voxels, rt_read_box, RT_SELFTEST_SCENE_MAPS (sparse voxel edits).
- *        Additive, same minor version: RtRay, RtRayHit, RT_HIT_*, rt_trace_rays, rt_trace_rays_async, rt_pick_pixels (ray queries). */
+ *        Additive, same minor version: RtRay, RtRayHit, RT_HIT_*, rt_trace_rays, rt_trace_rays_async, rt_pick_pixels (ray queries).
+ *        Additive, same minor version: rt_generate_world, rt_generate_slice (terrain generated on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -20,7 +20,7 @@ ABI_SYMBOLS = (
     "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer", "rt_frame_ptr",
     "rt_frame_readback", "rt_selftest", "rt_get_info", "rt_samples_per_launch", "rt_get_gather_timing",
     "rt_reset_accumulation", "rt_get_accumulation", "rt_edit_voxels", "rt_read_box",
-    "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels",
+    "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels", "rt_generate_world", "rt_generate_slice",
 )
 
 _amd = None
@@ -111,6 +111,10 @@ def amd():
         lib.rt_trace_rays_async.restype = C.c_int
         lib.rt_pick_pixels.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P]
         lib.rt_pick_pixels.restype = C.c_int
+        lib.rt_generate_world.argtypes = [P, C.c_uint64, C.POINTER(C.c_int64)]
+        lib.rt_generate_world.restype = C.c_int
+        lib.rt_generate_slice.argtypes = [P, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]
+        lib.rt_generate_slice.restype = C.c_int
         for name in ("rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer"):
             getattr(lib, name).restype = C.c_int
         for name in ("rt_upload_world", "rt_upload_slice", "rt_slice_staging", "rt_upload_noise", "rt_draw_frame", "rt_sync", "rt_readback",
@@ -166,9 +170,13 @@ def host():
         lib.rth_tum_pending.argtypes = [P]
         lib.rth_tum_step.argtypes = [P]
         lib.rth_tum_render_offset.argtypes = [P, P]
+        lib.rth_tum_next_window.argtypes = [P, P, P]
+        lib.rth_tum_next_window.restype = C.c_int
         lib.rth_tum_region.argtypes = [P, P, P]
         lib.rth_pipeline_enable_streaming.argtypes = [P, C.c_uint64, C.c_char_p]
         lib.rth_pipeline_enable_streaming.restype = None
+        lib.rth_pipeline_enable_streaming_on_device.argtypes = [P, C.c_uint64]
+        lib.rth_pipeline_enable_streaming_on_device.restype = None
         lib.rth_compute_triple_euler_vector.argtypes = [C.c_float, C.c_float, P, P, P]
         lib.rth_game_new.argtypes = [C.c_int, P]
         lib.rth_game_new.restype = P
@@ -183,6 +191,7 @@ def host():
         lib.rth_game_set_world_r.argtypes = [P, P, P, C.c_int]
         lib.rth_game_generate_world.argtypes = [P, C.c_uint64]
         lib.rth_game_generate_world_r.argtypes = [P, C.c_uint64, C.c_int]
+        lib.rth_game_use_device_world.argtypes = [P, C.c_uint64, C.c_int]
         lib.rth_create_instance.argtypes = [C.POINTER(RtConfig), P, P, P, C.c_size_t]
         lib.rth_create_instance.restype = P
         lib.rth_pipeline_free.argtypes = [P]

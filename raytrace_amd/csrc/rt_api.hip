@@ -124,6 +124,7 @@ struct RtContext {
     uint64_t slabs = 0, edit_batches = 0;   // submitted so far: the next one uses set slabs & 1 / edit_batches & 1
     std::vector<uint32_t> edit_chunk, edit_order, edit_start, edit_stamp;   // host binning scratch, kept between calls
     uint32_t edit_gen = 0;                // edit_stamp generation: a voxel's slot holds the generation of the chunk run that kept it
+    int32_t* d_heights = nullptr;         // rt_generate_world / rt_generate_slice: column heights of (R/64 + 1)^2 chunks, on first use
 
     // tiling
     int tiles_x = 0, tiles_y = 0, ntiles_total = 0, ntiles_local = 0, tile_capacity = 0;
@@ -1114,6 +1115,61 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
     }
     RT_HIP(ctx, staging_applied(ctx, s));
     return RT_OK;
+}
+
+// ---- terrain on the device (rt_generate_world, rt_generate_slice) -------------------------------------------------------------
+namespace {
+// The window [lo, lo + ext) on every axis: 16-aligned, every voxel (and so lr = lo + R/2) inside int32.
+bool terrain_window_ok(const int64_t lo[3], const int64_t ext[3]) {
+    for (int a = 0; a < 3; a++)
+        if (lo[a] % RT_SLICE_SIZE != 0 || lo[a] < (int64_t)INT32_MIN || lo[a] + ext[a] - 1 > (int64_t)INT32_MAX) return false;
+    return true;
+}
+// Generates the window on the render stream after every frame already submitted (every lane) and every earlier query; later frames,
+// lanes and queries see the result (the ordering of rt_upload_slice, without staging: the kernels read nothing from the host).
+int generate_terrain(RtContext* c, uint64_t seed, const int64_t lo[3], int axis) {
+    RT_HIP(c, hipSetDevice(c->device));
+    if (!c->d_heights) {
+        const size_t cols = (size_t)(c->region + RT_CHUNK_SIZE) * (size_t)(c->region + RT_CHUNK_SIZE);
+        RT_HIP(c, dev_alloc(c, &c->d_heights, cols));
+    }
+    c->accum_valid = false;
+    RT_HIP(c, join_lanes_into(c, c->stream));
+    if (c->query_recorded) RT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_query, 0));   // queries still reading the region
+    {
+        LaunchTimer t(c, 1);
+        RT_HIP(c, rtd::launch_terrain(c->d_mine_sw, c->d_mat_sw, c->d_coarse, c->d_brick, c->d_heights, c->logr, seed, lo, axis, c->stream));
+    }
+    if (c->ev_world) { RT_HIP(c, hipEventRecord(c->ev_world, c->stream)); c->world_recorded = true; }
+    RT_HIP(c, fence_lanes_after(c, c->stream));
+    return RT_OK;
+}
+}  // namespace
+
+int rt_generate_world(RtContext* ctx, uint64_t seed, const int64_t window_lo[3]) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const int64_t R = ctx->region;
+    const int64_t lo[3] = {window_lo ? window_lo[0] : -R / 2, window_lo ? window_lo[1] : -R / 2, window_lo ? window_lo[2] : -R / 2};
+    const int64_t ext[3] = {R, R, R};
+    if (!terrain_window_ok(lo, ext))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_generate_world: window_lo must be a multiple of 16 and the window inside int32; nothing was enqueued");
+    const int rc = generate_terrain(ctx, seed, lo, -1);
+    if (rc != RT_OK) return rc;
+    ctx->has_world = true;
+    ctx->world_resident = true;
+    return RT_OK;
+}
+
+int rt_generate_slice(RtContext* ctx, uint64_t seed, int axis, const int64_t window_lo[3]) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (axis < 0 || axis > 2 || !window_lo) return fail(ctx, RT_ERR_INVALID_ARG, "rt_generate_slice: bad axis or null window; nothing was enqueued");
+    const int64_t R = ctx->region;
+    const int64_t lo[3] = {window_lo[0], window_lo[1], window_lo[2]};
+    const int64_t ext[3] = {axis == 0 ? RT_SLICE_SIZE : R, axis == 1 ? RT_SLICE_SIZE : R, axis == 2 ? RT_SLICE_SIZE : R};
+    if (!terrain_window_ok(lo, ext))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_generate_slice: window_lo must be a multiple of 16 and the window inside int32; nothing was enqueued");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_generate_slice: upload or generate the full region first");
+    return generate_terrain(ctx, seed, lo, axis);
 }
 
 namespace {

@@ -135,6 +135,10 @@ hipError_t launch_check_maps(const uint8_t* mine_sw, const uint32_t* coarse, con
                              unsigned long long* mismatches, hipStream_t st);
 hipError_t launch_read_box(const uint8_t* mine_sw, const uint32_t* mat_sw, int logr, int x0, int y0, int z0, int ex, int ey, int nz,
                            uint32_t* mat_out, uint8_t* mine_out, hipStream_t st);
+// rt_terrain.hip: rt_generate_world (axis = -1: the window [lo, lo + R) on every axis) and rt_generate_slice (axis 0..2: 16 voxels
+// from lo[axis] along it); heights: int32 scratch for (R/64 + 1)^2 chunk columns of 64^2
+hipError_t launch_terrain(uint8_t* mine_sw, uint32_t* mat_sw, uint32_t* coarse, uint32_t* brick, int32_t* heights, int logr,
+                          uint64_t seed, const int64_t lo[3], int axis, hipStream_t st);
 hipError_t launch_mega(const Scene& sc, const Frame& f, const Planes& pl, DevCounters* cn, bool count, hipStream_t st);
 hipError_t launch_trace(const Scene& sc, const Frame& f, const TraceArgs& a, bool primary, bool count, int nworkgroups, hipStream_t st);
 hipError_t launch_shade0(const Scene& sc, const Frame& f, const ShadeArgs& a, const Planes& pl, bool count, hipStream_t st);

@@ -163,6 +163,8 @@ int rth_tum_step(void* t) {
         return (int)RT_OK;
     });
 }
+// The window of the next request (rt_generate_slice's window_lo) without consuming it: 1 and *axis / lo3 set, or 0 when none is queued.
+int rth_tum_next_window(void* t, int* axis, long* lo3) { return static_cast<HostTum*>(t)->tum.next_request_window(axis, lo3) ? 1 : 0; }
 void rth_tum_render_offset(void* t, long* out3) { static_cast<HostTum*>(t)->tum.get_render_offset(out3); }
 void rth_tum_region(void* t, uint32_t* materials, uint8_t* minefield) {
     auto* h = static_cast<HostTum*>(t);
@@ -202,6 +204,7 @@ int rth_game_set_world_r(void* g, const uint32_t* materials, const uint8_t* mine
 }
 int rth_game_generate_world(void* g, uint64_t seed) { return static_cast<game::Game*>(g)->generate_world(seed); }
 int rth_game_generate_world_r(void* g, uint64_t seed, int region) { return static_cast<game::Game*>(g)->generate_world(seed, region); }
+int rth_game_use_device_world(void* g, uint64_t seed, int region) { return static_cast<game::Game*>(g)->use_device_world(seed, region); }
 
 void* rth_create_instance(const RtConfig* cfg, const uint8_t* blue_noise_rgba8, void* g, char* err, size_t err_len) {
     std::string msg;
@@ -219,6 +222,9 @@ void rth_pipeline_uniforms(void* p, RtUniforms* out) { *out = static_cast<render
 void rth_pipeline_set_seed(void* p, uint32_t seed) { static_cast<render::Pipeline*>(p)->set_seed(seed); }
 void rth_pipeline_enable_streaming(void* p, uint64_t seed, const char* dir) {
     static_cast<render::Pipeline*>(p)->enable_terrain_streaming(seed, dir ? dir : "");
+}
+void rth_pipeline_enable_streaming_on_device(void* p, uint64_t seed) {
+    static_cast<render::Pipeline*>(p)->enable_terrain_streaming(seed, "", true);
 }
 int rth_pipeline_enable_post_passes(void* p, int faithful) { return static_cast<render::Pipeline*>(p)->enable_post_passes(faithful != 0); }
 const char* rth_pipeline_last_error(void* p) { return static_cast<render::Pipeline*>(p)->last_error(); }

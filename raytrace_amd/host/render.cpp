@@ -40,7 +40,11 @@ Pipeline* create_instance(const RtConfig& cfg, const uint8_t* blue_noise_rgba8, 
     }
     RtContext* ctx = nullptr;
     if (rt_create(&cfg, &ctx) != RT_OK) return fail("rt_create", nullptr);
-    if (rt_upload_world(ctx, game.world_materials(), game.world_minefield()) != RT_OK) return fail("rt_upload_world", ctx);
+    if (game.device_world()) {   // Game::use_device_world: the same world, generated on the device
+        if (rt_generate_world(ctx, game.device_world_seed(), nullptr) != RT_OK) return fail("rt_generate_world", ctx);
+    } else if (rt_upload_world(ctx, game.world_materials(), game.world_minefield()) != RT_OK) {
+        return fail("rt_upload_world", ctx);
+    }
     if (rt_upload_noise(ctx, blue_noise_rgba8) != RT_OK) return fail("rt_upload_noise", ctx);
     Pipeline* p = new Pipeline();
     p->ctx_ = ctx;
@@ -59,6 +63,15 @@ Pipeline::~Pipeline() { rt_destroy(ctx_); }
 void Pipeline::enable_terrain_streaming(uint64_t seed, const std::string& storage_dir) {
     chunks_.reset(new world::ChunkStorage(storage_dir, seed));
     tum_.reset(new TerrainUploadManager(region_));
+    stream_on_device_ = false;
+}
+
+void Pipeline::enable_terrain_streaming(uint64_t seed, const std::string& storage_dir, bool on_device) {
+    if (!on_device) { enable_terrain_streaming(seed, storage_dir); return; }
+    chunks_.reset();
+    tum_.reset(new TerrainUploadManager(region_));
+    stream_on_device_ = true;
+    stream_seed_ = seed;
 }
 
 int Pipeline::enable_post_passes(bool faithful) {
@@ -109,15 +122,22 @@ int Pipeline::draw_frame(game::Game& game) {
     if (tum_) {                                                      // pipeline.rs:174-189
         const long towards[3] = {(long)camera.origin[0], 0, (long)camera.origin[2]};   // (x, literal 0, z) — :175-179
         tum_->request_move_towards(towards);
-        if (tum_->pending() > 0) {   // the slab is assembled in the library's pinned staging (the reference's mapped upload buffers, terrain_upload.rs:65-82)
-            uint32_t* sm = nullptr; uint8_t* sf = nullptr;
-            rc = rt_slice_staging(ctx_, &sm, &sf);
-            if (rc != RT_OK) return rc;
-            tum_->bind_upload_buffers(sm, sf);
+        if (stream_on_device_) {   // the slab is generated on the device, in the request's window
+            rc = tum_->setup_next_request_on_device([this](int axis, const long* lo) {
+                const int64_t w[3] = {lo[0], lo[1], lo[2]};
+                return rt_generate_slice(ctx_, stream_seed_, axis, w);
+            });
+        } else {
+            if (tum_->pending() > 0) {   // the slab is assembled in the library's pinned staging (the reference's mapped upload buffers, terrain_upload.rs:65-82)
+                uint32_t* sm = nullptr; uint8_t* sf = nullptr;
+                rc = rt_slice_staging(ctx_, &sm, &sf);
+                if (rc != RT_OK) return rc;
+                tum_->bind_upload_buffers(sm, sf);
+            }
+            rc = tum_->setup_next_request(*chunks_, [this](int axis, int off, const uint32_t* m, const uint8_t* f) {
+                return rt_upload_slice(ctx_, axis, off, m, f);
+            });
         }
-        rc = tum_->setup_next_request(*chunks_, [this](int axis, int off, const uint32_t* m, const uint8_t* f) {
-            return rt_upload_slice(ctx_, axis, off, m, f);
-        });
         if (rc != RT_OK) return rc;
         long off[3];
         tum_->get_render_offset(off);
@@ -180,6 +200,19 @@ int Game::generate_world(uint64_t seed, int region) {
     minefield_.assign(n, 0);
     world::assemble_region_procedural(seed, materials_.data(), minefield_.data(), region);
     region_ = region;
+    device_world_ = false;
+    return RT_OK;
+}
+
+int Game::use_device_world(uint64_t seed, int region) {
+    if (region != 256 && region != 512 && region != 1024) return RT_ERR_INVALID_ARG;
+    materials_.clear();
+    materials_.shrink_to_fit();
+    minefield_.clear();
+    minefield_.shrink_to_fit();
+    region_ = region;
+    device_world_ = true;
+    device_seed_ = seed;
     return RT_OK;
 }
 
@@ -190,6 +223,7 @@ int Game::set_world(const uint32_t* materials, const uint8_t* minefield, int reg
     materials_.assign(materials, materials + n);
     minefield_.assign(minefield, minefield + n);
     region_ = region;
+    device_world_ = false;
     return RT_OK;
 }
 

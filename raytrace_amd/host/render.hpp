@@ -40,7 +40,12 @@ class Game {
     int generate_world(uint64_t seed, int region = RT_ROOT_BLOCK_SIZE);   // region: 256 = the reference; 512 / 1024 = extension
     int world_region() const { return region_; }
     int set_world(const uint32_t* materials, const uint8_t* minefield, int region = RT_ROOT_BLOCK_SIZE);   // region^3 voxels each
-    bool has_world() const { return !materials_.empty(); }
+    // The procedural world of generate_world(seed, region) without its host bytes: create_instance generates it on the device
+    // (rt_generate_world) in place of rt_upload_world.  generate_world / set_world replace it with host bytes again.
+    int use_device_world(uint64_t seed, int region = RT_ROOT_BLOCK_SIZE);
+    bool device_world() const { return device_world_; }
+    uint64_t device_world_seed() const { return device_seed_; }
+    bool has_world() const { return device_world_ || !materials_.empty(); }
     const uint32_t* world_materials() const { return materials_.data(); }
     const uint8_t* world_minefield() const { return minefield_.data(); }
 
@@ -51,6 +56,8 @@ class Game {
     std::vector<uint32_t> materials_;
     std::vector<uint8_t> minefield_;
     int region_ = RT_ROOT_BLOCK_SIZE;
+    bool device_world_ = false;
+    uint64_t device_seed_ = 0;
 };
 
 }  // namespace rt::game
@@ -72,6 +79,9 @@ class Pipeline {
     // the camera and uploads at most one slab; the render offset becomes the uniform block's `lr`.  Off by default
     // (static region).  `storage_dir` empty = no disk cache.
     void enable_terrain_streaming(uint64_t seed, const std::string& storage_dir);
+    // on_device: every slab is generated on the device (rt_generate_slice on the request's window) instead of assembled from host
+    // chunks and uploaded (rt_slice_staging + rt_upload_slice); no ChunkStorage, no host bytes.  storage_dir is then unused.
+    void enable_terrain_streaming(uint64_t seed, const std::string& storage_dir, bool on_device);
     TerrainUploadManager* terrain_upload_manager() { return tum_.get(); }
     // The rest of the reference's per-frame command buffer (pipeline.rs:98-123): after the ray-trace dispatch, the six
     // bilateral_denoise.comp dispatches and finalize.comp, submitted together (:229-235).  When enabled, draw_frame enqueues
@@ -104,6 +114,8 @@ class Pipeline {
     bool post_ = false, post_faithful_ = true;
     std::unique_ptr<TerrainUploadManager> tum_;
     std::unique_ptr<world::ChunkStorage> chunks_;
+    bool stream_on_device_ = false;
+    uint64_t stream_seed_ = 0;
 };
 
 // render::create_instance (mod.rs:36-43) -> Pipeline::new (pipeline.rs:36-76): creates the device context, uploads

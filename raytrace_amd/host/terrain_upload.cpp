@@ -70,6 +70,25 @@ int TerrainUploadManager::setup_next_request(world::ChunkStorage& chunks, const 
     return upload_slice(chunks, sink, r);
 }
 
+bool TerrainUploadManager::next_request_window(int* axis, long window_lo[3]) const {
+    if (queue_.empty()) return false;
+    const Request& r = queue_.front();
+    *axis = (int)r.axis;
+    for (int a = 0; a < 3; a++) window_lo[a] = r.origin[a] * kChunk + (long)r.num_slices[a] * kSlice;
+    return true;
+}
+
+int TerrainUploadManager::setup_next_request_on_device(const DeviceSliceSink& sink) {
+    int axis = 0;
+    long win[3];
+    if (!next_request_window(&axis, win)) return RT_OK;
+    const Position next = queue_.front().new_position;
+    queue_.pop_front();
+    const int rc = sink(axis, win);
+    if (rc == RT_OK) gpu_position_ = next;                      // as upload_slice (:273)
+    return rc;
+}
+
 // The slab holds, on the main axis m, the 16 world voxels starting at request.origin[m]*64 + num_slices[m]*16, and on
 // each other axis a the R-voxel window starting at request.origin[a]*64 + num_slices[a]*16, every voxel stored at texel
 // (voxel - origin*64) mod R — the texture's toroidal addressing.  Chunk pieces never straddle the wrap because R is a

@@ -24,6 +24,9 @@ struct Position {
 // Where a finished slab goes: (axis, texel offset along it, materials, minefield) -> RtStatus.  The pipeline binds this to
 // rt_upload_slice; tests bind it to a host-side toroidal array.
 using SliceSink = std::function<int(int, int, const uint32_t*, const uint8_t*)>;
+// The second way to serve a request: (axis, window_lo) -> RtStatus, where window_lo[a] = origin[a]*64 + num_slices[a]*16 is the world
+// box the slab covers (16 voxels on `axis`, R on the others) — what rt_generate_slice takes.  No chunk is generated on the host.
+using DeviceSliceSink = std::function<int(int, const long*)>;
 
 class TerrainUploadManager {
  public:
@@ -36,6 +39,11 @@ class TerrainUploadManager {
     // Consumes at most one queued request (:275-287): builds the slab from the world chunks and hands it to `sink`.
     // Returns RT_OK (also when the queue is empty) or the sink's error.
     int setup_next_request(world::ChunkStorage& chunks, const SliceSink& sink);
+    // Same, but the slab is generated where the sink puts it (rt_generate_slice): the sink gets the request's axis and window.
+    // On RT_OK the GPU position advances exactly as after upload_slice.
+    int setup_next_request_on_device(const DeviceSliceSink& sink);
+    // The window of the next queued request, without consuming it (false when the queue is empty).
+    bool next_request_window(int* axis, long window_lo[3]) const;
     void get_render_offset(long out[3]) const { gpu_position_.render_offset(out); }   // :285-287
     // The reference's upload buffers are host-visible mapped device buffers (:65-82) that upload_slice fills in place; a host
     // that has such memory (rt_slice_staging: pinned) binds it here for the NEXT request, otherwise the slab is built in the

@@ -184,6 +184,19 @@ class Context:
         self._check(self._lib.rt_read_box(self._h, x0, y0, z0, ex, ey, ez, _p(mats), _p(mine)))
         return mats, mine
 
+    def generate_world(self, seed, window_lo=None):
+        """rt_generate_world: the procedural world of `seed` generated on the device into the whole region — the window
+        [lo, lo + R) on every axis, window_lo None = (-R/2, -R/2, -R/2), i.e. world.generate_region(seed, R); any other window
+        (multiples of 16) equals world.toroidal_region(lo + R/2, seed, R).  Asynchronous; makes the world resident."""
+        lo = None if window_lo is None else (C.c_int64 * 3)(*[int(v) for v in window_lo])
+        self._check(self._lib.rt_generate_world(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), lo))
+
+    def generate_slice(self, seed, axis, window_lo):
+        """rt_generate_slice: one 16-thick slab generated on the device — [lo[axis], lo[axis] + 16) along `axis`, [lo, lo + R)
+        along the other two, every voxel at texel (v + R/2) mod R (world.slice_window turns a streamer's request into it)."""
+        lo = (C.c_int64 * 3)(*[int(v) for v in window_lo])
+        self._check(self._lib.rt_generate_slice(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(axis), lo))
+
     def upload_noise(self, rgba8):
         rgba8 = np.ascontiguousarray(rgba8, dtype=np.uint8).reshape(-1)
         if rgba8.size != 512 * 512 * 4:
@@ -449,6 +462,13 @@ class Game:
         if rc != 0:
             raise RtError(rc, "generate_world: region must be 256, 512 or 1024")
 
+    def use_device_world(self, seed=0x5EED, region=256):
+        """The world of generate_world(seed, region) without its host bytes: create_instance generates it on the device
+        (rt_generate_world) instead of uploading it."""
+        rc = _lib.host().rth_game_use_device_world(self._h, C.c_uint64(int(seed)), int(region))
+        if rc != 0:
+            raise RtError(rc, "use_device_world: region must be 256, 512 or 1024")
+
     def close(self):
         if self._h:
             _lib.host().rth_game_free(self._h)
@@ -488,9 +508,13 @@ class Pipeline:
     def set_seed(self, seed):
         _lib.host().rth_pipeline_set_seed(self._h, C.c_uint32(int(seed)))
 
-    def enable_terrain_streaming(self, seed=0x5EED, storage_dir=""):
-        """pipeline.rs:174-189: every draw_frame moves the TerrainUploadManager towards the camera (<= 1 slab per frame)."""
-        _lib.host().rth_pipeline_enable_streaming(self._h, C.c_uint64(int(seed)), str(storage_dir).encode() if storage_dir else None)
+    def enable_terrain_streaming(self, seed=0x5EED, storage_dir="", on_device=False):
+        """pipeline.rs:174-189: every draw_frame moves the TerrainUploadManager towards the camera (<= 1 slab per frame).
+        on_device: the slabs are generated on the device (rt_generate_slice) instead of assembled from host chunks and uploaded."""
+        if on_device:
+            _lib.host().rth_pipeline_enable_streaming_on_device(self._h, C.c_uint64(int(seed)))
+        else:
+            _lib.host().rth_pipeline_enable_streaming(self._h, C.c_uint64(int(seed)), str(storage_dir).encode() if storage_dir else None)
 
     def enable_post_passes(self, faithful=True):
         """pipeline.rs:98-123: every draw_frame then enqueues ray trace -> six denoise dispatches -> finalize (the reference's one

@@ -203,6 +203,15 @@ class HostTerrainUploadManager:
         rc = _lib.host().rth_tum_step(self._h)
         assert rc == 0
 
+    def next_window(self):
+        """The next queued request as rt_generate_slice takes it: (axis, window_lo) with window_lo[a] = origin[a]*64 +
+        num_slices[a]*16, or None when nothing is queued.  Does not consume the request (setup_next_request does)."""
+        axis = C.c_int()
+        lo = (C.c_long * 3)()
+        if not _lib.host().rth_tum_next_window(self._h, C.byref(axis), lo):
+            return None
+        return int(axis.value), tuple(int(v) for v in lo)
+
     def get_render_offset(self):
         o = (C.c_long * 3)()
         _lib.host().rth_tum_render_offset(self._h, o)
