@@ -144,6 +144,27 @@ typedef enum RtKernel {
                                        but on the persistent kernels, whose prepass and accumulate launch continue the sum.
                                        RT_KERNEL_DEFAULT / FRAME / PATHS / PERSISTENT; rt_create rejects it on MEGA and WAVEFRONT
                                        (RT_ERR_UNIMPLEMENTED).  See rt_reset_accumulation / rt_get_accumulation.             */
+#define RT_FLAG_REPROJECT 0x80u /* (ABI 1.3, additive) temporal reprojection: an RT_FLAG_ACCUMULATE context of one-sample whole frames
+                                       keeps its lighting history when the camera moves.  Valid only together with RT_FLAG_ACCUMULATE
+                                       (else RT_ERR_INVALID_ARG), with spp == 1 and tile_world == 1 (else RT_ERR_UNIMPLEMENTED).  The
+                                       context owns two history sets used in turn (a frame's pass reads one and writes the other): per
+                                       pixel the fp32 sum of its lights, the frame's depth_f32 and a word count | normal << 27 —
+                                       npix_pad x 32 B more than RT_FLAG_ACCUMULATE alone (RtInfo.device_bytes) — and, on the host, the
+                                       previous frame's camera.  rt_draw_frame classifies the frame:
+                                         restart  no frame before, a world / noise change or rt_reset_accumulation since (the list of
+                                                  RT_FLAG_ACCUMULATE, rt_generate_* included), sun_angle differs, or the count would
+                                                  pass 2^24: every pixel sum = 0 + L, n = 1;
+                                         still    every live uniform other than seed bitwise equal: sum = sum_prev + L, n = n_prev + 1
+                                                  (a context that never moves is bit-identical to RT_FLAG_ACCUMULATE alone);
+                                         moved    origin, forward, up, right or lr differ: per pixel, the hit point rebuilt from
+                                                  depth_f32 is projected into the previous camera; the history of the nearest previous
+                                                  pixel is taken when it has the same normal and lies on the same face plane (at most
+                                                  0.25 apart along the normal's axis), scaled down to RtConfig.history_cap samples when
+                                                  it holds more; every other pixel (sky, off screen, disoccluded) restarts.
+                                       L = 16 x lighting_f32 of the frame just drawn; lighting_f32 / lighting_rgba16 = sum / n / 16 with
+                                       the pixel's own n (rt_read_history); the other planes are the frame's own.  The arithmetic is
+                                       fixed (DESIGN.md "Reprojection"; restated in tests/temporal_ref.py) and reproduced bit for bit.
+                                       One launch per frame (k_temporal_frame) in place of k_accumulate_frame.                 */
 
 /*
  * RtConfig — replaces the compile-time window constants (constants.rs:9-10) and adds the
@@ -168,7 +189,9 @@ typedef struct RtConfig {
     int32_t  tile_world;
     int32_t  kernel;        /* RtKernel */
     uint32_t flags;         /* RT_FLAG_* */
-    int32_t  reserved[5];
+    int32_t  history_cap;   /* (was reserved[0]) RT_FLAG_REPROJECT: the most samples a pixel's history carries across a camera
+                               change; 0 = the default, 32; valid 1..65535 (else RT_ERR_INVALID_ARG).  Ignored without the flag. */
+    int32_t  reserved[4];
 } RtConfig;
 
 /* Output planes. Bindings cited from shaders/glsl/raytrace.comp:14-21; formats from
@@ -500,8 +523,15 @@ int rt_selftest(RtContext* ctx, int which, uint64_t* result);
  * from zero.  No effect on a context without the flag. */
 int rt_reset_accumulation(RtContext* ctx);
 /* Frames and samples the lighting planes of the frame drawn last hold: (k, k x spp) after k frames of an accumulation; 1 and spp
- * on a context without RT_FLAG_ACCUMULATE; 0 and 0 before the first frame.  Host-side state only: does not synchronise. */
+ * on a context without RT_FLAG_ACCUMULATE; 0 and 0 before the first frame.  Host-side state only: does not synchronise.
+ * RT_FLAG_REPROJECT: frames = frames since the history last started from zero (a camera change does not restart it); samples = the
+ * upper bound of any pixel's count: s + 1 after a still frame, min(s, history_cap) + 1 after a moved one. */
 int rt_get_accumulation(RtContext* ctx, uint32_t* frames, uint32_t* samples);
+/* (ABI 1.3, additive; hosts detect the feature by this symbol) RT_FLAG_REPROJECT: the per-pixel sample counts behind the lighting of
+ * the frame drawn last, width x height u32, row-major, row 0 = bottom.  Synchronises first; bytes must equal width x height x 4;
+ * RT_ERR_INVALID_ARG on a context without the flag; all zero before the first frame.  For tests, and for a host that wants to
+ * denoise harder where the history is short. */
+int rt_read_history(RtContext* ctx, uint32_t* counts, size_t bytes);
 
 int rt_get_counters(RtContext* ctx, RtCounters* out);
 int rt_reset_counters(RtContext* ctx);
@@ -526,7 +556,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RT_FLAG_ACCUMULATE, rt_reset_accumulation, rt_get_accumulation (progressive accumulation).
  *        Additive, same minor version: RtVoxelEdit, rt_edit_voxels, rt_read_box, RT_SELFTEST_SCENE_MAPS (sparse voxel edits).
  *        Additive, same minor version: RtRay, RtRayHit, RT_HIT_*, rt_trace_rays, rt_trace_rays_async, rt_pick_pixels (ray queries).
- *        Additive, same minor version: rt_generate_world, rt_generate_slice (terrain generated on the device). */
+ *        Additive, same minor version: rt_generate_world, rt_generate_slice (terrain generated on the device).
+ *        Additive, same minor version: RT_FLAG_REPROJECT, RtConfig.history_cap (was reserved[0]), rt_read_history (temporal
+ *        reprojection of the accumulated lighting while the camera moves). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

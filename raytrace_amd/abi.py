@@ -23,6 +23,7 @@ RT_FLAG_TRUSTED_WORLD = 0x10
 RT_KERNEL_DEFAULT, RT_KERNEL_MEGA, RT_KERNEL_WAVEFRONT, RT_KERNEL_PERSISTENT, RT_KERNEL_PATHS, RT_KERNEL_FRAME = 0, 1, 2, 3, 5, 7   # 4 (PERSISTENT2) and 6 (SEQ): retired
 RT_FLAG_FRAMES_IN_FLIGHT_2 = 0x20
 RT_FLAG_ACCUMULATE = 0x40     # ABI 1.3, additive: progressive accumulation while the camera holds still
+RT_FLAG_REPROJECT = 0x80      # ABI 1.3, additive: the accumulated lighting is reprojected when the camera moves (1-spp whole frames)
 RT_FLAG_COUNTERS = 0x1
 RT_SELFTEST_DENOISE_DIVISION = 1
 RT_SELFTEST_SCENE_MAPS = 2    # ABI 1.3, additive: rebuild the nibble maps from the resident minefield, count differing words
@@ -79,7 +80,8 @@ class RtConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("region", C.c_int32),
         ("spp", C.c_int32), ("depth", C.c_int32), ("device", C.c_int32), ("tile_rank", C.c_int32),
-        ("tile_world", C.c_int32), ("kernel", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32 * 5),
+        ("tile_world", C.c_int32), ("kernel", C.c_int32), ("flags", C.c_uint32),
+        ("history_cap", C.c_int32), ("reserved", C.c_int32 * 4),
     ]
 
 

@@ -28,6 +28,7 @@ CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-f
 
 AMD_SRCS = [os.path.join(CSRC, "rt_kernels.hip"), os.path.join(CSRC, "rt_persist.hip"), os.path.join(CSRC, "rt_paths.hip"), os.path.join(CSRC, "rt_frame.hip"), os.path.join(CSRC, "rt_post.hip"),
             os.path.join(CSRC, "rt_edit.hip"), os.path.join(CSRC, "rt_query.hip"), os.path.join(CSRC, "rt_terrain.hip"),
+            os.path.join(CSRC, "rt_temporal.hip"),
             os.path.join(CSRC, "rt_api.hip")]
 AMD_DEPS = AMD_SRCS + [os.path.join(CSRC, "rt_device.hpp"), os.path.join(CSRC, "rt_kernels.hpp"), os.path.join(CSRC, "rt_dda.hpp"), os.path.join(CSRC, "rt_pslot.hpp"),
                        os.path.join(INC, "rt_abi.h"), os.path.join(INC, "rt_math.h")]

@@ -215,6 +215,14 @@ struct RtContext {
     hipEvent_t ev_accum = nullptr;      // the last step of the frame drawn last that touched d_accum (two lanes only) ...
     hipStream_t accum_stream = nullptr; // ... recorded on this stream
     bool accum_recorded = false;
+    // temporal reprojection (RT_FLAG_REPROJECT): two history sets used in turn — a frame's pass reads the set the previous frame's
+    // pass wrote and writes the other.  Sums by row-major pixel (set 0's is d_accum) and (depth_f32 bits, count | normal << 27)
+    // records; the previous frame's camera is accum_key's origin, forward, up and right
+    bool reproject = false;
+    uint32_t history_cap = 32;
+    float4* d_hist_sum[2] = {nullptr, nullptr};
+    uint2* d_hist_rec[2] = {nullptr, nullptr};
+    int hist_cur = 0;                   // the set the pass of the frame drawn last wrote
 
     // ray queries (rt_trace_rays, rt_pick_pixels): a stream of their own (the device's highest priority), so that a query waits for
     // the world changes before it (ev_world) and not for the frames; the world changes wait for the queries before them (ev_query)
@@ -528,6 +536,7 @@ struct PersistFrame {
     uint32_t key[16] = {};
     uint64_t accum_n = 0;               // samples the sum holds after this frame
     float4* accum_multi = nullptr;      // d_accum for frames of more than one sample
+    int temporal_mode = rtd::TEMPORAL_RESTART;   // RT_FLAG_REPROJECT: how this frame's pass treats the history
 };
 
 // the step that touches the running sum follows the previous frame's (ev_accum), not the whole previous frame
@@ -566,6 +575,19 @@ hipError_t frame_begin(RtContext* c, PersistFrame& p, const RtUniforms* u, bool 
     p.accum_cont = p.accum && c->accum_valid && memcmp(p.key, c->accum_key, sizeof(p.key)) == 0 && c->accum_samples + spp <= (1ull << 24);
     p.accum_n = p.accum_cont ? c->accum_samples + spp : spp;
     p.accum_multi = p.accum && spp > 1u ? c->d_accum : nullptr;
+    // RT_FLAG_REPROJECT (one-sample frames): a camera change no longer restarts the history — only sun_angle, what invalidates the
+    // sum anyway and the 2^24 bound do.  accum_n is then the upper bound of any pixel's count.
+    if (c->reproject) {
+        const bool still = p.accum_cont;   // (every live uniform equal, valid, below 2^24)
+        const bool same_camera = memcmp(p.key, c->accum_key, sizeof(p.key)) == 0;
+        if (still) p.temporal_mode = rtd::TEMPORAL_STILL;
+        else if (c->accum_valid && !same_camera && p.key[0] == c->accum_key[0]) p.temporal_mode = rtd::TEMPORAL_MOVED;
+        else p.temporal_mode = rtd::TEMPORAL_RESTART;
+        if (p.temporal_mode == rtd::TEMPORAL_MOVED) {
+            p.accum_cont = true;
+            p.accum_n = (c->accum_samples < c->history_cap ? c->accum_samples : (uint64_t)c->history_cap) + 1u;
+        }
+    }
     // the frame that used the slot before (frame k - 2 with two slots, k - 1 with one) has finished with it
     if (e == hipSuccess && p.fs->tail_recorded) e = hipStreamWaitEvent(p.st0, p.fs->ev_tail, 0);
     if (e == hipSuccess && frame_events) e = hipEventRecord(c->ev_frame0, p.st0);
@@ -693,7 +715,20 @@ hipError_t frame_accumulate_tail(RtContext* c, PersistFrame& p) {
     if (c->cfg.spp == 1) {
         e = accum_wait(c, p.tail);
         LaunchTimer t(c, 1, p.tail);
-        if (e == hipSuccess) e = rtd::launch_accumulate_frame(p.f, p.pl, c->d_accum, c->npix_pad, p.accum_cont, (int)p.accum_n, 1, false, p.tail);
+        if (e == hipSuccess && !c->reproject)
+            e = rtd::launch_accumulate_frame(p.f, p.pl, c->d_accum, c->npix_pad, p.accum_cont, (int)p.accum_n, 1, false, p.tail);
+        if (e == hipSuccess && c->reproject) {
+            // the pass reads the set the previous frame's pass wrote (ordered by accum_wait / stream order) and writes the other
+            rtd::TemporalArgs ta{};
+            const int prev = c->hist_cur, next = prev ^ 1;
+            ta.prev_sum = c->d_hist_sum[prev]; ta.prev_rec = c->d_hist_rec[prev];
+            ta.next_sum = c->d_hist_sum[next]; ta.next_rec = c->d_hist_rec[next];
+            memcpy(ta.origin, &c->accum_key[1], 12); memcpy(ta.forward, &c->accum_key[4], 12);
+            memcpy(ta.up, &c->accum_key[7], 12); memcpy(ta.right, &c->accum_key[10], 12);
+            ta.cap = c->history_cap;
+            e = rtd::launch_temporal_frame(p.f, p.pl, ta, p.temporal_mode, p.tail);
+            c->hist_cur = next;
+        }
     }
     if (e == hipSuccess && p.nl == 2) {
         e = hipEventRecord(c->ev_accum, p.tail);
@@ -867,6 +902,14 @@ int create_persistent(RtContext* c) {
         RT_HIP(c, dev_alloc(c, &c->d_accum, (size_t)c->npix_pad));
         RT_HIP(c, hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming));
     }
+    if (c->reproject) {
+        c->d_hist_sum[0] = c->d_accum;
+        RT_HIP(c, dev_alloc(c, &c->d_hist_sum[1], (size_t)c->npix_pad));
+        for (int h = 0; h < 2; h++) {
+            RT_HIP(c, dev_alloc(c, &c->d_hist_rec[h], (size_t)c->npix_pad));
+            RT_HIP(c, hipMemset(c->d_hist_rec[h], 0, (size_t)c->npix_pad * sizeof(uint2)));   // rt_read_history before the first frame
+        }
+    }
     RT_HIP(c, rtd::launch_sphere_lut(c->sphere_lut, c->own_stream));
     RT_HIP(c, rtd::launch_dif_lut(c->sphere_lut, c->dif_lut, c->own_stream));
     RT_HIP(c, hipStreamSynchronize(c->own_stream));
@@ -926,6 +969,14 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
         return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: unknown kernel");
     if ((cfg->flags & RT_FLAG_ACCUMULATE) && (cfg->kernel == RT_KERNEL_MEGA || cfg->kernel == RT_KERNEL_WAVEFRONT))
         return fail(nullptr, RT_ERR_UNIMPLEMENTED, "rt_create: RT_FLAG_ACCUMULATE needs RT_KERNEL_DEFAULT, FRAME, PATHS or PERSISTENT (not the baselines)");
+    if (cfg->flags & RT_FLAG_REPROJECT) {
+        if (!(cfg->flags & RT_FLAG_ACCUMULATE))
+            return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: RT_FLAG_REPROJECT needs RT_FLAG_ACCUMULATE");
+        if (cfg->history_cap < 0 || cfg->history_cap > 65535)
+            return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: history_cap must be 0 (the default, 32) or 1..65535");
+        if (cfg->spp != 1 || cfg->tile_world != 1)
+            return fail(nullptr, RT_ERR_UNIMPLEMENTED, "rt_create: RT_FLAG_REPROJECT needs one-sample whole frames (spp == 1, tile_world == 1)");
+    }
 
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -944,6 +995,8 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
     // decides which kernel takes what once the samples per launch are known
     c->route.family = (cfg->kernel == RT_KERNEL_MEGA || cfg->kernel == RT_KERNEL_WAVEFRONT) ? cfg->kernel : RT_KERNEL_PERSISTENT;
     const bool persistent = c->route.family == RT_KERNEL_PERSISTENT;
+    c->reproject = (cfg->flags & RT_FLAG_REPROJECT) != 0;
+    c->history_cap = cfg->history_cap > 0 ? (uint32_t)cfg->history_cap : 32u;
 
     // tiling: 8x8-pixel tiles dealt round-robin over tile_world contexts
     c->tiles_x = (cfg->width + 7) / 8; c->tiles_y = (cfg->height + 7) / 8;
@@ -1454,6 +1507,19 @@ int rt_get_accumulation(RtContext* ctx, uint32_t* frames, uint32_t* samples) {
     if (!ctx->drawn) { *frames = 0; *samples = 0; }
     else if (ctx->d_accum) { *frames = (uint32_t)ctx->accum_frames; *samples = (uint32_t)ctx->accum_samples; }
     else { *frames = 1; *samples = (uint32_t)ctx->cfg.spp; }
+    return RT_OK;
+}
+
+int rt_read_history(RtContext* ctx, uint32_t* counts, size_t bytes) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!ctx->reproject) return fail(ctx, RT_ERR_INVALID_ARG, "rt_read_history: the context was created without RT_FLAG_REPROJECT");
+    const size_t npix = (size_t)ctx->cfg.width * (size_t)ctx->cfg.height;
+    if (!counts || bytes != npix * sizeof(uint32_t)) return fail(ctx, RT_ERR_INVALID_ARG, "rt_read_history: null destination or size mismatch");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, sync_lanes(ctx));
+    std::vector<uint2> rec(npix);
+    RT_HIP(ctx, hipMemcpy(rec.data(), ctx->d_hist_rec[ctx->hist_cur], npix * sizeof(uint2), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < npix; i++) counts[i] = rec[i].y & ((1u << 27) - 1u);
     return RT_OK;
 }
 

@@ -160,6 +160,18 @@ struct QueryArgs {
 };
 hipError_t launch_query(const Scene& sc, const Frame& f, const QueryArgs& a, hipStream_t st);
 
+// rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
+enum { TEMPORAL_RESTART = 0, TEMPORAL_STILL = 1, TEMPORAL_MOVED = 2 };
+struct TemporalArgs {
+    const float4* prev_sum;   // the history set the previous frame's pass wrote: sums by row-major pixel ...
+    const uint2* prev_rec;    // ... and (depth_f32 bits, count | normal << 27)
+    float4* next_sum;         // the set this pass writes
+    uint2* next_rec;
+    float origin[3], forward[3], right[3], up[3];   // the previous frame's camera (TEMPORAL_MOVED)
+    uint32_t cap;             // most samples a history carries across a camera change (1..65535)
+};
+hipError_t launch_temporal_frame(const Frame& f, const Planes& planes, const TemporalArgs& a, int mode, hipStream_t st);
+
 // rt_post.hip: the reference's post passes
 hipError_t launch_denoise_prepare(const void* lighting, const void* depth, const void* normal, int W, int H, void* work,
                                   hipStream_t st);

@@ -6,7 +6,7 @@
 //
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
 //            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
-//            [--edits N [--edit-spread]] [--rays N [--rays-coherent]]
+//            [--reproject] [--camera-step DX] [--edits N [--edit-spread]] [--rays N [--rays-coherent]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -18,6 +18,11 @@
 // --accumulate: the contexts are created with RT_FLAG_ACCUMULATE.  The camera stays where it is and the mirror's draw_frame
 // advances the seed by spp per frame, so every frame continues the accumulation; the JSON line adds the samples the last frame's
 // lighting holds (rt_get_accumulation).
+//
+// --reproject (implies --accumulate): RT_FLAG_REPROJECT as well — the lighting history is carried across camera changes (one-sample
+// frames on one device).  --camera-step DX: before every frame after the first, DX is added to the camera's origin.x and DX / 100 rad
+// to its heading, so that every frame is a moved one; with --accumulate alone the accumulation then restarts every frame, which is
+// the baseline --reproject is measured against.
 //
 // --edits N: before every frame, rt_edit_voxels places or breaks (alternating from frame to frame) N voxels of a deterministic brush
 // near the camera — a cube of voxels centred 16 texels ahead of it — or, with --edit-spread, N voxels dealt round every 64^3 chunk
@@ -195,6 +200,8 @@ int main(int argc, char** argv) {
     int edits = 0;
     long long rays = 0;
     bool rays_coherent = false;
+    bool reproject = false;
+    float camera_step = 0.0f;
     std::string noise_path = "tests/golden/blue_noise_512.rgba";
     std::vector<const char*> positional = {argv[0]};
     for (int i = 1; i < argc; i++) {
@@ -211,6 +218,8 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--overlap") == 0) overlap = true;
         else if (std::strcmp(argv[i], "--post") == 0) post = true;
         else if (std::strcmp(argv[i], "--accumulate") == 0) accumulate = true;
+        else if (std::strcmp(argv[i], "--reproject") == 0) reproject = accumulate = true;
+        else if (want("--camera-step")) camera_step = std::strtof(argv[++i], nullptr);
         else if (want("--edits")) edits = std::atoi(argv[++i]);
         else if (std::strcmp(argv[i], "--edit-spread") == 0) edit_spread = true;
         else if (want("--rays")) rays = std::atoll(argv[++i]);
@@ -220,6 +229,7 @@ int main(int argc, char** argv) {
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
     if (edits < 0 || edits > (1 << 24)) { std::fprintf(stderr, "--edits must be in 0..2^24\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
+    if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
     if (gpus > 1) gather = true;
     if (post && gpus > 1) { std::fprintf(stderr, "--post needs the whole frame on one device (gather first on several)\n"); return 2; }
     rt::game::Game game((int)positional.size(), positional.data());
@@ -259,7 +269,8 @@ int main(int argc, char** argv) {
     std::vector<int> devices((size_t)gpus);
     for (int g = 0; g < gpus; g++) devices[(size_t)g] = device + g;
     for (int g = 0; g < gpus; g++) {
-        RtConfig cfg = make_config(width, height, spp, depth, devices[(size_t)g], g, gpus, RT_FLAG_CACHE_PRIMARY | (accumulate ? RT_FLAG_ACCUMULATE : 0u));
+        RtConfig cfg = make_config(width, height, spp, depth, devices[(size_t)g], g, gpus, RT_FLAG_CACHE_PRIMARY | (accumulate ? RT_FLAG_ACCUMULATE : 0u) |
+                                                                                                       (reproject ? RT_FLAG_REPROJECT : 0u));
         pipes[(size_t)g] = rt::render::create_instance(cfg, noise.data(), game, &err);
         if (!pipes[(size_t)g]) {
             std::fprintf(stderr, "create_instance failed on device %d: %s\n", devices[(size_t)g], err.c_str());
@@ -291,6 +302,10 @@ int main(int argc, char** argv) {
                 if (f > 0) perf.push_sample(millis);
             }
             int rc = RT_OK;
+            if (camera_step != 0.0f && f > 0) {   // (one device: this thread is the only one that reads the camera)
+                game.camera.origin[0] += camera_step;
+                game.camera.heading += camera_step / 100.0f;
+            }
             if (edits > 0) {
                 set_solid(brushes[(size_t)g], f);
                 rc = rt_edit_voxels(p->context(), brushes[(size_t)g].data(), (uint32_t)edits);
@@ -380,13 +395,13 @@ int main(int argc, char** argv) {
         std::printf("{\"binary\": \"rt_bench\", \"config\": {\"width\": %d, \"height\": %d, \"spp\": %d, \"depth\": %d, \"gpus\": %d, "
                     "\"gather\": \"%s\", \"post_passes\": %s, \"pose\": [%g, %g, %g, %g, %g], \"sun_angle\": %g}, \"frames\": %d, \"rays_per_frame\": %llu, "
                     "\"ms_per_frame\": %.4f, \"avg_ms_last_120\": %.4f, \"max_ms_last_120\": %.4f, \"mrays_per_s\": %.2f, "
-                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"samples\": %u, "
+                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"reproject\": %s, \"camera_step\": %g, \"samples\": %u, "
                     "\"edits\": %d, \"edit_spread\": %s, \"edit_device_ms_per_call\": %.4f, \"edit_launches_per_call\": %.1f, "
                     "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f}\n",
                     width, height, spp, depth, gpus, gather ? (overlap ? "rccl-overlapped" : "rccl-serial") : "none", post ? "true" : "false",
                     game.camera.origin[0], game.camera.origin[1], game.camera.origin[2], game.camera.heading, game.camera.pitch,
                     game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum,
-                    accumulate ? "true" : "false", acc_samples, edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
+                    accumulate ? "true" : "false", reproject ? "true" : "false", (double)camera_step, acc_samples, edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
                     edit_host_ms, edit_wall_ms);
     }
     for (int g = 0; g < gpus; g++) {

@@ -24,13 +24,14 @@ class RtError(RuntimeError):
 
 
 def make_config(width, height, spp=1, depth=2, device=0, tile_rank=0, tile_world=1, kernel=RT_KERNEL_DEFAULT, flags=0,
-                region=256):
+                region=256, history_cap=0):
     cfg = RtConfig()
     cfg.struct_size = C.sizeof(RtConfig)
     cfg.width, cfg.height, cfg.region = int(width), int(height), int(region)
     cfg.spp, cfg.depth, cfg.device = int(spp), int(depth), int(device)
     cfg.tile_rank, cfg.tile_world = int(tile_rank), int(tile_world)
     cfg.kernel, cfg.flags = int(kernel), int(flags)
+    cfg.history_cap = int(history_cap)   # RT_FLAG_REPROJECT: 0 = the default (32)
     return cfg
 
 
@@ -360,6 +361,13 @@ class Context:
         frames, samples = C.c_uint32(0), C.c_uint32(0)
         self._check(self._lib.rt_get_accumulation(self._h, C.byref(frames), C.byref(samples)))
         return int(frames.value), int(samples.value)
+
+    def read_history(self):
+        """rt_read_history: uint32[H, W] per-pixel sample counts behind the lighting of the frame drawn last (RT_FLAG_REPROJECT
+        contexts; row 0 = bottom).  Synchronises."""
+        out = np.empty((self.cfg.height, self.cfg.width), dtype=np.uint32)
+        self._check(self._lib.rt_read_history(self._h, _p(out), out.nbytes))
+        return out
 
     def info(self):
         i = RtInfo()
