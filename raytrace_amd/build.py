@@ -26,12 +26,12 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
              "-Wall", "-Wno-unused-function"]
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra"]
 
-AMD_SRCS = [os.path.join(CSRC, "rt_kernels.hip"), os.path.join(CSRC, "rt_persist.hip"), os.path.join(CSRC, "rt_paths.hip"), os.path.join(CSRC, "rt_frame.hip"), os.path.join(CSRC, "rt_post.hip"),
+AMD_SRCS = [os.path.join(CSRC, "rt_kernels.hip"), os.path.join(CSRC, "rt_world.hip"), os.path.join(CSRC, "rt_persist.hip"), os.path.join(CSRC, "rt_paths.hip"), os.path.join(CSRC, "rt_frame.hip"), os.path.join(CSRC, "rt_post.hip"),
             os.path.join(CSRC, "rt_edit.hip"), os.path.join(CSRC, "rt_query.hip"), os.path.join(CSRC, "rt_terrain.hip"),
             os.path.join(CSRC, "rt_temporal.hip"),
             os.path.join(CSRC, "rt_api.hip")]
-AMD_DEPS = AMD_SRCS + [os.path.join(CSRC, "rt_device.hpp"), os.path.join(CSRC, "rt_kernels.hpp"), os.path.join(CSRC, "rt_dda.hpp"), os.path.join(CSRC, "rt_pslot.hpp"),
-                       os.path.join(INC, "rt_abi.h"), os.path.join(INC, "rt_math.h")]
+AMD_DEPS = AMD_SRCS + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")) + [
+    os.path.join(INC, "rt_abi.h"), os.path.join(INC, "rt_math.h")]
 HOST_SRCS = [os.path.join(HOST, f) for f in ("world.cpp", "chunk_storage.cpp", "terrain_upload.cpp", "render.cpp", "host_capi.cpp")]
 HOST_DEPS = HOST_SRCS + [os.path.join(HOST, f) for f in ("world.hpp", "render.hpp", "chunk_storage.hpp", "terrain_upload.hpp")] + [os.path.join(INC, "rt_abi.h")]
 BENCH_SRCS = [os.path.join(HOST, "rt_bench.cpp")]

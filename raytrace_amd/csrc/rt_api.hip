@@ -413,6 +413,23 @@ hipError_t sync_lanes(RtContext* c) {
     return e;
 }
 
+// ---- a change of the resident world on the render stream (slabs, edits, generated terrain) ---------------------------------------
+// before its launches: they wait for the frames in flight on every lane and for the queries recorded so far (both read the region)
+hipError_t world_change_begin(RtContext* c) {
+    hipError_t e = join_lanes_into(c, c->stream);
+    if (e == hipSuccess && c->query_recorded) e = hipStreamWaitEvent(c->stream, c->ev_query, 0);
+    return e;
+}
+// after them: later queries (ev_world) and later frames, whichever lane they start on, see what changed
+hipError_t world_change_end(RtContext* c) {
+    if (c->ev_world) {
+        hipError_t e = hipEventRecord(c->ev_world, c->stream);
+        if (e != hipSuccess) return e;
+        c->world_recorded = true;
+    }
+    return fence_lanes_after(c, c->stream);
+}
+
 // ---- staging (StagingSet) ---------------------------------------------------------------------------------------------------
 // the upload stream and the set's events, created on first use
 hipError_t staging_create(RtContext* c, StagingSet& s) {
@@ -447,17 +464,14 @@ hipError_t staging_send(RtContext* c, StagingSet& s, size_t bytes) {
     if (e != hipSuccess) return e;
     s.copy_pending = true;
     e = hipStreamWaitEvent(c->stream, s.ev_copied, 0);
-    if (e == hipSuccess) e = join_lanes_into(c, c->stream);
-    if (e == hipSuccess && c->query_recorded) e = hipStreamWaitEvent(c->stream, c->ev_query, 0);   // queries still reading the region
-    return e;
+    return e == hipSuccess ? world_change_begin(c) : e;
 }
 // after the launch that read the device block: later frames, whichever lane they start on, see what it changed
 hipError_t staging_applied(RtContext* c, StagingSet& s) {
     hipError_t e = hipEventRecord(s.ev_applied, c->stream);
     if (e != hipSuccess) return e;
     s.apply_recorded = true;
-    if (c->ev_world) { e = hipEventRecord(c->ev_world, c->stream); if (e != hipSuccess) return e; c->world_recorded = true; }
-    return fence_lanes_after(c, c->stream);
+    return world_change_end(c);
 }
 
 int reflatten(RtContext* c, const uint8_t* d_mine_lin, const uint32_t* d_mat_lin) {
@@ -1187,14 +1201,12 @@ int generate_terrain(RtContext* c, uint64_t seed, const int64_t lo[3], int axis)
         RT_HIP(c, dev_alloc(c, &c->d_heights, cols));
     }
     c->accum_valid = false;
-    RT_HIP(c, join_lanes_into(c, c->stream));
-    if (c->query_recorded) RT_HIP(c, hipStreamWaitEvent(c->stream, c->ev_query, 0));   // queries still reading the region
+    RT_HIP(c, world_change_begin(c));
     {
         LaunchTimer t(c, 1);
         RT_HIP(c, rtd::launch_terrain(c->d_mine_sw, c->d_mat_sw, c->d_coarse, c->d_brick, c->d_heights, c->logr, seed, lo, axis, c->stream));
     }
-    if (c->ev_world) { RT_HIP(c, hipEventRecord(c->ev_world, c->stream)); c->world_recorded = true; }
-    RT_HIP(c, fence_lanes_after(c, c->stream));
+    RT_HIP(c, world_change_end(c));
     return RT_OK;
 }
 }  // namespace

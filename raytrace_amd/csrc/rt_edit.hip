@@ -1,15 +1,14 @@
-// rt_edit.hip — gfx950 kernels of rt_edit_voxels, rt_read_box and rt_selftest(RT_SELFTEST_SCENE_MAPS).
+// rt_edit.hip — gfx950 kernels of rt_edit_voxels.
 //
 //   k_rebuild_chunks   : one workgroup per touched 64^3 chunk: scatters the chunk's edited material words, loads its occupancy
 //                        (minefield == 0) into an LDS bitmap, applies the edits' solid bits, builds the OR pyramid of levels 1..6
 //                        and writes the chunk's whole minefield back with pack_into's rule (src/world/chunk.rs:125-184)
-//   k_rebuild_chunk_maps: the coarse (and, above R = 256, brick) nibble-map words that cover the touched chunks
-//   k_check_maps       : recomputes every nibble-map word from the resident minefield and counts the ones that differ
-//   k_read_box         : un-tiles a box of the swizzled region into the caller's layout (x fastest)
+//   k_rebuild_chunk_maps: the coarse (and, above R = 256, brick) nibble-map words that cover the touched chunks (rt_world.hpp's rule)
 #include <hip/hip_runtime.h>
 
 #include "rt_device.hpp"
 #include "rt_kernels.hpp"
+#include "rt_world.hpp"
 
 namespace rtd {
 
@@ -35,48 +34,6 @@ __device__ __forceinline__ uint32_t or_pairs64(uint64_t v) {
     t = (t | (t >> 8)) & 0x0000FFFF0000FFFFull;
     t = (t | (t >> 16)) & 0x00000000FFFFFFFFull;
     return (uint32_t)t;
-}
-
-// nibble of 64 bytes of the swizzled minefield (one 4^3 brick): the common value if all are equal and below 15, else 15
-__device__ __forceinline__ uint32_t brick_nibble(const uint8_t* mine_sw, size_t brick) {
-    const uint4* src = reinterpret_cast<const uint4*>(mine_sw + (brick << 6));
-    const uint4 a = src[0], q = src[1], d = src[2], e = src[3];
-    const uint32_t first = a.x & 0xFFu, splat = first * 0x01010101u;
-    const uint32_t diff = (a.x ^ splat) | (a.y ^ splat) | (a.z ^ splat) | (a.w ^ splat) | (q.x ^ splat) | (q.y ^ splat) |
-                          (q.z ^ splat) | (q.w ^ splat) | (d.x ^ splat) | (d.y ^ splat) | (d.z ^ splat) | (d.w ^ splat) |
-                          (e.x ^ splat) | (e.y ^ splat) | (e.z ^ splat) | (e.w ^ splat);
-    return (diff == 0u && first < kNibMixed) ? first : kNibMixed;
-}
-
-// Coarse nibble-map word w (8 x-adjacent cubes of edge R/64): the value k_build_coarse (rt_kernels.hip) stores there.
-__device__ uint32_t coarse_word(const uint8_t* mine_sw, uint32_t w, int logr) {
-    const int lb = logr - 2, sub = logr - 8;
-    const uint32_t nsub = 1u << sub;
-    uint32_t word = 0;
-    for (uint32_t b = 0; b < 8u; b++) {
-        const uint32_t c = w * 8u + b;
-        const uint32_t cx = c & 63u, cy = (c >> 6) & 63u, cz = c >> 12;
-        uint32_t nib = 0, first = 0;
-        bool mixed = false;
-        for (uint32_t bz = 0; bz < nsub && !mixed; bz++)
-            for (uint32_t by = 0; by < nsub && !mixed; by++)
-                for (uint32_t bx = 0; bx < nsub && !mixed; bx++) {
-                    const size_t brick = (((((size_t)(cz << sub) + bz) << lb) + ((cy << sub) + by)) << lb) + ((cx << sub) + bx);
-                    const uint32_t n = brick_nibble(mine_sw, brick);
-                    if ((bz | by | bx) == 0u) first = n;
-                    mixed = n == kNibMixed || n != first;
-                }
-        nib = mixed ? kNibMixed : first;
-        word |= nib << (4 * b);
-    }
-    return word;
-}
-
-// Per-brick nibble-map word w (R > 256; 8 x-adjacent bricks): the value k_build_brick stores there.
-__device__ __forceinline__ uint32_t brick_word(const uint8_t* mine_sw, uint32_t w) {
-    uint32_t word = 0;
-    for (uint32_t b = 0; b < 8u; b++) word |= brick_nibble(mine_sw, (size_t)w * 8u + b) << (4 * b);
-    return word;
 }
 
 }  // namespace
@@ -105,7 +62,7 @@ __global__ __launch_bounds__(1024) void k_rebuild_chunks(uint8_t* __restrict__ m
     // ---- load: occupancy of the resident minefield, 16 ballots per 1 KiB row ---------------------------------------------
     for (int q = wave; q < 256; q += 16) {
         const int bz = q >> 4, by = q & 15;
-        const size_t brick = ((size_t)(cz * 16u + bz) << (2 * lb)) | ((size_t)(cy * 16u + by) << lb) | (size_t)(cx * 16u + bx);
+        const size_t brick = brick_index(cx * 16u + bx, cy * 16u + by, cz * 16u + bz, lb);
         const uint4 v = *reinterpret_cast<const uint4*>(mine_sw + (brick << 6) + zl * 16);
         const uint32_t dw[4] = {v.x, v.y, v.z, v.w};
         uint64_t ball[16];
@@ -206,7 +163,7 @@ __global__ __launch_bounds__(1024) void k_rebuild_chunks(uint8_t* __restrict__ m
             }
             dw[r] = d;
         }
-        const size_t brick = ((size_t)(cz * 16u + bz) << (2 * lb)) | ((size_t)(cy * 16u + by) << lb) | (size_t)(cx * 16u + bx);
+        const size_t brick = brick_index(cx * 16u + bx, cy * 16u + by, cz * 16u + bz, lb);
         *reinterpret_cast<uint4*>(mine_sw + (brick << 6) + zl * 16) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
     }
 }
@@ -233,34 +190,10 @@ __global__ __launch_bounds__(512) void k_rebuild_chunk_maps(const uint8_t* __res
         } else {
             const uint32_t u = t - ncw;
             const uint32_t wx = 2u * cx + (u & 1u), by = cy * 16u + ((u >> 1) & 15u), bz = cz * 16u + (u >> 5);
-            const uint32_t w = (((bz << lb) + by) << (lb - 3)) + wx;
+            const uint32_t w = brick_index(8u * wx, by, bz, lb) >> 3;
             brick_words[w] = brick_word(mine_sw, w);
         }
     }
-}
-
-// rt_selftest(RT_SELFTEST_SCENE_MAPS): thread t recomputes coarse word t (t < 32768) or brick word t - 32768 and counts a difference.
-__global__ __launch_bounds__(256) void k_check_maps(const uint8_t* __restrict__ mine_sw, const uint32_t* __restrict__ coarse,
-                                                    const uint32_t* __restrict__ brick_words, uint32_t nbrick_words, int logr,
-                                                    unsigned long long* __restrict__ mismatches) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    bool differs = false;
-    if (t < (uint32_t)kCoarseWords) differs = coarse_word(mine_sw, t, logr) != coarse[t];
-    else if (t - (uint32_t)kCoarseWords < nbrick_words) differs = brick_word(mine_sw, t - kCoarseWords) != brick_words[t - kCoarseWords];
-    const uint64_t m = __ballot(differs);
-    if ((threadIdx.x & 63u) == 0u && m) atomicAdd(mismatches, (unsigned long long)__popcll(m));
-}
-
-// rt_read_box: out[i] for i over the box (x0, y0, z0) + [0, ex) x [0, ey) x [0, nz), x fastest.  Either output may be null.
-__global__ __launch_bounds__(256) void k_read_box(const uint8_t* __restrict__ mine_sw, const uint32_t* __restrict__ mat_sw, int logr,
-                                                  int x0, int y0, int z0, int ex, int ey, uint64_t n, uint32_t* __restrict__ mat_out,
-                                                  uint8_t* __restrict__ mine_out) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const int x = x0 + (int)(i % (uint64_t)ex), y = y0 + (int)((i / (uint64_t)ex) % (uint64_t)ey), z = z0 + (int)(i / ((uint64_t)ex * ey));
-    const uint32_t s = swizzled_index(x, y, z, logr - 2);
-    if (mat_out) mat_out[i] = mat_sw[s];
-    if (mine_out) mine_out[i] = mine_sw[s];
 }
 
 hipError_t launch_rebuild_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const uint32_t* offs, const uint2* recs,
@@ -274,24 +207,6 @@ hipError_t launch_rebuild_chunk_maps(const uint8_t* mine_sw, uint32_t* coarse, u
                                      int logr, hipStream_t st) {
     if (nchunks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_rebuild_chunk_maps, dim3(nchunks), dim3(512), 0, st, mine_sw, coarse, logr > 8 ? brick : nullptr, chunks, logr);
-    return hipGetLastError();
-}
-
-hipError_t launch_check_maps(const uint8_t* mine_sw, const uint32_t* coarse, const uint32_t* brick, int logr,
-                             unsigned long long* mismatches, hipStream_t st) {
-    const uint32_t nbw = (logr > 8 && brick) ? (1u << (3 * (logr - 2))) / 8u : 0u;
-    const uint32_t n = (uint32_t)kCoarseWords + nbw;
-    hipLaunchKernelGGL(k_check_maps, dim3((n + 255u) / 256u), dim3(256), 0, st, mine_sw, coarse, nbw ? brick : nullptr, nbw, logr,
-                       mismatches);
-    return hipGetLastError();
-}
-
-hipError_t launch_read_box(const uint8_t* mine_sw, const uint32_t* mat_sw, int logr, int x0, int y0, int z0, int ex, int ey, int nz,
-                           uint32_t* mat_out, uint8_t* mine_out, hipStream_t st) {
-    const uint64_t n = (uint64_t)ex * (uint64_t)ey * (uint64_t)nz;
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_read_box, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, st, mine_sw, mat_sw, logr, x0, y0, z0, ex, ey, n,
-                       mat_out, mine_out);
     return hipGetLastError();
 }
 

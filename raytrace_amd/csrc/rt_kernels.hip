@@ -1,6 +1,6 @@
-// rt_kernels.hip — gfx950 kernels of the ray-trace path.
+// rt_kernels.hip — gfx950 kernels of the two baseline pipelines and of the multi-GPU gather.  (The world's layout and its nibble maps
+// are rt_world.hip; the kernels a default frame runs are rt_paths.hip, rt_frame.hip and rt_persist.hip.)
 //
-//   flatten      : linear 256^3 arrays -> 4^3-brick-swizzled arrays + per-brick nibble map (src/world -> GPU layout)
 //   k_mega       : one thread per pixel, every ray inline (straight restatement; generic in lr; baseline + fallback)
 //   k_trace      : persistent wave64 traversal: __ballot lane compaction/refill, nibble map in LDS, SoA ray queue
 //   k_shade0/N   : per-path shading between traversal waves: sky, shadow/diffuse ray spawn, light unwinding
@@ -15,115 +15,6 @@
 #include "rt_kernels.hpp"
 
 namespace rtd {
-
-// =====================================================================================================
-// Scene flattening
-// =====================================================================================================
-// dst index i (swizzled) <- src linear index (x fastest, util.rs:104-106).  Writes are fully coalesced; reads come
-// in 4-voxel runs.  Flags minefield values above kMaxStepValue (the reference writes 0..6, chunk.rs:163-183).
-__global__ __launch_bounds__(256) void k_flatten_voxels(const uint8_t* __restrict__ mine_lin,
-                                                        const uint32_t* __restrict__ mat_lin,
-                                                        uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ mat_sw,
-                                                        uint32_t* __restrict__ bad_value_flag, int logr) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // grid covers exactly R^3 (< 2^31)
-    const int lb = logr - 2;
-    const uint32_t bmask = (1u << lb) - 1u;
-    uint32_t brick = i >> 6, l = i & 63u;
-    uint32_t ix = ((brick & bmask) << 2) | (l & 3u);
-    uint32_t iy = (((brick >> lb) & bmask) << 2) | ((l >> 2) & 3u);
-    uint32_t iz = ((brick >> (2 * lb)) << 2) | (l >> 4);
-    size_t src = (((((size_t)iz << logr) + iy) << logr)) + ix;
-    uint8_t v = mine_lin[src];
-    if (v > kMaxStepValue) atomicOr(bad_value_flag, 1u);
-    mine_sw[i] = v;
-    mat_sw[i] = mat_lin[src];
-}
-
-// rt_upload_slice: the same re-tiling for ONE 16-thick slab (TerrainUploadManager::upload_slice, terrain_upload.rs:84-275 ->
-// vkCmdCopyBufferToImage with an offset).  The slab arrives as a dense box of extent 16 along `axis` and R along the other
-// two (x fastest); thread i handles swizzled voxel i of the slab's bricks — 4 brick layers along `axis`, whole bricks, so every
-// thread writes inside one 64-byte line run.  (The slab's values were checked on the host before it got here: rt_upload_slice.)
-__global__ __launch_bounds__(256) void k_flatten_slab(const uint8_t* __restrict__ mine_slab, const uint32_t* __restrict__ mat_slab,
-                                                      uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ mat_sw,
-                                                      int logr, int axis, int offset) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // grid covers exactly 16 * R^2
-    const int lb = logr - 2;
-    const uint32_t bmask = (1u << lb) - 1u;
-    const uint32_t l = i & 63u, sb = i >> 6;              // sb: brick within the slab, 4 layers along `axis`
-    // brick coordinates: the two full axes take lb bits each, the slab axis 2 bits (layer) on top of offset/4
-    uint32_t bc[3];
-    uint32_t rest = sb;
-    for (int a = 0; a < 3; a++) {
-        if (a == axis) { bc[a] = (uint32_t)(offset >> 2) + (rest & 3u); rest >>= 2; }
-        else { bc[a] = rest & bmask; rest >>= lb; }
-    }
-    const uint32_t ix = (bc[0] << 2) | (l & 3u), iy = (bc[1] << 2) | ((l >> 2) & 3u), iz = (bc[2] << 2) | (l >> 4);
-    const uint32_t R = 1u << logr;
-    const uint32_t sx = axis == 0 ? ix - (uint32_t)offset : ix, sy = axis == 1 ? iy - (uint32_t)offset : iy,
-                   sz = axis == 2 ? iz - (uint32_t)offset : iz;
-    const uint32_t ex = axis == 0 ? (uint32_t)RT_SLICE_SIZE : R, ey = axis == 1 ? (uint32_t)RT_SLICE_SIZE : R;
-    const size_t src = ((size_t)sz * ey + sy) * ex + sx;
-    const size_t dst = ((((size_t)bc[2] << lb) + bc[1]) << lb) + bc[0];
-    mine_sw[(dst << 6) | l] = mine_slab[src];
-    mat_sw[(dst << 6) | l] = mat_slab[src];
-}
-
-// One thread per nibble-map word = 8 consecutive coarse cubes (x-adjacent).  A coarse cube has edge R/64 and is made of
-// (R/256)^3 4^3-bricks of 64 contiguous bytes each in the swizzled minefield.
-// (word0, nwords[3]): the box of words to rebuild — the whole map for an upload, the layers a slab touches for rt_upload_slice.
-__global__ __launch_bounds__(256) void k_build_coarse(const uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ coarse, int logr,
-                                                      uint3 word0, uint3 nwords) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= nwords.x * nwords.y * nwords.z) return;
-    // word (wx, cy, cz): wx in [0, 8) covers coarse cubes cx = 8 wx .. 8 wx + 7
-    const uint32_t wx = word0.x + t % nwords.x, cy_ = word0.y + (t / nwords.x) % nwords.y, cz_ = word0.z + t / (nwords.x * nwords.y);
-    const uint32_t w = (cz_ << 9) | (cy_ << 3) | wx;
-    const int lb = logr - 2, sub = logr - 8;               // sub: log2(4^3-bricks per coarse cube edge)
-    const uint32_t nsub = 1u << sub;
-    uint32_t word = 0;
-    for (uint32_t b = 0; b < 8u; b++) {
-        const uint32_t c = w * 8u + b;                     // coarse cube (cz, cy, cx), 6 bits each
-        const uint32_t cx = c & 63u, cy = (c >> 6) & 63u, cz = c >> 12;
-        uint32_t first = 0, diff = 0;
-        for (uint32_t bz = 0; bz < nsub; bz++)
-            for (uint32_t by = 0; by < nsub; by++)
-                for (uint32_t bx = 0; bx < nsub; bx++) {
-                    const uint32_t brick = (((((cz << sub) + bz) << lb) + ((cy << sub) + by)) << lb) + ((cx << sub) + bx);
-                    const uint4* src = reinterpret_cast<const uint4*>(mine_sw + ((size_t)brick << 6));
-                    const uint4 a = src[0], q = src[1], d = src[2], e = src[3];
-                    if ((bz | by | bx) == 0u) first = a.x & 0xFFu;
-                    const uint32_t splat = first * 0x01010101u;
-                    diff |= (a.x ^ splat) | (a.y ^ splat) | (a.z ^ splat) | (a.w ^ splat) | (q.x ^ splat) | (q.y ^ splat) |
-                            (q.z ^ splat) | (q.w ^ splat) | (d.x ^ splat) | (d.y ^ splat) | (d.z ^ splat) | (d.w ^ splat) |
-                            (e.x ^ splat) | (e.y ^ splat) | (e.z ^ splat) | (e.w ^ splat);
-                }
-        const uint32_t nib = (diff == 0u && first < kNibMixed) ? first : kNibMixed;
-        word |= nib << (4 * b);
-    }
-    coarse[w] = word;
-}
-
-// Regions above 256 (round 4): the per-BRICK nibble map behind the coarse one (Scene::brick).  One thread per word = 8 x-adjacent
-// bricks; brick (bz, by, bx) is 64 consecutive bytes of the swizzled minefield at index ((bz << lb | by) << lb | bx) << 6.
-// (word0, nwords): the box of words to rebuild, in (x word, brick y, brick z) — everything for an upload, a slab's for rt_upload_slice.
-__global__ __launch_bounds__(256) void k_build_brick(const uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ brick_words, int lb,
-                                                     uint3 word0, uint3 nwords) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= nwords.x * nwords.y * nwords.z) return;
-    const uint32_t wx = word0.x + t % nwords.x, by = word0.y + (t / nwords.x) % nwords.y, bz = word0.z + t / (nwords.x * nwords.y);
-    const uint32_t w = (((bz << lb) + by) << (lb - 3)) + wx;      // word index: 8 bricks per word along x
-    uint32_t word = 0;
-    for (uint32_t b = 0; b < 8u; b++) {
-        const uint4* src = reinterpret_cast<const uint4*>(mine_sw + ((size_t)(w * 8u + b) << 6));
-        const uint4 a = src[0], q = src[1], d = src[2], e = src[3];
-        const uint32_t first = a.x & 0xFFu, splat = first * 0x01010101u;
-        const uint32_t diff = (a.x ^ splat) | (a.y ^ splat) | (a.z ^ splat) | (a.w ^ splat) | (q.x ^ splat) | (q.y ^ splat) |
-                              (q.z ^ splat) | (q.w ^ splat) | (d.x ^ splat) | (d.y ^ splat) | (d.z ^ splat) | (d.w ^ splat) |
-                              (e.x ^ splat) | (e.y ^ splat) | (e.z ^ splat) | (e.w ^ splat);
-        word |= ((diff == 0u && first < kNibMixed) ? first : kNibMixed) << (4 * b);
-    }
-    brick_words[w] = word;
-}
 
 // =====================================================================================================
 // k_mega — one thread per pixel
@@ -541,48 +432,6 @@ __global__ __launch_bounds__(256) void k_untile(const uint8_t* __restrict__ gath
 // =====================================================================================================
 // Host-callable launchers (declared in rt_kernels.hpp)
 // =====================================================================================================
-hipError_t launch_flatten(const uint8_t* mine_lin, const uint32_t* mat_lin, uint8_t* mine_sw, uint32_t* mat_sw,
-                          uint32_t* coarse, uint32_t* brick, uint32_t* bad_flag, int logr, hipStream_t st) {
-    hipLaunchKernelGGL(k_flatten_voxels, dim3((1u << (3 * logr)) / 256u), dim3(256), 0, st, mine_lin, mat_lin, mine_sw, mat_sw,
-                       bad_flag, logr);
-    hipLaunchKernelGGL(k_build_coarse, dim3(kCoarseWords / 256), dim3(256), 0, st, mine_sw, coarse, logr, make_uint3(0, 0, 0),
-                       make_uint3(8, 64, 64));
-    if (logr > 8 && brick != nullptr) {
-        const int lb = logr - 2;
-        const uint32_t nb = 1u << lb, n = (nb / 8u) * nb * nb;
-        hipLaunchKernelGGL(k_build_brick, dim3((n + 255u) / 256u), dim3(256), 0, st, mine_sw, brick, lb, make_uint3(0, 0, 0), make_uint3(nb / 8u, nb, nb));
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_flatten_slab(const uint8_t* mine_slab, const uint32_t* mat_slab, uint8_t* mine_sw, uint32_t* mat_sw, uint32_t* coarse,
-                               uint32_t* brick, int logr, int axis, int offset, hipStream_t st) {
-    const uint32_t R = 1u << logr;
-    hipLaunchKernelGGL(k_flatten_slab, dim3(RT_SLICE_SIZE * R * R / 256u), dim3(256), 0, st, mine_slab, mat_slab, mine_sw, mat_sw,
-                       logr, axis, offset);
-    // nibble-map entries the slab touches: coarse cubes have edge R/64, so 16 voxels are 1024/R layers (4, 2, 1) — rounded out
-    // to whole words along x (a word holds 8 x-adjacent cubes, all recomputed from the re-tiled bytes)
-    const uint32_t e = R / 64u;
-    const uint32_t c0 = (uint32_t)offset / e, c1 = ((uint32_t)offset + RT_SLICE_SIZE - 1u) / e;   // inclusive cube range along `axis`
-    uint3 w0 = make_uint3(0, 0, 0), nw = make_uint3(8, 64, 64);
-    if (axis == 0) { w0.x = c0 / 8u; nw.x = c1 / 8u - w0.x + 1u; }
-    else if (axis == 1) { w0.y = c0; nw.y = c1 - c0 + 1u; }
-    else { w0.z = c0; nw.z = c1 - c0 + 1u; }
-    const uint32_t n = nw.x * nw.y * nw.z;
-    hipLaunchKernelGGL(k_build_coarse, dim3((n + 255u) / 256u), dim3(256), 0, st, mine_sw, coarse, logr, w0, nw);
-    if (logr > 8 && brick != nullptr) {   // the slab's four brick layers of the per-brick map (whole words along x)
-        const int lb = logr - 2;
-        const uint32_t nb = 1u << lb, b0 = (uint32_t)offset / 4u;
-        uint3 bw0 = make_uint3(0, 0, 0), bnw = make_uint3(nb / 8u, nb, nb);
-        if (axis == 0) { bw0.x = b0 / 8u; bnw.x = (b0 + 3u) / 8u - bw0.x + 1u; }
-        else if (axis == 1) { bw0.y = b0; bnw.y = 4u; }
-        else { bw0.z = b0; bnw.z = 4u; }
-        const uint32_t bn = bnw.x * bnw.y * bnw.z;
-        hipLaunchKernelGGL(k_build_brick, dim3((bn + 255u) / 256u), dim3(256), 0, st, mine_sw, brick, lb, bw0, bnw);
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_mega(const Scene& sc, const Frame& f, const Planes& pl, DevCounters* cn, bool count, hipStream_t st) {
     const uint32_t npix_pad = (uint32_t)f.ntiles_local * 64u;
     if (npix_pad == 0) return hipSuccess;

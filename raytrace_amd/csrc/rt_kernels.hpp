@@ -1,4 +1,4 @@
-// rt_kernels.hpp — argument blocks and host-callable launchers of the kernels in rt_kernels.hip.
+// rt_kernels.hpp — argument blocks and host-callable launchers of every kernel file (rt_*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -121,20 +121,26 @@ bool launch_paths_direct_ok(const Frame& f);   // does k_paths honour PersistArg
 hipError_t launch_paths(const Scene& sc, const Frame& f, const Planes& pl, const PersistArgs& a, bool count, int nworkgroups,
                         hipStream_t st);
 
+// rt_world.hip: the brick-swizzled region and its nibble maps.  A MapBoxes is the words of both maps that a change of the region
+// touches: a box of coarse words in (x word, cube y, cube z) and a box of brick words in (x word, brick y, brick z), first + count.
+struct MapBoxes { uint3 cw0, cwn, bw0, bwn; };
+MapBoxes map_boxes_region(int logr);                              // every word
+MapBoxes map_boxes_slab(int logr, int axis, int texel_offset);    // a 16-thick slab's
+hipError_t launch_build_maps(const uint8_t* mine_sw, uint32_t* coarse, uint32_t* brick /* R > 256: the per-brick map, else null */,
+                             int logr, const MapBoxes& boxes, hipStream_t st);
 hipError_t launch_flatten(const uint8_t* mine_lin, const uint32_t* mat_lin, uint8_t* mine_sw, uint32_t* mat_sw,
-                          uint32_t* coarse, uint32_t* brick /* R > 256: the per-brick map, else null */, uint32_t* bad_flag, int logr, hipStream_t st);
+                          uint32_t* coarse, uint32_t* brick, uint32_t* bad_flag, int logr, hipStream_t st);
 hipError_t launch_flatten_slab(const uint8_t* mine_slab, const uint32_t* mat_slab, uint8_t* mine_sw, uint32_t* mat_sw, uint32_t* coarse,
                                uint32_t* brick, int logr, int axis, int offset, hipStream_t st);
-// rt_edit.hip: rt_edit_voxels (chunk list, per-chunk edit ranges offs[0..n] and records as rt_edit.hip's k_rebuild_chunks
-// describes), rt_read_box, rt_selftest(RT_SELFTEST_SCENE_MAPS)
+hipError_t launch_check_maps(const uint8_t* mine_sw, const uint32_t* coarse, const uint32_t* brick, int logr,
+                             unsigned long long* mismatches, hipStream_t st);   // rt_selftest(RT_SELFTEST_SCENE_MAPS)
+hipError_t launch_read_box(const uint8_t* mine_sw, const uint32_t* mat_sw, int logr, int x0, int y0, int z0, int ex, int ey, int nz,
+                           uint32_t* mat_out, uint8_t* mine_out, hipStream_t st);
+// rt_edit.hip: rt_edit_voxels (chunk list, per-chunk edit ranges offs[0..n] and records as k_rebuild_chunks describes)
 hipError_t launch_rebuild_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const uint32_t* offs, const uint2* recs,
                                  uint32_t nchunks, int logr, hipStream_t st);
 hipError_t launch_rebuild_chunk_maps(const uint8_t* mine_sw, uint32_t* coarse, uint32_t* brick, const uint32_t* chunks, uint32_t nchunks,
                                      int logr, hipStream_t st);
-hipError_t launch_check_maps(const uint8_t* mine_sw, const uint32_t* coarse, const uint32_t* brick, int logr,
-                             unsigned long long* mismatches, hipStream_t st);
-hipError_t launch_read_box(const uint8_t* mine_sw, const uint32_t* mat_sw, int logr, int x0, int y0, int z0, int ex, int ey, int nz,
-                           uint32_t* mat_out, uint8_t* mine_out, hipStream_t st);
 // rt_terrain.hip: rt_generate_world (axis = -1: the window [lo, lo + R) on every axis) and rt_generate_slice (axis 0..2: 16 voxels
 // from lo[axis] along it); heights: int32 scratch for (R/64 + 1)^2 chunk columns of 64^2
 hipError_t launch_terrain(uint8_t* mine_sw, uint32_t* mat_sw, uint32_t* coarse, uint32_t* brick, int32_t* heights, int logr,

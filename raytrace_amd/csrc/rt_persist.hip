@@ -365,7 +365,7 @@ __global__ __launch_bounds__(1024, 4) void k_persist(Scene sc, Frame f, Planes p
                 // fetches of both slots first (:106 for a fresh ray, :137 otherwise), so their latencies overlap
                 // nibble-map entry: at R = 256 a coarse cube IS the 4^3 brick, so the entry index is vox >> 6
                 const uint32_t bS = LOGR == 8 ? S.vox >> 6 : S.cidx, bF = LOGR == 8 ? F.vox >> 6 : F.cidx;
-                // byte reads: entry b is nibble (b & 1) of byte b >> 1 (little-endian words, k_build_coarse)
+                // byte reads: entry b is nibble (b & 1) of byte b >> 1 (little-endian words, coarse_word, rt_world.hpp)
                 const uint32_t wS = s_nib[bS >> 1], wF = s_nib[bF >> 1];
                 uint32_t stS = (wS >> ((bS & 1u) << 2)) & 15u, stF = (wF >> ((bF & 1u) << 2)) & 15u;
                 const bool gS = S.tracing && stS == kNibMixed, gF = F.tracing && stF == kNibMixed;

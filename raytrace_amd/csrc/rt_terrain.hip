@@ -7,11 +7,12 @@
 //   k_terrain_fill   : one workgroup per world chunk that overlaps the window: the chunk column's 64^2 heights and their max
 //                      pyramid in LDS, then every voxel of the chunk inside the window from them — pack_into's minefield of a
 //                      generated chunk is a function of the heights alone (DESIGN.md "Terrain on the device")
-//   k_terrain_maps   : the coarse (and, above R = 256, brick) nibble-map words over the written box, recomputed from the bytes
+// The nibble-map words over the written box follow from the bytes (launch_build_maps, rt_world.hip).
 #include <hip/hip_runtime.h>
 
 #include "rt_device.hpp"
 #include "rt_kernels.hpp"
+#include "rt_world.hpp"
 
 namespace rtd {
 
@@ -92,18 +93,6 @@ __device__ __forceinline__ uint32_t tg_material(uint64_t col, int z) {
     const uint32_t r = (uint32_t)(tg_mix64(col ^ (uint64_t)(int64_t)z * kHashZ) >> 16);
     if (z < 80) return r % 60u < (uint32_t)(z - 20) ? kDirt : kGrass;
     return r % 80u < (uint32_t)(z - 80) ? kRock : kDirt;
-}
-
-// nibble of one 4^3 brick of the swizzled minefield (k_build_coarse / k_build_brick's rule)
-__device__ __forceinline__ uint32_t tg_brick_nibble(const uint8_t* mine_sw, size_t brick, uint32_t* first_out) {
-    const uint4* src = reinterpret_cast<const uint4*>(mine_sw + (brick << 6));
-    const uint4 a = src[0], q = src[1], d = src[2], e = src[3];
-    const uint32_t first = a.x & 0xFFu, splat = first * 0x01010101u;
-    const uint32_t diff = (a.x ^ splat) | (a.y ^ splat) | (a.z ^ splat) | (a.w ^ splat) | (q.x ^ splat) | (q.y ^ splat) |
-                          (q.z ^ splat) | (q.w ^ splat) | (d.x ^ splat) | (d.y ^ splat) | (d.z ^ splat) | (d.w ^ splat) |
-                          (e.x ^ splat) | (e.y ^ splat) | (e.z ^ splat) | (e.w ^ splat);
-    *first_out = first;
-    return (diff == 0u && first < kNibMixed) ? first : kNibMixed;
 }
 
 }  // namespace
@@ -222,58 +211,12 @@ __global__ __launch_bounds__(256) void k_terrain_fill(uint8_t* __restrict__ mine
             }
         }
         const uint32_t tx = tx0 + (uint32_t)lx, ty = ty0 + (uint32_t)ly, tz = (tz0 + (uint32_t)lz) & rmask;
-        const size_t brick = ((size_t)(tz >> 2) << (2 * lb)) | ((size_t)(ty >> 2) << lb) | (size_t)(tx >> 2);
+        const size_t brick = brick_index(tx >> 2, ty >> 2, tz >> 2, lb);
         const size_t at = (brick << 6) | ((size_t)(tz & 3u) << 4);
         *reinterpret_cast<uint4*>(mine_sw + at) = make_uint4(mine[0], mine[1], mine[2], mine[3]);
         uint4* mdst = reinterpret_cast<uint4*>(mat_sw + at);
 #pragma unroll
         for (int r = 0; r < 4; r++) mdst[r] = make_uint4(mats[4 * r], mats[4 * r + 1], mats[4 * r + 2], mats[4 * r + 3]);
-    }
-}
-
-// The nibble-map words over the written box, recomputed from the bytes: thread t < ncw is coarse word t of the box (cw0, cwn) in
-// (x word, cube y, cube z); the rest are brick words of the box (bw0, bwn) in (x word, brick y, brick z) — the boxes of
-// launch_flatten (whole region) and launch_flatten_slab (one slab), with the values k_build_coarse / k_build_brick store.
-__global__ __launch_bounds__(256) void k_terrain_maps(const uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ coarse,
-                                                      uint32_t* __restrict__ brick_words, int logr, uint3 cw0, uint3 cwn, uint3 bw0,
-                                                      uint3 bwn) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t ncw = cwn.x * cwn.y * cwn.z, nbw = brick_words ? bwn.x * bwn.y * bwn.z : 0u;
-    const int lb = logr - 2;
-    if (t < ncw) {
-        const uint32_t wx = cw0.x + t % cwn.x, wy = cw0.y + (t / cwn.x) % cwn.y, wz = cw0.z + t / (cwn.x * cwn.y);
-        const uint32_t w = (wz << 9) | (wy << 3) | wx;
-        const int sub = logr - 8;
-        const uint32_t nsub = 1u << sub;
-        uint32_t word = 0;
-        for (uint32_t b = 0; b < 8u; b++) {
-            const uint32_t c = w * 8u + b;
-            const uint32_t cx = c & 63u, cy = (c >> 6) & 63u, cz = c >> 12;
-            uint32_t first = 0, nib = 0;
-            bool mixed = false;
-            for (uint32_t bz = 0; bz < nsub && !mixed; bz++)
-                for (uint32_t by = 0; by < nsub && !mixed; by++)
-                    for (uint32_t bx = 0; bx < nsub && !mixed; bx++) {
-                        const size_t brick = (((((size_t)(cz << sub) + bz) << lb) + ((cy << sub) + by)) << lb) + ((cx << sub) + bx);
-                        uint32_t f;
-                        const uint32_t n = tg_brick_nibble(mine_sw, brick, &f);
-                        if ((bz | by | bx) == 0u) first = f;
-                        mixed = n == kNibMixed || f != first;
-                    }
-            nib = mixed ? kNibMixed : first;
-            word |= nib << (4 * b);
-        }
-        coarse[w] = word;
-    } else if (t - ncw < nbw) {
-        const uint32_t u = t - ncw;
-        const uint32_t wx = bw0.x + u % bwn.x, by = bw0.y + (u / bwn.x) % bwn.y, bz = bw0.z + u / (bwn.x * bwn.y);
-        const uint32_t w = (((bz << lb) + by) << (lb - 3)) + wx;
-        uint32_t word = 0;
-        for (uint32_t b = 0; b < 8u; b++) {
-            uint32_t f;
-            word |= tg_brick_nibble(mine_sw, (size_t)w * 8u + b, &f) << (4 * b);
-        }
-        brick_words[w] = word;
     }
 }
 
@@ -294,23 +237,9 @@ hipError_t launch_terrain(uint8_t* mine_sw, uint32_t* mat_sw, uint32_t* coarse, 
     const int3 ilo = make_int3((int)lo[0], (int)lo[1], (int)lo[2]), iext = make_int3((int)ext[0], (int)ext[1], (int)ext[2]);
     hipLaunchKernelGGL(k_terrain_fill, dim3((unsigned)nc[0], (unsigned)nc[1], (unsigned)nc[2]), dim3(256), 0, st, mine_sw, mat_sw,
                        (const int32_t*)heights, hw, ic0, ilo, iext, seed, logr);
-    // nibble-map words: everything for a whole region; the words a slab touches (launch_flatten_slab's boxes) for one slab
-    const uint32_t nb = 1u << (logr - 2);
-    uint3 cw0 = make_uint3(0, 0, 0), cwn = make_uint3(8, 64, 64), bw0 = make_uint3(0, 0, 0), bwn = make_uint3(nb / 8u, nb, nb);
-    if (axis >= 0) {
-        const uint32_t off = (uint32_t)((lo[axis] + R / 2) & (R - 1));   // the slab's texel offset along `axis`
-        const uint32_t e = (uint32_t)R / 64u;
-        const uint32_t a0 = off / e, a1 = (off + RT_SLICE_SIZE - 1u) / e;
-        const uint32_t b0 = off / 4u;
-        if (axis == 0) { cw0.x = a0 / 8u; cwn.x = a1 / 8u - cw0.x + 1u; bw0.x = b0 / 8u; bwn.x = (b0 + 3u) / 8u - bw0.x + 1u; }
-        else if (axis == 1) { cw0.y = a0; cwn.y = a1 - a0 + 1u; bw0.y = b0; bwn.y = 4u; }
-        else { cw0.z = a0; cwn.z = a1 - a0 + 1u; bw0.z = b0; bwn.z = 4u; }
-    }
-    uint32_t* bmap = logr > 8 ? brick : nullptr;
-    const uint32_t n = cwn.x * cwn.y * cwn.z + (bmap ? bwn.x * bwn.y * bwn.z : 0u);
-    hipLaunchKernelGGL(k_terrain_maps, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint8_t*)mine_sw, coarse, bmap, logr, cw0, cwn,
-                       bw0, bwn);
-    return hipGetLastError();
+    // nibble-map words: everything for a whole region, the words a slab at its texel offset touches for one slab
+    const MapBoxes boxes = axis < 0 ? map_boxes_region(logr) : map_boxes_slab(logr, axis, (int)((lo[axis] + R / 2) & (R - 1)));
+    return launch_build_maps(mine_sw, coarse, brick, logr, boxes, st);
 }
 
 }  // namespace rtd

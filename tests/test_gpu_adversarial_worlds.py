@@ -144,6 +144,7 @@ def test_slabs_across_the_nibble_boundaries(R, blue_noise, native_built):
             ctxs.append(ctx)
             ctx.upload_world(mats, mine)
             ctx.upload_noise(blue_noise)
+            assert ctx.selftest(abi.RT_SELFTEST_SCENE_MAPS) == 0      # every nibble value, uniform 15..30 included (mixed)
         rng = np.random.default_rng(R)
         slab_bricks = np.zeros((64, 64, 64), dtype=np.uint8) if R == 256 else None
         for k, (axis, off) in enumerate(edits):
@@ -165,6 +166,8 @@ def test_slabs_across_the_nibble_boundaries(R, blue_noise, native_built):
                     sm[:] = nt.reshape(-1)
                     sf[:] = nm.reshape(-1)
                     ctx.upload_slice(axis, off, sm, sf)
+        for ctx in ctxs:
+            assert ctx.selftest(abi.RT_SELFTEST_SCENE_MAPS) == 0      # ... and after the slabs' partial rebuilds
         cpu, _ = po.render(mats, mine, blue_noise, u, W, H, spp, depth, region=R)
         for ctx, (kernel, flags) in zip(ctxs, runs):
             ctx.draw_frame(u)
@@ -181,6 +184,34 @@ def test_slabs_across_the_nibble_boundaries(R, blue_noise, native_built):
         # the rays cross the slabs: the oracle's fetch statistics with the slabs' bricks as the "uniform" set count the fetches there
         _, _, hist = po.fetch_histogram(mats, mine, blue_noise, u, W, H, spp, depth, bricks=slab_bricks)
         assert hist[1].sum() > 1000 and hist[1][7] + hist[1][15] + hist[1][6] + hist[1][14] > 0, hist[1]
+
+
+def test_brick_map_words_of_every_builder(monkeypatch, native_built):
+    """RT_BRICK_MAP makes the library keep the per-brick nibble map above R = 256 (no shipped kernel consults it, so nothing else
+    runs its builders): on the arbitrary world, the brick words of the upload, of uploaded slabs on each axis, of an edit batch, of
+    a generated slab and of a generated region against the voxel-by-voxel self-test."""
+    R = 512
+    monkeypatch.setenv("RT_BRICK_MAP", "1")
+    for k in [k for k in _WORLDS if k[1] > 256]:
+        del _WORLDS[k]
+    mats, mine, _, _ = aw.arbitrary_world(R)
+    rng = np.random.default_rng(7)
+    with render.Context(render.make_config(64, 64, region=R)) as ctx:
+        ctx.upload_world(mats, mine)
+        assert ctx.selftest(abi.RT_SELFTEST_SCENE_MAPS) == 0
+        for axis, off in ((0, 16), (0, 208), (1, 0), (2, R - 16)):       # x slabs inside one brick word and across two
+            sl = [slice(None)] * 3
+            sl[2 - axis] = slice(off, off + 16)
+            nm, nt = _edit_slab(mine[tuple(sl)], mats[tuple(sl)], rng, R // 64)
+            ctx.upload_slice(axis, off, np.ascontiguousarray(nt), np.ascontiguousarray(nm))
+            assert ctx.selftest(abi.RT_SELFTEST_SCENE_MAPS) == 0, (axis, off)
+        n = 3000
+        ctx.edit_voxels(rng.integers(0, R, size=(n, 3)), rng.integers(0, 1 << 32, size=n, dtype=np.uint32), rng.random(n) < 0.5)
+        assert ctx.selftest(abi.RT_SELFTEST_SCENE_MAPS) == 0
+        ctx.generate_slice(0x5EED, 0, (R // 2 + 32, -R // 2, -R // 2))
+        assert ctx.selftest(abi.RT_SELFTEST_SCENE_MAPS) == 0
+        ctx.generate_world(0x5EED)
+        assert ctx.selftest(abi.RT_SELFTEST_SCENE_MAPS) == 0
 
 
 @pytest.mark.parametrize("W,H", [(1, 1), (3, 50), (333, 77), (1920, 1080)])

@@ -9,13 +9,15 @@ unrolled RT_PATHS_STEPS_PER_CHECK repetitions of the four ray slots).  The scrip
 """
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-files = ["rt_paths.hip", "rt_frame.hip", "rt_persist.hip", "rt_kernels.hip", "rt_post.hip", "rt_temporal.hip"]
+files = ["rt_paths.hip", "rt_frame.hip", "rt_persist.hip", "rt_kernels.hip", "rt_post.hip", "rt_temporal.hip", "rt_query.hip", "rt_world.hip",
+         "rt_edit.hip", "rt_terrain.hip"]
 FLAGS = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-I", os.path.join(ROOT, "include"),
          "--cuda-device-only"]
 
 
 def demangle(name):
-    return subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().split("(")[0].replace("void ", "")
+    # (k_query lives in an anonymous namespace: without the replace its name would be cut at that "(")
+    return subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")
 
 
 rows = []
