@@ -181,11 +181,31 @@ def normalize(v):
     return np.array(o[:], dtype=np.float32)
 
 
+def normalize_n(v):
+    """normalize() of every vector of float32[..., 3] in one call."""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    assert v.shape[-1] == 3
+    out = np.empty_like(v)
+    lib().rt_oracle_normalize_n(_p(v), _p(out), C.c_size_t(v.size // 3))
+    return out
+
+
 def unorm(x, maxv):
     f = lib().rt_oracle_unorm
     f.restype = C.c_uint32
     f.argtypes = [C.c_float, C.c_float]
     return int(f(float(x), float(maxv)))
+
+
+def unorm_n(x, maxv):
+    """unorm() of every element of a float32 array in one call: uint32 of the same shape."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty(x.shape, dtype=np.uint32)
+    f = lib().rt_oracle_unorm_n
+    f.restype = None
+    f.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_size_t]
+    f(_p(x), float(maxv), _p(out), x.size)
+    return out
 
 
 def f2u16(x):

@@ -596,6 +596,10 @@ void rt_oracle_normalize(const float* v3, float* out3) {
     rtm_vec3 o = rtm_normalize3({v3[0], v3[1], v3[2]});
     out3[0] = o.x; out3[1] = o.y; out3[2] = o.z;
 }
+// The same over n packed float3 vectors (in and out may be the same array).
+void rt_oracle_normalize_n(const float* v3, float* out3, size_t n) {
+    for (size_t i = 0; i < n; i++) rt_oracle_normalize(v3 + 3 * i, out3 + 3 * i);
+}
 // Texel coordinate (one axis) of the level-`level` noise_value lookup for a given noise_offset component
 // (raytrace.comp:324,336), exactly as level_light() computes it.
 int32_t rt_oracle_noise_level_texel(float noise_offset, int level) {
@@ -604,6 +608,9 @@ int32_t rt_oracle_noise_level_texel(float noise_offset, int level) {
     return c < 0 ? 0 : (c > 511 ? 511 : (int32_t)c);
 }
 uint32_t rt_oracle_unorm(float x, float maxv) { return rtm_unorm(x, maxv); }
+void rt_oracle_unorm_n(const float* x, float maxv, uint32_t* out, size_t n) {
+    for (size_t i = 0; i < n; i++) out[i] = rtm_unorm(x[i], maxv);
+}
 uint32_t rt_oracle_f2u16(float x) { return rtm_f2u16(x); }
 
 // The reference's region size (ROOT_BLOCK_WIDTH = 256).

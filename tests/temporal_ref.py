@@ -1,6 +1,7 @@
 """RT_FLAG_REPROJECT restated in numpy float32 (include/rt_abi.h, DESIGN.md "Reprojection"): one history set and the previous
 camera, fed with the oracle's one-sample frames.  Every operation is a float32 array operation rounded on its own; directions come
-from the oracle's normalize (rtm_normalize3, the one primary_ray uses), the UNORM plane from the oracle's unorm.
+from the oracle's normalize (rtm_normalize3, the one primary_ray uses), the UNORM plane from the oracle's unorm, both through
+their batched entry points: a frame costs two or three calls, not one per pixel.
 
     h = History(W, H, cap=32)
     lighting_f32, lighting_rgba16, counts, accepted = h.step(planes_of_the_oracle_frame, uniforms)
@@ -37,18 +38,12 @@ def directions(cam, xs, ys, W, H):
     sx = (xs.astype(f32) / f32(W)) * f32(2) - f32(1)
     sy = (ys.astype(f32) / f32(H)) * f32(2) - f32(1)
     v = (fwd + right * sx[..., None]) + up * sy[..., None]
-    flat = v.reshape(-1, 3)
-    out = np.empty_like(flat)
-    for i in range(flat.shape[0]):
-        out[i] = po.normalize(flat[i])
-    return out.reshape(v.shape)
+    return po.normalize_n(v)
 
 
 def unorm16(x):
-    """rtm_unorm(x, 65535) elementwise through the oracle (one call per distinct value)."""
-    vals, inv = np.unique(np.ascontiguousarray(x, dtype=f32).view(np.uint32), return_inverse=True)
-    q = np.array([po.unorm(v, 65535.0) for v in vals.view(f32)], dtype=np.uint16)
-    return q[inv].reshape(x.shape)
+    """rtm_unorm(x, 65535) elementwise through the oracle."""
+    return po.unorm_n(x, 65535.0).astype(np.uint16)
 
 
 class History:
@@ -115,14 +110,19 @@ class History:
             qy = np.floor(((sy + f32(1)) * f32(0.5)) * f32(H) + f32(0.5))
             in_frame = (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
         ok = hit & in_front & in_frame
-        qxi = np.where(ok, qx, 0).astype(np.int64)
-        qyi = np.where(ok, qy, 0).astype(np.int64)
-        same_face = ok & (self.nrm[qyi, qxi] == nrm) & (self.n[qyi, qxi] > 0)         # 5
+        # (pixels behind the previous camera whose mirrored projection lands in the frame go through steps 5 and 6 as well, for
+        # `mirror_match`: what a pass without step 3's test would accept.  Nothing of theirs reaches the result.)
+        cand = hit & in_frame
+        qxi = np.where(cand, qx, 0).astype(np.int64)
+        qyi = np.where(cand, qy, 0).astype(np.int64)
+        face = cand & (self.nrm[qyi, qxi] == nrm) & (self.n[qyi, qxi] > 0)            # 5
+        same_face = ok & face
         P1 = o1 + directions(self.cam, qxi, qyi, W, H) * (self.dep[qyi, qxi] / f32(32))[..., None]
         k = np.clip(nrm >> 1, 0, 2)[..., None]
         with np.errstate(all="ignore"):
             diff = np.abs(np.take_along_axis(P, k, 2)[..., 0] - np.take_along_axis(P1, k, 2)[..., 0])
         acc = same_face & (diff <= PLANE_TOLERANCE)
+        mirror_match = face & ~in_front & (diff <= PLANE_TOLERANCE)
         c = self.n[qyi, qxi]                                                         # 6
         sp = self.sum[qyi, qxi]
         with np.errstate(all="ignore"):
@@ -131,7 +131,7 @@ class History:
         s = np.where(acc[..., None], base, f32(0)).astype(f32) + L
         n = np.where(acc, np.minimum(c, cap) + 1, 1).astype(np.uint32)
         self.diag = dict(hit=hit, in_front=in_front, in_frame=in_frame, qx=qxi, qy=qyi, same_face=same_face, plane_diff=diff,
-                         accepted=acc)
+                         accepted=acc, prev_count=c, prev_sum=sp, mirror_match=mirror_match)
         return s, n, acc
 
 
@@ -147,3 +147,154 @@ def path_uniforms(k, step=None, base=TERRAIN_BASE, dx=0.25, dh=0.002, heading=np
     advances by one per FRAME (mod RT_NOISE_BYTES)."""
     j = k if step is None else step
     return po.camera_uniforms((base[0] + dx * j, base[1], base[2]), heading + dh * j, pitch, sun, (seed0 + k) % (512 * 512 * 4), lr)
+
+
+# ---- cameras and sequences that leave the gentle path (tests/test_reprojection_contract.py states on the CPU what each one
+# ---- exercises; tests/test_gpu_reprojection_edges.py walks the same frames on the GPU) -------------------------------------------
+NOISE_BYTES = 512 * 512 * 4
+SEQ_W, SEQ_H, SEQ_DEPTH = 72, 44, 2
+HD = np.pi / 2
+
+
+def cam(k, origin, heading, pitch, roll=0.0, zoom=1.0, fscale=1.0, right0=False, sun=0.3, lr=(0, 0, 0)):
+    """Uniforms of frame k (seed SEED0 + k mod RT_NOISE_BYTES): camera_uniforms' camera with right / up rolled by `roll` rad
+    about forward and scaled by `zoom`, forward scaled by `fscale` (all in float32), and right = 0 if `right0`.  The basis is no
+    longer orthonormal-times-0.4: forward need not be a unit vector, and right / up are not the axes of the screen."""
+    u = po.camera_uniforms(origin, heading, pitch, sun, (SEED0 + k) % NOISE_BYTES, lr)
+    f, r, up = (np.array(v[:], dtype=f32) for v in (u.forward, u.right, u.up))
+    c, s = f32(np.cos(roll)), f32(np.sin(roll))
+    r2 = (r * c + up * s) * f32(zoom)
+    up2 = (up * c - r * s) * f32(zoom)
+    f2 = f * f32(fscale)
+    if right0:
+        r2 = np.zeros(3, dtype=f32)
+    for a in range(3):
+        u.forward[a], u.right[a], u.up[a] = float(f2[a]), float(r2[a]), float(up2[a])
+    return u
+
+
+class Sequence:
+    def __init__(self, world, cap, uniforms, width=SEQ_W, height=SEQ_H):
+        self.world, self.cap, self.uniforms, self.width, self.height = world, int(cap), list(uniforms), int(width), int(height)
+
+
+SHAPES = ((1, 1), (7, 3), (9, 17), (333, 77))
+SEQUENCE_NAMES = ("turn", "mirror", "lens", "dolly", "cap1", "cap3", "cap3_edge", "cap_max", "degenerate", "arbitrary",
+                  "pyramid") + tuple(
+    "shape %dx%d" % s for s in SHAPES)
+_cache = {}
+
+
+def _noise_key(noise):
+    import zlib
+    return zlib.crc32(np.ascontiguousarray(noise, dtype=np.uint8))
+
+
+def _add(a, b):
+    return tuple(x + y for x, y in zip(a, b))
+
+
+def sequence_world(name):
+    """(materials, minefield) of a sequence's world, built once."""
+    key = ("world", name)
+    if key not in _cache:
+        from raytrace_amd import world
+        from tests import adversarial_worlds as aw
+        from tests import scenes
+        if name == "blocks":
+            _cache[key] = world.region_from_ids(scenes.random_blocks_ids())
+        elif name == "floor":
+            _cache[key] = world.region_from_ids(scenes.floor_ids())
+        elif name == "stairs":
+            _cache[key] = world.region_from_ids(scenes.staircase_ids())
+        elif name == "terrain":
+            _cache[key] = world.generate_region(world.DEFAULT_SEED)
+        elif name == "arbitrary":
+            _cache[key] = aw.arbitrary_world(256)[:2]
+        elif name == "pyramid":
+            _cache[key] = aw.pyramid_world(256)[:2]
+        else:
+            raise KeyError(name)
+    return _cache[key]
+
+
+def sequences():
+    """name -> Sequence, for every name of SEQUENCE_NAMES."""
+    if "sequences" in _cache:
+        return _cache["sequences"]
+    from tests import adversarial_worlds as aw
+    C0, O, S = (2.0, 3.0, 40.0), (0.0, -100.0, 40.0), (-60.0, -90.0, 30.0)
+    P4 = _add(C0, (9.0, 6.0, -4.0))
+    seq = {}
+    turn = [(C0, HD, -0.3), (C0, HD + np.pi, -0.3), (C0, HD + np.pi - 1.7, -0.3), (C0, HD + np.pi - 1.7, 0.9),
+            (P4, HD + np.pi - 2.0, -0.5), (P4, HD + np.pi + 0.2, -0.5), (_add(P4, (0.3, 0.0, 0.0)), HD + np.pi + 0.204, -0.5)]
+    seq["turn"] = Sequence("blocks", DEFAULT_CAP, [cam(k, o, h, p) for k, (o, h, p) in enumerate(turn)])
+    # mirror: frame 0 skims a floor (z = 0) from 0.1 above it, looking along +y and down by 0.004 rad; frame 1 looks back from behind
+    # and above at floor that lies behind camera 0.  Such a point's projection, mirrored through camera 0's centre, is a ray 0.1 / D rad
+    # ABOVE the horizon; the nearest pixel's ray (rows are 0.018 rad apart) is the one 0.004 rad BELOW it, which meets the same floor
+    # plane with the same normal 25 voxels ahead: only step 3's `a > 0` rejects these pixels.  Frames 2 and 3 move on gently.
+    seq["mirror"] = Sequence("floor", DEFAULT_CAP, [cam(0, (0.0, 0.0, 0.1), HD, -0.004), cam(1, (0.0, -10.0, 6.0), HD + np.pi, -0.2),
+                                                    cam(2, (0.3, -10.0, 6.0), HD + np.pi + 0.004, -0.2),
+                                                    cam(3, (0.0, 0.0, 0.1), HD, -0.004)])
+    last = dict(roll=-0.2, zoom=1.7, fscale=0.5)
+    lens = [dict(), dict(roll=0.3), dict(roll=0.3, zoom=0.6), dict(roll=0.3, zoom=0.6, fscale=2.0), last]
+    seq["lens"] = Sequence("blocks", DEFAULT_CAP, [cam(k, O, HD, -0.2, **kw) for k, kw in enumerate(lens)] +
+                           [cam(5, _add(O, (1.5, 3.0, -1.0)), HD + 0.05, -0.25, **last)])
+    seq["dolly"] = Sequence("stairs", DEFAULT_CAP, [cam(k, _add(S, (0.8 * d, 2.0 * d, 0.0)), HD - 0.4, -0.15)
+                                                    for k, d in enumerate((0, 1, 2, -3, -3, 5, 0))])
+    cap_steps = (0, 0, 0, 0, 0, 1, 2, 2, 3)
+    cap_poses = [cam(k, _add(O, (0.3 * s, 0.0, 0.0)), HD + 0.004 * s, -0.2) for k, s in enumerate(cap_steps)]
+    seq["cap1"] = Sequence("blocks", 1, cap_poses)
+    seq["cap3"] = Sequence("terrain", 3, [path_uniforms(k, step=s) for k, s in enumerate((0, 0, 0, 0, 0, 0, 1, 2, 3))])
+    # three frames at one pose, then moves: the first moved frame reads c == cap everywhere, later ones 3 beside 4, 2 and 1
+    seq["cap3_edge"] = Sequence("terrain", 3, [path_uniforms(k, step=s) for k, s in enumerate((0, 0, 0, 1, 2, 3, 4))])
+    seq["cap_max"] = Sequence("blocks", 65535, cap_poses)
+    seq["degenerate"] = Sequence("blocks", DEFAULT_CAP, [cam(0, O, HD, -0.2), cam(1, O, HD, -0.2, right0=True),
+                                                         cam(2, _add(O, (0.5, 0.0, 0.0)), HD, -0.2), cam(3, O, HD, -0.2)])
+    steps = (0, 1, 2, 2, 3, 10)
+
+    def stepped(poses):
+        return [cam(len(steps) * i + j, _add(p["origin"], (0.3 * s, 0.1 * s, 0.0)), p["heading"] + 0.004 * s, p["pitch"], sun=p["sun"])
+                for i, p in enumerate(poses) for j, s in enumerate(steps)]
+    seq["arbitrary"] = Sequence("arbitrary", 2, stepped([aw.POSES[0], aw.POSES[2]]))
+    seq["pyramid"] = Sequence("pyramid", 2, stepped([aw.PYRAMID_POSES[2]]))
+    for w, h in SHAPES:
+        seq["shape %dx%d" % (w, h)] = Sequence("blocks", DEFAULT_CAP, [cam(k, _add(O, (0.3 * s, 0.0, 0.0)), HD + 0.004 * s, -0.2)
+                                                                        for k, s in enumerate((0, 1, 1, 2, 3))], w, h)
+    assert tuple(seq) == SEQUENCE_NAMES
+    _cache["sequences"] = seq
+    return seq
+
+
+def sequence_frames(name, noise):
+    """The oracle's one-sample frames of a sequence (a list of plane dicts), rendered once and shared: read-only."""
+    key = ("frames", name, _noise_key(noise))
+    if key not in _cache:
+        q = sequences()[name]
+        mats, mine = sequence_world(q.world)
+        _cache[key] = [po.render(mats, mine, noise, u, q.width, q.height, 1, SEQ_DEPTH)[0] for u in q.uniforms]
+        for planes in _cache[key]:
+            for a in planes.values():
+                a.setflags(write=False)
+    return _cache[key]
+
+
+def sequence_expected(name, noise):
+    """What the contract asks of every frame of a sequence, computed once and shared (read-only): a list of dicts with
+    `planes` (the oracle's frame with the restatement's two lighting planes), `counts`, `accumulation` = (frames, samples), `mode`
+    and, on moved frames, `diag` plus `prev_counts` (the counts of the frame before)."""
+    key = ("expected", name, _noise_key(noise))
+    if key not in _cache:
+        q = sequences()[name]
+        h = History(q.width, q.height, q.cap)
+        out, prev = [], None
+        for u, planes in zip(q.uniforms, sequence_frames(name, noise)):
+            want = dict(planes)
+            want["lighting_f32"], want["lighting_rgba16"], counts, acc = h.step(planes, u)
+            for a in (want["lighting_f32"], want["lighting_rgba16"], counts, acc):
+                a.setflags(write=False)
+            out.append(dict(planes=want, counts=counts, accepted=acc, accumulation=(h.frames, h.samples), mode=h.mode,
+                            diag=dict(h.diag) if h.mode == "moved" else None, prev_counts=prev))
+            prev = counts
+        _cache[key] = out
+    return _cache[key]

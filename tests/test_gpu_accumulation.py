@@ -295,3 +295,43 @@ def test_accumulation_is_zero_before_the_first_frame(procedural_region, blue_noi
         inf = ctx.info()
     with _ctx(procedural_region, blue_noise, 2, flags=CACHE) as plain:
         assert inf.device_bytes - plain.info().device_bytes == ((W + 7) // 8) * ((H + 7) // 8) * 64 * 16
+
+
+# ---- a frame of more (padded) pixels than one trip of k_accumulate_frame's grid covers --------------------------------------------
+BIG_W, BIG_H, BIG_DEPTH = 1028, 1021, 2     # 129 x 128 tiles = 1,056,768 padded pixels; 4096 blocks of 256 lanes cover 1,048,576
+ONE_TRIP = 4096 * 256
+
+
+def _second_trip(width, height):
+    """[H, W] bool: the pixels whose padded tile-major index (what k_accumulate_frame strides over) is past the first trip."""
+    ys, xs = np.mgrid[0:height, 0:width]
+    return ((ys // 8) * ((width + 7) // 8) + xs // 8) * 64 >= ONE_TRIP
+
+
+@pytest.mark.parametrize("spp,K,pitch", [(1, 3, -0.8), (2, 2, -0.5)])
+@pytest.mark.parametrize("kernel", [abi.RT_KERNEL_DEFAULT, abi.RT_KERNEL_PATHS])
+def test_a_frame_of_more_pixels_than_one_trip_of_the_grid(procedural_region, blue_noise, kernel, spp, K, pitch):
+    """1028 x 1021: the pass runs its grid-stride loop twice for the last 128 tiles, the top five rows of the frame from x = 8 on.
+    A sky pixel there cannot tell a skipped trip from a correct one, because its light is the same in every sample: at the other
+    tests' pitch the whole tail is sky.  So the one-sample case looks down at pitch -0.8, where the tail is terrain whose light
+    differs from sample to sample (k_accumulate_frame takes every pixel).  The two-sample case uses pitch -0.5, where the tail holds
+    terrain and sky: k_accumulate_frame in its finished-pixel mode (the sky) and k_accumulate_paths<.., ACCUM> (the terrain) both
+    meet pixels past the first trip.  Both conditions are asserted on the oracle's frames before the comparison."""
+    tail = _second_trip(BIG_W, BIG_H)
+    assert tail.sum() == 5 * 1020 and tail[BIG_H - 1, BIG_W - 1] and not tail[BIG_H - 6].any()
+    u = _u(SEED0, pitch=pitch)
+    kw = dict(depth=BIG_DEPTH, W=BIG_W, H=BIG_H)
+    one = _oracle(procedural_region, blue_noise, u, 1, **kw)[0]
+    want = _oracle(procedural_region, blue_noise, u, K * spp, **kw)[0]
+    hit = one["normal_r8"][tail] < 6
+    differ = (one["lighting_f32"][tail] != want["lighting_f32"][tail]).any(axis=1)
+    print("tail: %d pixels, %d hit, %d differ between 1 and %d samples" % (tail.sum(), hit.sum(), differ.sum(), K * spp))
+    if spp == 1:
+        assert hit.sum() >= 0.9 * tail.sum() and differ.sum() >= 0.8 * tail.sum()
+    else:
+        assert 0.25 * tail.sum() <= hit.sum() <= 0.75 * tail.sum() and differ.sum() >= 0.8 * hit.sum()
+    with _ctx(procedural_region, blue_noise, spp, kernel, ACC | CACHE, **kw) as ctx:
+        _accumulate(ctx, spp, K, pitch=pitch)
+        ctx.sync()
+        got = ctx.readback_all()
+    _same(got, want, "after %d frames of %d" % (K, spp))

@@ -79,6 +79,31 @@ def test_store_conversions():
     assert po.f2u16(319.97) == 319 and po.f2u16(-3.0) == 0 and po.f2u16(1e9) == 65535 and po.f2u16(float("nan")) == 0
 
 
+def test_the_batched_calls_equal_the_scalar_ones():
+    """normalize_n / unorm_n (what tests/temporal_ref.py runs whole frames through) against normalize / unorm, element for
+    element as bit patterns: random vectors and values plus the zero vector (NaN), NaN and infinite components, subnormals, and
+    values below 0, above 1 and at the rounding ties of the UNORM conversion."""
+    rng = np.random.default_rng(3)
+    v = np.concatenate([rng.normal(0, 1, (500, 3)), rng.normal(0, 1e-20, (20, 3)), rng.normal(0, 1e18, (20, 3)), [
+        (0.0, 0.0, 0.0), (-0.0, 0.0, 0.0), (np.nan, 1.0, 0.0), (1.0, np.nan, np.nan), (np.inf, 1.0, 2.0), (-np.inf, np.inf, 0.0),
+        (1e-45, 0.0, 0.0), (3.0, 4.0, 0.0), (3e38, 3e38, 3e38)]]).astype(np.float32)
+    got = po.normalize_n(v)
+    assert got.shape == v.shape and got.dtype == np.float32
+    want = np.stack([po.normalize(r) for r in v])
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.isnan(got[540]).all() and np.isnan(got[542]).all()
+    assert np.array_equal(po.normalize_n(v[3:].reshape(6, 91, 3)[:, 80:]).view(np.uint32), want[3:].reshape(6, 91, 3)[:, 80:].view(np.uint32))
+    x = np.concatenate([rng.uniform(-0.5, 1.5, 2000), (np.arange(0, 400) + 0.5) / 65535.0, (np.arange(0, 255) + 0.5) / 255.0, [
+        0.0, -0.0, 1.0, -1e-30, -3.0, 1.0000001, 2.5, 1e30, -1e30, np.inf, -np.inf, np.nan, 1e-45, 1.0 / 16.0]]).astype(np.float32)
+    for maxv in (65535.0, 255.0):
+        got = po.unorm_n(x, maxv)
+        assert got.shape == x.shape and got.dtype == np.uint32
+        assert np.array_equal(got, np.array([po.unorm(e, maxv) for e in x], dtype=np.uint32))
+        assert got.min() == 0 and got.max() == int(maxv)
+    assert po.unorm_n(x[-21:].reshape(7, 3), 255.0).shape == (7, 3)
+    assert po.normalize_n(np.zeros((0, 3), dtype=np.float32)).shape == (0, 3) and po.unorm_n(np.zeros(0), 255.0).size == 0
+
+
 def test_noise_value_texel_is_level_independent():
     """Q5: the per-level noise offset (level-1) * 2/512 never reaches the next texel, and noise_offset is an exact
     integer in float, so floor(mod(offset + add, 512)) == int(offset) & 511 for every level — the path kernel fetches the
