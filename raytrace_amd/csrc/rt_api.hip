@@ -29,6 +29,7 @@ const size_t kBytesPerPixel[RT_BUF_COUNT] = {8, 2, 1, 4, 4, 4, 16, 16, 4, 4};
 
 }  // namespace
 
+constexpr size_t kWlSetWords = 64, kWlClearWords = 33;   // FrameSlot::wl_count: words of one set, and those of it that are in use
 constexpr size_t kCursorWords = 8 * 32;   // path cursors of the persistent kernels: one word per XCD group, each on its own 128-byte line
 // light records of one launch above which k_paths streams them out and k_accumulate_paths streams them in (see draw_path_batches)
 constexpr uint64_t kStreamRecordBytes = 384ull << 20;
@@ -89,9 +90,14 @@ struct FrameSlot {
     uint32_t* worklist = nullptr;
     float4* phit = nullptr;            // primary-hit records of the worklist (rtd::PrimaryArgs::phit)
     float4* pacc = nullptr;
-    uint32_t* wl_count = nullptr;      // two words on lines of their own: the frame in the slot counts in [wl_parity] while its prepass clears the other
-    int wl_parity = 0;
+    uint32_t* wl_count = nullptr;      // two sets of kWlSetWords: worklist counter (word 0) and the prepass' tile cursor (word 32), on lines of
+                                       // their own; the frame in the slot uses set [wl_parity] while its prepass clears the other
+    int wl_parity = 0;                 // the set the slot's NEXT prepass uses (the prepass that ran last used the other)
     bool wl_clean[2] = {false, false};
+    // the slot holds the prepass of a frame drawn under prepass_key (worklist, count, primary hits, the primary-only planes, finished sky
+    // lighting) and nothing has changed what that prepass read or wrote since: a frame with the same key may skip its prepass
+    bool prepass_valid = false;
+    uint32_t prepass_key[16] = {};
     void* denoise_work[2] = {nullptr, nullptr};   // ping/pong working planes of the denoise passes (16 B/pixel), allocated on first use
     hipEvent_t ev_prepass = nullptr;   // the frame's prepass and tables are done (launches on the other lane wait for it)
     hipEvent_t ev_acc = nullptr;       // the frame's most recent accumulate launch (the next one adds to the same sums, in sample order)
@@ -209,6 +215,7 @@ struct RtContext {
     // shared by the frame slots; what it holds is host-side state
     float4* d_accum = nullptr;
     bool accum_valid = false;           // the next frame may continue the sum (a frame was drawn and nothing reset it since)
+    bool prepass_reuse = true;          // RT_PREPASS_REUSE=0: every frame runs its prepass (FrameSlot::prepass_valid)
     uint32_t accum_key[16] = {};        // live uniforms other than seed of the frame drawn last (bit patterns)
     uint64_t accum_frames = 0, accum_samples = 0;   // frames and samples the planes of the frame drawn last hold
     bool drawn = false;                 // a frame was drawn (rt_get_accumulation of a context without the flag)
@@ -544,7 +551,8 @@ struct PersistFrame {
     Lane* L0 = nullptr;                 // the lane of the prepass and the first launch ...
     hipStream_t st0 = nullptr;          // ... and its stream
     hipStream_t tail = nullptr;         // the stream the frame ends on
-    uint32_t* wlc = nullptr;            // the frame's worklist counter (the slot has two: the other is its next frame's)
+    uint32_t* wlc = nullptr;            // the frame's worklist counter (the slot has two: the other is its next prepass')
+    bool reuse = false;                 // the slot's prepass is this frame's too: no prepass launch
     // RT_FLAG_ACCUMULATE
     bool accum = false, accum_cont = false;   // the context accumulates; this frame continues the running sum
     uint32_t key[16] = {};
@@ -552,6 +560,23 @@ struct PersistFrame {
     float4* accum_multi = nullptr;      // d_accum for frames of more than one sample
     int temporal_mode = rtd::TEMPORAL_RESTART;   // RT_FLAG_REPROJECT: how this frame's pass treats the history
 };
+
+// Something the prepasses read or wrote has changed (the world, the stream, a plane, a failed frame): no slot's is reused.
+void invalidate_prepass(RtContext* c) {
+    for (FrameSlot& fs : c->slots) fs.prepass_valid = false;
+}
+
+// A library call writes device memory the caller names (a post pass in place, an untiled frame): if that lies in a plane of a frame
+// slot, the slot's prepass results are no longer what its planes hold (rt_denoise rewrites the sky pixels' lighting in place).
+void plane_written(RtContext* c, const void* ptr) {
+    const uint8_t* q = static_cast<const uint8_t*>(ptr);
+    for (int sl = 0; sl < c->nslots; sl++)
+        for (int b = 0; b < RT_BUF_COUNT; b++) {
+            if (b == RT_BUF_FINAL_BGRA8) continue;   // (rt_finalize's output: no prepass result)
+            const uint8_t* base = static_cast<const uint8_t*>(c->slots[sl].planes[b]);
+            if (base && q >= base && q < base + c->plane_pixels * kBytesPerPixel[b]) c->slots[sl].prepass_valid = false;
+        }
+}
 
 // the step that touches the running sum follows the previous frame's (ev_accum), not the whole previous frame
 hipError_t accum_wait(RtContext* c, hipStream_t st) {
@@ -577,15 +602,26 @@ hipError_t frame_begin(RtContext* c, PersistFrame& p, const RtUniforms* u, bool 
     p.one_lane = p.nsl == 1 && (uint32_t)c->cfg.spp <= c->persist_batch;
     p.L0 = &c->lanes[p.one_lane ? 0u : c->path_launches % (uint64_t)p.nl];
     p.st0 = p.tail = p.L0->stream;
-    // worklist counter of this frame: clean already if the slot's previous frame's prepass cleared it, otherwise cleared there
-    p.wlc = p.fs->wl_count + 32 * p.fs->wl_parity;
+    accum_key_of(u, p.key);
+    // The primary ray reads no noise, so what the prepass leaves in the slot depends on every live uniform but the seed (the
+    // accumulation key), the context's configuration and the world.  A frame whose slot still holds the prepass of that key skips
+    // its own: a still camera over an unchanged world re-traces nothing.  Not where the prepass does more than that: counters
+    // (they count the prepass' rays), a running sum or history (the prepass then runs as a one-sample frame and k_accumulate_frame /
+    // the temporal pass rewrite the lighting it finished).  Everything else a later launch of the frame writes, it writes again
+    // in every frame (the lighting of worklist pixels: the last accumulate launch, or the path launch itself on the direct
+    // route; the per-pixel sums of a multi-batch frame start from 0 in its first batch).
+    p.reuse = c->prepass_reuse && p.cache && !c->route.frame && !p.count && c->d_accum == nullptr && !c->reproject &&
+              (c->cfg.flags & (RT_FLAG_ACCUMULATE | RT_FLAG_REPROJECT)) == 0 && p.fs->prepass_valid &&
+              memcmp(p.key, p.fs->prepass_key, sizeof(p.key)) == 0;
+    // worklist counter of this frame: clean already if the slot's previous prepass cleared it, otherwise cleared there; a reusing
+    // frame reads the one its slot's last prepass counted in (no flip, no clear)
+    p.wlc = p.fs->wl_count + kWlSetWords * (size_t)(p.fs->wl_parity ^ (p.reuse ? 1 : 0));
     // RT_FLAG_ACCUMULATE: does this frame continue the running sum, and how many samples will it hold (the lighting's divisor)?
     // One-sample frames add theirs in k_accumulate_frame after the frame's launches.  Frames of more samples continue the ordered
     // sum from the running one: k_accumulate_frame for the pixels the prepass finishes, k_accumulate_paths<.., ACCUM> for the
     // paths' (its first batch starts from the running sum, its last stores it back).
     const uint32_t spp = (uint32_t)c->cfg.spp;
     p.accum = c->d_accum != nullptr;
-    accum_key_of(u, p.key);
     p.accum_cont = p.accum && c->accum_valid && memcmp(p.key, c->accum_key, sizeof(p.key)) == 0 && c->accum_samples + spp <= (1ull << 24);
     p.accum_n = p.accum_cont ? c->accum_samples + spp : spp;
     p.accum_multi = p.accum && spp > 1u ? c->d_accum : nullptr;
@@ -613,16 +649,19 @@ hipError_t frame_prepass(RtContext* c, PersistFrame& p) {
     FrameSlot& fs = *p.fs;
     const bool prepass_clears = c->primary_version == 2 && c->npix_pad != 0;
     hipError_t e = hipSuccess;
-    if (!fs.wl_clean[fs.wl_parity]) e = hipMemsetAsync(p.wlc, 0, sizeof(uint32_t), p.st0);
+    fs.prepass_valid = false;   // (until this one is enqueued: it overwrites the worklist)
+    if (!fs.wl_clean[fs.wl_parity]) e = hipMemsetAsync(p.wlc, 0, kWlClearWords * sizeof(uint32_t), p.st0);
     fs.wl_clean[fs.wl_parity] = false;
     LaunchTimer t(c, 1, p.st0);
     rtd::PrimaryArgs pr{};
     pr.phit = fs.phit;
-    pr.worklist = fs.worklist; pr.wl_count = p.wlc; pr.acc = fs.pacc; pr.counters = c->d_counters;
+    pr.worklist = fs.worklist; pr.wl_count = p.wlc; pr.tile_cursor = p.wlc + 32; pr.acc = fs.pacc; pr.counters = c->d_counters;
     // the prepass clears what the NEXT users need zeroed instead of a memset of its own in front of them: the slot's other
-    // worklist counter (the slot's next frame) and the path cursors of the lane it runs on (this frame's first launch)
-    pr.zero_words = prepass_clears ? fs.wl_count + 32 * (fs.wl_parity ^ 1) : nullptr; pr.zero_count = 1u;
-    pr.zero_words2 = prepass_clears ? p.L0->cursor : nullptr; pr.zero_count2 = (uint32_t)kCursorWords;
+    // worklist counter and tile cursor (the slot's next prepass) and, unless the lane's last accumulate launch has done it, the
+    // path cursors of the lane it runs on (this frame's first launch)
+    const bool clear_cursors = prepass_clears && !p.L0->cursor_clean;
+    pr.zero_words = prepass_clears ? fs.wl_count + kWlSetWords * (size_t)(fs.wl_parity ^ 1) : nullptr; pr.zero_count = (uint32_t)kWlClearWords;
+    pr.zero_words2 = clear_cursors ? p.L0->cursor : nullptr; pr.zero_count2 = (uint32_t)kCursorWords;
     // accumulating: the prepass runs as a one-sample frame, so the light of a pixel it finishes is 16 x its lighting_f32 exactly;
     // k_accumulate_frame then adds it spp times to the pixel's running sum (the prepass adds it spp times to 0 otherwise)
     rtd::Frame fpre = p.f;
@@ -633,6 +672,7 @@ hipError_t frame_prepass(RtContext* c, PersistFrame& p) {
         e = rtd::launch_accumulate_frame(p.f, p.pl, c->d_accum, c->npix_pad, p.accum_cont, (int)p.accum_n, c->cfg.spp, true, p.st0);
     if (prepass_clears && e == hipSuccess) { fs.wl_clean[fs.wl_parity ^ 1] = true; p.L0->cursor_clean = true; }
     fs.wl_parity ^= 1;
+    if (e == hipSuccess) { fs.prepass_valid = true; memcpy(fs.prepass_key, p.key, sizeof(p.key)); }
     return e;
 }
 
@@ -713,7 +753,10 @@ hipError_t frame_path_batches(RtContext* c, PersistFrame& p) {
                 LaunchTimer t(c, 1, st);
                 if (e == hipSuccess)
                     e = rtd::launch_accumulate_paths(p.f, p.pl, L->ppl, fs.worklist, p.wlc, c->npix_pad, ns, s0 == 0, s0 + B >= spp, p.cache,
-                                                     stream_ld, fs.pacc, p.accum_multi, p.accum_cont, (int)p.accum_n, st);
+                                                     stream_ld, fs.pacc, p.accum_multi, p.accum_cont, (int)p.accum_n, L->cursor,
+                                                     (uint32_t)kCursorWords, st);
+                // (it has cleared the lane's path cursors behind the path launch: the lane's next one needs no memset)
+                if (e == hipSuccess && c->npix_pad != 0) L->cursor_clean = true;
             }
             if (e == hipSuccess && p.nl == 2 && s0 + B < spp) e = hipEventRecord(fs.ev_acc, st);
         }
@@ -754,6 +797,7 @@ hipError_t frame_accumulate_tail(RtContext* c, PersistFrame& p) {
 
 // The frame ends on `tail`: post passes, gather and readback of THIS frame follow it there; its planes are the context's.
 void frame_publish(RtContext* c, const PersistFrame& p, hipError_t e) {
+    if (e != hipSuccess) invalidate_prepass(c);
     if (p.accum) {
         c->accum_valid = e == hipSuccess;
         c->accum_frames = p.accum_cont ? c->accum_frames + 1u : 1u;
@@ -770,7 +814,7 @@ void frame_publish(RtContext* c, const PersistFrame& p, hipError_t e) {
 int draw_persistent(RtContext* c, const rtd::Frame& f, const RtUniforms* u, bool frame_events) {
     PersistFrame p{f};
     hipError_t e = frame_begin(c, p, u, frame_events);
-    if (e == hipSuccess && p.cache && !c->route.frame) e = frame_prepass(c, p);
+    if (e == hipSuccess && p.cache && !c->route.frame && !p.reuse) e = frame_prepass(c, p);
     if (e == hipSuccess) e = frame_tables(c, p);
     if (e == hipSuccess && c->route.frame) e = frame_one_launch(c, p);
     else if (e == hipSuccess && (!p.cache || c->cfg.depth >= 1)) e = frame_path_batches(c, p);   // (cached depth 0: the prepass is the frame)
@@ -884,8 +928,8 @@ int create_persistent(RtContext* c) {
     }
     for (int sl = 0; sl < c->nslots; sl++) {
         FrameSlot& fs = c->slots[sl];
-        RT_HIP(c, dev_alloc(c, &fs.wl_count, (size_t)64));   // two counters, 128 bytes apart
-        RT_HIP(c, hipMemset(fs.wl_count, 0, 64 * sizeof(uint32_t)));
+        RT_HIP(c, dev_alloc(c, &fs.wl_count, 2 * kWlSetWords));   // two sets: counter and tile cursor, 128 bytes apart
+        RT_HIP(c, hipMemset(fs.wl_count, 0, 2 * kWlSetWords * sizeof(uint32_t)));
         fs.wl_clean[0] = fs.wl_clean[1] = true;
         RT_HIP(c, dev_alloc(c, &fs.worklist, (size_t)c->npix_pad));
         RT_HIP(c, dev_alloc(c, &fs.phit, (size_t)c->npix_pad));
@@ -1035,6 +1079,7 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
     if (const char* s = getenv("RT_FRAME_TILES")) { int v = atoi(s); if (v >= 1 && v <= 4) c->frame_tiles = 4u * (uint32_t)v; }           // per wave
     if (const char* s = getenv("RT_FRAME_GROUP_TILES")) { int v = atoi(s); if (v >= 1 && v <= 16) c->frame_tiles = (uint32_t)v; }     // per four-wave workgroup
     if (const char* s = getenv("RT_REFILL_THRESHOLD")) { int v = atoi(s); if (v >= 1 && v <= 64) c->refill_threshold = (uint32_t)v; }
+    if (const char* s = getenv("RT_PREPASS_REUSE")) { if (atoi(s) == 0) c->prepass_reuse = false; }
     if (const char* s = getenv("RT_PRIMARY_V")) { int v = atoi(s); if (v == 1 || v == 2) c->primary_version = v; }
     if (const char* s = getenv("RT_PERSIST_THRESHOLD")) { int v = atoi(s); if (v >= 1 && v <= 64) c->persist_threshold = (uint32_t)v; }
     if (const char* s = getenv("RT_PL_STREAM")) { int v = atoi(s); if (v >= 0 && v <= 3) c->pl_stream_mode = v; }
@@ -1097,6 +1142,7 @@ int rt_set_stream(RtContext* ctx, void* hip_stream) {
     ctx->lanes[0].stream = ctx->stream;
     ctx->user_stream = hip_stream != nullptr;
     ctx->accum_recorded = false;   // (everything before has finished)
+    invalidate_prepass(ctx);       // (lanes and slots in use change with the stream)
     return RT_OK;
 }
 
@@ -1104,6 +1150,7 @@ int rt_upload_world(RtContext* ctx, const uint32_t* materials, const uint8_t* mi
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_world: null pointer");
     ctx->accum_valid = false;
+    invalidate_prepass(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, sync_lanes(ctx));
     // the caller-layout copy lives for the duration of this call only (it used to stay resident — 160 MiB at
@@ -1147,6 +1194,7 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: null pointer");
     ctx->accum_valid = false;
+    invalidate_prepass(ctx);
     const size_t kR = (size_t)ctx->region;
     if (axis < 0 || axis > 2 || texel_offset < 0 || texel_offset + RT_SLICE_SIZE > ctx->region || texel_offset % RT_SLICE_SIZE != 0)
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: bad axis or offset");
@@ -1201,6 +1249,7 @@ int generate_terrain(RtContext* c, uint64_t seed, const int64_t lo[3], int axis)
         RT_HIP(c, dev_alloc(c, &c->d_heights, cols));
     }
     c->accum_valid = false;
+    invalidate_prepass(c);
     RT_HIP(c, world_change_begin(c));
     {
         LaunchTimer t(c, 1);
@@ -1308,6 +1357,7 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
     // later frames after the rebuild — the ordering of rt_upload_slice.
     ctx->edit_batches++;
     ctx->accum_valid = false;
+    invalidate_prepass(ctx);
     RT_HIP(ctx, staging_send(ctx, s, off_recs + (size_t)nrec * 8u));
     const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
     const uint32_t* d_offs = reinterpret_cast<const uint32_t*>(s.dev + off_offs);
@@ -1471,6 +1521,7 @@ int rt_upload_noise(RtContext* ctx, const uint8_t* rgba8) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!rgba8) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_noise: null pointer");
     ctx->accum_valid = false;
+    invalidate_prepass(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, sync_lanes(ctx));
     RT_HIP(ctx, hipMemcpy(ctx->d_noise, rgba8, RT_NOISE_BYTES, hipMemcpyHostToDevice));
@@ -1570,6 +1621,7 @@ int rt_untile(RtContext* ctx, int id, const void* gathered_dev, int world, void*
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (id < 0 || id >= RT_BUF_COUNT || !gathered_dev || !frame_dev || world < 1)
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_untile: bad argument");
+    plane_written(ctx, frame_dev);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const int capacity = (ctx->ntiles_total + world - 1) / world;
     RT_HIP(ctx, rtd::launch_untile(gathered_dev, frame_dev, world, capacity, ctx->tiles_x, ctx->tiles_y, ctx->cfg.width,
@@ -1580,6 +1632,7 @@ int rt_untile(RtContext* ctx, int id, const void* gathered_dev, int world, void*
 int rt_denoise_planes(RtContext* ctx, void* lighting, const void* depth, const void* normal, int faithful) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!lighting || !depth || !normal) return fail(ctx, RT_ERR_INVALID_ARG, "rt_denoise_planes: null plane");
+    plane_written(ctx, lighting);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const int sizes[6] = {1, 2, 4, 8, 8, 16};                         // pipeline.rs:103
     const int W = ctx->cfg.width, H = ctx->cfg.height;
@@ -1606,6 +1659,7 @@ int rt_finalize_planes(RtContext* ctx, const void* albedo, const void* emission,
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!albedo || !emission || !fog || !lighting || !depth || !out_bgra8) return fail(ctx, RT_ERR_INVALID_ARG, "rt_finalize_planes: null plane");
     if (!ctx->has_noise) return fail(ctx, RT_ERR_NOT_READY, "rt_finalize_planes: noise must be uploaded first");
+    plane_written(ctx, out_bgra8);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     LaunchTimer t(ctx, 1);
     RT_HIP(ctx, rtd::launch_finalize(albedo, emission, fog, lighting, depth, ctx->d_noise, ctx->cfg.width, ctx->cfg.height, out_bgra8,

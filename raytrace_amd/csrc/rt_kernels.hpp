@@ -52,8 +52,9 @@ struct PrimaryArgs {
                                 // face id << 28 | gl_WorkGroupID.y * 8 << 14 | gl_WorkGroupID.x * 8 (the noise_offset terms, raytrace.comp:304)
     uint32_t* worklist;         // local pixel ids that need shadow/diffuse rays
     uint32_t* wl_count;         // zero before launch
+    uint32_t* tile_cursor;      // k_primary2: next tile to hand out (a workgroup takes 16 at a time); zero before launch
     uint32_t* zero_words;       // k_primary2: words the prepass clears for later launches instead of a memset of their own: the slot's other
-    uint32_t zero_count;        // worklist counter (the slot's next frame) ...
+    uint32_t zero_count;        // worklist counter and tile cursor (the slot's next prepass) ...
     uint32_t* zero_words2;      // ... and the path cursors of the lane this frame's first path launch runs on; either may be null
     uint32_t zero_count2;
     float4* acc;                // (unused by the prepass since it stores the lighting of the pixels it finishes itself)
@@ -100,8 +101,9 @@ hipError_t launch_frame(const Scene& sc, const Frame& f, const Planes& pl, Frame
 hipError_t launch_accumulate_paths(const Frame& f, const Planes& planes, const PathLight* pl, const uint32_t* worklist,
                                    const uint32_t* wl_count, uint32_t npix_pad, uint32_t nsamples, bool first_batch, bool last_batch,
                                    bool cache, bool stream, float4* acc, float4* accum, bool accum_continue, int accum_div,
-                                   hipStream_t st);
-// (accum: RT_FLAG_ACCUMULATE's running sums by out_index, null without; see k_accumulate_paths)
+                                   uint32_t* zero_words, uint32_t zero_count, hipStream_t st);
+// (accum: RT_FLAG_ACCUMULATE's running sums by out_index, null without; zero_words: the lane's path cursors, cleared for its next
+// path launch, or null; see k_accumulate_paths)
 // RT_FLAG_ACCUMULATE: accum[out] = (accum_continue ? accum[out] : 0) + reps x (16 x lighting_f32[out], a one-sample light, exactly),
 // and the two lighting planes become that sum / n / 16 — for every pixel (one-sample frames, after the frame's launches) or only
 // for the pixels a one-sample prepass finished (finished_only: sky pixels, or all of them at depth 0)

@@ -2,8 +2,9 @@
 // (k_persist).  The default path kernel of big launches is k_paths (rt_paths.hip); k_persist runs the small ones,
 // frames with lr != 0 and frames without the primary cache.
 //
-//   k_primary2 : primary prepass.  One 1024-thread workgroup per CU, nibble map of the scene in LDS; a wave walks whole
-//                8x8 tiles (lane = pixel, so the wave's rays are coherent): primary ray, the five primary-only G-buffer
+//   k_primary2 : primary prepass.  One 1024-thread workgroup per CU, nibble map of the scene in LDS; a workgroup takes chunks
+//                of 16 consecutive 8x8 tiles from a cursor in global memory until none are left, a wave walks one tile of the
+//                chunk (lane = pixel, so the wave's rays are coherent): primary ray, the five primary-only G-buffer
 //                planes, finished lighting for sky pixels, and a __ballot-compacted worklist of the pixels that still
 //                need shadow/diffuse rays together with their primary hits (SoA in HBM).  (k_primary: the same with
 //                one thread per pixel over the byte array, RT_PRIMARY_V=1.)
@@ -140,6 +141,7 @@ __global__ __launch_bounds__(1024) void k_primary2(Scene sc, Frame f, Planes pl,
     __shared__ uint32_t s_coarse[kCoarseWords];
     __shared__ uint32_t s_swz[dda_uses_swz<LOGR, LRZ>() ? 3 * kSwzStride : 1];
     __shared__ uint32_t s_cnt[16], s_off[17];   // worklist append: pixels queued by each wave this round, their slot offsets
+    __shared__ uint32_t s_chunk;                // first tile of the workgroup's current chunk of 16 (one per wave)
     // what later launches need zeroed — the frame slot's other worklist counter (the slot's next frame) and the path cursors of
     // the lane this frame's first path launch runs on (idle until then) — is cleared here instead of by memsets of their own in
     // front of every frame (two fill kernels, 9 us of a 230 us frame at 1024^2)
@@ -152,20 +154,24 @@ __global__ __launch_bounds__(1024) void k_primary2(Scene sc, Frame f, Planes pl,
         uint4* dst = reinterpret_cast<uint4*>(s_coarse);
         for (uint32_t i = threadIdx.x; i < kCoarseWords / 4; i += 1024u) dst[i] = src[i];
         if (dda_uses_swz<LOGR, LRZ>()) dda_fill_swz(s_swz, threadIdx.x, 1024u);
+        if (threadIdx.x == 0) s_chunk = atomicAdd(a.tile_cursor, 16u);
     }
     __syncthreads();
     const uint8_t* s_nib = reinterpret_cast<const uint8_t*>(s_coarse);
     constexpr int R = 1 << LOGR, LB = LOGR - 2;
     const float half = (float)R / 2;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (blockIdx.x * 1024u + threadIdx.x) >> 6, nwaves = gridDim.x * 16u;
+    const uint32_t wiw = threadIdx.x >> 6;
     unsigned long long c_prim = 0, c_pix = 0, c_border = 0;
     RayTally tl;
-    // All waves of the workgroup run the same number of rounds (the append below has two barriers per round); a wave whose
-    // tile index is past the end carries no pixels in that round.
-    const uint32_t nrounds = ((uint32_t)f.ntiles_local + nwaves - 1u) / nwaves;
-    for (uint32_t round = 0; round < nrounds; round++) {
-        const uint32_t tile = round * nwaves + wave;
+    // The tiles are handed out dynamically: a chunk of 16 consecutive tiles per workgroup and round, ONE atomicAdd on the frame's
+    // tile cursor by one thread, broadcast through LDS.  A workgroup that starts late (on a CU the previous frame's draining path
+    // launch has just left) finds less work left, or none, so the kernel ends when the tiles do and not when the workgroup that
+    // started last has walked a fixed share; no workgroup ever waits for another.  Chunks taken in time order keep the worklist
+    // close to tile order.  All waves of the workgroup leave the loop in the same round (the append below has two barriers per
+    // round); a wave whose tile index is past the end carries no pixels in that round.
+    for (uint32_t chunk = s_chunk; chunk < (uint32_t)f.ntiles_local; chunk = s_chunk) {
+        const uint32_t tile = chunk + wiw;
         const uint32_t lp = tile * 64u + lane;
         PixelId pix = pixel_of_local(f, lp);
         if (tile >= (uint32_t)f.ntiles_local) pix.inside = false;
@@ -217,11 +223,13 @@ __global__ __launch_bounds__(1024) void k_primary2(Scene sc, Frame f, Planes pl,
         }
         // worklist append: ONE atomic per workgroup and round (a single counter word saturates near 90 returning atomics
         // per microsecond — one per wave made the append, not the tracing, the bound of this kernel), slots ballot-ranked
+        // (the same thread takes the workgroup's next chunk here: every wave has read s_chunk before the first barrier and reads
+        // the new one after the second)
         const uint64_t m = __ballot(queue);
-        const uint32_t wiw = threadIdx.x >> 6;
         if (lane == 0) s_cnt[wiw] = (uint32_t)__popcll(m);
         __syncthreads();
         if (threadIdx.x == 0) {
+            s_chunk = atomicAdd(a.tile_cursor, 16u);
             uint32_t total = 0;
             for (uint32_t i = 0; i < 16u; i++) { s_off[i] = total; total += s_cnt[i]; }
             const uint32_t base = total ? atomicAdd(a.wl_count, total) : 0u;
@@ -601,7 +609,12 @@ __global__ __launch_bounds__(256) void k_accumulate_paths(Frame f, Planes planes
                                                           const uint32_t* __restrict__ worklist,
                                                           const uint32_t* __restrict__ wl_count, uint32_t npix_pad,
                                                           uint32_t nsamples, int first_batch, int last_batch, float4* __restrict__ acc,
-                                                          float4* __restrict__ accum, int accum_continue, int accum_div) {
+                                                          float4* __restrict__ accum, int accum_continue, int accum_div,
+                                                          uint32_t* __restrict__ zero_words, uint32_t zero_count) {
+    // the path cursors of the lane this launch runs on, which the path launch in front of it has finished with: cleared here for
+    // the lane's next path launch, so that no memset stands in front of that one (a frame that reuses its slot's prepass has no
+    // prepass to do it)
+    if (blockIdx.x == 0u && zero_words != nullptr) for (uint32_t i = threadIdx.x; i < zero_count; i += 256u) zero_words[i] = 0u;
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
     const uint32_t nwork = CACHE ? *wl_count : npix_pad;
     if (w >= nwork) return;
@@ -668,11 +681,11 @@ hipError_t launch_accumulate_frame(const Frame& f, const Planes& planes, float4*
 hipError_t launch_accumulate_paths(const Frame& f, const Planes& planes, const PathLight* pl, const uint32_t* worklist,
                                    const uint32_t* wl_count, uint32_t npix_pad, uint32_t nsamples, bool first_batch, bool last_batch,
                                    bool cache, bool stream, float4* acc, float4* accum, bool accum_continue, int accum_div,
-                                   hipStream_t st) {
+                                   uint32_t* zero_words, uint32_t zero_count, hipStream_t st) {
     if (npix_pad == 0) return hipSuccess;
     dim3 grid((npix_pad + 255u) / 256u), block(256);
 #define RT_LAUNCH_ACC(C, S, A) hipLaunchKernelGGL((k_accumulate_paths<C, S, A>), grid, block, 0, st, f, planes, pl, worklist, wl_count, npix_pad, nsamples, first_batch ? 1 : 0, last_batch ? 1 : 0, acc, \
-                                                  accum, accum_continue ? 1 : 0, accum_div)
+                                                  accum, accum_continue ? 1 : 0, accum_div, zero_words, zero_count)
     if (accum != nullptr) {
         if (cache) { if (stream) RT_LAUNCH_ACC(true, true, true); else RT_LAUNCH_ACC(true, false, true); }
         else { if (stream) RT_LAUNCH_ACC(false, true, true); else RT_LAUNCH_ACC(false, false, true); }

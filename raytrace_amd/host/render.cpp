@@ -116,7 +116,7 @@ static bool invert3(const float c0[3], const float c1[3], const float c2[3], flo
 }
 
 int Pipeline::draw_frame(game::Game& game) {
-    int rc = rt_sync(ctx_);                                          // pipeline.rs:162-172
+    int rc = no_fence_ ? RT_OK : rt_sync(ctx_);                      // pipeline.rs:162-172
     if (rc != RT_OK) return rc;
     const Camera& camera = game.borrow_camera();
     if (tum_) {                                                      // pipeline.rs:174-189

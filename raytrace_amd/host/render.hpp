@@ -90,6 +90,9 @@ class Pipeline {
     // Off by default (the G-buffer planes are then the ray-trace dispatch's own output, which the parity tests compare);
     // whole-frame contexts only (RT_ERR_UNIMPLEMENTED on a tile-split one: the passes need a halo, gather first).
     int enable_post_passes(bool faithful);
+    // A context created with RT_FLAG_FRAMES_IN_FLIGHT_2: draw_frame no longer waits for the previous frame (the library orders a frame
+    // after the one that used its slot before), so frame k + 1 is enqueued while frame k runs.  Off by default (the reference's fence).
+    void set_frames_in_flight(int n) { no_fence_ = n == 2; }
     // The block under a pixel of the frame drawn last (its uniforms, the `lr` terrain streaming moved included): rt_pick_pixels on
     // pixel (x, height - 1 - y_from_top), the texel in front of the face it crossed (where a placed block goes) and the hit texel's
     // world coordinate in the lr window.  A game breaks the block with rt_edit_voxels on `hit.texel`, places one on `adjacent`.
@@ -112,6 +115,7 @@ class Pipeline {
     int tile_world_ = 1;
     int height_ = 0;                   // frame height (Pipeline::pick counts rows from the top)
     bool post_ = false, post_faithful_ = true;
+    bool no_fence_ = false;            // set_frames_in_flight(2)
     std::unique_ptr<TerrainUploadManager> tum_;
     std::unique_ptr<world::ChunkStorage> chunks_;
     bool stream_on_device_ = false;

@@ -6,7 +6,7 @@
 //
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
 //            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
-//            [--reproject] [--camera-step DX] [--edits N [--edit-spread]] [--rays N [--rays-coherent]]
+//            [--reproject] [--camera-step DX] [--frames-in-flight N] [--edits N [--edit-spread]] [--rays N [--rays-coherent]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -23,6 +23,10 @@
 // frames on one device).  --camera-step DX: before every frame after the first, DX is added to the camera's origin.x and DX / 100 rad
 // to its heading, so that every frame is a moved one; with --accumulate alone the accumulation then restarts every frame, which is
 // the baseline --reproject is measured against.
+//
+// --frames-in-flight 2 (one device): the context gets RT_FLAG_FRAMES_IN_FLIGHT_2 and the mirror's draw_frame does not wait for the
+// previous frame (Pipeline::set_frames_in_flight), so frame k + 1 is enqueued while frame k runs, as bench.py does by default; with
+// --camera-step every frame then runs its own prepass (a still camera's frames reuse their slot's).
 //
 // --edits N: before every frame, rt_edit_voxels places or breaks (alternating from frame to frame) N voxels of a deterministic brush
 // near the camera — a cube of voxels centred 16 texels ahead of it — or, with --edit-spread, N voxels dealt round every 64^3 chunk
@@ -202,6 +206,7 @@ int main(int argc, char** argv) {
     bool rays_coherent = false;
     bool reproject = false;
     float camera_step = 0.0f;
+    int frames_in_flight = 1;      // 2: RT_FLAG_FRAMES_IN_FLIGHT_2 and no fence between frames (bench.py's default), one device
     std::string noise_path = "tests/golden/blue_noise_512.rgba";
     std::vector<const char*> positional = {argv[0]};
     for (int i = 1; i < argc; i++) {
@@ -220,6 +225,7 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--accumulate") == 0) accumulate = true;
         else if (std::strcmp(argv[i], "--reproject") == 0) reproject = accumulate = true;
         else if (want("--camera-step")) camera_step = std::strtof(argv[++i], nullptr);
+        else if (want("--frames-in-flight")) frames_in_flight = std::atoi(argv[++i]);
         else if (want("--edits")) edits = std::atoi(argv[++i]);
         else if (std::strcmp(argv[i], "--edit-spread") == 0) edit_spread = true;
         else if (want("--rays")) rays = std::atoll(argv[++i]);
@@ -229,6 +235,7 @@ int main(int argc, char** argv) {
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
     if (edits < 0 || edits > (1 << 24)) { std::fprintf(stderr, "--edits must be in 0..2^24\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
+    if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
     if (gpus > 1) gather = true;
     if (post && gpus > 1) { std::fprintf(stderr, "--post needs the whole frame on one device (gather first on several)\n"); return 2; }
@@ -270,12 +277,14 @@ int main(int argc, char** argv) {
     for (int g = 0; g < gpus; g++) devices[(size_t)g] = device + g;
     for (int g = 0; g < gpus; g++) {
         RtConfig cfg = make_config(width, height, spp, depth, devices[(size_t)g], g, gpus, RT_FLAG_CACHE_PRIMARY | (accumulate ? RT_FLAG_ACCUMULATE : 0u) |
-                                                                                                       (reproject ? RT_FLAG_REPROJECT : 0u));
+                                                                                                       (reproject ? RT_FLAG_REPROJECT : 0u) |
+                                                                                                       (frames_in_flight == 2 ? RT_FLAG_FRAMES_IN_FLIGHT_2 : 0u));
         pipes[(size_t)g] = rt::render::create_instance(cfg, noise.data(), game, &err);
         if (!pipes[(size_t)g]) {
             std::fprintf(stderr, "create_instance failed on device %d: %s\n", devices[(size_t)g], err.c_str());
             return 1;
         }
+        pipes[(size_t)g]->set_frames_in_flight(frames_in_flight);
     }
     if (post && pipes[0]->enable_post_passes(true) != RT_OK) { std::fprintf(stderr, "enable_post_passes failed\n"); return 1; }
     if (gather) {
