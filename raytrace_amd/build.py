@@ -15,6 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
+API = os.path.join(CSRC, "api")   # the host layer of the C ABI: no device code (bench.py's kernel hash does not cover it)
 HOST = os.path.join(HERE, "host")
 INC = os.path.join(ROOT, "include")
 
@@ -29,8 +30,9 @@ CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-f
 AMD_SRCS = [os.path.join(CSRC, "rt_kernels.hip"), os.path.join(CSRC, "rt_world.hip"), os.path.join(CSRC, "rt_persist.hip"), os.path.join(CSRC, "rt_paths.hip"), os.path.join(CSRC, "rt_frame.hip"), os.path.join(CSRC, "rt_post.hip"),
             os.path.join(CSRC, "rt_edit.hip"), os.path.join(CSRC, "rt_query.hip"), os.path.join(CSRC, "rt_terrain.hip"),
             os.path.join(CSRC, "rt_temporal.hip"),
-            os.path.join(CSRC, "rt_api.hip")]
-AMD_DEPS = AMD_SRCS + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")) + [
+            ] + [os.path.join(API, f) for f in ("api_context.hip", "api_frame.hip", "api_world.hip", "api_query.hip", "api_post.hip",
+                                                 "api_gather.hip")]
+AMD_DEPS = AMD_SRCS + sorted(os.path.join(d, f) for d in (CSRC, API) for f in os.listdir(d) if f.endswith(".hpp")) + [
     os.path.join(INC, "rt_abi.h"), os.path.join(INC, "rt_math.h")]
 HOST_SRCS = [os.path.join(HOST, f) for f in ("world.cpp", "chunk_storage.cpp", "terrain_upload.cpp", "render.cpp", "host_capi.cpp")]
 HOST_DEPS = HOST_SRCS + [os.path.join(HOST, f) for f in ("world.hpp", "render.hpp", "chunk_storage.hpp", "terrain_upload.hpp")] + [os.path.join(INC, "rt_abi.h")]
@@ -58,7 +60,7 @@ def build(force=False, verbose=True):
     if force or _stale(LIB_AMD, AMD_DEPS):
         objs = []
         for src in AMD_SRCS:
-            obj = os.path.join(CSRC, os.path.basename(src) + ".o")
+            obj = src + ".o"
             _run([HIPCC] + HIP_FLAGS + ["-I", INC, "-c", src, "-o", obj])
             objs.append(obj)
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_AMD] + objs)

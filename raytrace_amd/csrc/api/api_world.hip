@@ -1,0 +1,273 @@
+// api_world.hip — the three kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits,
+// and terrain generated on the device; rt_read_box reads the resident region back.
+#include "rt_context.hpp"
+
+using namespace rta;
+
+namespace {
+
+// ---- a change of the resident world on the render stream (slabs, edits, generated terrain) ---------------------------------------
+// before its launches: they wait for the frames in flight on every lane and for the queries recorded so far (both read the region)
+hipError_t world_change_begin(RtContext* c) {
+    hipError_t e = join_lanes_into(c, c->stream);
+    if (e == hipSuccess) e = c->ev_query.wait(c->stream);
+    return e;
+}
+// after them: later queries (ev_world) and later frames, whichever lane they start on, see what changed
+hipError_t world_change_end(RtContext* c) {
+    hipError_t e = c->ev_world.record(c->stream);
+    return e == hipSuccess ? fence_lanes_after(c, c->stream) : e;
+}
+
+// ---- staging (StagingSet) ---------------------------------------------------------------------------------------------------
+// the host may write `need` bytes to the set: its previous transfer has left the host block; a smaller set is replaced by one of
+// `alloc` bytes once its device block has been applied.  (The upload stream and the set's events are created on first use.)
+hipError_t staging_claim(RtContext* c, StagingSet& s, size_t need, size_t alloc) {
+    hipError_t e = c->upload_stream ? hipSuccess : new_stream(c, &c->upload_stream);
+    for (hipEvent_t* ev : {&s.ev_copied.ev, &s.ev_applied.ev})
+        if (e == hipSuccess && !*ev) e = new_event(c, ev);
+    if (e == hipSuccess) e = s.ev_copied.host_wait();
+    if (e == hipSuccess) s.ev_copied.forget();
+    if (e != hipSuccess || need <= s.cap) return e;
+    e = s.ev_applied.host_wait();
+    return e == hipSuccess ? s.grow(c, need, alloc) : e;
+}
+// the first `bytes` of the host block to the device block on the upload stream, after the set's previous launch has read it; the
+// render stream waits for the transfer, and for the frames in flight on the other lane (they read what the launch changes)
+hipError_t staging_send(RtContext* c, StagingSet& s, size_t bytes) {
+    hipError_t e = s.ev_applied.wait(c->upload_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, c->upload_stream);
+    if (e == hipSuccess) e = s.ev_copied.record(c->upload_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, s.ev_copied.ev, 0);
+    return e == hipSuccess ? world_change_begin(c) : e;
+}
+// after the launch that read the device block: later frames, whichever lane they start on, see what it changed
+hipError_t staging_applied(RtContext* c, StagingSet& s) {
+    hipError_t e = s.ev_applied.record(c->stream);
+    return e == hipSuccess ? world_change_end(c) : e;
+}
+
+int reflatten(RtContext* c, const uint8_t* d_mine_lin, const uint32_t* d_mat_lin) {
+    RT_HIP(c, hipMemsetAsync(c->d_flag, 0, sizeof(uint32_t), c->stream));
+    RT_HIP(c, rtd::launch_flatten(d_mine_lin, d_mat_lin, c->d_mine_sw, c->d_mat_sw, c->d_coarse, c->d_brick, c->d_flag, c->logr, c->stream));
+    uint32_t flag = 0;
+    RT_HIP(c, hipMemcpyAsync(&flag, c->d_flag, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    if (flag) return fail(c, RT_ERR_INVALID_ARG, "minefield holds a value above 30 (the reference writes 0..6, src/world/chunk.rs:163-183)");
+    return RT_OK;
+}
+
+// ---- terrain on the device (rt_generate_world, rt_generate_slice) -------------------------------------------------------------
+// The window [lo, lo + ext) on every axis: 16-aligned, every voxel (and so lr = lo + R/2) inside int32.
+bool terrain_window_ok(const int64_t lo[3], const int64_t ext[3]) {
+    for (int a = 0; a < 3; a++)
+        if (lo[a] % RT_SLICE_SIZE != 0 || lo[a] < (int64_t)INT32_MIN || lo[a] + ext[a] - 1 > (int64_t)INT32_MAX) return false;
+    return true;
+}
+// Generates the window on the render stream after every frame already submitted (every lane) and every earlier query; later frames,
+// lanes and queries see the result (the ordering of rt_upload_slice, without staging: the kernels read nothing from the host).
+int generate_terrain(RtContext* c, uint64_t seed, const int64_t lo[3], int axis) {
+    RT_HIP(c, hipSetDevice(c->device));
+    if (!c->d_heights) {
+        const size_t cols = (size_t)(c->region + RT_CHUNK_SIZE) * (size_t)(c->region + RT_CHUNK_SIZE);
+        RT_HIP(c, dev_alloc(c, &c->d_heights, cols));
+    }
+    c->accum_valid = false;
+    invalidate_prepass(c);
+    RT_HIP(c, world_change_begin(c));
+    {
+        LaunchTimer t(c, 1);
+        RT_HIP(c, rtd::launch_terrain(c->d_mine_sw, c->d_mat_sw, c->d_coarse, c->d_brick, c->d_heights, c->logr, seed, lo, axis, c->stream));
+    }
+    RT_HIP(c, world_change_end(c));
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_upload_world(RtContext* ctx, const uint32_t* materials, const uint8_t* minefield) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_world: null pointer");
+    ctx->accum_valid = false;
+    invalidate_prepass(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, sync_lanes(ctx));
+    // the caller-layout copy lives for the duration of this call only (it used to stay resident — 160 MiB at
+    // R = 256, 5 GiB at R = 1024 — although nothing but this function reads it)
+    uint32_t* d_mat_lin = nullptr; uint8_t* d_mine_lin = nullptr;
+    hipError_t e = hipMalloc((void**)&d_mat_lin, ctx->vox * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_mine_lin, ctx->vox);
+    if (e == hipSuccess) e = hipMemcpy(d_mat_lin, materials, ctx->vox * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_mine_lin, minefield, ctx->vox, hipMemcpyHostToDevice);
+    int rc = RT_OK;
+    if (e != hipSuccess) rc = fail(ctx, e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_upload_world: ") + hipGetErrorString(e));
+    else {
+        ctx->has_world = false;
+        ctx->world_resident = false;
+        rc = reflatten(ctx, d_mine_lin, d_mat_lin);      // synchronises the stream before it returns
+    }
+    if (d_mat_lin) (void)hipFree(d_mat_lin);
+    if (d_mine_lin) (void)hipFree(d_mine_lin);
+    if (rc != RT_OK) return rc;
+    ctx->has_world = true;
+    ctx->world_resident = true;
+    ctx->ev_world.forget();   // (the region is complete on the device: reflatten synchronised)
+    return RT_OK;
+}
+
+int rt_slice_staging(RtContext* ctx, uint32_t** materials, uint8_t** minefield) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_slice_staging: null pointer");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    // staging of one slab: pinned host memory (the reference's upload buffers are host-visible mapped Vulkan buffers,
+    // terrain_upload.rs:65-82) holding the materials, then the minefield, and its device twin
+    const size_t n = (size_t)RT_SLICE_SIZE * (size_t)ctx->region * (size_t)ctx->region;
+    StagingSet& s = ctx->slab_sets[ctx->slabs & 1u];   // the set the NEXT rt_upload_slice uses: the slab before last has left it
+    RT_HIP(ctx, staging_claim(ctx, s, 5 * n, 5 * n));
+    *materials = reinterpret_cast<uint32_t*>(s.host);
+    *minefield = s.host + 4 * n;
+    return RT_OK;
+}
+
+int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* materials, const uint8_t* minefield) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: null pointer");
+    ctx->accum_valid = false;
+    invalidate_prepass(ctx);
+    const size_t kR = (size_t)ctx->region;
+    if (axis < 0 || axis > 2 || texel_offset < 0 || texel_offset + RT_SLICE_SIZE > ctx->region || texel_offset % RT_SLICE_SIZE != 0)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: bad axis or offset");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_upload_slice: upload the full region first");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    // Incremental and asynchronous.  The slab goes pinned host staging -> device staging (5 bytes x 16 x R^2) on the upload
+    // stream; the render stream waits for that event (not the host), then ONE launch re-tiles the slab's 16 R^2 voxels into the
+    // brick-swizzled arrays and a second rebuilds the nibble-map words it touches.  Frames in flight keep reading the region
+    // until then by stream order — the host waits for nothing on the device (the reference blocks on vkQueueWaitIdle here,
+    // pipeline.rs:181-189); only a previous slab still leaving the pinned staging is waited for.
+    const size_t n = (size_t)RT_SLICE_SIZE * kR * kR;
+    StagingSet& s = ctx->slab_sets[ctx->slabs & 1u];
+    RT_HIP(ctx, staging_claim(ctx, s, 5 * n, 5 * n));
+    if ((ctx->cfg.flags & RT_FLAG_TRUSTED_WORLD) == 0) {
+        // values above 30 are rejected as in rt_upload_world — BEFORE anything is written or transferred: a rejected slab leaves
+        // the region (and what can be drawn) as it was.  The bytes are in host memory, so the check is a host loop over 16 R^2
+        // bytes (~20 us at R = 256) and needs no device round trip; a host that vouches for its data skips it.
+        uint8_t worst = 0;
+        for (size_t i = 0; i < n; i++) worst = minefield[i] > worst ? minefield[i] : worst;
+        if (worst > rtd::kMaxStepValue)
+            return fail(ctx, RT_ERR_INVALID_ARG, "minefield slab holds a value above 30 (the reference writes 0..6, src/world/chunk.rs:163-183); the region is unchanged");
+    }
+    uint32_t* h_mat = reinterpret_cast<uint32_t*>(s.host);
+    uint8_t* h_mine = s.host + 4 * n;
+    if (materials != h_mat) memcpy(h_mat, materials, n * sizeof(uint32_t));   // borrowed buffers are released at return;
+    if (minefield != h_mine) memcpy(h_mine, minefield, n);                     // rt_slice_staging's pointers need no copy
+    ctx->slabs++;
+    RT_HIP(ctx, staging_send(ctx, s, 5 * n));
+    {
+        LaunchTimer t(ctx, 1);
+        RT_HIP(ctx, rtd::launch_flatten_slab(s.dev + 4 * n, reinterpret_cast<const uint32_t*>(s.dev), ctx->d_mine_sw, ctx->d_mat_sw,
+                                             ctx->d_coarse, ctx->d_brick, ctx->logr, axis, texel_offset, ctx->stream));
+    }
+    RT_HIP(ctx, staging_applied(ctx, s));
+    return RT_OK;
+}
+
+int rt_generate_world(RtContext* ctx, uint64_t seed, const int64_t window_lo[3]) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const int64_t R = ctx->region;
+    const int64_t lo[3] = {window_lo ? window_lo[0] : -R / 2, window_lo ? window_lo[1] : -R / 2, window_lo ? window_lo[2] : -R / 2};
+    const int64_t ext[3] = {R, R, R};
+    if (!terrain_window_ok(lo, ext))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_generate_world: window_lo must be a multiple of 16 and the window inside int32; nothing was enqueued");
+    const int rc = generate_terrain(ctx, seed, lo, -1);
+    if (rc != RT_OK) return rc;
+    ctx->has_world = true;
+    ctx->world_resident = true;
+    return RT_OK;
+}
+
+int rt_generate_slice(RtContext* ctx, uint64_t seed, int axis, const int64_t window_lo[3]) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (axis < 0 || axis > 2 || !window_lo) return fail(ctx, RT_ERR_INVALID_ARG, "rt_generate_slice: bad axis or null window; nothing was enqueued");
+    const int64_t R = ctx->region;
+    const int64_t lo[3] = {window_lo[0], window_lo[1], window_lo[2]};
+    const int64_t ext[3] = {axis == 0 ? RT_SLICE_SIZE : R, axis == 1 ? RT_SLICE_SIZE : R, axis == 2 ? RT_SLICE_SIZE : R};
+    if (!terrain_window_ok(lo, ext))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_generate_slice: window_lo must be a multiple of 16 and the window inside int32; nothing was enqueued");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_generate_slice: upload or generate the full region first");
+    return generate_terrain(ctx, seed, lo, axis);
+}
+
+int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (count > (1u << 24)) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_voxels: more than 2^24 edits in one call; nothing was applied");
+    if (count == 0) return RT_OK;
+    if (!edits) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_voxels: null edits");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_edit_voxels: upload the full region first");
+    // Binning on the host, all of it before anything is enqueued (edit_binning.hpp)
+    EditBins bins;
+    const uint32_t bad = edit_bin(ctx->edit_binning, edits, count, ctx->logr, &bins);
+    if (bad != count)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_voxels: edit " + std::to_string(bad) +
+                                                 " has a coordinate outside the region or reserved != 0; nothing was applied");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    StagingSet& s = ctx->edit_sets[ctx->edit_batches & 1u];
+    size_t cap = bins.need < ((size_t)64 << 10) ? ((size_t)64 << 10) : bins.need;   // (if the set must grow)
+    if (cap < bins.need + bins.need / 2u) cap = align16(bins.need + bins.need / 2u);
+    RT_HIP(ctx, staging_claim(ctx, s, bins.need, cap));
+    const uint32_t nrec = edit_fill(ctx->edit_binning, edits, ctx->logr, reinterpret_cast<uint32_t*>(s.host),
+                                    reinterpret_cast<uint32_t*>(s.host + bins.off_offs), reinterpret_cast<uint32_t*>(s.host + bins.off_recs));
+    // Transfer on the upload stream, then the rebuild on the render stream after the frames already submitted (every lane), and
+    // later frames after the rebuild — the ordering of rt_upload_slice.
+    ctx->edit_batches++;
+    ctx->accum_valid = false;
+    invalidate_prepass(ctx);
+    RT_HIP(ctx, staging_send(ctx, s, bins.off_recs + (size_t)nrec * 8u));
+    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
+    const uint32_t* d_offs = reinterpret_cast<const uint32_t*>(s.dev + bins.off_offs);
+    const uint2* d_recs = reinterpret_cast<const uint2*>(s.dev + bins.off_recs);
+    {
+        LaunchTimer lt(ctx, 1);
+        RT_HIP(ctx, rtd::launch_rebuild_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, d_offs, d_recs, bins.touched, ctx->logr, ctx->stream));
+    }
+    {
+        LaunchTimer lt(ctx, 1);
+        RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, bins.touched, ctx->logr, ctx->stream));
+    }
+    RT_HIP(ctx, staging_applied(ctx, s));
+    return RT_OK;
+}
+
+int rt_read_box(RtContext* ctx, int x0, int y0, int z0, int ex, int ey, int ez, uint32_t* materials, uint8_t* minefield) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const int R = ctx->region;
+    if (x0 < 0 || y0 < 0 || z0 < 0 || ex < 1 || ey < 1 || ez < 1 || ex > R - x0 || ey > R - y0 || ez > R - z0)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_read_box: box outside the region");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_read_box: no region uploaded");
+    if (!materials && !minefield) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, sync_lanes(ctx));
+    // z-slabs of at most 2^24 voxels through a temporary device buffer (80 MiB)
+    const size_t plane = (size_t)ex * (size_t)ey;
+    const int nz = (int)(((size_t)1 << 24) / plane >= (size_t)ez ? (size_t)ez : (((size_t)1 << 24) / plane > 0 ? ((size_t)1 << 24) / plane : 1));
+    uint32_t* d_mat = nullptr; uint8_t* d_mine = nullptr;
+    hipError_t e = hipSuccess;
+    if (materials) e = hipMalloc((void**)&d_mat, plane * (size_t)nz * sizeof(uint32_t));
+    if (e == hipSuccess && minefield) e = hipMalloc((void**)&d_mine, plane * (size_t)nz);
+    for (int z = 0; z < ez && e == hipSuccess; z += nz) {
+        const int n = ez - z < nz ? ez - z : nz;
+        e = rtd::launch_read_box(ctx->d_mine_sw, ctx->d_mat_sw, ctx->logr, x0, y0, z0 + z, ex, ey, n, d_mat, d_mine, ctx->stream);
+        if (e == hipSuccess && materials)
+            e = hipMemcpyAsync(materials + plane * (size_t)z, d_mat, plane * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && minefield)
+            e = hipMemcpyAsync(minefield + plane * (size_t)z, d_mine, plane * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    if (d_mat) (void)hipFree(d_mat);
+    if (d_mine) (void)hipFree(d_mine);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_read_box: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+}  // extern "C"
