@@ -164,7 +164,19 @@ typedef enum RtKernel {
                                        L = 16 x lighting_f32 of the frame just drawn; lighting_f32 / lighting_rgba16 = sum / n / 16 with
                                        the pixel's own n (rt_read_history); the other planes are the frame's own.  The arithmetic is
                                        fixed (DESIGN.md "Reprojection"; restated in tests/temporal_ref.py) and reproduced bit for bit.
-                                       One launch per frame (k_temporal_frame) in place of k_accumulate_frame.                 */
+                                       One launch per frame (k_temporal_frame) in place of k_accumulate_frame.
+                                       RtConfig.edit_radius > 0 keeps the history across rt_edit_voxels: each call records one box per
+                                       touched 64^3 chunk (the texel min / max of its records; at most 16 may wait, see
+                                       rt_edit_boxes_pending) and the next frame drawn consumes them.  If that frame would be still or
+                                       moved it is
+                                         moved with boxes  the moved pass — also under an unchanged camera, where it projects into the
+                                                  same camera — in which a pixel whose rebuilt hit point lies within edit_radius voxels
+                                                  of an edited box, or from which the ray towards the sun meets a box grown by 1 voxel,
+                                                  restarts (sum = 0 + L, n = 1) and every other pixel goes on as in a moved frame;
+                                       a frame that restarts anyway, or whose set overflowed, restarts as before and drops the boxes.
+                                       Boxes are texels until that frame's lr places them in the world (a box cut by the window's seam
+                                       covers the whole window on that axis).  Bounce light beyond the radius and sky occlusion are
+                                       not tested: they fade through history_cap.  DESIGN.md "Edits under a kept history".        */
 
 /*
  * RtConfig — replaces the compile-time window constants (constants.rs:9-10) and adds the
@@ -191,7 +203,11 @@ typedef struct RtConfig {
     uint32_t flags;         /* RT_FLAG_* */
     int32_t  history_cap;   /* (was reserved[0]) RT_FLAG_REPROJECT: the most samples a pixel's history carries across a camera
                                change; 0 = the default, 32; valid 1..65535 (else RT_ERR_INVALID_ARG).  Ignored without the flag. */
-    int32_t  reserved[4];
+    int32_t  edit_radius;   /* (was reserved[0]) RT_FLAG_REPROJECT: 0 = rt_edit_voxels restarts the lighting history; 1..64 = it keeps
+                               the history, and the next frame restarts only the pixels whose hit point lies within this many voxels
+                               of an edited box or in the sun shadow of one; anything else RT_ERR_INVALID_ARG.  Ignored without
+                               the flag. */
+    int32_t  reserved[3];
 } RtConfig;
 
 /* Output planes. Bindings cited from shaders/glsl/raytrace.comp:14-21; formats from
@@ -326,7 +342,8 @@ typedef struct RtVoxelEdit {
  *     on every lane and frame slot and on a stream set with rt_set_stream, read the new one.  Edits and slabs apply in call order.
  *     The caller's array is free once the call returns: the binned batch is staged in pinned memory (two staging sets used in
  *     turn, grown when a batch needs more; the call waits on the host only until the batch before last has left its set).
- *   Accumulation: a call with count > 0 resets RT_FLAG_ACCUMULATE's running sum, as the uploads do.
+ *   Accumulation: a call with count > 0 resets RT_FLAG_ACCUMULATE's running sum, as the uploads do — except on an RT_FLAG_REPROJECT
+ *     context with RtConfig.edit_radius > 0, which keeps its history and records the edited boxes for the next frame instead.
  * Device work per call: one launch that scatters the material words and rebuilds the touched chunks (one workgroup per chunk), one
  * that rebuilds their nibble-map words (counted by RT_FLAG_TIMING_ALL). */
 int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count);
@@ -532,6 +549,12 @@ int rt_get_accumulation(RtContext* ctx, uint32_t* frames, uint32_t* samples);
  * RT_ERR_INVALID_ARG on a context without the flag; all zero before the first frame.  For tests, and for a host that wants to
  * denoise harder where the history is short. */
 int rt_read_history(RtContext* ctx, uint32_t* counts, size_t bytes);
+/* (ABI 1.3, additive; hosts detect the feature by this symbol) RtConfig.edit_radius > 0: *boxes = the edited boxes that wait for
+ * the next rt_draw_frame (0..16; one per 64^3 chunk an rt_edit_voxels call touched), *overflowed = 1 when a call would have passed
+ * 16, so that the set was emptied and the next frame restarts the history.  An upload, rt_generate_*, rt_upload_noise and
+ * rt_reset_accumulation drop both; the next frame consumes both.  Host-side state only: does not synchronise.  0 and 0 on a
+ * context without the feature. */
+int rt_edit_boxes_pending(RtContext* ctx, uint32_t* boxes, uint32_t* overflowed);
 
 int rt_get_counters(RtContext* ctx, RtCounters* out);
 int rt_reset_counters(RtContext* ctx);
@@ -558,7 +581,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtRay, RtRayHit, RT_HIT_*, rt_trace_rays, rt_trace_rays_async, rt_pick_pixels (ray queries).
  *        Additive, same minor version: rt_generate_world, rt_generate_slice (terrain generated on the device).
  *        Additive, same minor version: RT_FLAG_REPROJECT, RtConfig.history_cap (was reserved[0]), rt_read_history (temporal
- *        reprojection of the accumulated lighting while the camera moves). */
+ *        reprojection of the accumulated lighting while the camera moves).
+ *        Additive, same minor version: RtConfig.edit_radius (was reserved[0]), rt_edit_boxes_pending (the lighting history is kept
+ *        across rt_edit_voxels and restarted only near an edit or in its sun shadow). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

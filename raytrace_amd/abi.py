@@ -76,12 +76,24 @@ class RtUniforms(C.Structure):
 assert C.sizeof(RtUniforms) == 192
 
 
+class _RtConfigTailFields(C.Structure):
+    _fields_ = [("edit_radius", C.c_int32), ("reserved3", C.c_int32 * 3)]
+
+
+class _RtConfigTail(C.Union):
+    """The last 16 bytes of RtConfig: the header's `edit_radius; reserved[3]` (ABI 1.3, additive: edit_radius took the first
+    reserved word), and `reserved`, the four words seen whole as callers written before that knew them (reserved[0] IS edit_radius)."""
+    _anonymous_ = ("named",)
+    _fields_ = [("named", _RtConfigTailFields), ("reserved", C.c_int32 * 4)]
+
+
 class RtConfig(C.Structure):
+    _anonymous_ = ("tail",)
     _fields_ = [
         ("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("region", C.c_int32),
         ("spp", C.c_int32), ("depth", C.c_int32), ("device", C.c_int32), ("tile_rank", C.c_int32),
         ("tile_world", C.c_int32), ("kernel", C.c_int32), ("flags", C.c_uint32),
-        ("history_cap", C.c_int32), ("reserved", C.c_int32 * 4),
+        ("history_cap", C.c_int32), ("tail", _RtConfigTail),
     ]
 
 

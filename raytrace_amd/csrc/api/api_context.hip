@@ -292,6 +292,8 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
             return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: RT_FLAG_REPROJECT needs RT_FLAG_ACCUMULATE");
         if (cfg->history_cap < 0 || cfg->history_cap > 65535)
             return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: history_cap must be 0 (the default, 32) or 1..65535");
+        if (cfg->edit_radius < 0 || cfg->edit_radius > 64)
+            return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: edit_radius must be 0 (an edit restarts the history) or 1..64");
         if (cfg->spp != 1 || cfg->tile_world != 1)
             return fail(nullptr, RT_ERR_UNIMPLEMENTED, "rt_create: RT_FLAG_REPROJECT needs one-sample whole frames (spp == 1, tile_world == 1)");
     }
@@ -315,6 +317,7 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
     const bool persistent = c->route.family == RT_KERNEL_PERSISTENT;
     c->reproject = (cfg->flags & RT_FLAG_REPROJECT) != 0;
     c->history_cap = cfg->history_cap > 0 ? (uint32_t)cfg->history_cap : 32u;
+    c->edit_radius = c->reproject ? (uint32_t)cfg->edit_radius : 0u;   // (ignored without the flag, like history_cap)
 
     // tiling: 8x8-pixel tiles dealt round-robin over tile_world contexts
     c->tiles_x = (cfg->width + 7) / 8; c->tiles_y = (cfg->height + 7) / 8;
@@ -401,7 +404,7 @@ int rt_sync(RtContext* ctx) {
 int rt_upload_noise(RtContext* ctx, const uint8_t* rgba8) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!rgba8) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_noise: null pointer");
-    ctx->accum_valid = false;
+    restart_history(ctx);
     invalidate_prepass(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, sync_lanes(ctx));

@@ -154,7 +154,24 @@ struct PersistFrame {
     uint64_t accum_n = 0;               // samples the sum holds after this frame
     float4* accum_multi = nullptr;      // d_accum for frames of more than one sample
     int temporal_mode = rtd::TEMPORAL_RESTART;   // RT_FLAG_REPROJECT: how this frame's pass treats the history
+    uint32_t nbox = 0;                  // RtConfig.edit_radius > 0: the edited boxes this frame consumed, in world coordinates
+    rtd::TemporalBox boxes[rtd::kTemporalMaxBoxes];
 };
+
+// A pending texel box in the world coordinates of a frame with render offset lr: w = lr - R/2 + (t - lr) mod R per axis
+// (render.texel_to_world), the box [w(min), w(max) + 1].  Where the window's seam cuts the box (w(min) > w(max)) it covers the
+// whole window on that axis, which is conservative.
+rtd::TemporalBox world_box(const EditBox& b, const int32_t lr[3], int region) {
+    rtd::TemporalBox w;
+    const int64_t R = region;
+    for (int k = 0; k < 3; k++) {
+        const int64_t base = (int64_t)lr[k] - R / 2;
+        const int64_t lo = base + ((((int64_t)b.lo[k] - lr[k]) % R) + R) % R, hi = base + ((((int64_t)b.hi[k] - lr[k]) % R) + R) % R;
+        w.lo[k] = (float)(lo <= hi ? lo : base);
+        w.hi[k] = (float)(lo <= hi ? hi + 1 : base + R);
+    }
+    return w;
+}
 
 // The frame's slot and first lane, its accumulation key; then the slot's previous frame has finished with the slot.
 hipError_t frame_begin(RtContext* c, PersistFrame& p, const RtUniforms* u, bool frame_events) {
@@ -194,6 +211,12 @@ hipError_t frame_begin(RtContext* c, PersistFrame& p, const RtUniforms* u, bool 
     // paths' (its first batch starts from the running sum, its last stores it back).
     const uint32_t spp = (uint32_t)c->cfg.spp;
     p.accum = c->d_accum != nullptr;
+    // (edit boxes belong to the next frame drawn: this one consumes them, whatever it makes of them; an overflowed set restarts it)
+    if (c->edit_overflow) c->accum_valid = false;
+    p.nbox = c->edit_nbox;
+    for (uint32_t b = 0; b < p.nbox; b++) p.boxes[b] = world_box(c->edit_boxes[b], u->lr, c->region);
+    c->edit_nbox = 0;
+    c->edit_overflow = false;
     p.accum_cont = p.accum && c->accum_valid && memcmp(p.key, c->accum_key, sizeof(p.key)) == 0 && c->accum_samples + spp <= (1ull << 24);
     p.accum_n = p.accum_cont ? c->accum_samples + spp : spp;
     p.accum_multi = p.accum && spp > 1u ? c->d_accum : nullptr;
@@ -205,7 +228,10 @@ hipError_t frame_begin(RtContext* c, PersistFrame& p, const RtUniforms* u, bool 
         if (still) p.temporal_mode = rtd::TEMPORAL_STILL;
         else if (c->accum_valid && !same_camera && p.key[0] == c->accum_key[0]) p.temporal_mode = rtd::TEMPORAL_MOVED;
         else p.temporal_mode = rtd::TEMPORAL_RESTART;
-        if (p.temporal_mode == rtd::TEMPORAL_MOVED) {
+        // pending boxes and a history that goes on: the moved pass with the box test — also under an unchanged camera, where it
+        // projects into the same camera.  (A frame that restarts anyway drops them.)
+        if (p.temporal_mode != rtd::TEMPORAL_RESTART && p.nbox > 0u) p.temporal_mode = rtd::TEMPORAL_MOVED_BOXES;
+        if (p.temporal_mode == rtd::TEMPORAL_MOVED || p.temporal_mode == rtd::TEMPORAL_MOVED_BOXES) {
             p.accum_cont = true;
             p.accum_n = (c->accum_samples < c->history_cap ? c->accum_samples : (uint64_t)c->history_cap) + 1u;
         }
@@ -355,6 +381,12 @@ hipError_t frame_accumulate_tail(RtContext* c, PersistFrame& p) {
             memcpy(ta.origin, &c->accum_key[1], 12); memcpy(ta.forward, &c->accum_key[4], 12);
             memcpy(ta.up, &c->accum_key[7], 12); memcpy(ta.right, &c->accum_key[10], 12);
             ta.cap = c->history_cap;
+            if (p.temporal_mode == rtd::TEMPORAL_MOVED_BOXES) {
+                ta.nbox = p.nbox;
+                memcpy(ta.box, p.boxes, sizeof(ta.box));
+                ta.r2 = (float)(c->edit_radius * c->edit_radius);
+                for (int k = 0; k < 3; k++) { ta.sun[k] = p.f.sunangle[k]; ta.inv_sun[k] = 1.0f / p.f.sunangle[k]; }
+            }
             e = rtd::launch_temporal_frame(p.f, p.pl, ta, p.temporal_mode, p.tail);
             c->hist_cur = next;
         }
@@ -426,7 +458,15 @@ int rt_draw_frame(RtContext* ctx, const RtUniforms* u) {
 
 int rt_reset_accumulation(RtContext* ctx) {
     if (!ctx) return RT_ERR_INVALID_ARG;
-    ctx->accum_valid = false;
+    restart_history(ctx);
+    return RT_OK;
+}
+
+int rt_edit_boxes_pending(RtContext* ctx, uint32_t* boxes, uint32_t* overflowed) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!boxes || !overflowed) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_boxes_pending: null pointer");
+    *boxes = ctx->edit_nbox;
+    *overflowed = ctx->edit_overflow ? 1u : 0u;
     return RT_OK;
 }
 

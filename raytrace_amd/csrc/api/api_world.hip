@@ -72,7 +72,7 @@ int generate_terrain(RtContext* c, uint64_t seed, const int64_t lo[3], int axis)
         const size_t cols = (size_t)(c->region + RT_CHUNK_SIZE) * (size_t)(c->region + RT_CHUNK_SIZE);
         RT_HIP(c, dev_alloc(c, &c->d_heights, cols));
     }
-    c->accum_valid = false;
+    restart_history(c);
     invalidate_prepass(c);
     RT_HIP(c, world_change_begin(c));
     {
@@ -90,7 +90,7 @@ extern "C" {
 int rt_upload_world(RtContext* ctx, const uint32_t* materials, const uint8_t* minefield) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_world: null pointer");
-    ctx->accum_valid = false;
+    restart_history(ctx);
     invalidate_prepass(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     RT_HIP(ctx, sync_lanes(ctx));
@@ -134,7 +134,7 @@ int rt_slice_staging(RtContext* ctx, uint32_t** materials, uint8_t** minefield) 
 int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* materials, const uint8_t* minefield) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: null pointer");
-    ctx->accum_valid = false;
+    restart_history(ctx);
     invalidate_prepass(ctx);
     const size_t kR = (size_t)ctx->region;
     if (axis < 0 || axis > 2 || texel_offset < 0 || texel_offset + RT_SLICE_SIZE > ctx->region || texel_offset % RT_SLICE_SIZE != 0)
@@ -221,7 +221,18 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
     // Transfer on the upload stream, then the rebuild on the render stream after the frames already submitted (every lane), and
     // later frames after the rebuild — the ordering of rt_upload_slice.
     ctx->edit_batches++;
-    ctx->accum_valid = false;
+    if (ctx->edit_radius == 0u) {
+        ctx->accum_valid = false;
+    } else if (!ctx->edit_overflow) {
+        // the history stays: one box per touched chunk waits for the next frame drawn, which restarts only the pixels an edit can
+        // have changed (api_frame.hip); a set that would pass its capacity is emptied and that frame restarts
+        if (ctx->edit_nbox + bins.touched > rtd::kTemporalMaxBoxes) {
+            ctx->edit_nbox = 0;
+            ctx->edit_overflow = true;
+        } else {
+            ctx->edit_nbox += edit_chunk_boxes(ctx->edit_binning, edits, ctx->logr, ctx->edit_boxes + ctx->edit_nbox);
+        }
+    }
     invalidate_prepass(ctx);
     RT_HIP(ctx, staging_send(ctx, s, bins.off_recs + (size_t)nrec * 8u));
     const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);

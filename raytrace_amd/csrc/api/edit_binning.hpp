@@ -56,6 +56,29 @@ inline uint32_t edit_bin(EditBinning& b, const RtVoxelEdit* edits, uint32_t coun
     return count;
 }
 
+// The texel box (min / max per axis, inclusive) of one chunk's edits.
+struct EditBox { uint16_t lo[3], hi[3]; };
+
+// One box per touched chunk of the batch edit_bin binned last, in chunk order: the texel min / max over EVERY record of the chunk
+// (duplicates and records that change nothing included).  out[] holds at least `touched` boxes; returns how many were written.
+inline uint32_t edit_chunk_boxes(const EditBinning& b, const RtVoxelEdit* edits, int logr, EditBox* out) {
+    const uint32_t nchunks = 1u << (3 * (logr - 6));
+    const std::vector<uint32_t>&start = b.start, &order = b.order;
+    uint32_t t = 0;
+    for (uint32_t c = 0; c < nchunks; c++) {
+        const uint32_t lo = c ? start[c - 1u] : 0u, hi = start[c];
+        if (lo == hi) continue;
+        EditBox& x = out[t++];
+        for (int k = 0; k < 3; k++) { x.lo[k] = 0xFFFFu; x.hi[k] = 0u; }
+        for (uint32_t j = lo; j < hi; j++) {
+            const RtVoxelEdit& ed = edits[order[j]];
+            const uint16_t p[3] = {ed.x, ed.y, ed.z};
+            for (int k = 0; k < 3; k++) { x.lo[k] = std::min(x.lo[k], p[k]); x.hi[k] = std::max(x.hi[k], p[k]); }
+        }
+    }
+    return t;
+}
+
 // Staging of the batch edit_bin binned last: touched chunk ids, their edit ranges, and per chunk one record per edited voxel — its
 // last edit in the batch (the range is walked backwards; b.stamp marks the voxels a chunk's run has kept).  Returns the records.
 inline uint32_t edit_fill(EditBinning& b, const RtVoxelEdit* edits, int logr, uint32_t* h_chunks, uint32_t* h_offs, uint32_t* h_recs) {

@@ -284,6 +284,13 @@ struct __attribute__((visibility("hidden"))) RtContext {
     float4* d_hist_sum[2] = {nullptr, nullptr};
     uint2* d_hist_rec[2] = {nullptr, nullptr};
     int hist_cur = 0;                   // the set the pass of the frame drawn last wrote
+    // RtConfig.edit_radius > 0 (with RT_FLAG_REPROJECT): rt_edit_voxels keeps the history and records one texel box per touched
+    // chunk; the next frame drawn turns them into world boxes (its lr) and restarts only the pixels near or shadowed by one.
+    // More than kTemporalMaxBoxes pending: the set is emptied and marked overflowed, and that frame restarts.
+    uint32_t edit_radius = 0;           // 0: an edit restarts the history (accum_valid = false), no boxes are kept
+    rta::EditBox edit_boxes[rtd::kTemporalMaxBoxes];
+    uint32_t edit_nbox = 0;
+    bool edit_overflow = false;
 
     // ray queries (rt_trace_rays, rt_pick_pixels): a stream of their own (the device's highest priority), so that a query waits for
     // the world changes before it (ev_world) and not for the frames; the world changes wait for the queries before them (ev_query)
@@ -295,6 +302,14 @@ struct __attribute__((visibility("hidden"))) RtContext {
 namespace rta __attribute__((visibility("hidden"))) {
 
 extern thread_local std::string g_create_error;   // rt_last_error(NULL): why the last rt_create of this thread failed
+
+// What restarts the accumulation / the history outright (uploads, generated terrain, new noise, rt_reset_accumulation): the next
+// frame starts from zero, and edit boxes still waiting for it mean nothing any more.
+inline void restart_history(RtContext* c) {
+    c->accum_valid = false;
+    c->edit_nbox = 0;
+    c->edit_overflow = false;
+}
 
 inline int fail(RtContext* c, int code, const std::string& msg) {
     if (c) c->err = msg; else g_create_error = msg;

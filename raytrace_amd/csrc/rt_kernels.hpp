@@ -169,7 +169,11 @@ struct QueryArgs {
 hipError_t launch_query(const Scene& sc, const Frame& f, const QueryArgs& a, hipStream_t st);
 
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
-enum { TEMPORAL_RESTART = 0, TEMPORAL_STILL = 1, TEMPORAL_MOVED = 2 };
+// (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
+// or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)
+enum { TEMPORAL_RESTART = 0, TEMPORAL_STILL = 1, TEMPORAL_MOVED = 2, TEMPORAL_MOVED_BOXES = 3 };
+constexpr uint32_t kTemporalMaxBoxes = 16;
+struct TemporalBox { float lo[3], hi[3]; };   // world coordinates, [first voxel, last voxel + 1] per axis
 struct TemporalArgs {
     const float4* prev_sum;   // the history set the previous frame's pass wrote: sums by row-major pixel ...
     const uint2* prev_rec;    // ... and (depth_f32 bits, count | normal << 27)
@@ -177,6 +181,11 @@ struct TemporalArgs {
     uint2* next_rec;
     float origin[3], forward[3], right[3], up[3];   // the previous frame's camera (TEMPORAL_MOVED)
     uint32_t cap;             // most samples a history carries across a camera change (1..65535)
+    // TEMPORAL_MOVED_BOXES only (appended: the other modes read what they read before, at the offsets they had)
+    uint32_t nbox;            // edited boxes in use (1..kTemporalMaxBoxes)
+    TemporalBox box[kTemporalMaxBoxes];
+    float r2;                 // (float)(edit_radius^2)
+    float sun[3], inv_sun[3]; // Frame::sunangle and 1.0f / it, divided on the host
 };
 hipError_t launch_temporal_frame(const Frame& f, const Planes& planes, const TemporalArgs& a, int mode, hipStream_t st);
 

@@ -124,7 +124,8 @@ class Pipeline {
 
 // render::create_instance (mod.rs:36-43) -> Pipeline::new (pipeline.rs:36-76): creates the device context, uploads
 // the game's world (RenderData::initialize, render_data.rs:269-301) and the blue-noise table
-// (render_data.rs:110-133).  Returns nullptr and fills *error on failure.
+// (render_data.rs:110-133).  Returns nullptr and fills *error on failure.  `cfg` goes to rt_create as it is: history_cap and
+// edit_radius (RT_FLAG_REPROJECT) included.
 Pipeline* create_instance(const RtConfig& cfg, const uint8_t* blue_noise_rgba8, game::Game& game, std::string* error);
 
 }  // namespace rt::render

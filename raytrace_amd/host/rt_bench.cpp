@@ -6,7 +6,8 @@
 //
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
 //            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
-//            [--reproject] [--camera-step DX] [--frames-in-flight N] [--edits N [--edit-spread]] [--rays N [--rays-coherent]]
+//            [--reproject] [--camera-step DX] [--frames-in-flight N] [--edits N [--edit-spread]] [--edit-radius N]
+//            [--rays N [--rays-coherent]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -33,6 +34,10 @@
 // of the region.  After the timed loop the same batches run alone on a second pipeline created with RT_FLAG_TIMING_ALL: the JSON
 // line adds the device time of the edit launches per call (rt_get_timing's shade_ms: the rebuild and nibble-map launches, each
 // bracketed by events), the launches per call, the host time spent inside rt_edit_voxels and the wall time per call.
+//
+// --edit-radius N (with --reproject --edits N): RtConfig.edit_radius — the edits no longer restart the lighting history; every frame
+// runs the moved pass with the edited boxes and restarts only the pixels near one or in its sun shadow.  The JSON line's acc_frames /
+// samples (rt_get_accumulation) show that the history went on.
 //
 // --rays N: instead of the frame loop, ray queries against the generated world.  rt_trace_rays on N rays — seeded origins in the
 // region with random directions, or with --rays-coherent the primary rays of a --width x --height camera at the default pose handed
@@ -201,7 +206,7 @@ int main(int argc, char** argv) {
     int width = 1024, height = 1024;   // WINDOW_WIDTH / WINDOW_HEIGHT, src/render/constants.rs:9-10
     int spp = 1, depth = 2, frames = 240, device = 0, gpus = 1;
     bool gather = false, overlap = false, post = false, accumulate = false, edit_spread = false;
-    int edits = 0;
+    int edits = 0, edit_radius = 0;
     long long rays = 0;
     bool rays_coherent = false;
     bool reproject = false;
@@ -228,12 +233,14 @@ int main(int argc, char** argv) {
         else if (want("--frames-in-flight")) frames_in_flight = std::atoi(argv[++i]);
         else if (want("--edits")) edits = std::atoi(argv[++i]);
         else if (std::strcmp(argv[i], "--edit-spread") == 0) edit_spread = true;
+        else if (want("--edit-radius")) edit_radius = std::atoi(argv[++i]);
         else if (want("--rays")) rays = std::atoll(argv[++i]);
         else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
         else positional.push_back(argv[i]);
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
     if (edits < 0 || edits > (1 << 24)) { std::fprintf(stderr, "--edits must be in 0..2^24\n"); return 2; }
+    if (edit_radius != 0 && (!reproject || edits == 0)) { std::fprintf(stderr, "--edit-radius goes with --reproject --edits N\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
     if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
@@ -279,6 +286,7 @@ int main(int argc, char** argv) {
         RtConfig cfg = make_config(width, height, spp, depth, devices[(size_t)g], g, gpus, RT_FLAG_CACHE_PRIMARY | (accumulate ? RT_FLAG_ACCUMULATE : 0u) |
                                                                                                        (reproject ? RT_FLAG_REPROJECT : 0u) |
                                                                                                        (frames_in_flight == 2 ? RT_FLAG_FRAMES_IN_FLIGHT_2 : 0u));
+        cfg.edit_radius = edit_radius;
         pipes[(size_t)g] = rt::render::create_instance(cfg, noise.data(), game, &err);
         if (!pipes[(size_t)g]) {
             std::fprintf(stderr, "create_instance failed on device %d: %s\n", devices[(size_t)g], err.c_str());
@@ -404,13 +412,13 @@ int main(int argc, char** argv) {
         std::printf("{\"binary\": \"rt_bench\", \"config\": {\"width\": %d, \"height\": %d, \"spp\": %d, \"depth\": %d, \"gpus\": %d, "
                     "\"gather\": \"%s\", \"post_passes\": %s, \"pose\": [%g, %g, %g, %g, %g], \"sun_angle\": %g}, \"frames\": %d, \"rays_per_frame\": %llu, "
                     "\"ms_per_frame\": %.4f, \"avg_ms_last_120\": %.4f, \"max_ms_last_120\": %.4f, \"mrays_per_s\": %.2f, "
-                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"reproject\": %s, \"camera_step\": %g, \"samples\": %u, "
+                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"reproject\": %s, \"camera_step\": %g, \"samples\": %u, \"acc_frames\": %u, \"edit_radius\": %d, "
                     "\"edits\": %d, \"edit_spread\": %s, \"edit_device_ms_per_call\": %.4f, \"edit_launches_per_call\": %.1f, "
                     "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f}\n",
                     width, height, spp, depth, gpus, gather ? (overlap ? "rccl-overlapped" : "rccl-serial") : "none", post ? "true" : "false",
                     game.camera.origin[0], game.camera.origin[1], game.camera.origin[2], game.camera.heading, game.camera.pitch,
                     game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum,
-                    accumulate ? "true" : "false", reproject ? "true" : "false", (double)camera_step, acc_samples, edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
+                    accumulate ? "true" : "false", reproject ? "true" : "false", (double)camera_step, acc_samples, acc_frames, edit_radius, edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
                     edit_host_ms, edit_wall_ms);
     }
     for (int g = 0; g < gpus; g++) {

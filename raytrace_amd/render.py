@@ -24,7 +24,7 @@ class RtError(RuntimeError):
 
 
 def make_config(width, height, spp=1, depth=2, device=0, tile_rank=0, tile_world=1, kernel=RT_KERNEL_DEFAULT, flags=0,
-                region=256, history_cap=0):
+                region=256, history_cap=0, edit_radius=0):
     cfg = RtConfig()
     cfg.struct_size = C.sizeof(RtConfig)
     cfg.width, cfg.height, cfg.region = int(width), int(height), int(region)
@@ -32,6 +32,7 @@ def make_config(width, height, spp=1, depth=2, device=0, tile_rank=0, tile_world
     cfg.tile_rank, cfg.tile_world = int(tile_rank), int(tile_world)
     cfg.kernel, cfg.flags = int(kernel), int(flags)
     cfg.history_cap = int(history_cap)   # RT_FLAG_REPROJECT: 0 = the default (32)
+    cfg.edit_radius = int(edit_radius)   # RT_FLAG_REPROJECT: 0 = an edit restarts the history; 1..64 = only near the edit
     return cfg
 
 
@@ -368,6 +369,13 @@ class Context:
         out = np.empty((self.cfg.height, self.cfg.width), dtype=np.uint32)
         self._check(self._lib.rt_read_history(self._h, _p(out), out.nbytes))
         return out
+
+    def edit_boxes_pending(self):
+        """rt_edit_boxes_pending: (boxes, overflowed) — the edited boxes that wait for the next frame of a context with
+        edit_radius > 0, and whether the set overflowed so that the frame restarts (host-side state, no wait)."""
+        boxes, over = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.rt_edit_boxes_pending(self._h, C.byref(boxes), C.byref(over)))
+        return int(boxes.value), bool(over.value)
 
     def info(self):
         i = RtInfo()
