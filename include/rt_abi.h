@@ -176,7 +176,17 @@ typedef enum RtKernel {
                                        a frame that restarts anyway, or whose set overflowed, restarts as before and drops the boxes.
                                        Boxes are texels until that frame's lr places them in the world (a box cut by the window's seam
                                        covers the whole window on that axis).  Bounce light beyond the radius and sky occlusion are
-                                       not tested: they fade through history_cap.  DESIGN.md "Edits under a kept history".        */
+                                       not tested: they fade through history_cap.  DESIGN.md "Edits under a kept history".
+                                       RtConfig.stream_history = 1 keeps the history across rt_upload_slice and rt_generate_slice as
+                                       well: an accepted slab takes one of 4 pending slots (rt_slabs_pending), and the device records
+                                       per axis which texels hold an occupied voxel (minefield byte 0) of the slab just before and
+                                       just after it is written.  The next frame drawn consumes the slots like edit boxes: it places
+                                       what left with the previous frame's lr and what arrived with its own — per set bit, so that the
+                                       window's seam costs nothing — into at most 8 world boxes on the device (rt_read_slab_boxes) and
+                                       runs the moved pass with the same near / sun-shadow test against the frame's edit boxes, then
+                                       those.  A fifth slab empties the set and the next frame restarts.  One box per content is
+                                       conservative for a slab whose terrain is tall in one corner.  DESIGN.md "Slabs under a kept
+                                       history".                                                                                 */
 
 /*
  * RtConfig — replaces the compile-time window constants (constants.rs:9-10) and adds the
@@ -207,7 +217,11 @@ typedef struct RtConfig {
                                the history, and the next frame restarts only the pixels whose hit point lies within this many voxels
                                of an edited box or in the sun shadow of one; anything else RT_ERR_INVALID_ARG.  Ignored without
                                the flag. */
-    int32_t  reserved[3];
+    int32_t  stream_history;/* (was reserved[0]) RT_FLAG_REPROJECT: 0 = rt_upload_slice and rt_generate_slice restart the lighting
+                               history; 1 = they keep it, and the next frame restarts only the pixels near the occupied voxels that
+                               left or arrived or in their sun shadow — the test of edit_radius, which must then be 1..64; anything
+                               else RT_ERR_INVALID_ARG.  Ignored without the flag. */
+    int32_t  reserved[2];
 } RtConfig;
 
 /* Output planes. Bindings cited from shaders/glsl/raytrace.comp:14-21; formats from
@@ -304,7 +318,10 @@ int rt_upload_world(RtContext* ctx, const uint32_t* materials, const uint8_t* mi
  * re-tile of the one two before it — a host that uploads one slab per frame with one or two frames in flight never waits for
  * a frame; three slabs back to back behind a long frame do wait for it.  Without RT_FLAG_TRUSTED_WORLD the minefield
  * is checked first, on the host (values above 30 -> RT_ERR_INVALID_ARG); a rejected slab is NOT applied: the region and
- * what can be drawn stay as they were. */
+ * what can be drawn stay as they were.
+ * Accumulation: a slab resets RT_FLAG_ACCUMULATE's running sum — except on an RT_FLAG_REPROJECT context with
+ * RtConfig.stream_history = 1, where an accepted slab keeps the history and takes a pending slot for the next frame instead (two
+ * more launches per slab, each reading the slab's 16 R^2 minefield bytes) and a rejected one leaves history and slots alone. */
 int rt_upload_slice(RtContext* ctx, int axis, int texel_offset,
                     const uint32_t* materials, const uint8_t* minefield);
 
@@ -419,7 +436,8 @@ int rt_pick_pixels(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint3
  *     resident world: RT_ERR_NOT_READY.
  *   Ordering: asynchronous and stream-ordered like rt_upload_slice — after every frame already submitted on every lane and frame slot
  *     and after earlier queries; later frames, queries and edits see the new region; the host waits for nothing.  Works on a stream
- *     set with rt_set_stream and on tile-split contexts.  Resets RT_FLAG_ACCUMULATE's running sum.  rt_generate_world makes the world
+ *     set with rt_set_stream and on tile-split contexts.  Resets RT_FLAG_ACCUMULATE's running sum (rt_generate_slice: unless
+ *     RtConfig.stream_history keeps the history, as for rt_upload_slice).  rt_generate_world makes the world
  *     resident: a context may start from it with no rt_upload_world at all.
  * Device work per call: heights of the window's chunk columns, one workgroup per world chunk in the window that writes its voxels, one
  * launch that rebuilds the nibble-map words (counted by RT_FLAG_TIMING_ALL as one launch); scratch of (R + 64)^2 int32 on first use. */
@@ -555,6 +573,17 @@ int rt_read_history(RtContext* ctx, uint32_t* counts, size_t bytes);
  * rt_reset_accumulation drop both; the next frame consumes both.  Host-side state only: does not synchronise.  0 and 0 on a
  * context without the feature. */
 int rt_edit_boxes_pending(RtContext* ctx, uint32_t* boxes, uint32_t* overflowed);
+/* (ABI 1.3, additive; hosts detect the feature by this symbol) RtConfig.stream_history = 1: *slabs = the slabs that wait for the next
+ * rt_draw_frame (0..4; one per accepted rt_upload_slice / rt_generate_slice), *overflowed = 1 when a call would have needed a fifth
+ * slot, so that the set was emptied and the next frame restarts the history.  rt_upload_world, rt_generate_world, rt_upload_noise
+ * and rt_reset_accumulation drop both; the next frame consumes both; a rejected slab changes neither.  Host-side state only: does
+ * not synchronise.  0 and 0 on a context without the feature. */
+int rt_slabs_pending(RtContext* ctx, uint32_t* slabs, uint32_t* overflowed);
+/* (ABI 1.3, additive) The world boxes the pending slabs of the frame drawn last produced on the device: boxes[8][6] = lo x y z, hi
+ * x y z ([first voxel, last voxel + 1], per slab in call order what left, then what arrived; contents without an occupied voxel give
+ * none), *count = how many (0..8) — 0 when that frame had no pending slab or restarted.  Waits for the frame.  RT_ERR_INVALID_ARG on
+ * a context without the feature.  For tests, and for a host that wants to show the boxes. */
+int rt_read_slab_boxes(RtContext* ctx, float* boxes, uint32_t* count);
 
 int rt_get_counters(RtContext* ctx, RtCounters* out);
 int rt_reset_counters(RtContext* ctx);
@@ -583,7 +612,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RT_FLAG_REPROJECT, RtConfig.history_cap (was reserved[0]), rt_read_history (temporal
  *        reprojection of the accumulated lighting while the camera moves).
  *        Additive, same minor version: RtConfig.edit_radius (was reserved[0]), rt_edit_boxes_pending (the lighting history is kept
- *        across rt_edit_voxels and restarted only near an edit or in its sun shadow). */
+ *        across rt_edit_voxels and restarted only near an edit or in its sun shadow).
+ *        Additive, same minor version: RtConfig.stream_history (was reserved[0]), rt_slabs_pending, rt_read_slab_boxes (the lighting
+ *        history is kept across rt_upload_slice / rt_generate_slice and restarted only near what left or arrived). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -21,7 +21,7 @@ ABI_SYMBOLS = (
     "rt_frame_readback", "rt_selftest", "rt_get_info", "rt_samples_per_launch", "rt_get_gather_timing",
     "rt_reset_accumulation", "rt_get_accumulation", "rt_edit_voxels", "rt_read_box",
     "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels", "rt_generate_world", "rt_generate_slice", "rt_read_history",
-    "rt_edit_boxes_pending",
+    "rt_edit_boxes_pending", "rt_slabs_pending", "rt_read_slab_boxes",
 )
 
 _amd = None
@@ -106,6 +106,10 @@ def amd():
         lib.rt_read_history.restype = C.c_int
         lib.rt_edit_boxes_pending.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.rt_edit_boxes_pending.restype = C.c_int
+        lib.rt_slabs_pending.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.rt_slabs_pending.restype = C.c_int
+        lib.rt_read_slab_boxes.argtypes = [P, P, C.POINTER(C.c_uint32)]
+        lib.rt_read_slab_boxes.restype = C.c_int
         lib.rt_edit_voxels.argtypes = [P, C.POINTER(RtVoxelEdit), C.c_uint32]
         lib.rt_edit_voxels.restype = C.c_int
         lib.rt_read_box.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]

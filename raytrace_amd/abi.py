@@ -77,12 +77,13 @@ assert C.sizeof(RtUniforms) == 192
 
 
 class _RtConfigTailFields(C.Structure):
-    _fields_ = [("edit_radius", C.c_int32), ("reserved3", C.c_int32 * 3)]
+    _fields_ = [("edit_radius", C.c_int32), ("stream_history", C.c_int32), ("reserved2", C.c_int32 * 2)]
 
 
 class _RtConfigTail(C.Union):
-    """The last 16 bytes of RtConfig: the header's `edit_radius; reserved[3]` (ABI 1.3, additive: edit_radius took the first
-    reserved word), and `reserved`, the four words seen whole as callers written before that knew them (reserved[0] IS edit_radius)."""
+    """The last 16 bytes of RtConfig: the header's `edit_radius; stream_history; reserved[2]` (ABI 1.3, additive: each took the first
+    reserved word of its time), and `reserved`, the four words seen whole as callers written before that knew them (reserved[0] IS
+    edit_radius, reserved[1] IS stream_history)."""
     _anonymous_ = ("named",)
     _fields_ = [("named", _RtConfigTailFields), ("reserved", C.c_int32 * 4)]
 

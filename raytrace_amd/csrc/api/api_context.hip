@@ -218,6 +218,11 @@ int create_persistent(RtContext* c) {
             RT_HIP(c, hipMemset(c->d_hist_rec[h], 0, (size_t)c->npix_pad * sizeof(uint2)));   // rt_read_history before the first frame
         }
     }
+    if (c->stream_history) {
+        RT_HIP(c, dev_alloc(c, &c->d_slab_masks, (size_t)rtd::kSlabSlots * rtd::kSlabSlotWords));
+        RT_HIP(c, dev_alloc(c, &c->d_slab_boxes, 1));
+        RT_HIP(c, hipMemset(c->d_slab_boxes, 0, sizeof(rtd::SlabBoxes)));
+    }
     RT_HIP(c, rtd::launch_sphere_lut(c->sphere_lut, c->own_stream));
     RT_HIP(c, rtd::launch_dif_lut(c->sphere_lut, c->dif_lut, c->own_stream));
     RT_HIP(c, hipStreamSynchronize(c->own_stream));
@@ -294,6 +299,10 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
             return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: history_cap must be 0 (the default, 32) or 1..65535");
         if (cfg->edit_radius < 0 || cfg->edit_radius > 64)
             return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: edit_radius must be 0 (an edit restarts the history) or 1..64");
+        if (cfg->stream_history != 0 && cfg->stream_history != 1)
+            return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: stream_history must be 0 (a slab restarts the history) or 1");
+        if (cfg->stream_history == 1 && cfg->edit_radius < 1)
+            return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: stream_history = 1 needs edit_radius in 1..64 (its near test uses it)");
         if (cfg->spp != 1 || cfg->tile_world != 1)
             return fail(nullptr, RT_ERR_UNIMPLEMENTED, "rt_create: RT_FLAG_REPROJECT needs one-sample whole frames (spp == 1, tile_world == 1)");
     }
@@ -318,6 +327,7 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
     c->reproject = (cfg->flags & RT_FLAG_REPROJECT) != 0;
     c->history_cap = cfg->history_cap > 0 ? (uint32_t)cfg->history_cap : 32u;
     c->edit_radius = c->reproject ? (uint32_t)cfg->edit_radius : 0u;   // (ignored without the flag, like history_cap)
+    c->stream_history = c->reproject && cfg->stream_history == 1;      // (likewise)
 
     // tiling: 8x8-pixel tiles dealt round-robin over tile_world contexts
     c->tiles_x = (cfg->width + 7) / 8; c->tiles_y = (cfg->height + 7) / 8;

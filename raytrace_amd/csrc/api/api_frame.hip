@@ -156,6 +156,8 @@ struct PersistFrame {
     int temporal_mode = rtd::TEMPORAL_RESTART;   // RT_FLAG_REPROJECT: how this frame's pass treats the history
     uint32_t nbox = 0;                  // RtConfig.edit_radius > 0: the edited boxes this frame consumed, in world coordinates
     rtd::TemporalBox boxes[rtd::kTemporalMaxBoxes];
+    uint32_t nslab = 0;                 // RtConfig.stream_history: the pending slabs this frame consumed (mask slots 0 .. nslab - 1)
+    int32_t lr_prev[3] = {}, lr[3] = {};   // ... and the lr that places what left (the previous frame's) and what arrived (this one's)
 };
 
 // A pending texel box in the world coordinates of a frame with render offset lr: w = lr - R/2 + (t - lr) mod R per axis
@@ -217,6 +219,13 @@ hipError_t frame_begin(RtContext* c, PersistFrame& p, const RtUniforms* u, bool 
     for (uint32_t b = 0; b < p.nbox; b++) p.boxes[b] = world_box(c->edit_boxes[b], u->lr, c->region);
     c->edit_nbox = 0;
     c->edit_overflow = false;
+    // (pending slabs likewise; their boxes are made on the device, in front of the pass)
+    if (c->slab_overflow) c->accum_valid = false;
+    p.nslab = c->slab_pending;
+    memcpy(p.lr_prev, &c->accum_key[13], 12); memcpy(p.lr, u->lr, 12);
+    c->slab_pending = 0;
+    c->slab_overflow = false;
+    c->slab_boxes_drawn = false;
     p.accum_cont = p.accum && c->accum_valid && memcmp(p.key, c->accum_key, sizeof(p.key)) == 0 && c->accum_samples + spp <= (1ull << 24);
     p.accum_n = p.accum_cont ? c->accum_samples + spp : spp;
     p.accum_multi = p.accum && spp > 1u ? c->d_accum : nullptr;
@@ -231,7 +240,9 @@ hipError_t frame_begin(RtContext* c, PersistFrame& p, const RtUniforms* u, bool 
         // pending boxes and a history that goes on: the moved pass with the box test — also under an unchanged camera, where it
         // projects into the same camera.  (A frame that restarts anyway drops them.)
         if (p.temporal_mode != rtd::TEMPORAL_RESTART && p.nbox > 0u) p.temporal_mode = rtd::TEMPORAL_MOVED_BOXES;
-        if (p.temporal_mode == rtd::TEMPORAL_MOVED || p.temporal_mode == rtd::TEMPORAL_MOVED_BOXES) {
+        // pending slabs and a history that goes on: the same, with the slab boxes behind the edit boxes (of which there may be none)
+        if (p.temporal_mode != rtd::TEMPORAL_RESTART && p.nslab > 0u) p.temporal_mode = rtd::TEMPORAL_MOVED_SLABS;
+        if (p.temporal_mode != rtd::TEMPORAL_RESTART && p.temporal_mode != rtd::TEMPORAL_STILL) {
             p.accum_cont = true;
             p.accum_n = (c->accum_samples < c->history_cap ? c->accum_samples : (uint64_t)c->history_cap) + 1u;
         }
@@ -381,13 +392,19 @@ hipError_t frame_accumulate_tail(RtContext* c, PersistFrame& p) {
             memcpy(ta.origin, &c->accum_key[1], 12); memcpy(ta.forward, &c->accum_key[4], 12);
             memcpy(ta.up, &c->accum_key[7], 12); memcpy(ta.right, &c->accum_key[10], 12);
             ta.cap = c->history_cap;
-            if (p.temporal_mode == rtd::TEMPORAL_MOVED_BOXES) {
+            if (p.temporal_mode == rtd::TEMPORAL_MOVED_SLABS) {
+                // (behind the previous frame's pass, which read the boxes of ITS slabs: ev_accum above, or stream order)
+                e = rtd::launch_place_slab_boxes(c->d_slab_masks, p.nslab, p.lr_prev, p.lr, c->logr, c->d_slab_boxes, p.tail);
+                ta.slab = c->d_slab_boxes;
+                c->slab_boxes_drawn = e == hipSuccess;
+            }
+            if (p.temporal_mode == rtd::TEMPORAL_MOVED_BOXES || p.temporal_mode == rtd::TEMPORAL_MOVED_SLABS) {
                 ta.nbox = p.nbox;
                 memcpy(ta.box, p.boxes, sizeof(ta.box));
                 ta.r2 = (float)(c->edit_radius * c->edit_radius);
                 for (int k = 0; k < 3; k++) { ta.sun[k] = p.f.sunangle[k]; ta.inv_sun[k] = 1.0f / p.f.sunangle[k]; }
             }
-            e = rtd::launch_temporal_frame(p.f, p.pl, ta, p.temporal_mode, p.tail);
+            if (e == hipSuccess) e = rtd::launch_temporal_frame(p.f, p.pl, ta, p.temporal_mode, p.tail);
             c->hist_cur = next;
         }
     }
@@ -467,6 +484,29 @@ int rt_edit_boxes_pending(RtContext* ctx, uint32_t* boxes, uint32_t* overflowed)
     if (!boxes || !overflowed) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_boxes_pending: null pointer");
     *boxes = ctx->edit_nbox;
     *overflowed = ctx->edit_overflow ? 1u : 0u;
+    return RT_OK;
+}
+
+int rt_slabs_pending(RtContext* ctx, uint32_t* slabs, uint32_t* overflowed) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!slabs || !overflowed) return fail(ctx, RT_ERR_INVALID_ARG, "rt_slabs_pending: null pointer");
+    *slabs = ctx->slab_pending;
+    *overflowed = ctx->slab_overflow ? 1u : 0u;
+    return RT_OK;
+}
+
+int rt_read_slab_boxes(RtContext* ctx, float* boxes, uint32_t* count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!ctx->stream_history) return fail(ctx, RT_ERR_INVALID_ARG, "rt_read_slab_boxes: the context was created without RtConfig.stream_history");
+    if (!boxes || !count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_read_slab_boxes: null pointer");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, sync_lanes(ctx));
+    *count = 0;
+    if (!ctx->slab_boxes_drawn) return RT_OK;   // (the frame drawn last had no pending slab, or restarted)
+    rtd::SlabBoxes b;
+    RT_HIP(ctx, hipMemcpy(&b, ctx->d_slab_boxes, sizeof(b), hipMemcpyDeviceToHost));
+    *count = b.count <= rtd::kSlabMaxBoxes ? b.count : rtd::kSlabMaxBoxes;
+    memcpy(boxes, b.box, (size_t)*count * sizeof(rtd::TemporalBox));
     return RT_OK;
 }
 

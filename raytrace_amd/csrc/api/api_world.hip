@@ -47,6 +47,30 @@ hipError_t staging_applied(RtContext* c, StagingSet& s) {
     return e == hipSuccess ? world_change_end(c) : e;
 }
 
+// ---- RtConfig.stream_history: a slab that keeps the lighting history ------------------------------------------------------------
+// An accepted slab takes the next pending slot, or — a fifth — empties the set and marks it overflowed; returns the slot's masks
+// (old set, then new), or null where nothing is to be scanned.  Called once nothing can reject the slab any more.
+uint32_t* slab_take_slot(RtContext* c) {
+    if (!c->stream_history) { restart_history(c); return nullptr; }
+    if (c->slab_overflow) return nullptr;
+    if (c->slab_pending == rtd::kSlabSlots) { c->slab_pending = 0; c->slab_overflow = true; return nullptr; }
+    return c->d_slab_masks + (size_t)rtd::kSlabSlotWords * c->slab_pending++;
+}
+// inside world_change_begin / world_change_end, in front of the launch that writes the slab: the slot is cleared, then what the
+// slab holds now is scanned into its old set
+hipError_t slab_scan_old(RtContext* c, uint32_t* masks, int axis, int offset) {
+    if (!masks) return hipSuccess;
+    hipError_t e = hipMemsetAsync(masks, 0, rtd::kSlabSlotWords * sizeof(uint32_t), c->stream);
+    LaunchTimer t(c, 1);
+    return e == hipSuccess ? rtd::launch_slab_occupancy(c->d_mine_sw, c->logr, axis, offset, masks, c->stream) : e;
+}
+// ... and behind it: what arrived, into the new set
+hipError_t slab_scan_new(RtContext* c, uint32_t* masks, int axis, int offset) {
+    if (!masks) return hipSuccess;
+    LaunchTimer t(c, 1);
+    return rtd::launch_slab_occupancy(c->d_mine_sw, c->logr, axis, offset, masks + rtd::kSlabSetWords, c->stream);
+}
+
 int reflatten(RtContext* c, const uint8_t* d_mine_lin, const uint32_t* d_mat_lin) {
     RT_HIP(c, hipMemsetAsync(c->d_flag, 0, sizeof(uint32_t), c->stream));
     RT_HIP(c, rtd::launch_flatten(d_mine_lin, d_mat_lin, c->d_mine_sw, c->d_mat_sw, c->d_coarse, c->d_brick, c->d_flag, c->logr, c->stream));
@@ -72,13 +96,18 @@ int generate_terrain(RtContext* c, uint64_t seed, const int64_t lo[3], int axis)
         const size_t cols = (size_t)(c->region + RT_CHUNK_SIZE) * (size_t)(c->region + RT_CHUNK_SIZE);
         RT_HIP(c, dev_alloc(c, &c->d_heights, cols));
     }
-    restart_history(c);
+    // (a whole region restarts the history; a slab does unless the context keeps it: RtConfig.stream_history)
+    uint32_t* masks = nullptr;
+    if (axis < 0) restart_history(c); else masks = slab_take_slot(c);
+    const int offset = axis < 0 ? 0 : (int)((lo[axis] + c->region / 2) & (int64_t)(c->region - 1));
     invalidate_prepass(c);
     RT_HIP(c, world_change_begin(c));
+    RT_HIP(c, slab_scan_old(c, masks, axis, offset));
     {
         LaunchTimer t(c, 1);
         RT_HIP(c, rtd::launch_terrain(c->d_mine_sw, c->d_mat_sw, c->d_coarse, c->d_brick, c->d_heights, c->logr, seed, lo, axis, c->stream));
     }
+    RT_HIP(c, slab_scan_new(c, masks, axis, offset));
     RT_HIP(c, world_change_end(c));
     return RT_OK;
 }
@@ -134,7 +163,8 @@ int rt_slice_staging(RtContext* ctx, uint32_t** materials, uint8_t** minefield) 
 int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* materials, const uint8_t* minefield) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     if (!materials || !minefield) return fail(ctx, RT_ERR_INVALID_ARG, "rt_upload_slice: null pointer");
-    restart_history(ctx);
+    // (RtConfig.stream_history: the history, and the slabs that wait, change only once the slab is accepted)
+    if (!ctx->stream_history) restart_history(ctx);
     invalidate_prepass(ctx);
     const size_t kR = (size_t)ctx->region;
     if (axis < 0 || axis > 2 || texel_offset < 0 || texel_offset + RT_SLICE_SIZE > ctx->region || texel_offset % RT_SLICE_SIZE != 0)
@@ -163,12 +193,15 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
     if (materials != h_mat) memcpy(h_mat, materials, n * sizeof(uint32_t));   // borrowed buffers are released at return;
     if (minefield != h_mine) memcpy(h_mine, minefield, n);                     // rt_slice_staging's pointers need no copy
     ctx->slabs++;
+    uint32_t* masks = ctx->stream_history ? slab_take_slot(ctx) : nullptr;
     RT_HIP(ctx, staging_send(ctx, s, 5 * n));
+    RT_HIP(ctx, slab_scan_old(ctx, masks, axis, texel_offset));
     {
         LaunchTimer t(ctx, 1);
         RT_HIP(ctx, rtd::launch_flatten_slab(s.dev + 4 * n, reinterpret_cast<const uint32_t*>(s.dev), ctx->d_mine_sw, ctx->d_mat_sw,
                                              ctx->d_coarse, ctx->d_brick, ctx->logr, axis, texel_offset, ctx->stream));
     }
+    RT_HIP(ctx, slab_scan_new(ctx, masks, axis, texel_offset));
     RT_HIP(ctx, staging_applied(ctx, s));
     return RT_OK;
 }

@@ -291,6 +291,17 @@ struct __attribute__((visibility("hidden"))) RtContext {
     rta::EditBox edit_boxes[rtd::kTemporalMaxBoxes];
     uint32_t edit_nbox = 0;
     bool edit_overflow = false;
+    // RtConfig.stream_history (with RT_FLAG_REPROJECT and edit_radius > 0): rt_upload_slice and rt_generate_slice keep the history.
+    // An accepted slab takes the next of rtd::kSlabSlots mask slots — cleared and scanned in stream order round the launch that
+    // writes the slab (rt_slab.hip) — and the next frame drawn consumes the pending slots: k_place_slab_boxes, then the moved pass
+    // with the slab boxes.  A slot is written again only by a later slab call, whose launches follow every frame submitted before
+    // it on every lane (world_change_begin), the frame that consumed the slot among them.
+    bool stream_history = false;
+    uint32_t* d_slab_masks = nullptr;   // kSlabSlots x kSlabSlotWords
+    rtd::SlabBoxes* d_slab_boxes = nullptr;   // the frame's pass reads it behind k_place_slab_boxes, on the stream of both
+    uint32_t slab_pending = 0;          // slots 0 .. slab_pending - 1 wait for the next frame, in call order
+    bool slab_overflow = false;         // a fifth slab came: the set was emptied and the next frame restarts
+    bool slab_boxes_drawn = false;      // the frame drawn last placed boxes (rt_read_slab_boxes reads them)
 
     // ray queries (rt_trace_rays, rt_pick_pixels): a stream of their own (the device's highest priority), so that a query waits for
     // the world changes before it (ev_world) and not for the frames; the world changes wait for the queries before them (ev_query)
@@ -304,11 +315,13 @@ namespace rta __attribute__((visibility("hidden"))) {
 extern thread_local std::string g_create_error;   // rt_last_error(NULL): why the last rt_create of this thread failed
 
 // What restarts the accumulation / the history outright (uploads, generated terrain, new noise, rt_reset_accumulation): the next
-// frame starts from zero, and edit boxes still waiting for it mean nothing any more.
+// frame starts from zero, and edit boxes and slabs still waiting for it mean nothing any more.
 inline void restart_history(RtContext* c) {
     c->accum_valid = false;
     c->edit_nbox = 0;
     c->edit_overflow = false;
+    c->slab_pending = 0;
+    c->slab_overflow = false;
 }
 
 inline int fail(RtContext* c, int code, const std::string& msg) {

@@ -171,9 +171,24 @@ hipError_t launch_query(const Scene& sc, const Frame& f, const QueryArgs& a, hip
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
 // (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
 // or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)
-enum { TEMPORAL_RESTART = 0, TEMPORAL_STILL = 1, TEMPORAL_MOVED = 2, TEMPORAL_MOVED_BOXES = 3 };
+// (TEMPORAL_MOVED_SLABS: a moved frame after rt_upload_slice / rt_generate_slice on a context with RtConfig.stream_history — the
+// test of TEMPORAL_MOVED_BOXES against the frame's edit boxes, 0..kTemporalMaxBoxes of them, and then against the boxes
+// k_place_slab_boxes left in device memory)
+enum { TEMPORAL_RESTART = 0, TEMPORAL_STILL = 1, TEMPORAL_MOVED = 2, TEMPORAL_MOVED_BOXES = 3, TEMPORAL_MOVED_SLABS = 4 };
 constexpr uint32_t kTemporalMaxBoxes = 16;
 struct TemporalBox { float lo[3], hi[3]; };   // world coordinates, [first voxel, last voxel + 1] per axis
+// rt_slab.hip: RtConfig.stream_history.  A pending slab owns one of kSlabSlots mask slots: two sets (what the slab held just before
+// it was written, what it holds just after), each three rows of kSlabMaskWords words — bit t of row a is set when an occupied voxel
+// (minefield byte 0) of the slab has coordinate t on axis a.  k_place_slab_boxes turns the pending slots into world boxes.
+constexpr uint32_t kSlabSlots = 4, kSlabMaskWords = 32, kSlabSetWords = 3 * kSlabMaskWords, kSlabSlotWords = 2 * kSlabSetWords;
+constexpr uint32_t kSlabMaxBoxes = 2 * kSlabSlots;
+struct SlabBoxes { uint32_t count, pad[3]; TemporalBox box[kSlabMaxBoxes]; };
+// ORs the occupancy of the 16-thick slab at texel `offset` of `axis` into masks[kSlabSetWords] (cleared by the caller)
+hipError_t launch_slab_occupancy(const uint8_t* mine_sw, int logr, int axis, int offset, uint32_t* masks, hipStream_t st);
+// slots 0..nslots-1 of masks (kSlabSlotWords each), in order: the old set placed with lr_prev, the new one with lr_cur; w(t) =
+// lr - R/2 + (t - lr) mod R per set bit, the box [min w, max w + 1] per axis; a set without a bit gives no box
+hipError_t launch_place_slab_boxes(const uint32_t* masks, uint32_t nslots, const int32_t lr_prev[3], const int32_t lr_cur[3], int logr,
+                                   SlabBoxes* out, hipStream_t st);
 struct TemporalArgs {
     const float4* prev_sum;   // the history set the previous frame's pass wrote: sums by row-major pixel ...
     const uint2* prev_rec;    // ... and (depth_f32 bits, count | normal << 27)
@@ -186,6 +201,8 @@ struct TemporalArgs {
     TemporalBox box[kTemporalMaxBoxes];
     float r2;                 // (float)(edit_radius^2)
     float sun[3], inv_sun[3]; // Frame::sunangle and 1.0f / it, divided on the host
+    // TEMPORAL_MOVED_SLABS only (appended likewise)
+    const SlabBoxes* slab;    // what k_place_slab_boxes wrote in front of this launch, in stream order
 };
 hipError_t launch_temporal_frame(const Frame& f, const Planes& planes, const TemporalArgs& a, int mode, hipStream_t st);
 

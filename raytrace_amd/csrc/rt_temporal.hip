@@ -15,6 +15,9 @@
 //                       against every edited box (kernel arguments: wave-uniform scalar loads, no LDS) — within edit_radius of
 //                       the box, or on a ray from P towards the sun that meets the box grown by 1 (edit_touches) — and a pixel
 //                       that is near or shadowed restarts; every other pixel goes on exactly as in TEMPORAL_MOVED.
+//     TEMPORAL_MOVED_SLABS  a moved frame after streamed slabs (RtConfig.stream_history): TEMPORAL_MOVED_BOXES' test against the frame's
+//                       edit boxes (there may be none), then against the boxes k_place_slab_boxes (rt_slab.hip) wrote in front
+//                       of this launch — their count and bounds are wave-uniform loads from device memory, same arithmetic.
 //   L = 16 x lighting_f32 of the frame just drawn (exact); the lighting planes become store_lighting(sum, n).
 //
 // All fp32, every operation rounded on its own (-ffp-contract=off); only the two normalizes fuse, as primary_ray's does: the CPU
@@ -74,6 +77,24 @@ __device__ __forceinline__ bool edit_touches(const TemporalArgs& a, vec3 P) {
     return touched;
 }
 
+// TEMPORAL_MOVED_SLABS: the same test against the boxes in device memory
+__device__ __forceinline__ bool slab_touches(const TemporalArgs& a, vec3 P) {
+    const SlabBoxes* __restrict__ s = a.slab;
+    const uint32_t nbox = s->count;
+    bool touched = false;
+    for (uint32_t b = 0; b < nbox; b++) {
+        const TemporalBox x = s->box[b];
+        float tn = -__builtin_inff(), tf = __builtin_inff();
+        bool miss = false;
+        const float dx = edit_axis(x.lo[0], x.hi[0], P.x, a.sun[0], a.inv_sun[0], tn, tf, miss);
+        const float dy = edit_axis(x.lo[1], x.hi[1], P.y, a.sun[1], a.inv_sun[1], tn, tf, miss);
+        const float dz = edit_axis(x.lo[2], x.hi[2], P.z, a.sun[2], a.inv_sun[2], tn, tf, miss);
+        const float dist2 = (dx * dx + dy * dy) + dz * dz;
+        touched = touched || dist2 <= a.r2 || (!miss && tn <= tf && tf > 0.0f);
+    }
+    return touched;
+}
+
 }  // namespace
 
 template <int MODE>
@@ -99,12 +120,14 @@ __global__ __launch_bounds__(kTemporalWg) void k_temporal_frame(Frame f, Planes 
             dep = planes.depth_f32[i];
             nrm = (uint32_t)planes.normal_r8[i];
         }
-        if ((MODE == TEMPORAL_MOVED || MODE == TEMPORAL_MOVED_BOXES) && nrm < 6u && dep < 65535.0f) {
+        if ((MODE == TEMPORAL_MOVED || MODE == TEMPORAL_MOVED_BOXES || MODE == TEMPORAL_MOVED_SLABS) && nrm < 6u && dep < 65535.0f) {
             const vec3 o = ld3(f.origin), o1 = ld3(a.origin), f1 = ld3(a.forward), r1 = ld3(a.right), u1 = ld3(a.up);
             const uint32_t px = i % W, py = i / W;
             const vec3 d = pixel_dir(ld3(f.forward), ld3(f.right), ld3(f.up), (float)px, (float)py, fw, fh);
             const vec3 P = vadd(o, vscale(d, dep / 32.0f));
-            if (MODE != TEMPORAL_MOVED_BOXES || !edit_touches(a, P)) {
+            const bool touched = MODE == TEMPORAL_MOVED_BOXES ? edit_touches(a, P)
+                                 : MODE == TEMPORAL_MOVED_SLABS ? (edit_touches(a, P) || slab_touches(a, P)) : false;
+            if (!touched) {
                 const vec3 v = vsub(P, o1);
                 const float along = dotp(v, f1) / dotp(f1, f1);
                 const float sx = (dotp(v, r1) / dotp(r1, r1)) / along;
@@ -154,6 +177,10 @@ hipError_t launch_temporal_frame(const Frame& f, const Planes& planes, const Tem
     else if (mode == TEMPORAL_MOVED_BOXES) {
         if (a.nbox < 1u || a.nbox > kTemporalMaxBoxes) return hipErrorInvalidValue;
         hipLaunchKernelGGL((k_temporal_frame<TEMPORAL_MOVED_BOXES>), grid, block, 0, st, f, planes, a);
+    }
+    else if (mode == TEMPORAL_MOVED_SLABS) {
+        if (a.nbox > kTemporalMaxBoxes || a.slab == nullptr) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_temporal_frame<TEMPORAL_MOVED_SLABS>), grid, block, 0, st, f, planes, a);
     }
     else return hipErrorInvalidValue;
     return hipGetLastError();

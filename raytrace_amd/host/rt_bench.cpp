@@ -7,6 +7,7 @@
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
 //            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
 //            [--reproject] [--camera-step DX] [--frames-in-flight N] [--edits N [--edit-spread]] [--edit-radius N]
+//            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
@@ -38,6 +39,12 @@
 // --edit-radius N (with --reproject --edits N): RtConfig.edit_radius — the edits no longer restart the lighting history; every frame
 // runs the moved pass with the edited boxes and restarts only the pixels near one or in its sun shadow.  The JSON line's acc_frames /
 // samples (rt_get_accumulation) show that the history went on.
+//
+// --stream (one device): the terrain streams as --camera-step moves the camera — Pipeline::enable_terrain_streaming(seed, "", true),
+// one rt_generate_slice per frame while the window lags the camera, lr following.  With --reproject every slab restarts the
+// lighting history unless --stream-history (with --edit-radius N) sets RtConfig.stream_history: then a frame after a slab restarts
+// only the pixels near the occupied voxels that left or arrived or in their sun shadow.  The JSON line's acc_frames / samples
+// (rt_get_accumulation) show whether the history went on.
 //
 // --rays N: instead of the frame loop, ray queries against the generated world.  rt_trace_rays on N rays — seeded origins in the
 // region with random directions, or with --rays-coherent the primary rays of a --width x --height camera at the default pose handed
@@ -209,7 +216,7 @@ int main(int argc, char** argv) {
     int edits = 0, edit_radius = 0;
     long long rays = 0;
     bool rays_coherent = false;
-    bool reproject = false;
+    bool reproject = false, stream = false, stream_history = false;
     float camera_step = 0.0f;
     int frames_in_flight = 1;      // 2: RT_FLAG_FRAMES_IN_FLIGHT_2 and no fence between frames (bench.py's default), one device
     std::string noise_path = "tests/golden/blue_noise_512.rgba";
@@ -234,13 +241,17 @@ int main(int argc, char** argv) {
         else if (want("--edits")) edits = std::atoi(argv[++i]);
         else if (std::strcmp(argv[i], "--edit-spread") == 0) edit_spread = true;
         else if (want("--edit-radius")) edit_radius = std::atoi(argv[++i]);
+        else if (std::strcmp(argv[i], "--stream") == 0) stream = true;
+        else if (std::strcmp(argv[i], "--stream-history") == 0) stream_history = true;
         else if (want("--rays")) rays = std::atoll(argv[++i]);
         else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
         else positional.push_back(argv[i]);
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
     if (edits < 0 || edits > (1 << 24)) { std::fprintf(stderr, "--edits must be in 0..2^24\n"); return 2; }
-    if (edit_radius != 0 && (!reproject || edits == 0)) { std::fprintf(stderr, "--edit-radius goes with --reproject --edits N\n"); return 2; }
+    if (edit_radius != 0 && (!reproject || (edits == 0 && !stream_history))) { std::fprintf(stderr, "--edit-radius goes with --reproject and --edits N or --stream-history\n"); return 2; }
+    if (stream && gpus > 1) { std::fprintf(stderr, "--stream needs one device\n"); return 2; }
+    if (stream_history && (!stream || !reproject || edit_radius == 0)) { std::fprintf(stderr, "--stream-history goes with --stream --reproject --edit-radius N\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
     if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
@@ -287,12 +298,14 @@ int main(int argc, char** argv) {
                                                                                                        (reproject ? RT_FLAG_REPROJECT : 0u) |
                                                                                                        (frames_in_flight == 2 ? RT_FLAG_FRAMES_IN_FLIGHT_2 : 0u));
         cfg.edit_radius = edit_radius;
+        cfg.stream_history = stream_history ? 1 : 0;
         pipes[(size_t)g] = rt::render::create_instance(cfg, noise.data(), game, &err);
         if (!pipes[(size_t)g]) {
             std::fprintf(stderr, "create_instance failed on device %d: %s\n", devices[(size_t)g], err.c_str());
             return 1;
         }
         pipes[(size_t)g]->set_frames_in_flight(frames_in_flight);
+        if (stream) pipes[(size_t)g]->enable_terrain_streaming(0x5EED, "", true);   // (the seed of game.generate_world above)
     }
     if (post && pipes[0]->enable_post_passes(true) != RT_OK) { std::fprintf(stderr, "enable_post_passes failed\n"); return 1; }
     if (gather) {
@@ -412,13 +425,13 @@ int main(int argc, char** argv) {
         std::printf("{\"binary\": \"rt_bench\", \"config\": {\"width\": %d, \"height\": %d, \"spp\": %d, \"depth\": %d, \"gpus\": %d, "
                     "\"gather\": \"%s\", \"post_passes\": %s, \"pose\": [%g, %g, %g, %g, %g], \"sun_angle\": %g}, \"frames\": %d, \"rays_per_frame\": %llu, "
                     "\"ms_per_frame\": %.4f, \"avg_ms_last_120\": %.4f, \"max_ms_last_120\": %.4f, \"mrays_per_s\": %.2f, "
-                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"reproject\": %s, \"camera_step\": %g, \"samples\": %u, \"acc_frames\": %u, \"edit_radius\": %d, "
+                    "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"reproject\": %s, \"camera_step\": %g, \"samples\": %u, \"acc_frames\": %u, \"edit_radius\": %d, \"stream\": %s, \"stream_history\": %s, "
                     "\"edits\": %d, \"edit_spread\": %s, \"edit_device_ms_per_call\": %.4f, \"edit_launches_per_call\": %.1f, "
                     "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f}\n",
                     width, height, spp, depth, gpus, gather ? (overlap ? "rccl-overlapped" : "rccl-serial") : "none", post ? "true" : "false",
                     game.camera.origin[0], game.camera.origin[1], game.camera.origin[2], game.camera.heading, game.camera.pitch,
                     game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum,
-                    accumulate ? "true" : "false", reproject ? "true" : "false", (double)camera_step, acc_samples, acc_frames, edit_radius, edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
+                    accumulate ? "true" : "false", reproject ? "true" : "false", (double)camera_step, acc_samples, acc_frames, edit_radius, stream ? "true" : "false", stream_history ? "true" : "false", edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
                     edit_host_ms, edit_wall_ms);
     }
     for (int g = 0; g < gpus; g++) {

@@ -24,7 +24,7 @@ class RtError(RuntimeError):
 
 
 def make_config(width, height, spp=1, depth=2, device=0, tile_rank=0, tile_world=1, kernel=RT_KERNEL_DEFAULT, flags=0,
-                region=256, history_cap=0, edit_radius=0):
+                region=256, history_cap=0, edit_radius=0, stream_history=0):
     cfg = RtConfig()
     cfg.struct_size = C.sizeof(RtConfig)
     cfg.width, cfg.height, cfg.region = int(width), int(height), int(region)
@@ -33,6 +33,7 @@ def make_config(width, height, spp=1, depth=2, device=0, tile_rank=0, tile_world
     cfg.kernel, cfg.flags = int(kernel), int(flags)
     cfg.history_cap = int(history_cap)   # RT_FLAG_REPROJECT: 0 = the default (32)
     cfg.edit_radius = int(edit_radius)   # RT_FLAG_REPROJECT: 0 = an edit restarts the history; 1..64 = only near the edit
+    cfg.stream_history = int(stream_history)   # RT_FLAG_REPROJECT: 0 = a slab restarts the history; 1 = only near what left or arrived
     return cfg
 
 
@@ -376,6 +377,21 @@ class Context:
         boxes, over = C.c_uint32(0), C.c_uint32(0)
         self._check(self._lib.rt_edit_boxes_pending(self._h, C.byref(boxes), C.byref(over)))
         return int(boxes.value), bool(over.value)
+
+    def slabs_pending(self):
+        """rt_slabs_pending: (slabs, overflowed) — the slabs that wait for the next frame of a context with stream_history = 1, and
+        whether the set overflowed so that the frame restarts (host-side state, no wait)."""
+        slabs, over = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.rt_slabs_pending(self._h, C.byref(slabs), C.byref(over)))
+        return int(slabs.value), bool(over.value)
+
+    def read_slab_boxes(self):
+        """rt_read_slab_boxes: float32 [count, 2, 3] — (lo, hi) of the world boxes the pending slabs of the frame drawn last
+        produced, in order; count = 0 when that frame had none or restarted.  Waits for the frame."""
+        out = np.zeros((8, 2, 3), dtype=np.float32)
+        n = C.c_uint32(0)
+        self._check(self._lib.rt_read_slab_boxes(self._h, _p(out), C.byref(n)))
+        return out[:int(n.value)].copy()
 
     def info(self):
         i = RtInfo()
