@@ -419,6 +419,64 @@ int rt_trace_rays_async(RtContext* ctx, const RtRay* rays_dev, uint32_t count, c
  * are read.  Host pointers, synchronous. */
 int rt_pick_pixels(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint32_t count, RtRayHit* hits);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Light probes: path-traced light at arbitrary points of the resident
+ * region — what lights an entity, a particle, a held item or an irradiance grid, and "is this spot in the sun?".  The whole light
+ * loop of the shader's non-air branch (raytrace.comp:317-350: shadow ray, diffuse bounce, sky, albedo chain, noise addressing) runs
+ * on the device, `samples` times per probe.  One probe, 32 bytes: */
+#define RT_PROBE_SPHERE 6          /* normal code: no hemisphere offset (the fall-through of diffuse_direction, raytrace.comp:198-210) */
+typedef struct RtLightProbe {
+    float    position[3];          /*  0  where light is gathered: a point just off a surface, e.g. RtRayHit.position as returned      */
+    uint32_t normal;               /* 12  0..5: the shader's face code (RtRayHit.normal); RT_PROBE_SPHERE: whole sphere; else INVALID_ARG */
+    uint16_t cell[2];              /* 16  noise cell: plays gl_WorkGroupID.xy in noise_offset (raytrace.comp:304)                       */
+    uint32_t reserved[3];          /* 20  must be 0                                                                                     */
+} RtLightProbe;
+/* One result, 16 bytes: */
+typedef struct RtProbeLight {
+    float    light[3];             /*  0  the shader's `light` of a non-air primary (raytrace.comp:323-349), mean over the samples      */
+    uint32_t sun_samples;          /* 12  samples whose level-1 shadow ray left the region (sun1.air): exact; / samples = sun visibility */
+} RtProbeLight;
+/* Contract of the two calls:
+ *   Inputs read from `u`: sun_angle, seed and lr only (the camera fields play no part: there is no primary ray).
+ *   Per sample: sample s of a probe is the non-air branch of the shader's main with the surface {position, normal}:
+ *     seed_s = (seed + s) mod RT_NOISE_BYTES, noise_offset = base(seed_s) + cell * 8 (:298-304 with cell in place of gl_WorkGroupID.xy),
+ *     then per level j = 1..depth the noise value of the level (:324, :336: + (j - 1) * 2 / 512), the shadow ray (trace_sun, :185-187)
+ *     and the diffuse ray (diffuse_direction, :189-212) from the surface, the diffuse ray's hit being the surface of level j + 1; the
+ *     path ends when a diffuse ray leaves the region (sample_sky of its direction) or at level `depth`, and the light is unwound
+ *     innermost first with the albedo of each surface (light2 *= albedo2; light2 += emission; light += light2) — the loop RtConfig.depth
+ *     generalises for frames, in the same fp32 operation order.  A probe whose normal is RT_PROBE_SPHERE draws its first diffuse
+ *     direction from the whole sphere (diffuse_direction without the +-1 offset); deeper levels use the face their ray hit.
+ *   Sum: the samples' lights are added in order s = 0 .. samples - 1 in fp32 starting from 0, light = sum / (float)samples per channel.
+ *     The order does not depend on count, on the probe's place in the batch or on how the library splits a call into launches:
+ *     equal probes give equal results, bit for bit.
+ *   Identity with frames (what the feature means): take a pixel (px, py) whose primary ray hits, a probe with position / normal of
+ *     that hit as rt_pick_pixels returns them and cell = (wg(px), wg(py)), wg(p) = (p / 128) * 16 + p % 16 (the workgroup that owns the
+ *     coordinate, raytrace.comp:291-294).  Then light / 16 is bitwise equal to the .rgb of RT_BUF_LIGHTING_F32 of that pixel in a frame
+ *     drawn with the same u, RtConfig.spp = samples and RtConfig.depth = depth (the division by RT_LIGHTING_SCALE is exact).
+ *   Any position is legal: what trace_ray does from inside a solid voxel, outside the window or at a NaN is the result (as for the
+ *     ray queries).
+ *   Validation, before anything is enqueued (a rejected call changes nothing): samples outside 1..4096, depth outside 1..RT_MAX_DEPTH,
+ *     count x samples > 2^26, a NULL pointer with count > 0: RT_ERR_INVALID_ARG.  rt_probe_light also rejects a normal above 6 and a
+ *     non-zero reserved word (RT_ERR_INVALID_ARG).  No world resident or no noise uploaded: RT_ERR_NOT_READY.  count == 0: RT_OK,
+ *     nothing enqueued.
+ *   Which world, ordering and side effects: exactly those of the ray queries — probes see every earlier world change and run on the
+ *     query stream, not after the frames; later edits, slabs and generated terrain wait for them; after rt_set_stream(non-NULL) they
+ *     run on the caller's stream, in order.  No output plane, accumulation sum or history, RtCounters or RtTiming changes.  Tile
+ *     contexts, every RtKernel and every region size answer the same.
+ *   Device work per call: one launch, one lane per (probe, sample) path; a probe's samples are added by one lane, inside the launch
+ *     when `samples` divides 256 and in a second small launch over a scratch buffer of the context otherwise (16 bytes per path,
+ *     at most 64 MiB, grown on demand and counted in RtInfo.device_bytes; larger calls run as several launches of whole probes).
+ *     DESIGN.md "Light probes".
+ * Host pointers; returns when the results are in host memory. */
+int rt_probe_light(RtContext* ctx, const RtUniforms* u, const RtLightProbe* probes, uint32_t count, uint32_t samples, int32_t depth,
+                   RtProbeLight* out);
+/* Same with device pointers, enqueued: `out_dev` is valid after rt_sync (or, after rt_set_stream, in the caller's stream order).  Both
+ * pointers must pass rt_trace_rays_async's test (16-byte aligned memory of the context's device, or managed memory), else
+ * RT_ERR_INVALID_ARG before anything is enqueued; the probes must be complete on the device when the call is made.  The library
+ * cannot read device records on the host: here a normal above 6 is handled on the device as RT_PROBE_SPHERE and the reserved words
+ * are ignored. */
+int rt_probe_light_async(RtContext* ctx, const RtUniforms* u, const RtLightProbe* probes_dev, uint32_t count, uint32_t samples,
+                         int32_t depth, RtProbeLight* out_dev);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Terrain generated on the device: the project's deterministic
  * procedural world (raytrace_amd/host/world.cpp: generate_chunk + pack_into per world chunk, MATERIALS[id].pack()) written straight
  * into the resident region, byte for byte what the host generator assembles — no host bytes, no staging, no transfer.
@@ -614,7 +672,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtConfig.edit_radius (was reserved[0]), rt_edit_boxes_pending (the lighting history is kept
  *        across rt_edit_voxels and restarted only near an edit or in its sun shadow).
  *        Additive, same minor version: RtConfig.stream_history (was reserved[0]), rt_slabs_pending, rt_read_slab_boxes (the lighting
- *        history is kept across rt_upload_slice / rt_generate_slice and restarted only near what left or arrived). */
+ *        history is kept across rt_upload_slice / rt_generate_slice and restarted only near what left or arrived).
+ *        Additive, same minor version: RtLightProbe, RtProbeLight, RT_PROBE_SPHERE, rt_probe_light, rt_probe_light_async (light
+ *        probes: path-traced light at arbitrary points). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

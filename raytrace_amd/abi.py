@@ -146,3 +146,19 @@ class RtRayHit(C.Structure):
 
 
 assert C.sizeof(RtRay) == 32 and C.sizeof(RtRayHit) == 48
+
+
+RT_PROBE_SPHERE = 6   # RtLightProbe.normal: no hemisphere offset (ABI 1.3, additive: light probes)
+
+
+class RtLightProbe(C.Structure):
+    """rt_probe_light input (ABI 1.3, additive): 32 bytes; `reserved` must be 0."""
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_uint32), ("cell", C.c_uint16 * 2), ("reserved", C.c_uint32 * 3)]
+
+
+class RtProbeLight(C.Structure):
+    """rt_probe_light result (ABI 1.3, additive): 16 bytes."""
+    _fields_ = [("light", C.c_float * 3), ("sun_samples", C.c_uint32)]
+
+
+assert C.sizeof(RtLightProbe) == 32 and C.sizeof(RtProbeLight) == 16

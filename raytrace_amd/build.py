@@ -28,7 +28,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra"]
 
 AMD_SRCS = [os.path.join(CSRC, "rt_kernels.hip"), os.path.join(CSRC, "rt_world.hip"), os.path.join(CSRC, "rt_persist.hip"), os.path.join(CSRC, "rt_paths.hip"), os.path.join(CSRC, "rt_frame.hip"), os.path.join(CSRC, "rt_post.hip"),
-            os.path.join(CSRC, "rt_edit.hip"), os.path.join(CSRC, "rt_query.hip"), os.path.join(CSRC, "rt_terrain.hip"),
+            os.path.join(CSRC, "rt_edit.hip"), os.path.join(CSRC, "rt_query.hip"), os.path.join(CSRC, "rt_probe.hip"), os.path.join(CSRC, "rt_terrain.hip"),
             os.path.join(CSRC, "rt_temporal.hip"), os.path.join(CSRC, "rt_slab.hip"),
             ] + [os.path.join(API, f) for f in ("api_context.hip", "api_frame.hip", "api_world.hip", "api_query.hip", "api_post.hip",
                                                  "api_gather.hip")]

@@ -353,6 +353,7 @@ int rt_create(const RtConfig* cfg, RtContext** out) {
     env_int("RT_FRAME_GROUP_TILES", 1, 16, &c->frame_tiles);                      // per four-wave workgroup
     env_int("RT_REFILL_THRESHOLD", 1, 64, &c->wave.refill_threshold);
     env_int("RT_PREPASS_REUSE", 0, 0, &c->prepass_reuse);
+    env_int("RT_PROBE_PAIR", 0, 1, &c->probe_pair);
     env_int("RT_PRIMARY_V", 1, 2, &c->primary_version);
     env_int("RT_PERSIST_THRESHOLD", 1, 64, &c->persist_threshold);
     env_int("RT_PL_STREAM", 0, 3, &c->pl_stream_mode);

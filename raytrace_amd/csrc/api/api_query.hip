@@ -1,4 +1,5 @@
-// api_query.hip — ray queries against the resident world: rt_trace_rays, rt_trace_rays_async, rt_pick_pixels.
+// api_query.hip — queries against the resident world: ray queries (rt_trace_rays, rt_trace_rays_async, rt_pick_pixels) and light
+// probes (rt_probe_light, rt_probe_light_async), which share their checks, stream and staging.
 #include "rt_context.hpp"
 
 using namespace rta;
@@ -75,6 +76,62 @@ int query_sync(RtContext* c, const rtd::Frame& f, const void* in, size_t in_byte
     memcpy(hits, q.host + off, (size_t)count * sizeof(RtRayHit));
     return RT_OK;
 }
+
+// ---- light probes -------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kMaxProbeSamples = 4096;
+constexpr size_t kProbeScratchBytes = (size_t)64 << 20;   // the most path records a launch leaves in the context's scratch
+
+// checks shared by the two calls (query_check's, and the probe's own); RT_OK when there is work to enqueue, 1 for count == 0
+int probe_check(RtContext* c, const char* fn, const RtUniforms* u, const void* probes, uint32_t count, uint32_t samples, int32_t depth,
+                const void* out) {
+    if (samples < 1u || samples > kMaxProbeSamples) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": samples must be 1..4096");
+    if (depth < 1 || depth > RT_MAX_DEPTH) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": depth must be 1..RT_MAX_DEPTH");
+    if ((uint64_t)count * samples > rtd::kProbeMaxPaths) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^26 paths in one call");
+    const int rc = query_check(c, fn, count, probes, u, out);
+    if (rc != RT_OK) return rc;
+    if (!c->has_noise) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the blue-noise table first");
+    return RT_OK;
+}
+
+// The launches of one call on `st`: all probes at once when a workgroup adds its probes' samples itself, else whole probes in
+// pieces whose path records fit the scratch (the pieces follow each other on the stream, so they share it).
+int probe_launch(RtContext* c, hipStream_t st, const RtUniforms* u, const void* probes_dev, void* out_dev, uint32_t count, uint32_t samples,
+                 int32_t depth) {
+    rtd::Frame f = frame_of(c, u);
+    f.depth = depth;
+    f.spp = (int)samples;
+    uint32_t per_launch = count;
+    if (!rtd::probe_sums_in_lds(samples)) {
+        per_launch = (uint32_t)(kProbeScratchBytes / sizeof(float4)) / samples;   // >= 1024 probes: samples <= 4096
+        if (per_launch > count) per_launch = count;
+        const size_t need = (size_t)per_launch * samples * sizeof(float4);
+        if (need > c->probe_scratch_bytes) {
+            if (c->probe_scratch) {
+                RT_HIP(c, hipStreamSynchronize(st));   // (an earlier call's launches may still use it)
+                for (size_t i = 0; i < c->allocs.size(); i++)
+                    if (c->allocs[i] == c->probe_scratch) { c->allocs.erase(c->allocs.begin() + (long)i); break; }
+                (void)hipFree(c->probe_scratch);
+                c->device_bytes -= c->probe_scratch_bytes;
+                c->probe_scratch = nullptr;
+                c->probe_scratch_bytes = 0;
+            }
+            const size_t bytes = (need + (((size_t)1 << 20) - 1u)) & ~(((size_t)1 << 20) - 1u);
+            RT_HIP(c, dev_alloc(c, &c->probe_scratch, bytes / sizeof(float4)));
+            c->probe_scratch_bytes = bytes;
+        }
+    }
+    for (uint32_t first = 0; first < count; first += per_launch) {
+        rtd::ProbeArgs a;
+        a.probes = reinterpret_cast<const uint4*>(probes_dev) + 2u * (size_t)first;
+        a.out = reinterpret_cast<uint4*>(out_dev) + first;
+        a.scratch = c->probe_scratch;
+        a.count = count - first < per_launch ? count - first : per_launch;
+        a.samples = samples;
+        RT_HIP(c, rtd::launch_probe(scene_of(c), f, a, c->probe_pair, st));
+    }
+    if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
+    return RT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -107,6 +164,49 @@ int rt_pick_pixels(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint3
         if (xy[2 * i] < 0 || xy[2 * i] >= ctx->cfg.width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= ctx->cfg.height)
             return fail(ctx, RT_ERR_INVALID_ARG, "rt_pick_pixels: pixel " + std::to_string(i) + " is outside the frame");
     return query_sync(ctx, frame_of(ctx, u), xy, (size_t)count * 8u, true, hits, count);
+}
+
+int rt_probe_light(RtContext* ctx, const RtUniforms* u, const RtLightProbe* probes, uint32_t count, uint32_t samples, int32_t depth,
+                   RtProbeLight* out) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = probe_check(ctx, "rt_probe_light", u, probes, count, samples, depth, out);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    for (uint32_t i = 0; i < count; i++) {
+        if (probes[i].normal > (uint32_t)RT_PROBE_SPHERE)
+            return fail(ctx, RT_ERR_INVALID_ARG, "rt_probe_light: probe " + std::to_string(i) + " has a normal above RT_PROBE_SPHERE");
+        if (probes[i].reserved[0] || probes[i].reserved[1] || probes[i].reserved[2])
+            return fail(ctx, RT_ERR_INVALID_ARG, "rt_probe_light: probe " + std::to_string(i) + " has a non-zero reserved word");
+    }
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    // the probes through pinned and device staging, the launches, the results back (the previous synchronous call has finished
+    // with the staging: it waited for its results)
+    const size_t in_bytes = (size_t)count * sizeof(RtLightProbe), out_bytes = (size_t)count * sizeof(RtProbeLight), need = in_bytes + out_bytes;
+    StagingBlock& q = ctx->query_block;
+    RT_HIP(ctx, q.grow(ctx, need, need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(need + need / 2u)));
+    memcpy(q.host, probes, in_bytes);
+    RT_HIP(ctx, hipMemcpyAsync(q.dev, q.host, in_bytes, hipMemcpyHostToDevice, st));
+    rc = probe_launch(ctx, st, u, q.dev, q.dev + in_bytes, count, samples, depth);
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(q.host + in_bytes, q.dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    memcpy(out, q.host + in_bytes, out_bytes);
+    return RT_OK;
+}
+
+int rt_probe_light_async(RtContext* ctx, const RtUniforms* u, const RtLightProbe* probes_dev, uint32_t count, uint32_t samples,
+                         int32_t depth, RtProbeLight* out_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = probe_check(ctx, "rt_probe_light_async", u, probes_dev, count, samples, depth, out_dev);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, probes_dev) || !query_device_ptr(ctx, out_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_probe_light_async: probes and out must be 16-byte aligned memory of the context's device");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    return probe_launch(ctx, st, u, probes_dev, out_dev, count, samples, depth);
 }
 
 }  // extern "C"

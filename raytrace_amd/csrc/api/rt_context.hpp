@@ -308,6 +308,11 @@ struct __attribute__((visibility("hidden"))) RtContext {
     hipStream_t query_stream = nullptr;
     rta::LatchEvent ev_world, ev_query;
     rta::StagingBlock query_block;   // the synchronous calls' pinned and device staging (inputs, then hits), grown on demand
+    // light probes (rt_probe_light): the path records of a launch whose samples one workgroup cannot add itself (16 bytes per path),
+    // grown on demand up to kProbeScratchBytes, in c->allocs (device_bytes; freed by rt_destroy)
+    float4* probe_scratch = nullptr;
+    size_t probe_scratch_bytes = 0;
+    bool probe_pair = true;          // RT_PROBE_PAIR=0: the plain form of k_probe (A/B timing)
 };
 
 namespace rta __attribute__((visibility("hidden"))) {

@@ -168,6 +168,19 @@ struct QueryArgs {
 };
 hipError_t launch_query(const Scene& sc, const Frame& f, const QueryArgs& a, hipStream_t st);
 
+// rt_probe.hip: light probes (rt_probe_light).  One launch covers `count` whole probes of `samples` paths each, at most kProbeMaxPaths
+// paths; Frame supplies sunangle / sunlight, seed, lr, the region and `depth` (1..RT_MAX_DEPTH).
+constexpr uint64_t kProbeMaxPaths = 1ull << 26;
+struct ProbeArgs {
+    const uint4* probes;  // RtLightProbe[count] (two uint4 each)
+    uint4* out;           // RtProbeLight[count]
+    float4* scratch;      // [count * samples] path records (light rgb, sun1.air bit) when !probe_sums_in_lds(samples); else unused
+    uint32_t count, samples;
+};
+bool probe_sums_in_lds(uint32_t samples);   // a workgroup holds whole probes and adds their samples itself: no scratch, one launch
+// pair: a lane steps the shadow and the diffuse ray of a level together (the shipped form); false: one after the other
+hipError_t launch_probe(const Scene& sc, const Frame& f, const ProbeArgs& a, bool pair, hipStream_t st);
+
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
 // (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
 // or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)

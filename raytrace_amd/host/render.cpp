@@ -101,6 +101,10 @@ int Pipeline::pick(int x, int y_from_top, PickResult* out) {
     return RT_OK;
 }
 
+int Pipeline::probe_light(const RtLightProbe* probes, uint32_t count, uint32_t samples, int32_t depth, RtProbeLight* out) {
+    return rt_probe_light(ctx_, &uniforms_, probes, count, samples, depth, out);
+}
+
 int Pipeline::wait() { return rt_sync(ctx_); }
 
 static bool invert3(const float c0[3], const float c1[3], const float c2[3], float out[3][3]) {

@@ -102,6 +102,9 @@ class Pipeline {
         int32_t world[3];
     };
     int pick(int x, int y_from_top, PickResult* out);
+    // Path-traced light at `count` points under the sun, seed and lr of the frame drawn last: rt_probe_light with the pipeline's
+    // uniforms (a host that accumulates over calls advances the seed by `samples` between them: set_seed).
+    int probe_light(const RtLightProbe* probes, uint32_t count, uint32_t samples, int32_t depth, RtProbeLight* out);
     bool post_passes() const { return post_; }
 
  private:

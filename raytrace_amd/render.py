@@ -13,8 +13,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RtConfig, RtCounters, RtInfo, RtRayHit,
-                  RtTiming, RtUniforms, RtVoxelEdit)
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RtConfig, RtCounters, RtInfo, RtLightProbe,
+                  RtProbeLight, RtRayHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
 class RtError(RuntimeError):
@@ -45,6 +45,10 @@ def _p(a):
 HIT_DTYPE = np.dtype([("position", "<f4", 3), ("distance", "<f4"), ("texel", "<i4", 3), ("material", "<u4"), ("normal", "<u4"),
                       ("kind", "<u4"), ("iterations", "<u4"), ("border_fetches", "<u4")])
 assert HIT_DTYPE.itemsize == C.sizeof(RtRayHit)
+# numpy views of RtLightProbe and RtProbeLight (include/rt_abi.h)
+PROBE_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<u4"), ("cell", "<u2", 2), ("reserved", "<u4", 3)])
+PROBE_LIGHT_DTYPE = np.dtype([("light", "<f4", 3), ("sun_samples", "<u4")])
+assert PROBE_DTYPE.itemsize == C.sizeof(RtLightProbe) and PROBE_LIGHT_DTYPE.itemsize == C.sizeof(RtProbeLight)
 
 # Texel step from a hit voxel to the empty neighbour in front of the face the ray crossed, per normal code (raytrace.comp:89-93): an
 # even code means the ray travelled towards -axis, so it came from +axis.
@@ -235,6 +239,30 @@ class Context:
         hits = np.zeros(xy.shape[0], dtype=HIT_DTYPE)
         self._check(self._lib.rt_pick_pixels(self._h, C.byref(uniforms), _p(xy), int(xy.shape[0]), _p(hits)))
         return hits
+
+    # -- light probes ------------------------------------------------------------------------------------
+    def probe_light(self, uniforms, positions, normals, cells, samples, depth):
+        """rt_probe_light: float[N, 3] positions, int[N] normal codes (0..5, or RT_PROBE_SPHERE), int[N, 2] noise cells ->
+        numpy array of PROBE_LIGHT_DTYPE (RtProbeLight) per probe: the mean light of `samples` paths of `depth` levels from each
+        surface under the sun_angle, seed and lr of `uniforms`.  Synchronous."""
+        return self.probe_records(uniforms, make_probes(positions, normals, cells), samples, depth)
+
+    def probe_records(self, uniforms, probes, samples, depth):
+        """rt_probe_light on a ready array of RtLightProbe records (numpy PROBE_DTYPE rows, reserved included)."""
+        probes = np.ascontiguousarray(probes)
+        assert probes.dtype.itemsize == C.sizeof(RtLightProbe)
+        out = np.zeros(probes.size, dtype=PROBE_LIGHT_DTYPE)
+        self._check(self._lib.rt_probe_light(self._h, C.byref(uniforms), _p(probes), int(probes.size), int(samples), int(depth), _p(out)))
+        return out
+
+    def probe_light_async(self, uniforms, probes, out, samples, depth):
+        """rt_probe_light_async on torch device tensors: `probes` any contiguous tensor of N * 32 bytes (RtLightProbe rows, e.g.
+        uint8[N, 32] from make_probes), `out` any contiguous tensor of N * 16 bytes (e.g. float32[N, 4]: light rgb, then the bits of
+        sun_samples).  Enqueued: valid after sync(), or in the order of a stream given to set_stream().  `probes` must be complete
+        on the device when the call is made."""
+        n = check_probe_tensors(probes, out, self.cfg.device if self.cfg is not None else 0)
+        self._check(self._lib.rt_probe_light_async(self._h, C.byref(uniforms), C.c_void_p(probes.data_ptr()), n, int(samples), int(depth),
+                                                   C.c_void_p(out.data_ptr())))
 
     # -- frames ------------------------------------------------------------------------------------------
     def draw_frame(self, uniforms):
@@ -632,6 +660,48 @@ def check_query_tensors(rays, hits, device):
     n = int(rays.shape[0])
     if not hits.is_contiguous() or hits.numel() * hits.element_size() != n * HIT_DTYPE.itemsize:
         raise ValueError("hits must be a contiguous tensor of N * 48 bytes")
+    return n
+
+
+def make_probes(positions, normals, cells):
+    """RtLightProbe records (PROBE_DTYPE) from float[N, 3] positions, int[N] normal codes and int[N, 2] noise cells."""
+    pos = np.asarray(positions, dtype=np.float32).reshape(-1, 3)
+    nrm = np.asarray(normals).reshape(-1)
+    cell = np.asarray(cells).reshape(-1, 2)
+    if nrm.size != pos.shape[0] or cell.shape[0] != pos.shape[0]:
+        raise ValueError("positions, normals and cells must describe the same number of probes")
+    if pos.shape[0] and (cell.min() < 0 or cell.max() > 0xFFFF or nrm.min() < 0 or nrm.max() > 0xFFFFFFFF):
+        raise ValueError("cells must fit uint16 and normals uint32 (the library checks the normal codes)")
+    probes = np.zeros(pos.shape[0], dtype=PROBE_DTYPE)
+    probes["position"], probes["normal"], probes["cell"] = pos, nrm, cell
+    return probes
+
+
+def workgroup_of(p):
+    """The noise cell of a frame's pixel coordinate: the shader workgroup that owns it (raytrace.comp:291-294)."""
+    p = np.asarray(p, dtype=np.int64)
+    return (p // 128) * 16 + p % 16
+
+
+def check_probe_tensors(probes, out, device):
+    """Context.probe_light_async's arguments: contiguous tensors of N * 32 and N * 16 bytes on GPU `device`, 16-byte aligned.
+    Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
+    import torch
+    if not isinstance(probes, torch.Tensor) or not isinstance(out, torch.Tensor):
+        raise ValueError("probes and out must be torch tensors")
+    for name, t in (("probes", probes), ("out", out)):
+        if not t.is_cuda or t.device.index != int(device):
+            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    nbytes = probes.numel() * probes.element_size()
+    if nbytes % PROBE_DTYPE.itemsize:
+        raise ValueError("probes must hold whole 32-byte RtLightProbe records")
+    n = nbytes // PROBE_DTYPE.itemsize
+    if out.numel() * out.element_size() != n * PROBE_LIGHT_DTYPE.itemsize:
+        raise ValueError("out must be a contiguous tensor of N * 16 bytes")
     return n
 
 
