@@ -597,6 +597,37 @@ int rt_denoise_planes(RtContext* ctx, void* lighting_rgba16, const void* depth_r
 int rt_finalize_planes(RtContext* ctx, const void* albedo_rgba8, const void* emission_rgba8, const void* fog_rgba8,
                        const void* lighting_rgba16, const void* depth_r16, void* out_bgra8);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) History-aware denoise: the six dispatches of rt_denoise with the
+ * per-pixel sample counts of RT_FLAG_REPROJECT taken into account, so that a pixel with a long history is not blurred as hard as one
+ * disoccluded this frame.  With m(p) = min(max(count(p), 1), 127), dispatch i (tap spacings 1, 2, 4, 8, 8, 16) is dispatch i of
+ * rt_denoise -- same spacing, same binding rule for `faithful` -- with two changes:
+ *   settle   when settle[i] != 0 and m(p) >= settle[i], pixel p takes the shader's copy branch in dispatch i: its working value
+ *            passes through unchanged, whatever its normal / depth binding says.  It is still read as a tap by its neighbours.
+ *   weight   with weight_by_count = 1 the centre starts from total_weight = 0.146634f * (float)m(c) and sum = L_c * total_weight,
+ *            and each tap's weight is the existing quotient times (float)m(tap): one fp32 multiply behind the division, whose
+ *            domain (RT_SELFTEST_DENOISE_DIVISION) is unchanged.
+ * The fma accumulation, the tap order, the UNORM16 quantisation between dispatches and the alpha rule are rt_denoise's: alpha is
+ * 65535 once any dispatch filtered the pixel, else the original texel's.  Neutral parameters -- weight_by_count = 0 with settle all
+ * 0, or weight_by_count = 1 with every count equal to 1 -- give rt_denoise's bits exactly.  Same seven launches and working memory.
+ * A block with a wrong struct_size, settle[i] > 127, weight_by_count outside 0 / 1 or a non-zero reserved word, or a NULL block, is
+ * RT_ERR_INVALID_ARG, and nothing is enqueued. */
+typedef struct RtDenoiseParams {   /* 48 bytes */
+    uint32_t struct_size;          /* sizeof(RtDenoiseParams) */
+    int32_t  faithful;             /* as rt_denoise: odd dispatches use the pong binding */
+    int32_t  weight_by_count;      /* 0 / 1 */
+    uint32_t settle[6];            /* per dispatch: 0 = nobody settles; 1..127 = pixels with m >= it are left alone */
+    uint32_t reserved[3];          /* must be 0 */
+} RtDenoiseParams;
+/* Filters RT_BUF_LIGHTING_RGBA16 of the frame drawn last in place, like rt_denoise, with the counts that frame's pass wrote (what
+ * rt_read_history returns).  The history sums, the counts and RT_BUF_LIGHTING_F32 are not touched.  Asynchronous, on rt_denoise's
+ * stream; the counts are read before any later frame overwrites them, with two frames in flight too.  RT_ERR_UNIMPLEMENTED on a
+ * tile-split context, RT_ERR_INVALID_ARG on one without RT_FLAG_REPROJECT, RT_ERR_NOT_READY before the first frame. */
+int rt_denoise_history(RtContext* ctx, const RtDenoiseParams* params);
+/* The same on caller-owned planes (as rt_denoise_planes) plus a row-major u32 device plane of width x height counts: the route for a
+ * gathered multi-GPU frame.  Valid on any context. */
+int rt_denoise_planes_counted(RtContext* ctx, void* lighting_rgba16, const void* depth_r16, const void* normal_r8,
+                              const uint32_t* counts_dev, const RtDenoiseParams* params);
+
 /* The traversal implementation the context runs: the kernel of a frame's last launch, the same before the first frame and after
  * it.  The choice is fixed per context when it is created (launch size, primary cache, region, depth, accumulation); a cached
  * frame of depth 0, which has no path launch, reports RT_KERNEL_PATHS or RT_KERNEL_PERSISTENT as configured.  Negative RtStatus on
@@ -674,7 +705,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtConfig.stream_history (was reserved[0]), rt_slabs_pending, rt_read_slab_boxes (the lighting
  *        history is kept across rt_upload_slice / rt_generate_slice and restarted only near what left or arrived).
  *        Additive, same minor version: RtLightProbe, RtProbeLight, RT_PROBE_SPHERE, rt_probe_light, rt_probe_light_async (light
- *        probes: path-traced light at arbitrary points). */
+ *        probes: path-traced light at arbitrary points).
+ *        Additive, same minor version: RtDenoiseParams, rt_denoise_history, rt_denoise_planes_counted (history-aware denoise:
+ *        converged pixels settle, taps may be weighted by their sample counts). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

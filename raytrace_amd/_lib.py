@@ -3,7 +3,7 @@ import fails loudly (build it with `python -m raytrace_amd.build`)."""
 import ctypes as C
 import os
 
-from .abi import RtConfig, RtCounters, RtInfo, RtTiming, RtUniforms, RtVoxelEdit
+from .abi import RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtTiming, RtUniforms, RtVoxelEdit
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_AMD_LIB: load another build of the same library (same-box A/B timing of two kernel variants, tools/ab.sh)
@@ -22,6 +22,7 @@ ABI_SYMBOLS = (
     "rt_reset_accumulation", "rt_get_accumulation", "rt_edit_voxels", "rt_read_box",
     "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels", "rt_generate_world", "rt_generate_slice", "rt_read_history",
     "rt_edit_boxes_pending", "rt_slabs_pending", "rt_read_slab_boxes", "rt_probe_light", "rt_probe_light_async",
+    "rt_denoise_history", "rt_denoise_planes_counted",
 )
 
 _amd = None
@@ -75,6 +76,10 @@ def amd():
         lib.rt_finalize.argtypes = [P]
         lib.rt_denoise_planes.argtypes = [P, P, P, P, C.c_int]
         lib.rt_finalize_planes.argtypes = [P, P, P, P, P, P, P]
+        lib.rt_denoise_history.argtypes = [P, C.POINTER(RtDenoiseParams)]
+        lib.rt_denoise_history.restype = C.c_int
+        lib.rt_denoise_planes_counted.argtypes = [P, P, P, P, P, C.POINTER(RtDenoiseParams)]
+        lib.rt_denoise_planes_counted.restype = C.c_int
         lib.rt_kernel_in_use.argtypes = [P]
         lib.rt_kernel_in_use.restype = C.c_int
         lib.rt_get_counters.argtypes = [P, C.POINTER(RtCounters)]
@@ -217,6 +222,8 @@ def host():
         lib.rth_pipeline_set_seed.argtypes = [P, C.c_uint32]
         lib.rth_pipeline_enable_post_passes.argtypes = [P, C.c_int]
         lib.rth_pipeline_enable_post_passes.restype = C.c_int
+        lib.rth_pipeline_enable_history_denoise.argtypes = [P, C.POINTER(RtDenoiseParams)]
+        lib.rth_pipeline_enable_history_denoise.restype = C.c_int
         lib.rth_pipeline_last_error.argtypes = [P]
         lib.rth_pipeline_last_error.restype = C.c_char_p
         lib.rth_pipeline_pick.argtypes = [P, C.c_int, C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

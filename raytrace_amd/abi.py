@@ -162,3 +162,12 @@ class RtProbeLight(C.Structure):
 
 
 assert C.sizeof(RtLightProbe) == 32 and C.sizeof(RtProbeLight) == 16
+
+
+class RtDenoiseParams(C.Structure):
+    """rt_denoise_history / rt_denoise_planes_counted parameters (ABI 1.3, additive): 48 bytes; `reserved` must be 0."""
+    _fields_ = [("struct_size", C.c_uint32), ("faithful", C.c_int32), ("weight_by_count", C.c_int32), ("settle", C.c_uint32 * 6),
+                ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(RtDenoiseParams) == 48

@@ -43,6 +43,69 @@ int rt_denoise_planes(RtContext* ctx, void* lighting, const void* depth, const v
     return RT_OK;
 }
 
+namespace {
+
+// RtDenoiseParams as the header states it; nothing is enqueued for a block that fails
+int check_denoise_params(RtContext* ctx, const char* who, const RtDenoiseParams* p) {
+    const std::string w(who);
+    if (!p) return fail(ctx, RT_ERR_INVALID_ARG, w + ": null params");
+    if (p->struct_size != sizeof(RtDenoiseParams)) return fail(ctx, RT_ERR_INVALID_ARG, w + ": RtDenoiseParams.struct_size mismatch");
+    if (p->weight_by_count != 0 && p->weight_by_count != 1) return fail(ctx, RT_ERR_INVALID_ARG, w + ": weight_by_count must be 0 or 1");
+    for (int i = 0; i < 6; i++)
+        if (p->settle[i] > 127u) return fail(ctx, RT_ERR_INVALID_ARG, w + ": settle[i] must be 0 (nobody settles) or 1..127");
+    for (int i = 0; i < 3; i++)
+        if (p->reserved[i] != 0u) return fail(ctx, RT_ERR_INVALID_ARG, w + ": reserved words must be 0");
+    return RT_OK;
+}
+
+// rt_denoise_planes' seven launches with the counts packed into the working pixel (`counts`: a u32 plane, or the history records)
+int denoise_counted(RtContext* ctx, void* lighting, const void* depth, const void* normal, const void* counts, bool counts_are_records,
+                    const RtDenoiseParams& p) {
+    plane_written(ctx, lighting);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const int sizes[6] = {1, 2, 4, 8, 8, 16};                         // pipeline.rs:103
+    const int W = ctx->cfg.width, H = ctx->cfg.height;
+    void** work = ctx->slots[ctx->cur_slot].denoise_work;
+    for (int i = 0; i < 2; i++)
+        if (!work[i]) { uint4* q = nullptr; RT_HIP(ctx, dev_alloc(ctx, &q, (size_t)W * H)); work[i] = q; }
+    {
+        LaunchTimer t(ctx, 1);
+        RT_HIP(ctx, rtd::launch_denoise_prepare_counted(lighting, depth, normal, counts, counts_are_records, W, H, work[0], ctx->stream));
+    }
+    for (int pass = 0; pass < 6; pass++) {
+        const bool odd = pass % 2 == 1;
+        LaunchTimer t(ctx, 1);
+        RT_HIP(ctx, rtd::launch_denoise_counted(work[pass & 1], W, H, sizes[pass], odd && p.faithful != 0, pass == 5, p.weight_by_count == 1,
+                                                p.settle[pass], work[(pass & 1) ^ 1], lighting, ctx->stream));
+    }
+    return RT_OK;
+}
+
+}  // namespace
+
+int rt_denoise_planes_counted(RtContext* ctx, void* lighting, const void* depth, const void* normal, const uint32_t* counts_dev,
+                              const RtDenoiseParams* params) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!lighting || !depth || !normal || !counts_dev) return fail(ctx, RT_ERR_INVALID_ARG, "rt_denoise_planes_counted: null plane");
+    const int rc = check_denoise_params(ctx, "rt_denoise_planes_counted", params);
+    if (rc != RT_OK) return rc;
+    return denoise_counted(ctx, lighting, depth, normal, counts_dev, false, *params);
+}
+
+int rt_denoise_history(RtContext* ctx, const RtDenoiseParams* params) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (ctx->cfg.tile_world != 1) return fail(ctx, RT_ERR_UNIMPLEMENTED, "rt_denoise_history: whole-frame contexts only (gather the tiles, then rt_denoise_planes_counted)");
+    if (!ctx->reproject) return fail(ctx, RT_ERR_INVALID_ARG, "rt_denoise_history: the context was created without RT_FLAG_REPROJECT");
+    const int rc = check_denoise_params(ctx, "rt_denoise_history", params);
+    if (rc != RT_OK) return rc;
+    if (!ctx->frame_recorded) return fail(ctx, RT_ERR_NOT_READY, "rt_denoise_history: no frame drawn yet");
+    // The records of the frame drawn last, read on the stream that frame ended on.  The set is next written by the pass of the
+    // second frame from now, which is ordered behind this read: it uses this frame's slot (two slots) or follows the next frame,
+    // which uses it (one slot), and a frame starts by waiting for everything put behind the previous user of its slot (ev_tail).
+    return denoise_counted(ctx, ctx->planes[RT_BUF_LIGHTING_RGBA16], ctx->planes[RT_BUF_DEPTH_R16UI], ctx->planes[RT_BUF_NORMAL_R8UI],
+                           ctx->d_hist_rec[ctx->hist_cur], true, *params);
+}
+
 int rt_finalize_planes(RtContext* ctx, const void* albedo, const void* emission, const void* fog, const void* lighting,
                        const void* depth, void* out_bgra8) {
     if (!ctx) return RT_ERR_INVALID_ARG;

@@ -224,6 +224,12 @@ hipError_t launch_denoise_prepare(const void* lighting, const void* depth, const
                                   hipStream_t st);
 hipError_t launch_denoise(const void* work_in, int W, int H, int size, bool swapped, bool last, void* work_out, void* lighting,
                           hipStream_t st);
+// the history-aware dispatches (rt_denoise_history, rt_denoise_planes_counted): `counts` is the history record of RT_FLAG_REPROJECT
+// (TemporalArgs::next_rec) or a row-major u32 plane; settle 0 = nobody settles, else 1..127
+hipError_t launch_denoise_prepare_counted(const void* lighting, const void* depth, const void* normal, const void* counts,
+                                          bool counts_are_records, int W, int H, void* work, hipStream_t st);
+hipError_t launch_denoise_counted(const void* work_in, int W, int H, int size, bool swapped, bool last, bool weight, uint32_t settle,
+                                  void* work_out, void* lighting, hipStream_t st);
 hipError_t launch_selftest_dn_div(unsigned long long* mismatches_dev, hipStream_t st);
 hipError_t launch_finalize(const void* albedo, const void* emission, const void* fog, const void* lighting, const void* depth,
                            const uint32_t* noise, int W, int H, void* out_bgra8, hipStream_t st);

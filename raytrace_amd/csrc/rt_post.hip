@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "rt_device.hpp"
 #include "rt_kernels.hpp"
@@ -197,6 +198,153 @@ __global__ __launch_bounds__(256) void k_denoise_tiled(const uint4* __restrict__
     if (!LAST) out[c] = pc;
 }
 
+// ---- the history-aware dispatches (rt_denoise_history, rt_denoise_planes_counted; DESIGN.md "History-aware denoise") ---------
+// The same six dispatches on the same 16-byte working pixel, with m(p) = min(max(count(p), 1), 127) in bits 25..31 of the guide
+// word (depth 0..15, normal 16..23 and the computed flag at bit 24 are where they were): bytes moved per dispatch do not change.
+// Sibling kernels, so that the instantiations rt_denoise launches stay what they are — and written out like them: the same body
+// behind a tap-fetch callback compiled to 104-124 registers, four waves per SIMD where these run six to eight.
+constexpr uint32_t kDnCountShift = 25;
+
+// REC: `counts` is the history record of RT_FLAG_REPROJECT, (depth_f32 bits, count | normal << 27) per row-major pixel; else a
+// row-major u32 plane of counts
+template <bool REC>
+__global__ __launch_bounds__(256) void k_denoise_prepare_counted(const ushort4* __restrict__ lin, const uint16_t* __restrict__ depth,
+                                                                 const uint8_t* __restrict__ normal, const uint32_t* __restrict__ counts,
+                                                                 uint32_t n, uint4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const ushort4 l = lin[i];
+    const uint32_t cnt = REC ? (reinterpret_cast<const uint2*>(counts)[i].y & ((1u << 27) - 1u)) : counts[i];
+    const uint32_t m = cnt < 1u ? 1u : (cnt > 127u ? 127u : cnt);
+    uint4 o;
+    o.x = __builtin_bit_cast(uint32_t, (float)l.x / 65535.0f);
+    o.y = __builtin_bit_cast(uint32_t, (float)l.y / 65535.0f);
+    o.z = __builtin_bit_cast(uint32_t, (float)l.z / 65535.0f);
+    o.w = (uint32_t)depth[i] | (uint32_t)normal[i] << 16 | m << kDnCountShift;
+    out[i] = o;
+}
+
+template <bool SWAPPED> __device__ __forceinline__ uint32_t dn_depth_binding(uint32_t g) { return SWAPPED ? (g >> 16 & 0xFFu) : (g & 0xFFFFu); }
+template <bool SWAPPED> __device__ __forceinline__ uint32_t dn_normal_binding(uint32_t g) { return SWAPPED ? (g & 0xFFFFu) : (g >> 16 & 0xFFu); }
+
+// the sixth dispatch's store of a pixel on the copy branch (:91): alpha of a never-filtered pixel is the original one
+__device__ __forceinline__ void dn_store_copy(const uint4& pc, ushort4* __restrict__ lighting, size_t c) {
+    ushort4 o;
+    o.x = (uint16_t)rtm_unorm(__builtin_bit_cast(float, pc.x), 65535.0f);
+    o.y = (uint16_t)rtm_unorm(__builtin_bit_cast(float, pc.y), 65535.0f);
+    o.z = (uint16_t)rtm_unorm(__builtin_bit_cast(float, pc.z), 65535.0f);
+    o.w = (pc.w & kDnComputed) ? (uint16_t)65535 : lighting[c].w;
+    lighting[c] = o;
+}
+
+// k_denoise_pass with the settle test: a pixel with m >= settle takes the copy branch whatever its normal binding says (it is
+// still read as a tap).  `settle` is wave-uniform, 1..127, or 128 for "nobody settles" (m never reaches it).
+template <bool SWAPPED, bool LAST, bool WEIGHT>
+__global__ __launch_bounds__(256) void k_denoise_pass_counted(const uint4* __restrict__ in, int W, int H, int size, uint32_t settle,
+                                                              uint4* __restrict__ out, ushort4* __restrict__ lighting) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const size_t c = (size_t)y * W + x;
+    uint4 pc = in[c];
+    const float center_distance = (float)dn_depth_binding<SWAPPED>(pc.w) / 256.0f;                   // :36
+    const uint32_t center_normal = dn_normal_binding<SWAPPED>(pc.w);                                 // :37
+    if (center_normal < 16u && (pc.w >> kDnCountShift) < settle) {                                   // :39, and not settled
+        float total_weight = 0.146634f;                                                              // :40
+        if (WEIGHT) total_weight = 0.146634f * (float)(pc.w >> kDnCountShift);
+        float sr = __builtin_bit_cast(float, pc.x) * total_weight, sg = __builtin_bit_cast(float, pc.y) * total_weight,
+              sb = __builtin_bit_cast(float, pc.z) * total_weight;                                   // :41
+#pragma unroll
+        for (int t = 0; t < 36; t++) {                                                               // SAMPLE, :23-33
+            int px = x + kDenoiseTaps[t].dx * size, py = y + kDenoiseTaps[t].dy * size;             // sampleAt, :14-21
+            px = px < 0 ? 0 : (px >= W ? W - 1 : px);
+            py = py < 0 ? 0 : (py >= H ? H - 1 : py);
+            const uint4 l = in[(size_t)py * W + px];
+            const float dist = (float)dn_depth_binding<SWAPPED>(l.w) / 256.0f;
+            const float distance_difference = 4.0f * rtm_abs(center_distance - dist);
+            const float normal_difference = dn_normal_binding<SWAPPED>(l.w) == center_normal ? 0.0f : 10.0f;
+            float weight = dn_div(kDenoiseTaps[t].w, distance_difference + normal_difference + 1.0f);
+            if (WEIGHT) weight *= (float)(l.w >> kDnCountShift);
+            total_weight += weight;
+            sr = rtm_fma(__builtin_bit_cast(float, l.x), weight, sr);
+            sg = rtm_fma(__builtin_bit_cast(float, l.y), weight, sg);
+            sb = rtm_fma(__builtin_bit_cast(float, l.z), weight, sb);
+        }
+        const uint32_t qr = rtm_unorm(sr / total_weight, 65535.0f), qg = rtm_unorm(sg / total_weight, 65535.0f),
+                       qb = rtm_unorm(sb / total_weight, 65535.0f);                                  // imageStore to RGBA16_UNORM, :89
+        pc.x = __builtin_bit_cast(uint32_t, (float)qr / 65535.0f);
+        pc.y = __builtin_bit_cast(uint32_t, (float)qg / 65535.0f);
+        pc.z = __builtin_bit_cast(uint32_t, (float)qb / 65535.0f);
+        pc.w |= kDnComputed;
+        if (LAST) { ushort4 o; o.x = (uint16_t)qr; o.y = (uint16_t)qg; o.z = (uint16_t)qb; o.w = 65535; lighting[c] = o; }
+    } else if (LAST) {
+        dn_store_copy(pc, lighting, c);
+    }
+    if (!LAST) out[c] = pc;
+}
+
+// k_denoise_tiled likewise.  The tile is skipped when none of its pixels filters — the whole tile on the copy branch or settled:
+// on a long-held camera the dispatch then costs a copy.  (Seven waves per SIMD asked for: left alone, the compiler spends 126
+// registers on the <.., LAST = false, WEIGHT = true, ..> instantiations, four waves per SIMD where k_denoise_tiled runs seven or eight.)
+template <bool SWAPPED, bool LAST, bool WEIGHT, int S>
+__global__ __launch_bounds__(256, 7) void k_denoise_tiled_counted(const uint4* __restrict__ in, int W, int H, uint32_t settle,
+                                                               uint4* __restrict__ out, ushort4* __restrict__ lighting) {
+    constexpr int TW = 32, THt = 8, HALO = 3 * S, PW = TW + 2 * HALO, PH = THt + 2 * HALO;
+    __shared__ uint4 tile[PH * PW];
+    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * THt;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int x = x0 + tx, y = y0 + ty;
+    const bool inside = x < W && y < H;
+    const size_t c = (size_t)y * W + x;
+    uint4 pc = make_uint4(0, 0, 0, 0);
+    if (inside) pc = in[c];
+    const bool filter = inside && dn_normal_binding<SWAPPED>(pc.w) < 16u && (pc.w >> kDnCountShift) < settle;
+    if (!__syncthreads_or(filter)) {
+        if (!inside) return;
+        if (LAST) dn_store_copy(pc, lighting, c); else out[c] = pc;
+        return;
+    }
+    for (int i = threadIdx.x; i < PW * PH; i += 256) {
+        int gx = x0 + i % PW - HALO, gy = y0 + i / PW - HALO;
+        gx = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+        gy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy);
+        tile[i] = in[(size_t)gy * W + gx];
+    }
+    __syncthreads();
+    if (!inside) return;
+    const uint4* ctr = tile + (ty + HALO) * PW + tx + HALO;
+    const float center_distance = (float)dn_depth_binding<SWAPPED>(pc.w) / 256.0f;                   // :36
+    const uint32_t center_normal = dn_normal_binding<SWAPPED>(pc.w);                                 // :37
+    if (filter) {
+        float total_weight = 0.146634f;                                                              // :40
+        if (WEIGHT) total_weight = 0.146634f * (float)(pc.w >> kDnCountShift);
+        float sr = __builtin_bit_cast(float, pc.x) * total_weight, sg = __builtin_bit_cast(float, pc.y) * total_weight,
+              sb = __builtin_bit_cast(float, pc.z) * total_weight;                                   // :41
+#pragma unroll
+        for (int t = 0; t < 36; t++) {                                                               // SAMPLE, :23-33
+            const uint4 l = ctr[kDenoiseTaps[t].dy * S * PW + kDenoiseTaps[t].dx * S];
+            const float dist = (float)dn_depth_binding<SWAPPED>(l.w) / 256.0f;
+            const float distance_difference = 4.0f * rtm_abs(center_distance - dist);
+            const float normal_difference = dn_normal_binding<SWAPPED>(l.w) == center_normal ? 0.0f : 10.0f;
+            float weight = dn_div(kDenoiseTaps[t].w, distance_difference + normal_difference + 1.0f);
+            if (WEIGHT) weight *= (float)(l.w >> kDnCountShift);
+            total_weight += weight;
+            sr = rtm_fma(__builtin_bit_cast(float, l.x), weight, sr);
+            sg = rtm_fma(__builtin_bit_cast(float, l.y), weight, sg);
+            sb = rtm_fma(__builtin_bit_cast(float, l.z), weight, sb);
+        }
+        const uint32_t qr = rtm_unorm(sr / total_weight, 65535.0f), qg = rtm_unorm(sg / total_weight, 65535.0f),
+                       qb = rtm_unorm(sb / total_weight, 65535.0f);                                  // imageStore to RGBA16_UNORM, :89
+        pc.x = __builtin_bit_cast(uint32_t, (float)qr / 65535.0f);
+        pc.y = __builtin_bit_cast(uint32_t, (float)qg / 65535.0f);
+        pc.z = __builtin_bit_cast(uint32_t, (float)qb / 65535.0f);
+        pc.w |= kDnComputed;
+        if (LAST) { ushort4 o; o.x = (uint16_t)qr; o.y = (uint16_t)qg; o.z = (uint16_t)qb; o.w = 65535; lighting[c] = o; }
+    } else if (LAST) {
+        dn_store_copy(pc, lighting, c);
+    }
+    if (!LAST) out[c] = pc;
+}
+
 __device__ __forceinline__ float filmic_curve(float x) {   // finalize.comp:21-31
     if (x < 0.3f) return x * x;
     if (x < 1.13333f) return rtm_fma(x, 0.6f, -0.09f);
@@ -258,6 +406,50 @@ hipError_t launch_denoise(const void* work_in, int W, int H, int size, bool swap
     if (swapped) { if (last) RT_LAUNCH_DN(true, true); else RT_LAUNCH_DN(true, false); }
     else { if (last) RT_LAUNCH_DN(false, true); else RT_LAUNCH_DN(false, false); }
 #undef RT_LAUNCH_DN
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_prepare_counted(const void* lighting, const void* depth, const void* normal, const void* counts,
+                                          bool counts_are_records, int W, int H, void* work, hipStream_t st) {
+    const uint32_t n = (uint32_t)W * (uint32_t)H;
+#define RT_LAUNCH_DPC(REC) hipLaunchKernelGGL((k_denoise_prepare_counted<REC>), dim3((n + 255u) / 256u), dim3(256), 0, st, (const ushort4*)lighting, \
+                                              (const uint16_t*)depth, (const uint8_t*)normal, (const uint32_t*)counts, n, (uint4*)work)
+    if (counts_are_records) RT_LAUNCH_DPC(true); else RT_LAUNCH_DPC(false);
+#undef RT_LAUNCH_DPC
+    return hipGetLastError();
+}
+
+namespace {
+// f(std::bool_constant<a>, <b>, <c>): three run-time flags as template arguments
+template <typename F>
+void with_flags(bool a, bool b, bool c, F&& f) {
+    auto on_c = [&](auto A, auto B) { if (c) f(A, B, std::true_type{}); else f(A, B, std::false_type{}); };
+    auto on_b = [&](auto A) { if (b) on_c(A, std::true_type{}); else on_c(A, std::false_type{}); };
+    if (a) on_b(std::true_type{}); else on_b(std::false_type{});
+}
+}  // namespace
+
+hipError_t launch_denoise_counted(const void* work_in, int W, int H, int size, bool swapped, bool last, bool weight, uint32_t settle,
+                                  void* work_out, void* lighting, hipStream_t st) {
+    const uint32_t settle_at = settle ? settle : 128u;   // m <= 127: nobody settles
+    const dim3 block(256);
+    if ((size == 1 || size == 2) && !getenv("RT_DENOISE_UNTILED")) {
+        const dim3 grid((W + 31) / 32, (H + 7) / 8);
+        with_flags(swapped, last, weight, [&](auto SW, auto L, auto WT) {
+            if (size == 1)
+                hipLaunchKernelGGL((k_denoise_tiled_counted<decltype(SW)::value, decltype(L)::value, decltype(WT)::value, 1>), grid, block, 0, st,
+                                   (const uint4*)work_in, W, H, settle_at, (uint4*)work_out, (ushort4*)lighting);
+            else
+                hipLaunchKernelGGL((k_denoise_tiled_counted<decltype(SW)::value, decltype(L)::value, decltype(WT)::value, 2>), grid, block, 0, st,
+                                   (const uint4*)work_in, W, H, settle_at, (uint4*)work_out, (ushort4*)lighting);
+        });
+        return hipGetLastError();
+    }
+    const dim3 grid((W + 63) / 64, (H + 3) / 4);
+    with_flags(swapped, last, weight, [&](auto SW, auto L, auto WT) {
+        hipLaunchKernelGGL((k_denoise_pass_counted<decltype(SW)::value, decltype(L)::value, decltype(WT)::value>), grid, block, 0, st,
+                           (const uint4*)work_in, W, H, size, settle_at, (uint4*)work_out, (ushort4*)lighting);
+    });
     return hipGetLastError();
 }
 

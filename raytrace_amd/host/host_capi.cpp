@@ -227,6 +227,9 @@ void rth_pipeline_enable_streaming_on_device(void* p, uint64_t seed) {
     static_cast<render::Pipeline*>(p)->enable_terrain_streaming(seed, "", true);
 }
 int rth_pipeline_enable_post_passes(void* p, int faithful) { return static_cast<render::Pipeline*>(p)->enable_post_passes(faithful != 0); }
+int rth_pipeline_enable_history_denoise(void* p, const RtDenoiseParams* params) {
+    return params ? static_cast<render::Pipeline*>(p)->enable_history_denoise(*params) : RT_ERR_INVALID_ARG;
+}
 const char* rth_pipeline_last_error(void* p) { return static_cast<render::Pipeline*>(p)->last_error(); }
 // Pipeline::pick: hit (RtRayHit), adjacent and world (int32[3] each)
 int rth_pipeline_pick(void* p, int x, int y_from_top, RtRayHit* hit, int32_t* adjacent, int32_t* world) {

@@ -52,6 +52,7 @@ Pipeline* create_instance(const RtConfig& cfg, const uint8_t* blue_noise_rgba8, 
     p->region_ = cfg.region;
     p->tile_world_ = cfg.tile_world;
     p->height_ = cfg.height;
+    p->reproject_ = (cfg.flags & RT_FLAG_REPROJECT) != 0;
     std::memset(&p->uniforms_, 0, sizeof(p->uniforms_));
     p->uniforms_.lr[0] = -64; p->uniforms_.lr[1] = -64;    // create_raytrace_uniform_data, render_data.rs:146-147;
     p->uniforms_.lso[0] = -64; p->uniforms_.lso[1] = -64;  // overwritten on the first draw_frame (pipeline.rs:203-207)
@@ -78,6 +79,16 @@ int Pipeline::enable_post_passes(bool faithful) {
     if (tile_world_ != 1) return RT_ERR_UNIMPLEMENTED;   // a 48-pixel halo is needed: gather the tiles, then rt_denoise_planes / rt_finalize_planes
     post_ = true;
     post_faithful_ = faithful;
+    return RT_OK;
+}
+
+int Pipeline::enable_history_denoise(const RtDenoiseParams& params) {
+    bool ok = reproject_ && params.struct_size == sizeof(RtDenoiseParams) && (params.weight_by_count == 0 || params.weight_by_count == 1);
+    for (int i = 0; i < 6; i++) ok = ok && params.settle[i] <= 127u;
+    for (int i = 0; i < 3; i++) ok = ok && params.reserved[i] == 0u;
+    if (!ok) return RT_ERR_INVALID_ARG;
+    history_denoise_ = true;
+    denoise_params_ = params;
     return RT_OK;
 }
 
@@ -161,7 +172,8 @@ int Pipeline::draw_frame(game::Game& game) {
     u.sun_angle = game.get_sun_angle();                              // :202
     rc = rt_draw_frame(ctx_, &u);                                    // :209-211; the dispatch recorded at :86-90
     if (rc == RT_OK && post_) {                                      // the same command buffer goes on (:98-123), one submit (:229-235)
-        rc = rt_denoise(ctx_, post_faithful_ ? 1 : 0);               // six bilateral_denoise.comp dispatches, sizes 1,2,4,8,8,16
+        // six bilateral_denoise.comp dispatches, sizes 1,2,4,8,8,16
+        rc = history_denoise_ ? rt_denoise_history(ctx_, &denoise_params_) : rt_denoise(ctx_, post_faithful_ ? 1 : 0);
         if (rc == RT_OK) rc = rt_finalize(ctx_);                     // finalize.comp -> the swapchain image
     }
     // spp > 1 consumes seeds seed..seed+spp-1; leave the counter on the last one used.

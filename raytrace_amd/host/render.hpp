@@ -90,6 +90,11 @@ class Pipeline {
     // Off by default (the G-buffer planes are then the ray-trace dispatch's own output, which the parity tests compare);
     // whole-frame contexts only (RT_ERR_UNIMPLEMENTED on a tile-split one: the passes need a halo, gather first).
     int enable_post_passes(bool faithful);
+    // With post passes on a context created with RT_FLAG_REPROJECT: draw_frame calls rt_denoise_history(params) in place of
+    // rt_denoise, so that pixels with a long history are not blurred as hard as fresh ones (params.faithful replaces
+    // enable_post_passes' flag for the denoise).  RT_ERR_INVALID_ARG on a context that does not reproject or for a block
+    // rt_denoise_history would refuse.
+    int enable_history_denoise(const RtDenoiseParams& params);
     // A context created with RT_FLAG_FRAMES_IN_FLIGHT_2: draw_frame no longer waits for the previous frame (the library orders a frame
     // after the one that used its slot before), so frame k + 1 is enqueued while frame k runs.  Off by default (the reference's fence).
     void set_frames_in_flight(int n) { no_fence_ = n == 2; }
@@ -118,6 +123,9 @@ class Pipeline {
     int tile_world_ = 1;
     int height_ = 0;                   // frame height (Pipeline::pick counts rows from the top)
     bool post_ = false, post_faithful_ = true;
+    bool reproject_ = false;           // the context was created with RT_FLAG_REPROJECT
+    bool history_denoise_ = false;     // enable_history_denoise
+    RtDenoiseParams denoise_params_{};
     bool no_fence_ = false;            // set_frames_in_flight(2)
     std::unique_ptr<TerrainUploadManager> tum_;
     std::unique_ptr<world::ChunkStorage> chunks_;

@@ -6,7 +6,7 @@
 //
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
 //            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
-//            [--reproject] [--camera-step DX] [--frames-in-flight N] [--edits N [--edit-spread]] [--edit-radius N]
+//            [--reproject [--history-denoise]] [--camera-step DX] [--frames-in-flight N] [--edits N [--edit-spread]] [--edit-radius N]
 //            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
 //
@@ -25,6 +25,8 @@
 // frames on one device).  --camera-step DX: before every frame after the first, DX is added to the camera's origin.x and DX / 100 rad
 // to its heading, so that every frame is a moved one; with --accumulate alone the accumulation then restarts every frame, which is
 // the baseline --reproject is measured against.
+// --history-denoise (with --post --reproject): the denoise is rt_denoise_history with the measured preset (settle 0, 16, 8, 4, 4, 2; no
+// count weighting) in place of rt_denoise (Pipeline::enable_history_denoise); the JSON line then carries "history_denoise": true.
 //
 // --frames-in-flight 2 (one device): the context gets RT_FLAG_FRAMES_IN_FLIGHT_2 and the mirror's draw_frame does not wait for the
 // previous frame (Pipeline::set_frames_in_flight), so frame k + 1 is enqueued while frame k runs, as bench.py does by default; with
@@ -216,7 +218,7 @@ int main(int argc, char** argv) {
     int edits = 0, edit_radius = 0;
     long long rays = 0;
     bool rays_coherent = false;
-    bool reproject = false, stream = false, stream_history = false;
+    bool reproject = false, stream = false, stream_history = false, history_denoise = false;
     float camera_step = 0.0f;
     int frames_in_flight = 1;      // 2: RT_FLAG_FRAMES_IN_FLIGHT_2 and no fence between frames (bench.py's default), one device
     std::string noise_path = "tests/golden/blue_noise_512.rgba";
@@ -236,6 +238,7 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--post") == 0) post = true;
         else if (std::strcmp(argv[i], "--accumulate") == 0) accumulate = true;
         else if (std::strcmp(argv[i], "--reproject") == 0) reproject = accumulate = true;
+        else if (std::strcmp(argv[i], "--history-denoise") == 0) history_denoise = true;
         else if (want("--camera-step")) camera_step = std::strtof(argv[++i], nullptr);
         else if (want("--frames-in-flight")) frames_in_flight = std::atoi(argv[++i]);
         else if (want("--edits")) edits = std::atoi(argv[++i]);
@@ -256,6 +259,7 @@ int main(int argc, char** argv) {
     if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
     if (gpus > 1) gather = true;
+    if (history_denoise && (!post || !reproject)) { std::fprintf(stderr, "--history-denoise goes with --post --reproject\n"); return 2; }
     if (post && gpus > 1) { std::fprintf(stderr, "--post needs the whole frame on one device (gather first on several)\n"); return 2; }
     rt::game::Game game((int)positional.size(), positional.data());
 
@@ -308,6 +312,14 @@ int main(int argc, char** argv) {
         if (stream) pipes[(size_t)g]->enable_terrain_streaming(0x5EED, "", true);   // (the seed of game.generate_world above)
     }
     if (post && pipes[0]->enable_post_passes(true) != RT_OK) { std::fprintf(stderr, "enable_post_passes failed\n"); return 1; }
+    if (history_denoise) {   // the measured preset (raytrace_amd.render.HISTORY_DENOISE_PRESET), the reference's bindings
+        RtDenoiseParams dp{};
+        dp.struct_size = sizeof(dp);
+        dp.faithful = 1;
+        const uint32_t settle[6] = {0, 16, 8, 4, 4, 2};
+        for (int i = 0; i < 6; i++) dp.settle[i] = settle[i];
+        if (pipes[0]->enable_history_denoise(dp) != RT_OK) { std::fprintf(stderr, "enable_history_denoise failed\n"); return 1; }
+    }
     if (gather) {
         int rc = rt_comm_init_all(gpus, devices.data(), comms.data());
         if (rc != RT_OK) { std::fprintf(stderr, "rt_comm_init_all failed (%d): %s\n", rc, rt_last_error(nullptr)); return 1; }
@@ -427,12 +439,12 @@ int main(int argc, char** argv) {
                     "\"ms_per_frame\": %.4f, \"avg_ms_last_120\": %.4f, \"max_ms_last_120\": %.4f, \"mrays_per_s\": %.2f, "
                     "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"reproject\": %s, \"camera_step\": %g, \"samples\": %u, \"acc_frames\": %u, \"edit_radius\": %d, \"stream\": %s, \"stream_history\": %s, "
                     "\"edits\": %d, \"edit_spread\": %s, \"edit_device_ms_per_call\": %.4f, \"edit_launches_per_call\": %.1f, "
-                    "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f}\n",
+                    "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f%s}\n",
                     width, height, spp, depth, gpus, gather ? (overlap ? "rccl-overlapped" : "rccl-serial") : "none", post ? "true" : "false",
                     game.camera.origin[0], game.camera.origin[1], game.camera.origin[2], game.camera.heading, game.camera.pitch,
                     game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum,
                     accumulate ? "true" : "false", reproject ? "true" : "false", (double)camera_step, acc_samples, acc_frames, edit_radius, stream ? "true" : "false", stream_history ? "true" : "false", edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
-                    edit_host_ms, edit_wall_ms);
+                    edit_host_ms, edit_wall_ms, history_denoise ? ", \"history_denoise\": true" : "");
     }
     for (int g = 0; g < gpus; g++) {
         if (comms[(size_t)g]) rt_comm_destroy(comms[(size_t)g]);

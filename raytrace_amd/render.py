@@ -13,7 +13,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RtConfig, RtCounters, RtInfo, RtLightProbe,
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtLightProbe,
                   RtProbeLight, RtRayHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
@@ -39,6 +39,28 @@ def make_config(width, height, spp=1, depth=2, device=0, tile_rank=0, tile_world
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# The measured settle thresholds of rt_denoise_history (DESIGN.md "History-aware denoise"): the size-1 dispatch filters everybody,
+# pixels with 16 / 8 / 4 / 4 / 2 samples or more sit out the dispatches of size 2 / 4 / 8 / 8 / 16, taps are not weighted by their
+# counts.  On the measurement scene this lowers the error against a converged frame over all surface pixels and over those with 8
+# samples or more, in both bindings, and leaves fresh pixels where plain rt_denoise puts them; count weighting lowers the error of
+# old pixels further but raises that of fresh ones, so it is offered and not part of the preset.
+HISTORY_DENOISE_PRESET = dict(weight_by_count=False, settle=(0, 16, 8, 4, 4, 2))
+
+
+def denoise_params(faithful=True, weight_by_count=False, settle=(0, 0, 0, 0, 0, 0)):
+    """An RtDenoiseParams block (include/rt_abi.h); the defaults are the neutral parameters, which give rt_denoise's result."""
+    p = RtDenoiseParams()
+    p.struct_size = C.sizeof(RtDenoiseParams)
+    p.faithful = 1 if faithful else 0
+    p.weight_by_count = 1 if weight_by_count else 0
+    settle = tuple(int(v) for v in settle)
+    if len(settle) != 6:
+        raise ValueError("settle holds one threshold per dispatch: six")
+    for i, v in enumerate(settle):
+        p.settle[i] = v
+    return p
 
 
 # numpy view of RtRayHit (include/rt_abi.h)
@@ -365,6 +387,18 @@ class Context:
         self._check(self._lib.rt_denoise_planes(self._h, C.c_void_p(lighting_ptr), C.c_void_p(depth_ptr), C.c_void_p(normal_ptr),
                                                 1 if faithful else 0))
 
+    def denoise_history(self, params=None, faithful=True):
+        """rt_denoise_history: the six denoise dispatches on the frame drawn last of an RT_FLAG_REPROJECT context, with its per-pixel
+        sample counts.  `params`: an RtDenoiseParams (denoise_params); None = HISTORY_DENOISE_PRESET with `faithful`."""
+        if params is None:
+            params = denoise_params(faithful=faithful, **HISTORY_DENOISE_PRESET)
+        self._check(self._lib.rt_denoise_history(self._h, C.byref(params)))
+
+    def denoise_planes_counted(self, lighting_ptr, depth_ptr, normal_ptr, counts_ptr, params):
+        """rt_denoise_planes_counted: the same on caller-owned row-major device planes and a u32[H, W] device plane of counts."""
+        self._check(self._lib.rt_denoise_planes_counted(self._h, C.c_void_p(lighting_ptr), C.c_void_p(depth_ptr), C.c_void_p(normal_ptr),
+                                                        C.c_void_p(counts_ptr), C.byref(params)))
+
     def finalize_planes(self, albedo_ptr, emission_ptr, fog_ptr, lighting_ptr, depth_ptr, out_ptr):
         self._check(self._lib.rt_finalize_planes(self._h, C.c_void_p(albedo_ptr), C.c_void_p(emission_ptr), C.c_void_p(fog_ptr),
                                                  C.c_void_p(lighting_ptr), C.c_void_p(depth_ptr), C.c_void_p(out_ptr)))
@@ -582,6 +616,16 @@ class Pipeline:
         rc = _lib.host().rth_pipeline_enable_post_passes(self._h, 1 if faithful else 0)
         if rc != 0:
             raise RtError(rc, "enable_post_passes: whole-frame contexts only (tile_world == 1)")
+
+    def enable_history_denoise(self, params=None, faithful=True):
+        """With enable_post_passes on an RT_FLAG_REPROJECT context: draw_frame enqueues rt_denoise_history(params) in place of
+        rt_denoise.  `params` as Context.denoise_history.  RT_ERR_INVALID_ARG on a context that does not reproject or for a bad
+        block."""
+        if params is None:
+            params = denoise_params(faithful=faithful, **HISTORY_DENOISE_PRESET)
+        rc = _lib.host().rth_pipeline_enable_history_denoise(self._h, C.byref(params))
+        if rc != 0:
+            raise RtError(rc, "enable_history_denoise: needs an RT_FLAG_REPROJECT context and a valid RtDenoiseParams")
 
     def pick(self, game, x, y_from_top):
         """The block under screen pixel (x, y_from_top) of the frame drawn last for `game` (Pipeline::pick: the pipeline's current
