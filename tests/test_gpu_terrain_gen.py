@@ -288,3 +288,10 @@ def test_rejections_change_nothing(procedural_region, native_built):
         # the edges of the int32 range are accepted
         ctx.generate_world(world.DEFAULT_SEED, (2 ** 31 - 256, -2 ** 31, 0))
         assert ctx.selftest(MAPS) == 0
+        # ... and hold the host's terrain there: the surface chunk in the corner, which ends at 2^31 in x and starts at -2^31 in y
+        c = (2 ** 25 - 1, -2 ** 25, 0)
+        cs = world.ChunkStorage("", world.DEFAULT_SEED)
+        want = cs.borrow_packed_chunk_data(*c)
+        cs.close()
+        assert (want[1] == 0).any() and (want[1] != 0).any()
+        _same(ctx.read_box(tuple((64 * v + 128) % 256 for v in c), (64, 64, 64)), want, "chunk %s" % (c,))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from raytrace_amd import _lib, world
+from tests import terrain_ref
 from tests.conftest import ROOT
 
 pytestmark = pytest.mark.usefixtures("native_built")
@@ -55,7 +56,7 @@ def test_minefield_is_a_function_of_the_heights(seed):
             assert np.array_equal(mine, want), (cx, cy, cz)
             ids = np.where(mine == 0, 2, 0).astype(np.uint8)          # any solid id: pack_into only sees solidity
             assert np.array_equal(world.pack_chunk(ids)[1], want), (cx, cy, cz)
-            # materials: grass in a deep chunk, air 0, the z bands of material_for_height elsewhere
+            # materials: grass in a deep chunk, air 0, material_for_height (restated in tests/terrain_ref.py) elsewhere
             z = 64 * cz + np.arange(64)[:, None, None] + np.zeros((64, 64, 64), int)
             solid = mine == 0
             assert np.all(mats[~solid] == 0)
@@ -63,8 +64,10 @@ def test_minefield_is_a_function_of_the_heights(seed):
                 assert np.all(mats == GRASS)
             else:
                 assert np.all(mats[solid & (z < 20)] == GRASS) and np.all(mats[solid & (z >= 160)] == ROCK)
-                band = mats[solid & (z >= 20) & (z < 160)]
-                assert np.all(np.isin(band, [GRASS, DIRT, ROCK]))
+                ids = terrain_ref.material_for_height(seed, 64 * cx + np.arange(64)[None, None, :], 64 * cy + np.arange(64)[None, :, None], z)
+                words = np.zeros(7, np.uint32)
+                words[[2, 5, 6]] = GRASS, DIRT, ROCK
+                assert np.array_equal(mats[solid], words[ids][solid])
     finally:
         cs.close()
 
