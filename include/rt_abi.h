@@ -371,7 +371,8 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count);
 int rt_read_box(RtContext* ctx, int x0, int y0, int z0, int ex, int ey, int ez, uint32_t* materials, uint8_t* minefield);
 
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Ray queries against the resident region: what a ray hits, for
- * picking the block under the cursor (then rt_edit_voxels), line of sight, collision and light probes.  One ray, 32 bytes: */
+ * picking the block under the cursor (then rt_edit_voxels), line of sight and light probes (a body with a volume moves by
+ * rt_sweep_boxes: a ray tunnels through corners).  One ray, 32 bytes: */
 typedef struct RtRay {
     float origin[3];     uint32_t reserved0;   /* reserved words are ignored                                                  */
     float direction[3];  uint32_t reserved1;   /* need not be normalized: trace_ray normalizes it (raytrace.comp:83)          */
@@ -476,6 +477,67 @@ int rt_probe_light(RtContext* ctx, const RtUniforms* u, const RtLightProbe* prob
  * are ignored. */
 int rt_probe_light_async(RtContext* ctx, const RtUniforms* u, const RtLightProbe* probes_dev, uint32_t count, uint32_t samples,
                          int32_t depth, RtProbeLight* out_dev);
+
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Box sweeps: an axis-aligned box moved through the resident region until
+ * it meets an occupied voxel — what moves a player, an entity or a particle through the world without passing through it (the
+ * reference's camera flies through terrain: src/game/mod.rs:89-95).  A ray has no volume; a box swept by these rules neither tunnels
+ * through corners nor catches on faces it only touches.  One sweep, 48 bytes: */
+typedef struct RtBoxSweep {      /* 48 bytes */
+    float lo[3];     uint32_t reserved0;   /* world coordinates of the box's low corner  */
+    float hi[3];     uint32_t reserved1;   /* ... and high corner                        */
+    float motion[3]; uint32_t reserved2;   /* displacement over the sweep                */
+} RtBoxSweep;                    /* the reserved words are ignored */
+#define RT_SWEEP_FREE     0   /* travelled the whole motion                        */
+#define RT_SWEEP_BLOCKED  1   /* stopped against an occupied voxel at fraction t   */
+#define RT_SWEEP_EMBEDDED 2   /* overlaps an occupied voxel before moving          */
+#define RT_SWEEP_INVALID  3   /* async only: record outside the validated domain   */
+/* One hit, 64 bytes: */
+typedef struct RtSweepHit {      /* 64 bytes */
+    float    t;  uint32_t kind;  uint32_t normal;  uint32_t material;   /*  0  fraction of the motion travelled; RT_SWEEP_*; face code    */
+    int32_t  texel[3];           uint32_t axis;      /* 16  blocking / embedding texel (RtVoxelEdit's space); blocked axis 0..2, else 3 */
+    float    lo[3];              uint32_t reserved0; /* 32  the box where the sweep ended: the next sweep's box                         */
+    float    hi[3];              uint32_t reserved1; /* 48  (the reserved words are written as 0)                                       */
+} RtSweepHit;
+/* The rules.  All float arithmetic is fp32 with one rounding per operation; once the event times are known everything is integers.
+ * Results are reproduced bit for bit by tests/sweep_ref.py (DESIGN.md "Box sweeps").
+ *   Occupancy: world voxel v (the cell [v, v + 1) per axis) is occupied iff lr - R/2 <= v < lr + R/2 on every axis and the minefield
+ *     byte at texel (v + R/2) mod R (Euclidean; the addressing of rt_upload_slice / rt_generate_*) is 0.  Outside the window is air.
+ *   Cells of a box: per axis the closed integer range c = [floor(lo), ceil(hi) - 1]: a box that touches a face does not overlap the
+ *     cell behind it (a box resting on a floor whose top is z = 10 has lo_z = 10.0 and does not include cell 9).
+ *   Embedded: if a cell of c_x x c_y x c_z is occupied: kind EMBEDDED, t = 0, axis = 3, normal = 6, lo / hi = the inputs, texel /
+ *     material of the first such voxel in ascending (z, y, x) order.
+ *   Events: on every axis a with motion != 0 the leading face (hi moving +, lo moving -) and the trailing face cross integer planes g
+ *     at t = (float(g) - face) / motion (one subtraction, one IEEE division); only events with t < 1 exist.  Moving +: leading planes
+ *     g = ceil(hi), ceil(hi) + 1, ... enter cell layer g; trailing planes g = floor(lo) + 1, ... set c.lo = g.  Moving -: leading planes
+ *     g = floor(lo), floor(lo) - 1, ... enter layer g - 1; trailing planes g = ceil(hi) - 1, ... set c.hi = g - 1.  Order: ascending t
+ *     compared as floats; at equal t trailing before leading; then axis x, y, z.  A leading event tests its layer against the current
+ *     ranges of the other two axes: an occupied cell gives kind BLOCKED, t = the event's, axis = a, texel / material of the first
+ *     occupied cell in (z, y, x) order, normal = the code rt_trace_rays reports for a ray travelling along a in the motion's direction
+ *     (2 a + 1 moving +, 2 a moving -); otherwise the layer joins c.  No event left: kind FREE, t = 1, axis = 3, normal = 6, texel
+ *     (-1, -1, -1), material 0.
+ *   Returned box, per moving axis: lo' = max(lo + motion * t, float(c.lo)), hi' = min(hi + motion * t, float(c.hi + 1)); on the blocked
+ *     axis, with size = hi - lo: moving + hi' = float(g), lo' = max(g - size, float(c.lo)); moving - lo' = float(g), hi' =
+ *     min(g + size, float(c.hi + 1)).  max / min keep the moved face unless it lies beyond the clamp.  An axis with motion == 0 returns
+ *     its input bits.  The clamps close the contract: the returned box, swept again on an unchanged world, is never EMBEDDED (its
+ *     cells are cells this sweep found free).
+ *   Validated domain: every float finite; |lo|, |hi| <= 2^22; per axis 0 < hi - lo <= 8 (the fp32 difference); |motion| <= 64 per
+ *     component.  rt_sweep_boxes checks every record on the host before anything is enqueued (RT_ERR_INVALID_ARG; a rejected call
+ *     changes nothing, `hits` included).  rt_sweep_boxes_async cannot read its records on the host: the device gives a record outside
+ *     the domain kind = RT_SWEEP_INVALID, t = 0, axis = 3, normal = 6, texel (-1, -1, -1), material 0, lo / hi = the input bits, and
+ *     fetches no voxel for it.
+ *   Errors: no world resident: RT_ERR_NOT_READY.  A NULL pointer with count > 0 or count > 2^24: RT_ERR_INVALID_ARG.  count == 0: RT_OK,
+ *     nothing enqueued.
+ *   Which world, ordering and side effects: exactly those of the ray queries — sweeps see every earlier upload, edit, slab and
+ *     generated region and run on the query stream, not after the frames; later world changes wait for them; after
+ *     rt_set_stream(non-NULL) they run on the caller's stream, in order.  No output plane, accumulation sum or history, RtCounters or
+ *     RtTiming changes.  Tile contexts, every RtKernel and every region size answer the same.
+ *   Device work per call: one launch, one lane per sweep (DESIGN.md "Box sweeps"); the synchronous call adds a transfer each way.
+ * Host pointers; returns when the hits are in host memory. */
+int rt_sweep_boxes(RtContext* ctx, const RtBoxSweep* sweeps, uint32_t count, const int32_t lr[3], RtSweepHit* hits);
+/* Same with device pointers, enqueued: the hits are valid after rt_sync (or, after rt_set_stream, in the caller's stream order).  Both
+ * pointers must pass rt_trace_rays_async's test (16-byte aligned memory of the context's device, or managed memory), else
+ * RT_ERR_INVALID_ARG before anything is enqueued; the sweeps must be complete on the device when the call is made. */
+int rt_sweep_boxes_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t count, const int32_t lr[3], RtSweepHit* hits_dev);
 
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Terrain generated on the device: the project's deterministic
  * procedural world (raytrace_amd/host/world.cpp: generate_chunk + pack_into per world chunk, MATERIALS[id].pack()) written straight
@@ -707,7 +769,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtLightProbe, RtProbeLight, RT_PROBE_SPHERE, rt_probe_light, rt_probe_light_async (light
  *        probes: path-traced light at arbitrary points).
  *        Additive, same minor version: RtDenoiseParams, rt_denoise_history, rt_denoise_planes_counted (history-aware denoise:
- *        converged pixels settle, taps may be weighted by their sample counts). */
+ *        converged pixels settle, taps may be weighted by their sample counts).
+ *        Additive, same minor version: RtBoxSweep, RtSweepHit, RT_SWEEP_*, rt_sweep_boxes, rt_sweep_boxes_async (box sweeps: collision
+ *        queries against the resident world). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -22,7 +22,7 @@ ABI_SYMBOLS = (
     "rt_reset_accumulation", "rt_get_accumulation", "rt_edit_voxels", "rt_read_box",
     "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels", "rt_generate_world", "rt_generate_slice", "rt_read_history",
     "rt_edit_boxes_pending", "rt_slabs_pending", "rt_read_slab_boxes", "rt_probe_light", "rt_probe_light_async",
-    "rt_denoise_history", "rt_denoise_planes_counted",
+    "rt_denoise_history", "rt_denoise_planes_counted", "rt_sweep_boxes", "rt_sweep_boxes_async",
 )
 
 _amd = None
@@ -129,6 +129,10 @@ def amd():
         lib.rt_probe_light.restype = C.c_int
         lib.rt_probe_light_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, C.c_uint32, C.c_int32, P]
         lib.rt_probe_light_async.restype = C.c_int
+        lib.rt_sweep_boxes.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
+        lib.rt_sweep_boxes.restype = C.c_int
+        lib.rt_sweep_boxes_async.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
+        lib.rt_sweep_boxes_async.restype = C.c_int
         lib.rt_generate_world.argtypes = [P, C.c_uint64, C.POINTER(C.c_int64)]
         lib.rt_generate_world.restype = C.c_int
         lib.rt_generate_slice.argtypes = [P, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]

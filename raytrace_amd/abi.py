@@ -164,6 +164,25 @@ class RtProbeLight(C.Structure):
 assert C.sizeof(RtLightProbe) == 32 and C.sizeof(RtProbeLight) == 16
 
 
+RT_SWEEP_FREE, RT_SWEEP_BLOCKED, RT_SWEEP_EMBEDDED, RT_SWEEP_INVALID = 0, 1, 2, 3   # RtSweepHit.kind (ABI 1.3, additive: box sweeps)
+
+
+class RtBoxSweep(C.Structure):
+    """rt_sweep_boxes input (ABI 1.3, additive): 48 bytes; the reserved words are ignored."""
+    _fields_ = [("lo", C.c_float * 3), ("reserved0", C.c_uint32), ("hi", C.c_float * 3), ("reserved1", C.c_uint32),
+                ("motion", C.c_float * 3), ("reserved2", C.c_uint32)]
+
+
+class RtSweepHit(C.Structure):
+    """rt_sweep_boxes result (ABI 1.3, additive): 64 bytes."""
+    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("normal", C.c_uint32), ("material", C.c_uint32),
+                ("texel", C.c_int32 * 3), ("axis", C.c_uint32), ("lo", C.c_float * 3), ("reserved0", C.c_uint32),
+                ("hi", C.c_float * 3), ("reserved1", C.c_uint32)]
+
+
+assert C.sizeof(RtBoxSweep) == 48 and C.sizeof(RtSweepHit) == 64
+
+
 class RtDenoiseParams(C.Structure):
     """rt_denoise_history / rt_denoise_planes_counted parameters (ABI 1.3, additive): 48 bytes; `reserved` must be 0."""
     _fields_ = [("struct_size", C.c_uint32), ("faithful", C.c_int32), ("weight_by_count", C.c_int32), ("settle", C.c_uint32 * 6),

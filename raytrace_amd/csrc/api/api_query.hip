@@ -1,5 +1,6 @@
-// api_query.hip — queries against the resident world: ray queries (rt_trace_rays, rt_trace_rays_async, rt_pick_pixels) and light
-// probes (rt_probe_light, rt_probe_light_async), which share their checks, stream and staging.
+// api_query.hip — queries against the resident world: ray queries (rt_trace_rays, rt_trace_rays_async, rt_pick_pixels), light
+// probes (rt_probe_light, rt_probe_light_async) and box sweeps (rt_sweep_boxes, rt_sweep_boxes_async), which share their checks,
+// stream and staging.
 #include "rt_context.hpp"
 
 using namespace rta;
@@ -132,6 +133,36 @@ int probe_launch(RtContext* c, hipStream_t st, const RtUniforms* u, const void* 
     if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
     return RT_OK;
 }
+
+// ---- box sweeps ---------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kMaxSweeps = 1u << 24;
+static_assert(sizeof(RtBoxSweep) == 48 && sizeof(RtSweepHit) == 64, "the kernel reads three and writes four 16-byte words per sweep");
+
+// checks shared by the two calls; RT_OK when there is work to enqueue, 1 for count == 0
+int sweep_check(RtContext* c, const char* fn, uint32_t count, const void* sweeps, const void* lr, const void* hits) {
+    if (count > kMaxSweeps) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": more than 2^24 sweeps in one call");
+    return query_check(c, fn, count, sweeps, lr, hits);
+}
+
+// the validated domain of a record, in the kernel's fp32 operations (a NaN fails every comparison)
+bool sweep_in_domain(const RtBoxSweep& s) {
+    for (int k = 0; k < 3; k++) {
+        const float e = s.hi[k] - s.lo[k];
+        if (!(fabsf(s.lo[k]) <= 4194304.0f && fabsf(s.hi[k]) <= 4194304.0f && fabsf(s.motion[k]) <= 64.0f && e > 0.0f && e <= 8.0f)) return false;
+    }
+    return true;
+}
+
+int sweep_launch(RtContext* c, hipStream_t st, const int32_t lr[3], const void* sweeps_dev, void* hits_dev, uint32_t count) {
+    rtd::SweepArgs a;
+    a.sweeps = reinterpret_cast<const uint4*>(sweeps_dev);
+    a.hits = reinterpret_cast<uint4*>(hits_dev);
+    a.count = count;
+    for (int k = 0; k < 3; k++) a.lr[k] = lr[k];
+    RT_HIP(c, rtd::launch_sweep(scene_of(c), c->logr, a, st));
+    if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
+    return RT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -207,6 +238,44 @@ int rt_probe_light_async(RtContext* ctx, const RtUniforms* u, const RtLightProbe
     rc = query_stream_of(ctx, &st);
     if (rc != RT_OK) return rc;
     return probe_launch(ctx, st, u, probes_dev, out_dev, count, samples, depth);
+}
+
+int rt_sweep_boxes(RtContext* ctx, const RtBoxSweep* sweeps, uint32_t count, const int32_t lr[3], RtSweepHit* hits) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = sweep_check(ctx, "rt_sweep_boxes", count, sweeps, lr, hits);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    for (uint32_t i = 0; i < count; i++)
+        if (!sweep_in_domain(sweeps[i]))
+            return fail(ctx, RT_ERR_INVALID_ARG, "rt_sweep_boxes: sweep " + std::to_string(i) + " is outside the validated domain");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    // the sweeps through pinned and device staging, the launch, the hits back (the previous synchronous call has finished with the
+    // staging: it waited for its results)
+    const size_t in_bytes = (size_t)count * sizeof(RtBoxSweep), out_bytes = (size_t)count * sizeof(RtSweepHit), need = in_bytes + out_bytes;
+    StagingBlock& q = ctx->query_block;
+    RT_HIP(ctx, q.grow(ctx, need, need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(need + need / 2u)));
+    memcpy(q.host, sweeps, in_bytes);
+    RT_HIP(ctx, hipMemcpyAsync(q.dev, q.host, in_bytes, hipMemcpyHostToDevice, st));
+    rc = sweep_launch(ctx, st, lr, q.dev, q.dev + in_bytes, count);
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(q.host + in_bytes, q.dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
+    RT_HIP(ctx, hipStreamSynchronize(st));
+    memcpy(hits, q.host + in_bytes, out_bytes);
+    return RT_OK;
+}
+
+int rt_sweep_boxes_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t count, const int32_t lr[3], RtSweepHit* hits_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = sweep_check(ctx, "rt_sweep_boxes_async", count, sweeps_dev, lr, hits_dev);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, sweeps_dev) || !query_device_ptr(ctx, hits_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_sweep_boxes_async: sweeps and hits must be 16-byte aligned memory of the context's device");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    return sweep_launch(ctx, st, lr, sweeps_dev, hits_dev, count);
 }
 
 }  // extern "C"

@@ -181,6 +181,15 @@ bool probe_sums_in_lds(uint32_t samples);   // a workgroup holds whole probes an
 // pair: a lane steps the shadow and the diffuse ray of a level together (the shipped form); false: one after the other
 hipError_t launch_probe(const Scene& sc, const Frame& f, const ProbeArgs& a, bool pair, hipStream_t st);
 
+// rt_sweep.hip: box sweeps (rt_sweep_boxes).  One lane per sweep; `lr` is the window's centre in world voxels (RtUniforms.lr).
+struct SweepArgs {
+    const uint4* sweeps;  // RtBoxSweep[count] (three uint4 each)
+    uint4* hits;          // RtSweepHit[count] (four uint4 each)
+    uint32_t count;
+    int32_t lr[3];
+};
+hipError_t launch_sweep(const Scene& sc, int logr, const SweepArgs& a, hipStream_t st);
+
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
 // (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
 // or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)

@@ -13,8 +13,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtLightProbe,
-                  RtProbeLight, RtRayHit, RtTiming, RtUniforms, RtVoxelEdit)
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RtBoxSweep, RtConfig,
+                  RtCounters, RtDenoiseParams, RtInfo, RtLightProbe, RtProbeLight, RtRayHit, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
 class RtError(RuntimeError):
@@ -71,6 +71,11 @@ assert HIT_DTYPE.itemsize == C.sizeof(RtRayHit)
 PROBE_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<u4"), ("cell", "<u2", 2), ("reserved", "<u4", 3)])
 PROBE_LIGHT_DTYPE = np.dtype([("light", "<f4", 3), ("sun_samples", "<u4")])
 assert PROBE_DTYPE.itemsize == C.sizeof(RtLightProbe) and PROBE_LIGHT_DTYPE.itemsize == C.sizeof(RtProbeLight)
+# numpy views of RtBoxSweep and RtSweepHit (include/rt_abi.h)
+SWEEP_DTYPE = np.dtype([("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3), ("reserved1", "<u4"), ("motion", "<f4", 3), ("reserved2", "<u4")])
+SWEEP_HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<u4"), ("normal", "<u4"), ("material", "<u4"), ("texel", "<i4", 3), ("axis", "<u4"),
+                            ("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3), ("reserved1", "<u4")])
+assert SWEEP_DTYPE.itemsize == C.sizeof(RtBoxSweep) and SWEEP_HIT_DTYPE.itemsize == C.sizeof(RtSweepHit)
 
 # Texel step from a hit voxel to the empty neighbour in front of the face the ray crossed, per normal code (raytrace.comp:89-93): an
 # even code means the ray travelled towards -axis, so it came from +axis.
@@ -285,6 +290,45 @@ class Context:
         n = check_probe_tensors(probes, out, self.cfg.device if self.cfg is not None else 0)
         self._check(self._lib.rt_probe_light_async(self._h, C.byref(uniforms), C.c_void_p(probes.data_ptr()), n, int(samples), int(depth),
                                                    C.c_void_p(out.data_ptr())))
+
+    # -- box sweeps --------------------------------------------------------------------------------------
+    def sweep_boxes(self, sweeps, lr=(0, 0, 0)):
+        """rt_sweep_boxes: `sweeps` float[N, 3, 3] (lo, hi, motion per row) or SWEEP_DTYPE[N] records -> numpy array of SWEEP_HIT_DTYPE
+        (RtSweepHit) per sweep.  Synchronous; a record outside the validated domain fails the whole call (RtError, INVALID_ARG)."""
+        recs = make_sweeps(sweeps)
+        hits = np.zeros(recs.size, dtype=SWEEP_HIT_DTYPE)
+        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
+        self._check(self._lib.rt_sweep_boxes(self._h, _p(recs), int(recs.size), lr3, _p(hits)))
+        return hits
+
+    def sweep_boxes_async(self, sweeps, hits, lr=(0, 0, 0)):
+        """rt_sweep_boxes_async on torch device tensors: `sweeps` any contiguous tensor of N * 48 bytes (RtBoxSweep rows, e.g.
+        float32[N, 12]), `hits` any contiguous tensor of N * 64 bytes.  Enqueued: valid after sync(), or in the order of a stream
+        given to set_stream().  `sweeps` must be complete on the device when the call is made.  A record outside the validated
+        domain gets kind RT_SWEEP_INVALID."""
+        n = check_sweep_tensors(sweeps, hits, self.cfg.device if self.cfg is not None else 0)
+        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
+        self._check(self._lib.rt_sweep_boxes_async(self._h, C.c_void_p(sweeps.data_ptr()), n, lr3, C.c_void_p(hits.data_ptr())))
+
+    def move_and_slide(self, lo, hi, motion, lr=(0, 0, 0), iterations=3):
+        """The character-controller loop over rt_sweep_boxes: sweep; on BLOCKED take the returned box, zero the blocked axis of
+        motion * (1 - t) and sweep again; stop on FREE, on a zero remainder or after `iterations` sweeps (an EMBEDDED start stops at
+        once, where it is).  Returns (lo, hi, hits): the final box as float32[3] arrays and the list of SWEEP_HIT_DTYPE records."""
+        lo, hi, m = (np.asarray(v, dtype=np.float32).reshape(3).copy() for v in (lo, hi, motion))
+        hits = []
+        for _ in range(int(iterations)):
+            h = self.sweep_boxes(np.stack([lo, hi, m])[None], lr)[0]
+            hits.append(h)
+            if h["kind"] not in (RT_SWEEP_FREE, RT_SWEEP_BLOCKED):
+                break
+            lo, hi = h["lo"].copy(), h["hi"].copy()
+            if h["kind"] == RT_SWEEP_FREE:
+                break
+            m = m * (np.float32(1.0) - h["t"])
+            m[int(h["axis"])] = 0
+            if not m.any():
+                break
+        return lo, hi, hits
 
     # -- frames ------------------------------------------------------------------------------------------
     def draw_frame(self, uniforms):
@@ -704,6 +748,41 @@ def check_query_tensors(rays, hits, device):
     n = int(rays.shape[0])
     if not hits.is_contiguous() or hits.numel() * hits.element_size() != n * HIT_DTYPE.itemsize:
         raise ValueError("hits must be a contiguous tensor of N * 48 bytes")
+    return n
+
+
+def make_sweeps(sweeps):
+    """RtBoxSweep records (SWEEP_DTYPE) from float[N, 3, 3] rows of (lo, hi, motion); ready records pass through."""
+    if isinstance(sweeps, np.ndarray) and sweeps.dtype == SWEEP_DTYPE:
+        return np.ascontiguousarray(sweeps).reshape(-1)
+    a = np.asarray(sweeps, dtype=np.float32)
+    if a.size % 9:
+        raise ValueError("sweeps must hold rows of lo[3], hi[3], motion[3]")
+    a = a.reshape(-1, 3, 3)
+    recs = np.zeros(a.shape[0], dtype=SWEEP_DTYPE)
+    recs["lo"], recs["hi"], recs["motion"] = a[:, 0], a[:, 1], a[:, 2]
+    return recs
+
+
+def check_sweep_tensors(sweeps, hits, device):
+    """Context.sweep_boxes_async's arguments: contiguous tensors of N * 48 and N * 64 bytes on GPU `device`, 16-byte aligned.
+    Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
+    import torch
+    if not isinstance(sweeps, torch.Tensor) or not isinstance(hits, torch.Tensor):
+        raise ValueError("sweeps and hits must be torch tensors")
+    for name, t in (("sweeps", sweeps), ("hits", hits)):
+        if not t.is_cuda or t.device.index != int(device):
+            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    nbytes = sweeps.numel() * sweeps.element_size()
+    if nbytes % SWEEP_DTYPE.itemsize:
+        raise ValueError("sweeps must hold whole 48-byte RtBoxSweep records")
+    n = nbytes // SWEEP_DTYPE.itemsize
+    if hits.numel() * hits.element_size() != n * SWEEP_HIT_DTYPE.itemsize:
+        raise ValueError("hits must be a contiguous tensor of N * 64 bytes")
     return n
 
 
