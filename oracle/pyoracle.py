@@ -142,6 +142,22 @@ def diffuse_direction(normal, noise_rg):
     return np.array(o[:], dtype=np.float32)
 
 
+def diffuse_direction_n(normal, noise_rg):
+    """diffuse_direction() of every (noise.r, noise.g) of float32[N, 2] on one face in one call: float32[N, 3]."""
+    rg = np.ascontiguousarray(noise_rg, dtype=np.float32).reshape(-1, 2)
+    out = np.empty((rg.shape[0], 3), dtype=np.float32)
+    lib().rt_oracle_diffuse_direction_n(C.c_uint32(int(normal)), _p(rg), _p(out), C.c_size_t(rg.shape[0]))
+    return out
+
+
+def sample_sky_n(directions, sun_angle, include_sun):
+    """sample_sky() of every direction of float32[N, 3] in one call: float32[N, 3]."""
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    out = np.empty_like(d)
+    lib().rt_oracle_sample_sky_n(_p(d), C.c_float(float(sun_angle)), C.c_int(int(bool(include_sun))), _p(out), C.c_size_t(d.shape[0]))
+    return out
+
+
 def noise_lookup(noise, seed, px, py):
     noise = np.ascontiguousarray(noise, dtype=np.uint8).reshape(-1)
     base = (C.c_int32 * 2)()

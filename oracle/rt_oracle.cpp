@@ -655,6 +655,13 @@ void rt_oracle_diffuse_direction(uint32_t normal, const float* noise_rg, float* 
     vec3 d = diffuse_direction(normal, {noise_rg[0], noise_rg[1], 0, 0});
     out3[0] = d.x; out3[1] = d.y; out3[2] = d.z;
 }
+// The two above for n inputs in one call (every (face, noise byte pair) entry of the kernels' direction tables).
+void rt_oracle_sample_sky_n(const float* dir3, float sun_angle, int include_sun, float* out3, size_t n) {
+    for (size_t i = 0; i < n; i++) rt_oracle_sample_sky(dir3 + 3 * i, sun_angle, include_sun, out3 + 3 * i);
+}
+void rt_oracle_diffuse_direction_n(uint32_t normal, const float* noise_rg, float* out3, size_t n) {
+    for (size_t i = 0; i < n; i++) rt_oracle_diffuse_direction(normal, noise_rg + 2 * i, out3 + 3 * i);
+}
 
 // Forward thread -> pixel map of raytrace.comp:291-294 for one axis, and its inverse.
 uint32_t rt_oracle_pixel_of(uint32_t workgroup, uint32_t local) {

@@ -63,6 +63,43 @@ def diffuse_direction(normal, noise_rg):
     return d / np.linalg.norm(d)
 
 
+def sphere_point_n(noise_rg):
+    """raytrace.comp:190-197 for float64[N, 2] noise values: the unit-sphere points float64[N, 3] (before the face is added)."""
+    rg = np.asarray(noise_rg, dtype=np.float64)
+    theta1 = np.pi * 2.0 * rg[:, 0]
+    theta2 = np.arccos(1.0 - 2.0 * rg[:, 1])
+    return np.stack([np.sin(theta1) * np.sin(theta2), np.cos(theta1) * np.sin(theta2), np.cos(theta2)], axis=-1)
+
+
+def diffuse_direction_n(normal, noise_rg):
+    """diffuse_direction for float64[N, 2] noise values on one face: (directions float64[N, 3], |vector| before :211's normalize).
+    A vector of length 0 gives NaN, as the shader's 0 / 0 does."""
+    d = sphere_point_n(noise_rg)
+    d[:, normal // 2] += 1.0 if normal % 2 == 0 else -1.0
+    length = np.linalg.norm(d, axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return d / length[:, None], length
+
+
+def sample_sky_n(directions, sun_direction, sunlight, include_sun):
+    """sample_sky for float64[N, 3] directions: (colours float64[N, 3], sun_amount float64[N])."""
+    d = np.asarray(directions, dtype=np.float64)
+    sunlight = np.asarray(sunlight, dtype=np.float64)
+    bright_color = np.array([0.5294, 0.8275, 0.9647])
+    dark_color = np.array([0.0863, 0.1294, 0.2196])
+    sunlight_amount = min(max(float(sunlight.sum()) * 0.2 - 0.02, 0.0), 1.0)
+    horizon = np.hypot(d[:, 0], d[:, 1]) ** float(mix(40.0, 10.0, sunlight_amount))
+    sun_amount = 1.0 - 0.5 * np.linalg.norm(np.asarray(sun_direction, dtype=np.float64) - d, axis=-1)
+    sun_halo_amount = sun_amount ** float(mix(5.0, 1.0, sunlight_amount))
+    bright_amount = np.minimum(horizon + sun_halo_amount * 0.5, 1.0)
+    a = (bright_amount * max(sunlight_amount, 0.1))[:, None]
+    color = dark_color * (1.0 - a) + bright_color * a
+    color = color + sunlight * (sun_amount ** 5.0 * 0.5)[:, None]
+    if include_sun:
+        color = color + sunlight * (sun_amount > 0.98)[:, None]
+    return color, sun_amount
+
+
 def sun_ray_direction(sun_direction, noise_rg):
     """raytrace.comp:185-187 — normalize(direction + vec3(noise_value.rg, 0) * 0.05)."""
     v = np.asarray(sun_direction) + np.array([noise_rg[0], noise_rg[1], 0.0]) * 0.05
