@@ -364,6 +364,46 @@ typedef struct RtVoxelEdit {
  * Device work per call: one launch that scatters the material words and rebuilds the touched chunks (one workgroup per chunk), one
  * that rebuilds their nibble-map words (counted by RT_FLAG_TIMING_ALL). */
 int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count);
+
+/* (ABI 1.3, additive; hosts detect the feature by the rt_edit_shapes symbol) Shape edits: boxes and spheres filled, painted or
+ * carved on the device — an explosion, a build tool, a brush.  A shape is 32 bytes whatever its volume: */
+#define RT_SHAPE_BOX    0
+#define RT_SHAPE_SPHERE 1
+#define RT_WHERE_ALL    0   /* every voxel of the shape is selected                   */
+#define RT_WHERE_SOLID  1   /* only voxels that are occupied at that moment (paint)   */
+#define RT_WHERE_AIR    2   /* only voxels that are not (fill without overwriting)    */
+typedef struct RtShapeEdit {      /* 32 bytes */
+    int32_t  a[3];      /*  0  BOX: low corner, texels, inclusive.  SPHERE: twice the centre, in half texels */
+    uint32_t material;  /* 12  written as is to every selected voxel                                        */
+    int32_t  b[3];      /* 16  BOX: high corner, inclusive.  SPHERE: b[0] = (2 r)^2, b[1] = b[2] = 0         */
+    uint8_t  kind, where, solid, reserved;   /* 28  solid: 0 air, non-zero occupied; reserved must be 0     */
+} RtShapeEdit;
+/* rt_edit_shapes — apply `count` shapes to the resident region, in batch order, each to the world the previous one left.  All of
+ * it is integer arithmetic, so the result is exact.
+ *   Coordinates: texels, the space of RtVoxelEdit; a voxel's centre in half texels is 2 x + 1.
+ *   Membership: BOX a[k] <= x_k <= b[k] on every axis; SPHERE sum_k (2 x_k + 1 - a[k])^2 <= b[0] (radius 3.5 round voxel
+ *     (10, 10, 10): a = (21, 21, 21), b[0] = 49; with b[0] = 0 an odd `a` selects one voxel and an even `a` none).
+ *   Clipping: a shape may reach or lie outside [0, R)^3; only its voxels inside count.  A host applies a shape that crosses the
+ *     window's seam by issuing it again shifted by +-R texels (+-2 R in `a` of a sphere).  The shape's BOUNDING BOX is, per axis,
+ *     the texels of [0, R) that pass that axis's own test (a box's range; a sphere's (2 x + 1 - a[k])^2 <= b[0]); a shape whose
+ *     bounding box is empty on an axis does nothing.
+ *   Selection: `where` narrows the shape to the voxels that are occupied (minefield 0) or not at that moment, earlier shapes of
+ *     the call included.  A selected voxel gets `material` and its occupancy becomes `solid`; any other voxel keeps both.
+ *   Touched chunks: every 64^3 chunk that meets the bounding box of at least one shape — whether or not a voxel of it is
+ *     selected — gets its whole minefield rebuilt by rt_edit_voxels' rule and its nibble-map words rebuilt; every other chunk
+ *     keeps its bytes.  In a chunk that holds a selected voxel the result equals rt_edit_voxels with one record per selected
+ *     voxel in shape order.
+ *   Validation: on the host, before anything is enqueued; a rejected call changes nothing.  RT_ERR_INVALID_ARG: count > 4096; a
+ *     NULL pointer with count > 0; kind > 1, where > 2 or reserved != 0; an a[k] or a box's b[k] outside [-4 R, 4 R]; a box with
+ *     a[k] > b[k]; a sphere with b[0] outside [0, 2^26] or b[1], b[2] != 0 (the sphere's sum then stays below 2^27).  No world
+ *     resident: RT_ERR_NOT_READY.  count == 0, or a call that touches no chunk: RT_OK, nothing is enqueued or reset.
+ *   Ordering, staging, accumulation: rt_edit_voxels' — stream-ordered after the frames and queries already submitted and before
+ *     later ones, also under rt_set_stream; the same two staging sets, so that shapes, voxel edits and slabs apply in call order.
+ *     A call that touches a chunk resets RT_FLAG_ACCUMULATE's sum — except with RtConfig.edit_radius > 0, where it records one
+ *     pending box per shape that has a bounding box (that box, in shape order; at most 16 wait, rt_edit_boxes_pending).
+ * Device work per call: one launch that applies the shapes and rebuilds the touched chunks (one workgroup per chunk; only the
+ * shape records and the chunk list travel), one that rebuilds their nibble-map words (counted by RT_FLAG_TIMING_ALL). */
+int rt_edit_shapes(RtContext* ctx, const RtShapeEdit* shapes, uint32_t count);
 /* Un-tile the box [x0, x0 + ex) x [y0, y0 + ey) x [z0, z0 + ez) of the resident region (texel coordinates) into the caller's layout:
  * materials u32[ex ey ez], minefield u8[ex ey ez], x fastest; either pointer may be NULL.  Waits for everything submitted before
  * (the region as the next frame would see it), then synchronises.  A box outside the region (or an extent < 1) returns
@@ -771,7 +811,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtDenoiseParams, rt_denoise_history, rt_denoise_planes_counted (history-aware denoise:
  *        converged pixels settle, taps may be weighted by their sample counts).
  *        Additive, same minor version: RtBoxSweep, RtSweepHit, RT_SWEEP_*, rt_sweep_boxes, rt_sweep_boxes_async (box sweeps: collision
- *        queries against the resident world). */
+ *        queries against the resident world).
+ *        Additive, same minor version: RtShapeEdit, RT_SHAPE_*, RT_WHERE_*, rt_edit_shapes (shape edits: boxes and spheres filled
+ *        or carved on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

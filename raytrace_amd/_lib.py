@@ -3,7 +3,7 @@ import fails loudly (build it with `python -m raytrace_amd.build`)."""
 import ctypes as C
 import os
 
-from .abi import RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtTiming, RtUniforms, RtVoxelEdit
+from .abi import RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtShapeEdit, RtTiming, RtUniforms, RtVoxelEdit
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_AMD_LIB: load another build of the same library (same-box A/B timing of two kernel variants, tools/ab.sh)
@@ -23,6 +23,7 @@ ABI_SYMBOLS = (
     "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels", "rt_generate_world", "rt_generate_slice", "rt_read_history",
     "rt_edit_boxes_pending", "rt_slabs_pending", "rt_read_slab_boxes", "rt_probe_light", "rt_probe_light_async",
     "rt_denoise_history", "rt_denoise_planes_counted", "rt_sweep_boxes", "rt_sweep_boxes_async",
+    "rt_edit_shapes",
 )
 
 _amd = None
@@ -117,6 +118,8 @@ def amd():
         lib.rt_read_slab_boxes.restype = C.c_int
         lib.rt_edit_voxels.argtypes = [P, C.POINTER(RtVoxelEdit), C.c_uint32]
         lib.rt_edit_voxels.restype = C.c_int
+        lib.rt_edit_shapes.argtypes = [P, C.POINTER(RtShapeEdit), C.c_uint32]
+        lib.rt_edit_shapes.restype = C.c_int
         lib.rt_read_box.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]
         lib.rt_read_box.restype = C.c_int
         lib.rt_trace_rays.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]

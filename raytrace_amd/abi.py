@@ -131,6 +131,19 @@ class RtVoxelEdit(C.Structure):
 assert C.sizeof(RtVoxelEdit) == 16
 
 
+RT_SHAPE_BOX, RT_SHAPE_SPHERE = 0, 1                # RtShapeEdit.kind (ABI 1.3, additive: shape edits)
+RT_WHERE_ALL, RT_WHERE_SOLID, RT_WHERE_AIR = 0, 1, 2   # RtShapeEdit.where
+
+
+class RtShapeEdit(C.Structure):
+    """rt_edit_shapes record (ABI 1.3, additive): one box or sphere, 32 bytes; `reserved` must be 0."""
+    _fields_ = [("a", C.c_int32 * 3), ("material", C.c_uint32), ("b", C.c_int32 * 3), ("kind", C.c_uint8), ("where", C.c_uint8),
+                ("solid", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+assert C.sizeof(RtShapeEdit) == 32
+
+
 RT_HIT_AIR, RT_HIT_SOLID, RT_HIT_LIMIT = 0, 1, 2   # RtRayHit.kind (ABI 1.3, additive: ray queries)
 
 

@@ -1,5 +1,5 @@
-// api_world.hip — the three kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits,
-// and terrain generated on the device; rt_read_box reads the resident region back.
+// api_world.hip — the kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits, shape
+// edits and terrain generated on the device; rt_read_box reads the resident region back.
 #include "rt_context.hpp"
 
 using namespace rta;
@@ -278,6 +278,54 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
     {
         LaunchTimer lt(ctx, 1);
         RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, bins.touched, ctx->logr, ctx->stream));
+    }
+    RT_HIP(ctx, staging_applied(ctx, s));
+    return RT_OK;
+}
+
+int rt_edit_shapes(RtContext* ctx, const RtShapeEdit* shapes, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (count > kMaxShapes) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_shapes: more than 4096 shapes in one call; nothing was applied");
+    if (count == 0) return RT_OK;
+    if (!shapes) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_shapes: null shapes");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_edit_shapes: upload the full region first");
+    // Validation, bounding boxes and the touched chunks on the host, all of it before anything is enqueued (edit_shapes.hpp)
+    const uint32_t bad = shapes_validate(shapes, count, ctx->logr);
+    if (bad != count)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_shapes: shape " + std::to_string(bad) +
+                                                 " has a bad kind, where or reserved, a coordinate outside [-4R, 4R], a box with a > b or a"
+                                                 " sphere with b[0] outside [0, 2^26] or b[1], b[2] != 0; nothing was applied");
+    const ShapePlan plan = shapes_touched(ctx->shape_scratch, shapes, count, ctx->logr);
+    if (plan.touched == 0u) return RT_OK;   // (every shape lies outside the region: nothing is enqueued, nothing is reset)
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    // rt_edit_voxels' staging sets and counter, so that shapes and voxel edits apply in call order: the chunk ids, then the records
+    StagingSet& s = ctx->edit_sets[ctx->edit_batches & 1u];
+    const size_t cap = plan.need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(plan.need + plan.need / 2u);   // (if the set must grow)
+    RT_HIP(ctx, staging_claim(ctx, s, plan.need, cap));
+    shapes_fill_chunks(ctx->shape_scratch, reinterpret_cast<uint32_t*>(s.host));
+    memcpy(s.host + plan.off_shapes, shapes, (size_t)count * sizeof(RtShapeEdit));
+    ctx->edit_batches++;
+    if (ctx->edit_radius == 0u) {
+        ctx->accum_valid = false;
+    } else if (!ctx->edit_overflow) {
+        // the history stays: one box per shape that has a bounding box waits for the next frame drawn (rt_edit_voxels' set and rule)
+        if (ctx->edit_nbox + plan.boxes > rtd::kTemporalMaxBoxes) {
+            ctx->edit_nbox = 0;
+            ctx->edit_overflow = true;
+        } else {
+            ctx->edit_nbox += shape_pending_boxes(shapes, count, ctx->logr, ctx->edit_boxes + ctx->edit_nbox);
+        }
+    }
+    invalidate_prepass(ctx);
+    RT_HIP(ctx, staging_send(ctx, s, plan.need));
+    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
+    {
+        LaunchTimer lt(ctx, 1);
+        RT_HIP(ctx, rtd::launch_shape_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, s.dev + plan.off_shapes, count, plan.touched, ctx->logr, ctx->stream));
+    }
+    {
+        LaunchTimer lt(ctx, 1);
+        RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, plan.touched, ctx->logr, ctx->stream));
     }
     RT_HIP(ctx, staging_applied(ctx, s));
     return RT_OK;

@@ -1,8 +1,10 @@
-// rt_edit.hip — gfx950 kernels of rt_edit_voxels.
+// rt_edit.hip — gfx950 kernels of rt_edit_voxels and rt_edit_shapes.
 //
 //   k_rebuild_chunks   : one workgroup per touched 64^3 chunk: scatters the chunk's edited material words, loads its occupancy
 //                        (minefield == 0) into an LDS bitmap, applies the edits' solid bits, builds the OR pyramid of levels 1..6
 //                        and writes the chunk's whole minefield back with pack_into's rule (src/world/chunk.rs:125-184)
+//   k_shape_chunks     : the same chunk rebuild (rebuild_chunk) with another edit stage: the batch's boxes and spheres, applied in
+//                        order to the bitmap rows a thread owns, their material words stored by that thread
 //   k_rebuild_chunk_maps: the coarse (and, above R = 256, brick) nibble-map words that cover the touched chunks (rt_world.hpp's rule)
 #include <hip/hip_runtime.h>
 
@@ -38,12 +40,12 @@ __device__ __forceinline__ uint32_t or_pairs64(uint64_t v) {
 
 }  // namespace
 
-// One workgroup (16 waves) per touched chunk.  chunks[blockIdx.x] = (cz * n + cy) * n + cx with n = R / 64 chunks per axis; the
-// chunk's edits are recs[offs[i] .. offs[i + 1]): .x = local index (z << 12 | y << 6 | x) | solid << 18, .y = material word, each
-// voxel at most once (the host keeps the last edit of a voxel).  Chunks are distinct, so workgroups never touch the same bytes.
-__global__ __launch_bounds__(1024) void k_rebuild_chunks(uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ mat_sw,
-                                                         const uint32_t* __restrict__ chunks, const uint32_t* __restrict__ offs,
-                                                         const uint2* __restrict__ recs, int logr) {
+// The rebuild of one chunk by one workgroup of 1024 threads (16 waves): chunks[blockIdx.x] = (cz * n + cy) * n + cx with n = R / 64
+// chunks per axis.  `stage(occ0, cx, cy, cz, lb, tid)` is the edit stage: it runs between two barriers on the loaded level 0
+// bitmap, changes its bits and stores the material words of what it changes.  Chunks are distinct, so workgroups never touch the
+// same bytes.
+template <typename Stage>
+__device__ __forceinline__ void rebuild_chunk(uint8_t* __restrict__ mine_sw, const uint32_t* __restrict__ chunks, int logr, const Stage& stage) {
     __shared__ uint32_t occ0[2 * 64 * kRow0Stride];   // 33280 B: level 0 bitmap
     __shared__ uint32_t occ1[32 * kRow1Stride];       //  4224 B: level 1 rows
     __shared__ uint8_t occ2[16 * 16 * 16];            //  4096 B: levels 2..5, one byte per cell
@@ -85,16 +87,7 @@ __global__ __launch_bounds__(1024) void k_rebuild_chunks(uint8_t* __restrict__ m
     __syncthreads();
 
     // ---- edits: material words to the region, solid bits to the bitmap -------------------------------------------------
-    const uint32_t e0 = offs[blockIdx.x], e1 = offs[blockIdx.x + 1];
-    for (uint32_t e = e0 + tid; e < e1; e += 1024u) {
-        const uint2 rec = recs[e];
-        const int x = rec.x & 63u, y = (rec.x >> 6) & 63u, z = (rec.x >> 12) & 63u;
-        const int w = 2 * (z * kRow0Stride + y) + (x >> 5);
-        const uint32_t bit = 1u << (x & 31);
-        if (rec.x & (1u << 18)) atomicOr(&occ0[w], bit);
-        else atomicAnd(&occ0[w], ~bit);
-        mat_sw[swizzled_index((int)(cx * 64u) + x, (int)(cy * 64u) + y, (int)(cz * 64u) + z, lb)] = rec.y;
-    }
+    stage(occ0, cx, cy, cz, lb, tid);
     __syncthreads();
 
     // ---- OR pyramid ----------------------------------------------------------------------------------------------------
@@ -168,6 +161,132 @@ __global__ __launch_bounds__(1024) void k_rebuild_chunks(uint8_t* __restrict__ m
     }
 }
 
+namespace {
+
+// rt_edit_voxels' edit stage.  The chunk's edits are recs[offs[i] .. offs[i + 1]): .x = local index (z << 12 | y << 6 | x) |
+// solid << 18, .y = material word, each voxel at most once (the host keeps the last edit of a voxel).
+struct RecordStage {
+    uint32_t* __restrict__ mat_sw;
+    const uint32_t* __restrict__ offs;
+    const uint2* __restrict__ recs;
+    __device__ __forceinline__ void operator()(uint32_t* occ0, uint32_t cx, uint32_t cy, uint32_t cz, int lb, int tid) const {
+        const uint32_t e0 = offs[blockIdx.x], e1 = offs[blockIdx.x + 1];
+        for (uint32_t e = e0 + tid; e < e1; e += 1024u) {
+            const uint2 rec = recs[e];
+            const int x = rec.x & 63u, y = (rec.x >> 6) & 63u, z = (rec.x >> 12) & 63u;
+            const int w = 2 * (z * kRow0Stride + y) + (x >> 5);
+            const uint32_t bit = 1u << (x & 31);
+            if (rec.x & (1u << 18)) atomicOr(&occ0[w], bit);
+            else atomicAnd(&occ0[w], ~bit);
+            mat_sw[swizzled_index((int)(cx * 64u) + x, (int)(cy * 64u) + y, (int)(cz * 64u) + z, lb)] = rec.y;
+        }
+    }
+};
+
+// bits lo..hi of a 64-voxel row, clipped to it (none when the range misses the row)
+__device__ __forceinline__ uint64_t row_range(int lo, int hi) {
+    const int l = lo < 0 ? 0 : lo > 63 ? 63 : lo, h = hi < 0 ? 0 : hi > 63 ? 63 : hi;
+    return (lo > hi || hi < 0 || lo > 63) ? 0ull : (~0ull >> (63 - h)) & (~0ull << l);
+}
+// floor(sqrt(v)) for 0 <= v <= 2^26, bit by bit (the host's rule, api/edit_shapes.hpp)
+__device__ __forceinline__ int isqrt26(int v) {
+    int s = 0;
+#pragma unroll
+    for (int bit = 1 << 13; bit; bit >>= 1) {
+        const int t = s | bit;
+        s = t * t <= v ? t : s;
+    }
+    return s;
+}
+// the least |2 x + 1 - a| over the 64 texels x0 .. x0 + 63
+__device__ __forceinline__ int sphere_gap(int a, int x0) {
+    const int lo = 2 * x0 + 1, hi = 2 * x0 + 127;
+    return a < lo ? lo - a : a > hi ? a - hi : 1 - (a & 1);
+}
+
+// rt_edit_shapes' edit stage.  shapes[2 s], shapes[2 s + 1] = RtShapeEdit s as two dword4: (a, material), (b, kind | where << 8 |
+// solid << 16).  Thread t owns the rows (z, y) = ((t >> 6) + 16 j, t & 63), j = 0..3, for EVERY shape: it keeps them in registers
+// through the batch, so the bitmap needs no atomics, and every store to a voxel's material word comes from that one thread in
+// program order — the last shape wins.  The loop and a shape's fields are uniform across the workgroup (scalar loads).
+struct ShapeStage {
+    uint32_t* __restrict__ mat_sw;
+    const int4* __restrict__ shapes;
+    uint32_t nshapes;
+    __device__ __forceinline__ void operator()(uint32_t* occ0, uint32_t cx, uint32_t cy, uint32_t cz, int lb, int tid) const {
+        const int x0 = (int)(cx * 64u), y0 = (int)(cy * 64u), z0 = (int)(cz * 64u);
+        const int ly = tid & 63, lz = tid >> 6, y = y0 + ly;
+        uint64_t row[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) row[j] = occ_row0(occ0, lz + 16 * j, ly);
+        for (uint32_t s = 0; s < nshapes; s++) {
+            const int4 p = shapes[2u * s], q = shapes[2u * s + 1u];
+            const uint32_t kind = (uint32_t)q.w & 0xFFu, where = ((uint32_t)q.w >> 8) & 0xFFu;
+            const bool solid = (((uint32_t)q.w >> 16) & 0xFFu) != 0u;
+            const uint32_t material = (uint32_t)p.w;
+            // a shape whose bounding box misses the chunk selects nothing in it
+            if (kind == 0u) {
+                if (p.x > x0 + 63 || q.x < x0 || p.y > y0 + 63 || q.y < y0 || p.z > z0 + 63 || q.z < z0) continue;
+            } else {
+                const int gx = sphere_gap(p.x, x0), gy = sphere_gap(p.y, y0), gz = sphere_gap(p.z, z0);
+                if (gx * gx > q.x || gy * gy > q.x || gz * gz > q.x) continue;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int z = z0 + lz + 16 * j;
+                uint64_t m;
+                if (kind == 0u) {
+                    m = (y >= p.y && y <= q.y && z >= p.z && z <= q.z) ? row_range(p.x - x0, q.x - x0) : 0ull;
+                } else {
+                    // what is left of (2 r)^2 for x: every term is below 2^26, so int32 is exact
+                    const int dy = 2 * y + 1 - p.y, dz = 2 * z + 1 - p.z;
+                    const int budget = q.x - dy * dy - dz * dz;
+                    const int r = isqrt26(budget < 0 ? 0 : budget);
+                    // a - r <= 2 x + 1 <= a + r: x from ceil((a - r - 1) / 2) to floor((a + r - 1) / 2)
+                    m = budget < 0 ? 0ull : row_range(((p.x - r) >> 1) - x0, ((p.x + r - 1) >> 1) - x0);
+                }
+                uint64_t sel = where == 0u ? m : where == 1u ? (m & row[j]) : (m & ~row[j]);
+                row[j] = solid ? (row[j] | sel) : (row[j] & ~sel);
+                // material words: the four x of one brick are 16 contiguous bytes of the swizzled array
+                while (sel) {
+                    const int g = (int)(__ffsll((unsigned long long)sel) - 1) >> 2;
+                    const uint32_t nib = (uint32_t)(sel >> (4 * g)) & 0xFu;
+                    uint32_t* dst = mat_sw + swizzled_index(x0 + 4 * g, y, z, lb);
+                    if (nib == 0xFu) {
+                        *reinterpret_cast<uint4*>(dst) = make_uint4(material, material, material, material);
+                    } else {
+#pragma unroll
+                        for (int xi = 0; xi < 4; xi++)
+                            if ((nib >> xi) & 1u) dst[xi] = material;
+                    }
+                    sel &= ~(0xFull << (4 * g));
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int w = 2 * ((lz + 16 * j) * kRow0Stride + ly);
+            occ0[w] = (uint32_t)row[j];
+            occ0[w + 1] = (uint32_t)(row[j] >> 32);
+        }
+    }
+};
+
+}  // namespace
+
+// One workgroup (16 waves) per touched chunk: chunks[blockIdx.x] is its id, recs[offs[i] .. offs[i + 1]) its edits (RecordStage).
+__global__ __launch_bounds__(1024) void k_rebuild_chunks(uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ mat_sw,
+                                                         const uint32_t* __restrict__ chunks, const uint32_t* __restrict__ offs,
+                                                         const uint2* __restrict__ recs, int logr) {
+    rebuild_chunk(mine_sw, chunks, logr, RecordStage{mat_sw, offs, recs});
+}
+
+// One workgroup per chunk that meets a shape's bounding box; every workgroup walks the whole batch (ShapeStage).
+__global__ __launch_bounds__(1024) void k_shape_chunks(uint8_t* __restrict__ mine_sw, uint32_t* __restrict__ mat_sw,
+                                                       const uint32_t* __restrict__ chunks, const int4* __restrict__ shapes,
+                                                       uint32_t nshapes, int logr) {
+    rebuild_chunk(mine_sw, chunks, logr, ShapeStage{mat_sw, shapes, nshapes});
+}
+
 // The nibble-map words over the touched chunks, after k_rebuild_chunks: one workgroup per chunk.  A coarse cube has edge R/64, so a
 // chunk holds 4096/R cubes per axis (16, 8, 4); at R = 1024 a word's 8 cubes span two chunks along x and the other chunk's half is
 // recomputed from its unchanged bytes (two touched neighbours both write the same value).  R > 256: the chunk's 16^3 bricks as well.
@@ -200,6 +319,13 @@ hipError_t launch_rebuild_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint3
                                  uint32_t nchunks, int logr, hipStream_t st) {
     if (nchunks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_rebuild_chunks, dim3(nchunks), dim3(1024), 0, st, mine_sw, mat_sw, chunks, offs, recs, logr);
+    return hipGetLastError();
+}
+
+hipError_t launch_shape_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const void* shapes, uint32_t nshapes,
+                               uint32_t nchunks, int logr, hipStream_t st) {
+    if (nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_shape_chunks, dim3(nchunks), dim3(1024), 0, st, mine_sw, mat_sw, chunks, static_cast<const int4*>(shapes), nshapes, logr);
     return hipGetLastError();
 }
 

@@ -141,6 +141,9 @@ hipError_t launch_read_box(const uint8_t* mine_sw, const uint32_t* mat_sw, int l
 // rt_edit.hip: rt_edit_voxels (chunk list, per-chunk edit ranges offs[0..n] and records as k_rebuild_chunks describes)
 hipError_t launch_rebuild_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const uint32_t* offs, const uint2* recs,
                                  uint32_t nchunks, int logr, hipStream_t st);
+// rt_edit_shapes: `shapes` = nshapes RtShapeEdit records (32 bytes each) as the caller gave them, validated on the host
+hipError_t launch_shape_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const void* shapes, uint32_t nshapes,
+                               uint32_t nchunks, int logr, hipStream_t st);
 hipError_t launch_rebuild_chunk_maps(const uint8_t* mine_sw, uint32_t* coarse, uint32_t* brick, const uint32_t* chunks, uint32_t nchunks,
                                      int logr, hipStream_t st);
 // rt_terrain.hip: rt_generate_world (axis = -1: the window [lo, lo + R) on every axis) and rt_generate_slice (axis 0..2: 16 voxels

@@ -116,6 +116,8 @@ int Pipeline::probe_light(const RtLightProbe* probes, uint32_t count, uint32_t s
     return rt_probe_light(ctx_, &uniforms_, probes, count, samples, depth, out);
 }
 
+int Pipeline::edit_shapes(const RtShapeEdit* shapes, uint32_t count) { return rt_edit_shapes(ctx_, shapes, count); }
+
 int Pipeline::wait() { return rt_sync(ctx_); }
 
 static bool invert3(const float c0[3], const float c1[3], const float c2[3], float out[3][3]) {

@@ -110,6 +110,10 @@ class Pipeline {
     // Path-traced light at `count` points under the sun, seed and lr of the frame drawn last: rt_probe_light with the pipeline's
     // uniforms (a host that accumulates over calls advances the seed by `samples` between them: set_seed).
     int probe_light(const RtLightProbe* probes, uint32_t count, uint32_t samples, int32_t depth, RtProbeLight* out);
+    // Boxes and spheres filled, painted or carved in the resident region, in order (an explosion, a brush): rt_edit_shapes.  The
+    // texels are the region's, as PickResult::hit.texel; a shape that crosses the window's seam is issued again shifted by the
+    // region's edge (INTEGRATION.md "Explosions and brushes").
+    int edit_shapes(const RtShapeEdit* shapes, uint32_t count);
     bool post_passes() const { return post_; }
 
  private:

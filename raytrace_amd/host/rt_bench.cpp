@@ -7,6 +7,7 @@
 //   rt_bench [x y z heading pitch sun] [--width W] [--height H] [--spp N] [--depth D] [--frames F]
 //            [--noise tests/golden/blue_noise_512.rgba] [--device I] [--gpus N] [--gather] [--overlap] [--post] [--accumulate]
 //            [--reproject [--history-denoise]] [--camera-step DX] [--frames-in-flight N] [--edits N [--edit-spread]] [--edit-radius N]
+//            [--edit-shape sphere:R|box:E]
 //            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
 //
@@ -37,6 +38,11 @@
 // of the region.  After the timed loop the same batches run alone on a second pipeline created with RT_FLAG_TIMING_ALL: the JSON
 // line adds the device time of the edit launches per call (rt_get_timing's shade_ms: the rebuild and nibble-map launches, each
 // bracketed by events), the launches per call, the host time spent inside rt_edit_voxels and the wall time per call.
+//
+// --edit-shape sphere:R | box:E: before every frame, rt_edit_shapes carves or fills (alternating from frame to frame) ONE shape where
+// --edits puts its brush, centred 16 texels ahead of the camera: a sphere of radius R round that voxel's centre, or a cube of E voxels
+// per edge — whose low corner is moved down to a multiple of 64 when E is one (box:64 is exactly one chunk, box:256 the region) —
+// clipped to the region.  Timed like --edits; the JSON line carries the same four edit timing fields and "edit_shape".
 //
 // --edit-radius N (with --reproject --edits N): RtConfig.edit_radius — the edits no longer restart the lighting history; every frame
 // runs the moved pass with the edited boxes and restarts only the pixels near one or in its sun shadow.  The JSON line's acc_frames /
@@ -142,6 +148,32 @@ std::vector<RtVoxelEdit> edit_brush(int n, bool spread, const float origin[3]) {
 }
 void set_solid(std::vector<RtVoxelEdit>& v, int frame) { for (RtVoxelEdit& e : v) e.solid = (uint16_t)((frame & 1) == 0); }
 
+// --edit-shape: "sphere:R" or "box:E" at the brush's centre; false when the text is neither
+bool shape_brush(const char* text, const float origin[3], RtShapeEdit* out) {
+    const int R = RT_ROOT_BLOCK_SIZE;
+    const int c[3] = {(int)origin[0] + R / 2, (int)origin[1] + R / 2 + 16, (int)origin[2] + R / 2};
+    RtShapeEdit s{};
+    s.material = (1u << 15) | (90u << 14) | (60u << 7) | 30u;
+    s.where = RT_WHERE_ALL;
+    int n = 0;
+    if (std::sscanf(text, "sphere:%d", &n) == 1 && n >= 0 && n <= 2 * R) {
+        s.kind = RT_SHAPE_SPHERE;
+        for (int a = 0; a < 3; a++) s.a[a] = 2 * c[a] + 1;
+        s.b[0] = (2 * n) * (2 * n);
+    } else if (std::sscanf(text, "box:%d", &n) == 1 && n >= 1 && n <= R) {
+        s.kind = RT_SHAPE_BOX;
+        for (int a = 0; a < 3; a++) {
+            int lo = std::min(std::max(c[a] - n / 2, 0), R - n);
+            if (n % 64 == 0) lo -= lo % 64;
+            s.a[a] = lo; s.b[a] = lo + n - 1;
+        }
+    } else {
+        return false;
+    }
+    *out = s;
+    return true;
+}
+
 // --rays: see the head of the file
 int run_rays(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device,
              uint32_t n, bool coherent) {
@@ -216,6 +248,7 @@ int main(int argc, char** argv) {
     int spp = 1, depth = 2, frames = 240, device = 0, gpus = 1;
     bool gather = false, overlap = false, post = false, accumulate = false, edit_spread = false;
     int edits = 0, edit_radius = 0;
+    const char* edit_shape = nullptr;
     long long rays = 0;
     bool rays_coherent = false;
     bool reproject = false, stream = false, stream_history = false, history_denoise = false;
@@ -244,6 +277,7 @@ int main(int argc, char** argv) {
         else if (want("--edits")) edits = std::atoi(argv[++i]);
         else if (std::strcmp(argv[i], "--edit-spread") == 0) edit_spread = true;
         else if (want("--edit-radius")) edit_radius = std::atoi(argv[++i]);
+        else if (want("--edit-shape")) edit_shape = argv[++i];
         else if (std::strcmp(argv[i], "--stream") == 0) stream = true;
         else if (std::strcmp(argv[i], "--stream-history") == 0) stream_history = true;
         else if (want("--rays")) rays = std::atoll(argv[++i]);
@@ -252,7 +286,7 @@ int main(int argc, char** argv) {
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
     if (edits < 0 || edits > (1 << 24)) { std::fprintf(stderr, "--edits must be in 0..2^24\n"); return 2; }
-    if (edit_radius != 0 && (!reproject || (edits == 0 && !stream_history))) { std::fprintf(stderr, "--edit-radius goes with --reproject and --edits N or --stream-history\n"); return 2; }
+    if (edit_radius != 0 && (!reproject || (edits == 0 && !edit_shape && !stream_history))) { std::fprintf(stderr, "--edit-radius goes with --reproject and --edits N or --stream-history\n"); return 2; }
     if (stream && gpus > 1) { std::fprintf(stderr, "--stream needs one device\n"); return 2; }
     if (stream_history && (!stream || !reproject || edit_radius == 0)) { std::fprintf(stderr, "--stream-history goes with --stream --reproject --edit-radius N\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
@@ -262,6 +296,11 @@ int main(int argc, char** argv) {
     if (history_denoise && (!post || !reproject)) { std::fprintf(stderr, "--history-denoise goes with --post --reproject\n"); return 2; }
     if (post && gpus > 1) { std::fprintf(stderr, "--post needs the whole frame on one device (gather first on several)\n"); return 2; }
     rt::game::Game game((int)positional.size(), positional.data());
+    RtShapeEdit shape{};
+    if (edit_shape && (edits > 0 || !shape_brush(edit_shape, game.camera.origin, &shape))) {
+        std::fprintf(stderr, "--edit-shape is sphere:R (0..512) or box:E (1..256), without --edits\n");
+        return 2;
+    }
 
     std::vector<uint8_t> noise(RT_NOISE_BYTES);
     FILE* fp = std::fopen(noise_path.c_str(), "rb");
@@ -353,6 +392,12 @@ int main(int argc, char** argv) {
                 rc = rt_edit_voxels(p->context(), brushes[(size_t)g].data(), (uint32_t)edits);
                 if (rc != RT_OK) std::fprintf(stderr, "rt_edit_voxels failed on device %d (%d): %s\n", devices[(size_t)g], rc, rt_last_error(p->context()));
             }
+            if (edit_shape) {
+                RtShapeEdit sh = shape;
+                sh.solid = (uint8_t)((f & 1) == 0);
+                rc = p->edit_shapes(&sh, 1);
+                if (rc != RT_OK) std::fprintf(stderr, "rt_edit_shapes failed on device %d (%d): %s\n", devices[(size_t)g], rc, rt_last_error(p->context()));
+            }
             if (rc == RT_OK) rc = p->draw_frame(game);                // main.rs:52
             if (rc != RT_OK) {
                 std::fprintf(stderr, "frame %d failed on device %d (%d): %s\n", f, devices[(size_t)g], rc, p->last_error());
@@ -387,7 +432,7 @@ int main(int argc, char** argv) {
     int exit_code = failed.load() ? 1 : 0;
     // --edits: the edit batches alone, on a pipeline whose launches are timed
     double edit_dev_ms = 0.0, edit_host_ms = 0.0, edit_wall_ms = 0.0, edit_launches = 0.0;
-    if (!exit_code && edits > 0) {
+    if (!exit_code && (edits > 0 || edit_shape)) {
         RtConfig tcfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
         rt::render::Pipeline* tp = rt::render::create_instance(tcfg, noise.data(), game, &err);
         RtTiming tm{};
@@ -399,8 +444,10 @@ int main(int argc, char** argv) {
             const auto w0 = std::chrono::steady_clock::now();
             for (int f = 0; f < frames && !exit_code; f++) {
                 set_solid(brush, f);
+                RtShapeEdit sh = shape;
+                sh.solid = (uint8_t)((f & 1) == 0);
                 const auto h0 = std::chrono::steady_clock::now();
-                if (rt_edit_voxels(tp->context(), brush.data(), (uint32_t)edits) != RT_OK) exit_code = 1;
+                if ((edit_shape ? tp->edit_shapes(&sh, 1) : rt_edit_voxels(tp->context(), brush.data(), (uint32_t)edits)) != RT_OK) exit_code = 1;
                 edit_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
             }
             if (rt_sync(tp->context()) != RT_OK) exit_code = 1;
@@ -439,12 +486,13 @@ int main(int argc, char** argv) {
                     "\"ms_per_frame\": %.4f, \"avg_ms_last_120\": %.4f, \"max_ms_last_120\": %.4f, \"mrays_per_s\": %.2f, "
                     "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"reproject\": %s, \"camera_step\": %g, \"samples\": %u, \"acc_frames\": %u, \"edit_radius\": %d, \"stream\": %s, \"stream_history\": %s, "
                     "\"edits\": %d, \"edit_spread\": %s, \"edit_device_ms_per_call\": %.4f, \"edit_launches_per_call\": %.1f, "
-                    "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f%s}\n",
+                    "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f%s%s%s%s}\n",
                     width, height, spp, depth, gpus, gather ? (overlap ? "rccl-overlapped" : "rccl-serial") : "none", post ? "true" : "false",
                     game.camera.origin[0], game.camera.origin[1], game.camera.origin[2], game.camera.heading, game.camera.pitch,
                     game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum,
                     accumulate ? "true" : "false", reproject ? "true" : "false", (double)camera_step, acc_samples, acc_frames, edit_radius, stream ? "true" : "false", stream_history ? "true" : "false", edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
-                    edit_host_ms, edit_wall_ms, history_denoise ? ", \"history_denoise\": true" : "");
+                    edit_host_ms, edit_wall_ms, history_denoise ? ", \"history_denoise\": true" : "", edit_shape ? ", \"edit_shape\": \"" : "",
+                    edit_shape ? edit_shape : "", edit_shape ? "\"" : "");
     }
     for (int g = 0; g < gpus; g++) {
         if (comms[(size_t)g]) rt_comm_destroy(comms[(size_t)g]);

@@ -13,8 +13,9 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RtBoxSweep, RtConfig,
-                  RtCounters, RtDenoiseParams, RtInfo, RtLightProbe, RtProbeLight, RtRayHit, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE, RT_SWEEP_BLOCKED,
+                  RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtLightProbe, RtProbeLight, RtRayHit,
+                  RtShapeEdit, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
 class RtError(RuntimeError):
@@ -76,6 +77,33 @@ SWEEP_DTYPE = np.dtype([("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3)
 SWEEP_HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<u4"), ("normal", "<u4"), ("material", "<u4"), ("texel", "<i4", 3), ("axis", "<u4"),
                             ("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3), ("reserved1", "<u4")])
 assert SWEEP_DTYPE.itemsize == C.sizeof(RtBoxSweep) and SWEEP_HIT_DTYPE.itemsize == C.sizeof(RtSweepHit)
+
+# numpy view of RtShapeEdit (include/rt_abi.h)
+SHAPE_DTYPE = np.dtype([("a", "<i4", 3), ("material", "<u4"), ("b", "<i4", 3), ("kind", "u1"), ("where", "u1"), ("solid", "u1"),
+                        ("reserved", "u1")])
+assert SHAPE_DTYPE.itemsize == C.sizeof(RtShapeEdit)
+
+
+def box_shape(lo, hi, material=0, solid=True, where=RT_WHERE_ALL):
+    """One RtShapeEdit row: the box of texels lo..hi (x, y, z), both corners inclusive."""
+    s = np.zeros((), dtype=SHAPE_DTYPE)
+    s["a"], s["b"] = [int(v) for v in lo], [int(v) for v in hi]
+    s["material"], s["kind"], s["where"], s["solid"] = int(material) & 0xFFFFFFFF, RT_SHAPE_BOX, int(where), 1 if solid else 0
+    return s
+
+
+def sphere_shape(centre, radius, material=0, solid=True, where=RT_WHERE_ALL):
+    """One RtShapeEdit row: the sphere of `radius` texels round `centre`, in texel coordinates with a voxel's centre at x + 0.5 —
+    both in half texels at most (centre (10.5, 10.5, 10.5), radius 3.5: the sphere round voxel (10, 10, 10))."""
+    c2 = [2.0 * float(v) for v in centre]
+    d = 2.0 * float(radius)
+    if any(v != math.floor(v) for v in c2) or d != math.floor(d) or d < 0:
+        raise ValueError("a sphere's centre and radius are whole or half texels")
+    s = np.zeros((), dtype=SHAPE_DTYPE)
+    s["a"], s["b"] = [int(v) for v in c2], [int(d) * int(d), 0, 0]
+    s["material"], s["kind"], s["where"], s["solid"] = int(material) & 0xFFFFFFFF, RT_SHAPE_SPHERE, int(where), 1 if solid else 0
+    return s
+
 
 # Texel step from a hit voxel to the empty neighbour in front of the face the ray crossed, per normal code (raytrace.comp:89-93): an
 # even code means the ray travelled towards -axis, so it came from +axis.
@@ -206,6 +234,14 @@ class Context:
         recs = np.ascontiguousarray(recs)
         assert recs.dtype.itemsize == C.sizeof(RtVoxelEdit)
         self._check(self._lib.rt_edit_voxels(self._h, recs.ctypes.data_as(C.POINTER(RtVoxelEdit)), int(recs.size)))
+
+    def edit_shapes(self, shapes):
+        """rt_edit_shapes: a sequence of box_shape / sphere_shape rows, or a ready SHAPE_DTYPE array (32-byte RtShapeEdit rows),
+        applied in order on the device; every 64^3 chunk that meets a shape's bounding box is rebuilt (see include/rt_abi.h)."""
+        if not (isinstance(shapes, np.ndarray) and shapes.dtype == SHAPE_DTYPE):
+            shapes = np.array([np.asarray(s, dtype=SHAPE_DTYPE) for s in shapes], dtype=SHAPE_DTYPE).reshape(-1)
+        shapes = np.ascontiguousarray(shapes).reshape(-1)
+        self._check(self._lib.rt_edit_shapes(self._h, shapes.ctypes.data_as(C.POINTER(RtShapeEdit)), int(shapes.size)))
 
     def read_box(self, origin, extent):
         """rt_read_box: (materials u32[ez, ey, ex], minefield u8[ez, ey, ex]) of the resident region's box at texel `origin` (x, y, z)
