@@ -579,6 +579,59 @@ int rt_sweep_boxes(RtContext* ctx, const RtBoxSweep* sweeps, uint32_t count, con
  * RT_ERR_INVALID_ARG before anything is enqueued; the sweeps must be complete on the device when the call is made. */
 int rt_sweep_boxes_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t count, const int32_t lr[3], RtSweepHit* hits_dev);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Entity boxes: world-space axis-aligned boxes — a player model, mobs,
+ * dropped items, projectiles — composited by depth into the G-buffer of the frame drawn last, after rt_draw_frame and before the
+ * post passes.  A box has RtBoxSweep's shape; a drawn pixel gets the box's depth, face code, albedo and emission and the light of that
+ * face as rt_probe_light computed it, so rt_denoise, rt_denoise_history and rt_finalize treat it like any other pixel.  Entities cast
+ * no shadow into the world and do not appear in bounce light; boxes are not rotated.  One box, 32 bytes: */
+typedef struct RtDrawBox {        /* 32 bytes */
+    float    lo[3];  uint32_t material;   /* world coordinates of the low corner; packed material word: albedo decoded as a voxel's (raytrace.comp:156-158) */
+    float    hi[3];  uint32_t emission;   /* high corner; RGBA8 word written as is to RT_BUF_EMISSION_RGBA8 (a voxel's is 0xFF000000) */
+} RtDrawBox;
+/* The rules.  All arithmetic is fp32 with one rounding per operation; fused operations appear only where rtm_fma is written.  Results
+ * are reproduced bit for bit by tests/draw_boxes_ref.py, which tests every box against every pixel (DESIGN.md "Entity boxes").
+ *   Inputs: only origin, forward, up and right of `u` are read, as for rt_pick_pixels; the host passes the uniforms of the frame it
+ *     drew.  `face_lights` holds 6 * count records: record 6 b + n is the light of box b's face with normal code n (0..5, the codes of
+ *     RtRayHit.normal); only .light is read, in the shader's unit — what rt_probe_light returns, before the division by 16.
+ *   Ray of pixel (px, py), row 0 the bottom row: sx = (float(px) / float(width)) * 2 - 1, sy likewise from py and height,
+ *     d = normalize(forward + right * sx + up * sy) (rt_math.h's rtm_normalize3; the products and sums in this order), o = u.origin.
+ *     The shader's "start below the region" slide is not applied: the depth plane is measured from u.origin too.
+ *   Valid box: every float finite, |lo_k|, |hi_k| <= 2^22 and lo_k < hi_k on every axis.  The device skips an invalid box in both
+ *     calls (it is never hit); rt_draw_boxes also rejects the whole call (RT_ERR_INVALID_ARG) before anything is enqueued.
+ *   Slab test of box b: for each axis k = x, y, z with d_k != 0: inv = 1.0f / d_k, t0 = (lo_k - o_k) * inv, t1 = (hi_k - o_k) * inv,
+ *     tn_k = rtm_min(t0, t1), tf_k = rtm_max(t0, t1).  An axis with d_k == 0 (either sign) passes iff lo_k < o_k && o_k < hi_k and gives
+ *     no bound.  t_in is the largest tn_k and the entry axis the axis that supplied it, the lowest axis on equal values: the first
+ *     bounded axis starts both, a later axis k replaces them iff tn_k > t_in.  t_out is the smallest tf_k: a later axis replaces it iff
+ *     tf_k < t_out.  The box is hit iff some axis gave a bound, every d_k == 0 axis passes, t_in > 0 and t_in < t_out: a camera inside
+ *     a box does not see it (the player's own box never blinds them) and a grazing ray misses.  Any comparison with a NaN is false.
+ *   Winner: among the boxes hit the one with the smallest t_in, on equal t_in the lowest index.
+ *   Depth test: P_k = rtm_fma(d_k, t_in, o_k); depth_f = rtm_length3(o - P) * 32.0f (the G-buffer's expression, raytrace.comp:356-359).
+ *     The pixel is drawn iff depth_f < RT_BUF_DEPTH_F32[pixel]: strict, the world wins ties; sky is 65535.0, so a box 2048 or more
+ *     units away is never drawn.
+ *   Writes of a drawn pixel (every other pixel and plane keeps its bits): RT_BUF_DEPTH_F32 = depth_f; RT_BUF_DEPTH_R16UI =
+ *     rtm_f2u16(depth_f); RT_BUF_NORMAL_R8UI = 2 a + 1 if d_a > 0, else 2 a, a the entry axis (the code trace_ray gives a ray crossing
+ *     that face); RT_BUF_ALBEDO_RGBA8 = the UNORM8 pack of (albedo of `material`, 1); RT_BUF_EMISSION_RGBA8 = `emission`;
+ *     RT_BUF_LIGHTING_F32 and RT_BUF_LIGHTING_RGBA16 exactly what a one-sample frame stores for light = face_lights[6 b + normal].light:
+ *     (light / 1.0f) / 16 per channel and 1 / 16 in alpha, and their UNORM16.  The fog planes depend on the direction only and are
+ *     not touched.
+ *   Which frame, ordering: the call acts on the planes of the frame drawn last, on the stream rt_denoise uses — after that frame and
+ *     before later post passes, also with RT_FLAG_FRAMES_IN_FLIGHT_2 and after rt_set_stream.  On the device it waits for the queries
+ *     already enqueued on the context, so rt_probe_light_async can feed rt_draw_boxes_async through a device buffer without a host
+ *     sync.
+ *   Side effects: the frame slot's cached prepass is dropped (a still camera does not carry entity pixels into the next frame).  No
+ *     accumulation sum, RT_FLAG_REPROJECT history set or count, RtCounters, pending edit box or slab changes.
+ *   Errors: NULL ctx, NULL u, a NULL array with count > 0, count > 4096: RT_ERR_INVALID_ARG.  tile_world != 1: RT_ERR_UNIMPLEMENTED
+ *     (whole-frame contexts only, as for rt_denoise).  No frame drawn yet: RT_ERR_NOT_READY.  count == 0: RT_OK, nothing enqueued,
+ *     no prepass dropped.  A rejected call changes nothing.
+ *   Device work per call: one launch, a wave per 8x8 pixel tile; per tile the boxes pass a conservative cull 64 at a time and only
+ *     the survivors are tested per pixel (DESIGN.md "Entity boxes"); the synchronous call adds one transfer.
+ * Host pointers; returns when the planes are written. */
+int rt_draw_boxes(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes, const RtProbeLight* face_lights, uint32_t count);
+/* Same with device pointers, enqueued.  Both pointers must pass rt_trace_rays_async's test (16-byte aligned memory of the context's
+ * device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued.  The library cannot read device records on the
+ * host: an invalid box is skipped on the device. */
+int rt_draw_boxes_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes_dev, const RtProbeLight* face_lights_dev, uint32_t count);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Terrain generated on the device: the project's deterministic
  * procedural world (raytrace_amd/host/world.cpp: generate_chunk + pack_into per world chunk, MATERIALS[id].pack()) written straight
  * into the resident region, byte for byte what the host generator assembles — no host bytes, no staging, no transfer.
@@ -813,7 +866,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtBoxSweep, RtSweepHit, RT_SWEEP_*, rt_sweep_boxes, rt_sweep_boxes_async (box sweeps: collision
  *        queries against the resident world).
  *        Additive, same minor version: RtShapeEdit, RT_SHAPE_*, RT_WHERE_*, rt_edit_shapes (shape edits: boxes and spheres filled
- *        or carved on the device). */
+ *        or carved on the device).
+ *        Additive, same minor version: RtDrawBox, rt_draw_boxes, rt_draw_boxes_async (entity boxes composited into the G-buffer by
+ *        depth). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -23,7 +23,7 @@ ABI_SYMBOLS = (
     "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels", "rt_generate_world", "rt_generate_slice", "rt_read_history",
     "rt_edit_boxes_pending", "rt_slabs_pending", "rt_read_slab_boxes", "rt_probe_light", "rt_probe_light_async",
     "rt_denoise_history", "rt_denoise_planes_counted", "rt_sweep_boxes", "rt_sweep_boxes_async",
-    "rt_edit_shapes",
+    "rt_edit_shapes", "rt_draw_boxes", "rt_draw_boxes_async",
 )
 
 _amd = None
@@ -136,6 +136,10 @@ def amd():
         lib.rt_sweep_boxes.restype = C.c_int
         lib.rt_sweep_boxes_async.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
         lib.rt_sweep_boxes_async.restype = C.c_int
+        lib.rt_draw_boxes.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
+        lib.rt_draw_boxes.restype = C.c_int
+        lib.rt_draw_boxes_async.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
+        lib.rt_draw_boxes_async.restype = C.c_int
         lib.rt_generate_world.argtypes = [P, C.c_uint64, C.POINTER(C.c_int64)]
         lib.rt_generate_world.restype = C.c_int
         lib.rt_generate_slice.argtypes = [P, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]
@@ -235,5 +239,7 @@ def host():
         lib.rth_pipeline_last_error.restype = C.c_char_p
         lib.rth_pipeline_pick.argtypes = [P, C.c_int, C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.rth_pipeline_pick.restype = C.c_int
+        lib.rth_pipeline_set_boxes.argtypes = [P, P, P, C.c_uint32]
+        lib.rth_pipeline_set_boxes.restype = C.c_int
         _host = lib
     return _host

@@ -196,6 +196,16 @@ class RtSweepHit(C.Structure):
 assert C.sizeof(RtBoxSweep) == 48 and C.sizeof(RtSweepHit) == 64
 
 
+class RtDrawBox(C.Structure):
+    """rt_draw_boxes input (ABI 1.3, additive: entity boxes): 32 bytes."""
+    _fields_ = [("lo", C.c_float * 3), ("material", C.c_uint32), ("hi", C.c_float * 3), ("emission", C.c_uint32)]
+
+
+assert C.sizeof(RtDrawBox) == 32
+assert (RtDrawBox.lo.offset, RtDrawBox.material.offset, RtDrawBox.hi.offset, RtDrawBox.emission.offset) == (0, 12, 16, 28)
+MAX_DRAW_BOXES = 4096   # rt_draw_boxes: boxes per call
+
+
 class RtDenoiseParams(C.Structure):
     """rt_denoise_history / rt_denoise_planes_counted parameters (ABI 1.3, additive): 48 bytes; `reserved` must be 0."""
     _fields_ = [("struct_size", C.c_uint32), ("faithful", C.c_int32), ("weight_by_count", C.c_int32), ("settle", C.c_uint32 * 6),

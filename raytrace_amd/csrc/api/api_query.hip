@@ -5,6 +5,18 @@
 
 using namespace rta;
 
+namespace rta {
+// rt_trace_rays_async's pointers: 16-byte aligned (the kernel's float4 / uint4 accesses) and memory of the context's device (or
+// managed memory).  A host address would fault the kernel: pageable memory is not mapped for the device with XNACK off.
+bool query_device_ptr(const RtContext* c, const void* p) {
+    if (((uintptr_t)p & 15u) != 0u) return false;
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (clears the error it set)
+    if (a.type == hipMemoryTypeManaged || a.isManaged) return true;
+    return a.type == hipMemoryTypeDevice && a.device == c->device;
+}
+}  // namespace rta
+
 namespace {
 constexpr uint32_t kMaxQueryRays = 1u << 26;
 
@@ -41,16 +53,6 @@ int query_launch(RtContext* c, hipStream_t st, const rtd::Frame& f, const void* 
     RT_HIP(c, rtd::launch_query(scene_of(c), f, a, st));
     if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
     return RT_OK;
-}
-
-// rt_trace_rays_async's pointers: 16-byte aligned (the kernel's float4 / uint4 accesses) and memory of the context's device (or
-// managed memory).  A host address would fault the kernel: pageable memory is not mapped for the device with XNACK off.
-bool query_device_ptr(const RtContext* c, const void* p) {
-    if (((uintptr_t)p & 15u) != 0u) return false;
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // (clears the error it set)
-    if (a.type == hipMemoryTypeManaged || a.isManaged) return true;
-    return a.type == hipMemoryTypeDevice && a.device == c->device;
 }
 
 rtd::Frame query_frame(const RtContext* c, const int32_t lr[3]) {

@@ -422,5 +422,6 @@ rtd::Planes planes_of(void* const* planes);
 inline rtd::Planes planes_of(const RtContext* c) { return planes_of(c->planes); }
 void resolve_route(RtContext* c);
 rtd::Frame frame_of(const RtContext* c, const RtUniforms* u);
+bool query_device_ptr(const RtContext* c, const void* p);   // api_query.hip: rt_trace_rays_async's test of a caller's device pointer
 
 }  // namespace rta

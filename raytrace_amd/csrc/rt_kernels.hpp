@@ -193,6 +193,17 @@ struct SweepArgs {
 };
 hipError_t launch_sweep(const Scene& sc, int logr, const SweepArgs& a, hipStream_t st);
 
+// rt_boxes.hip: entity boxes composited into a whole frame's row-major planes by depth (rt_draw_boxes).  One launch for the batch;
+// a wave owns an 8x8 pixel tile.
+struct DrawBoxesArgs {
+    const uint4* boxes;   // RtDrawBox[count] (two uint4 each)
+    const float4* lights; // RtProbeLight[6 * count]: record 6 b + n lights face n of box b (.xyz read)
+    uint32_t count;
+    int width, height;
+    float origin[3], forward[3], up[3], right[3];   // the camera of the frame the planes hold (primary_ray without the slide)
+};
+hipError_t launch_draw_boxes(const Planes& pl, const DrawBoxesArgs& a, hipStream_t st);
+
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
 // (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
 // or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)

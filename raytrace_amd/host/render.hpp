@@ -114,6 +114,10 @@ class Pipeline {
     // texels are the region's, as PickResult::hit.texel; a shape that crosses the window's seam is issued again shifted by the
     // region's edge (INTEGRATION.md "Explosions and brushes").
     int edit_shapes(const RtShapeEdit* shapes, uint32_t count);
+    // Entity boxes: every draw_frame from now on enqueues rt_draw_boxes(boxes, face_lights, count) between the ray trace and the
+    // denoise (both arrays are copied; face_lights holds 6 * count records, e.g. probe_light's for the boxes' face probes).
+    // count == 0 draws none.  RT_ERR_INVALID_ARG for more than 4096 boxes or a NULL array with count > 0.
+    int set_boxes(const RtDrawBox* boxes, const RtProbeLight* face_lights, uint32_t count);
     bool post_passes() const { return post_; }
 
  private:
@@ -131,6 +135,8 @@ class Pipeline {
     bool history_denoise_ = false;     // enable_history_denoise
     RtDenoiseParams denoise_params_{};
     bool no_fence_ = false;            // set_frames_in_flight(2)
+    std::vector<RtDrawBox> boxes_;     // set_boxes
+    std::vector<RtProbeLight> box_lights_;
     std::unique_ptr<TerrainUploadManager> tum_;
     std::unique_ptr<world::ChunkStorage> chunks_;
     bool stream_on_device_ = false;

@@ -10,6 +10,7 @@
 //            [--edit-shape sphere:R|box:E]
 //            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
+//            [--boxes N]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -59,9 +60,14 @@
 // over as arbitrary rays — timed call to return (the transfers both ways included; the kernel alone: rocprofv3 --kernel-trace
 // --stats, or tools/ray_query_bench.py's device events), then the call-to-return latency of one-pixel rt_pick_pixels, idle and
 // right behind a --width x --height --spp --depth frame still in flight.  One JSON line.
+// --boxes N: instead of the frame loop, entity boxes.  N entity-sized boxes are scattered deterministically in front of the camera
+// (20 to 400 units away, over the whole view), their six face probes lit with rt_probe_light (4 samples, depth 2), and rt_draw_boxes
+// composites them into a freshly drawn --width x --height frame, 20 times.  One JSON line: the device time of the pass (the launch
+// bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time of rt_draw_boxes and of the probes, and the pixels drawn.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -241,6 +247,76 @@ int run_rays(rt::game::Game& game, const std::vector<uint8_t>& noise, int width,
     return 0;
 }
 
+// --boxes: see the head of the file
+int run_boxes(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    std::vector<RtDrawBox> boxes(n);
+    std::vector<RtLightProbe> probes(6u * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        const float sx = rnd() * 2.0f - 1.0f, sy = rnd() * 2.0f - 1.0f, dist = 20.0f * std::pow(20.0f, rnd());   // 20 .. 400, log-uniform
+        float v[3], len = 0.0f;
+        for (int a = 0; a < 3; a++) { v[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; len += v[a] * v[a]; }
+        len = std::sqrt(len);
+        RtDrawBox& b = boxes[i];
+        for (int a = 0; a < 3; a++) {
+            const float c = u.origin[a] + v[a] / len * dist, half = a == 2 ? 0.9f : 0.3f;   // a player's box: 0.6 x 0.6 x 1.8
+            b.lo[a] = c - half; b.hi[a] = c + half;
+        }
+        b.material = (1u << 15) | ((40u + i % 80u) << 14) | ((30u + i % 90u) << 7) | (20u + i % 100u);
+        b.emission = 0xFF000000u;
+        for (uint32_t code = 0; code < 6u; code++) {   // the face centre, 0.001 off the face along its normal
+            RtLightProbe& q = probes[6u * (size_t)i + code];
+            q = RtLightProbe{};
+            for (int a = 0; a < 3; a++) q.position[a] = (b.lo[a] + b.hi[a]) * 0.5f;
+            const int a = (int)(code / 2u);
+            q.position[a] = code % 2u == 0u ? b.hi[a] + 0.001f : b.lo[a] - 0.001f;
+            q.normal = code;
+            q.cell[0] = (uint16_t)(i % 16u); q.cell[1] = (uint16_t)((i / 16u) % 16u);
+        }
+    }
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    std::vector<RtProbeLight> lights(probes.size());
+    auto t = std::chrono::steady_clock::now();
+    int rc = n ? rt_probe_light(ctx, &u, probes.data(), (uint32_t)probes.size(), 4, 2, lights.data()) : RT_OK;
+    const double probe_ms = ms_since(t);
+    const size_t npix = (size_t)width * (size_t)height;
+    std::vector<float> before(npix), after(npix);
+    if (rc == RT_OK) rc = rt_readback(ctx, RT_BUF_DEPTH_F32, before.data(), npix * sizeof(float));
+    const int reps = 20;
+    double device_ms = 0.0, call_ms = 0.0;
+    uint32_t launches = 0;
+    for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {   // (the first repetition warms the staging up)
+        RtTiming tm{};
+        rc = rt_draw_frame(ctx, &u);
+        if (rc == RT_OK) rc = rt_sync(ctx);
+        if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);   // (drains the frame's own launches)
+        t = std::chrono::steady_clock::now();
+        if (rc == RT_OK) rc = rt_draw_boxes(ctx, &u, boxes.data(), lights.data(), n);
+        const double call = ms_since(t);
+        if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);
+        if (i > 0) { device_ms += tm.shade_ms / reps; call_ms += call / reps; launches += tm.other_launches; }
+    }
+    if (rc == RT_OK) rc = rt_readback(ctx, RT_BUF_DEPTH_F32, after.data(), npix * sizeof(float));
+    if (rc != RT_OK) { std::fprintf(stderr, "entity boxes failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    uint64_t drawn = 0;
+    for (size_t i = 0; i < npix; i++) drawn += std::memcmp(&before[i], &after[i], 4) != 0;
+    std::printf("{\"boxes\": %u, \"frame\": \"%dx%d spp %d depth %d\", \"draw_boxes_device_ms\": %.4f, \"draw_boxes_call_ms\": %.4f, "
+                "\"launches_per_call\": %.2f, \"probe_light_call_ms\": %.3f, \"pixels_drawn\": %llu}\n",
+                n, width, height, spp, depth, device_ms, call_ms, (double)launches / reps, probe_ms, (unsigned long long)drawn);
+    delete p;
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -249,7 +325,7 @@ int main(int argc, char** argv) {
     bool gather = false, overlap = false, post = false, accumulate = false, edit_spread = false;
     int edits = 0, edit_radius = 0;
     const char* edit_shape = nullptr;
-    long long rays = 0;
+    long long rays = 0, boxes = -1;
     bool rays_coherent = false;
     bool reproject = false, stream = false, stream_history = false, history_denoise = false;
     float camera_step = 0.0f;
@@ -282,6 +358,7 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--stream-history") == 0) stream_history = true;
         else if (want("--rays")) rays = std::atoll(argv[++i]);
         else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
+        else if (want("--boxes")) boxes = std::atoll(argv[++i]);
         else positional.push_back(argv[i]);
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
@@ -290,6 +367,7 @@ int main(int argc, char** argv) {
     if (stream && gpus > 1) { std::fprintf(stderr, "--stream needs one device\n"); return 2; }
     if (stream_history && (!stream || !reproject || edit_radius == 0)) { std::fprintf(stderr, "--stream-history goes with --stream --reproject --edit-radius N\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
+    if (boxes < -1 || boxes > 4096) { std::fprintf(stderr, "--boxes must be in 0..4096\n"); return 2; }
     if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
     if (gpus > 1) gather = true;
@@ -314,6 +392,7 @@ int main(int argc, char** argv) {
     auto t0 = std::chrono::steady_clock::now();
     game.generate_world(0x5EED);
     if (rays > 0) return run_rays(game, noise, width, height, spp, depth, device, (uint32_t)rays, rays_coherent);
+    if (boxes >= 0) return run_boxes(game, noise, width, height, spp, depth, device, (uint32_t)boxes);
     std::string err;
 
     // exact ray count of one frame (a counting context, outside the timed loop): the JSON line's Mrays/s is rays actually traced

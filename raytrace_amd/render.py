@@ -13,9 +13,9 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE, RT_SWEEP_BLOCKED,
-                  RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtLightProbe, RtProbeLight, RtRayHit,
-                  RtShapeEdit, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
+                  RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtInfo, RtLightProbe,
+                  RtProbeLight, RtRayHit, RtShapeEdit, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
 class RtError(RuntimeError):
@@ -77,6 +77,9 @@ SWEEP_DTYPE = np.dtype([("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3)
 SWEEP_HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<u4"), ("normal", "<u4"), ("material", "<u4"), ("texel", "<i4", 3), ("axis", "<u4"),
                             ("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3), ("reserved1", "<u4")])
 assert SWEEP_DTYPE.itemsize == C.sizeof(RtBoxSweep) and SWEEP_HIT_DTYPE.itemsize == C.sizeof(RtSweepHit)
+# numpy view of RtDrawBox (include/rt_abi.h)
+DRAW_BOX_DTYPE = np.dtype([("lo", "<f4", 3), ("material", "<u4"), ("hi", "<f4", 3), ("emission", "<u4")])
+assert DRAW_BOX_DTYPE.itemsize == C.sizeof(RtDrawBox)
 
 # numpy view of RtShapeEdit (include/rt_abi.h)
 SHAPE_DTYPE = np.dtype([("a", "<i4", 3), ("material", "<u4"), ("b", "<i4", 3), ("kind", "u1"), ("where", "u1"), ("solid", "u1"),
@@ -365,6 +368,25 @@ class Context:
             if not m.any():
                 break
         return lo, hi, hits
+
+    # -- entity boxes ------------------------------------------------------------------------------------
+    def draw_boxes(self, uniforms, boxes, face_lights):
+        """rt_draw_boxes: `boxes` DRAW_BOX_DTYPE[N] records (make_draw_boxes) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
+        probe_records returns for face_probes(boxes, ...)), composited by depth into the planes of the frame drawn last under the camera
+        of `uniforms`.  Synchronous; an invalid box fails the whole call (RtError, INVALID_ARG)."""
+        boxes = np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
+        lights = np.ascontiguousarray(face_lights, dtype=PROBE_LIGHT_DTYPE).reshape(-1)
+        if lights.size != 6 * boxes.size:
+            raise ValueError("face_lights must hold six records per box")
+        self._check(self._lib.rt_draw_boxes(self._h, C.byref(uniforms), _p(boxes) if boxes.size else None, _p(lights) if boxes.size else None,
+                                            int(boxes.size)))
+
+    def draw_boxes_async(self, uniforms, boxes, face_lights):
+        """rt_draw_boxes_async on torch device tensors: `boxes` any contiguous tensor of N * 32 bytes (RtDrawBox rows), `face_lights` any
+        contiguous tensor of 6 N * 16 bytes (e.g. the `out` of probe_light_async).  Enqueued behind the frame drawn last and the queries
+        enqueued so far; an invalid box is skipped on the device."""
+        n = check_draw_box_tensors(boxes, face_lights, self.cfg.device if self.cfg is not None else 0)
+        self._check(self._lib.rt_draw_boxes_async(self._h, C.byref(uniforms), C.c_void_p(boxes.data_ptr()), C.c_void_p(face_lights.data_ptr()), n))
 
     # -- frames ------------------------------------------------------------------------------------------
     def draw_frame(self, uniforms):
@@ -722,6 +744,17 @@ class Pipeline:
         return {"hit": h, "texel": tuple(int(v) for v in h["texel"]), "normal": int(h["normal"]), "kind": int(h["kind"]),
                 "adjacent": tuple(adj[:]), "world": tuple(wld[:])}
 
+    def set_boxes(self, boxes=None, face_lights=None):
+        """Pipeline::set_boxes: every draw_frame from now on enqueues rt_draw_boxes for this set between the ray trace and the denoise
+        (DRAW_BOX_DTYPE[N] and PROBE_LIGHT_DTYPE[6 N], copied); None or an empty set draws none."""
+        boxes = np.zeros(0, dtype=DRAW_BOX_DTYPE) if boxes is None else np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
+        lights = np.zeros(0, dtype=PROBE_LIGHT_DTYPE) if face_lights is None else np.ascontiguousarray(face_lights, dtype=PROBE_LIGHT_DTYPE).reshape(-1)
+        if lights.size != 6 * boxes.size:
+            raise ValueError("face_lights must hold six records per box")
+        rc = _lib.host().rth_pipeline_set_boxes(self._h, _p(boxes) if boxes.size else None, _p(lights) if boxes.size else None, int(boxes.size))
+        if rc != 0:
+            raise RtError(rc, "set_boxes: at most %d boxes" % MAX_DRAW_BOXES)
+
     def close(self):
         if self._h:
             _lib.host().rth_pipeline_free(self._h)   # impl Drop for Pipeline, pipeline.rs:258-277
@@ -819,6 +852,71 @@ def check_sweep_tensors(sweeps, hits, device):
     n = nbytes // SWEEP_DTYPE.itemsize
     if hits.numel() * hits.element_size() != n * SWEEP_HIT_DTYPE.itemsize:
         raise ValueError("hits must be a contiguous tensor of N * 64 bytes")
+    return n
+
+
+def make_draw_boxes(lo, hi, materials, emissions=0xFF000000):
+    """RtDrawBox records (DRAW_BOX_DTYPE) from float[N, 3] corners, u32[N] packed material words and u32[N] RGBA8 emission words (one
+    value serves every box; a voxel's emission is 0xFF000000).  Refuses what rt_draw_boxes refuses: a non-finite float, a coordinate
+    beyond 2^22, lo >= hi on an axis, more than 4096 boxes."""
+    lo = np.asarray(lo, dtype=np.float32).reshape(-1, 3)
+    hi = np.asarray(hi, dtype=np.float32).reshape(-1, 3)
+    if lo.shape != hi.shape:
+        raise ValueError("lo and hi must have the same shape [N, 3]")
+    n = lo.shape[0]
+    if n > MAX_DRAW_BOXES:
+        raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("box corners must be finite")
+    if n and (np.abs(lo).max() > 2.0 ** 22 or np.abs(hi).max() > 2.0 ** 22):
+        raise ValueError("box corners must lie within +-2^22")
+    if not (lo < hi).all():
+        raise ValueError("lo must be below hi on every axis")
+    boxes = np.zeros(n, dtype=DRAW_BOX_DTYPE)
+    boxes["lo"], boxes["hi"] = lo, hi
+    boxes["material"] = np.broadcast_to(np.asarray(materials, dtype=np.uint32), (n,))
+    boxes["emission"] = np.broadcast_to(np.asarray(emissions, dtype=np.uint32), (n,))
+    return boxes
+
+
+def face_probes(boxes, cells=(0, 0)):
+    """The six RtLightProbe records (PROBE_DTYPE) per box that light its faces: record 6 b + n sits at the centre of box b's face with
+    normal code n, moved 0.001 off the face along its normal, with normal n.  `cells`: int[N, 2] noise cells per box, or one pair for
+    all.  probe_records(u, face_probes(boxes), samples, depth) is the face_lights of draw_boxes."""
+    boxes = np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
+    n = boxes.size
+    lo, hi = boxes["lo"].astype(np.float32), boxes["hi"].astype(np.float32)
+    centre = (lo + hi) * np.float32(0.5)
+    pos = np.repeat(centre[:, None, :], 6, axis=1)
+    for code in range(6):
+        axis = code // 2
+        # a ray travelling towards -axis (even code) crosses the high face, one towards +axis the low face
+        pos[:, code, axis] = hi[:, axis] + np.float32(0.001) if code % 2 == 0 else lo[:, axis] - np.float32(0.001)
+    cell = np.broadcast_to(np.asarray(cells).reshape(-1, 2), (n, 2))
+    return make_probes(pos.reshape(-1, 3), np.tile(np.arange(6), n), np.repeat(cell, 6, axis=0))
+
+
+def check_draw_box_tensors(boxes, face_lights, device):
+    """Context.draw_boxes_async's arguments: contiguous tensors of N * 32 and 6 N * 16 bytes on GPU `device`, 16-byte aligned, N at most
+    4096.  Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
+    import torch
+    if not isinstance(boxes, torch.Tensor) or not isinstance(face_lights, torch.Tensor):
+        raise ValueError("boxes and face_lights must be torch tensors")
+    for name, t in (("boxes", boxes), ("face_lights", face_lights)):
+        if not t.is_cuda or t.device.index != int(device):
+            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    nbytes = boxes.numel() * boxes.element_size()
+    if nbytes % DRAW_BOX_DTYPE.itemsize:
+        raise ValueError("boxes must hold whole 32-byte RtDrawBox records")
+    n = nbytes // DRAW_BOX_DTYPE.itemsize
+    if n > MAX_DRAW_BOXES:
+        raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
+    if face_lights.numel() * face_lights.element_size() != 6 * n * PROBE_LIGHT_DTYPE.itemsize:
+        raise ValueError("face_lights must be a contiguous tensor of 6 N * 16 bytes")
     return n
 
 
