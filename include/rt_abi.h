@@ -632,6 +632,60 @@ int rt_draw_boxes(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes, c
  * host: an invalid box is skipped on the device. */
 int rt_draw_boxes_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes_dev, const RtProbeLight* face_lights_dev, uint32_t count);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
+ * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
+ * after rt_draw_frame (and rt_draw_boxes) and before or after rt_denoise.  Each light reaches a pixel through one hard shadow ray
+ * against the resident region; rt_finalize multiplies lighting by albedo, so the added light is diffuse shading.  Entities cast no
+ * shadow, the source gives no bounce light, and the light belongs to one frame: it enters no accumulation sum or history.  One light,
+ * 32 bytes: */
+typedef struct RtPointLight {     /* 32 bytes */
+    float    position[3];  float    radius;     /* world coordinates; nothing is lit at or beyond `radius` */
+    float    color[3];     uint32_t reserved;   /* the shader's light unit (what RtProbeLight.light is in); reserved must be 0 */
+} RtPointLight;
+/* The rules.  All arithmetic is fp32 with one rounding per operation; fused operations appear only where rtm_fma or rtm_dot3 is
+ * written.  Results are reproduced bit for bit by tests/point_light_ref.py, which tests every light against every pixel (DESIGN.md
+ * "Point lights").
+ *   Inputs: origin, forward, up, right and lr of `u` are read; the host passes the uniforms of the frame it drew.
+ *   Surface pixel: RT_BUF_NORMAL_R8UI < 6 and RT_BUF_DEPTH_F32 < 65535.0f (a NaN depth fails).  Every other pixel keeps all its bits.
+ *   Surface point: d is the ray of rt_draw_boxes (the same sx, sy and rtm_normalize3, from o = u.origin, no slide);
+ *     t = depth_f / 32.0f; P_k = rtm_fma(d_k, t, o_k).  With a = normal >> 1: P'_a = P_a + 0.03125f for an even code (it faces +axis)
+ *     and P_a - 0.03125f for an odd one; the other two components of P' are P's.  (1/32 is far above the error of a rebuilt point,
+ *     about 1e-3 at 2048 units.)  Entity pixels written by rt_draw_boxes go through the same rule with the box's depth and face code.
+ *   Valid light: every float finite, |position_k| <= 2^22, 0 < radius <= 1024, 0 <= color_k <= 2^20, reserved == 0.  The device skips
+ *     an invalid light in both calls; rt_add_lights also rejects the whole call (RT_ERR_INVALID_ARG) before anything is enqueued.
+ *   Light i against the pixel ("skip": the light adds nothing to this pixel): v = position - P' per component; dist2 = rtm_dot3(v, v);
+ *     r2 = radius * radius; skip unless dist2 > 0 && dist2 < r2; c = v_a for an even code, -v_a for an odd one; skip unless c > 0.
+ *     A comparison with a NaN is false: a NaN skips.
+ *   Shadow ray: trace_ray (raytrace.comp:82-183) from P' in direction v (trace_ray normalises it), with u.lr and the resident region,
+ *     and one added exit: in each loop iteration, after the sky test (:138-145) found the new position inside the window and before
+ *     the hit test (:146), if rtm_dot3(pos - P', pos - P') >= dist2 the ray has reached the light: visible.  The other exits are the
+ *     shader's: leaving the window: visible; a minefield value of 0 (the border value and a start inside an occupied texel, the
+ *     mod(x, 0) case, included): blocked; the loop limit: blocked.  A light inside a solid voxel lights nothing; a solid voxel behind
+ *     the light does not shadow it.
+ *   Weight and sum: len = rtm_sqrt(dist2); cosine = c / len; x = 1.0f - dist2 / r2; w = (cosine * (x * x)) / (1.0f + dist2);
+ *     add_k = add_k + color_k * w over the visible lights in index order, starting from +0.0f.  (Colours are >= 0, so a skipped light
+ *     leaves the sum's bits as they are.)
+ *   Writes, only for a pixel with at least one visible light: s_k = add_k / 16.0f; RT_BUF_LIGHTING_F32.rgb += s; independently
+ *     RT_BUF_LIGHTING_RGBA16.rgb = rtm_unorm(float(q_k) / 65535.0f + s_k, 65535.0f), q the texel as it stands.  Both alphas are
+ *     untouched.  Each plane gets the light in its own representation, so the host chooses where to call: before rt_denoise the light
+ *     is filtered with the rest, after it point-light shadows stay crisp.  No other plane, pixel or byte changes.
+ *   Which frame, ordering: the call acts on the planes of the frame drawn last, on the stream rt_denoise uses, also with
+ *     RT_FLAG_FRAMES_IN_FLIGHT_2 and after rt_set_stream.  It sees the region as every earlier upload, edit, shape, slab and generated
+ *     region left it, and later world changes wait for it.
+ *   Side effects: the frame slot's cached prepass is dropped.  No accumulation sum, RT_FLAG_REPROJECT history set or count,
+ *     RtCounters, pending edit box or slab changes.
+ *   Errors: NULL ctx, NULL u, a NULL array with count > 0, count > 1024: RT_ERR_INVALID_ARG.  tile_world != 1: RT_ERR_UNIMPLEMENTED
+ *     (whole-frame contexts only).  No frame drawn yet, or no world resident: RT_ERR_NOT_READY.  count == 0: RT_OK, nothing enqueued.
+ *     A rejected call changes nothing.
+ *   Device work per call: one launch, a wave per 8x8 pixel tile; per tile the lights pass a conservative sphere-against-bounds cull
+ *     64 at a time and only the survivors are tested, and traced, per pixel; the synchronous call adds one transfer.
+ * Host pointer; returns when the planes are written. */
+int rt_add_lights(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights, uint32_t count);
+/* Same with a device pointer, enqueued.  The pointer must pass rt_trace_rays_async's test (16-byte aligned memory of the context's
+ * device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued.  The library cannot read device records on the
+ * host: an invalid light is skipped on the device. */
+int rt_add_lights_async(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights_dev, uint32_t count);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Terrain generated on the device: the project's deterministic
  * procedural world (raytrace_amd/host/world.cpp: generate_chunk + pack_into per world chunk, MATERIALS[id].pack()) written straight
  * into the resident region, byte for byte what the host generator assembles — no host bytes, no staging, no transfer.
@@ -868,7 +922,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtShapeEdit, RT_SHAPE_*, RT_WHERE_*, rt_edit_shapes (shape edits: boxes and spheres filled
  *        or carved on the device).
  *        Additive, same minor version: RtDrawBox, rt_draw_boxes, rt_draw_boxes_async (entity boxes composited into the G-buffer by
- *        depth). */
+ *        depth).
+ *        Additive, same minor version: RtPointLight, rt_add_lights, rt_add_lights_async (point lights added to the lighting planes
+ *        through one shadow ray per pixel and light). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

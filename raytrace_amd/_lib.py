@@ -23,7 +23,7 @@ ABI_SYMBOLS = (
     "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels", "rt_generate_world", "rt_generate_slice", "rt_read_history",
     "rt_edit_boxes_pending", "rt_slabs_pending", "rt_read_slab_boxes", "rt_probe_light", "rt_probe_light_async",
     "rt_denoise_history", "rt_denoise_planes_counted", "rt_sweep_boxes", "rt_sweep_boxes_async",
-    "rt_edit_shapes", "rt_draw_boxes", "rt_draw_boxes_async",
+    "rt_edit_shapes", "rt_draw_boxes", "rt_draw_boxes_async", "rt_add_lights", "rt_add_lights_async",
 )
 
 _amd = None
@@ -140,6 +140,10 @@ def amd():
         lib.rt_draw_boxes.restype = C.c_int
         lib.rt_draw_boxes_async.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
         lib.rt_draw_boxes_async.restype = C.c_int
+        lib.rt_add_lights.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
+        lib.rt_add_lights.restype = C.c_int
+        lib.rt_add_lights_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
+        lib.rt_add_lights_async.restype = C.c_int
         lib.rt_generate_world.argtypes = [P, C.c_uint64, C.POINTER(C.c_int64)]
         lib.rt_generate_world.restype = C.c_int
         lib.rt_generate_slice.argtypes = [P, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]
@@ -241,5 +245,7 @@ def host():
         lib.rth_pipeline_pick.restype = C.c_int
         lib.rth_pipeline_set_boxes.argtypes = [P, P, P, C.c_uint32]
         lib.rth_pipeline_set_boxes.restype = C.c_int
+        lib.rth_pipeline_set_lights.argtypes = [P, P, C.c_uint32]
+        lib.rth_pipeline_set_lights.restype = C.c_int
         _host = lib
     return _host

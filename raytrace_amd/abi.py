@@ -206,6 +206,16 @@ assert (RtDrawBox.lo.offset, RtDrawBox.material.offset, RtDrawBox.hi.offset, RtD
 MAX_DRAW_BOXES = 4096   # rt_draw_boxes: boxes per call
 
 
+class RtPointLight(C.Structure):
+    """rt_add_lights input (ABI 1.3, additive: point lights): 32 bytes; `reserved` must be 0."""
+    _fields_ = [("position", C.c_float * 3), ("radius", C.c_float), ("color", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RtPointLight) == 32
+assert (RtPointLight.position.offset, RtPointLight.radius.offset, RtPointLight.color.offset, RtPointLight.reserved.offset) == (0, 12, 16, 28)
+MAX_POINT_LIGHTS = 1024   # rt_add_lights: lights per call
+
+
 class RtDenoiseParams(C.Structure):
     """rt_denoise_history / rt_denoise_planes_counted parameters (ABI 1.3, additive): 48 bytes; `reserved` must be 0."""
     _fields_ = [("struct_size", C.c_uint32), ("faithful", C.c_int32), ("weight_by_count", C.c_int32), ("settle", C.c_uint32 * 6),

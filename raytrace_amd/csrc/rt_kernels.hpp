@@ -204,6 +204,15 @@ struct DrawBoxesArgs {
 };
 hipError_t launch_draw_boxes(const Planes& pl, const DrawBoxesArgs& a, hipStream_t st);
 
+// rt_lights.hip: point lights added to the lighting planes of a whole frame's row-major planes (rt_add_lights).  One launch for the
+// batch; a wave owns an 8x8 pixel tile.  Frame supplies the camera of the frame the planes hold (origin, forward, up, right: the ray
+// of rt_draw_boxes), lr and the region.
+struct LightsArgs {
+    const uint4* lights;  // RtPointLight[count] (two uint4 each)
+    uint32_t count;
+};
+hipError_t launch_add_lights(const Scene& sc, const Frame& f, const Planes& pl, const LightsArgs& a, hipStream_t st);
+
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
 // (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
 // or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)

@@ -233,6 +233,9 @@ int rth_pipeline_enable_history_denoise(void* p, const RtDenoiseParams* params) 
 int rth_pipeline_set_boxes(void* p, const RtDrawBox* boxes, const RtProbeLight* face_lights, uint32_t count) {
     return static_cast<render::Pipeline*>(p)->set_boxes(boxes, face_lights, count);
 }
+int rth_pipeline_set_lights(void* p, const RtPointLight* lights, uint32_t count) {
+    return static_cast<render::Pipeline*>(p)->set_lights(lights, count);
+}
 const char* rth_pipeline_last_error(void* p) { return static_cast<render::Pipeline*>(p)->last_error(); }
 // Pipeline::pick: hit (RtRayHit), adjacent and world (int32[3] each)
 int rth_pipeline_pick(void* p, int x, int y_from_top, RtRayHit* hit, int32_t* adjacent, int32_t* world) {

@@ -89,6 +89,12 @@ int Pipeline::set_boxes(const RtDrawBox* boxes, const RtProbeLight* face_lights,
     return RT_OK;
 }
 
+int Pipeline::set_lights(const RtPointLight* lights, uint32_t count) {
+    if (count > 1024u || (count > 0u && !lights)) return RT_ERR_INVALID_ARG;
+    lights_.assign(lights, lights + count);
+    return RT_OK;
+}
+
 int Pipeline::enable_history_denoise(const RtDenoiseParams& params) {
     bool ok = reproject_ && params.struct_size == sizeof(RtDenoiseParams) && (params.weight_by_count == 0 || params.weight_by_count == 1);
     for (int i = 0; i < 6; i++) ok = ok && params.settle[i] <= 127u;
@@ -182,6 +188,8 @@ int Pipeline::draw_frame(game::Game& game) {
     rc = rt_draw_frame(ctx_, &u);                                    // :209-211; the dispatch recorded at :86-90
     if (rc == RT_OK && !boxes_.empty())                              // entities go into the G-buffer before the post passes see it
         rc = rt_draw_boxes(ctx_, &u, boxes_.data(), box_lights_.data(), (uint32_t)boxes_.size());
+    if (rc == RT_OK && !lights_.empty())                             // moving lights shade the frame and its entities; the denoise filters them
+        rc = rt_add_lights(ctx_, &u, lights_.data(), (uint32_t)lights_.size());
     if (rc == RT_OK && post_) {                                      // the same command buffer goes on (:98-123), one submit (:229-235)
         // six bilateral_denoise.comp dispatches, sizes 1,2,4,8,8,16
         rc = history_denoise_ ? rt_denoise_history(ctx_, &denoise_params_) : rt_denoise(ctx_, post_faithful_ ? 1 : 0);

@@ -11,6 +11,7 @@
 //            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
 //            [--boxes N]
+//            [--lights N]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -64,6 +65,11 @@
 // (20 to 400 units away, over the whole view), their six face probes lit with rt_probe_light (4 samples, depth 2), and rt_draw_boxes
 // composites them into a freshly drawn --width x --height frame, 20 times.  One JSON line: the device time of the pass (the launch
 // bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time of rt_draw_boxes and of the probes, and the pixels drawn.
+// --lights N: instead of the frame loop, point lights.  N lights of radius 8 are scattered deterministically just off visible
+// surfaces — rt_pick_pixels on N pixels spread over the view, each light 1 to 4 units off its hit point along the face's normal (30
+// units along the ray where the pixel shows sky) — and rt_add_lights adds them to a freshly drawn --width x --height frame, 20 times.
+// One JSON line: the device time of the pass (the launch bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time of
+// rt_add_lights and the pixels lit.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -317,6 +323,73 @@ int run_boxes(rt::game::Game& game, const std::vector<uint8_t>& noise, int width
     return 0;
 }
 
+// --lights: see the head of the file
+int run_lights(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    std::vector<int32_t> xy(2u * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        xy[2u * i] = std::min(width - 1, (int)(rnd() * (float)width));
+        xy[2u * i + 1] = std::min(height - 1, (int)(rnd() * (float)height));
+    }
+    std::vector<RtRayHit> hits(n);
+    int rc = n ? rt_pick_pixels(ctx, &u, xy.data(), n, hits.data()) : RT_OK;
+    std::vector<RtPointLight> lights(n);
+    for (uint32_t i = 0; i < n && rc == RT_OK; i++) {
+        RtPointLight& l = lights[i];
+        l = RtPointLight{};
+        const float off = 1.0f + 3.0f * rnd();
+        if (hits[i].kind == RT_HIT_SOLID) {
+            for (int a = 0; a < 3; a++) l.position[a] = hits[i].position[a];
+            l.position[hits[i].normal / 2u] += hits[i].normal % 2u == 0u ? off : -off;
+        } else {
+            const float sx = ((float)xy[2u * i] / (float)width) * 2.0f - 1.0f, sy = ((float)xy[2u * i + 1] / (float)height) * 2.0f - 1.0f;
+            float v[3], len = 0.0f;
+            for (int a = 0; a < 3; a++) { v[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; len += v[a] * v[a]; }
+            len = std::sqrt(len);
+            for (int a = 0; a < 3; a++) l.position[a] = u.origin[a] + v[a] / len * 30.0f;
+        }
+        l.radius = 8.0f;
+        l.color[0] = 20.0f + 20.0f * rnd(); l.color[1] = 15.0f + 15.0f * rnd(); l.color[2] = 5.0f + 10.0f * rnd();
+    }
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    const size_t npix = (size_t)width * (size_t)height;
+    std::vector<float> before(4u * npix), after(4u * npix);
+    const int reps = 20;
+    double device_ms = 0.0, call_ms = 0.0;
+    uint32_t launches = 0;
+    for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {   // (the first repetition warms the staging up)
+        RtTiming tm{};
+        rc = rt_draw_frame(ctx, &u);
+        if (rc == RT_OK) rc = rt_sync(ctx);
+        if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);   // (drains the frame's own launches)
+        if (rc == RT_OK && i == reps) rc = rt_readback(ctx, RT_BUF_LIGHTING_F32, before.data(), npix * 16u);
+        auto t = std::chrono::steady_clock::now();
+        if (rc == RT_OK) rc = rt_add_lights(ctx, &u, lights.data(), n);
+        const double call = ms_since(t);
+        if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);
+        if (i > 0) { device_ms += tm.shade_ms / reps; call_ms += call / reps; launches += tm.other_launches; }
+    }
+    if (rc == RT_OK) rc = rt_readback(ctx, RT_BUF_LIGHTING_F32, after.data(), npix * 16u);
+    if (rc != RT_OK) { std::fprintf(stderr, "point lights failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    uint64_t lit = 0;
+    for (size_t i = 0; i < npix; i++) lit += std::memcmp(&before[4u * i], &after[4u * i], 16) != 0;
+    std::printf("{\"lights\": %u, \"frame\": \"%dx%d spp %d depth %d\", \"add_lights_device_ms\": %.4f, \"add_lights_call_ms\": %.4f, "
+                "\"launches_per_call\": %.2f, \"pixels_lit\": %llu}\n",
+                n, width, height, spp, depth, device_ms, call_ms, (double)launches / reps, (unsigned long long)lit);
+    delete p;
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -325,7 +398,7 @@ int main(int argc, char** argv) {
     bool gather = false, overlap = false, post = false, accumulate = false, edit_spread = false;
     int edits = 0, edit_radius = 0;
     const char* edit_shape = nullptr;
-    long long rays = 0, boxes = -1;
+    long long rays = 0, boxes = -1, lights = -1;
     bool rays_coherent = false;
     bool reproject = false, stream = false, stream_history = false, history_denoise = false;
     float camera_step = 0.0f;
@@ -359,6 +432,7 @@ int main(int argc, char** argv) {
         else if (want("--rays")) rays = std::atoll(argv[++i]);
         else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
         else if (want("--boxes")) boxes = std::atoll(argv[++i]);
+        else if (want("--lights")) lights = std::atoll(argv[++i]);
         else positional.push_back(argv[i]);
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
@@ -368,6 +442,7 @@ int main(int argc, char** argv) {
     if (stream_history && (!stream || !reproject || edit_radius == 0)) { std::fprintf(stderr, "--stream-history goes with --stream --reproject --edit-radius N\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
     if (boxes < -1 || boxes > 4096) { std::fprintf(stderr, "--boxes must be in 0..4096\n"); return 2; }
+    if (lights < -1 || lights > 1024) { std::fprintf(stderr, "--lights must be in 0..1024\n"); return 2; }
     if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
     if (gpus > 1) gather = true;
@@ -393,6 +468,7 @@ int main(int argc, char** argv) {
     game.generate_world(0x5EED);
     if (rays > 0) return run_rays(game, noise, width, height, spp, depth, device, (uint32_t)rays, rays_coherent);
     if (boxes >= 0) return run_boxes(game, noise, width, height, spp, depth, device, (uint32_t)boxes);
+    if (lights >= 0) return run_lights(game, noise, width, height, spp, depth, device, (uint32_t)lights);
     std::string err;
 
     // exact ray count of one frame (a counting context, outside the timed loop): the JSON line's Mrays/s is rays actually traced

@@ -13,9 +13,9 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
                   RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtInfo, RtLightProbe,
-                  RtProbeLight, RtRayHit, RtShapeEdit, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
+                  RtPointLight, RtProbeLight, RtRayHit, RtShapeEdit, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
 class RtError(RuntimeError):
@@ -80,6 +80,9 @@ assert SWEEP_DTYPE.itemsize == C.sizeof(RtBoxSweep) and SWEEP_HIT_DTYPE.itemsize
 # numpy view of RtDrawBox (include/rt_abi.h)
 DRAW_BOX_DTYPE = np.dtype([("lo", "<f4", 3), ("material", "<u4"), ("hi", "<f4", 3), ("emission", "<u4")])
 assert DRAW_BOX_DTYPE.itemsize == C.sizeof(RtDrawBox)
+# numpy view of RtPointLight (include/rt_abi.h)
+POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("reserved", "<u4")])
+assert POINT_LIGHT_DTYPE.itemsize == C.sizeof(RtPointLight)
 
 # numpy view of RtShapeEdit (include/rt_abi.h)
 SHAPE_DTYPE = np.dtype([("a", "<i4", 3), ("material", "<u4"), ("b", "<i4", 3), ("kind", "u1"), ("where", "u1"), ("solid", "u1"),
@@ -387,6 +390,20 @@ class Context:
         enqueued so far; an invalid box is skipped on the device."""
         n = check_draw_box_tensors(boxes, face_lights, self.cfg.device if self.cfg is not None else 0)
         self._check(self._lib.rt_draw_boxes_async(self._h, C.byref(uniforms), C.c_void_p(boxes.data_ptr()), C.c_void_p(face_lights.data_ptr()), n))
+
+    # -- point lights ------------------------------------------------------------------------------------
+    def add_lights(self, uniforms, lights):
+        """rt_add_lights: `lights` POINT_LIGHT_DTYPE[N] records (make_point_lights) added to the two lighting planes of the frame drawn
+        last under the camera and lr of `uniforms`, each through one shadow ray per pixel.  Synchronous; an invalid light fails the whole
+        call (RtError, INVALID_ARG)."""
+        lights = np.ascontiguousarray(lights, dtype=POINT_LIGHT_DTYPE).reshape(-1)
+        self._check(self._lib.rt_add_lights(self._h, C.byref(uniforms), _p(lights) if lights.size else None, int(lights.size)))
+
+    def add_lights_async(self, uniforms, lights):
+        """rt_add_lights_async on a torch device tensor: any contiguous tensor of N * 32 bytes (RtPointLight rows).  Enqueued behind the
+        frame drawn last; an invalid light is skipped on the device."""
+        n = check_point_light_tensors(lights, self.cfg.device if self.cfg is not None else 0)
+        self._check(self._lib.rt_add_lights_async(self._h, C.byref(uniforms), C.c_void_p(lights.data_ptr()), n))
 
     # -- frames ------------------------------------------------------------------------------------------
     def draw_frame(self, uniforms):
@@ -755,6 +772,14 @@ class Pipeline:
         if rc != 0:
             raise RtError(rc, "set_boxes: at most %d boxes" % MAX_DRAW_BOXES)
 
+    def set_lights(self, lights=None):
+        """Pipeline::set_lights: every draw_frame from now on enqueues rt_add_lights for this set behind the ray trace and the entity
+        boxes and in front of the denoise (POINT_LIGHT_DTYPE[N], copied); None or an empty set adds none."""
+        lights = np.zeros(0, dtype=POINT_LIGHT_DTYPE) if lights is None else np.ascontiguousarray(lights, dtype=POINT_LIGHT_DTYPE).reshape(-1)
+        rc = _lib.host().rth_pipeline_set_lights(self._h, _p(lights) if lights.size else None, int(lights.size))
+        if rc != 0:
+            raise RtError(rc, "set_lights: at most %d lights" % MAX_POINT_LIGHTS)
+
     def close(self):
         if self._h:
             _lib.host().rth_pipeline_free(self._h)   # impl Drop for Pipeline, pipeline.rs:258-277
@@ -917,6 +942,50 @@ def check_draw_box_tensors(boxes, face_lights, device):
         raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
     if face_lights.numel() * face_lights.element_size() != 6 * n * PROBE_LIGHT_DTYPE.itemsize:
         raise ValueError("face_lights must be a contiguous tensor of 6 N * 16 bytes")
+    return n
+
+
+def make_point_lights(positions, radii, colors):
+    """RtPointLight records (POINT_LIGHT_DTYPE) from float[N, 3] positions, float[N] radii and float[N, 3] colours in the shader's light
+    unit (one radius or colour serves every light).  Refuses what rt_add_lights refuses: a non-finite float, a coordinate beyond 2^22,
+    a radius outside (0, 1024], a colour outside [0, 2^20], more than 1024 lights."""
+    pos = np.asarray(positions, dtype=np.float32).reshape(-1, 3)
+    n = pos.shape[0]
+    if n > MAX_POINT_LIGHTS:
+        raise ValueError("at most %d lights per call" % MAX_POINT_LIGHTS)
+    radius = np.broadcast_to(np.asarray(radii, dtype=np.float32), (n,))
+    color = np.broadcast_to(np.asarray(colors, dtype=np.float32), (n, 3))
+    if not (np.isfinite(pos).all() and np.isfinite(radius).all() and np.isfinite(color).all()):
+        raise ValueError("positions, radii and colours must be finite")
+    if n and np.abs(pos).max() > 2.0 ** 22:
+        raise ValueError("positions must lie within +-2^22")
+    if not ((radius > 0) & (radius <= 1024.0)).all():
+        raise ValueError("radii must lie in (0, 1024]")
+    if not ((color >= 0) & (color <= 2.0 ** 20)).all():
+        raise ValueError("colours must lie in [0, 2^20]")
+    lights = np.zeros(n, dtype=POINT_LIGHT_DTYPE)
+    lights["position"], lights["radius"], lights["color"] = pos, radius, color
+    return lights
+
+
+def check_point_light_tensors(lights, device):
+    """Context.add_lights_async's argument: a contiguous tensor of N * 32 bytes on GPU `device`, 16-byte aligned, N at most 1024.
+    Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
+    import torch
+    if not isinstance(lights, torch.Tensor):
+        raise ValueError("lights must be a torch tensor")
+    if not lights.is_cuda or lights.device.index != int(device):
+        raise ValueError("lights must be a tensor on cuda:%d (the context's device), not %s" % (int(device), lights.device))
+    if lights.data_ptr() % 16:
+        raise ValueError("lights must be 16-byte aligned")
+    if not lights.is_contiguous():
+        raise ValueError("lights must be contiguous")
+    nbytes = lights.numel() * lights.element_size()
+    if nbytes % POINT_LIGHT_DTYPE.itemsize:
+        raise ValueError("lights must hold whole 32-byte RtPointLight records")
+    n = nbytes // POINT_LIGHT_DTYPE.itemsize
+    if n > MAX_POINT_LIGHTS:
+        raise ValueError("at most %d lights per call" % MAX_POINT_LIGHTS)
     return n
 
 
