@@ -404,6 +404,74 @@ typedef struct RtShapeEdit {      /* 32 bytes */
  * Device work per call: one launch that applies the shapes and rebuilds the touched chunks (one workgroup per chunk; only the
  * shape records and the chunk list travel), one that rebuilds their nibble-map words (counted by RT_FLAG_TIMING_ALL). */
 int rt_edit_shapes(RtContext* ctx, const RtShapeEdit* shapes, uint32_t count);
+
+/* (ABI 1.3, additive; hosts detect the feature by the rt_edit_stamps symbol) Voxel stamps: a STAMP is a dense box of voxels with
+ * their own materials that lives in device memory of a context — a tree, a house, a schematic, a moving platform, the undo of an
+ * explosion — created from host arrays or captured from the resident region, and pasted anywhere, turned or mirrored, from 32
+ * bytes per placement.  Its extent is E = (ex, ey, ez), each 1..256; per voxel it holds a packed material word and a state: */
+#define RT_STAMP_ABSENT 0          /* not part of the stamp: the world keeps what it has                         */
+#define RT_STAMP_AIR    1          /* the placed voxel becomes unoccupied                                        */
+#define RT_STAMP_SOLID  2          /* the placed voxel becomes occupied (minefield 0)                            */
+#define RT_STAMP_SKIP_AIR 0x1u     /* rt_stamp_capture: unoccupied voxels become ABSENT, not AIR */
+/*   Layout: `materials` and `state` are [ez][ey][ex], x fastest.  The material word of an ABSENT voxel is ignored, and
+ *     rt_stamp_read returns it as 0.  All of it is integer arithmetic, so results are exact.
+ *   Ids: non-zero; an id is valid from the call that returned it until rt_stamp_destroy.  Any other id is RT_ERR_INVALID_ARG in
+ *     every call.  At most 1024 live stamps per context: one more returns RT_ERR_INVALID_ARG.  Stamps belong to their context.
+ * rt_stamp_create — a stamp from host arrays.  The call returns when the stamp is on the device, so the caller's arrays are free
+ *   again.  RT_ERR_INVALID_ARG: an extent outside 1..256, a state above 2, or a NULL pointer.  RT_ERR_OOM: the stamp cannot be
+ *   allocated.  (It needs no resident world.)
+ * rt_stamp_capture — a stamp from the texel box [lo, lo + extent) of the resident region, device to device, without a host round
+ *   trip: one launch.  The box must lie inside [0, R)^3 with extents 1..256; anything else (an unknown flag bit included) is
+ *   RT_ERR_INVALID_ARG.  No resident world: RT_ERR_NOT_READY.  It is stream-ordered like the edits: it sees every earlier upload,
+ *   edit, shape, stamp, slab and generated region, and later world changes do not disturb it.  A voxel is SOLID iff its minefield
+ *   byte is 0; otherwise it is AIR, or ABSENT with RT_STAMP_SKIP_AIR.  The material word is the voxel's (0 where ABSENT).  It
+ *   changes nothing the renderer reads: no accumulation reset, no pending box, no prepass dropped.
+ * rt_stamp_info — the extent.  rt_stamp_read — the stamp's arrays back to the host (either may be NULL; synchronises).
+ * rt_stamp_destroy — placements already enqueued still read the stamp; the call may wait for them.  RtInfo.device_bytes counts
+ *   live stamps; rt_destroy frees the rest. */
+int rt_stamp_create (RtContext* ctx, const int32_t extent[3], const uint32_t* materials, const uint8_t* state, uint32_t* id_out);
+int rt_stamp_capture(RtContext* ctx, const int32_t lo[3], const int32_t extent[3], uint32_t flags, uint32_t* id_out);
+int rt_stamp_info   (RtContext* ctx, uint32_t id, int32_t extent_out[3]);
+int rt_stamp_read   (RtContext* ctx, uint32_t id, uint32_t* materials, uint8_t* state);   /* either may be NULL; synchronises */
+int rt_stamp_destroy(RtContext* ctx, uint32_t id);
+
+typedef struct RtStampPlace {      /* 32 bytes */
+    int32_t  at[3];                /*  0  texel of the low corner of the placed (oriented) box; RtVoxelEdit's space */
+    uint32_t stamp;                /* 12  id */
+    uint8_t  orient, where, reserved0[2];   /* 16  orient 0..47; where = RT_WHERE_ALL / SOLID / AIR */
+    uint32_t reserved[3];          /* 20  must be 0 */
+} RtStampPlace;
+/* rt_edit_stamps — paste `count` placements into the resident region, in batch order, each to the world the previous one left.
+ *   Orientation: orient = p << 3 | f.  p in 0..5 selects perm: (0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0): world axis k
+ *     of the placed box is stamp axis perm[k].  Bit j of f flips stamp axis j.  The placed extent is E'_k = E[perm[k]].
+ *     Placed-local cell d (0 <= d_k < E'_k) lies at world texel at + d and shows stamp voxel s, with
+ *     s[perm[k]] = (f >> perm[k]) & 1 ? E[perm[k]] - 1 - d_k : d_k.  orient >= 48 is invalid.  An orientation is a proper rotation
+ *     iff the permutation's parity plus the number of flips is even; the other 24 mirror.
+ *   Placement: the BOUNDING BOX of a placement is [at, at + E') clipped to [0, R)^3; a placement whose box is empty does nothing.
+ *     A host reissues a placement shifted by +-R when it crosses the window's seam.  Selected voxels are those of the box whose
+ *     stamp voxel is not ABSENT; `where` narrows them to world voxels occupied (minefield 0) or not at that moment, earlier
+ *     placements of the call included.  A selected voxel gets the stamp's material word and its occupancy becomes
+ *     state == SOLID; any other voxel keeps both.
+ *   Touched chunks: every 64^3 chunk that meets the bounding box of at least one placement — whether or not a voxel of it is
+ *     selected — gets its whole minefield rebuilt by rt_edit_voxels' rule and its nibble-map words rebuilt; every other chunk
+ *     keeps its bytes.  In a chunk that holds a selected voxel the result equals rt_edit_voxels with one record per selected
+ *     voxel in placement order.
+ *   Validation: on the host, before anything is enqueued; a rejected call changes nothing.  RT_ERR_INVALID_ARG: count > 4096; a
+ *     NULL pointer with count > 0; an unknown id; orient >= 48; where > 2; a non-zero reserved byte or word; an at[k] outside
+ *     [-4 R, 4 R].  No world resident: RT_ERR_NOT_READY.  count == 0, or a call that touches no chunk: RT_OK, nothing is enqueued
+ *     or reset.
+ *   Ordering, staging, accumulation: rt_edit_voxels' — stream-ordered after the frames and queries already submitted and before
+ *     later ones, also under rt_set_stream; the same two staging sets, so that stamps, shapes, voxel edits and slabs apply in call
+ *     order.  A call that touches a chunk resets RT_FLAG_ACCUMULATE's sum — except with RtConfig.edit_radius > 0, where it records
+ *     one pending box per placement that has a bounding box (that box, in placement order; at most 16 wait,
+ *     rt_edit_boxes_pending; an overflow empties the set).
+ *   Undo: capture a box with flags 0, change the world inside it by any of the edit calls, place the stamp at `lo` with orient 0
+ *     and RT_WHERE_ALL: every material word and every voxel's occupancy in the box is then what it was (on a world built by
+ *     pack_into the touched chunks' minefield bytes and all nibble-map words are too).
+ * Device work per call: one launch that applies the placements and rebuilds the touched chunks (one workgroup per chunk; only
+ * a 64-byte record per placement and the chunk list travel), one that rebuilds their nibble-map words (counted by
+ * RT_FLAG_TIMING_ALL). */
+int rt_edit_stamps(RtContext* ctx, const RtStampPlace* places, uint32_t count);
 /* Un-tile the box [x0, x0 + ex) x [y0, y0 + ey) x [z0, z0 + ez) of the resident region (texel coordinates) into the caller's layout:
  * materials u32[ex ey ez], minefield u8[ex ey ez], x fastest; either pointer may be NULL.  Waits for everything submitted before
  * (the region as the next frame would see it), then synchronises.  A box outside the region (or an extent < 1) returns
@@ -924,7 +992,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtDrawBox, rt_draw_boxes, rt_draw_boxes_async (entity boxes composited into the G-buffer by
  *        depth).
  *        Additive, same minor version: RtPointLight, rt_add_lights, rt_add_lights_async (point lights added to the lighting planes
- *        through one shadow ray per pixel and light). */
+ *        through one shadow ray per pixel and light).
+ *        Additive, same minor version: RtStampPlace, RT_STAMP_*, rt_stamp_create, rt_stamp_capture, rt_stamp_info, rt_stamp_read,
+ *        rt_stamp_destroy, rt_edit_stamps (voxel stamps: prefabs captured and pasted with rotation on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

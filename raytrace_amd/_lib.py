@@ -3,7 +3,7 @@ import fails loudly (build it with `python -m raytrace_amd.build`)."""
 import ctypes as C
 import os
 
-from .abi import RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtShapeEdit, RtTiming, RtUniforms, RtVoxelEdit
+from .abi import RtConfig, RtCounters, RtDenoiseParams, RtInfo, RtShapeEdit, RtStampPlace, RtTiming, RtUniforms, RtVoxelEdit
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # RT_AMD_LIB: load another build of the same library (same-box A/B timing of two kernel variants, tools/ab.sh)
@@ -24,6 +24,7 @@ ABI_SYMBOLS = (
     "rt_edit_boxes_pending", "rt_slabs_pending", "rt_read_slab_boxes", "rt_probe_light", "rt_probe_light_async",
     "rt_denoise_history", "rt_denoise_planes_counted", "rt_sweep_boxes", "rt_sweep_boxes_async",
     "rt_edit_shapes", "rt_draw_boxes", "rt_draw_boxes_async", "rt_add_lights", "rt_add_lights_async",
+    "rt_stamp_create", "rt_stamp_capture", "rt_stamp_info", "rt_stamp_read", "rt_stamp_destroy", "rt_edit_stamps",
 )
 
 _amd = None
@@ -120,6 +121,14 @@ def amd():
         lib.rt_edit_voxels.restype = C.c_int
         lib.rt_edit_shapes.argtypes = [P, C.POINTER(RtShapeEdit), C.c_uint32]
         lib.rt_edit_shapes.restype = C.c_int
+        lib.rt_stamp_create.argtypes = [P, C.POINTER(C.c_int32), P, P, C.POINTER(C.c_uint32)]
+        lib.rt_stamp_capture.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.rt_stamp_info.argtypes = [P, C.c_uint32, C.POINTER(C.c_int32)]
+        lib.rt_stamp_read.argtypes = [P, C.c_uint32, P, P]
+        lib.rt_stamp_destroy.argtypes = [P, C.c_uint32]
+        lib.rt_edit_stamps.argtypes = [P, C.POINTER(RtStampPlace), C.c_uint32]
+        for name in ("rt_stamp_create", "rt_stamp_capture", "rt_stamp_info", "rt_stamp_read", "rt_stamp_destroy", "rt_edit_stamps"):
+            getattr(lib, name).restype = C.c_int
         lib.rt_read_box.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]
         lib.rt_read_box.restype = C.c_int
         lib.rt_trace_rays.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]

@@ -144,6 +144,19 @@ class RtShapeEdit(C.Structure):
 assert C.sizeof(RtShapeEdit) == 32
 
 
+RT_STAMP_ABSENT, RT_STAMP_AIR, RT_STAMP_SOLID = 0, 1, 2   # a stamp voxel's state (ABI 1.3, additive: voxel stamps)
+RT_STAMP_SKIP_AIR = 0x1                                    # rt_stamp_capture flag: unoccupied voxels become ABSENT, not AIR
+
+
+class RtStampPlace(C.Structure):
+    """rt_edit_stamps record (ABI 1.3, additive): one placement of a stamp, 32 bytes; the reserved fields must be 0."""
+    _fields_ = [("at", C.c_int32 * 3), ("stamp", C.c_uint32), ("orient", C.c_uint8), ("where", C.c_uint8), ("reserved0", C.c_uint8 * 2),
+                ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(RtStampPlace) == 32
+
+
 RT_HIT_AIR, RT_HIT_SOLID, RT_HIT_LIMIT = 0, 1, 2   # RtRayHit.kind (ABI 1.3, additive: ray queries)
 
 

@@ -383,6 +383,10 @@ void rt_destroy(RtContext* ctx) {
     for (TimingPool* t : {&ctx->launch_times, &ctx->gather_times}) for (hipEvent_t e : t->ev) (void)hipEventDestroy(e);
     for (StagingSet* s : {&ctx->slab_sets[0], &ctx->slab_sets[1], &ctx->edit_sets[0], &ctx->edit_sets[1]}) s->release();
     ctx->query_block.release();
+    for (StampEntry& e : ctx->stamps.slots) {   // the stamps nobody destroyed
+        if (e.mats) (void)hipFree(reinterpret_cast<void*>(e.mats));
+        if (e.state) (void)hipFree(reinterpret_cast<void*>(e.state));
+    }
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (hipStream_t st : ctx->streams) (void)hipStreamDestroy(st);
     delete ctx;

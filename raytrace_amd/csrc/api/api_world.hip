@@ -1,5 +1,6 @@
 // api_world.hip — the kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits, shape
-// edits and terrain generated on the device; rt_read_box reads the resident region back.
+// edits, voxel stamps (their store, capture and placement) and terrain generated on the device; rt_read_box reads the resident
+// region back.
 #include "rt_context.hpp"
 
 using namespace rta;
@@ -110,6 +111,29 @@ int generate_terrain(RtContext* c, uint64_t seed, const int64_t lo[3], int axis)
     RT_HIP(c, slab_scan_new(c, masks, axis, offset));
     RT_HIP(c, world_change_end(c));
     return RT_OK;
+}
+
+// ---- voxel stamps (rt_stamp_*): device arrays of their own, counted in device_bytes while the stamp lives -----------------------
+// the arrays of a new entry; on failure nothing stays allocated and the entry is removed
+hipError_t stamp_alloc(RtContext* c, StampEntry* e) {
+    void *m = nullptr, *s = nullptr;
+    hipError_t err = hipMalloc(&m, e->voxels() * sizeof(uint32_t));
+    if (err == hipSuccess) err = hipMalloc(&s, e->voxels());
+    if (err != hipSuccess) {
+        if (m) (void)hipFree(m);
+        c->stamps.remove(e);
+        return err;
+    }
+    e->mats = reinterpret_cast<uint64_t>(m);
+    e->state = reinterpret_cast<uint64_t>(s);
+    c->device_bytes += e->voxels() * 5u;
+    return hipSuccess;
+}
+void stamp_free(RtContext* c, StampEntry* e) {
+    c->device_bytes -= e->voxels() * 5u;
+    (void)hipFree(reinterpret_cast<void*>(e->mats));
+    (void)hipFree(reinterpret_cast<void*>(e->state));
+    c->stamps.remove(e);
 }
 
 }  // namespace
@@ -322,6 +346,145 @@ int rt_edit_shapes(RtContext* ctx, const RtShapeEdit* shapes, uint32_t count) {
     {
         LaunchTimer lt(ctx, 1);
         RT_HIP(ctx, rtd::launch_shape_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, s.dev + plan.off_shapes, count, plan.touched, ctx->logr, ctx->stream));
+    }
+    {
+        LaunchTimer lt(ctx, 1);
+        RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, plan.touched, ctx->logr, ctx->stream));
+    }
+    RT_HIP(ctx, staging_applied(ctx, s));
+    return RT_OK;
+}
+
+int rt_stamp_create(RtContext* ctx, const int32_t extent[3], const uint32_t* materials, const uint8_t* state, uint32_t* id_out) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!extent || !materials || !state || !id_out) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_create: null pointer");
+    if (!stamp_extent_valid(extent)) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_create: an extent outside 1..256");
+    const size_t n = (size_t)extent[0] * (size_t)extent[1] * (size_t)extent[2];
+    for (size_t i = 0; i < n; i++)
+        if (state[i] > RT_STAMP_SOLID) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_create: a state above 2");
+    if (ctx->stamps.live == kMaxStamps) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_create: 1024 stamps are live");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->upload_stream) RT_HIP(ctx, new_stream(ctx, &ctx->upload_stream));
+    StampEntry* e = ctx->stamps.add(extent);
+    RT_HIP(ctx, stamp_alloc(ctx, e));
+    // the arrays, then the words of ABSENT voxels cleared, on the upload stream; the host waits for both, so that the caller's
+    // arrays are free and every later call, whatever its stream, finds the stamp complete
+    hipError_t err = hipMemcpyAsync(reinterpret_cast<void*>(e->mats), materials, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->upload_stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(reinterpret_cast<void*>(e->state), state, n, hipMemcpyHostToDevice, ctx->upload_stream);
+    if (err == hipSuccess) err = rtd::launch_stamp_clean(reinterpret_cast<uint32_t*>(e->mats), reinterpret_cast<const uint8_t*>(e->state), (uint32_t)n, ctx->upload_stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->upload_stream);
+    if (err != hipSuccess) {
+        stamp_free(ctx, e);
+        return fail(ctx, err == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, std::string("rt_stamp_create: ") + hipGetErrorString(err));
+    }
+    *id_out = e->id;
+    return RT_OK;
+}
+
+int rt_stamp_capture(RtContext* ctx, const int32_t lo[3], const int32_t extent[3], uint32_t flags, uint32_t* id_out) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (!lo || !extent || !id_out) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_capture: null pointer");
+    if ((flags & ~RT_STAMP_SKIP_AIR) != 0u) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_capture: unknown flag");
+    if (!stamp_extent_valid(extent)) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_capture: an extent outside 1..256");
+    for (int k = 0; k < 3; k++)
+        if (lo[k] < 0 || extent[k] > ctx->region - lo[k]) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_capture: box outside the region");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_stamp_capture: upload the full region first");
+    if (ctx->stamps.live == kMaxStamps) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_capture: 1024 stamps are live");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    StampEntry* e = ctx->stamps.add(extent);
+    RT_HIP(ctx, stamp_alloc(ctx, e));
+    // One launch on the stream the edits use: behind every earlier world change (they ran there, or the lanes were fenced behind
+    // them), and every later one joins the lanes before it writes.  It reads the region only, so frames and queries need no order.
+    hipError_t err;
+    {
+        LaunchTimer lt(ctx, 1);
+        err = rtd::launch_stamp_capture(ctx->d_mine_sw, ctx->d_mat_sw, ctx->logr, lo[0], lo[1], lo[2], extent[0], extent[1], extent[2],
+                                        (flags & RT_STAMP_SKIP_AIR) != 0u, reinterpret_cast<uint32_t*>(e->mats), reinterpret_cast<uint8_t*>(e->state),
+                                        ctx->stream);
+    }
+    if (err == hipSuccess) err = fence_lanes_after(ctx, ctx->stream);   // (a later change may start on the other lane's stream)
+    if (err != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);
+        stamp_free(ctx, e);
+        return fail(ctx, RT_ERR_HIP, std::string("rt_stamp_capture: ") + hipGetErrorString(err));
+    }
+    e->used = true;
+    *id_out = e->id;
+    return RT_OK;
+}
+
+int rt_stamp_info(RtContext* ctx, uint32_t id, int32_t extent_out[3]) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const StampEntry* e = ctx->stamps.find(id);
+    if (!e) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_info: unknown stamp id");
+    if (!extent_out) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_info: null pointer");
+    for (int k = 0; k < 3; k++) extent_out[k] = e->ext[k];
+    return RT_OK;
+}
+
+int rt_stamp_read(RtContext* ctx, uint32_t id, uint32_t* materials, uint8_t* state) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    StampEntry* e = ctx->stamps.find(id);
+    if (!e) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_read: unknown stamp id");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, sync_lanes(ctx));   // (a capture may still be writing it)
+    e->used = false;
+    if (materials) RT_HIP(ctx, hipMemcpy(materials, reinterpret_cast<const void*>(e->mats), e->voxels() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (state) RT_HIP(ctx, hipMemcpy(state, reinterpret_cast<const void*>(e->state), e->voxels(), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_stamp_destroy(RtContext* ctx, uint32_t id) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    StampEntry* e = ctx->stamps.find(id);
+    if (!e) return fail(ctx, RT_ERR_INVALID_ARG, "rt_stamp_destroy: unknown stamp id");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (e->used) RT_HIP(ctx, sync_lanes(ctx));   // the capture that wrote it and the placements that read it have finished
+    stamp_free(ctx, e);
+    return RT_OK;
+}
+
+int rt_edit_stamps(RtContext* ctx, const RtStampPlace* places, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    if (count > kMaxStampPlaces) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_stamps: more than 4096 placements in one call; nothing was applied");
+    if (count == 0) return RT_OK;
+    if (!places) return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_stamps: null places");
+    if (!ctx->world_resident) return fail(ctx, RT_ERR_NOT_READY, "rt_edit_stamps: upload the full region first");
+    // Validation, bounding boxes and the touched chunks on the host, all of it before anything is enqueued (edit_stamps.hpp)
+    const uint32_t bad = places_validate(ctx->stamps, places, count, ctx->logr);
+    if (bad != count)
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_stamps: placement " + std::to_string(bad) +
+                                                 " has an unknown stamp id, orient >= 48, where > 2, a non-zero reserved field or an at[k]"
+                                                 " outside [-4R, 4R]; nothing was applied");
+    const StampPlan plan = stamps_touched(ctx->shape_scratch, ctx->stamps, places, count, ctx->logr);
+    if (plan.touched == 0u) return RT_OK;   // (every placement lies outside the region: nothing is enqueued, nothing is reset)
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    // rt_edit_voxels' staging sets and counter, so that stamps, shapes and voxel edits apply in call order: the chunk ids, then one
+    // record per placement with the id resolved into the stamp's device arrays
+    StagingSet& s = ctx->edit_sets[ctx->edit_batches & 1u];
+    const size_t cap = plan.need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(plan.need + plan.need / 2u);   // (if the set must grow)
+    RT_HIP(ctx, staging_claim(ctx, s, plan.need, cap));
+    shapes_fill_chunks(ctx->shape_scratch, reinterpret_cast<uint32_t*>(s.host));
+    stamp_fill_records(ctx->stamps, places, count, ctx->logr, reinterpret_cast<StampRecord*>(s.host + plan.off_recs));
+    for (uint32_t i = 0; i < count; i++) ctx->stamps.find(places[i].stamp)->used = true;
+    ctx->edit_batches++;
+    if (ctx->edit_radius == 0u) {
+        ctx->accum_valid = false;
+    } else if (!ctx->edit_overflow) {
+        // the history stays: one box per placement that has a bounding box waits for the next frame drawn (rt_edit_voxels' set and rule)
+        if (ctx->edit_nbox + plan.boxes > rtd::kTemporalMaxBoxes) {
+            ctx->edit_nbox = 0;
+            ctx->edit_overflow = true;
+        } else {
+            ctx->edit_nbox += stamp_pending_boxes(ctx->stamps, places, count, ctx->logr, ctx->edit_boxes + ctx->edit_nbox);
+        }
+    }
+    invalidate_prepass(ctx);
+    RT_HIP(ctx, staging_send(ctx, s, plan.need));
+    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
+    {
+        LaunchTimer lt(ctx, 1);
+        RT_HIP(ctx, rtd::launch_stamp_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, s.dev + plan.off_recs, count, plan.touched, ctx->logr, ctx->stream));
     }
     {
         LaunchTimer lt(ctx, 1);

@@ -20,6 +20,7 @@
 #include "../rt_kernels.hpp"
 #include "edit_binning.hpp"
 #include "edit_shapes.hpp"
+#include "edit_stamps.hpp"
 
 namespace rta __attribute__((visibility("hidden"))) {
 
@@ -197,12 +198,13 @@ struct __attribute__((visibility("hidden"))) RtContext {
     uint32_t* d_brick = nullptr;          // R > 256: per-brick nibble map (rtd::Scene::brick), R^3 / 128 bytes
     // staging (StagingSet): rt_upload_slice's 16-thick slab (materials, then minefield at 4 x 16 R^2) is re-tiled, rt_edit_voxels'
     // binned batch (touched chunks, per-chunk edit ranges, records) and rt_edit_shapes' (touched chunks, shape records) rebuild
-    // their chunks; the edit sets grow when a batch needs more
+    // their chunks, as does rt_edit_stamps' (touched chunks, one 64-byte record per placement); the edit sets grow when a batch needs more
     hipStream_t upload_stream = nullptr;
     rta::StagingSet slab_sets[2], edit_sets[2];
     uint64_t slabs = 0, edit_batches = 0;   // submitted so far: the next one uses set slabs & 1 / edit_batches & 1
     rta::EditBinning edit_binning;        // host binning scratch, kept between calls
     rta::ShapeScratch shape_scratch;      // rt_edit_shapes: the mark per chunk, kept between calls (it shares the edit sets)
+    rta::StampStore stamps;               // the live voxel stamps (rt_stamp_*): device arrays of their own, counted in device_bytes
     int32_t* d_heights = nullptr;         // rt_generate_world / rt_generate_slice: column heights of (R/64 + 1)^2 chunks, on first use
 
     // tiling

@@ -144,6 +144,14 @@ hipError_t launch_rebuild_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint3
 // rt_edit_shapes: `shapes` = nshapes RtShapeEdit records (32 bytes each) as the caller gave them, validated on the host
 hipError_t launch_shape_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const void* shapes, uint32_t nshapes,
                                uint32_t nchunks, int logr, hipStream_t st);
+// rt_edit_stamps: `recs` = nrecs 64-byte placement records (api/edit_stamps.hpp, StampRecord), resolved and validated on the host
+hipError_t launch_stamp_chunks(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, const void* recs, uint32_t nrecs,
+                               uint32_t nchunks, int logr, hipStream_t st);
+// rt_stamp_capture: the region's box (x0, y0, z0) + [0, ex) x [0, ey) x [0, ez) into a stamp's arrays (x fastest; at most 2^24 voxels)
+hipError_t launch_stamp_capture(const uint8_t* mine_sw, const uint32_t* mat_sw, int logr, int x0, int y0, int z0, int ex, int ey, int ez,
+                                bool skip_air, uint32_t* mats_out, uint8_t* state_out, hipStream_t st);
+// rt_stamp_create: clears the material words of the n voxels' ABSENT ones
+hipError_t launch_stamp_clean(uint32_t* mats, const uint8_t* state, uint32_t n, hipStream_t st);
 hipError_t launch_rebuild_chunk_maps(const uint8_t* mine_sw, uint32_t* coarse, uint32_t* brick, const uint32_t* chunks, uint32_t nchunks,
                                      int logr, hipStream_t st);
 // rt_terrain.hip: rt_generate_world (axis = -1: the window [lo, lo + R) on every axis) and rt_generate_slice (axis 0..2: 16 voxels

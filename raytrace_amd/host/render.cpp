@@ -131,6 +131,17 @@ int Pipeline::probe_light(const RtLightProbe* probes, uint32_t count, uint32_t s
 
 int Pipeline::edit_shapes(const RtShapeEdit* shapes, uint32_t count) { return rt_edit_shapes(ctx_, shapes, count); }
 
+int Pipeline::stamp_create(const int32_t extent[3], const uint32_t* materials, const uint8_t* state, uint32_t* id_out) {
+    return rt_stamp_create(ctx_, extent, materials, state, id_out);
+}
+int Pipeline::stamp_capture(const int32_t lo[3], const int32_t extent[3], uint32_t flags, uint32_t* id_out) {
+    return rt_stamp_capture(ctx_, lo, extent, flags, id_out);
+}
+int Pipeline::stamp_info(uint32_t id, int32_t extent_out[3]) { return rt_stamp_info(ctx_, id, extent_out); }
+int Pipeline::stamp_read(uint32_t id, uint32_t* materials, uint8_t* state) { return rt_stamp_read(ctx_, id, materials, state); }
+int Pipeline::stamp_destroy(uint32_t id) { return rt_stamp_destroy(ctx_, id); }
+int Pipeline::edit_stamps(const RtStampPlace* places, uint32_t count) { return rt_edit_stamps(ctx_, places, count); }
+
 int Pipeline::wait() { return rt_sync(ctx_); }
 
 static bool invert3(const float c0[3], const float c1[3], const float c2[3], float out[3][3]) {

@@ -114,6 +114,15 @@ class Pipeline {
     // texels are the region's, as PickResult::hit.texel; a shape that crosses the window's seam is issued again shifted by the
     // region's edge (INTEGRATION.md "Explosions and brushes").
     int edit_shapes(const RtShapeEdit* shapes, uint32_t count);
+    // Voxel stamps: dense boxes of voxels kept on the device (a tree, a house, a saved box for undo), made from host arrays or
+    // captured from the resident region, and pasted turned or mirrored from 32 bytes per placement: rt_stamp_*, rt_edit_stamps.
+    // Ids belong to this pipeline's context (INTEGRATION.md "Prefabs and undo").
+    int stamp_create(const int32_t extent[3], const uint32_t* materials, const uint8_t* state, uint32_t* id_out);
+    int stamp_capture(const int32_t lo[3], const int32_t extent[3], uint32_t flags, uint32_t* id_out);
+    int stamp_info(uint32_t id, int32_t extent_out[3]);
+    int stamp_read(uint32_t id, uint32_t* materials, uint8_t* state);
+    int stamp_destroy(uint32_t id);
+    int edit_stamps(const RtStampPlace* places, uint32_t count);
     // Entity boxes: every draw_frame from now on enqueues rt_draw_boxes(boxes, face_lights, count) between the ray trace and the
     // denoise (both arrays are copied; face_lights holds 6 * count records, e.g. probe_light's for the boxes' face probes).
     // count == 0 draws none.  RT_ERR_INVALID_ARG for more than 4096 boxes or a NULL array with count > 0.

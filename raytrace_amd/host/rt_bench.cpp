@@ -46,6 +46,11 @@
 // per edge — whose low corner is moved down to a multiple of 64 when E is one (box:64 is exactly one chunk, box:256 the region) —
 // clipped to the region.  Timed like --edits; the JSON line carries the same four edit timing fields and "edit_shape".
 //
+// --edit-stamp N (1..4096): before every frame, rt_edit_stamps pastes N copies of a small built-in stamp (a 5 x 5 x 7 hut: walls, a
+// hollow of AIR, ABSENT corners) where --edit-shape puts its shape, side by side in rows of eight and each turned by its index — on odd
+// frames an all-AIR stamp of the same extent, which takes the huts away again.  Timed like --edits; the JSON line carries the same
+// four edit timing fields and "edit_stamp".
+//
 // --edit-radius N (with --reproject --edits N): RtConfig.edit_radius — the edits no longer restart the lighting history; every frame
 // runs the moved pass with the edited boxes and restarts only the pixels near one or in its sun shadow.  The JSON line's acc_frames /
 // samples (rt_get_accumulation) show that the history went on.
@@ -185,6 +190,35 @@ bool shape_brush(const char* text, const float origin[3], RtShapeEdit* out) {
     *out = s;
     return true;
 }
+
+// --edit-stamp: the built-in stamps of one pipeline (ids[0] the hut, ids[1] the all-AIR one) and the placements of N copies
+bool stamp_brush_create(rt::render::Pipeline* p, uint32_t ids[2]) {
+    const int32_t ext[3] = {5, 5, 7};
+    std::vector<uint32_t> mats(5 * 5 * 7, (1u << 15) | (90u << 14) | (60u << 7) | 30u);
+    std::vector<uint8_t> hut(5 * 5 * 7), air(5 * 5 * 7, RT_STAMP_AIR);
+    for (int z = 0; z < 7; z++)
+        for (int y = 0; y < 5; y++)
+            for (int x = 0; x < 5; x++) {
+                const bool edge_x = x == 0 || x == 4, edge_y = y == 0 || y == 4;
+                hut[(size_t)(z * 5 + y) * 5 + x] = (edge_x && edge_y && z > 4) ? RT_STAMP_ABSENT : (edge_x || edge_y || z == 0 || z >= 5) ? RT_STAMP_SOLID : RT_STAMP_AIR;
+            }
+    return p->stamp_create(ext, mats.data(), hut.data(), &ids[0]) == RT_OK && p->stamp_create(ext, mats.data(), air.data(), &ids[1]) == RT_OK;
+}
+std::vector<RtStampPlace> stamp_brush(int n, const float origin[3]) {
+    const int R = RT_ROOT_BLOCK_SIZE;
+    const int c[3] = {(int)origin[0] + R / 2, (int)origin[1] + R / 2 + 16, (int)origin[2] + R / 2};
+    std::vector<RtStampPlace> v((size_t)n);
+    for (int i = 0; i < n; i++) {
+        RtStampPlace& s = v[(size_t)i];
+        s = RtStampPlace{};
+        const int at[3] = {c[0] - 32 + 8 * (i % 8), c[1] - 32 + 8 * ((i / 8) % 8), c[2] - 8 + 8 * (i / 64)};
+        for (int a = 0; a < 3; a++) s.at[a] = std::min(std::max(at[a], 0), R - 8);   // (inside the region, as --edit-shape's box)
+        s.orient = (uint8_t)(i % 48);
+        s.where = RT_WHERE_ALL;
+    }
+    return v;
+}
+void set_stamp(std::vector<RtStampPlace>& v, const uint32_t ids[2], int frame) { for (RtStampPlace& s : v) s.stamp = ids[frame & 1]; }
 
 // --rays: see the head of the file
 int run_rays(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device,
@@ -398,6 +432,7 @@ int main(int argc, char** argv) {
     bool gather = false, overlap = false, post = false, accumulate = false, edit_spread = false;
     int edits = 0, edit_radius = 0;
     const char* edit_shape = nullptr;
+    int edit_stamp = -1;
     long long rays = 0, boxes = -1, lights = -1;
     bool rays_coherent = false;
     bool reproject = false, stream = false, stream_history = false, history_denoise = false;
@@ -427,6 +462,7 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--edit-spread") == 0) edit_spread = true;
         else if (want("--edit-radius")) edit_radius = std::atoi(argv[++i]);
         else if (want("--edit-shape")) edit_shape = argv[++i];
+        else if (want("--edit-stamp")) edit_stamp = std::atoi(argv[++i]);
         else if (std::strcmp(argv[i], "--stream") == 0) stream = true;
         else if (std::strcmp(argv[i], "--stream-history") == 0) stream_history = true;
         else if (want("--rays")) rays = std::atoll(argv[++i]);
@@ -437,7 +473,7 @@ int main(int argc, char** argv) {
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
     if (edits < 0 || edits > (1 << 24)) { std::fprintf(stderr, "--edits must be in 0..2^24\n"); return 2; }
-    if (edit_radius != 0 && (!reproject || (edits == 0 && !edit_shape && !stream_history))) { std::fprintf(stderr, "--edit-radius goes with --reproject and --edits N or --stream-history\n"); return 2; }
+    if (edit_radius != 0 && (!reproject || (edits == 0 && !edit_shape && edit_stamp < 0 && !stream_history))) { std::fprintf(stderr, "--edit-radius goes with --reproject and --edits N or --stream-history\n"); return 2; }
     if (stream && gpus > 1) { std::fprintf(stderr, "--stream needs one device\n"); return 2; }
     if (stream_history && (!stream || !reproject || edit_radius == 0)) { std::fprintf(stderr, "--stream-history goes with --stream --reproject --edit-radius N\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
@@ -452,6 +488,11 @@ int main(int argc, char** argv) {
     RtShapeEdit shape{};
     if (edit_shape && (edits > 0 || !shape_brush(edit_shape, game.camera.origin, &shape))) {
         std::fprintf(stderr, "--edit-shape is sphere:R (0..512) or box:E (1..256), without --edits\n");
+        return 2;
+    }
+
+    if (edit_stamp != -1 && (edit_stamp < 1 || edit_stamp > 4096 || edits > 0 || edit_shape)) {
+        std::fprintf(stderr, "--edit-stamp is 1..4096, without --edits and --edit-shape\n");
         return 2;
     }
 
@@ -521,6 +562,13 @@ int main(int argc, char** argv) {
     std::printf("Created in %fs.\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());   // main.rs:13
 
     std::vector<std::vector<RtVoxelEdit>> brushes((size_t)gpus, edit_brush(edits, edit_spread, game.camera.origin));
+    std::vector<std::vector<RtStampPlace>> stamp_places((size_t)gpus, stamp_brush(edit_stamp > 0 ? edit_stamp : 0, game.camera.origin));
+    std::vector<uint32_t> stamp_ids(2 * (size_t)gpus, 0u);
+    for (int g = 0; g < gpus && edit_stamp > 0; g++)
+        if (!stamp_brush_create(pipes[(size_t)g], &stamp_ids[2 * (size_t)g])) {
+            std::fprintf(stderr, "rt_stamp_create failed on device %d: %s\n", devices[(size_t)g], pipes[(size_t)g]->last_error());
+            return 1;
+        }
     RingBufferAverage perf(120);                                      // main.rs:16
     ThreadBarrier frame_barrier(gpus);
     std::atomic<int> failed{0};
@@ -552,6 +600,11 @@ int main(int argc, char** argv) {
                 sh.solid = (uint8_t)((f & 1) == 0);
                 rc = p->edit_shapes(&sh, 1);
                 if (rc != RT_OK) std::fprintf(stderr, "rt_edit_shapes failed on device %d (%d): %s\n", devices[(size_t)g], rc, rt_last_error(p->context()));
+            }
+            if (edit_stamp > 0) {
+                set_stamp(stamp_places[(size_t)g], &stamp_ids[2 * (size_t)g], f);
+                rc = p->edit_stamps(stamp_places[(size_t)g].data(), (uint32_t)edit_stamp);
+                if (rc != RT_OK) std::fprintf(stderr, "rt_edit_stamps failed on device %d (%d): %s\n", devices[(size_t)g], rc, rt_last_error(p->context()));
             }
             if (rc == RT_OK) rc = p->draw_frame(game);                // main.rs:52
             if (rc != RT_OK) {
@@ -587,7 +640,7 @@ int main(int argc, char** argv) {
     int exit_code = failed.load() ? 1 : 0;
     // --edits: the edit batches alone, on a pipeline whose launches are timed
     double edit_dev_ms = 0.0, edit_host_ms = 0.0, edit_wall_ms = 0.0, edit_launches = 0.0;
-    if (!exit_code && (edits > 0 || edit_shape)) {
+    if (!exit_code && (edits > 0 || edit_shape || edit_stamp > 0)) {
         RtConfig tcfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
         rt::render::Pipeline* tp = rt::render::create_instance(tcfg, noise.data(), game, &err);
         RtTiming tm{};
@@ -596,13 +649,18 @@ int main(int argc, char** argv) {
             exit_code = 1;
         } else {
             std::vector<RtVoxelEdit> brush = edit_brush(edits, edit_spread, game.camera.origin);
+            std::vector<RtStampPlace> places = stamp_brush(edit_stamp > 0 ? edit_stamp : 0, game.camera.origin);
+            uint32_t ids[2] = {0, 0};
+            if (edit_stamp > 0 && !stamp_brush_create(tp, ids)) exit_code = 1;
             const auto w0 = std::chrono::steady_clock::now();
             for (int f = 0; f < frames && !exit_code; f++) {
                 set_solid(brush, f);
                 RtShapeEdit sh = shape;
                 sh.solid = (uint8_t)((f & 1) == 0);
                 const auto h0 = std::chrono::steady_clock::now();
-                if ((edit_shape ? tp->edit_shapes(&sh, 1) : rt_edit_voxels(tp->context(), brush.data(), (uint32_t)edits)) != RT_OK) exit_code = 1;
+                set_stamp(places, ids, f);
+                if ((edit_stamp > 0 ? tp->edit_stamps(places.data(), (uint32_t)edit_stamp)
+                     : edit_shape ? tp->edit_shapes(&sh, 1) : rt_edit_voxels(tp->context(), brush.data(), (uint32_t)edits)) != RT_OK) exit_code = 1;
                 edit_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
             }
             if (rt_sync(tp->context()) != RT_OK) exit_code = 1;
@@ -641,13 +699,13 @@ int main(int argc, char** argv) {
                     "\"ms_per_frame\": %.4f, \"avg_ms_last_120\": %.4f, \"max_ms_last_120\": %.4f, \"mrays_per_s\": %.2f, "
                     "\"depth_plane_checksum\": %llu, \"final_image_checksum\": %llu, \"accumulate\": %s, \"reproject\": %s, \"camera_step\": %g, \"samples\": %u, \"acc_frames\": %u, \"edit_radius\": %d, \"stream\": %s, \"stream_history\": %s, "
                     "\"edits\": %d, \"edit_spread\": %s, \"edit_device_ms_per_call\": %.4f, \"edit_launches_per_call\": %.1f, "
-                    "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f%s%s%s%s}\n",
+                    "\"edit_host_ms_per_call\": %.4f, \"edit_wall_ms_per_call\": %.4f%s%s%s%s%s}\n",
                     width, height, spp, depth, gpus, gather ? (overlap ? "rccl-overlapped" : "rccl-serial") : "none", post ? "true" : "false",
                     game.camera.origin[0], game.camera.origin[1], game.camera.origin[2], game.camera.heading, game.camera.pitch,
                     game.sun_angle, frames, rays_per_frame, ms, perf.average(), perf.max(), (double)rays_per_frame / (ms * 1e3), checksum, final_checksum,
                     accumulate ? "true" : "false", reproject ? "true" : "false", (double)camera_step, acc_samples, acc_frames, edit_radius, stream ? "true" : "false", stream_history ? "true" : "false", edits, edit_spread ? "true" : "false", edit_dev_ms, edit_launches,
                     edit_host_ms, edit_wall_ms, history_denoise ? ", \"history_denoise\": true" : "", edit_shape ? ", \"edit_shape\": \"" : "",
-                    edit_shape ? edit_shape : "", edit_shape ? "\"" : "");
+                    edit_shape ? edit_shape : "", edit_shape ? "\"" : "", edit_stamp > 0 ? (", \"edit_stamp\": " + std::to_string(edit_stamp)).c_str() : "");
     }
     for (int g = 0; g < gpus; g++) {
         if (comms[(size_t)g]) rt_comm_destroy(comms[(size_t)g]);

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
                   RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtInfo, RtLightProbe,
-                  RtPointLight, RtProbeLight, RtRayHit, RtShapeEdit, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
+                  RtPointLight, RtProbeLight, RtRayHit, RtShapeEdit, RtStampPlace, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
 class RtError(RuntimeError):
@@ -108,6 +108,19 @@ def sphere_shape(centre, radius, material=0, solid=True, where=RT_WHERE_ALL):
     s = np.zeros((), dtype=SHAPE_DTYPE)
     s["a"], s["b"] = [int(v) for v in c2], [int(d) * int(d), 0, 0]
     s["material"], s["kind"], s["where"], s["solid"] = int(material) & 0xFFFFFFFF, RT_SHAPE_SPHERE, int(where), 1 if solid else 0
+    return s
+
+
+# numpy view of RtStampPlace (include/rt_abi.h)
+STAMP_PLACE_DTYPE = np.dtype([("at", "<i4", 3), ("stamp", "<u4"), ("orient", "u1"), ("where", "u1"), ("reserved0", "u1", 2),
+                              ("reserved", "<u4", 3)])
+assert STAMP_PLACE_DTYPE.itemsize == C.sizeof(RtStampPlace)
+
+
+def stamp_place(stamp, at, orient=0, where=RT_WHERE_ALL):
+    """One RtStampPlace row: stamp `stamp` with the low corner of its oriented box at texel `at` (x, y, z); orient = p << 3 | f."""
+    s = np.zeros((), dtype=STAMP_PLACE_DTYPE)
+    s["at"], s["stamp"], s["orient"], s["where"] = [int(v) for v in at], int(stamp), int(orient), int(where)
     return s
 
 
@@ -248,6 +261,51 @@ class Context:
             shapes = np.array([np.asarray(s, dtype=SHAPE_DTYPE) for s in shapes], dtype=SHAPE_DTYPE).reshape(-1)
         shapes = np.ascontiguousarray(shapes).reshape(-1)
         self._check(self._lib.rt_edit_shapes(self._h, shapes.ctypes.data_as(C.POINTER(RtShapeEdit)), int(shapes.size)))
+
+    def stamp_create(self, materials, state):
+        """rt_stamp_create: a stamp from materials u32[ez, ey, ex] and state u8[ez, ey, ex] (0 absent, 1 air, 2 solid); returns its id."""
+        materials = np.ascontiguousarray(materials, dtype=np.uint32)
+        state = np.ascontiguousarray(state, dtype=np.uint8)
+        if materials.ndim != 3 or materials.shape != state.shape:
+            raise ValueError("materials and state are [ez, ey, ex] arrays of one shape")
+        ext = (C.c_int32 * 3)(*materials.shape[::-1])
+        out = C.c_uint32(0)
+        self._check(self._lib.rt_stamp_create(self._h, ext, _p(materials), _p(state), C.byref(out)))
+        return out.value
+
+    def stamp_capture(self, lo, extent, flags=0):
+        """rt_stamp_capture: a stamp from the resident region's box at texel `lo` (x, y, z) of `extent` (ex, ey, ez), copied on the
+        device in stream order; RT_STAMP_SKIP_AIR leaves the unoccupied voxels out of it.  Returns its id."""
+        out = C.c_uint32(0)
+        self._check(self._lib.rt_stamp_capture(self._h, (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in extent]),
+                                               int(flags), C.byref(out)))
+        return out.value
+
+    def stamp_info(self, stamp):
+        """rt_stamp_info: the stamp's extent (ex, ey, ez)."""
+        ext = (C.c_int32 * 3)()
+        self._check(self._lib.rt_stamp_info(self._h, int(stamp), ext))
+        return tuple(ext)
+
+    def stamp_read(self, stamp):
+        """rt_stamp_read: (materials u32[ez, ey, ex], state u8[ez, ey, ex]) of the stamp.  Synchronises."""
+        ex, ey, ez = self.stamp_info(stamp)
+        mats = np.empty((ez, ey, ex), dtype=np.uint32)
+        state = np.empty((ez, ey, ex), dtype=np.uint8)
+        self._check(self._lib.rt_stamp_read(self._h, int(stamp), _p(mats), _p(state)))
+        return mats, state
+
+    def stamp_destroy(self, stamp):
+        """rt_stamp_destroy: the id is invalid afterwards; placements already enqueued still read the stamp."""
+        self._check(self._lib.rt_stamp_destroy(self._h, int(stamp)))
+
+    def edit_stamps(self, places):
+        """rt_edit_stamps: a sequence of stamp_place rows, or a ready STAMP_PLACE_DTYPE array (32-byte RtStampPlace rows), pasted in
+        order on the device; every 64^3 chunk that meets a placement's bounding box is rebuilt (see include/rt_abi.h)."""
+        if not (isinstance(places, np.ndarray) and places.dtype == STAMP_PLACE_DTYPE):
+            places = np.array([np.asarray(s, dtype=STAMP_PLACE_DTYPE) for s in places], dtype=STAMP_PLACE_DTYPE).reshape(-1)
+        places = np.ascontiguousarray(places).reshape(-1)
+        self._check(self._lib.rt_edit_stamps(self._h, places.ctypes.data_as(C.POINTER(RtStampPlace)), int(places.size)))
 
     def read_box(self, origin, extent):
         """rt_read_box: (materials u32[ez, ey, ex], minefield u8[ez, ey, ex]) of the resident region's box at texel `origin` (x, y, z)
