@@ -700,6 +700,68 @@ int rt_draw_boxes(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes, c
  * host: an invalid box is skipped on the device. */
 int rt_draw_boxes_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes_dev, const RtProbeLight* face_lights_dev, uint32_t count);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Voxel-model entities: a stamp (rt_stamp_create, rt_stamp_capture)
+ * drawn as an entity — a mob, a dropped block, a held tool, a door, a moving platform — at any float position, at any scale (voxels
+ * smaller than the world's, 1/16 say) and in any of the 48 orientations, composited by depth into the G-buffer of the frame drawn
+ * last exactly as the entity boxes are.  Each pixel walks the model's voxels and takes the albedo of the voxel it hits.  No world
+ * byte, accumulation sum or history is touched: the model is not part of the world it collides with.  Entities cast no shadow into
+ * the world and do not appear in bounce light; the light is one value per bounding-box face, as for boxes.  One model, 32 bytes: */
+typedef struct RtDrawStamp {      /* 32 bytes */
+    float    origin[3];           /*  0  world coordinates of the low corner of the placed (oriented) model            */
+    float    scale;               /* 12  edge of one model voxel in world units                                         */
+    uint32_t stamp;               /* 16  id of a live stamp of this context                                             */
+    uint8_t  orient, reserved0[3];/* 20  orient 0..47, RtStampPlace's; reserved bytes must be 0                         */
+    uint32_t emission;            /* 24  RGBA8 word written as is to RT_BUF_EMISSION_RGBA8 (a voxel's is 0xFF000000)    */
+    uint32_t reserved;            /* 28  must be 0                                                                      */
+} RtDrawStamp;
+/* The rules.  All arithmetic is fp32 with one rounding per operation; fused operations appear only where rtm_fma is written; any
+ * comparison with a NaN is false.  Results are reproduced bit for bit by tests/draw_stamps_ref.py, which walks every model for every
+ * pixel (DESIGN.md "Voxel-model entities").
+ *   Inputs: `u` and `face_lights` as for rt_draw_boxes: record 6 i + n is the light of the face with normal code n of model i's
+ *     bounding box; only .light is read.
+ *   Placed model: orient is RtStampPlace's.  The placed extent is E'_k = E[perm[k]], and placed-local cell c (0 <= c_k < E'_k) shows
+ *     the stamp voxel that rt_edit_stamps' placed-local cell d = c shows.  Cell c occupies [origin_k + c_k scale, origin_k + (c_k + 1) scale]
+ *     on axis k, up to the rounding of the planes below.
+ *   Valid record: a live id; orient < 48; reserved0 and reserved zero; every float finite; 2^-8 <= scale <= 64; |origin_k| <= 2^22
+ *     and |hi_k| <= 2^22 on every axis, hi_k = rtm_fma(float(E'_k), scale, origin_k).
+ *   Ray: rt_draw_boxes' — the same sx, sy and rtm_normalize3, o = u.origin, no slide.
+ *   Bounding box: lo = origin, hi as above; rt_draw_boxes' slab test unchanged gives t_in, t_out and the entry axis a.  The model is
+ *     entered iff that test says hit; so a camera inside the bounding box does not see the model (a limit kept from boxes), and a
+ *     grazing ray misses.
+ *   Planes of axis k: plane i (0..E'_k) lies at w = rtm_fma(float(i), scale, origin_k), and the ray reaches it at
+ *     t_k(i) = (w - o_k) * inv_k with the slab test's inv_k = 1.0f / d_k; planes 0 and E'_k are the bounding box's own.
+ *   First cell: c_a = d_a > 0 ? 0 : E'_a - 1.  On each other axis c_k = clamp(int(rtm_floor((p - origin_k) / scale)), 0, E'_k - 1)
+ *     with p = rtm_fma(d_k, t_in, o_k), or p = o_k when d_k == 0; the division is IEEE.  t = t_in, axis = a.
+ *   Walk: repeat — (1) if the stamp voxel shown by cell c has state RT_STAMP_SOLID, stop: a hit at t through `axis`; RT_STAMP_AIR and
+ *     RT_STAMP_ABSENT are both see-through.  (2) Otherwise, over the axes with d_k != 0 in the order x, y, z, tk = t_k(d_k > 0 ?
+ *     c_k + 1 : c_k); the first such axis starts the minimum, a later one replaces it iff its tk < the minimum, so the lowest axis
+ *     wins ties.  (3) c_k moves by +1 (d_k > 0) or -1 on that axis; if it leaves [0, E'_k), stop: a miss.  (4) Otherwise
+ *     t = t < tk ? tk : t and axis = k.  Every step moves one coordinate the ray's way, so the walk ends within E'_x + E'_y + E'_z
+ *     steps (at most 768).
+ *   Winner: among the models hit the one with the smallest t, on equal t the lowest index.
+ *   Depth test and writes: rt_draw_boxes' with t in place of t_in — P_k = rtm_fma(d_k, t, o_k), depth_f = rtm_length3(o - P) * 32.0f,
+ *     drawn iff depth_f < RT_BUF_DEPTH_F32[pixel]; RT_BUF_NORMAL_R8UI = 2 axis + 1 if d_axis > 0, else 2 axis; RT_BUF_ALBEDO_RGBA8 = the
+ *     UNORM8 pack of (albedo of the hit voxel's material word, 1); RT_BUF_EMISSION_RGBA8 = the record's `emission`; the two depth
+ *     planes and the two lighting planes as for a box, with light = face_lights[6 i + normal].light.  The fog planes are not touched;
+ *     every other pixel and plane keeps its bits.
+ *   Which frame, ordering, side effects: rt_draw_boxes' — the planes of the frame drawn last, on the stream rt_denoise uses, behind
+ *     the queries already enqueued; the frame slot's cached prepass is dropped; no accumulation sum, RT_FLAG_REPROJECT history set or
+ *     count, RtCounters, pending edit box or slab changes.  Boxes and models drawn one after the other composite by the depth test,
+ *     in either order.  A draw names its stamps as a placement does: rt_stamp_destroy after an enqueued draw waits for it.
+ *   Errors: NULL ctx, NULL u, a NULL array with count > 0, count > 4096, a record that is not valid: RT_ERR_INVALID_ARG.
+ *     tile_world != 1: RT_ERR_UNIMPLEMENTED.  No frame drawn yet: RT_ERR_NOT_READY.  count == 0: RT_OK, nothing enqueued, no prepass
+ *     dropped.  All of it is checked on the host before anything is enqueued; a rejected call changes nothing.  No world need be
+ *     resident beyond what a drawn frame implies.
+ *   Device work per call: one transfer of a 64-byte record per model and one launch, a wave per 8x8 pixel tile; per tile the
+ *     bounding boxes pass rt_draw_boxes' cull 64 at a time and only the survivors are walked per pixel.
+ * `models` and `face_lights` are host pointers; returns when the planes are written. */
+int rt_draw_stamps(RtContext* ctx, const RtUniforms* u, const RtDrawStamp* models, const RtProbeLight* face_lights, uint32_t count);
+/* Same, enqueued.  `models` is a host pointer here too (ids, extents and orientations are resolved on the host, where entity
+ * positions live) and is free again when the call returns; only `face_lights_dev` is device memory — what rt_probe_light_async
+ * wrote, so probes feed models without a host sync.  It must pass rt_trace_rays_async's test (16-byte aligned memory of the context's
+ * device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued. */
+int rt_draw_stamps_async(RtContext* ctx, const RtUniforms* u, const RtDrawStamp* models, const RtProbeLight* face_lights_dev, uint32_t count);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
  * after rt_draw_frame (and rt_draw_boxes) and before or after rt_denoise.  Each light reaches a pixel through one hard shadow ray
@@ -994,7 +1056,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtPointLight, rt_add_lights, rt_add_lights_async (point lights added to the lighting planes
  *        through one shadow ray per pixel and light).
  *        Additive, same minor version: RtStampPlace, RT_STAMP_*, rt_stamp_create, rt_stamp_capture, rt_stamp_info, rt_stamp_read,
- *        rt_stamp_destroy, rt_edit_stamps (voxel stamps: prefabs captured and pasted with rotation on the device). */
+ *        rt_stamp_destroy, rt_edit_stamps (voxel stamps: prefabs captured and pasted with rotation on the device).
+ *        Additive, same minor version: RtDrawStamp, rt_draw_stamps, rt_draw_stamps_async (voxel-model entities: stamps drawn at
+ *        float positions and scales, composited into the G-buffer by depth). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -25,6 +25,7 @@ ABI_SYMBOLS = (
     "rt_denoise_history", "rt_denoise_planes_counted", "rt_sweep_boxes", "rt_sweep_boxes_async",
     "rt_edit_shapes", "rt_draw_boxes", "rt_draw_boxes_async", "rt_add_lights", "rt_add_lights_async",
     "rt_stamp_create", "rt_stamp_capture", "rt_stamp_info", "rt_stamp_read", "rt_stamp_destroy", "rt_edit_stamps",
+    "rt_draw_stamps", "rt_draw_stamps_async",
 )
 
 _amd = None
@@ -149,6 +150,10 @@ def amd():
         lib.rt_draw_boxes.restype = C.c_int
         lib.rt_draw_boxes_async.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
         lib.rt_draw_boxes_async.restype = C.c_int
+        lib.rt_draw_stamps.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
+        lib.rt_draw_stamps.restype = C.c_int
+        lib.rt_draw_stamps_async.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
+        lib.rt_draw_stamps_async.restype = C.c_int
         lib.rt_add_lights.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
         lib.rt_add_lights.restype = C.c_int
         lib.rt_add_lights_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
@@ -254,6 +259,8 @@ def host():
         lib.rth_pipeline_pick.restype = C.c_int
         lib.rth_pipeline_set_boxes.argtypes = [P, P, P, C.c_uint32]
         lib.rth_pipeline_set_boxes.restype = C.c_int
+        lib.rth_pipeline_set_models.argtypes = [P, P, P, C.c_uint32]
+        lib.rth_pipeline_set_models.restype = C.c_int
         lib.rth_pipeline_set_lights.argtypes = [P, P, C.c_uint32]
         lib.rth_pipeline_set_lights.restype = C.c_int
         _host = lib

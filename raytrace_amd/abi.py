@@ -219,6 +219,18 @@ assert (RtDrawBox.lo.offset, RtDrawBox.material.offset, RtDrawBox.hi.offset, RtD
 MAX_DRAW_BOXES = 4096   # rt_draw_boxes: boxes per call
 
 
+class RtDrawStamp(C.Structure):
+    """rt_draw_stamps input (ABI 1.3, additive: voxel-model entities): 32 bytes; the reserved fields must be 0."""
+    _fields_ = [("origin", C.c_float * 3), ("scale", C.c_float), ("stamp", C.c_uint32), ("orient", C.c_uint8), ("reserved0", C.c_uint8 * 3),
+                ("emission", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RtDrawStamp) == 32
+assert (RtDrawStamp.origin.offset, RtDrawStamp.scale.offset, RtDrawStamp.stamp.offset, RtDrawStamp.orient.offset,
+        RtDrawStamp.emission.offset, RtDrawStamp.reserved.offset) == (0, 12, 16, 20, 24, 28)
+MAX_DRAW_STAMPS = 4096   # rt_draw_stamps: models per call
+
+
 class RtPointLight(C.Structure):
     """rt_add_lights input (ABI 1.3, additive: point lights): 32 bytes; `reserved` must be 0."""
     _fields_ = [("position", C.c_float * 3), ("radius", C.c_float), ("color", C.c_float * 3), ("reserved", C.c_uint32)]

@@ -381,7 +381,7 @@ void rt_destroy(RtContext* ctx) {
     if (ctx->user_stream && ctx->stream) (void)hipStreamSynchronize(ctx->stream);   // (the caller's: not ours to destroy)
     for (hipEvent_t e : ctx->events) (void)hipEventDestroy(e);
     for (TimingPool* t : {&ctx->launch_times, &ctx->gather_times}) for (hipEvent_t e : t->ev) (void)hipEventDestroy(e);
-    for (StagingSet* s : {&ctx->slab_sets[0], &ctx->slab_sets[1], &ctx->edit_sets[0], &ctx->edit_sets[1]}) s->release();
+    for (StagingSet* s : {&ctx->slab_sets[0], &ctx->slab_sets[1], &ctx->edit_sets[0], &ctx->edit_sets[1], &ctx->draw_sets[0], &ctx->draw_sets[1]}) s->release();
     ctx->query_block.release();
     for (StampEntry& e : ctx->stamps.slots) {   // the stamps nobody destroyed
         if (e.mats) (void)hipFree(reinterpret_cast<void*>(e.mats));

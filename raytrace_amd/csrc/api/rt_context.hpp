@@ -21,6 +21,7 @@
 #include "edit_binning.hpp"
 #include "edit_shapes.hpp"
 #include "edit_stamps.hpp"
+#include "draw_stamps.hpp"
 
 namespace rta __attribute__((visibility("hidden"))) {
 
@@ -313,6 +314,11 @@ struct __attribute__((visibility("hidden"))) RtContext {
     hipStream_t query_stream = nullptr;
     rta::LatchEvent ev_world, ev_query;
     rta::StagingBlock query_block;   // the synchronous calls' pinned and device staging (inputs, then hits), grown on demand
+    // rt_draw_stamps[_async]: the models' device records (and the synchronous call's face lights).  The asynchronous call returns
+    // before its transfer has run, so the records cannot share query_block with the synchronous queries: two sets used in turn, as
+    // for the edits (call n waits for the transfer of call n - 2 to leave the host block and for its launch to leave the device block)
+    rta::StagingSet draw_sets[2];
+    uint64_t draw_batches = 0;
     // light probes (rt_probe_light): the path records of a launch whose samples one workgroup cannot add itself (16 bytes per path),
     // grown on demand up to kProbeScratchBytes, in c->allocs (device_bytes; freed by rt_destroy)
     float4* probe_scratch = nullptr;

@@ -212,6 +212,17 @@ struct DrawBoxesArgs {
 };
 hipError_t launch_draw_boxes(const Planes& pl, const DrawBoxesArgs& a, hipStream_t st);
 
+// rt_draw_stamps.hip: voxel-model entities (stamps placed at float positions) composited likewise (rt_draw_stamps).  One launch for
+// the batch; a wave owns an 8x8 pixel tile.
+struct DrawStampsArgs {
+    const uint4* recs;    // DrawStampRecord[count] (api/draw_stamps.hpp; four uint4 each), resolved and validated on the host
+    const float4* lights; // RtProbeLight[6 * count]: record 6 i + n lights bounding-box face n of model i (.xyz read)
+    uint32_t count;
+    int width, height;
+    float origin[3], forward[3], up[3], right[3];   // as DrawBoxesArgs
+};
+hipError_t launch_draw_stamps(const Planes& pl, const DrawStampsArgs& a, hipStream_t st);
+
 // rt_lights.hip: point lights added to the lighting planes of a whole frame's row-major planes (rt_add_lights).  One launch for the
 // batch; a wave owns an 8x8 pixel tile.  Frame supplies the camera of the frame the planes hold (origin, forward, up, right: the ray
 // of rt_draw_boxes), lr and the region.

@@ -233,6 +233,9 @@ int rth_pipeline_enable_history_denoise(void* p, const RtDenoiseParams* params) 
 int rth_pipeline_set_boxes(void* p, const RtDrawBox* boxes, const RtProbeLight* face_lights, uint32_t count) {
     return static_cast<render::Pipeline*>(p)->set_boxes(boxes, face_lights, count);
 }
+int rth_pipeline_set_models(void* p, const RtDrawStamp* models, const RtProbeLight* face_lights, uint32_t count) {
+    return static_cast<render::Pipeline*>(p)->set_models(models, face_lights, count);
+}
 int rth_pipeline_set_lights(void* p, const RtPointLight* lights, uint32_t count) {
     return static_cast<render::Pipeline*>(p)->set_lights(lights, count);
 }

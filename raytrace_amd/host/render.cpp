@@ -89,6 +89,13 @@ int Pipeline::set_boxes(const RtDrawBox* boxes, const RtProbeLight* face_lights,
     return RT_OK;
 }
 
+int Pipeline::set_models(const RtDrawStamp* models, const RtProbeLight* face_lights, uint32_t count) {
+    if (count > 4096u || (count > 0u && (!models || !face_lights))) return RT_ERR_INVALID_ARG;
+    models_.assign(models, models + count);
+    model_lights_.assign(face_lights, face_lights + 6u * (size_t)count);
+    return RT_OK;
+}
+
 int Pipeline::set_lights(const RtPointLight* lights, uint32_t count) {
     if (count > 1024u || (count > 0u && !lights)) return RT_ERR_INVALID_ARG;
     lights_.assign(lights, lights + count);
@@ -199,6 +206,8 @@ int Pipeline::draw_frame(game::Game& game) {
     rc = rt_draw_frame(ctx_, &u);                                    // :209-211; the dispatch recorded at :86-90
     if (rc == RT_OK && !boxes_.empty())                              // entities go into the G-buffer before the post passes see it
         rc = rt_draw_boxes(ctx_, &u, boxes_.data(), box_lights_.data(), (uint32_t)boxes_.size());
+    if (rc == RT_OK && !models_.empty())                             // voxel-model entities likewise, after the boxes
+        rc = rt_draw_stamps(ctx_, &u, models_.data(), model_lights_.data(), (uint32_t)models_.size());
     if (rc == RT_OK && !lights_.empty())                             // moving lights shade the frame and its entities; the denoise filters them
         rc = rt_add_lights(ctx_, &u, lights_.data(), (uint32_t)lights_.size());
     if (rc == RT_OK && post_) {                                      // the same command buffer goes on (:98-123), one submit (:229-235)

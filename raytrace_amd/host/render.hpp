@@ -127,6 +127,11 @@ class Pipeline {
     // denoise (both arrays are copied; face_lights holds 6 * count records, e.g. probe_light's for the boxes' face probes).
     // count == 0 draws none.  RT_ERR_INVALID_ARG for more than 4096 boxes or a NULL array with count > 0.
     int set_boxes(const RtDrawBox* boxes, const RtProbeLight* face_lights, uint32_t count);
+    // Voxel-model entities: every draw_frame from now on enqueues rt_draw_stamps(models, face_lights, count) between the ray trace and
+    // the denoise, after the boxes (both arrays are copied; the stamps are this pipeline's and must be live at every draw).
+    // count == 0 draws none.  RT_ERR_INVALID_ARG for more than 4096 models or a NULL array with count > 0; an invalid record fails
+    // the draw_frame that draws it.
+    int set_models(const RtDrawStamp* models, const RtProbeLight* face_lights, uint32_t count);
     // Point lights: every draw_frame from now on enqueues rt_add_lights(lights, count) behind the ray trace and the entity boxes and
     // in front of the denoise (the array is copied).  count == 0 adds none.  RT_ERR_INVALID_ARG for more than 1024 lights or a NULL
     // array with count > 0.
@@ -150,6 +155,8 @@ class Pipeline {
     bool no_fence_ = false;            // set_frames_in_flight(2)
     std::vector<RtDrawBox> boxes_;     // set_boxes
     std::vector<RtProbeLight> box_lights_;
+    std::vector<RtDrawStamp> models_;  // set_models
+    std::vector<RtProbeLight> model_lights_;
     std::vector<RtPointLight> lights_; // set_lights
     std::unique_ptr<TerrainUploadManager> tum_;
     std::unique_ptr<world::ChunkStorage> chunks_;

@@ -70,6 +70,11 @@
 // (20 to 400 units away, over the whole view), their six face probes lit with rt_probe_light (4 samples, depth 2), and rt_draw_boxes
 // composites them into a freshly drawn --width x --height frame, 20 times.  One JSON line: the device time of the pass (the launch
 // bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time of rt_draw_boxes and of the probes, and the pixels drawn.
+// --models N [--model-scale S]: instead of the frame loop, voxel-model entities.  One built-in 9 x 9 x 12 sparse stamp (about a third of
+// its voxels solid) is drawn N times at scale S (default 1/8) — scattered like --boxes' boxes, in seeded orientations, lit by their
+// bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times; and, as a yardstick in the
+// same process, rt_draw_boxes draws the bounding boxes of the same records, 20 times.  One JSON line: the device time of both passes
+// (the launch bracketed by events, RT_FLAG_TIMING_ALL), their ratio, the call-to-return time of rt_draw_stamps and the pixels drawn.
 // --lights N: instead of the frame loop, point lights.  N lights of radius 8 are scattered deterministically just off visible
 // surfaces — rt_pick_pixels on N pixels spread over the view, each light 1 to 4 units off its hit point along the face's normal (30
 // units along the ray where the pixel shows sky) — and rt_add_lights adds them to a freshly drawn --width x --height frame, 20 times.
@@ -357,6 +362,93 @@ int run_boxes(rt::game::Game& game, const std::vector<uint8_t>& noise, int width
     return 0;
 }
 
+// --models: see the head of the file
+int run_models(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n, float scale) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    // the stamp: a third solid, the rest air and absent in turn, a material per voxel
+    const int32_t E[3] = {9, 9, 12};
+    std::vector<uint32_t> mats((size_t)E[0] * E[1] * E[2]);
+    std::vector<uint8_t> state(mats.size());
+    for (size_t i = 0; i < mats.size(); i++) {
+        const float r = rnd();
+        state[i] = r < 0.3333f ? RT_STAMP_SOLID : (i & 1u ? RT_STAMP_AIR : RT_STAMP_ABSENT);
+        mats[i] = (1u << 15) | ((40u + (uint32_t)i % 80u) << 14) | ((30u + (uint32_t)i % 90u) << 7) | (20u + (uint32_t)i % 100u);
+    }
+    uint32_t id = 0;
+    if (p->stamp_create(E, mats.data(), state.data(), &id) != RT_OK) { std::fprintf(stderr, "stamp_create failed: %s\n", p->last_error()); delete p; return 1; }
+    static const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    std::vector<RtDrawStamp> models(n);
+    std::vector<RtDrawBox> boxes(n);
+    std::vector<RtLightProbe> probes(6u * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        const float sx = rnd() * 2.0f - 1.0f, sy = rnd() * 2.0f - 1.0f, dist = 20.0f * std::pow(20.0f, rnd());   // 20 .. 400, log-uniform
+        float v[3], len = 0.0f;
+        for (int a = 0; a < 3; a++) { v[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; len += v[a] * v[a]; }
+        len = std::sqrt(len);
+        RtDrawStamp& m = models[i];
+        m = RtDrawStamp{};
+        m.stamp = id; m.scale = scale; m.orient = (uint8_t)(i % 48u); m.emission = 0xFF000000u;
+        RtDrawBox& b = boxes[i];
+        for (int a = 0; a < 3; a++) {
+            const float ext = (float)E[perms[m.orient >> 3][a]];
+            m.origin[a] = u.origin[a] + v[a] / len * dist - 0.5f * ext * scale;
+            b.lo[a] = m.origin[a]; b.hi[a] = std::fma(ext, scale, m.origin[a]);
+        }
+        b.material = mats[0]; b.emission = m.emission;
+        for (uint32_t code = 0; code < 6u; code++) {   // the bounding box's face centre, 0.001 off the face along its normal
+            RtLightProbe& q = probes[6u * (size_t)i + code];
+            q = RtLightProbe{};
+            for (int a = 0; a < 3; a++) q.position[a] = (b.lo[a] + b.hi[a]) * 0.5f;
+            const int a = (int)(code / 2u);
+            q.position[a] = code % 2u == 0u ? b.hi[a] + 0.001f : b.lo[a] - 0.001f;
+            q.normal = code;
+            q.cell[0] = (uint16_t)(i % 16u); q.cell[1] = (uint16_t)((i / 16u) % 16u);
+        }
+    }
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    std::vector<RtProbeLight> lights(probes.size());
+    int rc = n ? rt_probe_light(ctx, &u, probes.data(), (uint32_t)probes.size(), 4, 2, lights.data()) : RT_OK;
+    const size_t npix = (size_t)width * (size_t)height;
+    std::vector<float> before(npix), after(npix);
+    if (rc == RT_OK) rc = rt_readback(ctx, RT_BUF_DEPTH_F32, before.data(), npix * sizeof(float));
+    const int reps = 20;
+    double device_ms[2] = {0.0, 0.0}, call_ms[2] = {0.0, 0.0};
+    uint64_t drawn[2] = {0, 0};
+    for (int pass = 0; pass < 2 && rc == RT_OK; pass++) {       // 0: the models, 1: their bounding boxes
+        for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {      // (the first repetition warms the staging up)
+            RtTiming tm{};
+            rc = rt_draw_frame(ctx, &u);
+            if (rc == RT_OK) rc = rt_sync(ctx);
+            if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);       // (drains the frame's own launches)
+            auto t = std::chrono::steady_clock::now();
+            if (rc == RT_OK) rc = pass == 0 ? rt_draw_stamps(ctx, &u, models.data(), lights.data(), n) : rt_draw_boxes(ctx, &u, boxes.data(), lights.data(), n);
+            const double call = ms_since(t);
+            if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);
+            if (i > 0) { device_ms[pass] += tm.shade_ms / reps; call_ms[pass] += call / reps; }
+        }
+        if (rc == RT_OK) rc = rt_readback(ctx, RT_BUF_DEPTH_F32, after.data(), npix * sizeof(float));
+        for (size_t i = 0; i < npix; i++) drawn[pass] += std::memcmp(&before[i], &after[i], 4) != 0;
+    }
+    if (rc != RT_OK) { std::fprintf(stderr, "voxel-model entities failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    std::printf("{\"models\": %u, \"model_scale\": %g, \"frame\": \"%dx%d spp %d depth %d\", \"draw_stamps_device_ms\": %.4f, "
+                "\"bounding_boxes_device_ms\": %.4f, \"ratio\": %.2f, \"draw_stamps_call_ms\": %.4f, \"draw_boxes_call_ms\": %.4f, "
+                "\"pixels_drawn\": %llu, \"bounding_box_pixels\": %llu}\n",
+                n, (double)scale, width, height, spp, depth, device_ms[0], device_ms[1], device_ms[1] > 0.0 ? device_ms[0] / device_ms[1] : 0.0,
+                call_ms[0], call_ms[1], (unsigned long long)drawn[0], (unsigned long long)drawn[1]);
+    delete p;
+    return 0;
+}
+
 // --lights: see the head of the file
 int run_lights(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n) {
     std::string err;
@@ -433,7 +525,8 @@ int main(int argc, char** argv) {
     int edits = 0, edit_radius = 0;
     const char* edit_shape = nullptr;
     int edit_stamp = -1;
-    long long rays = 0, boxes = -1, lights = -1;
+    long long rays = 0, boxes = -1, lights = -1, models = -1;
+    float model_scale = 0.125f;
     bool rays_coherent = false;
     bool reproject = false, stream = false, stream_history = false, history_denoise = false;
     float camera_step = 0.0f;
@@ -469,6 +562,8 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
         else if (want("--boxes")) boxes = std::atoll(argv[++i]);
         else if (want("--lights")) lights = std::atoll(argv[++i]);
+        else if (want("--models")) models = std::atoll(argv[++i]);
+        else if (want("--model-scale")) model_scale = std::strtof(argv[++i], nullptr);
         else positional.push_back(argv[i]);
     }
     if (gpus < 1 || frames < 1) { std::fprintf(stderr, "--gpus and --frames must be >= 1\n"); return 2; }
@@ -478,6 +573,10 @@ int main(int argc, char** argv) {
     if (stream_history && (!stream || !reproject || edit_radius == 0)) { std::fprintf(stderr, "--stream-history goes with --stream --reproject --edit-radius N\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
     if (boxes < -1 || boxes > 4096) { std::fprintf(stderr, "--boxes must be in 0..4096\n"); return 2; }
+    if (models < -1 || models > 4096 || !(model_scale >= 1.0f / 256.0f && model_scale <= 64.0f)) {
+        std::fprintf(stderr, "--models must be in 0..4096, --model-scale in 2^-8..64\n");
+        return 2;
+    }
     if (lights < -1 || lights > 1024) { std::fprintf(stderr, "--lights must be in 0..1024\n"); return 2; }
     if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
@@ -509,6 +608,7 @@ int main(int argc, char** argv) {
     game.generate_world(0x5EED);
     if (rays > 0) return run_rays(game, noise, width, height, spp, depth, device, (uint32_t)rays, rays_coherent);
     if (boxes >= 0) return run_boxes(game, noise, width, height, spp, depth, device, (uint32_t)boxes);
+    if (models >= 0) return run_models(game, noise, width, height, spp, depth, device, (uint32_t)models, model_scale);
     if (lights >= 0) return run_lights(game, noise, width, height, spp, depth, device, (uint32_t)lights);
     std::string err;
 

@@ -13,8 +13,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
-                  RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtInfo, RtLightProbe,
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_DRAW_STAMPS, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
+                  RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtDrawStamp, RtInfo, RtLightProbe,
                   RtPointLight, RtProbeLight, RtRayHit, RtShapeEdit, RtStampPlace, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
@@ -80,6 +80,10 @@ assert SWEEP_DTYPE.itemsize == C.sizeof(RtBoxSweep) and SWEEP_HIT_DTYPE.itemsize
 # numpy view of RtDrawBox (include/rt_abi.h)
 DRAW_BOX_DTYPE = np.dtype([("lo", "<f4", 3), ("material", "<u4"), ("hi", "<f4", 3), ("emission", "<u4")])
 assert DRAW_BOX_DTYPE.itemsize == C.sizeof(RtDrawBox)
+# numpy view of RtDrawStamp (include/rt_abi.h)
+DRAW_STAMP_DTYPE = np.dtype([("origin", "<f4", 3), ("scale", "<f4"), ("stamp", "<u4"), ("orient", "u1"), ("reserved0", "u1", 3),
+                             ("emission", "<u4"), ("reserved", "<u4")])
+assert DRAW_STAMP_DTYPE.itemsize == C.sizeof(RtDrawStamp)
 # numpy view of RtPointLight (include/rt_abi.h)
 POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("reserved", "<u4")])
 assert POINT_LIGHT_DTYPE.itemsize == C.sizeof(RtPointLight)
@@ -448,6 +452,27 @@ class Context:
         enqueued so far; an invalid box is skipped on the device."""
         n = check_draw_box_tensors(boxes, face_lights, self.cfg.device if self.cfg is not None else 0)
         self._check(self._lib.rt_draw_boxes_async(self._h, C.byref(uniforms), C.c_void_p(boxes.data_ptr()), C.c_void_p(face_lights.data_ptr()), n))
+
+    # -- voxel-model entities ----------------------------------------------------------------------------
+    def draw_stamps(self, uniforms, models, face_lights):
+        """rt_draw_stamps: `models` DRAW_STAMP_DTYPE[N] records (make_draw_stamps) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
+        probe_records returns for stamp_face_probes(models, extents)), composited by depth into the planes of the frame drawn last under
+        the camera of `uniforms`.  Synchronous; an invalid record fails the whole call (RtError, INVALID_ARG)."""
+        models = np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
+        lights = np.ascontiguousarray(face_lights, dtype=PROBE_LIGHT_DTYPE).reshape(-1)
+        if lights.size != 6 * models.size:
+            raise ValueError("face_lights must hold six records per model")
+        self._check(self._lib.rt_draw_stamps(self._h, C.byref(uniforms), _p(models) if models.size else None,
+                                             _p(lights) if models.size else None, int(models.size)))
+
+    def draw_stamps_async(self, uniforms, models, face_lights):
+        """rt_draw_stamps_async: `models` host records as for draw_stamps (free again on return), `face_lights` a torch device tensor:
+        any contiguous tensor of 6 N * 16 bytes (e.g. the `out` of probe_light_async).  Enqueued behind the frame drawn last and the
+        queries enqueued so far; an invalid record fails the whole call before anything is enqueued."""
+        models = np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
+        check_draw_stamp_lights(models.size, face_lights, self.cfg.device if self.cfg is not None else 0)
+        self._check(self._lib.rt_draw_stamps_async(self._h, C.byref(uniforms), _p(models) if models.size else None,
+                                                   C.c_void_p(face_lights.data_ptr()), int(models.size)))
 
     # -- point lights ------------------------------------------------------------------------------------
     def add_lights(self, uniforms, lights):
@@ -830,6 +855,18 @@ class Pipeline:
         if rc != 0:
             raise RtError(rc, "set_boxes: at most %d boxes" % MAX_DRAW_BOXES)
 
+    def set_models(self, models=None, face_lights=None):
+        """Pipeline::set_models: every draw_frame from now on enqueues rt_draw_stamps for this set between the ray trace and the denoise,
+        after the entity boxes (DRAW_STAMP_DTYPE[N] and PROBE_LIGHT_DTYPE[6 N], copied); None or an empty set draws none.  The stamps
+        are the pipeline's (stamp_create / stamp_capture) and must be live at every draw."""
+        models = np.zeros(0, dtype=DRAW_STAMP_DTYPE) if models is None else np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
+        lights = np.zeros(0, dtype=PROBE_LIGHT_DTYPE) if face_lights is None else np.ascontiguousarray(face_lights, dtype=PROBE_LIGHT_DTYPE).reshape(-1)
+        if lights.size != 6 * models.size:
+            raise ValueError("face_lights must hold six records per model")
+        rc = _lib.host().rth_pipeline_set_models(self._h, _p(models) if models.size else None, _p(lights) if models.size else None, int(models.size))
+        if rc != 0:
+            raise RtError(rc, "set_models: at most %d models" % MAX_DRAW_STAMPS)
+
     def set_lights(self, lights=None):
         """Pipeline::set_lights: every draw_frame from now on enqueues rt_add_lights for this set behind the ray trace and the entity
         boxes and in front of the denoise (POINT_LIGHT_DTYPE[N], copied); None or an empty set adds none."""
@@ -1001,6 +1038,76 @@ def check_draw_box_tensors(boxes, face_lights, device):
     if face_lights.numel() * face_lights.element_size() != 6 * n * PROBE_LIGHT_DTYPE.itemsize:
         raise ValueError("face_lights must be a contiguous tensor of 6 N * 16 bytes")
     return n
+
+
+# world axis k of a placed stamp is stamp axis STAMP_PERMS[orient >> 3][k] (include/rt_abi.h, rt_edit_stamps)
+STAMP_PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+
+
+def make_draw_stamps(stamps, origins, scales=1.0, orients=0, emissions=0xFF000000):
+    """RtDrawStamp records (DRAW_STAMP_DTYPE) from u32[N] stamp ids, float[N, 3] low corners, float[N] scales, int[N] orientations and
+    u32[N] RGBA8 emission words (one value serves every model).  Refuses what can be refused without the stamps' extents: a non-finite
+    float, an origin beyond 2^22, a scale outside [2^-8, 64], orient >= 48, more than 4096 models."""
+    origin = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    n = origin.shape[0]
+    if n > MAX_DRAW_STAMPS:
+        raise ValueError("at most %d models per call" % MAX_DRAW_STAMPS)
+    scale = np.broadcast_to(np.asarray(scales, dtype=np.float32), (n,))
+    orient = np.broadcast_to(np.asarray(orients, dtype=np.int64), (n,))
+    if not (np.isfinite(origin).all() and np.isfinite(scale).all()):
+        raise ValueError("origins and scales must be finite")
+    if n and np.abs(origin).max() > 2.0 ** 22:
+        raise ValueError("origins must lie within +-2^22")
+    if n and (scale.min() < 2.0 ** -8 or scale.max() > 64.0):
+        raise ValueError("scales must lie within [2^-8, 64]")
+    if n and (orient.min() < 0 or orient.max() >= 48):
+        raise ValueError("orient is 0..47")
+    m = np.zeros(n, dtype=DRAW_STAMP_DTYPE)
+    m["origin"], m["scale"], m["orient"] = origin, scale, orient
+    m["stamp"] = np.broadcast_to(np.asarray(stamps, dtype=np.uint32), (n,))
+    m["emission"] = np.broadcast_to(np.asarray(emissions, dtype=np.uint32), (n,))
+    return m
+
+
+def stamp_bounding_boxes(models, extents):
+    """(lo, hi) float32[N, 3] of the models' bounding boxes: lo = origin, hi = origin + E' * scale with E'_k = E[perm[k]].  `extents`:
+    int[N, 3] stamp extents (ex, ey, ez) per model, or one triple for all."""
+    models = np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
+    n = models.size
+    ext = np.broadcast_to(np.asarray(extents, dtype=np.int64).reshape(-1, 3), (n, 3))
+    perm = np.array(STAMP_PERMS, dtype=np.int64)[models["orient"].astype(np.int64) >> 3] if n else np.zeros((0, 3), dtype=np.int64)
+    placed = np.take_along_axis(ext, perm, axis=1)
+    lo = models["origin"].astype(np.float32)
+    hi = (placed.astype(np.float64) * models["scale"].astype(np.float64)[:, None] + lo.astype(np.float64)).astype(np.float32)
+    return lo, hi
+
+
+def stamp_face_probes(models, extents, cells=(0, 0)):
+    """The six RtLightProbe records (PROBE_DTYPE) per model that light its bounding box's faces, as face_probes does for boxes: record
+    6 i + n sits at the centre of the face with normal code n, 0.001 off it.  probe_records(u, stamp_face_probes(models, extents),
+    samples, depth) is the face_lights of draw_stamps."""
+    lo, hi = stamp_bounding_boxes(models, extents)
+    boxes = np.zeros(lo.shape[0], dtype=DRAW_BOX_DTYPE)
+    boxes["lo"], boxes["hi"] = lo, hi
+    return face_probes(boxes, cells)
+
+
+def check_draw_stamp_lights(n, face_lights, device):
+    """Context.draw_stamps_async's device argument: a contiguous tensor of 6 n * 16 bytes on GPU `device`, 16-byte aligned, n at most
+    4096.  Raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
+    import torch
+    if not isinstance(face_lights, torch.Tensor):
+        raise ValueError("face_lights must be a torch tensor")
+    if not face_lights.is_cuda or face_lights.device.index != int(device):
+        raise ValueError("face_lights must be a tensor on cuda:%d (the context's device), not %s" % (int(device), face_lights.device))
+    if face_lights.data_ptr() % 16:
+        raise ValueError("face_lights must be 16-byte aligned")
+    if not face_lights.is_contiguous():
+        raise ValueError("face_lights must be contiguous")
+    if n > MAX_DRAW_STAMPS:
+        raise ValueError("at most %d models per call" % MAX_DRAW_STAMPS)
+    if face_lights.numel() * face_lights.element_size() != 6 * n * PROBE_LIGHT_DTYPE.itemsize:
+        raise ValueError("face_lights must be a contiguous tensor of 6 N * 16 bytes")
 
 
 def make_point_lights(positions, radii, colors):
