@@ -651,7 +651,8 @@ int rt_sweep_boxes_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t 
  * dropped items, projectiles — composited by depth into the G-buffer of the frame drawn last, after rt_draw_frame and before the
  * post passes.  A box has RtBoxSweep's shape; a drawn pixel gets the box's depth, face code, albedo and emission and the light of that
  * face as rt_probe_light computed it, so rt_denoise, rt_denoise_history and rt_finalize treat it like any other pixel.  Entities cast
- * no shadow into the world and do not appear in bounce light; boxes are not rotated.  One box, 32 bytes: */
+ * no shadow into the world by themselves (rt_shadow_entities adds the sun's) and do not appear in bounce light; boxes are not
+ * rotated.  One box, 32 bytes: */
 typedef struct RtDrawBox {        /* 32 bytes */
     float    lo[3];  uint32_t material;   /* world coordinates of the low corner; packed material word: albedo decoded as a voxel's (raytrace.comp:156-158) */
     float    hi[3];  uint32_t emission;   /* high corner; RGBA8 word written as is to RT_BUF_EMISSION_RGBA8 (a voxel's is 0xFF000000) */
@@ -705,7 +706,8 @@ int rt_draw_boxes_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* bo
  * smaller than the world's, 1/16 say) and in any of the 48 orientations, composited by depth into the G-buffer of the frame drawn
  * last exactly as the entity boxes are.  Each pixel walks the model's voxels and takes the albedo of the voxel it hits.  No world
  * byte, accumulation sum or history is touched: the model is not part of the world it collides with.  Entities cast no shadow into
- * the world and do not appear in bounce light; the light is one value per bounding-box face, as for boxes.  One model, 32 bytes: */
+ * the world by themselves (rt_shadow_entities adds the sun's) and do not appear in bounce light; the light is one value per
+ * bounding-box face, as for boxes.  One model, 32 bytes: */
 typedef struct RtDrawStamp {      /* 32 bytes */
     float    origin[3];           /*  0  world coordinates of the low corner of the placed (oriented) model            */
     float    scale;               /* 12  edge of one model voxel in world units                                         */
@@ -766,7 +768,7 @@ int rt_draw_stamps_async(RtContext* ctx, const RtUniforms* u, const RtDrawStamp*
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
  * after rt_draw_frame (and rt_draw_boxes) and before or after rt_denoise.  Each light reaches a pixel through one hard shadow ray
  * against the resident region; rt_finalize multiplies lighting by albedo, so the added light is diffuse shading.  Entities cast no
- * shadow, the source gives no bounce light, and the light belongs to one frame: it enters no accumulation sum or history.  One light,
+ * shadow in a point light, the source gives no bounce light, and the light belongs to one frame: it enters no accumulation sum or history.  One light,
  * 32 bytes: */
 typedef struct RtPointLight {     /* 32 bytes */
     float    position[3];  float    radius;     /* world coordinates; nothing is lit at or beyond `radius` */
@@ -815,6 +817,74 @@ int rt_add_lights(RtContext* ctx, const RtUniforms* u, const RtPointLight* light
  * device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued.  The library cannot read device records on the
  * host: an invalid light is skipped on the device. */
 int rt_add_lights_async(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights_dev, uint32_t count);
+
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Entity shadows: the entities the host drew — the very RtDrawBox and
+ * RtDrawStamp records of rt_draw_boxes and rt_draw_stamps — cast the sun's shadow into the frame drawn last: onto the world, onto
+ * each other and onto their own averted faces.  The shader's direct sun term of a lit surface is the per-frame constant `sunlight`,
+ * with no cosine and no albedo (raytrace.comp:325-328), so the call removes exactly that term, times `strength`, from the pixels an
+ * entity shades and the world does not; it holds for one-sample, multi-sample, accumulated and reprojected lighting alike, whose
+ * planes hold a mean of samples with a sun term of `sunlight` or 0.  `material`, `emission` and the face lights play no part.  The
+ * intended order is boxes, models, shadows, point lights, denoise.
+ * The rules.  All arithmetic is fp32 with one rounding per operation; fused operations appear only where rtm_fma or rtm_dot3 is
+ * written; any comparison with a NaN is false.  Results are reproduced bit for bit by tests/entity_shadow_ref.py, which tests every
+ * occluder against every pixel (DESIGN.md "Entity shadows").
+ *   Inputs: sun_angle, origin, forward, up, right and lr of `u` are read; the host passes the uniforms of the frame it drew.  s is the
+ *     sun's direction and sunlight its colour, exactly the values the frame uses (raytrace.comp:317-318, sun_color :259-269): s is
+ *     normalised once there, and it is NOT jittered as the frame's own shadow rays are.
+ *   Surface pixel and its point P': rt_add_lights' rules, word for word — a surface pixel has RT_BUF_NORMAL_R8UI < 6 and
+ *     RT_BUF_DEPTH_F32 < 65535.0f; P lies on the ray of rt_draw_boxes at t = depth_f / 32.0f; P' is P moved 0.03125f off its face along
+ *     the normal code.  The planes are read as they stand: entity pixels written by rt_draw_boxes / rt_draw_stamps take part with
+ *     their own depth and face.  Every other pixel keeps all its bits.
+ *   A box shades the pixel: rt_draw_boxes' slab test with o = P', d = s and inv_k = 1.0f / s_k gives t_in and t_out by the same
+ *     replacement rules; an axis with s_k == 0 passes iff lo_k < o_k && o_k < hi_k and gives no bound.  The box shades iff some axis
+ *     gave a bound, every zero axis passes, t_out > 0 and t_in < t_out.  The one change from the draw rule is t_out > 0 in place of
+ *     t_in > 0: a point inside a box is shaded by it (an entity sunk into the ground shades the ground inside it).  An entity's own
+ *     pixels have P' 1/32 outside their face: a face turned from the sun re-enters its own box and goes dark, a face turned to the sun
+ *     leaves it.  Valid box: rt_draw_boxes'.  The device skips an invalid box in both calls; rt_shadow_entities also rejects the whole
+ *     call (RT_ERR_INVALID_ARG) before anything is enqueued.
+ *   A model shades the pixel: the bounding box is lo = origin, hi_k = rtm_fma(float(E'_k), scale, origin_k), and the model is entered
+ *     iff the box rule above holds for it.  First cell if t_in > 0: rt_draw_stamps' rule — the entry axis a gets c_a = s_a > 0 ? 0 :
+ *     E'_a - 1, every other axis c_k = clamp(int(rtm_floor((p - origin_k) / scale)), 0, E'_k - 1) with p = rtm_fma(s_k, t_in, o_k), or
+ *     p = o_k when s_k == 0.  First cell if not (P' lies inside the bounding box, or on it): on EVERY axis p = o_k and c_k by the same
+ *     clamp.  Then rt_draw_stamps' walk steps (1) to (3) unchanged, with the same plane expression t_k(i) = (rtm_fma(float(i), scale,
+ *     origin_k) - o_k) * inv_k, the same tie rule and the same step bound; no t and no axis is tracked.  The model shades iff the walk
+ *     stops on an RT_STAMP_SOLID cell.  Valid record: rt_draw_stamps'; an invalid record rejects either call on the host.
+ *   Sunlit: a pixel shaded by at least one occluder is CHANGED iff trace_ray (raytrace.comp:82-183) from P' in direction s (trace_ray
+ *     normalises it again), with u.lr against the resident region, leaves the window (RT_HIT_AIR).  A hit, the border value, a start
+ *     inside an occupied texel and the loop limit all leave the pixel as it is: the world shades it already and there is no sun term
+ *     to remove.  (Entities first, the world's ray only for shaded pixels: that order is the cost model's, the result does not depend
+ *     on it.)
+ *   Writes, only for a changed pixel: sub_k = (sunlight_k * strength) / 16.0f; RT_BUF_LIGHTING_F32.rgb = rtm_max(L_k - sub_k, 0.0f);
+ *     independently RT_BUF_LIGHTING_RGBA16.rgb = rtm_unorm(rtm_max(float(q_k) / 65535.0f - sub_k, 0.0f), 65535.0f), q the texel as it
+ *     stands.  Both alphas, every other plane and every other pixel keep their bits.  The clamp serves the pixels at a world-shadow
+ *     edge, whose frame's jittered sun ray was blocked while the un-jittered one here is not.  As with point lights each plane gets
+ *     the change in its own representation: before rt_denoise the shadow's edge is filtered with the rest, after it the edge stays
+ *     crisp.
+ *   Which frame, ordering: rt_add_lights' — the planes of the frame drawn last, on the stream rt_denoise uses, also with
+ *     RT_FLAG_FRAMES_IN_FLIGHT_2 and after rt_set_stream, behind the queries already enqueued on the context.  The call sees the region
+ *     as every earlier upload, edit, shape, slab and generated region left it, and later world changes wait for it.
+ *   Side effects: the frame slot's cached prepass is dropped.  No accumulation sum, RT_FLAG_REPROJECT history set or count, RtCounters,
+ *     pending edit box or slab changes.  The call names its stamps as a draw does: rt_stamp_destroy after an enqueued call waits for it.
+ *   Errors: NULL ctx, NULL u, a NULL array with its count above 0, a count above 4096, strength not finite or outside (0, 1], a model
+ *     record that is not valid: RT_ERR_INVALID_ARG.  tile_world != 1: RT_ERR_UNIMPLEMENTED.  No frame drawn yet, or no world resident:
+ *     RT_ERR_NOT_READY.  nboxes + nmodels == 0, or sunlight == (0, 0, 0): RT_OK, nothing enqueued, no prepass dropped.  (sunlight is
+ *     (0, 0, 0) for no sun angle the tests know: below the horizon the shader's sun colour is negative, and the call then removes that
+ *     negative term, as the rule says.)  A rejected call changes nothing.
+ *   Limits, not bugs: hard shadows only.  The sun only: point lights still ignore entities.  No entity shadow in bounce light.  The
+ *     shadow belongs to one frame and enters no accumulation sum or history.  Crevices narrower than 1/32 of a model whose voxels are
+ *     smaller than 1/16 may shade themselves.
+ *   Device work per call: one transfer of a 64-byte record per model and one launch, a wave per 8x8 pixel tile; per tile the boxes and
+ *     the models' bounding boxes pass a conservative cull 64 at a time, only the survivors are tested (and walked) per pixel, and only
+ *     the shaded pixels trace the world's sun ray; the synchronous call adds one transfer of the boxes.
+ * Host pointers; returns when the planes are written. */
+int rt_shadow_entities(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes, uint32_t nboxes, const RtDrawStamp* models,
+                       uint32_t nmodels, float strength);
+/* Same, enqueued.  `boxes_dev` is device memory and must pass rt_trace_rays_async's test (16-byte aligned memory of the context's
+ * device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued; the library cannot read device records on the host:
+ * an invalid box is skipped on the device.  `models` is a host pointer here too, as for rt_draw_stamps_async and for the same reason,
+ * and is free again when the call returns. */
+int rt_shadow_entities_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes_dev, uint32_t nboxes, const RtDrawStamp* models,
+                             uint32_t nmodels, float strength);
 
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Terrain generated on the device: the project's deterministic
  * procedural world (raytrace_amd/host/world.cpp: generate_chunk + pack_into per world chunk, MATERIALS[id].pack()) written straight
@@ -1058,7 +1128,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtStampPlace, RT_STAMP_*, rt_stamp_create, rt_stamp_capture, rt_stamp_info, rt_stamp_read,
  *        rt_stamp_destroy, rt_edit_stamps (voxel stamps: prefabs captured and pasted with rotation on the device).
  *        Additive, same minor version: RtDrawStamp, rt_draw_stamps, rt_draw_stamps_async (voxel-model entities: stamps drawn at
- *        float positions and scales, composited into the G-buffer by depth). */
+ *        float positions and scales, composited into the G-buffer by depth).
+ *        Additive, same minor version: rt_shadow_entities, rt_shadow_entities_async (entity shadows: drawn boxes and models take the
+ *        sun's direct term out of the lighting planes where they shade a pixel). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -25,7 +25,7 @@ ABI_SYMBOLS = (
     "rt_denoise_history", "rt_denoise_planes_counted", "rt_sweep_boxes", "rt_sweep_boxes_async",
     "rt_edit_shapes", "rt_draw_boxes", "rt_draw_boxes_async", "rt_add_lights", "rt_add_lights_async",
     "rt_stamp_create", "rt_stamp_capture", "rt_stamp_info", "rt_stamp_read", "rt_stamp_destroy", "rt_edit_stamps",
-    "rt_draw_stamps", "rt_draw_stamps_async",
+    "rt_draw_stamps", "rt_draw_stamps_async", "rt_shadow_entities", "rt_shadow_entities_async",
 )
 
 _amd = None
@@ -154,6 +154,10 @@ def amd():
         lib.rt_draw_stamps.restype = C.c_int
         lib.rt_draw_stamps_async.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
         lib.rt_draw_stamps_async.restype = C.c_int
+        lib.rt_shadow_entities.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P, C.c_uint32, C.c_float]
+        lib.rt_shadow_entities.restype = C.c_int
+        lib.rt_shadow_entities_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P, C.c_uint32, C.c_float]
+        lib.rt_shadow_entities_async.restype = C.c_int
         lib.rt_add_lights.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
         lib.rt_add_lights.restype = C.c_int
         lib.rt_add_lights_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
@@ -263,5 +267,7 @@ def host():
         lib.rth_pipeline_set_models.restype = C.c_int
         lib.rth_pipeline_set_lights.argtypes = [P, P, C.c_uint32]
         lib.rth_pipeline_set_lights.restype = C.c_int
+        lib.rth_pipeline_enable_entity_shadows.argtypes = [P, C.c_float]
+        lib.rth_pipeline_enable_entity_shadows.restype = C.c_int
         _host = lib
     return _host

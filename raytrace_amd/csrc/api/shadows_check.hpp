@@ -1,0 +1,46 @@
+// shadows_check.hpp — the host half of rt_shadow_entities that needs no context: the test of the call's plain arguments, the
+// validity of a batch of RtDrawBox occluders and whether a frame has a sun term at all.  Plain C++ with no HIP include, so that
+// tests/entity_shadows_main.cpp runs this very code on the CPU.  The comparisons are the kernel's (rt_shadows.hip, box_valid): each
+// is false for a NaN, so a record with a NaN fails.  (The models' records are draw_stamps.hpp's, unchanged.)
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../../include/rt_abi.h"
+
+namespace rta __attribute__((visibility("hidden"))) {
+
+constexpr uint32_t kMaxShadowBoxes = 4096, kMaxShadowModels = 4096;   // occluders per call, of either kind
+
+// What is wrong with the arguments that are tested before the context is looked at, or nullptr: NULL uniforms, a NULL array with its
+// count above 0, a count above 4096, a strength that is not finite or lies outside (0, 1].
+inline const char* shadow_args_error(const void* u, const void* boxes, uint32_t nboxes, const void* models, uint32_t nmodels, float strength) {
+    if (!u) return "null uniforms";
+    if (nboxes > kMaxShadowBoxes) return "more than 4096 boxes in one call";
+    if (nmodels > kMaxShadowModels) return "more than 4096 models in one call";
+    if ((nboxes > 0u && !boxes) || (nmodels > 0u && !models)) return "null pointer";
+    if (!(strength > 0.0f && strength <= 1.0f)) return "strength must lie in (0, 1]";   // (false for a NaN)
+    return nullptr;
+}
+
+// One occluder box, rt_draw_boxes' valid box: every float finite, |lo_k|, |hi_k| <= 2^22 and lo_k < hi_k.  material and emission
+// play no part.
+inline bool shadow_box_valid(const RtDrawBox& b) {
+    for (int k = 0; k < 3; k++)
+        if (!(std::fabs(b.lo[k]) <= 4194304.0f && std::fabs(b.hi[k]) <= 4194304.0f && b.lo[k] < b.hi[k])) return false;
+    return true;
+}
+
+// The index of the first invalid box of a batch, or `count` when every one is valid.
+inline uint32_t first_invalid_shadow_box(const RtDrawBox* boxes, uint32_t count) {
+    for (uint32_t i = 0; i < count; i++)
+        if (!shadow_box_valid(boxes[i])) return i;
+    return count;
+}
+
+// A frame whose sun colour is (0, 0, 0) — the night — has no sun term to remove: the call enqueues nothing.  (-0 counts as 0; a NaN
+// does not.)
+inline bool shadow_sun_is_dark(const float sunlight[3]) { return sunlight[0] == 0.0f && sunlight[1] == 0.0f && sunlight[2] == 0.0f; }
+
+}  // namespace rta

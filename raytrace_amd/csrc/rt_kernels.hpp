@@ -232,6 +232,17 @@ struct LightsArgs {
 };
 hipError_t launch_add_lights(const Scene& sc, const Frame& f, const Planes& pl, const LightsArgs& a, hipStream_t st);
 
+// rt_shadows.hip: the sun's direct term taken out of the lighting planes of a whole frame's row-major planes where an entity shades
+// the pixel (rt_shadow_entities).  One launch for boxes and models together; a wave owns an 8x8 pixel tile.  Frame supplies the camera
+// of the frame the planes hold, lr, the region and sunangle / sunlight.
+struct ShadowArgs {
+    const uint4* boxes;   // RtDrawBox[nboxes] (two uint4 each; lo and hi are read)
+    const uint4* recs;    // DrawStampRecord[nmodels] (api/draw_stamps.hpp; four uint4 each), resolved and validated on the host
+    uint32_t nboxes, nmodels;
+    float strength;       // (0, 1]
+};
+hipError_t launch_shadow_entities(const Scene& sc, const Frame& f, const Planes& pl, const ShadowArgs& a, hipStream_t st);
+
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
 // (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
 // or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)

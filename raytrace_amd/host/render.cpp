@@ -102,6 +102,12 @@ int Pipeline::set_lights(const RtPointLight* lights, uint32_t count) {
     return RT_OK;
 }
 
+int Pipeline::enable_entity_shadows(float strength) {
+    if (!(strength >= 0.0f && strength <= 1.0f)) return RT_ERR_INVALID_ARG;   // (false for a NaN)
+    shadow_strength_ = strength;
+    return RT_OK;
+}
+
 int Pipeline::enable_history_denoise(const RtDenoiseParams& params) {
     bool ok = reproject_ && params.struct_size == sizeof(RtDenoiseParams) && (params.weight_by_count == 0 || params.weight_by_count == 1);
     for (int i = 0; i < 6; i++) ok = ok && params.settle[i] <= 127u;
@@ -208,6 +214,8 @@ int Pipeline::draw_frame(game::Game& game) {
         rc = rt_draw_boxes(ctx_, &u, boxes_.data(), box_lights_.data(), (uint32_t)boxes_.size());
     if (rc == RT_OK && !models_.empty())                             // voxel-model entities likewise, after the boxes
         rc = rt_draw_stamps(ctx_, &u, models_.data(), model_lights_.data(), (uint32_t)models_.size());
+    if (rc == RT_OK && shadow_strength_ > 0.0f && !(boxes_.empty() && models_.empty()))   // the drawn entities shade what lies behind them from the sun
+        rc = rt_shadow_entities(ctx_, &u, boxes_.data(), (uint32_t)boxes_.size(), models_.data(), (uint32_t)models_.size(), shadow_strength_);
     if (rc == RT_OK && !lights_.empty())                             // moving lights shade the frame and its entities; the denoise filters them
         rc = rt_add_lights(ctx_, &u, lights_.data(), (uint32_t)lights_.size());
     if (rc == RT_OK && post_) {                                      // the same command buffer goes on (:98-123), one submit (:229-235)

@@ -136,6 +136,10 @@ class Pipeline {
     // in front of the denoise (the array is copied).  count == 0 adds none.  RT_ERR_INVALID_ARG for more than 1024 lights or a NULL
     // array with count > 0.
     int set_lights(const RtPointLight* lights, uint32_t count);
+    // Entity shadows: every draw_frame from now on enqueues rt_shadow_entities(boxes, models, strength) for the boxes and models set
+    // above, behind their draws and in front of the point lights — the intended order: boxes, models, shadows, lights, denoise.
+    // strength in (0, 1]; 0 switches it off again.  RT_ERR_INVALID_ARG for anything else.
+    int enable_entity_shadows(float strength);
     bool post_passes() const { return post_; }
 
  private:
@@ -158,6 +162,7 @@ class Pipeline {
     std::vector<RtDrawStamp> models_;  // set_models
     std::vector<RtProbeLight> model_lights_;
     std::vector<RtPointLight> lights_; // set_lights
+    float shadow_strength_ = 0.0f;     // enable_entity_shadows; 0 = off
     std::unique_ptr<TerrainUploadManager> tum_;
     std::unique_ptr<world::ChunkStorage> chunks_;
     bool stream_on_device_ = false;

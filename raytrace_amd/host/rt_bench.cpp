@@ -11,7 +11,7 @@
 //            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
 //            [--boxes N]
-//            [--lights N]
+//            [--lights N] [--shadows N [--shadow-models]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -75,6 +75,12 @@
 // bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times; and, as a yardstick in the
 // same process, rt_draw_boxes draws the bounding boxes of the same records, 20 times.  One JSON line: the device time of both passes
 // (the launch bracketed by events, RT_FLAG_TIMING_ALL), their ratio, the call-to-return time of rt_draw_stamps and the pixels drawn.
+// --shadows N [--shadow-models [--model-scale S]]: instead of the frame loop, entity shadows.  N occluders stand 0.5 to 6 units above what
+// N random pixels show — player-sized boxes, or with --shadow-models the 9 x 9 x 12 stamp of --models at scale S in the 48
+// orientations in turn — and rt_shadow_entities shades a freshly drawn --width x --height frame with them, 20 times.  As yardsticks in
+// the same process rt_draw_boxes draws the same boxes (the models' bounding boxes) and rt_add_lights adds as many lights (at most 1024)
+// at the occluders' centres.  One JSON line: the device time of each launch (bracketed by events, RT_FLAG_TIMING_ALL), the
+// call-to-return time of rt_shadow_entities and the pixels it changed.
 // --lights N: instead of the frame loop, point lights.  N lights of radius 8 are scattered deterministically just off visible
 // surfaces — rt_pick_pixels on N pixels spread over the view, each light 1 to 4 units off its hit point along the face's normal (30
 // units along the ray where the pixel shows sky) — and rt_add_lights adds them to a freshly drawn --width x --height frame, 20 times.
@@ -516,6 +522,117 @@ int run_lights(rt::game::Game& game, const std::vector<uint8_t>& noise, int widt
     return 0;
 }
 
+// --shadows: see the head of the file
+int run_shadows(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n,
+                bool as_models, float scale) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    // the stamp of --models: a third solid, the rest air and absent in turn
+    const int32_t E[3] = {9, 9, 12};
+    std::vector<uint32_t> mats((size_t)E[0] * E[1] * E[2]);
+    std::vector<uint8_t> state(mats.size());
+    for (size_t i = 0; i < mats.size(); i++) {
+        state[i] = rnd() < 0.3333f ? RT_STAMP_SOLID : (i & 1u ? RT_STAMP_AIR : RT_STAMP_ABSENT);
+        mats[i] = (1u << 15) | ((40u + (uint32_t)i % 80u) << 14) | ((30u + (uint32_t)i % 90u) << 7) | (20u + (uint32_t)i % 100u);
+    }
+    uint32_t id = 0;
+    if (as_models && p->stamp_create(E, mats.data(), state.data(), &id) != RT_OK) { std::fprintf(stderr, "stamp_create failed: %s\n", p->last_error()); delete p; return 1; }
+    static const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    // where the occluders stand: what random pixels show, 0.5 to 6 units above it (30 units along the ray where the pixel shows sky)
+    std::vector<int32_t> xy(2u * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        xy[2u * i] = std::min(width - 1, (int)(rnd() * (float)width));
+        xy[2u * i + 1] = std::min(height - 1, (int)(rnd() * (float)height));
+    }
+    std::vector<RtRayHit> hits(n);
+    int rc = n ? rt_pick_pixels(ctx, &u, xy.data(), n, hits.data()) : RT_OK;
+    std::vector<RtDrawBox> boxes(n);
+    std::vector<RtDrawStamp> models(as_models ? n : 0u);
+    const uint32_t nlights = std::min(n, 1024u);
+    std::vector<RtPointLight> lights(nlights);
+    for (uint32_t i = 0; i < n && rc == RT_OK; i++) {
+        float c[3];
+        if (hits[i].kind == RT_HIT_SOLID) {
+            for (int a = 0; a < 3; a++) c[a] = hits[i].position[a];
+            c[2] += 0.5f + 5.5f * rnd();
+        } else {
+            const float sx = ((float)xy[2u * i] / (float)width) * 2.0f - 1.0f, sy = ((float)xy[2u * i + 1] / (float)height) * 2.0f - 1.0f;
+            float v[3], len = 0.0f;
+            for (int a = 0; a < 3; a++) { v[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; len += v[a] * v[a]; }
+            len = std::sqrt(len);
+            for (int a = 0; a < 3; a++) c[a] = u.origin[a] + v[a] / len * 30.0f;
+        }
+        RtDrawBox& b = boxes[i];
+        b = RtDrawBox{};
+        if (as_models) {
+            RtDrawStamp& m = models[i];
+            m = RtDrawStamp{};
+            m.stamp = id; m.scale = scale; m.orient = (uint8_t)(i % 48u); m.emission = 0xFF000000u;
+            for (int a = 0; a < 3; a++) {
+                const float ext = (float)E[perms[m.orient >> 3][a]];
+                m.origin[a] = c[a] - 0.5f * ext * scale;
+                b.lo[a] = m.origin[a]; b.hi[a] = std::fma(ext, scale, m.origin[a]);
+            }
+        } else {
+            for (int a = 0; a < 3; a++) { const float half = a == 2 ? 0.9f : 0.3f; b.lo[a] = c[a] - half; b.hi[a] = c[a] + half; }   // a player's box
+        }
+        b.material = (1u << 15) | ((40u + i % 80u) << 14) | ((30u + i % 90u) << 7) | (20u + i % 100u);
+        b.emission = 0xFF000000u;
+        if (i < nlights) {
+            RtPointLight& l = lights[i];
+            l = RtPointLight{};
+            for (int a = 0; a < 3; a++) { l.position[a] = c[a]; l.color[a] = 20.0f; }
+            l.radius = 8.0f;
+        }
+    }
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    const size_t npix = (size_t)width * (size_t)height;
+    std::vector<float> before(4u * npix), after(4u * npix);
+    std::vector<RtProbeLight> face(6u * (size_t)n);
+    for (RtProbeLight& f : face) { f = RtProbeLight{}; f.light[0] = f.light[1] = f.light[2] = 8.0f; }
+    const int reps = 20;
+    double device_ms[3] = {0.0, 0.0, 0.0}, call_ms = 0.0;   // 0: the shadows; the yardsticks: 1 rt_draw_boxes of the same boxes, 2 rt_add_lights of as many lights
+    uint32_t launches = 0;
+    for (int pass = 0; pass < 3 && rc == RT_OK; pass++) {
+        for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {   // (the first repetition warms the staging up)
+            RtTiming tm{};
+            rc = rt_draw_frame(ctx, &u);
+            if (rc == RT_OK) rc = rt_sync(ctx);
+            if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);   // (drains the frame's own launches)
+            if (rc == RT_OK && pass == 0 && i == reps) rc = rt_readback(ctx, RT_BUF_LIGHTING_F32, before.data(), npix * 16u);
+            auto t = std::chrono::steady_clock::now();
+            if (rc == RT_OK) {
+                if (pass == 0) rc = rt_shadow_entities(ctx, &u, as_models ? nullptr : boxes.data(), as_models ? 0u : n, models.data(), as_models ? n : 0u, 1.0f);
+                else if (pass == 1) rc = rt_draw_boxes(ctx, &u, boxes.data(), face.data(), n);
+                else rc = rt_add_lights(ctx, &u, lights.data(), nlights);
+            }
+            const double call = ms_since(t);
+            if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);
+            if (i > 0) { device_ms[pass] += tm.shade_ms / reps; if (pass == 0) { call_ms += call / reps; launches += tm.other_launches; } }
+        }
+        if (rc == RT_OK && pass == 0) rc = rt_readback(ctx, RT_BUF_LIGHTING_F32, after.data(), npix * 16u);
+    }
+    if (rc != RT_OK) { std::fprintf(stderr, "entity shadows failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    uint64_t changed = 0;
+    for (size_t i = 0; i < npix; i++) changed += std::memcmp(&before[4u * i], &after[4u * i], 16) != 0;
+    std::printf("{\"shadows\": %u, \"shadow_models\": %d, \"model_scale\": %g, \"frame\": \"%dx%d spp %d depth %d\", \"shadow_entities_device_ms\": %.4f, "
+                "\"shadow_entities_call_ms\": %.4f, \"launches_per_call\": %.2f, \"draw_boxes_device_ms\": %.4f, \"add_lights_device_ms\": %.4f, "
+                "\"add_lights_count\": %u, \"pixels_changed\": %llu}\n",
+                n, as_models ? 1 : 0, (double)scale, width, height, spp, depth, device_ms[0], call_ms, (double)launches / reps, device_ms[1],
+                device_ms[2], nlights, (unsigned long long)changed);
+    delete p;
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -525,7 +642,8 @@ int main(int argc, char** argv) {
     int edits = 0, edit_radius = 0;
     const char* edit_shape = nullptr;
     int edit_stamp = -1;
-    long long rays = 0, boxes = -1, lights = -1, models = -1;
+    long long rays = 0, boxes = -1, lights = -1, models = -1, shadows = -1;
+    bool shadow_models = false;
     float model_scale = 0.125f;
     bool rays_coherent = false;
     bool reproject = false, stream = false, stream_history = false, history_denoise = false;
@@ -563,6 +681,8 @@ int main(int argc, char** argv) {
         else if (want("--boxes")) boxes = std::atoll(argv[++i]);
         else if (want("--lights")) lights = std::atoll(argv[++i]);
         else if (want("--models")) models = std::atoll(argv[++i]);
+        else if (want("--shadows")) shadows = std::atoll(argv[++i]);
+        else if (std::strcmp(argv[i], "--shadow-models") == 0) shadow_models = true;
         else if (want("--model-scale")) model_scale = std::strtof(argv[++i], nullptr);
         else positional.push_back(argv[i]);
     }
@@ -577,6 +697,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--models must be in 0..4096, --model-scale in 2^-8..64\n");
         return 2;
     }
+    if (shadows < -1 || shadows > 4096) { std::fprintf(stderr, "--shadows must be in 0..4096\n"); return 2; }
     if (lights < -1 || lights > 1024) { std::fprintf(stderr, "--lights must be in 0..1024\n"); return 2; }
     if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
@@ -609,6 +730,7 @@ int main(int argc, char** argv) {
     if (rays > 0) return run_rays(game, noise, width, height, spp, depth, device, (uint32_t)rays, rays_coherent);
     if (boxes >= 0) return run_boxes(game, noise, width, height, spp, depth, device, (uint32_t)boxes);
     if (models >= 0) return run_models(game, noise, width, height, spp, depth, device, (uint32_t)models, model_scale);
+    if (shadows >= 0) return run_shadows(game, noise, width, height, spp, depth, device, (uint32_t)shadows, shadow_models, model_scale);
     if (lights >= 0) return run_lights(game, noise, width, height, spp, depth, device, (uint32_t)lights);
     std::string err;
 

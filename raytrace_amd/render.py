@@ -474,6 +474,25 @@ class Context:
         self._check(self._lib.rt_draw_stamps_async(self._h, C.byref(uniforms), _p(models) if models.size else None,
                                                    C.c_void_p(face_lights.data_ptr()), int(models.size)))
 
+    # -- entity shadows ----------------------------------------------------------------------------------
+    def shadow_entities(self, uniforms, boxes=None, models=None, strength=1.0):
+        """rt_shadow_entities: the drawn `boxes` (DRAW_BOX_DTYPE[N]) and `models` (DRAW_STAMP_DTYPE[M]) take the sun's direct term, times
+        `strength` in (0, 1], out of the two lighting planes of the frame drawn last where they shade a pixel the world leaves sunlit,
+        under the camera, lr and sun angle of `uniforms`.  Synchronous; an invalid record fails the whole call (RtError, INVALID_ARG)."""
+        boxes = np.zeros(0, dtype=DRAW_BOX_DTYPE) if boxes is None else np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
+        models = np.zeros(0, dtype=DRAW_STAMP_DTYPE) if models is None else np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
+        self._check(self._lib.rt_shadow_entities(self._h, C.byref(uniforms), _p(boxes) if boxes.size else None, int(boxes.size),
+                                                 _p(models) if models.size else None, int(models.size), float(strength)))
+
+    def shadow_entities_async(self, uniforms, boxes=None, models=None, strength=1.0):
+        """rt_shadow_entities_async: `boxes` a torch device tensor, any contiguous tensor of N * 32 bytes (RtDrawBox rows: what
+        draw_boxes_async took), or None; `models` host records as for shadow_entities (free again on return).  Enqueued behind the frame
+        drawn last; an invalid box is skipped on the device, an invalid model fails the call before anything is enqueued."""
+        n = 0 if boxes is None else check_shadow_box_tensor(boxes, self.cfg.device if self.cfg is not None else 0)
+        models = np.zeros(0, dtype=DRAW_STAMP_DTYPE) if models is None else np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
+        self._check(self._lib.rt_shadow_entities_async(self._h, C.byref(uniforms), C.c_void_p(boxes.data_ptr()) if n else None, n,
+                                                       _p(models) if models.size else None, int(models.size), float(strength)))
+
     # -- point lights ------------------------------------------------------------------------------------
     def add_lights(self, uniforms, lights):
         """rt_add_lights: `lights` POINT_LIGHT_DTYPE[N] records (make_point_lights) added to the two lighting planes of the frame drawn
@@ -875,6 +894,13 @@ class Pipeline:
         if rc != 0:
             raise RtError(rc, "set_lights: at most %d lights" % MAX_POINT_LIGHTS)
 
+    def enable_entity_shadows(self, strength=1.0):
+        """Pipeline::enable_entity_shadows: every draw_frame from now on enqueues rt_shadow_entities for the boxes and models set
+        (set_boxes, set_models) behind their draws and in front of the point lights; strength in (0, 1], 0 switches it off again."""
+        rc = _lib.host().rth_pipeline_enable_entity_shadows(self._h, float(strength))
+        if rc != 0:
+            raise RtError(rc, "enable_entity_shadows: strength must be 0 (off) or lie in (0, 1]")
+
     def close(self):
         if self._h:
             _lib.host().rth_pipeline_free(self._h)   # impl Drop for Pipeline, pipeline.rs:258-277
@@ -1037,6 +1063,27 @@ def check_draw_box_tensors(boxes, face_lights, device):
         raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
     if face_lights.numel() * face_lights.element_size() != 6 * n * PROBE_LIGHT_DTYPE.itemsize:
         raise ValueError("face_lights must be a contiguous tensor of 6 N * 16 bytes")
+    return n
+
+
+def check_shadow_box_tensor(boxes, device):
+    """Context.shadow_entities_async's device argument: a contiguous tensor of N * 32 bytes on GPU `device`, 16-byte aligned, N at most
+    4096.  Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
+    import torch
+    if not isinstance(boxes, torch.Tensor):
+        raise ValueError("boxes must be a torch tensor")
+    if not boxes.is_cuda or boxes.device.index != int(device):
+        raise ValueError("boxes must be a tensor on cuda:%d (the context's device), not %s" % (int(device), boxes.device))
+    if boxes.data_ptr() % 16:
+        raise ValueError("boxes must be 16-byte aligned")
+    if not boxes.is_contiguous():
+        raise ValueError("boxes must be contiguous")
+    nbytes = boxes.numel() * boxes.element_size()
+    if nbytes % DRAW_BOX_DTYPE.itemsize:
+        raise ValueError("boxes must hold whole 32-byte RtDrawBox records")
+    n = nbytes // DRAW_BOX_DTYPE.itemsize
+    if n > MAX_DRAW_BOXES:
+        raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
     return n
 
 
