@@ -1,0 +1,311 @@
+// api_passes.hip — the passes over the frame drawn last, each one launch on the stream that frame ended on: entity boxes
+// (rt_draw_boxes[_async]) and voxel-model entities (rt_draw_stamps[_async]) between the frame and its post passes, entity shadows
+// (rt_shadow_entities[_async]) behind the entity draws, point lights (rt_add_lights[_async]) behind those.  What the passes share is
+// here once: the prologue (pass_begin), the verdict on a batch of models (models_check), the models' way to the device
+// (upload_models) and the planes a pass writes (planes_written); the synchronous calls' staging is rt_context.hpp's stage_sync.
+//
+// Every launch follows the queries enqueued so far (ev_query): their results may be its records or face lights.  The passes that
+// read the region (lights, shadows) find it on their stream: every world change runs there too, the earlier ones in front, and a
+// later one — whichever lane's stream it finds as the context's by then — first joins every lane (world_change_begin).
+#include "lights_check.hpp"
+#include "rt_context.hpp"
+#include "shadows_check.hpp"
+
+using namespace rta;
+
+namespace {
+constexpr uint32_t kMaxDrawBoxes = 4096;
+static_assert(sizeof(RtDrawBox) == 32 && sizeof(RtProbeLight) == 16, "the kernels read two 16-byte words per box and one per face light");
+static_assert(sizeof(RtPointLight) == 32, "the kernel reads two 16-byte words per light");
+static_assert(sizeof(RtDrawStamp) == 32 && sizeof(DrawStampRecord) == 64, "one 32-byte record per model from the caller, four 16-byte words to the kernels");
+
+// What is wrong with the plain arguments of a pass with one batch, or nullptr (shadow_args_error is the form with two batches).
+const char* batch_args_error(const void* u, const char* too_many, bool null_pointer) {
+    if (!u) return "null uniforms";
+    if (too_many) return too_many;
+    return null_pointer ? "null pointer" : nullptr;
+}
+
+// The prologue of every pass: the verdict on its plain arguments, then the context's state.  RT_OK with *work = false: a valid call
+// with no record, which enqueues nothing.
+int pass_begin(RtContext* c, const std::string& fn, const char* args_error, bool reads_world, uint32_t records, bool* work) {
+    *work = false;
+    if (args_error) return fail(c, RT_ERR_INVALID_ARG, fn + ": " + args_error);
+    if (c->cfg.tile_world != 1) return fail(c, RT_ERR_UNIMPLEMENTED, fn + ": whole-frame contexts only");
+    if (!c->frame_recorded) return fail(c, RT_ERR_NOT_READY, fn + ": no frame drawn yet");
+    if (reads_world && !c->world_resident) return fail(c, RT_ERR_NOT_READY, fn + ": upload the full region first");
+    *work = records > 0u;
+    return RT_OK;
+}
+
+// The models of a call, resolved against the live stamps before anything is enqueued; `nothing` ends the refusal.
+int models_check(RtContext* c, const std::string& fn, const RtDrawStamp* models, uint32_t n, const char* nothing) {
+    const uint32_t bad = draw_stamps_validate(c->stamps, models, n);
+    if (bad == n) return RT_OK;
+    return fail(c, RT_ERR_INVALID_ARG, fn + ": model " + std::to_string(bad) +
+                                           " has an unknown stamp id, orient >= 48, a non-zero reserved field, a scale outside"
+                                           " [2^-8, 64] or a corner beyond 2^22; " + nothing);
+}
+
+// The slot's prepass no longer describes the planes a pass writes: a still camera must not carry entity pixels, light or shadow into
+// the next frame.  The draws write the geometry planes too, the lighting passes the two lighting planes only.
+void planes_written(RtContext* c, bool geometry_too) {
+    if (geometry_too)
+        for (int b : {RT_BUF_DEPTH_F32, RT_BUF_DEPTH_R16UI, RT_BUF_NORMAL_R8UI, RT_BUF_ALBEDO_RGBA8, RT_BUF_EMISSION_RGBA8}) plane_written(c, c->planes[b]);
+    for (int b : {RT_BUF_LIGHTING_F32, RT_BUF_LIGHTING_RGBA16}) plane_written(c, c->planes[b]);
+}
+
+// the camera of the frame the planes hold (DrawBoxesArgs, DrawStampsArgs)
+template <typename Args>
+void set_camera(Args& a, const RtUniforms* u, const RtConfig& cfg) {
+    a.width = cfg.width; a.height = cfg.height;
+    for (int k = 0; k < 3; k++) { a.origin[k] = u->origin[k]; a.forward[k] = u->forward[k]; a.up[k] = u->up[k]; a.right[k] = u->right[k]; }
+}
+
+// The device records of `n` (valid) models, and `extra_bytes` of the caller's behind them, through the next of the two staging sets
+// (rt_draw_stamps and rt_shadow_entities take turns over the same two, in call order) to *dev; the context's stream waits for the
+// transfer.  The caller launches there and then records (*set)->ev_applied on it: the set's next transfer and rt_stamp_destroy wait
+// for that launch.
+int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const void* extra_host, size_t extra_bytes, StagingSet** set, uint8_t** dev) {
+    const size_t rec_bytes = (size_t)n * sizeof(DrawStampRecord), need = rec_bytes + extra_bytes;
+    StagingSet& s = c->draw_sets[c->draw_batches & 1u];
+    if (!c->upload_stream) RT_HIP(c, new_stream(c, &c->upload_stream));
+    for (hipEvent_t* ev : {&s.ev_copied.ev, &s.ev_applied.ev})
+        if (!*ev) RT_HIP(c, new_event(c, ev));
+    // the set's previous transfer has left the host block; a set that must grow waits for the launch that reads its device block
+    RT_HIP(c, s.ev_copied.host_wait());
+    s.ev_copied.forget();
+    if (need > s.cap) {
+        RT_HIP(c, s.ev_applied.host_wait());
+        s.ev_applied.forget();
+        RT_HIP(c, s.grow(c, need, staging_alloc(need)));
+    }
+    draw_stamp_fill_records(c->stamps, models, n, reinterpret_cast<DrawStampRecord*>(s.host));
+    if (extra_bytes) memcpy(s.host + rec_bytes, extra_host, extra_bytes);
+    for (uint32_t i = 0; i < n; i++) c->stamps.find(models[i].stamp)->used = true;   // rt_stamp_destroy waits for the launch
+    c->draw_batches++;
+    // the transfer on the upload stream, so that it does not queue behind the frame; it follows the set's previous launch
+    RT_HIP(c, s.ev_applied.wait(c->upload_stream));
+    RT_HIP(c, hipMemcpyAsync(s.dev, s.host, need, hipMemcpyHostToDevice, c->upload_stream));
+    RT_HIP(c, s.ev_copied.record(c->upload_stream));
+    RT_HIP(c, hipStreamWaitEvent(c->stream, s.ev_copied.ev, 0));
+    *set = &s;
+    *dev = s.dev;
+    return RT_OK;
+}
+
+// ---- entity boxes ---------------------------------------------------------------------------------------------------------------
+int draw_boxes_begin(RtContext* c, const char* fn, const RtUniforms* u, const void* boxes, const void* lights, uint32_t count, bool* work) {
+    return pass_begin(c, fn, batch_args_error(u, count > kMaxDrawBoxes ? "more than 4096 boxes in one call" : nullptr, count > 0u && (!boxes || !lights)),
+                      false, count, work);
+}
+
+int draw_boxes_launch(RtContext* c, const RtUniforms* u, const void* boxes_dev, const void* lights_dev, uint32_t count) {
+    planes_written(c, true);
+    RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
+    rtd::DrawBoxesArgs a;
+    a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
+    a.lights = reinterpret_cast<const float4*>(lights_dev);
+    a.count = count;
+    set_camera(a, u, c->cfg);
+    LaunchTimer t(c, 1);
+    RT_HIP(c, rtd::launch_draw_boxes(planes_of(c), a, c->stream));
+    return RT_OK;
+}
+
+// ---- point lights ---------------------------------------------------------------------------------------------------------------
+int add_lights_begin(RtContext* c, const char* fn, const RtUniforms* u, const void* lights, uint32_t count, bool* work) {
+    return pass_begin(c, fn, batch_args_error(u, count > kMaxPointLights ? "more than 1024 lights in one call" : nullptr, count > 0u && !lights), true,
+                      count, work);
+}
+
+int add_lights_launch(RtContext* c, const RtUniforms* u, const void* lights_dev, uint32_t count) {
+    planes_written(c, false);
+    RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
+    rtd::LightsArgs a;
+    a.lights = reinterpret_cast<const uint4*>(lights_dev);
+    a.count = count;
+    LaunchTimer t(c, 1);
+    RT_HIP(c, rtd::launch_add_lights(scene_of(c), frame_of(c, u), planes_of(c), a, c->stream));
+    return RT_OK;
+}
+
+// ---- voxel-model entities: the models are host records in both calls ------------------------------------------------------------
+int draw_stamps_begin(RtContext* c, const char* fn, const RtUniforms* u, const RtDrawStamp* models, const void* lights, uint32_t count, bool* work) {
+    const int rc = pass_begin(c, fn, batch_args_error(u, count > kMaxDrawStamps ? "more than 4096 models in one call" : nullptr, count > 0u && (!models || !lights)),
+                              false, count, work);
+    return rc == RT_OK && *work ? models_check(c, fn, models, count, "nothing was drawn") : rc;
+}
+
+// `lights_host` (the synchronous call's 6 * count face lights) travels behind the records; the asynchronous call names `lights_dev`.
+int draw_stamps_enqueue(RtContext* c, const RtUniforms* u, const RtDrawStamp* models, const RtProbeLight* lights_host,
+                        const RtProbeLight* lights_dev, uint32_t count) {
+    RT_HIP(c, hipSetDevice(c->device));
+    StagingSet* s;
+    uint8_t* recs;
+    const int rc = upload_models(c, models, count, lights_host, lights_host ? (size_t)count * 6u * sizeof(RtProbeLight) : 0u, &s, &recs);
+    if (rc != RT_OK) return rc;
+    planes_written(c, true);
+    RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
+    rtd::DrawStampsArgs a;
+    a.recs = reinterpret_cast<const uint4*>(recs);
+    a.lights = reinterpret_cast<const float4*>(lights_host ? reinterpret_cast<const RtProbeLight*>(recs + (size_t)count * sizeof(DrawStampRecord)) : lights_dev);
+    a.count = count;
+    set_camera(a, u, c->cfg);
+    {
+        LaunchTimer t(c, 1);
+        RT_HIP(c, rtd::launch_draw_stamps(planes_of(c), a, c->stream));
+    }
+    RT_HIP(c, s->ev_applied.record(c->stream));
+    return RT_OK;
+}
+
+// ---- entity shadows: device boxes (staged by the synchronous call), host models as rt_draw_stamps' ------------------------------
+int shadow_begin(RtContext* c, const char* fn, const RtUniforms* u, const void* boxes, uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels,
+                 float strength, bool* work) {
+    const int rc = pass_begin(c, fn, shadow_args_error(u, boxes, nboxes, models, nmodels, strength), true, nboxes + nmodels, work);
+    return rc == RT_OK && *work ? models_check(c, fn, models, nmodels, "nothing was changed") : rc;
+}
+
+int shadow_enqueue(RtContext* c, const RtUniforms* u, const void* boxes_dev, uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels,
+                   float strength) {
+    const rtd::Frame f = frame_of(c, u);
+    rtd::ShadowArgs a;
+    a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
+    a.recs = nullptr;
+    a.nboxes = nboxes; a.nmodels = nmodels;
+    a.strength = strength;
+    StagingSet* s = nullptr;
+    if (nmodels > 0u) {
+        uint8_t* recs;
+        const int rc = upload_models(c, models, nmodels, nullptr, 0u, &s, &recs);
+        if (rc != RT_OK) return rc;
+        a.recs = reinterpret_cast<const uint4*>(recs);
+    }
+    planes_written(c, false);
+    RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
+    {
+        LaunchTimer t(c, 1);
+        RT_HIP(c, rtd::launch_shadow_entities(scene_of(c), f, planes_of(c), a, c->stream));
+    }
+    if (s) RT_HIP(c, s->ev_applied.record(c->stream));
+    return RT_OK;
+}
+
+// night: the frame has no sun term
+bool sun_is_dark(const RtContext* c, const RtUniforms* u) {
+    const rtd::Frame f = frame_of(c, u);
+    return shadow_sun_is_dark(f.sunlight);
+}
+
+// the end of a synchronous call: it waits for its launch
+int finish_sync(RtContext* c, int rc) {
+    if (rc != RT_OK) return rc;
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rt_draw_boxes(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes, const RtProbeLight* face_lights, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    int rc = draw_boxes_begin(ctx, "rt_draw_boxes", u, boxes, face_lights, count, &work);
+    if (rc != RT_OK || !work) return rc;
+    const uint32_t bad = first_invalid_draw_box(boxes, count);
+    if (bad != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_draw_boxes: box " + std::to_string(bad) + " is not a valid box");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    uint8_t* dev[2];
+    rc = stage_sync(ctx, ctx->stream, {{boxes, (size_t)count * sizeof(RtDrawBox)}, {face_lights, (size_t)count * 6u * sizeof(RtProbeLight)}}, dev);
+    if (rc != RT_OK) return rc;
+    return finish_sync(ctx, draw_boxes_launch(ctx, u, dev[0], dev[1], count));
+}
+
+int rt_draw_boxes_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes_dev, const RtProbeLight* face_lights_dev, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    const int rc = draw_boxes_begin(ctx, "rt_draw_boxes_async", u, boxes_dev, face_lights_dev, count, &work);
+    if (rc != RT_OK || !work) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, boxes_dev) || !query_device_ptr(ctx, face_lights_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_draw_boxes_async: boxes and face_lights must be 16-byte aligned memory of the context's device");
+    return draw_boxes_launch(ctx, u, boxes_dev, face_lights_dev, count);
+}
+
+int rt_add_lights(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    int rc = add_lights_begin(ctx, "rt_add_lights", u, lights, count, &work);
+    if (rc != RT_OK || !work) return rc;
+    const uint32_t bad = first_invalid_point_light(lights, count);
+    if (bad != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_add_lights: light " + std::to_string(bad) + " is not a valid light");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    uint8_t* dev;
+    rc = stage_sync(ctx, ctx->stream, {{lights, (size_t)count * sizeof(RtPointLight)}}, &dev);
+    if (rc != RT_OK) return rc;
+    return finish_sync(ctx, add_lights_launch(ctx, u, dev, count));
+}
+
+int rt_add_lights_async(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights_dev, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    const int rc = add_lights_begin(ctx, "rt_add_lights_async", u, lights_dev, count, &work);
+    if (rc != RT_OK || !work) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, lights_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_add_lights_async: lights must be 16-byte aligned memory of the context's device");
+    return add_lights_launch(ctx, u, lights_dev, count);
+}
+
+int rt_draw_stamps(RtContext* ctx, const RtUniforms* u, const RtDrawStamp* models, const RtProbeLight* face_lights, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    const int rc = draw_stamps_begin(ctx, "rt_draw_stamps", u, models, face_lights, count, &work);
+    if (rc != RT_OK || !work) return rc;
+    return finish_sync(ctx, draw_stamps_enqueue(ctx, u, models, face_lights, nullptr, count));
+}
+
+int rt_draw_stamps_async(RtContext* ctx, const RtUniforms* u, const RtDrawStamp* models, const RtProbeLight* face_lights_dev, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    const int rc = draw_stamps_begin(ctx, "rt_draw_stamps_async", u, models, face_lights_dev, count, &work);
+    if (rc != RT_OK || !work) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, face_lights_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_draw_stamps_async: face_lights_dev must be 16-byte aligned memory of the context's device");
+    return draw_stamps_enqueue(ctx, u, models, nullptr, face_lights_dev, count);
+}
+
+int rt_shadow_entities(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes, uint32_t nboxes, const RtDrawStamp* models,
+                       uint32_t nmodels, float strength) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    int rc = shadow_begin(ctx, "rt_shadow_entities", u, boxes, nboxes, models, nmodels, strength, &work);
+    if (rc != RT_OK || !work) return rc;
+    const uint32_t bad = first_invalid_draw_box(boxes, nboxes);
+    if (bad != nboxes) return fail(ctx, RT_ERR_INVALID_ARG, "rt_shadow_entities: box " + std::to_string(bad) + " is not a valid box");
+    if (sun_is_dark(ctx, u)) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    uint8_t* boxes_dev = nullptr;
+    if (nboxes > 0u) {
+        rc = stage_sync(ctx, ctx->stream, {{boxes, (size_t)nboxes * sizeof(RtDrawBox)}}, &boxes_dev);
+        if (rc != RT_OK) return rc;
+    }
+    return finish_sync(ctx, shadow_enqueue(ctx, u, boxes_dev, nboxes, models, nmodels, strength));
+}
+
+int rt_shadow_entities_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes_dev, uint32_t nboxes, const RtDrawStamp* models,
+                             uint32_t nmodels, float strength) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    const int rc = shadow_begin(ctx, "rt_shadow_entities_async", u, boxes_dev, nboxes, models, nmodels, strength, &work);
+    if (rc != RT_OK || !work) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (nboxes > 0u && !query_device_ptr(ctx, boxes_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_shadow_entities_async: boxes_dev must be 16-byte aligned memory of the context's device");
+    if (sun_is_dark(ctx, u)) return RT_OK;
+    return shadow_enqueue(ctx, u, boxes_dev, nboxes, models, nmodels, strength);
+}
+
+}  // extern "C"

@@ -61,23 +61,27 @@ rtd::Frame query_frame(const RtContext* c, const int32_t lr[3]) {
     return frame_of(c, &u);
 }
 
-// The synchronous calls: `in_bytes` of input through pinned and device staging, the launch, the hits back; waits for them.
+// The end of a synchronous call: the `bytes` its launches left at `dev` (a part of stage_sync's) back to `out`; waits for them.
+int fetch_sync(RtContext* c, hipStream_t st, const uint8_t* dev, void* out, size_t bytes) {
+    uint8_t* host = c->query_block.host + (dev - c->query_block.dev);
+    RT_HIP(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+    RT_HIP(c, hipStreamSynchronize(st));
+    memcpy(out, host, bytes);
+    return RT_OK;
+}
+
+// The synchronous calls: `in_bytes` of input through pinned and device staging, the launch, the hits back.
 int query_sync(RtContext* c, const rtd::Frame& f, const void* in, size_t in_bytes, bool picks, RtRayHit* hits, uint32_t count) {
     hipStream_t st;
     int rc = query_stream_of(c, &st);
     if (rc != RT_OK) return rc;
-    const size_t off = align16(in_bytes), need = off + (size_t)count * sizeof(RtRayHit);
-    // (the previous synchronous call has finished with the staging: it waited for its hits)
-    StagingBlock& q = c->query_block;
-    RT_HIP(c, q.grow(c, need, need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(need + need / 2u)));
-    memcpy(q.host, in, in_bytes);
-    RT_HIP(c, hipMemcpyAsync(q.dev, q.host, in_bytes, hipMemcpyHostToDevice, st));
-    rc = query_launch(c, st, f, picks ? nullptr : q.dev, picks ? q.dev : nullptr, q.dev + off, count);
+    const size_t out_bytes = (size_t)count * sizeof(RtRayHit);
+    uint8_t* dev[2];
+    rc = stage_sync(c, st, {{in, in_bytes}, {nullptr, out_bytes}}, dev);
     if (rc != RT_OK) return rc;
-    RT_HIP(c, hipMemcpyAsync(q.host + off, q.dev + off, (size_t)count * sizeof(RtRayHit), hipMemcpyDeviceToHost, st));
-    RT_HIP(c, hipStreamSynchronize(st));
-    memcpy(hits, q.host + off, (size_t)count * sizeof(RtRayHit));
-    return RT_OK;
+    rc = query_launch(c, st, f, picks ? nullptr : dev[0], picks ? dev[0] : nullptr, dev[1], count);
+    if (rc != RT_OK) return rc;
+    return fetch_sync(c, st, dev[1], hits, out_bytes);
 }
 
 // ---- light probes -------------------------------------------------------------------------------------------------------------
@@ -213,19 +217,14 @@ int rt_probe_light(RtContext* ctx, const RtUniforms* u, const RtLightProbe* prob
     hipStream_t st;
     rc = query_stream_of(ctx, &st);
     if (rc != RT_OK) return rc;
-    // the probes through pinned and device staging, the launches, the results back (the previous synchronous call has finished
-    // with the staging: it waited for its results)
-    const size_t in_bytes = (size_t)count * sizeof(RtLightProbe), out_bytes = (size_t)count * sizeof(RtProbeLight), need = in_bytes + out_bytes;
-    StagingBlock& q = ctx->query_block;
-    RT_HIP(ctx, q.grow(ctx, need, need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(need + need / 2u)));
-    memcpy(q.host, probes, in_bytes);
-    RT_HIP(ctx, hipMemcpyAsync(q.dev, q.host, in_bytes, hipMemcpyHostToDevice, st));
-    rc = probe_launch(ctx, st, u, q.dev, q.dev + in_bytes, count, samples, depth);
+    // the probes through pinned and device staging, the launches, the results back
+    const size_t out_bytes = (size_t)count * sizeof(RtProbeLight);
+    uint8_t* dev[2];
+    rc = stage_sync(ctx, st, {{probes, (size_t)count * sizeof(RtLightProbe)}, {nullptr, out_bytes}}, dev);
     if (rc != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(q.host + in_bytes, q.dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
-    RT_HIP(ctx, hipStreamSynchronize(st));
-    memcpy(out, q.host + in_bytes, out_bytes);
-    return RT_OK;
+    rc = probe_launch(ctx, st, u, dev[0], dev[1], count, samples, depth);
+    if (rc != RT_OK) return rc;
+    return fetch_sync(ctx, st, dev[1], out, out_bytes);
 }
 
 int rt_probe_light_async(RtContext* ctx, const RtUniforms* u, const RtLightProbe* probes_dev, uint32_t count, uint32_t samples,
@@ -252,19 +251,14 @@ int rt_sweep_boxes(RtContext* ctx, const RtBoxSweep* sweeps, uint32_t count, con
     hipStream_t st;
     rc = query_stream_of(ctx, &st);
     if (rc != RT_OK) return rc;
-    // the sweeps through pinned and device staging, the launch, the hits back (the previous synchronous call has finished with the
-    // staging: it waited for its results)
-    const size_t in_bytes = (size_t)count * sizeof(RtBoxSweep), out_bytes = (size_t)count * sizeof(RtSweepHit), need = in_bytes + out_bytes;
-    StagingBlock& q = ctx->query_block;
-    RT_HIP(ctx, q.grow(ctx, need, need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(need + need / 2u)));
-    memcpy(q.host, sweeps, in_bytes);
-    RT_HIP(ctx, hipMemcpyAsync(q.dev, q.host, in_bytes, hipMemcpyHostToDevice, st));
-    rc = sweep_launch(ctx, st, lr, q.dev, q.dev + in_bytes, count);
+    // the sweeps through pinned and device staging, the launch, the hits back
+    const size_t out_bytes = (size_t)count * sizeof(RtSweepHit);
+    uint8_t* dev[2];
+    rc = stage_sync(ctx, st, {{sweeps, (size_t)count * sizeof(RtBoxSweep)}, {nullptr, out_bytes}}, dev);
     if (rc != RT_OK) return rc;
-    RT_HIP(ctx, hipMemcpyAsync(q.host + in_bytes, q.dev + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
-    RT_HIP(ctx, hipStreamSynchronize(st));
-    memcpy(hits, q.host + in_bytes, out_bytes);
-    return RT_OK;
+    rc = sweep_launch(ctx, st, lr, dev[0], dev[1], count);
+    if (rc != RT_OK) return rc;
+    return fetch_sync(ctx, st, dev[1], hits, out_bytes);
 }
 
 int rt_sweep_boxes_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t count, const int32_t lr[3], RtSweepHit* hits_dev) {

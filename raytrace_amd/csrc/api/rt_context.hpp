@@ -1,5 +1,6 @@
 // rt_context.hpp — the context behind the C ABI of include/rt_abi.h, shared by the api_*.hip translation units: its structs and
-// constants, the small helper types (LatchEvent, StagingBlock, TimingPool, env_int) and the few functions that cross files.
+// constants, the small helper types (LatchEvent, StagingBlock, TimingPool, env_int), the synchronous calls' staging (stage_sync)
+// and the few functions that cross files.
 //
 // One context = one GPU.  Nothing here runs ray-trace work on the CPU: if the HIP runtime or a device is missing, rt_create fails
 // with RT_ERR_NO_DEVICE and the caller gets no context.  Everything internal lives in namespace rta (hidden visibility): the
@@ -12,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -388,6 +390,30 @@ inline void StagingBlock::release() {
     if (host) { (void)hipHostFree(host); host = nullptr; }
     if (dev) { (void)hipFree(dev); dev = nullptr; }
     cap = 0;
+}
+
+// What a staging pair that must hold `need` bytes is allocated with when it has to grow: 64 KiB at least, else half as much again.
+inline size_t staging_alloc(size_t need) { return need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(need + need / 2u); }
+
+// One part of a synchronous call's staging: `bytes` copied from `host`, or (host == nullptr) room for what the launch leaves there.
+struct StagePart { const void* host; size_t bytes; };
+// The parts of a synchronous call through query_block, back to back and each on a 16-byte boundary: the host parts (they come first)
+// into the pinned half and from there to the device half in one transfer on `st`; dev[i] is part i's device address.  (The previous
+// synchronous call has finished with the block: it waited for its launch or its results.)
+inline int stage_sync(RtContext* c, hipStream_t st, std::initializer_list<StagePart> parts, uint8_t** dev) {
+    StagingBlock& q = c->query_block;
+    size_t need = 0, send = 0;
+    for (const StagePart& p : parts) { need = align16(need) + p.bytes; if (p.host) send = need; }
+    RT_HIP(c, q.grow(c, need, staging_alloc(need)));
+    size_t off = 0;
+    for (const StagePart& p : parts) {
+        off = align16(off);
+        *dev++ = q.dev + off;
+        if (p.host) memcpy(q.host + off, p.host, p.bytes);
+        off += p.bytes;
+    }
+    RT_HIP(c, hipMemcpyAsync(q.dev, q.host, send, hipMemcpyHostToDevice, st));
+    return RT_OK;
 }
 
 // An environment knob (experiments, A/B timing): *field = v when `s` holds an integer in lo..hi; anything else is ignored.

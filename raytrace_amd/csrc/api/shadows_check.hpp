@@ -1,7 +1,8 @@
 // shadows_check.hpp — the host half of rt_shadow_entities that needs no context: the test of the call's plain arguments, the
-// validity of a batch of RtDrawBox occluders and whether a frame has a sun term at all.  Plain C++ with no HIP include, so that
-// tests/entity_shadows_main.cpp runs this very code on the CPU.  The comparisons are the kernel's (rt_shadows.hip, box_valid): each
-// is false for a NaN, so a record with a NaN fails.  (The models' records are draw_stamps.hpp's, unchanged.)
+// validity of a batch of RtDrawBox records (rt_draw_boxes' boxes and this call's occluders: the one host definition) and whether a
+// frame has a sun term at all.  Plain C++ with no HIP include, so that tests/entity_shadows_main.cpp runs this very code on the CPU.
+// The comparisons are the kernels' (rt_tile_pass.hpp, box_valid): each is false for a NaN, so a record with a NaN fails.  (The
+// models' records are draw_stamps.hpp's, unchanged.)
 #pragma once
 
 #include <cmath>
@@ -24,18 +25,18 @@ inline const char* shadow_args_error(const void* u, const void* boxes, uint32_t 
     return nullptr;
 }
 
-// One occluder box, rt_draw_boxes' valid box: every float finite, |lo_k|, |hi_k| <= 2^22 and lo_k < hi_k.  material and emission
-// play no part.
-inline bool shadow_box_valid(const RtDrawBox& b) {
+// The valid RtDrawBox of rt_draw_boxes and rt_shadow_entities: every float finite, |lo_k|, |hi_k| <= 2^22 and lo_k < hi_k.  material
+// and emission play no part.
+inline bool draw_box_valid(const RtDrawBox& b) {
     for (int k = 0; k < 3; k++)
         if (!(std::fabs(b.lo[k]) <= 4194304.0f && std::fabs(b.hi[k]) <= 4194304.0f && b.lo[k] < b.hi[k])) return false;
     return true;
 }
 
 // The index of the first invalid box of a batch, or `count` when every one is valid.
-inline uint32_t first_invalid_shadow_box(const RtDrawBox* boxes, uint32_t count) {
+inline uint32_t first_invalid_draw_box(const RtDrawBox* boxes, uint32_t count) {
     for (uint32_t i = 0; i < count; i++)
-        if (!shadow_box_valid(boxes[i])) return i;
+        if (!draw_box_valid(boxes[i])) return i;
     return count;
 }
 

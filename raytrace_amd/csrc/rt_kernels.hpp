@@ -3,9 +3,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "rt_device.hpp"
 
 namespace rtd {
+
+// The launch of a kernel template over <LOGR, LRZ> for a frame's region: launch(L, Z) with decltype(L)::value = f.logr (8, 9 or 10;
+// the caller has checked the range) and decltype(Z)::value = (f.lr_zero != 0).
+template <typename Launch>
+void launch_for_region(const Frame& f, Launch&& launch) {
+    auto with = [&](auto L) {
+        if (f.lr_zero != 0) launch(L, std::true_type{});
+        else launch(L, std::false_type{});
+    };
+    if (f.logr == 8) with(std::integral_constant<int, 8>{});
+    else if (f.logr == 9) with(std::integral_constant<int, 9>{});
+    else with(std::integral_constant<int, 10>{});
+}
 
 // SoA ray queue + per-path hit/state arrays, all in HBM (sizes in elements; cap = paths per batch).
 //   queue : origin qo*[cap] shared by the pair, directions qd*[2*cap] (shadow at slot, diffuse at cap+slot), qid[cap] = path

@@ -2,13 +2,13 @@
 // last, each through one hard shadow ray per (pixel, light) (include/rt_abi.h "Point lights"; the rules are restated, without a cull,
 // in tests/point_light_ref.py).
 //
-//   k_add_lights : one wave64 owns one 8x8 pixel tile, a workgroup four tiles.  A lane rebuilds the surface point P' of its pixel from
-//                  the depth and normal planes; a tile without a surface pixel ends.  The wave reduces the per-axis bounds of its lanes'
-//                  P'.  Per batch of 64 lights lane l loads light base + l (two 16-byte loads), tests its validity and its sphere against
-//                  the tile's bounds (light_may_reach_tile); __ballot makes the candidates a 64-bit mask, and for each set bit the record is
-//                  broadcast with v_readlane and every lane runs the exact test with scalar light operands.  Lanes that pass step the
-//                  shadow ray with the shared DDA of rt_dda.hpp (DIRECT: minefield bytes straight from the swizzled array, as k_query)
-//                  and test between two steps whether the ray has reached the light.  No LDS, no atomics.
+//   k_add_lights : a tile pass (rt_tile_pass.hpp).  A lane rebuilds the surface point P' of its pixel from the depth and normal planes
+//                  (surface_point); a tile without a surface pixel ends.  The wave reduces the per-axis bounds of its lanes' P'
+//                  (tile_point_bounds).  Per batch of 64 lights lane l loads light base + l (two 16-byte loads), tests its validity and
+//                  its sphere against the tile's bounds (light_may_reach_tile); for each candidate every lane runs the exact test with
+//                  scalar light operands.  Lanes that pass step the shadow ray with the shared DDA of rt_dda.hpp (DIRECT: minefield
+//                  bytes straight from the swizzled array, as k_query) and test between two steps whether the ray has reached the
+//                  light.  No LDS, no atomics.
 //
 // All arithmetic that decides a pixel is fp32 with one rounding per operation (-ffp-contract=off).  The cull drops a light only where
 // the exact test skips it at every pixel of the tile; it needs no margin (DESIGN.md "Point lights"): it repeats the exact test's own
@@ -16,25 +16,22 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_dda.hpp"
-#include "rt_kernels.hpp"
+#include "rt_tile_pass.hpp"
 
 namespace rtd {
 
 namespace {
 
-constexpr uint32_t kLightsWg = 256;
-constexpr float kLightMaxCoord = 4194304.0f;   // 2^22
 constexpr float kLightMaxRadius = 1024.0f;
 constexpr float kLightMaxColor = 1048576.0f;   // 2^20
-constexpr float kFinite = 3.0e38f;
 
 // The contract's valid light (every comparison is false for a NaN).
 __device__ __forceinline__ bool light_valid(uint4 w0, uint4 w1) {
-    const float p[3] = {__uint_as_float(w0.x), __uint_as_float(w0.y), __uint_as_float(w0.z)};
-    const float c[3] = {__uint_as_float(w1.x), __uint_as_float(w1.y), __uint_as_float(w1.z)};
+    float p[3], c[3];
+    rec_xyz(w0, p); rec_xyz(w1, c);
     const float radius = __uint_as_float(w0.w);
     bool ok = radius > 0.0f && radius <= kLightMaxRadius && w1.w == 0u;
-    for (int k = 0; k < 3; k++) ok = ok && rtm_abs(p[k]) <= kLightMaxCoord && c[k] >= 0.0f && c[k] <= kLightMaxColor;
+    for (int k = 0; k < 3; k++) ok = ok && rtm_abs(p[k]) <= kPassMaxCoord && c[k] >= 0.0f && c[k] <= kLightMaxColor;
     return ok;
 }
 
@@ -54,44 +51,24 @@ __device__ __forceinline__ bool light_may_reach_tile(const float pos[3], float r
 }
 
 template <int LOGR, bool LRZ>
-__global__ __launch_bounds__(kLightsWg) void k_add_lights(Scene sc, Frame f, Planes pl, LightsArgs a) {
+__global__ __launch_bounds__(kTileWg) void k_add_lights(Scene sc, Frame f, Planes pl, LightsArgs a) {
     constexpr int R = 1 << LOGR, LB = LOGR - 2;
     constexpr float half = (float)(R / 2);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t tile = blockIdx.x * (kLightsWg / 64u) + (threadIdx.x >> 6);
-    const uint32_t tiles_x = ((uint32_t)f.width + 7u) / 8u, tiles_y = ((uint32_t)f.height + 7u) / 8u;
-    if (tile >= tiles_x * tiles_y) return;   // (a whole wave: the kernel has no barrier)
-    const int px = (int)(tile % tiles_x) * 8 + (int)(lane & 7u), py = (int)(tile / tiles_x) * 8 + (int)(lane >> 3);
-    const bool inside = px < f.width && py < f.height;
-    const size_t pix = (size_t)py * (size_t)f.width + (size_t)px;
+    const TileLane tl(f.width, f.height);
+    if (!tl.live) return;
+    const size_t pix = tl.pix;
 
-    const uint32_t normal = inside ? (uint32_t)pl.normal_r8[pix] : 255u;
-    const float depth = inside ? pl.depth_f32[pix] : 65535.0f;
+    const uint32_t normal = tl.inside ? (uint32_t)pl.normal_r8[pix] : 255u;
+    const float depth = tl.inside ? pl.depth_f32[pix] : 65535.0f;
     const bool surface = normal < 6u && depth < 65535.0f;   // (false for a NaN depth)
     if (__ballot(surface) == 0ull) return;
 
-    // ---- the surface point P' of this lane's pixel ----
-    const float sx = ((float)px / (float)f.width) * 2.0f - 1.0f;
-    const float sy = ((float)py / (float)f.height) * 2.0f - 1.0f;
-    const vec3 dv = vnormalize(vadd(vadd(ld3(f.forward), vscale(ld3(f.right), sx)), vscale(ld3(f.up), sy)));
-    const float t = depth / 32.0f;
-    float P[3] = {rtm_fma(dv.x, t, f.origin[0]), rtm_fma(dv.y, t, f.origin[1]), rtm_fma(dv.z, t, f.origin[2])};
+    // ---- the surface point P' of this lane's pixel and the tile's bounds of it, the same in every lane ----
+    float P[3], lo[3], hi[3];
+    surface_point(f, tl.px, tl.py, depth, normal, P);
+    tile_point_bounds(surface, P, lo, hi);
     const uint32_t axis = (normal >> 1) & 3u;
     const bool even = (normal & 1u) == 0u;
-    const float off = even ? 0.03125f : -0.03125f;
-    if (axis == 0u) P[0] = P[0] + off; else if (axis == 1u) P[1] = P[1] + off; else P[2] = P[2] + off;
-
-    // ---- the tile's bounds, the same in every lane ----
-    const bool bounded = surface && rtm_abs(P[0]) <= kFinite && rtm_abs(P[1]) <= kFinite && rtm_abs(P[2]) <= kFinite;
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; k++) {
-        lo[k] = bounded ? P[k] : INFINITY;
-        hi[k] = bounded ? P[k] : -INFINITY;
-        for (int s = 32; s > 0; s >>= 1) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], s, 64));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], s, 64));
-        }
-    }
 
     // the first texel of every shadow ray of this pixel (trace_ray's fetch at its origin)
     int ix, iy, iz;
@@ -101,26 +78,23 @@ __global__ __launch_bounds__(kLightsWg) void k_add_lights(Scene sc, Frame f, Pla
     float add[3] = {0.0f, 0.0f, 0.0f};
     bool lit = false;
     for (uint32_t base = 0; base < a.count; base += 64u) {
-        const uint32_t mine = base + lane;
+        const uint32_t mine = base + tl.lane;
         uint4 w0 = make_uint4(0u, 0u, 0u, 0u), w1 = w0;
         bool keep = false;
         if (mine < a.count) {
             w0 = a.lights[2u * (size_t)mine];
             w1 = a.lights[2u * (size_t)mine + 1u];
-            const float pos[3] = {__uint_as_float(w0.x), __uint_as_float(w0.y), __uint_as_float(w0.z)};
+            float pos[3];
+            rec_xyz(w0, pos);
             keep = light_valid(w0, w1) && light_may_reach_tile(pos, __uint_as_float(w0.w), lo, hi);
         }
         unsigned long long cand = __ballot(keep);
         while (cand) {
             const int j = __builtin_ctzll(cand);
             cand &= cand - 1ull;
-            const float pos[3] = {__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)w0.x, j)),
-                                  __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)w0.y, j)),
-                                  __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)w0.z, j))};
-            const float radius = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)w0.w, j));
-            const float col[3] = {__uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)w1.x, j)),
-                                  __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)w1.y, j)),
-                                  __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)w1.z, j))};
+            float pos[3], col[3];
+            rec_xyz(w0, j, pos); rec_xyz(w1, j, col);
+            const float radius = __uint_as_float(bcast(w0.w, j));
             // the exact test of this lane's pixel
             const float v[3] = {pos[0] - P[0], pos[1] - P[1], pos[2] - P[2]};
             const float dist2 = rtm_dot3({v[0], v[1], v[2]}, {v[0], v[1], v[2]});
@@ -169,15 +143,8 @@ __global__ __launch_bounds__(kLightsWg) void k_add_lights(Scene sc, Frame f, Pla
 hipError_t launch_add_lights(const Scene& sc, const Frame& f, const Planes& pl, const LightsArgs& a, hipStream_t st) {
     if (f.logr < 8 || f.logr > 10) return hipErrorInvalidValue;
     if (a.count == 0u || f.width <= 0 || f.height <= 0) return hipSuccess;
-    const uint32_t tiles = (((uint32_t)f.width + 7u) / 8u) * (((uint32_t)f.height + 7u) / 8u);
-    const dim3 grid((tiles + kLightsWg / 64u - 1u) / (kLightsWg / 64u)), block(kLightsWg);
-    const bool lrz = f.lr_zero != 0;
-#define RT_LAUNCH_LIGHTS(L) do { if (lrz) hipLaunchKernelGGL((k_add_lights<L, true>), grid, block, 0, st, sc, f, pl, a); \
-                                 else hipLaunchKernelGGL((k_add_lights<L, false>), grid, block, 0, st, sc, f, pl, a); } while (0)
-    if (f.logr == 8) RT_LAUNCH_LIGHTS(8);
-    else if (f.logr == 9) RT_LAUNCH_LIGHTS(9);
-    else RT_LAUNCH_LIGHTS(10);
-#undef RT_LAUNCH_LIGHTS
+    const dim3 grid = TileLane::grid(f.width, f.height), block(kTileWg);
+    launch_for_region(f, [&](auto L, auto Z) { hipLaunchKernelGGL((k_add_lights<decltype(L)::value, decltype(Z)::value>), grid, block, 0, st, sc, f, pl, a); });
     return hipGetLastError();
 }
 

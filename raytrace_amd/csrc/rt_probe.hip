@@ -174,13 +174,7 @@ hipError_t launch_probe(const Scene& sc, const Frame& f, const ProbeArgs& a, boo
     if (!in_lds && !a.scratch) return hipErrorInvalidValue;
     const uint32_t npaths = a.count * a.samples;
     const dim3 grid((npaths + kProbeWg - 1u) / kProbeWg);
-    const bool lrz = f.lr_zero != 0;
-#define RT_LAUNCH_PROBE(L) do { if (lrz) probe_launch<L, true>(sc, f, a, pair, in_lds, grid, st); \
-                                else probe_launch<L, false>(sc, f, a, pair, in_lds, grid, st); } while (0)
-    if (f.logr == 8) RT_LAUNCH_PROBE(8);
-    else if (f.logr == 9) RT_LAUNCH_PROBE(9);
-    else RT_LAUNCH_PROBE(10);
-#undef RT_LAUNCH_PROBE
+    launch_for_region(f, [&](auto L, auto Z) { probe_launch<decltype(L)::value, decltype(Z)::value>(sc, f, a, pair, in_lds, grid, st); });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && !in_lds) {
         hipLaunchKernelGGL(k_probe_sum, dim3((a.count + kProbeWg - 1u) / kProbeWg), dim3(kProbeWg), 0, st, a);

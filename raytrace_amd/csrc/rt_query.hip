@@ -101,13 +101,7 @@ hipError_t launch_query(const Scene& sc, const Frame& f, const QueryArgs& a, hip
     if (f.logr < 8 || f.logr > 10) return hipErrorInvalidValue;
     if (a.count == 0u) return hipSuccess;
     const dim3 grid((a.count + kQueryWg - 1u) / kQueryWg), block(kQueryWg);
-    const bool lrz = f.lr_zero != 0;
-#define RT_LAUNCH_QUERY(L) do { if (lrz) hipLaunchKernelGGL((k_query<L, true>), grid, block, 0, st, sc, f, a); \
-                                else hipLaunchKernelGGL((k_query<L, false>), grid, block, 0, st, sc, f, a); } while (0)
-    if (f.logr == 8) RT_LAUNCH_QUERY(8);
-    else if (f.logr == 9) RT_LAUNCH_QUERY(9);
-    else RT_LAUNCH_QUERY(10);
-#undef RT_LAUNCH_QUERY
+    launch_for_region(f, [&](auto L, auto Z) { hipLaunchKernelGGL((k_query<decltype(L)::value, decltype(Z)::value>), grid, block, 0, st, sc, f, a); });
     return hipGetLastError();
 }
 

@@ -2,12 +2,12 @@
 // voxel models) take the sun's direct term out of the two lighting planes of the frame drawn last, at the pixels they shade
 // (include/rt_abi.h "Entity shadows"; the rules are restated, without a cull, in tests/entity_shadow_ref.py).
 //
-//   k_shadow_entities : k_add_lights' shape: one wave64 owns one 8x8 pixel tile, a workgroup four tiles.  A lane rebuilds the surface
-//                       point P' of its pixel from the depth and normal planes; a tile without a surface pixel ends.  The wave reduces
-//                       the per-axis bounds of its lanes' P'.  Boxes, then model records, are taken 64 at a time: lane l loads record
-//                       base + l and tests it against the tile's bounds (sun_may_cross_tile); __ballot makes the candidates a 64-bit
-//                       mask, and for each set bit the record is broadcast with v_readlane and every lane not yet shaded runs the
-//                       exact slab test of its sun ray with scalar box operands — and, for a model, the walk of the model's cells.
+//   k_shadow_entities : a tile pass (rt_tile_pass.hpp), k_add_lights' shape.  A lane rebuilds the surface point P' of its pixel from
+//                       the depth and normal planes (surface_point); a tile without a surface pixel ends.  The wave reduces the
+//                       per-axis bounds of its lanes' P' (tile_point_bounds).  Boxes, then model records, are taken 64 at a time:
+//                       lane l loads record base + l and tests it against the tile's bounds (sun_may_cross_tile); for each
+//                       candidate every lane not yet shaded runs the exact slab test of its sun ray (slab_core) with scalar box
+//                       operands — and, for a model, the walk of the model's cells.
 //                       Shading is a boolean OR: a lane stops testing once it is shaded, the wave once every surface lane is.  Lanes
 //                       shaded at the end step the world's sun ray with the shared DDA of rt_dda.hpp (DIRECT, as k_add_lights and
 //                       k_query) and, where it leaves the window, subtract the sun term.  No LDS, no atomics.
@@ -17,37 +17,25 @@
 // same direction, so the cull repeats the exact test's own operations — a difference, a product with the one reciprocal — on
 // operands that bound every pixel's, and each of those operations is monotone.
 //
-// The walk of a model's cells is k_draw_stamps' without its (t, axis) bookkeeping and with a second way to its first cell.  It is a
-// second copy on purpose: k_draw_stamps' loop carries t and the axis through every step, so a shared body would be that loop with
-// both compiled in or out, and k_draw_stamps stays byte for byte what its recorded resources describe.
+// The walk of a model's cells shares with k_draw_stamps' what both start from — the record's decode (model_rec) and the slab test
+// (slab_core) — and stays a loop of its own on purpose: k_draw_stamps' carries t and the entry axis through every step and this one
+// does not, and it has a second way to its first cell.  A shared body would be that loop with the bookkeeping compiled in or out,
+// and each kernel would pay for the other's state.
 #include <hip/hip_runtime.h>
 
-#include "../../include/rt_abi.h"
 #include "rt_dda.hpp"
-#include "rt_kernels.hpp"
+#include "rt_tile_pass.hpp"
 
 namespace rtd {
 
 namespace {
 
-constexpr uint32_t kShadowsWg = 256;
-constexpr float kShadowMaxCoord = 4194304.0f;   // 2^22
-constexpr float kFinite = 3.0e38f;
-
-__device__ __forceinline__ uint32_t bcast(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-
-// rt_draw_boxes' valid box (every comparison is false for a NaN)
-__device__ __forceinline__ bool box_valid(const float lo[3], const float hi[3]) {
-    bool ok = true;
-    for (int k = 0; k < 3; k++) ok = ok && rtm_abs(lo[k]) <= kShadowMaxCoord && rtm_abs(hi[k]) <= kShadowMaxCoord && lo[k] < hi[k];
-    return ok;
-}
-
-// What the cull knows of the sun's direction, the same in every lane: per axis whether the direction is zero there and whether its
-// reciprocal is a number the cull can multiply by (the reciprocal of a denormal is inf: such an axis bounds nothing in the cull).
+// What the kernel knows of the sun's direction, the same in every lane: per axis whether the direction is not zero there (slab_core's
+// `nonzero`) and whether its reciprocal is a number the cull can multiply by (the reciprocal of a denormal is inf: such an axis
+// bounds nothing in the cull).
 struct SunDir {
     float s[3], inv[3];
-    bool zero[3], use[3];
+    bool nonzero[3], use[3];
 };
 
 // Conservative: false only when the exact test below fails for every pixel of the tile whose P' lies in [blo, bhi].  For such a
@@ -60,7 +48,7 @@ __device__ __forceinline__ bool sun_may_cross_tile(const float lo[3], const floa
     bool have = false;
     float tn_max = 0.0f, tf_min = 0.0f;
     for (int k = 0; k < 3; k++) {
-        if (sd.zero[k]) {
+        if (!sd.nonzero[k]) {
             if (hi[k] <= blo[k] || lo[k] >= bhi[k]) return false;   // no pixel has lo_k < o_k < hi_k
             continue;
         }
@@ -75,78 +63,32 @@ __device__ __forceinline__ bool sun_may_cross_tile(const float lo[3], const floa
     return !(tn_max >= tf_min || tf_min <= 0.0f);
 }
 
-// The slab test of the sun ray (o = P', direction s, inv = 1.0f / s per component) against [lo, hi], rt_draw_boxes' replacement rules:
-// does the ray's line cross the box at all — some axis bounds it and every zero-direction axis passes — and then t_in, t_out and
-// the entry axis.
-__device__ __forceinline__ bool sun_box_slab(const float lo[3], const float hi[3], const float o[3], const SunDir& sd, float* t_in_out,
-                                             float* t_out_out, uint32_t* axis_out) {
-    bool bounded = false, miss = false;
-    float t_in = 0.0f, t_out = 0.0f;
-    uint32_t axis = 0u;
-    for (int k = 0; k < 3; k++) {
-        if (!sd.zero[k]) {
-            const float t0 = (lo[k] - o[k]) * sd.inv[k], t1 = (hi[k] - o[k]) * sd.inv[k];
-            const float tn = rtm_min(t0, t1), tf = rtm_max(t0, t1);
-            if (!bounded) { t_in = tn; t_out = tf; axis = (uint32_t)k; bounded = true; }
-            else {
-                if (tn > t_in) { t_in = tn; axis = (uint32_t)k; }
-                if (tf < t_out) t_out = tf;
-            }
-        } else if (!(lo[k] < o[k] && o[k] < hi[k])) {
-            miss = true;
-        }
-    }
-    *t_in_out = t_in; *t_out_out = t_out; *axis_out = axis;
-    return bounded && !miss;
-}
-
 template <int LOGR, bool LRZ>
-__global__ __launch_bounds__(kShadowsWg) void k_shadow_entities(Scene sc, Frame f, Planes pl, ShadowArgs a) {
+__global__ __launch_bounds__(kTileWg) void k_shadow_entities(Scene sc, Frame f, Planes pl, ShadowArgs a) {
     constexpr int R = 1 << LOGR, LB = LOGR - 2;
     constexpr float half = (float)(R / 2);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t tile = blockIdx.x * (kShadowsWg / 64u) + (threadIdx.x >> 6);
-    const uint32_t tiles_x = ((uint32_t)f.width + 7u) / 8u, tiles_y = ((uint32_t)f.height + 7u) / 8u;
-    if (tile >= tiles_x * tiles_y) return;   // (a whole wave: the kernel has no barrier)
-    const int px = (int)(tile % tiles_x) * 8 + (int)(lane & 7u), py = (int)(tile / tiles_x) * 8 + (int)(lane >> 3);
-    const bool inside = px < f.width && py < f.height;
-    const size_t pix = (size_t)py * (size_t)f.width + (size_t)px;
+    const TileLane tl(f.width, f.height);
+    if (!tl.live) return;
+    const uint32_t lane = tl.lane;
+    const size_t pix = tl.pix;
 
-    const uint32_t normal = inside ? (uint32_t)pl.normal_r8[pix] : 255u;
-    const float depth = inside ? pl.depth_f32[pix] : 65535.0f;
+    const uint32_t normal = tl.inside ? (uint32_t)pl.normal_r8[pix] : 255u;
+    const float depth = tl.inside ? pl.depth_f32[pix] : 65535.0f;
     const bool surface = normal < 6u && depth < 65535.0f;   // (false for a NaN depth)
     if (__ballot(surface) == 0ull) return;
 
-    // ---- the surface point P' of this lane's pixel (k_add_lights') ----
-    const float sx = ((float)px / (float)f.width) * 2.0f - 1.0f;
-    const float sy = ((float)py / (float)f.height) * 2.0f - 1.0f;
-    const vec3 dv = vnormalize(vadd(vadd(ld3(f.forward), vscale(ld3(f.right), sx)), vscale(ld3(f.up), sy)));
-    const float tp = depth / 32.0f;
-    float P[3] = {rtm_fma(dv.x, tp, f.origin[0]), rtm_fma(dv.y, tp, f.origin[1]), rtm_fma(dv.z, tp, f.origin[2])};
-    {
-        const uint32_t axis = (normal >> 1) & 3u;
-        const float off = (normal & 1u) == 0u ? 0.03125f : -0.03125f;
-        if (axis == 0u) P[0] = P[0] + off; else if (axis == 1u) P[1] = P[1] + off; else P[2] = P[2] + off;
-    }
-
-    // ---- the tile's bounds, the same in every lane; a surface pixel whose P' is not finite switches the cull off for its tile ----
-    const bool bounded = surface && rtm_abs(P[0]) <= kFinite && rtm_abs(P[1]) <= kFinite && rtm_abs(P[2]) <= kFinite;
+    // ---- the surface point P' of this lane's pixel and the tile's bounds of it, the same in every lane; a surface pixel whose P' is
+    // not finite switches the cull off for its tile ----
+    float P[3], blo[3], bhi[3];
+    surface_point(f, tl.px, tl.py, depth, normal, P);
+    const bool bounded = tile_point_bounds(surface, P, blo, bhi);
     const bool cull = __ballot(surface && !bounded) == 0ull;
-    float blo[3], bhi[3];
-    for (int k = 0; k < 3; k++) {
-        blo[k] = bounded ? P[k] : INFINITY;
-        bhi[k] = bounded ? P[k] : -INFINITY;
-        for (int s = 32; s > 0; s >>= 1) {
-            blo[k] = fminf(blo[k], __shfl_xor(blo[k], s, 64));
-            bhi[k] = fmaxf(bhi[k], __shfl_xor(bhi[k], s, 64));
-        }
-    }
 
     SunDir sd;
     for (int k = 0; k < 3; k++) {
         sd.s[k] = f.sunangle[k];
         sd.inv[k] = 1.0f / sd.s[k];
-        sd.zero[k] = !(sd.s[k] != 0.0f);   // (the slab test's `d_k != 0`: a NaN direction takes the bounded branch)
+        sd.nonzero[k] = sd.s[k] != 0.0f;   // (the slab test's `d_k != 0`: a NaN direction takes the bounded branch)
         sd.use[k] = rtm_abs(sd.inv[k]) <= kFinite && (sd.s[k] > 0.0f || sd.s[k] < 0.0f);
     }
 
@@ -161,19 +103,19 @@ __global__ __launch_bounds__(kShadowsWg) void k_shadow_entities(Scene sc, Frame 
         if (mine < a.nboxes) {
             w0 = a.boxes[2u * (size_t)mine];
             w1 = a.boxes[2u * (size_t)mine + 1u];
-            const float lo[3] = {__uint_as_float(w0.x), __uint_as_float(w0.y), __uint_as_float(w0.z)};
-            const float hi[3] = {__uint_as_float(w1.x), __uint_as_float(w1.y), __uint_as_float(w1.z)};
+            float lo[3], hi[3];
+            rec_xyz(w0, lo); rec_xyz(w1, hi);
             keep = box_valid(lo, hi) && (!cull || sun_may_cross_tile(lo, hi, sd, blo, bhi));
         }
         unsigned long long cand = __ballot(keep);
         while (cand) {
             const int j = __builtin_ctzll(cand);
             cand &= cand - 1ull;
-            const float lo[3] = {__uint_as_float(bcast(w0.x, j)), __uint_as_float(bcast(w0.y, j)), __uint_as_float(bcast(w0.z, j))};
-            const float hi[3] = {__uint_as_float(bcast(w1.x, j)), __uint_as_float(bcast(w1.y, j)), __uint_as_float(bcast(w1.z, j))};
+            float lo[3], hi[3];
+            rec_xyz(w0, j, lo); rec_xyz(w1, j, hi);
             float t_in, t_out;
             uint32_t axis;
-            const bool crosses = sun_box_slab(lo, hi, P, sd, &t_in, &t_out, &axis);
+            const bool crosses = slab_core(lo, hi, P, sd.nonzero, sd.inv, &t_in, &t_out, &axis);
             if (need && crosses && t_out > 0.0f && t_in < t_out) { shaded = true; need = false; }
             if (__ballot(need) == 0ull) break;
         }
@@ -189,42 +131,40 @@ __global__ __launch_bounds__(kShadowsWg) void k_shadow_entities(Scene sc, Frame 
             w1 = a.recs[4u * (size_t)mine + 1u];
             w2 = a.recs[4u * (size_t)mine + 2u];
             w3 = a.recs[4u * (size_t)mine + 3u];
-            const float lo[3] = {__uint_as_float(w2.x), __uint_as_float(w2.y), __uint_as_float(w2.z)};
-            const float hi[3] = {__uint_as_float(w3.x), __uint_as_float(w3.y), __uint_as_float(w3.z)};
+            float lo[3], hi[3];
+            rec_xyz(w2, lo); rec_xyz(w3, hi);
             keep = !cull || sun_may_cross_tile(lo, hi, sd, blo, bhi);
         }
         unsigned long long cand = __ballot(keep);
         while (cand) {
             const int j = __builtin_ctzll(cand);
             cand &= cand - 1ull;
-            const float lo[3] = {__uint_as_float(bcast(w2.x, j)), __uint_as_float(bcast(w2.y, j)), __uint_as_float(bcast(w2.z, j))};
-            const float hi[3] = {__uint_as_float(bcast(w3.x, j)), __uint_as_float(bcast(w3.y, j)), __uint_as_float(bcast(w3.z, j))};
+            float lo[3], hi[3];
+            rec_xyz(w2, j, lo); rec_xyz(w3, j, hi);
             float t_in, t_out;
             uint32_t axis;
-            const bool crosses = sun_box_slab(lo, hi, P, sd, &t_in, &t_out, &axis);
+            const bool crosses = slab_core(lo, hi, P, sd.nonzero, sd.inv, &t_in, &t_out, &axis);
             if (need && crosses && t_out > 0.0f && t_in < t_out) {
-                // ---- the walk of this lane's sun ray through the model's cells ----
-                const float scale = __uint_as_float(bcast(w2.w, j));
-                const uint8_t* state = reinterpret_cast<const uint8_t*>((uint64_t)bcast(w0.z, j) | ((uint64_t)bcast(w0.w, j) << 32));
-                const uint32_t se0 = bcast(w1.y, j), se1 = bcast(w1.z, j), se2 = bcast(w1.w, j);
-                const int ex = (int)((se0 >> 18) & 0xFFu) + 1, ey = (int)((se1 >> 18) & 0xFFu) + 1, ez = (int)((se2 >> 18) & 0xFFu) + 1;
-                const int stx = (int)(se0 << 14) >> 14, sty = (int)(se1 << 14) >> 14, stz = (int)(se2 << 14) >> 14;
+                // ---- the walk of this lane's sun ray through the model's cells (its twin, with t and the axis: rt_draw_stamps.hip) ----
+                const ModelRec m = model_rec(w0, w1, w2, j);
+                const float scale = m.scale;
+                const uint8_t* state = m.state;
+                const int ex = m.ext[0], ey = m.ext[1], ez = m.ext[2], stx = m.stride[0], sty = m.stride[1], stz = m.stride[2];
                 // the first cell: entered from outside (t_in > 0), the entry axis' first or last layer and elsewhere where the entry
                 // point lies; started inside, where P' lies on every axis
                 const bool outside = t_in > 0.0f;
                 int c[3];
-                const int ext[3] = {ex, ey, ez};
                 for (int k = 0; k < 3; k++) {
                     const float p = (!outside || sd.s[k] == 0.0f) ? P[k] : rtm_fma(sd.s[k], t_in, P[k]);
-                    const float q = rtm_floor((p - lo[k]) / scale), qmax = (float)(ext[k] - 1);   // clamped as a float: the same cell
+                    const float q = rtm_floor((p - lo[k]) / scale), qmax = (float)(m.ext[k] - 1);   // clamped as a float: the same cell
                     const int ck = (int)(!(q > 0.0f) ? 0.0f : (q > qmax ? qmax : q));
-                    c[k] = (outside && (uint32_t)k == axis) ? (sd.s[k] > 0.0f ? 0 : ext[k] - 1) : ck;
+                    c[k] = (outside && (uint32_t)k == axis) ? (sd.s[k] > 0.0f ? 0 : m.ext[k] - 1) : ck;
                 }
                 int cx = c[0], cy = c[1], cz = c[2];
                 const int dcx = sd.s[0] > 0.0f ? 1 : -1, dcy = sd.s[1] > 0.0f ? 1 : -1, dcz = sd.s[2] > 0.0f ? 1 : -1;
                 const int ox = sd.s[0] > 0.0f ? 1 : 0, oy = sd.s[1] > 0.0f ? 1 : 0, oz = sd.s[2] > 0.0f ? 1 : 0;
                 const bool gx = sd.s[0] != 0.0f, gy = sd.s[1] != 0.0f, gz = sd.s[2] != 0.0f;
-                int voxel = (int)bcast(w1.x, j) + stx * cx + sty * cy + stz * cz;
+                int voxel = m.base + stx * cx + sty * cy + stz * cz;
                 bool found = false;
                 for (int n = ex + ey + ez; n > 0; n--) {   // (every step moves one coordinate the ray's way: at most E'x + E'y + E'z)
                     if (state[voxel] == RT_STAMP_SOLID) { found = true; break; }
@@ -285,15 +225,8 @@ __global__ __launch_bounds__(kShadowsWg) void k_shadow_entities(Scene sc, Frame 
 hipError_t launch_shadow_entities(const Scene& sc, const Frame& f, const Planes& pl, const ShadowArgs& a, hipStream_t st) {
     if (f.logr < 8 || f.logr > 10) return hipErrorInvalidValue;
     if ((a.nboxes == 0u && a.nmodels == 0u) || f.width <= 0 || f.height <= 0) return hipSuccess;
-    const uint32_t tiles = (((uint32_t)f.width + 7u) / 8u) * (((uint32_t)f.height + 7u) / 8u);
-    const dim3 grid((tiles + kShadowsWg / 64u - 1u) / (kShadowsWg / 64u)), block(kShadowsWg);
-    const bool lrz = f.lr_zero != 0;
-#define RT_LAUNCH_SHADOWS(L) do { if (lrz) hipLaunchKernelGGL((k_shadow_entities<L, true>), grid, block, 0, st, sc, f, pl, a); \
-                                  else hipLaunchKernelGGL((k_shadow_entities<L, false>), grid, block, 0, st, sc, f, pl, a); } while (0)
-    if (f.logr == 8) RT_LAUNCH_SHADOWS(8);
-    else if (f.logr == 9) RT_LAUNCH_SHADOWS(9);
-    else RT_LAUNCH_SHADOWS(10);
-#undef RT_LAUNCH_SHADOWS
+    const dim3 grid = TileLane::grid(f.width, f.height), block(kTileWg);
+    launch_for_region(f, [&](auto L, auto Z) { hipLaunchKernelGGL((k_shadow_entities<decltype(L)::value, decltype(Z)::value>), grid, block, 0, st, sc, f, pl, a); });
     return hipGetLastError();
 }
 

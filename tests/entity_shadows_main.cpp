@@ -60,7 +60,7 @@ void check_box(const RtDrawBox& b) {
     g_cases++;
     const bool want = model_box_valid(b);
     g_valid += want;
-    CHECK(rta::shadow_box_valid(b) == want, "lo %g %g %g hi %g %g %g: model says %d", b.lo[0], b.lo[1], b.lo[2], b.hi[0], b.hi[1], b.hi[2], (int)want);
+    CHECK(rta::draw_box_valid(b) == want, "lo %g %g %g hi %g %g %g: model says %d", b.lo[0], b.lo[1], b.lo[2], b.hi[0], b.hi[1], b.hi[2], (int)want);
 }
 
 float* field(RtDrawBox& b, int f) { return f < 3 ? &b.lo[f] : &b.hi[f - 3]; }
@@ -100,7 +100,7 @@ int main() {
                                  std::nextafter(-4194304.0f, -inf), std::nextafter(4194304.0f, 0.0f), std::nextafter(-4194304.0f, 0.0f), big, -big, inf,
                                  -inf, nan, -nan};
     check_box(good());
-    CHECK(rta::shadow_box_valid(good()), "the plain box is valid");
+    CHECK(rta::draw_box_valid(good()), "the plain box is valid");
     for (int f = 0; f < 6; f++)
         for (float v : probes) {
             RtDrawBox b = good();
@@ -123,7 +123,7 @@ int main() {
         RtDrawBox b = good();
         b.material = 0xFFFFFFFFu; b.emission = 0u;
         check_box(b);
-        CHECK(rta::shadow_box_valid(b), "material and emission are not looked at");
+        CHECK(rta::draw_box_valid(b), "material and emission are not looked at");
     }
     Rng rng{0x9E3779B97F4A7C15ull};
     for (int i = 0; i < 200000; i++) {   // random bit patterns in every float field: every class of float turns up
@@ -137,16 +137,16 @@ int main() {
     // ---- batches: the first invalid box at every position, and none ----
     for (uint32_t n : {0u, 1u, 2u, 63u, 64u, 65u, 4096u}) {
         std::vector<RtDrawBox> batch(n, good());
-        CHECK(rta::first_invalid_shadow_box(batch.data(), n) == n, "a batch of %u valid boxes", n);
+        CHECK(rta::first_invalid_draw_box(batch.data(), n) == n, "a batch of %u valid boxes", n);
         for (uint32_t bad = 0; bad < n; bad += (n > 70u ? 389u : 1u)) {
             std::vector<RtDrawBox> b = batch;
             b[bad].hi[1] = b[bad].lo[1];
             if (bad + 1u < n) b[n - 1u].lo[2] = nan;
-            CHECK(rta::first_invalid_shadow_box(b.data(), n) == bad, "batch of %u, first invalid at %u", n, bad);
+            CHECK(rta::first_invalid_draw_box(b.data(), n) == bad, "batch of %u, first invalid at %u", n, bad);
             g_cases++;
         }
     }
-    CHECK(rta::first_invalid_shadow_box(nullptr, 0) == 0, "an empty batch reads nothing");
+    CHECK(rta::first_invalid_draw_box(nullptr, 0) == 0, "an empty batch reads nothing");
 
     // ---- night ----
     {

@@ -14,6 +14,7 @@ from oracle import pyoracle as po
 from raytrace_amd import _lib, abi, render
 from tests import draw_boxes_ref as boxes_ref
 from tests import draw_stamps_ref as ref
+from tests import entity_shadow_ref as shadow_ref
 from tests import stamp_edits as se
 
 pytestmark = pytest.mark.gpu
@@ -442,6 +443,96 @@ def test_stamp_destroy_straight_after_an_async_draw(frame_ctx):
     assert _code(ctx.draw_stamps, u, models, lights) == abi.RT_ERR_INVALID_ARG
     for s in fill:
         ctx.stamp_destroy(s)
+
+
+# ---- rt_draw_stamps and rt_shadow_entities take turns over the same two staging sets --------------------------------------------------------
+class _DevBytes:
+    """Zero-copy view of device memory for torch.as_tensor (CUDA array interface v2)."""
+
+    def __init__(self, ptr, nbytes):
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+
+
+def _planes(copies):
+    """The numpy planes of device copies made by test_draws_and_shadows_alternate_over_the_staging_sets."""
+    W, H = 60, 36
+    out = {}
+    for b, t in copies.items():
+        dt, ch = abi.BUFFER_FORMATS[b]
+        out[abi.BUFFER_NAMES[b]] = t.cpu().numpy().view(dt).reshape((H, W, ch) if ch > 1 else (H, W))
+    return out
+
+
+def test_draws_and_shadows_alternate_over_the_staging_sets(procedural_region, blue_noise):
+    """draw (3 models), shadows (1100: more than the 1024 records of a set's first 64 KiB, so the set grows while its twin's launch is
+    still queued), draw (5), shadows (2) on one stream with no host sync in between — each step's planes are copied on that stream,
+    device to device — against the same calls made synchronously, one by one, on a second context.  60 x 36: edge tiles on both axes."""
+    W, H = 60, 36
+    u = _u()
+    specs = [((1, 1, 1), 41, 1.0), ((3, 2, 2), 42, 1.0)]                   # both solid: a ray through a model's centre hits it
+    with _ctx(procedural_region, blue_noise, W, H, spp=1, depth=2) as ctx, _ctx(procedural_region, blue_noise, W, H, spp=1, depth=2) as twin:
+        stamps = make_stamps(ctx, specs)
+        assert sorted(make_stamps(twin, specs)) == sorted(stamps)           # (fresh contexts hand out the same ids)
+        ids = np.array(sorted(stamps), dtype=np.uint32)
+        # where models surely show or shade: halfway to a surface pixel, and eight units up the sun's line from a sunlit one
+        before = _fresh_frame(twin, u)
+        surface, P, axis, even = shadow_ref.surface_points(before, u, W, H)
+        sun = shadow_ref.sun_of(u)[0].astype(np.float64)
+        lit = np.zeros(surface.shape, dtype=bool)
+        lit[surface] = shadow_ref.trace_kind(procedural_region[1], 256, (0, 0, 0), P[surface], shadow_ref.sun_of(u)[0]) == shadow_ref.AIR
+        ys, xs = np.nonzero(lit & (axis == 2) & even)
+        assert len(ys) >= 8
+        near = np.argsort(before["depth_f32"][ys, xs], kind="stable")
+        sunlit = P[ys[near], xs[near]].astype(np.float64)
+        eye = np.array(u.origin[:], dtype=np.float64)
+
+        def placed(centres, scale):
+            which = np.arange(len(centres)) % 2
+            half = 0.5 * scale * np.array([specs[k][0] for k in which], dtype=np.float64)
+            return render.make_draw_stamps(ids[which], np.asarray(centres) - half, scale, 0, 0xFF102030)
+
+        # 1100 models: a coarse lattice through the region, which mostly misses every tile's sun rays and is culled, and two that shade
+        g = np.stack(np.meshgrid(*([np.arange(-120.0, 121.0, 24.0)] * 3), indexing="ij"), axis=-1).reshape(-1, 3)
+        many = placed(np.concatenate([g[:1098], sunlit[[0, len(sunlit) // 2]] + 8.0 * sun]), 2.5)
+        assert len(many) == 1100
+        steps = [("draw", placed(eye + 0.5 * (sunlit[[1, 3, 5]] - eye), 1.0), some_lights(3, seed=1)), ("shade", many, None),
+                 ("draw", placed(eye + 0.5 * (sunlit[[0, 2, 4, 6, 7]] - eye), 1.0), some_lights(5, seed=2)),
+                 ("shade", placed(sunlit[[len(sunlit) // 3, 2]][::-1] + 8.0 * sun, 2.5), None)]
+        # the same calls, synchronously
+        want = []
+        for kind, models, lights in steps:
+            before = _fresh_frame(twin, u)
+            if kind == "draw":
+                twin.draw_stamps(u, models, lights)
+            else:
+                twin.shadow_entities(u, None, models)
+            want.append(_all(twin))
+            assert any(want[-1][k].tobytes() != before[k].tobytes() for k in before), "the step changes the frame"
+        # ... and asynchronously on a caller's stream, nothing waited for until the last call has returned
+        s = torch.cuda.Stream()
+        d_lights = [None if lights is None else _dev(lights) for _, _, lights in steps]
+        torch.cuda.synchronize()
+        ctx.set_stream(s.cuda_stream)
+        try:
+            copies = []
+            for (kind, models, _), d in zip(steps, d_lights):
+                ctx.draw_frame(u)
+                if kind == "draw":
+                    ctx.draw_stamps_async(u, models, d)
+                else:
+                    ctx.shadow_entities_async(u, None, models)
+                with torch.cuda.stream(s):
+                    copies.append({b: torch.as_tensor(_DevBytes(ctx.device_ptr(b), ctx.buffer_bytes(b)), device="cuda").clone()
+                                   for b in range(abi.RT_BUF_COUNT)})
+            ctx.stamp_destroy(int(ids[1]))                                  # waits for the calls that read the stamp
+            fill = ctx.stamp_create(*stamp_arrays((12, 12, 12), 95, 1.0))   # what reuses the freed memory is not seen
+            s.synchronize()
+            for k, (got, w) in enumerate(zip(copies, want)):
+                _assert_same(_planes(got), w, "step %d" % k)
+            _assert_same(_all(ctx), want[-1], "after the destroy")
+            ctx.stamp_destroy(fill)
+        finally:
+            ctx.set_stream(0)
 
 
 # ---- no leak into the next frame ------------------------------------------------------------------------------------------------------
