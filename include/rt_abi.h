@@ -886,6 +886,77 @@ int rt_shadow_entities(RtContext* ctx, const RtUniforms* u, const RtDrawBox* box
 int rt_shadow_entities_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes_dev, uint32_t nboxes, const RtDrawStamp* models,
                              uint32_t nmodels, float strength);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Entity queries: what a ray or a pixel hits among the entities a host
+ * draws — clicking a mob, a projectile against it, whether one mob sees another past a third, whether the cursor is on the mob or on
+ * the block behind it.  The calls take the records of rt_draw_boxes and rt_draw_stamps and apply their slab test, their walk and
+ * their depth test against the world, so the answer for a pixel is exactly the entity those draws put there.  One answer, 48 bytes: */
+#define RT_ENTITY_NONE  0
+#define RT_ENTITY_BOX   1
+#define RT_ENTITY_MODEL 2
+typedef struct RtEntityHit {        /* 48 bytes */
+    float    position[3];  float t;          /*  0  P_k = rtm_fma(d_k, t, o_k); t along the NORMALISED direction                    */
+    uint32_t kind, index, normal, material;  /* 16  RT_ENTITY_*; index into boxes / models; face code 0..5; the box's material word
+                                                    or the hit voxel's                                                             */
+    int32_t  cell[3];      uint32_t voxel;   /* 32  MODEL: placed-local cell c of the hit, and the hit voxel's index in the stamp's own
+                                                    arrays (rt_stamp_read's layout, x + ex (y + ey z))                              */
+} RtEntityHit;
+/* The rules.  All arithmetic is fp32 with one rounding per operation; fused operations appear only where rtm_fma is written; any
+ * comparison with a NaN is false.  Results are reproduced bit for bit by tests/entity_query_ref.py, which tests every entity against
+ * every ray (DESIGN.md "Entity queries").
+ *   World part: world_hits[i] (where the pointer is not NULL) is exactly what rt_trace_rays writes for the same ray, `lr` and region —
+ *     for rt_pick_entities exactly what rt_pick_pixels writes, the slide of a start below the region included — every field, bit for
+ *     bit.  The entity part is the same with world_hits NULL.
+ *   Entity ray: rt_trace_entities: o = the ray's origin, d = rtm_normalize3(direction).  rt_pick_entities: the ray of rt_draw_boxes —
+ *     o = u.origin, the same sx, sy and rtm_normalize3, and NO slide.  In both inv_k = 1.0f / d_k.  A ray whose o or d holds a NaN
+ *     hits no entity; that follows from the comparisons and is no special case.
+ *   Box b: rt_draw_boxes' valid box and slab test, word for word: the box is hit iff some axis bounds the ray, every zero-direction
+ *     axis passes, t_in > 0 and t_in < t_out; the hit's t = t_in and its axis the entry axis.  A ray that starts inside a box does not
+ *     hit it, so a mob never hits its own box.
+ *   Model m: rt_draw_stamps' valid record, bounding box, planes, first cell and walk, word for word, with the ray's o in place of the
+ *     camera's.  The hit's t and axis are the walk's, `cell` the cell c the walk stopped on, `voxel` the index of the stamp voxel that
+ *     cell shows and `material` that voxel's word.
+ *   Winner: the smallest t over boxes and models together; on equal t boxes come before models, and within each kind the lowest index
+ *     wins.
+ *   Depth test against the world: P_k = rtm_fma(d_k, t, o_k); depth_f = rtm_length3(o - P) * 32.0f.  D = 65535.0f if the world hit's
+ *     kind is RT_HIT_AIR, otherwise D = rtm_length3(o - world position as returned) * 32.0f (store_primary_planes' expression; a limit
+ *     exit counts as a hit there, so it does here).  For rt_pick_entities o in both expressions is u.origin, and D is bitwise what
+ *     RT_BUF_DEPTH_F32 holds for that pixel in a frame drawn with `u`.  The entity is reported iff depth_f < D: strict, the world wins
+ *     ties; a NaN D reports none, and an entity 2048 or more units away under the sky reports none — the draws' own rules.
+ *   Record of a reported entity: kind RT_ENTITY_BOX or RT_ENTITY_MODEL; index, position = P and t the winner's; normal = 2 axis + 1 if
+ *     d_axis > 0, else 2 axis; material the box's word or the voxel's; for a box cell = (-1, -1, -1) and voxel = 0xFFFFFFFF.
+ *   Record otherwise — nothing hit, the hit occluded, or nboxes + nmodels == 0: kind RT_ENTITY_NONE, index = 0xFFFFFFFF, normal = 6,
+ *     material = 0, t = 0, position = (0, 0, 0), cell = (-1, -1, -1), voxel = 0xFFFFFFFF.  Every byte of every record is written.
+ *   Ordering and side effects: the ray queries' — on the query stream behind the earlier world changes, not behind frames; later
+ *     world changes wait for it; after rt_set_stream(non-NULL) on the caller's stream, in order.  No plane, prepass, accumulation sum,
+ *     history, RtCounters or RtTiming changes.  The call names its stamps as a draw does: rt_stamp_destroy after an enqueued call
+ *     waits for it, and the call itself waits on the device for an earlier rt_stamp_capture, so a stamp captured a moment ago can be
+ *     queried with no host sync in between.
+ *   Errors, all checked before anything is enqueued (a rejected call changes nothing, outputs included): NULL ctx; NULL rays / xy / u /
+ *     lr / entity_hits with count > 0; a NULL entity array with its count above 0; count > 2^24; nboxes or nmodels above 4096; a pixel
+ *     outside the frame; a model record that is not valid; in the synchronous calls a box that is not valid (the asynchronous call
+ *     cannot read device boxes: the device skips an invalid box); in the asynchronous call a device pointer that fails
+ *     rt_trace_rays_async's test: RT_ERR_INVALID_ARG.  No world resident: RT_ERR_NOT_READY (no noise and no drawn frame are needed).
+ *     count == 0: RT_OK, nothing enqueued.  Tile contexts answer for whole-frame pixels, as the ray queries do; every RtKernel and
+ *     every region size answers the same.
+ *   Device work per call: one transfer of a 64-byte record per model and one launch, one lane per ray.  A wave of 64 consecutive rays
+ *     culls the entities against the bounds of its rays 64 at a time and tests only the survivors per ray.  Coherent rays — the pixels
+ *     of a screen region, a volley of projectiles — are culled well; incoherent rays in one wave are not, and the cost then tends to
+ *     rays x entities slab tests.  Send rays that lie together in consecutive order.  There is no acceleration structure over
+ *     entities.
+ * Arbitrary rays; host pointers; returns when the hits are in host memory. */
+int rt_trace_entities(RtContext* ctx, const RtRay* rays, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes, uint32_t nboxes,
+                      const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits, RtEntityHit* entity_hits);
+/* Same, enqueued.  rays_dev, boxes_dev, world_hits_dev (may be NULL) and entity_hits_dev are device memory and must pass
+ * rt_trace_rays_async's test; `models` is a HOST pointer, as for rt_draw_stamps_async and for the same reason, and is free again when
+ * the call returns. */
+int rt_trace_entities_async(RtContext* ctx, const RtRay* rays_dev, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes_dev,
+                            uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits_dev,
+                            RtEntityHit* entity_hits_dev);
+/* The pixels xy[2 i], xy[2 i + 1] = (x, y), row 0 = the bottom row, of the camera in `u`, as for rt_pick_pixels.  Host pointers,
+ * synchronous. */
+int rt_pick_entities(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint32_t count, const RtDrawBox* boxes, uint32_t nboxes,
+                     const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits, RtEntityHit* entity_hits);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Terrain generated on the device: the project's deterministic
  * procedural world (raytrace_amd/host/world.cpp: generate_chunk + pack_into per world chunk, MATERIALS[id].pack()) written straight
  * into the resident region, byte for byte what the host generator assembles — no host bytes, no staging, no transfer.
@@ -1130,7 +1201,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtDrawStamp, rt_draw_stamps, rt_draw_stamps_async (voxel-model entities: stamps drawn at
  *        float positions and scales, composited into the G-buffer by depth).
  *        Additive, same minor version: rt_shadow_entities, rt_shadow_entities_async (entity shadows: drawn boxes and models take the
- *        sun's direct term out of the lighting planes where they shade a pixel). */
+ *        sun's direct term out of the lighting planes where they shade a pixel).
+ *        Additive, same minor version: RtEntityHit, RT_ENTITY_*, rt_trace_entities, rt_trace_entities_async, rt_pick_entities (entity
+ *        queries: what a ray or a pixel hits among the drawn boxes and models, under the draws' own rules). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

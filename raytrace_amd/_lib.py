@@ -26,6 +26,7 @@ ABI_SYMBOLS = (
     "rt_edit_shapes", "rt_draw_boxes", "rt_draw_boxes_async", "rt_add_lights", "rt_add_lights_async",
     "rt_stamp_create", "rt_stamp_capture", "rt_stamp_info", "rt_stamp_read", "rt_stamp_destroy", "rt_edit_stamps",
     "rt_draw_stamps", "rt_draw_stamps_async", "rt_shadow_entities", "rt_shadow_entities_async",
+    "rt_trace_entities", "rt_trace_entities_async", "rt_pick_entities",
 )
 
 _amd = None
@@ -158,6 +159,12 @@ def amd():
         lib.rt_shadow_entities.restype = C.c_int
         lib.rt_shadow_entities_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P, C.c_uint32, C.c_float]
         lib.rt_shadow_entities_async.restype = C.c_int
+        lib.rt_trace_entities.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P, C.c_uint32, P, C.c_uint32, P, P]
+        lib.rt_trace_entities.restype = C.c_int
+        lib.rt_trace_entities_async.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P, C.c_uint32, P, C.c_uint32, P, P]
+        lib.rt_trace_entities_async.restype = C.c_int
+        lib.rt_pick_entities.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, P]
+        lib.rt_pick_entities.restype = C.c_int
         lib.rt_add_lights.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
         lib.rt_add_lights.restype = C.c_int
         lib.rt_add_lights_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
@@ -269,5 +276,7 @@ def host():
         lib.rth_pipeline_set_lights.restype = C.c_int
         lib.rth_pipeline_enable_entity_shadows.argtypes = [P, C.c_float]
         lib.rth_pipeline_enable_entity_shadows.restype = C.c_int
+        lib.rth_pipeline_pick_entity.argtypes = [P, C.c_int, C.c_int, P, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        lib.rth_pipeline_pick_entity.restype = C.c_int
         _host = lib
     return _host

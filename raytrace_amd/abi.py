@@ -231,6 +231,20 @@ assert (RtDrawStamp.origin.offset, RtDrawStamp.scale.offset, RtDrawStamp.stamp.o
 MAX_DRAW_STAMPS = 4096   # rt_draw_stamps: models per call
 
 
+RT_ENTITY_NONE, RT_ENTITY_BOX, RT_ENTITY_MODEL = 0, 1, 2   # RtEntityHit.kind (ABI 1.3, additive: entity queries)
+
+
+class RtEntityHit(C.Structure):
+    """rt_trace_entities / rt_pick_entities result (ABI 1.3, additive): 48 bytes."""
+    _fields_ = [("position", C.c_float * 3), ("t", C.c_float), ("kind", C.c_uint32), ("index", C.c_uint32), ("normal", C.c_uint32),
+                ("material", C.c_uint32), ("cell", C.c_int32 * 3), ("voxel", C.c_uint32)]
+
+
+assert C.sizeof(RtEntityHit) == 48
+assert (RtEntityHit.t.offset, RtEntityHit.kind.offset, RtEntityHit.material.offset, RtEntityHit.cell.offset, RtEntityHit.voxel.offset) == (12, 16, 28, 32, 44)
+MAX_ENTITY_RAYS = 1 << 24   # rt_trace_entities / rt_pick_entities: rays or pixels per call
+
+
 class RtPointLight(C.Structure):
     """rt_add_lights input (ABI 1.3, additive: point lights): 32 bytes; `reserved` must be 0."""
     _fields_ = [("position", C.c_float * 3), ("radius", C.c_float), ("color", C.c_float * 3), ("reserved", C.c_uint32)]

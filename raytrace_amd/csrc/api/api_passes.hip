@@ -13,30 +13,8 @@
 
 using namespace rta;
 
-namespace {
-constexpr uint32_t kMaxDrawBoxes = 4096;
-static_assert(sizeof(RtDrawBox) == 32 && sizeof(RtProbeLight) == 16, "the kernels read two 16-byte words per box and one per face light");
-static_assert(sizeof(RtPointLight) == 32, "the kernel reads two 16-byte words per light");
+namespace rta {
 static_assert(sizeof(RtDrawStamp) == 32 && sizeof(DrawStampRecord) == 64, "one 32-byte record per model from the caller, four 16-byte words to the kernels");
-
-// What is wrong with the plain arguments of a pass with one batch, or nullptr (shadow_args_error is the form with two batches).
-const char* batch_args_error(const void* u, const char* too_many, bool null_pointer) {
-    if (!u) return "null uniforms";
-    if (too_many) return too_many;
-    return null_pointer ? "null pointer" : nullptr;
-}
-
-// The prologue of every pass: the verdict on its plain arguments, then the context's state.  RT_OK with *work = false: a valid call
-// with no record, which enqueues nothing.
-int pass_begin(RtContext* c, const std::string& fn, const char* args_error, bool reads_world, uint32_t records, bool* work) {
-    *work = false;
-    if (args_error) return fail(c, RT_ERR_INVALID_ARG, fn + ": " + args_error);
-    if (c->cfg.tile_world != 1) return fail(c, RT_ERR_UNIMPLEMENTED, fn + ": whole-frame contexts only");
-    if (!c->frame_recorded) return fail(c, RT_ERR_NOT_READY, fn + ": no frame drawn yet");
-    if (reads_world && !c->world_resident) return fail(c, RT_ERR_NOT_READY, fn + ": upload the full region first");
-    *work = records > 0u;
-    return RT_OK;
-}
 
 // The models of a call, resolved against the live stamps before anything is enqueued; `nothing` ends the refusal.
 int models_check(RtContext* c, const std::string& fn, const RtDrawStamp* models, uint32_t n, const char* nothing) {
@@ -47,26 +25,12 @@ int models_check(RtContext* c, const std::string& fn, const RtDrawStamp* models,
                                            " [2^-8, 64] or a corner beyond 2^22; " + nothing);
 }
 
-// The slot's prepass no longer describes the planes a pass writes: a still camera must not carry entity pixels, light or shadow into
-// the next frame.  The draws write the geometry planes too, the lighting passes the two lighting planes only.
-void planes_written(RtContext* c, bool geometry_too) {
-    if (geometry_too)
-        for (int b : {RT_BUF_DEPTH_F32, RT_BUF_DEPTH_R16UI, RT_BUF_NORMAL_R8UI, RT_BUF_ALBEDO_RGBA8, RT_BUF_EMISSION_RGBA8}) plane_written(c, c->planes[b]);
-    for (int b : {RT_BUF_LIGHTING_F32, RT_BUF_LIGHTING_RGBA16}) plane_written(c, c->planes[b]);
-}
-
-// the camera of the frame the planes hold (DrawBoxesArgs, DrawStampsArgs)
-template <typename Args>
-void set_camera(Args& a, const RtUniforms* u, const RtConfig& cfg) {
-    a.width = cfg.width; a.height = cfg.height;
-    for (int k = 0; k < 3; k++) { a.origin[k] = u->origin[k]; a.forward[k] = u->forward[k]; a.up[k] = u->up[k]; a.right[k] = u->right[k]; }
-}
-
 // The device records of `n` (valid) models, and `extra_bytes` of the caller's behind them, through the next of the two staging sets
-// (rt_draw_stamps and rt_shadow_entities take turns over the same two, in call order) to *dev; the context's stream waits for the
-// transfer.  The caller launches there and then records (*set)->ev_applied on it: the set's next transfer and rt_stamp_destroy wait
-// for that launch.
-int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const void* extra_host, size_t extra_bytes, StagingSet** set, uint8_t** dev) {
+// (rt_draw_stamps, rt_shadow_entities and the entity queries take turns over the same two, in call order) to *dev; `reader` — the
+// stream whose launch will read the records: the context's for a pass, the query stream for a query — waits for the transfer.  The
+// caller launches there and then records (*set)->ev_applied on it: the set's next transfer and rt_stamp_destroy wait for that launch.
+int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const void* extra_host, size_t extra_bytes, hipStream_t reader,
+                  StagingSet** set, uint8_t** dev) {
     const size_t rec_bytes = (size_t)n * sizeof(DrawStampRecord), need = rec_bytes + extra_bytes;
     StagingSet& s = c->draw_sets[c->draw_batches & 1u];
     if (!c->upload_stream) RT_HIP(c, new_stream(c, &c->upload_stream));
@@ -88,10 +52,50 @@ int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const voi
     RT_HIP(c, s.ev_applied.wait(c->upload_stream));
     RT_HIP(c, hipMemcpyAsync(s.dev, s.host, need, hipMemcpyHostToDevice, c->upload_stream));
     RT_HIP(c, s.ev_copied.record(c->upload_stream));
-    RT_HIP(c, hipStreamWaitEvent(c->stream, s.ev_copied.ev, 0));
+    RT_HIP(c, hipStreamWaitEvent(reader, s.ev_copied.ev, 0));
     *set = &s;
     *dev = s.dev;
     return RT_OK;
+}
+}  // namespace rta
+
+namespace {
+constexpr uint32_t kMaxDrawBoxes = 4096;
+static_assert(sizeof(RtDrawBox) == 32 && sizeof(RtProbeLight) == 16, "the kernels read two 16-byte words per box and one per face light");
+static_assert(sizeof(RtPointLight) == 32, "the kernel reads two 16-byte words per light");
+
+// What is wrong with the plain arguments of a pass with one batch, or nullptr (shadow_args_error is the form with two batches).
+const char* batch_args_error(const void* u, const char* too_many, bool null_pointer) {
+    if (!u) return "null uniforms";
+    if (too_many) return too_many;
+    return null_pointer ? "null pointer" : nullptr;
+}
+
+// The prologue of every pass: the verdict on its plain arguments, then the context's state.  RT_OK with *work = false: a valid call
+// with no record, which enqueues nothing.
+int pass_begin(RtContext* c, const std::string& fn, const char* args_error, bool reads_world, uint32_t records, bool* work) {
+    *work = false;
+    if (args_error) return fail(c, RT_ERR_INVALID_ARG, fn + ": " + args_error);
+    if (c->cfg.tile_world != 1) return fail(c, RT_ERR_UNIMPLEMENTED, fn + ": whole-frame contexts only");
+    if (!c->frame_recorded) return fail(c, RT_ERR_NOT_READY, fn + ": no frame drawn yet");
+    if (reads_world && !c->world_resident) return fail(c, RT_ERR_NOT_READY, fn + ": upload the full region first");
+    *work = records > 0u;
+    return RT_OK;
+}
+
+// The slot's prepass no longer describes the planes a pass writes: a still camera must not carry entity pixels, light or shadow into
+// the next frame.  The draws write the geometry planes too, the lighting passes the two lighting planes only.
+void planes_written(RtContext* c, bool geometry_too) {
+    if (geometry_too)
+        for (int b : {RT_BUF_DEPTH_F32, RT_BUF_DEPTH_R16UI, RT_BUF_NORMAL_R8UI, RT_BUF_ALBEDO_RGBA8, RT_BUF_EMISSION_RGBA8}) plane_written(c, c->planes[b]);
+    for (int b : {RT_BUF_LIGHTING_F32, RT_BUF_LIGHTING_RGBA16}) plane_written(c, c->planes[b]);
+}
+
+// the camera of the frame the planes hold (DrawBoxesArgs, DrawStampsArgs)
+template <typename Args>
+void set_camera(Args& a, const RtUniforms* u, const RtConfig& cfg) {
+    a.width = cfg.width; a.height = cfg.height;
+    for (int k = 0; k < 3; k++) { a.origin[k] = u->origin[k]; a.forward[k] = u->forward[k]; a.up[k] = u->up[k]; a.right[k] = u->right[k]; }
 }
 
 // ---- entity boxes ---------------------------------------------------------------------------------------------------------------
@@ -143,7 +147,7 @@ int draw_stamps_enqueue(RtContext* c, const RtUniforms* u, const RtDrawStamp* mo
     RT_HIP(c, hipSetDevice(c->device));
     StagingSet* s;
     uint8_t* recs;
-    const int rc = upload_models(c, models, count, lights_host, lights_host ? (size_t)count * 6u * sizeof(RtProbeLight) : 0u, &s, &recs);
+    const int rc = upload_models(c, models, count, lights_host, lights_host ? (size_t)count * 6u * sizeof(RtProbeLight) : 0u, c->stream, &s, &recs);
     if (rc != RT_OK) return rc;
     planes_written(c, true);
     RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
@@ -178,7 +182,7 @@ int shadow_enqueue(RtContext* c, const RtUniforms* u, const void* boxes_dev, uin
     StagingSet* s = nullptr;
     if (nmodels > 0u) {
         uint8_t* recs;
-        const int rc = upload_models(c, models, nmodels, nullptr, 0u, &s, &recs);
+        const int rc = upload_models(c, models, nmodels, nullptr, 0u, c->stream, &s, &recs);
         if (rc != RT_OK) return rc;
         a.recs = reinterpret_cast<const uint4*>(recs);
     }

@@ -1,6 +1,7 @@
 // api_query.hip — queries against the resident world: ray queries (rt_trace_rays, rt_trace_rays_async, rt_pick_pixels), light
-// probes (rt_probe_light, rt_probe_light_async) and box sweeps (rt_sweep_boxes, rt_sweep_boxes_async), which share their checks,
-// stream and staging.
+// probes (rt_probe_light, rt_probe_light_async), box sweeps (rt_sweep_boxes, rt_sweep_boxes_async) and entity queries
+// (rt_trace_entities, rt_trace_entities_async, rt_pick_entities), which share their checks, stream and staging.
+#include "entity_query_check.hpp"
 #include "rt_context.hpp"
 
 using namespace rta;
@@ -169,6 +170,68 @@ int sweep_launch(RtContext* c, hipStream_t st, const int32_t lr[3], const void* 
     if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
     return RT_OK;
 }
+
+// ---- entity queries: device rays (or pixels) and boxes, host models as rt_draw_stamps' ------------------------------------------
+static_assert(sizeof(RtEntityHit) == 48 && sizeof(RtRayHit) == 48, "the kernel writes three 16-byte words per record of either kind");
+
+// checks shared by the three calls; RT_OK when there is work to enqueue, 1 for count == 0
+int entity_check(RtContext* c, const char* fn, uint32_t count, const void* in, const void* more, const void* entity_hits, const void* boxes,
+                 uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels) {
+    const char* e = entity_query_args_error(count, in, more, entity_hits, boxes, nboxes, models, nmodels);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e);
+    if (count == 0) return 1;
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    return models_check(c, fn, models, nmodels, "nothing was answered");
+}
+
+// The models to the device for `st` to read, the launch there, and what waits for it: the staging set's next transfer and
+// rt_stamp_destroy (ev_applied), later world changes (ev_query).
+int entity_launch(RtContext* c, hipStream_t st, const rtd::Frame& f, const void* rays_dev, const void* xy_dev, uint32_t count, const void* boxes_dev,
+                  uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels, void* world_dev, void* entity_dev) {
+    rtd::EntityQueryArgs a;
+    a.rays = reinterpret_cast<const float4*>(rays_dev);
+    a.xy = reinterpret_cast<const int2*>(xy_dev);
+    a.world_hits = reinterpret_cast<uint4*>(world_dev);
+    a.entity_hits = reinterpret_cast<uint4*>(entity_dev);
+    a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
+    a.recs = nullptr;
+    a.count = count; a.nboxes = nboxes; a.nmodels = nmodels;
+    StagingSet* s = nullptr;
+    if (nmodels > 0u) {
+        uint8_t* recs;
+        const int rc = upload_models(c, models, nmodels, nullptr, 0u, st, &s, &recs);
+        if (rc != RT_OK) return rc;
+        a.recs = reinterpret_cast<const uint4*>(recs);
+        // a stamp made by rt_stamp_capture is written on the render stream: the launch follows the latest capture (on a caller's
+        // stream, or when the capture ran on this very stream, stream order does it)
+        RT_HIP(c, c->ev_capture.wait_elsewhere(st));
+    }
+    RT_HIP(c, rtd::launch_entity_query(scene_of(c), f, a, st));
+    if (s) RT_HIP(c, s->ev_applied.record(st));
+    if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
+    return RT_OK;
+}
+
+// The synchronous calls: rays (or pixels), boxes and both outputs through one staging block, the launch, one or two blocks back.
+int entity_sync(RtContext* c, const rtd::Frame& f, const void* in, size_t in_bytes, bool picks, uint32_t count, const RtDrawBox* boxes, uint32_t nboxes,
+                const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits, RtEntityHit* entity_hits) {
+    hipStream_t st;
+    int rc = query_stream_of(c, &st);
+    if (rc != RT_OK) return rc;
+    const size_t out_bytes = (size_t)count * sizeof(RtEntityHit);   // (of either output)
+    uint8_t* dev[4];
+    rc = stage_sync(c, st, {{in, in_bytes}, {nboxes ? boxes : nullptr, (size_t)nboxes * sizeof(RtDrawBox)}, {nullptr, world_hits ? out_bytes : 0u},
+                            {nullptr, out_bytes}}, dev);
+    if (rc != RT_OK) return rc;
+    rc = entity_launch(c, st, f, picks ? nullptr : dev[0], picks ? dev[0] : nullptr, count, nboxes ? dev[1] : nullptr, nboxes, models, nmodels,
+                       world_hits ? dev[2] : nullptr, dev[3]);
+    if (rc != RT_OK) return rc;
+    if (world_hits) {
+        rc = fetch_sync(c, st, dev[2], world_hits, out_bytes);
+        if (rc != RT_OK) return rc;
+    }
+    return fetch_sync(c, st, dev[3], entity_hits, out_bytes);
+}
 }  // namespace
 
 extern "C" {
@@ -272,6 +335,47 @@ int rt_sweep_boxes_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t 
     rc = query_stream_of(ctx, &st);
     if (rc != RT_OK) return rc;
     return sweep_launch(ctx, st, lr, sweeps_dev, hits_dev, count);
+}
+
+int rt_trace_entities(RtContext* ctx, const RtRay* rays, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes, uint32_t nboxes,
+                      const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits, RtEntityHit* entity_hits) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const int rc = entity_check(ctx, "rt_trace_entities", count, rays, lr, entity_hits, boxes, nboxes, models, nmodels);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    const uint32_t bad = first_invalid_draw_box(boxes, nboxes);
+    if (bad != nboxes) return fail(ctx, RT_ERR_INVALID_ARG, "rt_trace_entities: box " + std::to_string(bad) + " is not a valid box");
+    return entity_sync(ctx, query_frame(ctx, lr), rays, (size_t)count * sizeof(RtRay), false, count, boxes, nboxes, models, nmodels, world_hits,
+                       entity_hits);
+}
+
+int rt_trace_entities_async(RtContext* ctx, const RtRay* rays_dev, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes_dev,
+                            uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits_dev,
+                            RtEntityHit* entity_hits_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = entity_check(ctx, "rt_trace_entities_async", count, rays_dev, lr, entity_hits_dev, boxes_dev, nboxes, models, nmodels);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, rays_dev) || !query_device_ptr(ctx, entity_hits_dev) || (nboxes > 0u && !query_device_ptr(ctx, boxes_dev)) ||
+        (world_hits_dev && !query_device_ptr(ctx, world_hits_dev)))
+        return fail(ctx, RT_ERR_INVALID_ARG,
+                    "rt_trace_entities_async: rays, boxes and both hits must be 16-byte aligned memory of the context's device");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    return entity_launch(ctx, st, query_frame(ctx, lr), rays_dev, nullptr, count, nboxes ? boxes_dev : nullptr, nboxes, models, nmodels,
+                         world_hits_dev, entity_hits_dev);
+}
+
+int rt_pick_entities(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint32_t count, const RtDrawBox* boxes, uint32_t nboxes,
+                     const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits, RtEntityHit* entity_hits) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const int rc = entity_check(ctx, "rt_pick_entities", count, xy, u, entity_hits, boxes, nboxes, models, nmodels);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    const uint32_t out = first_pixel_outside(xy, count, ctx->cfg.width, ctx->cfg.height);
+    if (out != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_pick_entities: pixel " + std::to_string(out) + " is outside the frame");
+    const uint32_t bad = first_invalid_draw_box(boxes, nboxes);
+    if (bad != nboxes) return fail(ctx, RT_ERR_INVALID_ARG, "rt_pick_entities: box " + std::to_string(bad) + " is not a valid box");
+    return entity_sync(ctx, frame_of(ctx, u), xy, (size_t)count * 8u, true, count, boxes, nboxes, models, nmodels, world_hits, entity_hits);
 }
 
 }  // extern "C"

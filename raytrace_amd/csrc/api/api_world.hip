@@ -394,14 +394,17 @@ int rt_stamp_capture(RtContext* ctx, const int32_t lo[3], const int32_t extent[3
     StampEntry* e = ctx->stamps.add(extent);
     RT_HIP(ctx, stamp_alloc(ctx, e));
     // One launch on the stream the edits use: behind every earlier world change (they ran there, or the lanes were fenced behind
-    // them), and every later one joins the lanes before it writes.  It reads the region only, so frames and queries need no order.
-    hipError_t err;
-    {
+    // them), and every later one joins the lanes before it writes.  It reads the region only, so frames and ray queries need no
+    // order.  It WRITES the stamp's arrays: what reads them on this stream (placements, draws, shadows) follows in stream order, and an
+    // entity query, which reads them on the query stream, waits for ev_capture.
+    hipError_t err = ctx->ev_capture.ev ? hipSuccess : new_event(ctx, &ctx->ev_capture.ev);
+    if (err == hipSuccess) {
         LaunchTimer lt(ctx, 1);
         err = rtd::launch_stamp_capture(ctx->d_mine_sw, ctx->d_mat_sw, ctx->logr, lo[0], lo[1], lo[2], extent[0], extent[1], extent[2],
                                         (flags & RT_STAMP_SKIP_AIR) != 0u, reinterpret_cast<uint32_t*>(e->mats), reinterpret_cast<uint8_t*>(e->state),
                                         ctx->stream);
     }
+    if (err == hipSuccess) err = ctx->ev_capture.record(ctx->stream);
     if (err == hipSuccess) err = fence_lanes_after(ctx, ctx->stream);   // (a later change may start on the other lane's stream)
     if (err != hipSuccess) {
         (void)hipStreamSynchronize(ctx->stream);

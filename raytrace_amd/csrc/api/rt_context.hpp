@@ -321,6 +321,9 @@ struct __attribute__((visibility("hidden"))) RtContext {
     // for the edits (call n waits for the transfer of call n - 2 to leave the host block and for its launch to leave the device block)
     rta::StagingSet draw_sets[2];
     uint64_t draw_batches = 0;
+    // the most recent rt_stamp_capture: its launch writes a stamp's arrays on the render stream, where the draws and the shadows read
+    // them in stream order; an entity query reads them on the query stream and waits for this first
+    rta::LatchEvent ev_capture;
     // light probes (rt_probe_light): the path records of a launch whose samples one workgroup cannot add itself (16 bytes per path),
     // grown on demand up to kProbeScratchBytes, in c->allocs (device_bytes; freed by rt_destroy)
     float4* probe_scratch = nullptr;
@@ -457,5 +460,10 @@ inline rtd::Planes planes_of(const RtContext* c) { return planes_of(c->planes); 
 void resolve_route(RtContext* c);
 rtd::Frame frame_of(const RtContext* c, const RtUniforms* u);
 bool query_device_ptr(const RtContext* c, const void* p);   // api_query.hip: rt_trace_rays_async's test of a caller's device pointer
+// api_passes.hip: the verdict on a batch of models, and their way to the device for the launch `reader` will run (the entity draws,
+// the entity shadows and the entity queries share both)
+int models_check(RtContext* c, const std::string& fn, const RtDrawStamp* models, uint32_t n, const char* nothing);
+int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const void* extra_host, size_t extra_bytes, hipStream_t reader,
+                  StagingSet** set, uint8_t** dev);
 
 }  // namespace rta

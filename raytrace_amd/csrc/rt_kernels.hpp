@@ -258,6 +258,19 @@ struct ShadowArgs {
 };
 hipError_t launch_shadow_entities(const Scene& sc, const Frame& f, const Planes& pl, const ShadowArgs& a, hipStream_t st);
 
+// rt_entity_query.hip: ray and pixel queries against drawn entities (rt_trace_entities, rt_pick_entities).  One launch, one lane per
+// ray: the world's hit as rt_query.hip finds it, then the nearest box or model under the draws' rules, depth-tested against it.
+struct EntityQueryArgs {
+    const float4* rays;   // RtRay[count] (two float4 each), or
+    const int2* xy;       // non-null: pixel (x, y) of the frame's camera per query
+    uint4* world_hits;    // RtRayHit[count] (three uint4 each), or null
+    uint4* entity_hits;   // RtEntityHit[count] (three uint4 each)
+    const uint4* boxes;   // RtDrawBox[nboxes] (two uint4 each); an invalid box is skipped
+    const uint4* recs;    // DrawStampRecord[nmodels] (api/draw_stamps.hpp; four uint4 each), resolved and validated on the host
+    uint32_t count, nboxes, nmodels;
+};
+hipError_t launch_entity_query(const Scene& sc, const Frame& f, const EntityQueryArgs& a, hipStream_t st);
+
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
 // (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
 // or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)

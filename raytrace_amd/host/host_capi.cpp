@@ -250,5 +250,15 @@ int rth_pipeline_pick(void* p, int x, int y_from_top, RtRayHit* hit, int32_t* ad
     for (int a = 0; a < 3; a++) { adjacent[a] = r.adjacent[a]; world[a] = r.world[a]; }
     return RT_OK;
 }
+// Pipeline::pick_entity: the entity hit, and the world's as rth_pipeline_pick gives it
+int rth_pipeline_pick_entity(void* p, int x, int y_from_top, RtEntityHit* entity, RtRayHit* hit, int32_t* adjacent, int32_t* world) {
+    render::Pipeline::EntityPick r;
+    const int rc = static_cast<render::Pipeline*>(p)->pick_entity(x, y_from_top, &r);
+    if (rc != RT_OK) return rc;
+    *entity = r.entity;
+    *hit = r.world.hit;
+    for (int a = 0; a < 3; a++) { adjacent[a] = r.world.adjacent[a]; world[a] = r.world.world[a]; }
+    return RT_OK;
+}
 
 }  // extern "C"

@@ -124,6 +124,21 @@ int Pipeline::pick(int x, int y_from_top, PickResult* out) {
     const int32_t xy[2] = {x, (int32_t)height_ - 1 - y_from_top};
     int rc = rt_pick_pixels(ctx_, &uniforms_, xy, 1, &out->hit);
     if (rc != RT_OK) return rc;
+    finish_pick(out);
+    return RT_OK;
+}
+
+int Pipeline::pick_entity(int x, int y_from_top, EntityPick* out) {
+    const int32_t xy[2] = {x, (int32_t)height_ - 1 - y_from_top};
+    int rc = rt_pick_entities(ctx_, &uniforms_, xy, 1, boxes_.data(), (uint32_t)boxes_.size(), models_.data(), (uint32_t)models_.size(),
+                              &out->world.hit, &out->entity);
+    if (rc != RT_OK) return rc;
+    finish_pick(&out->world);
+    return RT_OK;
+}
+
+// adjacent and world of a pick whose `hit` is filled
+void Pipeline::finish_pick(PickResult* out) const {
     // face normal code n (raytrace.comp:89-93): the ray crossed the face on the side it came from, so the empty neighbour lies
     // one texel back along the axis: +1 for even codes (the ray moved towards -axis), -1 for odd ones
     const int R = region_;
@@ -135,7 +150,6 @@ int Pipeline::pick(int x, int y_from_top, PickResult* out) {
         const int lr = uniforms_.lr[a];
         out->world[a] = lr - R / 2 + (((t - lr) % R) + R) % R;
     }
-    return RT_OK;
 }
 
 int Pipeline::probe_light(const RtLightProbe* probes, uint32_t count, uint32_t samples, int32_t depth, RtProbeLight* out) {

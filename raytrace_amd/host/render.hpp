@@ -107,6 +107,14 @@ class Pipeline {
         int32_t world[3];
     };
     int pick(int x, int y_from_top, PickResult* out);
+    // The entity under that pixel, if one is drawn there: rt_pick_entities with the pipeline's uniforms and the boxes and models of
+    // set_boxes / set_models — the depth test against the world included, so entity.kind != RT_ENTITY_NONE means the cursor is on an
+    // entity (entity.index counts within its kind's set) and not on the block behind it, which `world` describes as pick does.
+    struct EntityPick {
+        RtEntityHit entity;
+        PickResult world;
+    };
+    int pick_entity(int x, int y_from_top, EntityPick* out);
     // Path-traced light at `count` points under the sun, seed and lr of the frame drawn last: rt_probe_light with the pipeline's
     // uniforms (a host that accumulates over calls advances the seed by `samples` between them: set_seed).
     int probe_light(const RtLightProbe* probes, uint32_t count, uint32_t samples, int32_t depth, RtProbeLight* out);
@@ -145,6 +153,7 @@ class Pipeline {
  private:
     friend Pipeline* create_instance(const RtConfig&, const uint8_t*, game::Game&, std::string*);
     Pipeline() = default;
+    void finish_pick(PickResult* out) const;   // adjacent and world of a pick whose `hit` is filled
     RtContext* ctx_ = nullptr;
     RtUniforms uniforms_{};            // RenderData::raytrace_uniform_data, render_data.rs:134-162
     int spp_ = 1;

@@ -11,6 +11,7 @@
 //            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
 //            [--boxes N]
+//            [--entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--lights N] [--shadows N [--shadow-models]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
@@ -66,6 +67,12 @@
 // over as arbitrary rays — timed call to return (the transfers both ways included; the kernel alone: rocprofv3 --kernel-trace
 // --stats, or tools/ray_query_bench.py's device events), then the call-to-return latency of one-pixel rt_pick_pixels, idle and
 // right behind a --width x --height --spp --depth frame still in flight.  One JSON line.
+// --entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]: instead of the frame loop, entity queries.  rt_trace_entities on
+// N rays — --rays' seeded rays, or with --coherent its camera rays — against B boxes and M models scattered as --boxes and --models
+// scatter them, and rt_trace_rays on the same rays as the yardstick, both timed call to return; then their asynchronous twins on device
+// copies of the same records, on a stream of this program's, between two HIP events: the device time of each.  The JSON line also
+// counts the rays that report an entity and those whose entity the world occludes.  (The kernels alone, k_entity_query and k_query:
+// rocprofv3 --kernel-trace --stats, which tools/entity_query_bench.py runs.)
 // --boxes N: instead of the frame loop, entity boxes.  N entity-sized boxes are scattered deterministically in front of the camera
 // (20 to 400 units away, over the whole view), their six face probes lit with rt_probe_light (4 samples, depth 2), and rt_draw_boxes
 // composites them into a freshly drawn --width x --height frame, 20 times.  One JSON line: the device time of the pass (the launch
@@ -86,6 +93,8 @@
 // units along the ray where the pixel shows sky) — and rt_add_lights adds them to a freshly drawn --width x --height frame, 20 times.
 // One JSON line: the device time of the pass (the launch bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time of
 // rt_add_lights and the pixels lit.
+#include <dlfcn.h>
+
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -294,6 +303,166 @@ int run_rays(rt::game::Game& game, const std::vector<uint8_t>& noise, int width,
                 "\"frame\": \"%dx%d spp %d depth %d\", \"frame_ms\": %.3f}\n",
                 n, coherent ? "true" : "false", ms, (double)n / (ms * 1e-3) / 1e9, (unsigned long long)solid, idle[idle.size() / 2],
                 busy[busy.size() / 2], busy.back(), width, height, spp, depth, frame_ms);
+    delete p;
+    return 0;
+}
+
+// The few HIP runtime calls --entity-rays needs to time the asynchronous calls with an event pair, taken from the runtime the library
+// itself runs on (this program is plain C++ and includes no HIP header).  ok == false: no device times.
+struct HipEvents {
+    typedef int (*malloc_t)(void**, size_t);
+    typedef int (*free_t)(void*);
+    typedef int (*memcpy_t)(void*, const void*, size_t, int);
+    typedef int (*make_t)(void**);
+    typedef int (*one_t)(void*);
+    typedef int (*record_t)(void*, void*);
+    typedef int (*elapsed_t)(float*, void*, void*);
+    malloc_t dev_malloc = nullptr; free_t dev_free = nullptr; memcpy_t copy = nullptr;
+    make_t stream_create = nullptr, event_create = nullptr;
+    one_t stream_destroy = nullptr, event_destroy = nullptr, event_sync = nullptr;
+    record_t event_record = nullptr;
+    elapsed_t elapsed = nullptr;
+    bool ok = false;
+    HipEvents() {
+        void* h = dlopen("libamdhip64.so", RTLD_NOW | RTLD_GLOBAL);
+        if (!h) return;
+        dev_malloc = (malloc_t)dlsym(h, "hipMalloc"); dev_free = (free_t)dlsym(h, "hipFree"); copy = (memcpy_t)dlsym(h, "hipMemcpy");
+        stream_create = (make_t)dlsym(h, "hipStreamCreate"); stream_destroy = (one_t)dlsym(h, "hipStreamDestroy");
+        event_create = (make_t)dlsym(h, "hipEventCreate"); event_destroy = (one_t)dlsym(h, "hipEventDestroy");
+        event_sync = (one_t)dlsym(h, "hipEventSynchronize"); event_record = (record_t)dlsym(h, "hipEventRecord");
+        elapsed = (elapsed_t)dlsym(h, "hipEventElapsedTime");
+        ok = dev_malloc && dev_free && copy && stream_create && stream_destroy && event_create && event_destroy && event_sync && event_record && elapsed;
+    }
+    // `bytes` of device memory holding a copy of `host` (nullptr: uninitialised); nullptr on failure
+    void* on_device(const void* host, size_t bytes) const {
+        void* p = nullptr;
+        if (dev_malloc(&p, bytes ? bytes : 16) != 0) return nullptr;
+        if (host && bytes && copy(p, host, bytes, 1 /* hipMemcpyHostToDevice */) != 0) { (void)dev_free(p); return nullptr; }
+        return p;
+    }
+};
+
+// --entity-rays: see the head of the file
+int run_entity_rays(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n,
+                    uint32_t nboxes, uint32_t nmodels, float scale, bool coherent) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    // the rays of --rays: the camera's primary rays handed over as arbitrary rays, or seeded origins in the region and random directions
+    std::vector<RtRay> rays(n);
+    for (uint32_t i = 0; i < n; i++) {
+        RtRay& r = rays[i];
+        r = RtRay{};
+        if (coherent) {
+            const uint32_t px = i % (uint32_t)width, py = (i / (uint32_t)width) % (uint32_t)height;
+            const float sx = ((float)px / (float)width) * 2.0f - 1.0f, sy = ((float)py / (float)height) * 2.0f - 1.0f;
+            for (int a = 0; a < 3; a++) { r.origin[a] = u.origin[a]; r.direction[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; }
+        } else {
+            for (int a = 0; a < 3; a++) { r.origin[a] = (rnd() - 0.5f) * 254.0f; r.direction[a] = rnd() * 2.0f - 1.0f; }
+        }
+    }
+    // the entities of --boxes and --models: scattered over the view 20 to 400 units away
+    const int32_t E[3] = {9, 9, 12};
+    std::vector<uint32_t> mats((size_t)E[0] * E[1] * E[2]);
+    std::vector<uint8_t> state(mats.size());
+    for (size_t i = 0; i < mats.size(); i++) {
+        state[i] = rnd() < 0.3333f ? RT_STAMP_SOLID : (i & 1u ? RT_STAMP_AIR : RT_STAMP_ABSENT);
+        mats[i] = (1u << 15) | ((40u + (uint32_t)i % 80u) << 14) | ((30u + (uint32_t)i % 90u) << 7) | (20u + (uint32_t)i % 100u);
+    }
+    uint32_t id = 0;
+    if (p->stamp_create(E, mats.data(), state.data(), &id) != RT_OK) { std::fprintf(stderr, "stamp_create failed: %s\n", p->last_error()); delete p; return 1; }
+    static const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    std::vector<RtDrawBox> boxes(nboxes);
+    std::vector<RtDrawStamp> models(nmodels);
+    for (uint32_t i = 0; i < nboxes + nmodels; i++) {
+        const float sx = rnd() * 2.0f - 1.0f, sy = rnd() * 2.0f - 1.0f, dist = 20.0f * std::pow(20.0f, rnd());   // 20 .. 400, log-uniform
+        float v[3], len = 0.0f;
+        for (int a = 0; a < 3; a++) { v[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; len += v[a] * v[a]; }
+        len = std::sqrt(len);
+        if (i < nboxes) {
+            RtDrawBox& b = boxes[i];
+            for (int a = 0; a < 3; a++) {
+                const float c = u.origin[a] + v[a] / len * dist, half = a == 2 ? 0.9f : 0.3f;   // a player's box: 0.6 x 0.6 x 1.8
+                b.lo[a] = c - half; b.hi[a] = c + half;
+            }
+            b.material = 0x12345u; b.emission = 0xFF000000u;
+        } else {
+            RtDrawStamp& m = models[i - nboxes];
+            m = RtDrawStamp{};
+            m.stamp = id; m.scale = scale; m.orient = (uint8_t)(i % 48u); m.emission = 0xFF000000u;
+            for (int a = 0; a < 3; a++) m.origin[a] = u.origin[a] + v[a] / len * dist - 0.5f * (float)E[perms[m.orient >> 3][a]] * scale;
+        }
+    }
+    const int32_t lr[3] = {u.lr[0], u.lr[1], u.lr[2]};
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    std::vector<RtRayHit> world(n), plain(n);
+    std::vector<RtEntityHit> hits(n);
+    const int reps = n >= (1u << 20) ? 5 : 20;
+    double ms[2] = {0.0, 0.0};
+    int rc = RT_OK;
+    for (int which = 0; which < 2 && rc == RT_OK; which++) {      // 0: rt_trace_entities, 1: rt_trace_rays on the same rays, the yardstick
+        for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {       // (the first repetition warms the staging up)
+            const auto t = std::chrono::steady_clock::now();
+            rc = which == 0 ? rt_trace_entities(ctx, rays.data(), n, lr, boxes.data(), nboxes, models.data(), nmodels, world.data(), hits.data())
+                            : rt_trace_rays(ctx, rays.data(), n, lr, plain.data());
+            if (i > 0) ms[which] += ms_since(t) / reps;
+        }
+    }
+    if (rc != RT_OK) { std::fprintf(stderr, "entity queries failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    if (std::memcmp(world.data(), plain.data(), (size_t)n * sizeof(RtRayHit)) != 0) { std::fprintf(stderr, "the world hits differ from rt_trace_rays'\n"); delete p; return 1; }
+    // reported: the call's own answer; occluded: rays that report an entity only once the world is out of the way — the same call with
+    // the window moved 2^20 voxels off, where every ray leaves the region at once (D = 65535)
+    uint64_t reported = 0, under_sky = 0, met = 0;
+    for (uint32_t i = 0; i < n; i++) { reported += hits[i].kind != RT_ENTITY_NONE; under_sky += hits[i].kind != RT_ENTITY_NONE && world[i].kind == RT_HIT_AIR; }
+    const int32_t away[3] = {lr[0] + (1 << 20), lr[1], lr[2]};
+    rc = rt_trace_entities(ctx, rays.data(), n, away, boxes.data(), nboxes, models.data(), nmodels, nullptr, hits.data());
+    if (rc != RT_OK) { std::fprintf(stderr, "entity queries failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    for (uint32_t i = 0; i < n; i++) met += hits[i].kind != RT_ENTITY_NONE;
+    // device time of each call: the asynchronous twins on device copies of the same records, on a stream of this program's, between
+    // two events (-1: the HIP runtime could not be reached from here)
+    double device_ms[2] = {-1.0, -1.0};
+    const HipEvents hip;
+    if (hip.ok) {
+        void *st = nullptr, *e0 = nullptr, *e1 = nullptr;
+        void* d_rays = hip.on_device(rays.data(), (size_t)n * sizeof(RtRay));
+        void* d_boxes = hip.on_device(boxes.data(), (size_t)nboxes * sizeof(RtDrawBox));
+        void* d_world = hip.on_device(nullptr, (size_t)n * sizeof(RtRayHit));
+        void* d_hits = hip.on_device(nullptr, (size_t)n * sizeof(RtEntityHit));
+        bool fine = d_rays && d_boxes && d_world && d_hits && hip.stream_create(&st) == 0 && hip.event_create(&e0) == 0 && hip.event_create(&e1) == 0 &&
+                    rt_set_stream(ctx, st) == RT_OK;
+        for (int which = 0; which < 2 && fine; which++) {
+            for (int i = 0; i < reps + 1 && fine; i++) {          // (the first repetition warms up; the events bracket the others)
+                if (i == 1) fine = hip.event_record(e0, st) == 0;
+                if (fine)
+                    fine = (which == 0 ? rt_trace_entities_async(ctx, (const RtRay*)d_rays, n, lr, nboxes ? (const RtDrawBox*)d_boxes : nullptr, nboxes,
+                                                                 models.data(), nmodels, (RtRayHit*)d_world, (RtEntityHit*)d_hits)
+                                       : rt_trace_rays_async(ctx, (const RtRay*)d_rays, n, lr, (RtRayHit*)d_world)) == RT_OK;
+            }
+            float ms_f = 0.0f;
+            fine = fine && hip.event_record(e1, st) == 0 && hip.event_sync(e1) == 0 && hip.elapsed(&ms_f, e0, e1) == 0;
+            if (fine) device_ms[which] = (double)ms_f / reps;
+        }
+        if (rt_sync(ctx) != RT_OK || rt_set_stream(ctx, nullptr) != RT_OK) fine = false;
+        if (e0) (void)hip.event_destroy(e0);
+        if (e1) (void)hip.event_destroy(e1);
+        if (st) (void)hip.stream_destroy(st);
+        for (void* d : {d_rays, d_boxes, d_world, d_hits})
+            if (d) (void)hip.dev_free(d);
+        if (!fine) { std::fprintf(stderr, "timing the asynchronous calls failed: %s\n", rt_last_error(ctx)); delete p; return 1; }
+    }
+    std::printf("{\"entity_rays\": %u, \"coherent\": %s, \"boxes\": %u, \"models\": %u, \"model_scale\": %g, \"trace_entities_call_ms\": %.4f, "
+                "\"trace_rays_call_ms\": %.4f, \"ratio\": %.2f, \"entities_reported\": %llu, \"entities_occluded\": %llu, \"reported_under_sky\": %llu, "
+                "\"trace_entities_device_ms\": %.4f, \"trace_rays_device_ms\": %.4f}\n",
+                n, coherent ? "true" : "false", nboxes, nmodels, (double)scale, ms[0], ms[1], ms[1] > 0.0 ? ms[0] / ms[1] : 0.0,
+                (unsigned long long)reported, (unsigned long long)(met > reported ? met - reported : 0), (unsigned long long)under_sky, device_ms[0], device_ms[1]);
     delete p;
     return 0;
 }
@@ -642,6 +811,8 @@ int main(int argc, char** argv) {
     int edits = 0, edit_radius = 0;
     const char* edit_shape = nullptr;
     int edit_stamp = -1;
+    long long entity_rays = 0;
+    bool coherent = false;
     long long rays = 0, boxes = -1, lights = -1, models = -1, shadows = -1;
     bool shadow_models = false;
     float model_scale = 0.125f;
@@ -677,6 +848,8 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--stream") == 0) stream = true;
         else if (std::strcmp(argv[i], "--stream-history") == 0) stream_history = true;
         else if (want("--rays")) rays = std::atoll(argv[++i]);
+        else if (want("--entity-rays")) entity_rays = std::atoll(argv[++i]);
+        else if (std::strcmp(argv[i], "--coherent") == 0) coherent = true;
         else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
         else if (want("--boxes")) boxes = std::atoll(argv[++i]);
         else if (want("--lights")) lights = std::atoll(argv[++i]);
@@ -692,6 +865,7 @@ int main(int argc, char** argv) {
     if (stream && gpus > 1) { std::fprintf(stderr, "--stream needs one device\n"); return 2; }
     if (stream_history && (!stream || !reproject || edit_radius == 0)) { std::fprintf(stderr, "--stream-history goes with --stream --reproject --edit-radius N\n"); return 2; }
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
+    if (entity_rays < 0 || entity_rays > (1ll << 24)) { std::fprintf(stderr, "--entity-rays must be in 0..2^24\n"); return 2; }
     if (boxes < -1 || boxes > 4096) { std::fprintf(stderr, "--boxes must be in 0..4096\n"); return 2; }
     if (models < -1 || models > 4096 || !(model_scale >= 1.0f / 256.0f && model_scale <= 64.0f)) {
         std::fprintf(stderr, "--models must be in 0..4096, --model-scale in 2^-8..64\n");
@@ -727,6 +901,9 @@ int main(int argc, char** argv) {
     std::printf("Creating renderer (and world.)\n");                 // main.rs:10
     auto t0 = std::chrono::steady_clock::now();
     game.generate_world(0x5EED);
+    if (entity_rays > 0)
+        return run_entity_rays(game, noise, width, height, spp, depth, device, (uint32_t)entity_rays, (uint32_t)(boxes < 0 ? 0 : boxes),
+                               (uint32_t)(models < 0 ? 0 : models), model_scale, coherent);
     if (rays > 0) return run_rays(game, noise, width, height, spp, depth, device, (uint32_t)rays, rays_coherent);
     if (boxes >= 0) return run_boxes(game, noise, width, height, spp, depth, device, (uint32_t)boxes);
     if (models >= 0) return run_models(game, noise, width, height, spp, depth, device, (uint32_t)models, model_scale);

@@ -13,8 +13,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_DRAW_STAMPS, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
-                  RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtDrawStamp, RtInfo, RtLightProbe,
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_DRAW_STAMPS, MAX_ENTITY_RAYS, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
+                  RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtDrawStamp, RtEntityHit, RtInfo, RtLightProbe,
                   RtPointLight, RtProbeLight, RtRayHit, RtShapeEdit, RtStampPlace, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
 
@@ -84,6 +84,10 @@ assert DRAW_BOX_DTYPE.itemsize == C.sizeof(RtDrawBox)
 DRAW_STAMP_DTYPE = np.dtype([("origin", "<f4", 3), ("scale", "<f4"), ("stamp", "<u4"), ("orient", "u1"), ("reserved0", "u1", 3),
                              ("emission", "<u4"), ("reserved", "<u4")])
 assert DRAW_STAMP_DTYPE.itemsize == C.sizeof(RtDrawStamp)
+# numpy view of RtEntityHit (include/rt_abi.h)
+ENTITY_HIT_DTYPE = np.dtype([("position", "<f4", 3), ("t", "<f4"), ("kind", "<u4"), ("index", "<u4"), ("normal", "<u4"), ("material", "<u4"),
+                             ("cell", "<i4", 3), ("voxel", "<u4")])
+assert ENTITY_HIT_DTYPE.itemsize == C.sizeof(RtEntityHit) == 48
 # numpy view of RtPointLight (include/rt_abi.h)
 POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("reserved", "<u4")])
 assert POINT_LIGHT_DTYPE.itemsize == C.sizeof(RtPointLight)
@@ -370,6 +374,50 @@ class Context:
         hits = np.zeros(xy.shape[0], dtype=HIT_DTYPE)
         self._check(self._lib.rt_pick_pixels(self._h, C.byref(uniforms), _p(xy), int(xy.shape[0]), _p(hits)))
         return hits
+
+    # -- entity queries ----------------------------------------------------------------------------------
+    def trace_entities(self, origins, directions, lr=(0, 0, 0), boxes=None, models=None):
+        """rt_trace_entities: float[N, 3] origins and directions against the resident world and the drawn `boxes` (DRAW_BOX_DTYPE[B]) and
+        `models` (DRAW_STAMP_DTYPE[M]) -> (world_hits HIT_DTYPE[N], entity_hits ENTITY_HIT_DTYPE[N]).  Synchronous; an invalid record
+        fails the whole call (RtError, INVALID_ARG).  Rays that lie together should follow each other: a wave of 64 culls as one."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("origins and directions must have the same shape [N, 3]")
+        rays = np.zeros((o.shape[0], 8), dtype=np.float32)
+        rays[:, 0:3], rays[:, 4:7] = o, d
+        boxes, models = _entity_records(boxes, models)
+        world = np.zeros(o.shape[0], dtype=HIT_DTYPE)
+        hits = np.zeros(o.shape[0], dtype=ENTITY_HIT_DTYPE)
+        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
+        self._check(self._lib.rt_trace_entities(self._h, _p(rays), int(o.shape[0]), lr3, _p(boxes) if boxes.size else None, int(boxes.size),
+                                                _p(models) if models.size else None, int(models.size), _p(world), _p(hits)))
+        return world, hits
+
+    def pick_entities(self, uniforms, xy, boxes=None, models=None):
+        """rt_pick_entities: int[N, 2] whole-frame pixels (x, y), row 0 = bottom, of the camera in `uniforms` -> (world_hits HIT_DTYPE[N]
+        as pick_pixels gives them, entity_hits ENTITY_HIT_DTYPE[N]): kind != RT_ENTITY_NONE where rt_draw_boxes / rt_draw_stamps with the
+        same records draw an entity into that pixel."""
+        xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        boxes, models = _entity_records(boxes, models)
+        world = np.zeros(xy.shape[0], dtype=HIT_DTYPE)
+        hits = np.zeros(xy.shape[0], dtype=ENTITY_HIT_DTYPE)
+        self._check(self._lib.rt_pick_entities(self._h, C.byref(uniforms), _p(xy), int(xy.shape[0]), _p(boxes) if boxes.size else None,
+                                               int(boxes.size), _p(models) if models.size else None, int(models.size), _p(world), _p(hits)))
+        return world, hits
+
+    def trace_entities_async(self, rays, boxes, models, world_hits, entity_hits, lr=(0, 0, 0)):
+        """rt_trace_entities_async on torch device tensors: `rays` float32[N, 8] as for trace_rays_async, `boxes` any contiguous tensor of
+        B * 32 bytes (RtDrawBox rows) or None, `world_hits` any contiguous tensor of N * 48 bytes or None, `entity_hits` likewise (not
+        None); `models` host records as for draw_stamps_async (free again on return).  Enqueued: valid after sync(), or in the order of
+        a stream given to set_stream().  An invalid box is skipped on the device, an invalid model fails the call."""
+        n, nb = check_entity_query_tensors(rays, boxes, world_hits, entity_hits, self.cfg.device if self.cfg is not None else 0)
+        _, models = _entity_records(None, models)
+        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
+        self._check(self._lib.rt_trace_entities_async(self._h, C.c_void_p(rays.data_ptr()), n, lr3, C.c_void_p(boxes.data_ptr()) if nb else None, nb,
+                                                      _p(models) if models.size else None, int(models.size),
+                                                      C.c_void_p(world_hits.data_ptr()) if world_hits is not None else None,
+                                                      C.c_void_p(entity_hits.data_ptr())))
 
     # -- light probes ------------------------------------------------------------------------------------
     def probe_light(self, uniforms, positions, normals, cells, samples, depth):
@@ -863,6 +911,21 @@ class Pipeline:
         return {"hit": h, "texel": tuple(int(v) for v in h["texel"]), "normal": int(h["normal"]), "kind": int(h["kind"]),
                 "adjacent": tuple(adj[:]), "world": tuple(wld[:])}
 
+    def pick_entity(self, x, y_from_top):
+        """Pipeline::pick_entity: the entity under screen pixel (x, y_from_top) among the boxes and models of set_boxes / set_models,
+        under the uniforms of the frame drawn last.  Returns a dict: `entity` (ENTITY_HIT_DTYPE record; kind != RT_ENTITY_NONE means
+        the cursor is on an entity) and the world's `hit`, `texel`, `normal`, `kind`, `adjacent` and `world` as pick gives them."""
+        ent = np.zeros(1, dtype=ENTITY_HIT_DTYPE)
+        hit = np.zeros(1, dtype=HIT_DTYPE)
+        adj = (C.c_int32 * 3)()
+        wld = (C.c_int32 * 3)()
+        rc = _lib.host().rth_pipeline_pick_entity(self._h, int(x), int(y_from_top), _p(ent), _p(hit), adj, wld)
+        if rc != 0:
+            raise RtError(rc, _lib.host().rth_pipeline_last_error(self._h).decode())
+        h = hit[0]
+        return {"entity": ent[0], "hit": h, "texel": tuple(int(v) for v in h["texel"]), "normal": int(h["normal"]), "kind": int(h["kind"]),
+                "adjacent": tuple(adj[:]), "world": tuple(wld[:])}
+
     def set_boxes(self, boxes=None, face_lights=None):
         """Pipeline::set_boxes: every draw_frame from now on enqueues rt_draw_boxes for this set between the ray trace and the denoise
         (DRAW_BOX_DTYPE[N] and PROBE_LIGHT_DTYPE[6 N], copied); None or an empty set draws none."""
@@ -964,6 +1027,49 @@ def check_query_tensors(rays, hits, device):
     if not hits.is_contiguous() or hits.numel() * hits.element_size() != n * HIT_DTYPE.itemsize:
         raise ValueError("hits must be a contiguous tensor of N * 48 bytes")
     return n
+
+
+def _entity_records(boxes, models):
+    """The entity queries' host records: contiguous DRAW_BOX_DTYPE and DRAW_STAMP_DTYPE arrays (empty for None)."""
+    boxes = np.zeros(0, dtype=DRAW_BOX_DTYPE) if boxes is None else np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
+    models = np.zeros(0, dtype=DRAW_STAMP_DTYPE) if models is None else np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
+    return boxes, models
+
+
+def check_entity_query_tensors(rays, boxes, world_hits, entity_hits, device):
+    """Context.trace_entities_async's device arguments: `rays` a contiguous float32[N, 8] tensor, `boxes` a contiguous tensor of B * 32
+    bytes or None, `world_hits` a contiguous tensor of N * 48 bytes or None, `entity_hits` a contiguous tensor of N * 48 bytes, all on
+    GPU `device` and 16-byte aligned, N at most 2^24 and B at most 4096.  Returns (N, B); raises ValueError otherwise (a host tensor's
+    address handed to the kernel would fault the device)."""
+    import torch
+    given = [("rays", rays), ("entity_hits", entity_hits)] + [(k, t) for k, t in (("boxes", boxes), ("world_hits", world_hits)) if t is not None]
+    for name, t in given:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a torch tensor" % name)
+    for name, t in given:
+        if not t.is_cuda or t.device.index != int(device):
+            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
+        if t.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned" % name)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError("rays must be a contiguous float32 tensor of shape [N, 8]")
+    n = int(rays.shape[0])
+    if n > MAX_ENTITY_RAYS:
+        raise ValueError("at most 2^24 rays per call")
+    for name, t in (("world_hits", world_hits), ("entity_hits", entity_hits)):
+        if t is not None and t.numel() * t.element_size() != n * ENTITY_HIT_DTYPE.itemsize:
+            raise ValueError("%s must be a contiguous tensor of N * 48 bytes" % name)
+    nb = 0
+    if boxes is not None:
+        nbytes = boxes.numel() * boxes.element_size()
+        if nbytes % DRAW_BOX_DTYPE.itemsize:
+            raise ValueError("boxes must hold whole 32-byte RtDrawBox records")
+        nb = nbytes // DRAW_BOX_DTYPE.itemsize
+        if nb > MAX_DRAW_BOXES:
+            raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
+    return n, nb
 
 
 def make_sweeps(sweeps):
