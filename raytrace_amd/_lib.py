@@ -1,5 +1,8 @@
 """Loads the in-tree native libraries.  There is no Python or CPU fallback: if librt_amd.so is missing the
-import fails loudly (build it with `python -m raytrace_amd.build`)."""
+import fails loudly (build it with `python -m raytrace_amd.build`).
+
+Each library's signatures are one table, name -> (restype, argtypes), applied when it is loaded; restype None is `void`.
+tests/test_lib_signatures.py holds AMD_FUNCTIONS against include/rt_abi.h: the same functions, the same parameter counts."""
 import ctypes as C
 import os
 
@@ -10,24 +13,162 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_AMD_PATH = os.environ.get("RT_AMD_LIB") or os.path.join(HERE, "librt_amd.so")
 LIB_HOST_PATH = os.path.join(HERE, "librt_host.so")
 
-# Every symbol include/rt_abi.h declares.
-ABI_SYMBOLS = (
-    "rt_create", "rt_destroy", "rt_last_error", "rt_upload_world", "rt_upload_slice", "rt_slice_staging", "rt_upload_noise",
-    "rt_draw_frame", "rt_sync", "rt_readback", "rt_buffer_bytes", "rt_device_ptr", "rt_set_stream",
-    "rt_tile_count", "rt_tile_capacity", "rt_untile", "rt_gbuffer_ptr", "rt_gbuffer_bytes", "rt_gbuffer_offset",
-    "rt_untile_gbuffer", "rt_denoise", "rt_finalize", "rt_denoise_planes", "rt_finalize_planes", "rt_kernel_in_use", "rt_get_counters", "rt_reset_counters", "rt_get_timing",
-    "rt_abi_version",
-    "rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer", "rt_frame_ptr",
-    "rt_frame_readback", "rt_selftest", "rt_get_info", "rt_samples_per_launch", "rt_get_gather_timing",
-    "rt_reset_accumulation", "rt_get_accumulation", "rt_edit_voxels", "rt_read_box",
-    "rt_trace_rays", "rt_trace_rays_async", "rt_pick_pixels", "rt_generate_world", "rt_generate_slice", "rt_read_history",
-    "rt_edit_boxes_pending", "rt_slabs_pending", "rt_read_slab_boxes", "rt_probe_light", "rt_probe_light_async",
-    "rt_denoise_history", "rt_denoise_planes_counted", "rt_sweep_boxes", "rt_sweep_boxes_async",
-    "rt_edit_shapes", "rt_draw_boxes", "rt_draw_boxes_async", "rt_add_lights", "rt_add_lights_async",
-    "rt_stamp_create", "rt_stamp_capture", "rt_stamp_info", "rt_stamp_read", "rt_stamp_destroy", "rt_edit_stamps",
-    "rt_draw_stamps", "rt_draw_stamps_async", "rt_shadow_entities", "rt_shadow_entities_async",
-    "rt_trace_entities", "rt_trace_entities_async", "rt_pick_entities",
-)
+P, PP, STR = C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p
+INT, LONG, SIZE, FLOAT, U8, U32, U64 = C.c_int, C.c_long, C.c_size_t, C.c_float, C.c_uint8, C.c_uint32, C.c_uint64
+I32P, U32P, I64P = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
+UNI, DENOISE = C.POINTER(RtUniforms), C.POINTER(RtDenoiseParams)
+
+# Every function include/rt_abi.h declares; P first is the RtContext*.
+AMD_FUNCTIONS = {
+    "rt_abi_version": (U32, []),
+    "rt_create": (INT, [C.POINTER(RtConfig), PP]),
+    "rt_destroy": (None, [P]),
+    "rt_last_error": (STR, [P]),
+    "rt_get_info": (INT, [P, C.POINTER(RtInfo)]),
+    "rt_samples_per_launch": (U64, [U64, U64, U64, STR]),
+    # the world: uploads, edits, stamps, generated terrain
+    "rt_upload_world": (INT, [P, P, P]),
+    "rt_upload_slice": (INT, [P, INT, INT, P, P]),
+    "rt_slice_staging": (INT, [P, PP, PP]),
+    "rt_upload_noise": (INT, [P, P]),
+    "rt_edit_voxels": (INT, [P, C.POINTER(RtVoxelEdit), U32]),
+    "rt_edit_shapes": (INT, [P, C.POINTER(RtShapeEdit), U32]),
+    "rt_stamp_create": (INT, [P, I32P, P, P, U32P]),
+    "rt_stamp_capture": (INT, [P, I32P, I32P, U32, U32P]),
+    "rt_stamp_info": (INT, [P, U32, I32P]),
+    "rt_stamp_read": (INT, [P, U32, P, P]),
+    "rt_stamp_destroy": (INT, [P, U32]),
+    "rt_edit_stamps": (INT, [P, C.POINTER(RtStampPlace), U32]),
+    "rt_read_box": (INT, [P, INT, INT, INT, INT, INT, INT, P, P]),
+    "rt_generate_world": (INT, [P, U64, I64P]),
+    "rt_generate_slice": (INT, [P, U64, INT, I64P]),
+    # queries
+    "rt_trace_rays": (INT, [P, P, U32, I32P, P]),
+    "rt_trace_rays_async": (INT, [P, P, U32, I32P, P]),
+    "rt_pick_pixels": (INT, [P, UNI, P, U32, P]),
+    "rt_probe_light": (INT, [P, UNI, P, U32, U32, C.c_int32, P]),
+    "rt_probe_light_async": (INT, [P, UNI, P, U32, U32, C.c_int32, P]),
+    "rt_sweep_boxes": (INT, [P, P, U32, I32P, P]),
+    "rt_sweep_boxes_async": (INT, [P, P, U32, I32P, P]),
+    "rt_trace_entities": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
+    "rt_trace_entities_async": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
+    "rt_pick_entities": (INT, [P, UNI, P, U32, P, U32, P, U32, P, P]),
+    # the frame and the passes over it
+    "rt_draw_frame": (INT, [P, UNI]),
+    "rt_draw_boxes": (INT, [P, UNI, P, P, U32]),
+    "rt_draw_boxes_async": (INT, [P, UNI, P, P, U32]),
+    "rt_draw_stamps": (INT, [P, UNI, P, P, U32]),
+    "rt_draw_stamps_async": (INT, [P, UNI, P, P, U32]),
+    "rt_shadow_entities": (INT, [P, UNI, P, U32, P, U32, FLOAT]),
+    "rt_shadow_entities_async": (INT, [P, UNI, P, U32, P, U32, FLOAT]),
+    "rt_add_lights": (INT, [P, UNI, P, U32]),
+    "rt_add_lights_async": (INT, [P, UNI, P, U32]),
+    "rt_denoise": (INT, [P, INT]),
+    "rt_finalize": (INT, [P]),
+    "rt_denoise_planes": (INT, [P, P, P, P, INT]),
+    "rt_finalize_planes": (INT, [P, P, P, P, P, P, P]),
+    "rt_denoise_history": (INT, [P, DENOISE]),
+    "rt_denoise_planes_counted": (INT, [P, P, P, P, P, DENOISE]),
+    # streams, planes, tiles
+    "rt_sync": (INT, [P]),
+    "rt_set_stream": (INT, [P, P]),
+    "rt_readback": (INT, [P, INT, P, SIZE]),
+    "rt_buffer_bytes": (SIZE, [P, INT]),
+    "rt_device_ptr": (P, [P, INT]),
+    "rt_tile_count": (INT, [P]),
+    "rt_tile_capacity": (INT, [P]),
+    "rt_untile": (INT, [P, INT, P, INT, P]),
+    "rt_gbuffer_ptr": (P, [P]),
+    "rt_gbuffer_bytes": (SIZE, [P]),
+    "rt_gbuffer_offset": (SIZE, [P, INT]),
+    "rt_untile_gbuffer": (INT, [P, P, INT, P]),
+    # multi-GPU frame assembly
+    "rt_comm_unique_id": (INT, [P, SIZE]),
+    "rt_comm_init_rank": (INT, [P, P, SIZE, PP]),
+    "rt_comm_init_all": (INT, [INT, C.POINTER(INT), PP]),
+    "rt_comm_destroy": (INT, [P]),
+    "rt_gather_gbuffer": (INT, [P, P, INT, P, INT]),
+    "rt_frame_ptr": (P, [P, INT]),
+    "rt_frame_readback": (INT, [P, INT, P, SIZE]),
+    # instrumentation and host-side state
+    "rt_kernel_in_use": (INT, [P]),
+    "rt_selftest": (INT, [P, INT, C.POINTER(U64)]),
+    "rt_get_counters": (INT, [P, C.POINTER(RtCounters)]),
+    "rt_reset_counters": (INT, [P]),
+    "rt_get_timing": (INT, [P, C.POINTER(RtTiming)]),
+    "rt_get_gather_timing": (INT, [P, C.POINTER(FLOAT), U32P]),
+    "rt_reset_accumulation": (INT, [P]),
+    "rt_get_accumulation": (INT, [P, U32P, U32P]),
+    "rt_read_history": (INT, [P, P, SIZE]),
+    "rt_edit_boxes_pending": (INT, [P, U32P, U32P]),
+    "rt_slabs_pending": (INT, [P, U32P, U32P]),
+    "rt_read_slab_boxes": (INT, [P, P, U32P]),
+}
+ABI_SYMBOLS = tuple(AMD_FUNCTIONS)
+
+# The C surface of the host mirror (host/host_capi.cpp) that the package calls.
+HOST_FUNCTIONS = {
+    "rth_material_pack": (U32, [INT]),
+    "rth_material_unpack": (None, [U32, P, P]),
+    "rth_material_get": (INT, [INT, P, P, P]),
+    "rth_pack_chunk": (INT, [P, P, P]),
+    "rth_generate_region": (INT, [U64, P, P]),
+    "rth_generate_region_r": (INT, [U64, INT, P, P]),
+    "rth_region_from_ids": (INT, [P, P, P]),
+    "rth_heightmap": (INT, [LONG, LONG, U64, P]),
+    "rth_copy_3d_u32": (INT, [P] * 7),
+    "rth_copy_3d_auto_clip_u32": (None, [P, INT, P, P, INT]),
+    "rth_copy_3d_bounded_auto_clip_u32": (None, [P] * 7),
+    "rth_fill_slice_3d_auto_clip_u8": (None, [U8, P, INT, P, P]),
+    "rth_chunk_codec_available": (INT, []),
+    "rth_chunk_file_name": (None, [LONG, LONG, LONG, P]),
+    "rth_chunk_write": (INT, [STR, P, P]),
+    "rth_chunk_read": (INT, [STR, P, P]),
+    "rth_chunk_storage_new": (P, [STR, U64]),
+    "rth_chunk_storage_free": (None, [P]),
+    "rth_chunk_storage_borrow": (INT, [P, LONG, LONG, LONG, P, P]),
+    "rth_chunk_storage_stats": (None, [P, P, P]),
+    "rth_tum_new": (P, [U64]),
+    "rth_tum_new_r": (P, [U64, INT]),
+    "rth_tum_free": (None, [P]),
+    "rth_tum_request": (None, [P, INT, INT]),
+    "rth_tum_move_towards": (None, [P, P]),
+    "rth_tum_pending": (INT, [P]),
+    "rth_tum_step": (INT, [P]),
+    "rth_tum_render_offset": (None, [P, P]),
+    "rth_tum_next_window": (INT, [P, P, P]),
+    "rth_tum_region": (None, [P, P, P]),
+    "rth_compute_triple_euler_vector": (None, [FLOAT, FLOAT, P, P, P]),
+    "rth_game_new": (P, [INT, P]),
+    "rth_game_free": (None, [P]),
+    "rth_game_set_camera": (None, [P, P, FLOAT, FLOAT]),
+    "rth_game_get_camera": (None, [P, P, P, P]),
+    "rth_game_set_sun_angle": (None, [P, FLOAT]),
+    "rth_game_get_sun_angle": (FLOAT, [P]),
+    "rth_game_set_world": (INT, [P, P, P]),
+    "rth_game_set_world_r": (INT, [P, P, P, INT]),
+    "rth_game_generate_world": (INT, [P, U64]),
+    "rth_game_generate_world_r": (INT, [P, U64, INT]),
+    "rth_game_use_device_world": (INT, [P, U64, INT]),
+    "rth_create_instance": (P, [C.POINTER(RtConfig), P, P, P, SIZE]),
+    "rth_pipeline_free": (None, [P]),
+    "rth_pipeline_draw_frame": (INT, [P, P]),
+    "rth_pipeline_wait": (INT, [P]),
+    "rth_pipeline_context": (P, [P]),
+    "rth_pipeline_uniforms": (None, [P, UNI]),
+    "rth_pipeline_set_seed": (None, [P, U32]),
+    "rth_pipeline_enable_streaming": (None, [P, U64, STR]),
+    "rth_pipeline_enable_streaming_on_device": (None, [P, U64]),
+    "rth_pipeline_enable_post_passes": (INT, [P, INT]),
+    "rth_pipeline_enable_history_denoise": (INT, [P, DENOISE]),
+    "rth_pipeline_last_error": (STR, [P]),
+    "rth_pipeline_pick": (INT, [P, INT, INT, P, I32P, I32P]),
+    "rth_pipeline_pick_entity": (INT, [P, INT, INT, P, P, I32P, I32P]),
+    "rth_pipeline_set_boxes": (INT, [P, P, P, U32]),
+    "rth_pipeline_set_models": (INT, [P, P, P, U32]),
+    "rth_pipeline_set_lights": (INT, [P, P, U32]),
+    "rth_pipeline_enable_entity_shadows": (INT, [P, FLOAT]),
+}
 
 _amd = None
 _host = None
@@ -35,6 +176,13 @@ _host = None
 
 class NativeLibraryMissing(ImportError):
     pass
+
+
+def _declare(lib, functions):
+    for name, (restype, argtypes) in functions.items():
+        f = getattr(lib, name)
+        f.restype, f.argtypes = restype, argtypes
+    return lib
 
 
 def amd():
@@ -45,142 +193,7 @@ def amd():
             raise NativeLibraryMissing(
                 "%s not found: the HIP extension is required (run `python -m raytrace_amd.build`); "
                 "there is no CPU fallback" % LIB_AMD_PATH)
-        lib = C.CDLL(LIB_AMD_PATH, mode=C.RTLD_GLOBAL)
-        P = C.c_void_p
-        lib.rt_create.argtypes = [C.POINTER(RtConfig), C.POINTER(P)]
-        lib.rt_create.restype = C.c_int
-        lib.rt_destroy.argtypes = [P]
-        lib.rt_destroy.restype = None
-        lib.rt_last_error.argtypes = [P]
-        lib.rt_last_error.restype = C.c_char_p
-        lib.rt_upload_world.argtypes = [P, P, P]
-        lib.rt_upload_slice.argtypes = [P, C.c_int, C.c_int, P, P]
-        lib.rt_slice_staging.argtypes = [P, C.POINTER(P), C.POINTER(P)]
-        lib.rt_upload_noise.argtypes = [P, P]
-        lib.rt_draw_frame.argtypes = [P, C.POINTER(RtUniforms)]
-        lib.rt_sync.argtypes = [P]
-        lib.rt_readback.argtypes = [P, C.c_int, P, C.c_size_t]
-        lib.rt_buffer_bytes.argtypes = [P, C.c_int]
-        lib.rt_buffer_bytes.restype = C.c_size_t
-        lib.rt_device_ptr.argtypes = [P, C.c_int]
-        lib.rt_device_ptr.restype = P
-        lib.rt_set_stream.argtypes = [P, P]
-        lib.rt_tile_count.argtypes = [P]
-        lib.rt_tile_capacity.argtypes = [P]
-        lib.rt_untile.argtypes = [P, C.c_int, P, C.c_int, P]
-        lib.rt_gbuffer_ptr.argtypes = [P]
-        lib.rt_gbuffer_ptr.restype = P
-        lib.rt_gbuffer_bytes.argtypes = [P]
-        lib.rt_gbuffer_bytes.restype = C.c_size_t
-        lib.rt_gbuffer_offset.argtypes = [P, C.c_int]
-        lib.rt_gbuffer_offset.restype = C.c_size_t
-        lib.rt_untile_gbuffer.argtypes = [P, P, C.c_int, P]
-        lib.rt_untile_gbuffer.restype = C.c_int
-        lib.rt_denoise.argtypes = [P, C.c_int]
-        lib.rt_finalize.argtypes = [P]
-        lib.rt_denoise_planes.argtypes = [P, P, P, P, C.c_int]
-        lib.rt_finalize_planes.argtypes = [P, P, P, P, P, P, P]
-        lib.rt_denoise_history.argtypes = [P, C.POINTER(RtDenoiseParams)]
-        lib.rt_denoise_history.restype = C.c_int
-        lib.rt_denoise_planes_counted.argtypes = [P, P, P, P, P, C.POINTER(RtDenoiseParams)]
-        lib.rt_denoise_planes_counted.restype = C.c_int
-        lib.rt_kernel_in_use.argtypes = [P]
-        lib.rt_kernel_in_use.restype = C.c_int
-        lib.rt_get_counters.argtypes = [P, C.POINTER(RtCounters)]
-        lib.rt_reset_counters.argtypes = [P]
-        lib.rt_get_timing.argtypes = [P, C.POINTER(RtTiming)]
-        lib.rt_get_info.argtypes = [P, C.POINTER(RtInfo)]
-        lib.rt_get_info.restype = C.c_int
-        lib.rt_abi_version.restype = C.c_uint32
-        lib.rt_samples_per_launch.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p]
-        lib.rt_samples_per_launch.restype = C.c_uint64
-        lib.rt_get_gather_timing.argtypes = [P, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
-        lib.rt_get_gather_timing.restype = C.c_int
-        lib.rt_comm_unique_id.argtypes = [P, C.c_size_t]
-        lib.rt_comm_init_rank.argtypes = [P, P, C.c_size_t, C.POINTER(P)]
-        lib.rt_comm_init_all.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(P)]
-        lib.rt_comm_destroy.argtypes = [P]
-        lib.rt_gather_gbuffer.argtypes = [P, P, C.c_int, P, C.c_int]
-        lib.rt_frame_ptr.argtypes = [P, C.c_int]
-        lib.rt_frame_ptr.restype = P
-        lib.rt_frame_readback.argtypes = [P, C.c_int, P, C.c_size_t]
-        lib.rt_frame_readback.restype = C.c_int
-        lib.rt_selftest.argtypes = [P, C.c_int, C.POINTER(C.c_uint64)]
-        lib.rt_selftest.restype = C.c_int
-        lib.rt_reset_accumulation.argtypes = [P]
-        lib.rt_reset_accumulation.restype = C.c_int
-        lib.rt_get_accumulation.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        lib.rt_get_accumulation.restype = C.c_int
-        lib.rt_read_history.argtypes = [P, P, C.c_size_t]
-        lib.rt_read_history.restype = C.c_int
-        lib.rt_edit_boxes_pending.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        lib.rt_edit_boxes_pending.restype = C.c_int
-        lib.rt_slabs_pending.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        lib.rt_slabs_pending.restype = C.c_int
-        lib.rt_read_slab_boxes.argtypes = [P, P, C.POINTER(C.c_uint32)]
-        lib.rt_read_slab_boxes.restype = C.c_int
-        lib.rt_edit_voxels.argtypes = [P, C.POINTER(RtVoxelEdit), C.c_uint32]
-        lib.rt_edit_voxels.restype = C.c_int
-        lib.rt_edit_shapes.argtypes = [P, C.POINTER(RtShapeEdit), C.c_uint32]
-        lib.rt_edit_shapes.restype = C.c_int
-        lib.rt_stamp_create.argtypes = [P, C.POINTER(C.c_int32), P, P, C.POINTER(C.c_uint32)]
-        lib.rt_stamp_capture.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_uint32)]
-        lib.rt_stamp_info.argtypes = [P, C.c_uint32, C.POINTER(C.c_int32)]
-        lib.rt_stamp_read.argtypes = [P, C.c_uint32, P, P]
-        lib.rt_stamp_destroy.argtypes = [P, C.c_uint32]
-        lib.rt_edit_stamps.argtypes = [P, C.POINTER(RtStampPlace), C.c_uint32]
-        for name in ("rt_stamp_create", "rt_stamp_capture", "rt_stamp_info", "rt_stamp_read", "rt_stamp_destroy", "rt_edit_stamps"):
-            getattr(lib, name).restype = C.c_int
-        lib.rt_read_box.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]
-        lib.rt_read_box.restype = C.c_int
-        lib.rt_trace_rays.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
-        lib.rt_trace_rays.restype = C.c_int
-        lib.rt_trace_rays_async.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
-        lib.rt_trace_rays_async.restype = C.c_int
-        lib.rt_pick_pixels.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P]
-        lib.rt_pick_pixels.restype = C.c_int
-        lib.rt_probe_light.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, C.c_uint32, C.c_int32, P]
-        lib.rt_probe_light.restype = C.c_int
-        lib.rt_probe_light_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, C.c_uint32, C.c_int32, P]
-        lib.rt_probe_light_async.restype = C.c_int
-        lib.rt_sweep_boxes.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
-        lib.rt_sweep_boxes.restype = C.c_int
-        lib.rt_sweep_boxes_async.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P]
-        lib.rt_sweep_boxes_async.restype = C.c_int
-        lib.rt_draw_boxes.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
-        lib.rt_draw_boxes.restype = C.c_int
-        lib.rt_draw_boxes_async.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
-        lib.rt_draw_boxes_async.restype = C.c_int
-        lib.rt_draw_stamps.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
-        lib.rt_draw_stamps.restype = C.c_int
-        lib.rt_draw_stamps_async.argtypes = [P, C.POINTER(RtUniforms), P, P, C.c_uint32]
-        lib.rt_draw_stamps_async.restype = C.c_int
-        lib.rt_shadow_entities.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P, C.c_uint32, C.c_float]
-        lib.rt_shadow_entities.restype = C.c_int
-        lib.rt_shadow_entities_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P, C.c_uint32, C.c_float]
-        lib.rt_shadow_entities_async.restype = C.c_int
-        lib.rt_trace_entities.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P, C.c_uint32, P, C.c_uint32, P, P]
-        lib.rt_trace_entities.restype = C.c_int
-        lib.rt_trace_entities_async.argtypes = [P, P, C.c_uint32, C.POINTER(C.c_int32), P, C.c_uint32, P, C.c_uint32, P, P]
-        lib.rt_trace_entities_async.restype = C.c_int
-        lib.rt_pick_entities.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, P]
-        lib.rt_pick_entities.restype = C.c_int
-        lib.rt_add_lights.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
-        lib.rt_add_lights.restype = C.c_int
-        lib.rt_add_lights_async.argtypes = [P, C.POINTER(RtUniforms), P, C.c_uint32]
-        lib.rt_add_lights_async.restype = C.c_int
-        lib.rt_generate_world.argtypes = [P, C.c_uint64, C.POINTER(C.c_int64)]
-        lib.rt_generate_world.restype = C.c_int
-        lib.rt_generate_slice.argtypes = [P, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]
-        lib.rt_generate_slice.restype = C.c_int
-        for name in ("rt_comm_unique_id", "rt_comm_init_rank", "rt_comm_init_all", "rt_comm_destroy", "rt_gather_gbuffer"):
-            getattr(lib, name).restype = C.c_int
-        for name in ("rt_upload_world", "rt_upload_slice", "rt_slice_staging", "rt_upload_noise", "rt_draw_frame", "rt_sync", "rt_readback",
-                     "rt_set_stream", "rt_tile_count", "rt_tile_capacity", "rt_untile", "rt_untile_gbuffer", "rt_denoise", "rt_finalize",
-                     "rt_denoise_planes", "rt_finalize_planes", "rt_get_counters",
-                     "rt_reset_counters", "rt_get_timing"):
-            getattr(lib, name).restype = C.c_int
-        _amd = lib
+        _amd = _declare(C.CDLL(LIB_AMD_PATH, mode=C.RTLD_GLOBAL), AMD_FUNCTIONS)
     return _amd
 
 
@@ -192,91 +205,5 @@ def host():
         if not os.path.exists(LIB_HOST_PATH):
             raise NativeLibraryMissing("%s not found (run `python -m raytrace_amd.build`)" % LIB_HOST_PATH)
         # RT_HOST_LIB: another build of the same sources (the CPU sanitizer build, `make -C oracle asan`)
-        lib = C.CDLL(os.environ.get("RT_HOST_LIB") or LIB_HOST_PATH)
-        P = C.c_void_p
-        lib.rth_material_pack.argtypes = [C.c_int]
-        lib.rth_material_pack.restype = C.c_uint32
-        lib.rth_material_unpack.argtypes = [C.c_uint32, P, P]
-        lib.rth_material_get.argtypes = [C.c_int, P, P, P]
-        lib.rth_pack_chunk.argtypes = [P, P, P]
-        lib.rth_generate_region.argtypes = [C.c_uint64, P, P]
-        lib.rth_generate_region_r.argtypes = [C.c_uint64, C.c_int, P, P]
-        lib.rth_region_from_ids.argtypes = [P, P, P]
-        lib.rth_heightmap.argtypes = [C.c_long, C.c_long, C.c_uint64, P]
-        lib.rth_copy_3d_u32.argtypes = [P] * 7
-        lib.rth_copy_3d_auto_clip_u32.argtypes = [P, C.c_int, P, P, C.c_int]
-        lib.rth_copy_3d_bounded_auto_clip_u32.argtypes = [P] * 7
-        lib.rth_fill_slice_3d_auto_clip_u8.argtypes = [C.c_uint8, P, C.c_int, P, P]
-        lib.rth_chunk_codec_available.restype = C.c_int
-        lib.rth_chunk_file_name.argtypes = [C.c_long, C.c_long, C.c_long, P]
-        lib.rth_chunk_write.argtypes = [C.c_char_p, P, P]
-        lib.rth_chunk_read.argtypes = [C.c_char_p, P, P]
-        lib.rth_chunk_storage_new.argtypes = [C.c_char_p, C.c_uint64]
-        lib.rth_chunk_storage_new.restype = P
-        lib.rth_chunk_storage_free.argtypes = [P]
-        lib.rth_chunk_storage_free.restype = None
-        lib.rth_chunk_storage_borrow.argtypes = [P, C.c_long, C.c_long, C.c_long, P, P]
-        lib.rth_chunk_storage_stats.argtypes = [P, P, P]
-        lib.rth_tum_new.argtypes = [C.c_uint64]
-        lib.rth_tum_new.restype = P
-        lib.rth_tum_new_r.argtypes = [C.c_uint64, C.c_int]
-        lib.rth_tum_new_r.restype = P
-        lib.rth_tum_free.argtypes = [P]
-        lib.rth_tum_free.restype = None
-        lib.rth_tum_request.argtypes = [P, C.c_int, C.c_int]
-        lib.rth_tum_move_towards.argtypes = [P, P]
-        lib.rth_tum_pending.argtypes = [P]
-        lib.rth_tum_step.argtypes = [P]
-        lib.rth_tum_render_offset.argtypes = [P, P]
-        lib.rth_tum_next_window.argtypes = [P, P, P]
-        lib.rth_tum_next_window.restype = C.c_int
-        lib.rth_tum_region.argtypes = [P, P, P]
-        lib.rth_pipeline_enable_streaming.argtypes = [P, C.c_uint64, C.c_char_p]
-        lib.rth_pipeline_enable_streaming.restype = None
-        lib.rth_pipeline_enable_streaming_on_device.argtypes = [P, C.c_uint64]
-        lib.rth_pipeline_enable_streaming_on_device.restype = None
-        lib.rth_compute_triple_euler_vector.argtypes = [C.c_float, C.c_float, P, P, P]
-        lib.rth_game_new.argtypes = [C.c_int, P]
-        lib.rth_game_new.restype = P
-        lib.rth_game_free.argtypes = [P]
-        lib.rth_game_free.restype = None
-        lib.rth_game_set_camera.argtypes = [P, P, C.c_float, C.c_float]
-        lib.rth_game_get_camera.argtypes = [P, P, P, P]
-        lib.rth_game_set_sun_angle.argtypes = [P, C.c_float]
-        lib.rth_game_get_sun_angle.argtypes = [P]
-        lib.rth_game_get_sun_angle.restype = C.c_float
-        lib.rth_game_set_world.argtypes = [P, P, P]
-        lib.rth_game_set_world_r.argtypes = [P, P, P, C.c_int]
-        lib.rth_game_generate_world.argtypes = [P, C.c_uint64]
-        lib.rth_game_generate_world_r.argtypes = [P, C.c_uint64, C.c_int]
-        lib.rth_game_use_device_world.argtypes = [P, C.c_uint64, C.c_int]
-        lib.rth_create_instance.argtypes = [C.POINTER(RtConfig), P, P, P, C.c_size_t]
-        lib.rth_create_instance.restype = P
-        lib.rth_pipeline_free.argtypes = [P]
-        lib.rth_pipeline_free.restype = None
-        lib.rth_pipeline_draw_frame.argtypes = [P, P]
-        lib.rth_pipeline_wait.argtypes = [P]
-        lib.rth_pipeline_context.argtypes = [P]
-        lib.rth_pipeline_context.restype = P
-        lib.rth_pipeline_uniforms.argtypes = [P, C.POINTER(RtUniforms)]
-        lib.rth_pipeline_set_seed.argtypes = [P, C.c_uint32]
-        lib.rth_pipeline_enable_post_passes.argtypes = [P, C.c_int]
-        lib.rth_pipeline_enable_post_passes.restype = C.c_int
-        lib.rth_pipeline_enable_history_denoise.argtypes = [P, C.POINTER(RtDenoiseParams)]
-        lib.rth_pipeline_enable_history_denoise.restype = C.c_int
-        lib.rth_pipeline_last_error.argtypes = [P]
-        lib.rth_pipeline_last_error.restype = C.c_char_p
-        lib.rth_pipeline_pick.argtypes = [P, C.c_int, C.c_int, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        lib.rth_pipeline_pick.restype = C.c_int
-        lib.rth_pipeline_set_boxes.argtypes = [P, P, P, C.c_uint32]
-        lib.rth_pipeline_set_boxes.restype = C.c_int
-        lib.rth_pipeline_set_models.argtypes = [P, P, P, C.c_uint32]
-        lib.rth_pipeline_set_models.restype = C.c_int
-        lib.rth_pipeline_set_lights.argtypes = [P, P, C.c_uint32]
-        lib.rth_pipeline_set_lights.restype = C.c_int
-        lib.rth_pipeline_enable_entity_shadows.argtypes = [P, C.c_float]
-        lib.rth_pipeline_enable_entity_shadows.restype = C.c_int
-        lib.rth_pipeline_pick_entity.argtypes = [P, C.c_int, C.c_int, P, P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        lib.rth_pipeline_pick_entity.restype = C.c_int
-        _host = lib
+        _host = _declare(C.CDLL(os.environ.get("RT_HOST_LIB") or LIB_HOST_PATH), HOST_FUNCTIONS)
     return _host

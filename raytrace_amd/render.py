@@ -42,6 +42,64 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ptr_or_none(a):
+    """The host array's address, or NULL for an empty one (the library takes NULL with a count of 0)."""
+    return _p(a) if a.size else None
+
+
+def _dp(t):
+    """A device tensor's address (NULL for None)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _lr3(v):
+    """An int32[3] argument: a render offset `lr`, a texel, an extent."""
+    return (C.c_int32 * 3)(*[int(x) for x in v])
+
+
+def _records(x, dtype):
+    """Host data as the library reads it: a contiguous flat array of `dtype`; None is the empty array."""
+    return np.zeros(0, dtype=dtype) if x is None else np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+
+
+def _rows(rows, dtype):
+    """A ready array of `dtype` records, or a sequence of single rows (box_shape, stamp_place), as contiguous records."""
+    if not (isinstance(rows, np.ndarray) and rows.dtype == dtype):
+        rows = np.array([np.asarray(s, dtype=dtype) for s in rows], dtype=dtype)
+    return np.ascontiguousarray(rows).reshape(-1)
+
+
+def _entity_records(boxes, models):
+    """The entity calls' host records: contiguous DRAW_BOX_DTYPE and DRAW_STAMP_DTYPE arrays (empty for None)."""
+    return _records(boxes, DRAW_BOX_DTYPE), _records(models, DRAW_STAMP_DTYPE)
+
+
+def _face_lights(face_lights, n, what):
+    """The PROBE_LIGHT_DTYPE records that light `n` entities' faces: six per entity, or a ValueError."""
+    lights = _records(face_lights, PROBE_LIGHT_DTYPE)
+    if lights.size != 6 * n:
+        raise ValueError("face_lights must hold six records per %s" % what)
+    return lights
+
+
+def _rays(origins, directions):
+    """float32[N, 8] RtRay rows (origin, pad, direction, pad) from float[N, 3] origins and directions."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions must have the same shape [N, 3]")
+    rays = np.zeros((o.shape[0], 8), dtype=np.float32)
+    rays[:, 0:3], rays[:, 4:7] = o, d
+    return rays
+
+
+def _pick_result(hit, adjacent, world, **more):
+    """What Pipeline.pick and pick_entity return: the world's hit record, its fields as Python values, and the two texels."""
+    h = hit[0]
+    return dict(more, hit=h, texel=tuple(int(v) for v in h["texel"]), normal=int(h["normal"]), kind=int(h["kind"]),
+                adjacent=tuple(adjacent[:]), world=tuple(world[:]))
+
+
 # The measured settle thresholds of rt_denoise_history (DESIGN.md "History-aware denoise"): the size-1 dispatch filters everybody,
 # pixels with 16 / 8 / 4 / 4 / 2 samples or more sit out the dispatches of size 2 / 4 / 8 / 8 / 16, taps are not weighted by their
 # counts.  On the measurement scene this lowers the error against a converged frame over all surface pixels and over those with 8
@@ -64,38 +122,17 @@ def denoise_params(faithful=True, weight_by_count=False, settle=(0, 0, 0, 0, 0, 
     return p
 
 
-# numpy view of RtRayHit (include/rt_abi.h)
-HIT_DTYPE = np.dtype([("position", "<f4", 3), ("distance", "<f4"), ("texel", "<i4", 3), ("material", "<u4"), ("normal", "<u4"),
-                      ("kind", "<u4"), ("iterations", "<u4"), ("border_fetches", "<u4")])
-assert HIT_DTYPE.itemsize == C.sizeof(RtRayHit)
-# numpy views of RtLightProbe and RtProbeLight (include/rt_abi.h)
-PROBE_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<u4"), ("cell", "<u2", 2), ("reserved", "<u4", 3)])
-PROBE_LIGHT_DTYPE = np.dtype([("light", "<f4", 3), ("sun_samples", "<u4")])
-assert PROBE_DTYPE.itemsize == C.sizeof(RtLightProbe) and PROBE_LIGHT_DTYPE.itemsize == C.sizeof(RtProbeLight)
-# numpy views of RtBoxSweep and RtSweepHit (include/rt_abi.h)
-SWEEP_DTYPE = np.dtype([("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3), ("reserved1", "<u4"), ("motion", "<f4", 3), ("reserved2", "<u4")])
-SWEEP_HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<u4"), ("normal", "<u4"), ("material", "<u4"), ("texel", "<i4", 3), ("axis", "<u4"),
-                            ("lo", "<f4", 3), ("reserved0", "<u4"), ("hi", "<f4", 3), ("reserved1", "<u4")])
-assert SWEEP_DTYPE.itemsize == C.sizeof(RtBoxSweep) and SWEEP_HIT_DTYPE.itemsize == C.sizeof(RtSweepHit)
-# numpy view of RtDrawBox (include/rt_abi.h)
-DRAW_BOX_DTYPE = np.dtype([("lo", "<f4", 3), ("material", "<u4"), ("hi", "<f4", 3), ("emission", "<u4")])
-assert DRAW_BOX_DTYPE.itemsize == C.sizeof(RtDrawBox)
-# numpy view of RtDrawStamp (include/rt_abi.h)
-DRAW_STAMP_DTYPE = np.dtype([("origin", "<f4", 3), ("scale", "<f4"), ("stamp", "<u4"), ("orient", "u1"), ("reserved0", "u1", 3),
-                             ("emission", "<u4"), ("reserved", "<u4")])
-assert DRAW_STAMP_DTYPE.itemsize == C.sizeof(RtDrawStamp)
-# numpy view of RtEntityHit (include/rt_abi.h)
-ENTITY_HIT_DTYPE = np.dtype([("position", "<f4", 3), ("t", "<f4"), ("kind", "<u4"), ("index", "<u4"), ("normal", "<u4"), ("material", "<u4"),
-                             ("cell", "<i4", 3), ("voxel", "<u4")])
-assert ENTITY_HIT_DTYPE.itemsize == C.sizeof(RtEntityHit) == 48
-# numpy view of RtPointLight (include/rt_abi.h)
-POINT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("radius", "<f4"), ("color", "<f4", 3), ("reserved", "<u4")])
-assert POINT_LIGHT_DTYPE.itemsize == C.sizeof(RtPointLight)
-
-# numpy view of RtShapeEdit (include/rt_abi.h)
-SHAPE_DTYPE = np.dtype([("a", "<i4", 3), ("material", "<u4"), ("b", "<i4", 3), ("kind", "u1"), ("where", "u1"), ("solid", "u1"),
-                        ("reserved", "u1")])
-assert SHAPE_DTYPE.itemsize == C.sizeof(RtShapeEdit)
+# numpy views of the ABI's records: each layout is written once, as the ctypes struct in abi.py (tests/test_record_layouts.py pins them)
+HIT_DTYPE = np.dtype(RtRayHit)
+PROBE_DTYPE, PROBE_LIGHT_DTYPE = np.dtype(RtLightProbe), np.dtype(RtProbeLight)
+SWEEP_DTYPE, SWEEP_HIT_DTYPE = np.dtype(RtBoxSweep), np.dtype(RtSweepHit)
+DRAW_BOX_DTYPE = np.dtype(RtDrawBox)
+DRAW_STAMP_DTYPE = np.dtype(RtDrawStamp)
+ENTITY_HIT_DTYPE = np.dtype(RtEntityHit)
+POINT_LIGHT_DTYPE = np.dtype(RtPointLight)
+SHAPE_DTYPE = np.dtype(RtShapeEdit)
+STAMP_PLACE_DTYPE = np.dtype(RtStampPlace)
+VOXEL_EDIT_DTYPE = np.dtype(RtVoxelEdit)
 
 
 def box_shape(lo, hi, material=0, solid=True, where=RT_WHERE_ALL):
@@ -117,12 +154,6 @@ def sphere_shape(centre, radius, material=0, solid=True, where=RT_WHERE_ALL):
     s["a"], s["b"] = [int(v) for v in c2], [int(d) * int(d), 0, 0]
     s["material"], s["kind"], s["where"], s["solid"] = int(material) & 0xFFFFFFFF, RT_SHAPE_SPHERE, int(where), 1 if solid else 0
     return s
-
-
-# numpy view of RtStampPlace (include/rt_abi.h)
-STAMP_PLACE_DTYPE = np.dtype([("at", "<i4", 3), ("stamp", "<u4"), ("orient", "u1"), ("where", "u1"), ("reserved0", "u1", 2),
-                              ("reserved", "<u4", 3)])
-assert STAMP_PLACE_DTYPE.itemsize == C.sizeof(RtStampPlace)
 
 
 def stamp_place(stamp, at, orient=0, where=RT_WHERE_ALL):
@@ -201,11 +232,18 @@ class Context:
     def handle(self):
         return self._h
 
+    @property
+    def _device(self):
+        return self.cfg.device if self.cfg is not None else 0
+
+    @property
+    def _region(self):
+        return self.cfg.region if self.cfg is not None else 256
+
     # -- uploads -----------------------------------------------------------------------------------------
     def upload_world(self, materials, minefield):
-        materials = np.ascontiguousarray(materials, dtype=np.uint32).reshape(-1)
-        minefield = np.ascontiguousarray(minefield, dtype=np.uint8).reshape(-1)
-        n = (self.cfg.region if self.cfg is not None else 256) ** 3
+        materials, minefield = _records(materials, np.uint32), _records(minefield, np.uint8)
+        n = self._region ** 3
         if materials.size != n or minefield.size != n:
             raise ValueError("world arrays must hold region^3 voxels")
         self._check(self._lib.rt_upload_world(self._h, _p(materials), _p(minefield)))
@@ -217,7 +255,7 @@ class Context:
         are two staging sets, ask again for every slab) and dead after destroy() — do not keep them."""
         pm, pf = C.c_void_p(), C.c_void_p()
         self._check(self._lib.rt_slice_staging(self._h, C.byref(pm), C.byref(pf)))
-        n = 16 * (self.cfg.region if self.cfg is not None else 256) ** 2
+        n = 16 * self._region ** 2
         mats = np.ctypeslib.as_array(C.cast(pm, C.POINTER(C.c_uint32)), shape=(n,))
         mine = np.ctypeslib.as_array(C.cast(pf, C.POINTER(C.c_uint8)), shape=(n,))
         self._staging_views = (mats, mine)
@@ -229,9 +267,8 @@ class Context:
         self._staging_views = None
 
     def upload_slice(self, axis, texel_offset, materials, minefield):
-        materials = np.ascontiguousarray(materials, dtype=np.uint32).reshape(-1)
-        minefield = np.ascontiguousarray(minefield, dtype=np.uint8).reshape(-1)
-        n = 16 * (self.cfg.region if self.cfg is not None else 256) ** 2
+        materials, minefield = _records(materials, np.uint32), _records(minefield, np.uint8)
+        n = 16 * self._region ** 2
         if materials.size != n or minefield.size != n:
             raise ValueError("slice arrays must hold 16*region*region voxels")
         try:
@@ -250,7 +287,7 @@ class Context:
             raise ValueError("xyz, materials and solid must describe the same number of edits")
         if n and (xyz.min() < 0 or xyz.max() > 0xFFFF):
             raise ValueError("coordinates must fit uint16 (the library checks them against the region)")
-        recs = np.zeros(n, dtype=[("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("solid", "<u2"), ("material", "<u4"), ("reserved", "<u4")])
+        recs = np.zeros(n, dtype=VOXEL_EDIT_DTYPE)
         recs["x"], recs["y"], recs["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
         recs["solid"] = solid != 0
         recs["material"] = materials
@@ -259,15 +296,13 @@ class Context:
     def edit_records(self, recs):
         """rt_edit_voxels on a ready array of RtVoxelEdit records (numpy structured array of 16-byte rows, reserved included)."""
         recs = np.ascontiguousarray(recs)
-        assert recs.dtype.itemsize == C.sizeof(RtVoxelEdit)
+        assert recs.dtype.itemsize == VOXEL_EDIT_DTYPE.itemsize
         self._check(self._lib.rt_edit_voxels(self._h, recs.ctypes.data_as(C.POINTER(RtVoxelEdit)), int(recs.size)))
 
     def edit_shapes(self, shapes):
         """rt_edit_shapes: a sequence of box_shape / sphere_shape rows, or a ready SHAPE_DTYPE array (32-byte RtShapeEdit rows),
         applied in order on the device; every 64^3 chunk that meets a shape's bounding box is rebuilt (see include/rt_abi.h)."""
-        if not (isinstance(shapes, np.ndarray) and shapes.dtype == SHAPE_DTYPE):
-            shapes = np.array([np.asarray(s, dtype=SHAPE_DTYPE) for s in shapes], dtype=SHAPE_DTYPE).reshape(-1)
-        shapes = np.ascontiguousarray(shapes).reshape(-1)
+        shapes = _rows(shapes, SHAPE_DTYPE)
         self._check(self._lib.rt_edit_shapes(self._h, shapes.ctypes.data_as(C.POINTER(RtShapeEdit)), int(shapes.size)))
 
     def stamp_create(self, materials, state):
@@ -276,17 +311,15 @@ class Context:
         state = np.ascontiguousarray(state, dtype=np.uint8)
         if materials.ndim != 3 or materials.shape != state.shape:
             raise ValueError("materials and state are [ez, ey, ex] arrays of one shape")
-        ext = (C.c_int32 * 3)(*materials.shape[::-1])
         out = C.c_uint32(0)
-        self._check(self._lib.rt_stamp_create(self._h, ext, _p(materials), _p(state), C.byref(out)))
+        self._check(self._lib.rt_stamp_create(self._h, _lr3(materials.shape[::-1]), _p(materials), _p(state), C.byref(out)))
         return out.value
 
     def stamp_capture(self, lo, extent, flags=0):
         """rt_stamp_capture: a stamp from the resident region's box at texel `lo` (x, y, z) of `extent` (ex, ey, ez), copied on the
         device in stream order; RT_STAMP_SKIP_AIR leaves the unoccupied voxels out of it.  Returns its id."""
         out = C.c_uint32(0)
-        self._check(self._lib.rt_stamp_capture(self._h, (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in extent]),
-                                               int(flags), C.byref(out)))
+        self._check(self._lib.rt_stamp_capture(self._h, _lr3(lo), _lr3(extent), int(flags), C.byref(out)))
         return out.value
 
     def stamp_info(self, stamp):
@@ -310,9 +343,7 @@ class Context:
     def edit_stamps(self, places):
         """rt_edit_stamps: a sequence of stamp_place rows, or a ready STAMP_PLACE_DTYPE array (32-byte RtStampPlace rows), pasted in
         order on the device; every 64^3 chunk that meets a placement's bounding box is rebuilt (see include/rt_abi.h)."""
-        if not (isinstance(places, np.ndarray) and places.dtype == STAMP_PLACE_DTYPE):
-            places = np.array([np.asarray(s, dtype=STAMP_PLACE_DTYPE) for s in places], dtype=STAMP_PLACE_DTYPE).reshape(-1)
-        places = np.ascontiguousarray(places).reshape(-1)
+        places = _rows(places, STAMP_PLACE_DTYPE)
         self._check(self._lib.rt_edit_stamps(self._h, places.ctypes.data_as(C.POINTER(RtStampPlace)), int(places.size)))
 
     def read_box(self, origin, extent):
@@ -340,7 +371,7 @@ class Context:
         self._check(self._lib.rt_generate_slice(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(axis), lo))
 
     def upload_noise(self, rgba8):
-        rgba8 = np.ascontiguousarray(rgba8, dtype=np.uint8).reshape(-1)
+        rgba8 = _records(rgba8, np.uint8)
         if rgba8.size != 512 * 512 * 4:
             raise ValueError("noise must be 512x512 RGBA8")
         self._check(self._lib.rt_upload_noise(self._h, _p(rgba8)))
@@ -348,15 +379,9 @@ class Context:
     # -- ray queries -------------------------------------------------------------------------------------
     def trace_rays(self, origins, directions, lr=(0, 0, 0)):
         """rt_trace_rays: float[N, 3] origins and directions -> numpy array of HIT_DTYPE (RtRayHit) per ray.  Synchronous."""
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if o.shape != d.shape:
-            raise ValueError("origins and directions must have the same shape [N, 3]")
-        rays = np.zeros((o.shape[0], 8), dtype=np.float32)
-        rays[:, 0:3], rays[:, 4:7] = o, d
-        hits = np.zeros(o.shape[0], dtype=HIT_DTYPE)
-        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
-        self._check(self._lib.rt_trace_rays(self._h, _p(rays), int(o.shape[0]), lr3, _p(hits)))
+        rays = _rays(origins, directions)
+        hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        self._check(self._lib.rt_trace_rays(self._h, _p(rays), rays.shape[0], _lr3(lr), _p(hits)))
         return hits
 
     def trace_rays_async(self, rays, hits, lr=(0, 0, 0)):
@@ -364,9 +389,8 @@ class Context:
         contiguous tensor of N * 48 bytes (e.g. uint8[N, 48] or int32[N, 12]).  Enqueued: valid after sync(), or in the order of a
         stream given to set_stream().  `rays` must be complete on the device when the call is made (the query is not ordered
         after the caller's stream unless that stream was given to set_stream())."""
-        n = check_query_tensors(rays, hits, self.cfg.device if self.cfg is not None else 0)
-        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
-        self._check(self._lib.rt_trace_rays_async(self._h, C.c_void_p(rays.data_ptr()), n, lr3, C.c_void_p(hits.data_ptr())))
+        n = check_query_tensors(rays, hits, self._device)
+        self._check(self._lib.rt_trace_rays_async(self._h, _dp(rays), n, _lr3(lr), _dp(hits)))
 
     def pick_pixels(self, uniforms, xy):
         """rt_pick_pixels: int[N, 2] whole-frame pixels (x, y), row 0 = bottom, of the camera in `uniforms` -> HIT_DTYPE[N]."""
@@ -380,18 +404,12 @@ class Context:
         """rt_trace_entities: float[N, 3] origins and directions against the resident world and the drawn `boxes` (DRAW_BOX_DTYPE[B]) and
         `models` (DRAW_STAMP_DTYPE[M]) -> (world_hits HIT_DTYPE[N], entity_hits ENTITY_HIT_DTYPE[N]).  Synchronous; an invalid record
         fails the whole call (RtError, INVALID_ARG).  Rays that lie together should follow each other: a wave of 64 culls as one."""
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if o.shape != d.shape:
-            raise ValueError("origins and directions must have the same shape [N, 3]")
-        rays = np.zeros((o.shape[0], 8), dtype=np.float32)
-        rays[:, 0:3], rays[:, 4:7] = o, d
+        rays = _rays(origins, directions)
         boxes, models = _entity_records(boxes, models)
-        world = np.zeros(o.shape[0], dtype=HIT_DTYPE)
-        hits = np.zeros(o.shape[0], dtype=ENTITY_HIT_DTYPE)
-        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
-        self._check(self._lib.rt_trace_entities(self._h, _p(rays), int(o.shape[0]), lr3, _p(boxes) if boxes.size else None, int(boxes.size),
-                                                _p(models) if models.size else None, int(models.size), _p(world), _p(hits)))
+        world = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        hits = np.zeros(rays.shape[0], dtype=ENTITY_HIT_DTYPE)
+        self._check(self._lib.rt_trace_entities(self._h, _p(rays), rays.shape[0], _lr3(lr), _ptr_or_none(boxes), boxes.size,
+                                                _ptr_or_none(models), models.size, _p(world), _p(hits)))
         return world, hits
 
     def pick_entities(self, uniforms, xy, boxes=None, models=None):
@@ -402,8 +420,8 @@ class Context:
         boxes, models = _entity_records(boxes, models)
         world = np.zeros(xy.shape[0], dtype=HIT_DTYPE)
         hits = np.zeros(xy.shape[0], dtype=ENTITY_HIT_DTYPE)
-        self._check(self._lib.rt_pick_entities(self._h, C.byref(uniforms), _p(xy), int(xy.shape[0]), _p(boxes) if boxes.size else None,
-                                               int(boxes.size), _p(models) if models.size else None, int(models.size), _p(world), _p(hits)))
+        self._check(self._lib.rt_pick_entities(self._h, C.byref(uniforms), _p(xy), xy.shape[0], _ptr_or_none(boxes), boxes.size,
+                                               _ptr_or_none(models), models.size, _p(world), _p(hits)))
         return world, hits
 
     def trace_entities_async(self, rays, boxes, models, world_hits, entity_hits, lr=(0, 0, 0)):
@@ -411,13 +429,10 @@ class Context:
         B * 32 bytes (RtDrawBox rows) or None, `world_hits` any contiguous tensor of N * 48 bytes or None, `entity_hits` likewise (not
         None); `models` host records as for draw_stamps_async (free again on return).  Enqueued: valid after sync(), or in the order of
         a stream given to set_stream().  An invalid box is skipped on the device, an invalid model fails the call."""
-        n, nb = check_entity_query_tensors(rays, boxes, world_hits, entity_hits, self.cfg.device if self.cfg is not None else 0)
-        _, models = _entity_records(None, models)
-        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
-        self._check(self._lib.rt_trace_entities_async(self._h, C.c_void_p(rays.data_ptr()), n, lr3, C.c_void_p(boxes.data_ptr()) if nb else None, nb,
-                                                      _p(models) if models.size else None, int(models.size),
-                                                      C.c_void_p(world_hits.data_ptr()) if world_hits is not None else None,
-                                                      C.c_void_p(entity_hits.data_ptr())))
+        n, nb = check_entity_query_tensors(rays, boxes, world_hits, entity_hits, self._device)
+        models = _records(models, DRAW_STAMP_DTYPE)
+        self._check(self._lib.rt_trace_entities_async(self._h, _dp(rays), n, _lr3(lr), _dp(boxes) if nb else None, nb,
+                                                      _ptr_or_none(models), models.size, _dp(world_hits), _dp(entity_hits)))
 
     # -- light probes ------------------------------------------------------------------------------------
     def probe_light(self, uniforms, positions, normals, cells, samples, depth):
@@ -429,7 +444,7 @@ class Context:
     def probe_records(self, uniforms, probes, samples, depth):
         """rt_probe_light on a ready array of RtLightProbe records (numpy PROBE_DTYPE rows, reserved included)."""
         probes = np.ascontiguousarray(probes)
-        assert probes.dtype.itemsize == C.sizeof(RtLightProbe)
+        assert probes.dtype.itemsize == PROBE_DTYPE.itemsize
         out = np.zeros(probes.size, dtype=PROBE_LIGHT_DTYPE)
         self._check(self._lib.rt_probe_light(self._h, C.byref(uniforms), _p(probes), int(probes.size), int(samples), int(depth), _p(out)))
         return out
@@ -439,9 +454,8 @@ class Context:
         uint8[N, 32] from make_probes), `out` any contiguous tensor of N * 16 bytes (e.g. float32[N, 4]: light rgb, then the bits of
         sun_samples).  Enqueued: valid after sync(), or in the order of a stream given to set_stream().  `probes` must be complete
         on the device when the call is made."""
-        n = check_probe_tensors(probes, out, self.cfg.device if self.cfg is not None else 0)
-        self._check(self._lib.rt_probe_light_async(self._h, C.byref(uniforms), C.c_void_p(probes.data_ptr()), n, int(samples), int(depth),
-                                                   C.c_void_p(out.data_ptr())))
+        n = check_probe_tensors(probes, out, self._device)
+        self._check(self._lib.rt_probe_light_async(self._h, C.byref(uniforms), _dp(probes), n, int(samples), int(depth), _dp(out)))
 
     # -- box sweeps --------------------------------------------------------------------------------------
     def sweep_boxes(self, sweeps, lr=(0, 0, 0)):
@@ -449,8 +463,7 @@ class Context:
         (RtSweepHit) per sweep.  Synchronous; a record outside the validated domain fails the whole call (RtError, INVALID_ARG)."""
         recs = make_sweeps(sweeps)
         hits = np.zeros(recs.size, dtype=SWEEP_HIT_DTYPE)
-        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
-        self._check(self._lib.rt_sweep_boxes(self._h, _p(recs), int(recs.size), lr3, _p(hits)))
+        self._check(self._lib.rt_sweep_boxes(self._h, _p(recs), recs.size, _lr3(lr), _p(hits)))
         return hits
 
     def sweep_boxes_async(self, sweeps, hits, lr=(0, 0, 0)):
@@ -458,9 +471,8 @@ class Context:
         float32[N, 12]), `hits` any contiguous tensor of N * 64 bytes.  Enqueued: valid after sync(), or in the order of a stream
         given to set_stream().  `sweeps` must be complete on the device when the call is made.  A record outside the validated
         domain gets kind RT_SWEEP_INVALID."""
-        n = check_sweep_tensors(sweeps, hits, self.cfg.device if self.cfg is not None else 0)
-        lr3 = (C.c_int32 * 3)(*[int(v) for v in lr])
-        self._check(self._lib.rt_sweep_boxes_async(self._h, C.c_void_p(sweeps.data_ptr()), n, lr3, C.c_void_p(hits.data_ptr())))
+        n = check_sweep_tensors(sweeps, hits, self._device)
+        self._check(self._lib.rt_sweep_boxes_async(self._h, _dp(sweeps), n, _lr3(lr), _dp(hits)))
 
     def move_and_slide(self, lo, hi, motion, lr=(0, 0, 0), iterations=3):
         """The character-controller loop over rt_sweep_boxes: sweep; on BLOCKED take the returned box, zero the blocked axis of
@@ -487,73 +499,65 @@ class Context:
         """rt_draw_boxes: `boxes` DRAW_BOX_DTYPE[N] records (make_draw_boxes) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
         probe_records returns for face_probes(boxes, ...)), composited by depth into the planes of the frame drawn last under the camera
         of `uniforms`.  Synchronous; an invalid box fails the whole call (RtError, INVALID_ARG)."""
-        boxes = np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
-        lights = np.ascontiguousarray(face_lights, dtype=PROBE_LIGHT_DTYPE).reshape(-1)
-        if lights.size != 6 * boxes.size:
-            raise ValueError("face_lights must hold six records per box")
-        self._check(self._lib.rt_draw_boxes(self._h, C.byref(uniforms), _p(boxes) if boxes.size else None, _p(lights) if boxes.size else None,
-                                            int(boxes.size)))
+        boxes = _records(boxes, DRAW_BOX_DTYPE)
+        lights = _face_lights(face_lights, boxes.size, "box")
+        self._check(self._lib.rt_draw_boxes(self._h, C.byref(uniforms), _ptr_or_none(boxes), _ptr_or_none(lights), boxes.size))
 
     def draw_boxes_async(self, uniforms, boxes, face_lights):
         """rt_draw_boxes_async on torch device tensors: `boxes` any contiguous tensor of N * 32 bytes (RtDrawBox rows), `face_lights` any
         contiguous tensor of 6 N * 16 bytes (e.g. the `out` of probe_light_async).  Enqueued behind the frame drawn last and the queries
         enqueued so far; an invalid box is skipped on the device."""
-        n = check_draw_box_tensors(boxes, face_lights, self.cfg.device if self.cfg is not None else 0)
-        self._check(self._lib.rt_draw_boxes_async(self._h, C.byref(uniforms), C.c_void_p(boxes.data_ptr()), C.c_void_p(face_lights.data_ptr()), n))
+        n = check_draw_box_tensors(boxes, face_lights, self._device)
+        self._check(self._lib.rt_draw_boxes_async(self._h, C.byref(uniforms), _dp(boxes), _dp(face_lights), n))
 
     # -- voxel-model entities ----------------------------------------------------------------------------
     def draw_stamps(self, uniforms, models, face_lights):
         """rt_draw_stamps: `models` DRAW_STAMP_DTYPE[N] records (make_draw_stamps) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
         probe_records returns for stamp_face_probes(models, extents)), composited by depth into the planes of the frame drawn last under
         the camera of `uniforms`.  Synchronous; an invalid record fails the whole call (RtError, INVALID_ARG)."""
-        models = np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
-        lights = np.ascontiguousarray(face_lights, dtype=PROBE_LIGHT_DTYPE).reshape(-1)
-        if lights.size != 6 * models.size:
-            raise ValueError("face_lights must hold six records per model")
-        self._check(self._lib.rt_draw_stamps(self._h, C.byref(uniforms), _p(models) if models.size else None,
-                                             _p(lights) if models.size else None, int(models.size)))
+        models = _records(models, DRAW_STAMP_DTYPE)
+        lights = _face_lights(face_lights, models.size, "model")
+        self._check(self._lib.rt_draw_stamps(self._h, C.byref(uniforms), _ptr_or_none(models), _ptr_or_none(lights), models.size))
 
     def draw_stamps_async(self, uniforms, models, face_lights):
         """rt_draw_stamps_async: `models` host records as for draw_stamps (free again on return), `face_lights` a torch device tensor:
         any contiguous tensor of 6 N * 16 bytes (e.g. the `out` of probe_light_async).  Enqueued behind the frame drawn last and the
         queries enqueued so far; an invalid record fails the whole call before anything is enqueued."""
-        models = np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
-        check_draw_stamp_lights(models.size, face_lights, self.cfg.device if self.cfg is not None else 0)
-        self._check(self._lib.rt_draw_stamps_async(self._h, C.byref(uniforms), _p(models) if models.size else None,
-                                                   C.c_void_p(face_lights.data_ptr()), int(models.size)))
+        models = _records(models, DRAW_STAMP_DTYPE)
+        check_draw_stamp_lights(models.size, face_lights, self._device)
+        self._check(self._lib.rt_draw_stamps_async(self._h, C.byref(uniforms), _ptr_or_none(models), _dp(face_lights), models.size))
 
     # -- entity shadows ----------------------------------------------------------------------------------
     def shadow_entities(self, uniforms, boxes=None, models=None, strength=1.0):
         """rt_shadow_entities: the drawn `boxes` (DRAW_BOX_DTYPE[N]) and `models` (DRAW_STAMP_DTYPE[M]) take the sun's direct term, times
         `strength` in (0, 1], out of the two lighting planes of the frame drawn last where they shade a pixel the world leaves sunlit,
         under the camera, lr and sun angle of `uniforms`.  Synchronous; an invalid record fails the whole call (RtError, INVALID_ARG)."""
-        boxes = np.zeros(0, dtype=DRAW_BOX_DTYPE) if boxes is None else np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
-        models = np.zeros(0, dtype=DRAW_STAMP_DTYPE) if models is None else np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
-        self._check(self._lib.rt_shadow_entities(self._h, C.byref(uniforms), _p(boxes) if boxes.size else None, int(boxes.size),
-                                                 _p(models) if models.size else None, int(models.size), float(strength)))
+        boxes, models = _entity_records(boxes, models)
+        self._check(self._lib.rt_shadow_entities(self._h, C.byref(uniforms), _ptr_or_none(boxes), boxes.size, _ptr_or_none(models), models.size,
+                                                 float(strength)))
 
     def shadow_entities_async(self, uniforms, boxes=None, models=None, strength=1.0):
         """rt_shadow_entities_async: `boxes` a torch device tensor, any contiguous tensor of N * 32 bytes (RtDrawBox rows: what
         draw_boxes_async took), or None; `models` host records as for shadow_entities (free again on return).  Enqueued behind the frame
         drawn last; an invalid box is skipped on the device, an invalid model fails the call before anything is enqueued."""
-        n = 0 if boxes is None else check_shadow_box_tensor(boxes, self.cfg.device if self.cfg is not None else 0)
-        models = np.zeros(0, dtype=DRAW_STAMP_DTYPE) if models is None else np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
-        self._check(self._lib.rt_shadow_entities_async(self._h, C.byref(uniforms), C.c_void_p(boxes.data_ptr()) if n else None, n,
-                                                       _p(models) if models.size else None, int(models.size), float(strength)))
+        n = 0 if boxes is None else check_shadow_box_tensor(boxes, self._device)
+        models = _records(models, DRAW_STAMP_DTYPE)
+        self._check(self._lib.rt_shadow_entities_async(self._h, C.byref(uniforms), _dp(boxes) if n else None, n, _ptr_or_none(models), models.size,
+                                                       float(strength)))
 
     # -- point lights ------------------------------------------------------------------------------------
     def add_lights(self, uniforms, lights):
         """rt_add_lights: `lights` POINT_LIGHT_DTYPE[N] records (make_point_lights) added to the two lighting planes of the frame drawn
         last under the camera and lr of `uniforms`, each through one shadow ray per pixel.  Synchronous; an invalid light fails the whole
         call (RtError, INVALID_ARG)."""
-        lights = np.ascontiguousarray(lights, dtype=POINT_LIGHT_DTYPE).reshape(-1)
-        self._check(self._lib.rt_add_lights(self._h, C.byref(uniforms), _p(lights) if lights.size else None, int(lights.size)))
+        lights = _records(lights, POINT_LIGHT_DTYPE)
+        self._check(self._lib.rt_add_lights(self._h, C.byref(uniforms), _ptr_or_none(lights), lights.size))
 
     def add_lights_async(self, uniforms, lights):
         """rt_add_lights_async on a torch device tensor: any contiguous tensor of N * 32 bytes (RtPointLight rows).  Enqueued behind the
         frame drawn last; an invalid light is skipped on the device."""
-        n = check_point_light_tensors(lights, self.cfg.device if self.cfg is not None else 0)
-        self._check(self._lib.rt_add_lights_async(self._h, C.byref(uniforms), C.c_void_p(lights.data_ptr()), n))
+        n = check_point_light_tensors(lights, self._device)
+        self._check(self._lib.rt_add_lights_async(self._h, C.byref(uniforms), _dp(lights), n))
 
     # -- frames ------------------------------------------------------------------------------------------
     def draw_frame(self, uniforms):
@@ -811,26 +815,24 @@ class Game:
     def set_sun_angle(self, a):
         _lib.host().rth_game_set_sun_angle(self._h, float(a))
 
+    @staticmethod
+    def _check_region(rc, call):
+        if rc != 0:
+            raise RtError(rc, "%s: region must be 256, 512 or 1024" % call)
+
     def set_world(self, materials, minefield, region=256):
-        materials = np.ascontiguousarray(materials, dtype=np.uint32).reshape(-1)
-        minefield = np.ascontiguousarray(minefield, dtype=np.uint8).reshape(-1)
+        materials, minefield = _records(materials, np.uint32), _records(minefield, np.uint8)
         if materials.size != region ** 3 or minefield.size != region ** 3:
             raise ValueError("world arrays must hold region^3 voxels")
-        rc = _lib.host().rth_game_set_world_r(self._h, _p(materials), _p(minefield), int(region))
-        if rc != 0:
-            raise RtError(rc, "set_world: region must be 256, 512 or 1024")
+        self._check_region(_lib.host().rth_game_set_world_r(self._h, _p(materials), _p(minefield), int(region)), "set_world")
 
     def generate_world(self, seed=0x5EED, region=256):
-        rc = _lib.host().rth_game_generate_world_r(self._h, C.c_uint64(int(seed)), int(region))
-        if rc != 0:
-            raise RtError(rc, "generate_world: region must be 256, 512 or 1024")
+        self._check_region(_lib.host().rth_game_generate_world_r(self._h, C.c_uint64(int(seed)), int(region)), "generate_world")
 
     def use_device_world(self, seed=0x5EED, region=256):
         """The world of generate_world(seed, region) without its host bytes: create_instance generates it on the device
         (rt_generate_world) instead of uploading it."""
-        rc = _lib.host().rth_game_use_device_world(self._h, C.c_uint64(int(seed)), int(region))
-        if rc != 0:
-            raise RtError(rc, "use_device_world: region must be 256, 512 or 1024")
+        self._check_region(_lib.host().rth_game_use_device_world(self._h, C.c_uint64(int(seed)), int(region)), "use_device_world")
 
     def close(self):
         if self._h:
@@ -852,16 +854,17 @@ class Pipeline:
         self.cfg = cfg
         self.context = Context(cfg=cfg, handle=_lib.host().rth_pipeline_context(self._h), owned=False)
 
+    def _check(self, rc, message=None):
+        """RtError for a failed call: with `message`, or with the pipeline's own last error."""
+        if rc != 0:
+            raise RtError(rc, message or _lib.host().rth_pipeline_last_error(self._h).decode())
+
     def draw_frame(self, game):
         """pipeline.rs:134-255: derive uniforms from the camera, submit the ray-trace work (asynchronous)."""
-        rc = _lib.host().rth_pipeline_draw_frame(self._h, game._h)
-        if rc != 0:
-            raise RtError(rc, _lib.host().rth_pipeline_last_error(self._h).decode())
+        self._check(_lib.host().rth_pipeline_draw_frame(self._h, game._h))
 
     def wait(self):
-        rc = _lib.host().rth_pipeline_wait(self._h)
-        if rc != 0:
-            raise RtError(rc, _lib.host().rth_pipeline_last_error(self._h).decode())
+        self._check(_lib.host().rth_pipeline_wait(self._h))
 
     def uniforms(self):
         u = RtUniforms()
@@ -882,9 +885,8 @@ class Pipeline:
     def enable_post_passes(self, faithful=True):
         """pipeline.rs:98-123: every draw_frame then enqueues ray trace -> six denoise dispatches -> finalize (the reference's one
         command buffer, :229-235); RT_BUF_FINAL_BGRA8 holds the frame's swapchain image.  Whole-frame contexts only."""
-        rc = _lib.host().rth_pipeline_enable_post_passes(self._h, 1 if faithful else 0)
-        if rc != 0:
-            raise RtError(rc, "enable_post_passes: whole-frame contexts only (tile_world == 1)")
+        self._check(_lib.host().rth_pipeline_enable_post_passes(self._h, 1 if faithful else 0),
+                    "enable_post_passes: whole-frame contexts only (tile_world == 1)")
 
     def enable_history_denoise(self, params=None, faithful=True):
         """With enable_post_passes on an RT_FLAG_REPROJECT context: draw_frame enqueues rt_denoise_history(params) in place of
@@ -892,9 +894,8 @@ class Pipeline:
         block."""
         if params is None:
             params = denoise_params(faithful=faithful, **HISTORY_DENOISE_PRESET)
-        rc = _lib.host().rth_pipeline_enable_history_denoise(self._h, C.byref(params))
-        if rc != 0:
-            raise RtError(rc, "enable_history_denoise: needs an RT_FLAG_REPROJECT context and a valid RtDenoiseParams")
+        self._check(_lib.host().rth_pipeline_enable_history_denoise(self._h, C.byref(params)),
+                    "enable_history_denoise: needs an RT_FLAG_REPROJECT context and a valid RtDenoiseParams")
 
     def pick(self, game, x, y_from_top):
         """The block under screen pixel (x, y_from_top) of the frame drawn last for `game` (Pipeline::pick: the pipeline's current
@@ -902,14 +903,9 @@ class Pipeline:
         `adjacent` (the texel in front of the face, where a placed block goes) and `world` (the hit texel's world coordinate)."""
         del game   # the pick is of the frame the pipeline drew for it: its uniforms hold the camera
         hit = np.zeros(1, dtype=HIT_DTYPE)
-        adj = (C.c_int32 * 3)()
-        wld = (C.c_int32 * 3)()
-        rc = _lib.host().rth_pipeline_pick(self._h, int(x), int(y_from_top), _p(hit), adj, wld)
-        if rc != 0:
-            raise RtError(rc, _lib.host().rth_pipeline_last_error(self._h).decode())
-        h = hit[0]
-        return {"hit": h, "texel": tuple(int(v) for v in h["texel"]), "normal": int(h["normal"]), "kind": int(h["kind"]),
-                "adjacent": tuple(adj[:]), "world": tuple(wld[:])}
+        adj, wld = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        self._check(_lib.host().rth_pipeline_pick(self._h, int(x), int(y_from_top), _p(hit), adj, wld))
+        return _pick_result(hit, adj, wld)
 
     def pick_entity(self, x, y_from_top):
         """Pipeline::pick_entity: the entity under screen pixel (x, y_from_top) among the boxes and models of set_boxes / set_models,
@@ -917,52 +913,38 @@ class Pipeline:
         the cursor is on an entity) and the world's `hit`, `texel`, `normal`, `kind`, `adjacent` and `world` as pick gives them."""
         ent = np.zeros(1, dtype=ENTITY_HIT_DTYPE)
         hit = np.zeros(1, dtype=HIT_DTYPE)
-        adj = (C.c_int32 * 3)()
-        wld = (C.c_int32 * 3)()
-        rc = _lib.host().rth_pipeline_pick_entity(self._h, int(x), int(y_from_top), _p(ent), _p(hit), adj, wld)
-        if rc != 0:
-            raise RtError(rc, _lib.host().rth_pipeline_last_error(self._h).decode())
-        h = hit[0]
-        return {"entity": ent[0], "hit": h, "texel": tuple(int(v) for v in h["texel"]), "normal": int(h["normal"]), "kind": int(h["kind"]),
-                "adjacent": tuple(adj[:]), "world": tuple(wld[:])}
+        adj, wld = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        self._check(_lib.host().rth_pipeline_pick_entity(self._h, int(x), int(y_from_top), _p(ent), _p(hit), adj, wld))
+        return _pick_result(hit, adj, wld, entity=ent[0])
 
     def set_boxes(self, boxes=None, face_lights=None):
         """Pipeline::set_boxes: every draw_frame from now on enqueues rt_draw_boxes for this set between the ray trace and the denoise
         (DRAW_BOX_DTYPE[N] and PROBE_LIGHT_DTYPE[6 N], copied); None or an empty set draws none."""
-        boxes = np.zeros(0, dtype=DRAW_BOX_DTYPE) if boxes is None else np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
-        lights = np.zeros(0, dtype=PROBE_LIGHT_DTYPE) if face_lights is None else np.ascontiguousarray(face_lights, dtype=PROBE_LIGHT_DTYPE).reshape(-1)
-        if lights.size != 6 * boxes.size:
-            raise ValueError("face_lights must hold six records per box")
-        rc = _lib.host().rth_pipeline_set_boxes(self._h, _p(boxes) if boxes.size else None, _p(lights) if boxes.size else None, int(boxes.size))
-        if rc != 0:
-            raise RtError(rc, "set_boxes: at most %d boxes" % MAX_DRAW_BOXES)
+        boxes = _records(boxes, DRAW_BOX_DTYPE)
+        lights = _face_lights(face_lights, boxes.size, "box")
+        self._check(_lib.host().rth_pipeline_set_boxes(self._h, _ptr_or_none(boxes), _ptr_or_none(lights), boxes.size),
+                    "set_boxes: at most %d boxes" % MAX_DRAW_BOXES)
 
     def set_models(self, models=None, face_lights=None):
         """Pipeline::set_models: every draw_frame from now on enqueues rt_draw_stamps for this set between the ray trace and the denoise,
         after the entity boxes (DRAW_STAMP_DTYPE[N] and PROBE_LIGHT_DTYPE[6 N], copied); None or an empty set draws none.  The stamps
         are the pipeline's (stamp_create / stamp_capture) and must be live at every draw."""
-        models = np.zeros(0, dtype=DRAW_STAMP_DTYPE) if models is None else np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
-        lights = np.zeros(0, dtype=PROBE_LIGHT_DTYPE) if face_lights is None else np.ascontiguousarray(face_lights, dtype=PROBE_LIGHT_DTYPE).reshape(-1)
-        if lights.size != 6 * models.size:
-            raise ValueError("face_lights must hold six records per model")
-        rc = _lib.host().rth_pipeline_set_models(self._h, _p(models) if models.size else None, _p(lights) if models.size else None, int(models.size))
-        if rc != 0:
-            raise RtError(rc, "set_models: at most %d models" % MAX_DRAW_STAMPS)
+        models = _records(models, DRAW_STAMP_DTYPE)
+        lights = _face_lights(face_lights, models.size, "model")
+        self._check(_lib.host().rth_pipeline_set_models(self._h, _ptr_or_none(models), _ptr_or_none(lights), models.size),
+                    "set_models: at most %d models" % MAX_DRAW_STAMPS)
 
     def set_lights(self, lights=None):
         """Pipeline::set_lights: every draw_frame from now on enqueues rt_add_lights for this set behind the ray trace and the entity
         boxes and in front of the denoise (POINT_LIGHT_DTYPE[N], copied); None or an empty set adds none."""
-        lights = np.zeros(0, dtype=POINT_LIGHT_DTYPE) if lights is None else np.ascontiguousarray(lights, dtype=POINT_LIGHT_DTYPE).reshape(-1)
-        rc = _lib.host().rth_pipeline_set_lights(self._h, _p(lights) if lights.size else None, int(lights.size))
-        if rc != 0:
-            raise RtError(rc, "set_lights: at most %d lights" % MAX_POINT_LIGHTS)
+        lights = _records(lights, POINT_LIGHT_DTYPE)
+        self._check(_lib.host().rth_pipeline_set_lights(self._h, _ptr_or_none(lights), lights.size), "set_lights: at most %d lights" % MAX_POINT_LIGHTS)
 
     def enable_entity_shadows(self, strength=1.0):
         """Pipeline::enable_entity_shadows: every draw_frame from now on enqueues rt_shadow_entities for the boxes and models set
         (set_boxes, set_models) behind their draws and in front of the point lights; strength in (0, 1], 0 switches it off again."""
-        rc = _lib.host().rth_pipeline_enable_entity_shadows(self._h, float(strength))
-        if rc != 0:
-            raise RtError(rc, "enable_entity_shadows: strength must be 0 (off) or lie in (0, 1]")
+        self._check(_lib.host().rth_pipeline_enable_entity_shadows(self._h, float(strength)),
+                    "enable_entity_shadows: strength must be 0 (off) or lie in (0, 1]")
 
     def close(self):
         if self._h:
@@ -979,7 +961,7 @@ class Pipeline:
 def create_instance(cfg, game, blue_noise_rgba8):
     """render::create_instance (src/render/mod.rs:36-43): builds the pipeline, uploads the game's world
     (generating the procedural one if the game has none) and the blue-noise table."""
-    noise = np.ascontiguousarray(blue_noise_rgba8, dtype=np.uint8).reshape(-1)
+    noise = _records(blue_noise_rgba8, np.uint8)
     if noise.size != 512 * 512 * 4:
         raise ValueError("noise must be 512x512 RGBA8")
     err = C.create_string_buffer(512)
@@ -1009,31 +991,68 @@ def camera_uniforms(origin, heading, pitch, sun_angle=0.0, seed=1, lr=(0, 0, 0))
 DEFAULT_POSE = dict(origin=(-30.0, -128.0, 100.0), heading=math.pi / 2, pitch=0.0, sun_angle=0.0)  # game/mod.rs:53-55
 
 
-def check_query_tensors(rays, hits, device):
-    """Context.trace_rays_async's arguments: `rays` a contiguous float32[N, 8] tensor and `hits` a contiguous tensor of N * 48
-    bytes, both on GPU `device` and 16-byte aligned.  Returns N; raises ValueError otherwise (a host tensor's address handed to the
-    kernel would fault the device)."""
+# ---- device arguments of the *_async calls ------------------------------------------------------------------------
+# A host address handed to a kernel faults the device, so every torch tensor an *_async call takes goes through _device_tensors and
+# its size through record_count / _holds first.  Only host-side attributes of the tensors are read: no sync, no device work.
+
+def record_count(name, nbytes, itemsize, cap=None, record=""):
+    """N, where argument `name` holds `nbytes` bytes of `itemsize`-byte records (`record`: the struct's name, for the message).
+    Pure integers.  ValueError for a partial record and for N above `cap`."""
+    if nbytes % itemsize:
+        raise ValueError("%s must hold whole %d-byte %srecords" % (name, itemsize, record and record + " "))
+    n = nbytes // itemsize
+    if cap is not None and n > cap:
+        raise ValueError("at most %d %s per call" % (cap, name))
+    return n
+
+
+def _device_tensors(device, *named):
+    """ValueError unless every (name, tensor) of `named` is a torch tensor — asked of all of them first — on GPU `device`, 16-byte
+    aligned and contiguous: what a kernel may be given the address of."""
     import torch
-    if not isinstance(rays, torch.Tensor) or not isinstance(hits, torch.Tensor):
-        raise ValueError("rays and hits must be torch tensors")
-    for name, t in (("rays", rays), ("hits", hits)):
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a torch tensor" % name)
+    for name, t in named:
         if not t.is_cuda or t.device.index != int(device):
             raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
         if t.data_ptr() % 16:
             raise ValueError("%s must be 16-byte aligned" % name)
-    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def _holds(name, t, n, itemsize, per=1):
+    """ValueError unless tensor `t` is exactly `per` records of `itemsize` bytes for each of the call's `n`."""
+    if _nbytes(t) != per * n * itemsize:
+        raise ValueError("%s must be a contiguous tensor of %sN * %d bytes" % (name, "%d " % per if per > 1 else "", itemsize))
+
+
+def _ray_count(rays, cap=None):
+    """N of a checked device tensor of RtRay rows, which the queries take as float32[N, 8] only."""
+    import torch
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
         raise ValueError("rays must be a contiguous float32 tensor of shape [N, 8]")
-    n = int(rays.shape[0])
-    if not hits.is_contiguous() or hits.numel() * hits.element_size() != n * HIT_DTYPE.itemsize:
-        raise ValueError("hits must be a contiguous tensor of N * 48 bytes")
+    return record_count("rays", _nbytes(rays), 32, cap)
+
+
+def _box_count(boxes):
+    """N of a checked device tensor of RtDrawBox rows."""
+    return record_count("boxes", _nbytes(boxes), DRAW_BOX_DTYPE.itemsize, MAX_DRAW_BOXES, "RtDrawBox")
+
+
+def check_query_tensors(rays, hits, device):
+    """Context.trace_rays_async's arguments: `rays` a contiguous float32[N, 8] tensor and `hits` a contiguous tensor of N * 48
+    bytes, both on GPU `device` and 16-byte aligned.  Returns N; raises ValueError otherwise (a host tensor's address handed to the
+    kernel would fault the device)."""
+    _device_tensors(device, ("rays", rays), ("hits", hits))
+    n = _ray_count(rays)
+    _holds("hits", hits, n, HIT_DTYPE.itemsize)
     return n
-
-
-def _entity_records(boxes, models):
-    """The entity queries' host records: contiguous DRAW_BOX_DTYPE and DRAW_STAMP_DTYPE arrays (empty for None)."""
-    boxes = np.zeros(0, dtype=DRAW_BOX_DTYPE) if boxes is None else np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
-    models = np.zeros(0, dtype=DRAW_STAMP_DTYPE) if models is None else np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
-    return boxes, models
 
 
 def check_entity_query_tensors(rays, boxes, world_hits, entity_hits, device):
@@ -1041,35 +1060,13 @@ def check_entity_query_tensors(rays, boxes, world_hits, entity_hits, device):
     bytes or None, `world_hits` a contiguous tensor of N * 48 bytes or None, `entity_hits` a contiguous tensor of N * 48 bytes, all on
     GPU `device` and 16-byte aligned, N at most 2^24 and B at most 4096.  Returns (N, B); raises ValueError otherwise (a host tensor's
     address handed to the kernel would fault the device)."""
-    import torch
-    given = [("rays", rays), ("entity_hits", entity_hits)] + [(k, t) for k, t in (("boxes", boxes), ("world_hits", world_hits)) if t is not None]
-    for name, t in given:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s must be a torch tensor" % name)
-    for name, t in given:
-        if not t.is_cuda or t.device.index != int(device):
-            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
-        if t.data_ptr() % 16:
-            raise ValueError("%s must be 16-byte aligned" % name)
-        if not t.is_contiguous():
-            raise ValueError("%s must be contiguous" % name)
-    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-        raise ValueError("rays must be a contiguous float32 tensor of shape [N, 8]")
-    n = int(rays.shape[0])
-    if n > MAX_ENTITY_RAYS:
-        raise ValueError("at most 2^24 rays per call")
-    for name, t in (("world_hits", world_hits), ("entity_hits", entity_hits)):
-        if t is not None and t.numel() * t.element_size() != n * ENTITY_HIT_DTYPE.itemsize:
-            raise ValueError("%s must be a contiguous tensor of N * 48 bytes" % name)
-    nb = 0
-    if boxes is not None:
-        nbytes = boxes.numel() * boxes.element_size()
-        if nbytes % DRAW_BOX_DTYPE.itemsize:
-            raise ValueError("boxes must hold whole 32-byte RtDrawBox records")
-        nb = nbytes // DRAW_BOX_DTYPE.itemsize
-        if nb > MAX_DRAW_BOXES:
-            raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
-    return n, nb
+    optional = [(name, t) for name, t in (("boxes", boxes), ("world_hits", world_hits)) if t is not None]
+    _device_tensors(device, ("rays", rays), ("entity_hits", entity_hits), *optional)
+    n = _ray_count(rays, MAX_ENTITY_RAYS)
+    if world_hits is not None:
+        _holds("world_hits", world_hits, n, HIT_DTYPE.itemsize)
+    _holds("entity_hits", entity_hits, n, ENTITY_HIT_DTYPE.itemsize)
+    return n, 0 if boxes is None else _box_count(boxes)
 
 
 def make_sweeps(sweeps):
@@ -1088,22 +1085,9 @@ def make_sweeps(sweeps):
 def check_sweep_tensors(sweeps, hits, device):
     """Context.sweep_boxes_async's arguments: contiguous tensors of N * 48 and N * 64 bytes on GPU `device`, 16-byte aligned.
     Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
-    import torch
-    if not isinstance(sweeps, torch.Tensor) or not isinstance(hits, torch.Tensor):
-        raise ValueError("sweeps and hits must be torch tensors")
-    for name, t in (("sweeps", sweeps), ("hits", hits)):
-        if not t.is_cuda or t.device.index != int(device):
-            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
-        if t.data_ptr() % 16:
-            raise ValueError("%s must be 16-byte aligned" % name)
-        if not t.is_contiguous():
-            raise ValueError("%s must be contiguous" % name)
-    nbytes = sweeps.numel() * sweeps.element_size()
-    if nbytes % SWEEP_DTYPE.itemsize:
-        raise ValueError("sweeps must hold whole 48-byte RtBoxSweep records")
-    n = nbytes // SWEEP_DTYPE.itemsize
-    if hits.numel() * hits.element_size() != n * SWEEP_HIT_DTYPE.itemsize:
-        raise ValueError("hits must be a contiguous tensor of N * 64 bytes")
+    _device_tensors(device, ("sweeps", sweeps), ("hits", hits))
+    n = record_count("sweeps", _nbytes(sweeps), SWEEP_DTYPE.itemsize, None, "RtBoxSweep")
+    _holds("hits", hits, n, SWEEP_HIT_DTYPE.itemsize)
     return n
 
 
@@ -1135,7 +1119,7 @@ def face_probes(boxes, cells=(0, 0)):
     """The six RtLightProbe records (PROBE_DTYPE) per box that light its faces: record 6 b + n sits at the centre of box b's face with
     normal code n, moved 0.001 off the face along its normal, with normal n.  `cells`: int[N, 2] noise cells per box, or one pair for
     all.  probe_records(u, face_probes(boxes), samples, depth) is the face_lights of draw_boxes."""
-    boxes = np.ascontiguousarray(boxes, dtype=DRAW_BOX_DTYPE).reshape(-1)
+    boxes = _records(boxes, DRAW_BOX_DTYPE)
     n = boxes.size
     lo, hi = boxes["lo"].astype(np.float32), boxes["hi"].astype(np.float32)
     centre = (lo + hi) * np.float32(0.5)
@@ -1151,46 +1135,17 @@ def face_probes(boxes, cells=(0, 0)):
 def check_draw_box_tensors(boxes, face_lights, device):
     """Context.draw_boxes_async's arguments: contiguous tensors of N * 32 and 6 N * 16 bytes on GPU `device`, 16-byte aligned, N at most
     4096.  Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
-    import torch
-    if not isinstance(boxes, torch.Tensor) or not isinstance(face_lights, torch.Tensor):
-        raise ValueError("boxes and face_lights must be torch tensors")
-    for name, t in (("boxes", boxes), ("face_lights", face_lights)):
-        if not t.is_cuda or t.device.index != int(device):
-            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
-        if t.data_ptr() % 16:
-            raise ValueError("%s must be 16-byte aligned" % name)
-        if not t.is_contiguous():
-            raise ValueError("%s must be contiguous" % name)
-    nbytes = boxes.numel() * boxes.element_size()
-    if nbytes % DRAW_BOX_DTYPE.itemsize:
-        raise ValueError("boxes must hold whole 32-byte RtDrawBox records")
-    n = nbytes // DRAW_BOX_DTYPE.itemsize
-    if n > MAX_DRAW_BOXES:
-        raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
-    if face_lights.numel() * face_lights.element_size() != 6 * n * PROBE_LIGHT_DTYPE.itemsize:
-        raise ValueError("face_lights must be a contiguous tensor of 6 N * 16 bytes")
+    _device_tensors(device, ("boxes", boxes), ("face_lights", face_lights))
+    n = _box_count(boxes)
+    _holds("face_lights", face_lights, n, PROBE_LIGHT_DTYPE.itemsize, per=6)
     return n
 
 
 def check_shadow_box_tensor(boxes, device):
     """Context.shadow_entities_async's device argument: a contiguous tensor of N * 32 bytes on GPU `device`, 16-byte aligned, N at most
     4096.  Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
-    import torch
-    if not isinstance(boxes, torch.Tensor):
-        raise ValueError("boxes must be a torch tensor")
-    if not boxes.is_cuda or boxes.device.index != int(device):
-        raise ValueError("boxes must be a tensor on cuda:%d (the context's device), not %s" % (int(device), boxes.device))
-    if boxes.data_ptr() % 16:
-        raise ValueError("boxes must be 16-byte aligned")
-    if not boxes.is_contiguous():
-        raise ValueError("boxes must be contiguous")
-    nbytes = boxes.numel() * boxes.element_size()
-    if nbytes % DRAW_BOX_DTYPE.itemsize:
-        raise ValueError("boxes must hold whole 32-byte RtDrawBox records")
-    n = nbytes // DRAW_BOX_DTYPE.itemsize
-    if n > MAX_DRAW_BOXES:
-        raise ValueError("at most %d boxes per call" % MAX_DRAW_BOXES)
-    return n
+    _device_tensors(device, ("boxes", boxes))
+    return _box_count(boxes)
 
 
 # world axis k of a placed stamp is stamp axis STAMP_PERMS[orient >> 3][k] (include/rt_abi.h, rt_edit_stamps)
@@ -1225,7 +1180,7 @@ def make_draw_stamps(stamps, origins, scales=1.0, orients=0, emissions=0xFF00000
 def stamp_bounding_boxes(models, extents):
     """(lo, hi) float32[N, 3] of the models' bounding boxes: lo = origin, hi = origin + E' * scale with E'_k = E[perm[k]].  `extents`:
     int[N, 3] stamp extents (ex, ey, ez) per model, or one triple for all."""
-    models = np.ascontiguousarray(models, dtype=DRAW_STAMP_DTYPE).reshape(-1)
+    models = _records(models, DRAW_STAMP_DTYPE)
     n = models.size
     ext = np.broadcast_to(np.asarray(extents, dtype=np.int64).reshape(-1, 3), (n, 3))
     perm = np.array(STAMP_PERMS, dtype=np.int64)[models["orient"].astype(np.int64) >> 3] if n else np.zeros((0, 3), dtype=np.int64)
@@ -1248,19 +1203,9 @@ def stamp_face_probes(models, extents, cells=(0, 0)):
 def check_draw_stamp_lights(n, face_lights, device):
     """Context.draw_stamps_async's device argument: a contiguous tensor of 6 n * 16 bytes on GPU `device`, 16-byte aligned, n at most
     4096.  Raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
-    import torch
-    if not isinstance(face_lights, torch.Tensor):
-        raise ValueError("face_lights must be a torch tensor")
-    if not face_lights.is_cuda or face_lights.device.index != int(device):
-        raise ValueError("face_lights must be a tensor on cuda:%d (the context's device), not %s" % (int(device), face_lights.device))
-    if face_lights.data_ptr() % 16:
-        raise ValueError("face_lights must be 16-byte aligned")
-    if not face_lights.is_contiguous():
-        raise ValueError("face_lights must be contiguous")
-    if n > MAX_DRAW_STAMPS:
-        raise ValueError("at most %d models per call" % MAX_DRAW_STAMPS)
-    if face_lights.numel() * face_lights.element_size() != 6 * n * PROBE_LIGHT_DTYPE.itemsize:
-        raise ValueError("face_lights must be a contiguous tensor of 6 N * 16 bytes")
+    _device_tensors(device, ("face_lights", face_lights))
+    record_count("models", n * DRAW_STAMP_DTYPE.itemsize, DRAW_STAMP_DTYPE.itemsize, MAX_DRAW_STAMPS)     # the models are host records: n is exact
+    _holds("face_lights", face_lights, n, PROBE_LIGHT_DTYPE.itemsize, per=6)
 
 
 def make_point_lights(positions, radii, colors):
@@ -1289,22 +1234,8 @@ def make_point_lights(positions, radii, colors):
 def check_point_light_tensors(lights, device):
     """Context.add_lights_async's argument: a contiguous tensor of N * 32 bytes on GPU `device`, 16-byte aligned, N at most 1024.
     Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
-    import torch
-    if not isinstance(lights, torch.Tensor):
-        raise ValueError("lights must be a torch tensor")
-    if not lights.is_cuda or lights.device.index != int(device):
-        raise ValueError("lights must be a tensor on cuda:%d (the context's device), not %s" % (int(device), lights.device))
-    if lights.data_ptr() % 16:
-        raise ValueError("lights must be 16-byte aligned")
-    if not lights.is_contiguous():
-        raise ValueError("lights must be contiguous")
-    nbytes = lights.numel() * lights.element_size()
-    if nbytes % POINT_LIGHT_DTYPE.itemsize:
-        raise ValueError("lights must hold whole 32-byte RtPointLight records")
-    n = nbytes // POINT_LIGHT_DTYPE.itemsize
-    if n > MAX_POINT_LIGHTS:
-        raise ValueError("at most %d lights per call" % MAX_POINT_LIGHTS)
-    return n
+    _device_tensors(device, ("lights", lights))
+    return record_count("lights", _nbytes(lights), POINT_LIGHT_DTYPE.itemsize, MAX_POINT_LIGHTS, "RtPointLight")
 
 
 def make_probes(positions, normals, cells):
@@ -1330,22 +1261,9 @@ def workgroup_of(p):
 def check_probe_tensors(probes, out, device):
     """Context.probe_light_async's arguments: contiguous tensors of N * 32 and N * 16 bytes on GPU `device`, 16-byte aligned.
     Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
-    import torch
-    if not isinstance(probes, torch.Tensor) or not isinstance(out, torch.Tensor):
-        raise ValueError("probes and out must be torch tensors")
-    for name, t in (("probes", probes), ("out", out)):
-        if not t.is_cuda or t.device.index != int(device):
-            raise ValueError("%s must be a tensor on cuda:%d (the context's device), not %s" % (name, int(device), t.device))
-        if t.data_ptr() % 16:
-            raise ValueError("%s must be 16-byte aligned" % name)
-        if not t.is_contiguous():
-            raise ValueError("%s must be contiguous" % name)
-    nbytes = probes.numel() * probes.element_size()
-    if nbytes % PROBE_DTYPE.itemsize:
-        raise ValueError("probes must hold whole 32-byte RtLightProbe records")
-    n = nbytes // PROBE_DTYPE.itemsize
-    if out.numel() * out.element_size() != n * PROBE_LIGHT_DTYPE.itemsize:
-        raise ValueError("out must be a contiguous tensor of N * 16 bytes")
+    _device_tensors(device, ("probes", probes), ("out", out))
+    n = record_count("probes", _nbytes(probes), PROBE_DTYPE.itemsize, None, "RtLightProbe")
+    _holds("out", out, n, PROBE_LIGHT_DTYPE.itemsize)
     return n
 
 

@@ -102,7 +102,7 @@ def test_check_draw_box_tensors_refuses_what_the_kernel_could_not_read():
     lights = torch.zeros((12, 4), dtype=torch.float32)
     with pytest.raises(ValueError, match="cuda"):
         render.check_draw_box_tensors(boxes, lights, 0)                # host tensors
-    with pytest.raises(ValueError, match="torch tensors"):
+    with pytest.raises(ValueError, match="boxes must be a torch tensor"):
         render.check_draw_box_tensors(np.zeros((2, 8), np.float32), lights, 0)
-    with pytest.raises(ValueError, match="torch tensors"):
+    with pytest.raises(ValueError, match="face_lights must be a torch tensor"):
         render.check_draw_box_tensors(boxes, None, 0)
