@@ -768,7 +768,7 @@ int rt_draw_stamps_async(RtContext* ctx, const RtUniforms* u, const RtDrawStamp*
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
  * after rt_draw_frame (and rt_draw_boxes) and before or after rt_denoise.  Each light reaches a pixel through one hard shadow ray
  * against the resident region; rt_finalize multiplies lighting by albedo, so the added light is diffuse shading.  Entities cast no
- * shadow in a point light, the source gives no bounce light, and the light belongs to one frame: it enters no accumulation sum or history.  One light,
+ * shadow in a point light here (rt_add_lights_occluded is the call in which they do), the source gives no bounce light, and the light belongs to one frame: it enters no accumulation sum or history.  One light,
  * 32 bytes: */
 typedef struct RtPointLight {     /* 32 bytes */
     float    position[3];  float    radius;     /* world coordinates; nothing is lit at or beyond `radius` */
@@ -870,7 +870,8 @@ int rt_add_lights_async(RtContext* ctx, const RtUniforms* u, const RtPointLight*
  *     RT_ERR_NOT_READY.  nboxes + nmodels == 0, or sunlight == (0, 0, 0): RT_OK, nothing enqueued, no prepass dropped.  (sunlight is
  *     (0, 0, 0) for no sun angle the tests know: below the horizon the shader's sun colour is negative, and the call then removes that
  *     negative term, as the rule says.)  A rejected call changes nothing.
- *   Limits, not bugs: hard shadows only.  The sun only: point lights still ignore entities.  No entity shadow in bounce light.  The
+ *   Limits, not bugs: hard shadows only.  The sun only: in rt_add_lights point lights still ignore entities
+ *     (rt_add_lights_occluded is the call in which they do not).  No entity shadow in bounce light.  The
  *     shadow belongs to one frame and enters no accumulation sum or history.  Crevices narrower than 1/32 of a model whose voxels are
  *     smaller than 1/16 may shade themselves.
  *   Device work per call: one transfer of a 64-byte record per model and one launch, a wave per 8x8 pixel tile; per tile the boxes and
@@ -885,6 +886,61 @@ int rt_shadow_entities(RtContext* ctx, const RtUniforms* u, const RtDrawBox* box
  * and is free again when the call returns. */
 int rt_shadow_entities_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* boxes_dev, uint32_t nboxes, const RtDrawStamp* models,
                              uint32_t nmodels, float strength);
+
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Point-light shadows of entities: rt_add_lights with the entities the
+ * host drew — the very RtDrawBox and RtDrawStamp records of rt_draw_boxes, rt_draw_stamps and rt_shadow_entities — as occluders.  A
+ * torch in the hand, a glowing projectile or an explosion flash is the light a mob standing next to it blocks; indoors and at night
+ * it is the only shadow an entity has.  The call stands in rt_add_lights' place in the order boxes, models, sun shadows, lights,
+ * denoise.  rt_add_lights itself does not change.
+ * The rules.  All arithmetic is fp32 with one rounding per operation; fused operations appear only where rtm_fma or rtm_dot3 is
+ * written; any comparison with a NaN is false.  Results are reproduced bit for bit by tests/light_shadow_ref.py, which tests every
+ * occluder against every (pixel, light) pair that passed the pair test (DESIGN.md "Point-light shadows of entities").
+ *   Everything of rt_add_lights holds word for word: the surface pixel, P', the valid light, the pair test (dist2 > 0 && dist2 < r2 &&
+ *     c > 0), the world's shadow ray with its added exit, weight, sum, writes, which frame, ordering and side effects.  One thing is
+ *     added to the verdict on a (pixel, light) pair that passed the pair test:
+ *   Segment: o = P'; d = rtm_normalize3(v), the direction the world's shadow ray travels in (v times one reciprocal of its length);
+ *     inv_k = 1.0f / d_k; len = rtm_sqrt(dist2), the value the weight uses.
+ *   A box blocks the pair: rt_shadow_entities' slab rule with this o, d and inv — some axis gave a bound, every d_k == 0 axis passes
+ *     (lo_k < o_k && o_k < hi_k), t_out > 0 and t_in < t_out — and also t_in < len.  So a box beyond the light does not shade it, a
+ *     surface point inside a box is shaded by it, and a light inside a box lights nothing outside it.  Valid box: rt_draw_boxes'.  The
+ *     device skips an invalid box in both calls; rt_add_lights_occluded also rejects the whole call (RT_ERR_INVALID_ARG) before
+ *     anything is enqueued.
+ *   A model blocks the pair: the bounding box is rt_shadow_entities' (lo = origin, hi_k = rtm_fma(float(E'_k), scale, origin_k)) and is
+ *     entered iff the box rule above holds for it, t_in < len included.  The first cell follows rt_shadow_entities' two cases:
+ *     entered from outside when t_in > 0, started inside otherwise.  The walk is rt_draw_stamps' steps (1) to (3) with one added stop
+ *     between (2) and (3): if the minimum plane time tk of step (2) is not < len, the light lies in the current cell or before its
+ *     far plane; the walk stops there and the model does not block.  The model blocks iff the walk stops on an RT_STAMP_SOLID cell; a
+ *     solid cell of the same model behind the light does not block.  The step bound E'_x + E'_y + E'_z stays.  Valid record:
+ *     rt_draw_stamps'; an invalid record rejects either call on the host.
+ *   Verdict: the light is visible at the pixel iff no valid box and no model blocks the pair and rt_add_lights' shadow ray says
+ *     visible.  (Entities first, the world's ray only for the pairs no entity blocks: that order is the cost model's, the result does
+ *     not depend on it.)
+ *   Zero occluders: with nboxes + nmodels == 0 the call is rt_add_lights, every bit and every side effect.
+ *   Self-shadowing follows from the rules: a box's own lit faces have c > 0, their segment leaves the box and t_out <= 0 on the
+ *     face's axis; a concave model shades itself through the walk; crevices narrower than 1/32 of a model whose voxels are smaller
+ *     than 1/16 may shade themselves, as for rt_shadow_entities.
+ *   Side effects: rt_add_lights'.  The call names its stamps as a draw does: rt_stamp_destroy after an enqueued call waits for it.
+ *   Errors, all checked on the host before anything is enqueued: NULL ctx or u, a NULL `lights` with count > 0, count > 1024, an
+ *     invalid light in the synchronous call; for the occluder arrays a NULL array with its count above 0, a count above 4096, a model
+ *     record that is not valid, an invalid box in the synchronous call: RT_ERR_INVALID_ARG.  tile_world != 1: RT_ERR_UNIMPLEMENTED.
+ *     No frame drawn yet, or no world resident: RT_ERR_NOT_READY.  count == 0: RT_OK, nothing enqueued, no prepass dropped, whatever
+ *     the occluder counts.  A rejected call changes nothing.
+ *   Limits, not bugs: hard shadows only.  No per-light "owner" exemption: a host that carries a light inside an entity's box leaves
+ *     that box out of this call's list.  The light and its shadows belong to one frame and enter no accumulation sum or history.
+ *     Bounce light still ignores entities.
+ *   Device work per call: one transfer of a 64-byte record per model and one launch, a wave per 8x8 pixel tile; per tile the lights
+ *     pass rt_add_lights' cull, the boxes and the models' bounding boxes pass ONE conservative cull against the hull of the tile's
+ *     surface points and candidate lights, and only the survivors (up to 64 of a kind; beyond that the tile scans every record) are
+ *     tested per pair; the synchronous call adds one transfer of the lights and boxes.
+ * Host pointers; returns when the planes are written. */
+int rt_add_lights_occluded(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights, uint32_t count, const RtDrawBox* boxes,
+                           uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels);
+/* Same, enqueued.  `lights_dev` and `boxes_dev` are device memory and must pass rt_trace_rays_async's test (16-byte aligned memory of
+ * the context's device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued; an invalid light or box is skipped on
+ * the device.  `models` is a host pointer here too, as for rt_shadow_entities_async and for the same reason, and is free again when
+ * the call returns. */
+int rt_add_lights_occluded_async(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights_dev, uint32_t count,
+                                 const RtDrawBox* boxes_dev, uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels);
 
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Entity queries: what a ray or a pixel hits among the entities a host
  * draws — clicking a mob, a projectile against it, whether one mob sees another past a third, whether the cursor is on the mob or on
@@ -1203,7 +1259,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: rt_shadow_entities, rt_shadow_entities_async (entity shadows: drawn boxes and models take the
  *        sun's direct term out of the lighting planes where they shade a pixel).
  *        Additive, same minor version: RtEntityHit, RT_ENTITY_*, rt_trace_entities, rt_trace_entities_async, rt_pick_entities (entity
- *        queries: what a ray or a pixel hits among the drawn boxes and models, under the draws' own rules). */
+ *        queries: what a ray or a pixel hits among the drawn boxes and models, under the draws' own rules).
+ *        Additive, same minor version: rt_add_lights_occluded, rt_add_lights_occluded_async (point-light shadows of entities:
+ *        rt_add_lights with the drawn boxes and models blocking the segment from a pixel's surface point to the light). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

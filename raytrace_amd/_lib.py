@@ -63,6 +63,8 @@ AMD_FUNCTIONS = {
     "rt_shadow_entities_async": (INT, [P, UNI, P, U32, P, U32, FLOAT]),
     "rt_add_lights": (INT, [P, UNI, P, U32]),
     "rt_add_lights_async": (INT, [P, UNI, P, U32]),
+    "rt_add_lights_occluded": (INT, [P, UNI, P, U32, P, U32, P, U32]),
+    "rt_add_lights_occluded_async": (INT, [P, UNI, P, U32, P, U32, P, U32]),
     "rt_denoise": (INT, [P, INT]),
     "rt_finalize": (INT, [P]),
     "rt_denoise_planes": (INT, [P, P, P, P, INT]),
@@ -168,6 +170,7 @@ HOST_FUNCTIONS = {
     "rth_pipeline_set_models": (INT, [P, P, P, U32]),
     "rth_pipeline_set_lights": (INT, [P, P, U32]),
     "rth_pipeline_enable_entity_shadows": (INT, [P, FLOAT]),
+    "rth_pipeline_enable_light_shadows": (INT, [P, INT]),
 }
 
 _amd = None

@@ -1,12 +1,14 @@
 // api_passes.hip — the passes over the frame drawn last, each one launch on the stream that frame ended on: entity boxes
 // (rt_draw_boxes[_async]) and voxel-model entities (rt_draw_stamps[_async]) between the frame and its post passes, entity shadows
-// (rt_shadow_entities[_async]) behind the entity draws, point lights (rt_add_lights[_async]) behind those.  What the passes share is
+// (rt_shadow_entities[_async]) behind the entity draws, point lights (rt_add_lights[_async], and rt_add_lights_occluded[_async] with the
+// entities as occluders) behind those.  What the passes share is
 // here once: the prologue (pass_begin), the verdict on a batch of models (models_check), the models' way to the device
 // (upload_models) and the planes a pass writes (planes_written); the synchronous calls' staging is rt_context.hpp's stage_sync.
 //
 // Every launch follows the queries enqueued so far (ev_query): their results may be its records or face lights.  The passes that
 // read the region (lights, shadows) find it on their stream: every world change runs there too, the earlier ones in front, and a
 // later one — whichever lane's stream it finds as the context's by then — first joins every lane (world_change_begin).
+#include "light_shadows_check.hpp"
 #include "lights_check.hpp"
 #include "rt_context.hpp"
 #include "shadows_check.hpp"
@@ -196,6 +198,40 @@ int shadow_enqueue(RtContext* c, const RtUniforms* u, const void* boxes_dev, uin
     return RT_OK;
 }
 
+// ---- point lights with the entities as occluders: device lights and boxes (staged by the synchronous call), host models ----------
+int lights_occluded_begin(RtContext* c, const char* fn, const RtUniforms* u, const void* lights, uint32_t count, const void* boxes, uint32_t nboxes,
+                          const RtDrawStamp* models, uint32_t nmodels, bool* work) {
+    const int rc = pass_begin(c, fn, light_shadow_args_error(u, lights, count, boxes, nboxes, models, nmodels), true, count, work);
+    return rc == RT_OK && *work ? models_check(c, fn, models, nmodels, "nothing was changed") : rc;
+}
+
+// With no occluder the call is rt_add_lights, every bit and every side effect.
+int lights_occluded_enqueue(RtContext* c, const RtUniforms* u, const void* lights_dev, uint32_t count, const void* boxes_dev, uint32_t nboxes,
+                            const RtDrawStamp* models, uint32_t nmodels) {
+    if (nboxes + nmodels == 0u) return add_lights_launch(c, u, lights_dev, count);
+    const rtd::Frame f = frame_of(c, u);
+    rtd::LightShadowArgs a;
+    a.lights = reinterpret_cast<const uint4*>(lights_dev);
+    a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
+    a.recs = nullptr;
+    a.count = count; a.nboxes = nboxes; a.nmodels = nmodels;
+    StagingSet* s = nullptr;
+    if (nmodels > 0u) {
+        uint8_t* recs;
+        const int rc = upload_models(c, models, nmodels, nullptr, 0u, c->stream, &s, &recs);
+        if (rc != RT_OK) return rc;
+        a.recs = reinterpret_cast<const uint4*>(recs);
+    }
+    planes_written(c, false);
+    RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
+    {
+        LaunchTimer t(c, 1);
+        RT_HIP(c, rtd::launch_add_lights_occluded(scene_of(c), f, planes_of(c), a, c->stream));
+    }
+    if (s) RT_HIP(c, s->ev_applied.record(c->stream));
+    return RT_OK;
+}
+
 // night: the frame has no sun term
 bool sun_is_dark(const RtContext* c, const RtUniforms* u) {
     const rtd::Frame f = frame_of(c, u);
@@ -310,6 +346,36 @@ int rt_shadow_entities_async(RtContext* ctx, const RtUniforms* u, const RtDrawBo
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_shadow_entities_async: boxes_dev must be 16-byte aligned memory of the context's device");
     if (sun_is_dark(ctx, u)) return RT_OK;
     return shadow_enqueue(ctx, u, boxes_dev, nboxes, models, nmodels, strength);
+}
+
+int rt_add_lights_occluded(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights, uint32_t count, const RtDrawBox* boxes, uint32_t nboxes,
+                           const RtDrawStamp* models, uint32_t nmodels) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    int rc = lights_occluded_begin(ctx, "rt_add_lights_occluded", u, lights, count, boxes, nboxes, models, nmodels, &work);
+    if (rc != RT_OK || !work) return rc;
+    uint32_t bad;
+    const int which = light_shadow_first_invalid(lights, count, boxes, nboxes, &bad);
+    if (which != 0)
+        return fail(ctx, RT_ERR_INVALID_ARG, std::string("rt_add_lights_occluded: ") + (which == 1 ? "light " : "box ") + std::to_string(bad) +
+                                                 (which == 1 ? " is not a valid light" : " is not a valid box"));
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    uint8_t* dev[2];
+    rc = stage_sync(ctx, ctx->stream, {{lights, (size_t)count * sizeof(RtPointLight)}, {boxes, (size_t)nboxes * sizeof(RtDrawBox)}}, dev);
+    if (rc != RT_OK) return rc;
+    return finish_sync(ctx, lights_occluded_enqueue(ctx, u, dev[0], count, dev[1], nboxes, models, nmodels));
+}
+
+int rt_add_lights_occluded_async(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights_dev, uint32_t count, const RtDrawBox* boxes_dev,
+                                 uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    const int rc = lights_occluded_begin(ctx, "rt_add_lights_occluded_async", u, lights_dev, count, boxes_dev, nboxes, models, nmodels, &work);
+    if (rc != RT_OK || !work) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, lights_dev) || (nboxes > 0u && !query_device_ptr(ctx, boxes_dev)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_add_lights_occluded_async: lights_dev and boxes_dev must be 16-byte aligned memory of the context's device");
+    return lights_occluded_enqueue(ctx, u, lights_dev, count, boxes_dev, nboxes, models, nmodels);
 }
 
 }  // extern "C"

@@ -258,6 +258,16 @@ struct ShadowArgs {
 };
 hipError_t launch_shadow_entities(const Scene& sc, const Frame& f, const Planes& pl, const ShadowArgs& a, hipStream_t st);
 
+// rt_lights.hip: launch_add_lights with the drawn entities as occluders of each (pixel, light) segment (rt_add_lights_occluded).  One
+// launch; a wave owns an 8x8 pixel tile and culls the occluders once against the hull of its segments.
+struct LightShadowArgs {
+    const uint4* lights;  // RtPointLight[count] (two uint4 each)
+    const uint4* boxes;   // RtDrawBox[nboxes] (two uint4 each; lo and hi are read); an invalid box is skipped
+    const uint4* recs;    // DrawStampRecord[nmodels] (api/draw_stamps.hpp; four uint4 each), resolved and validated on the host
+    uint32_t count, nboxes, nmodels;
+};
+hipError_t launch_add_lights_occluded(const Scene& sc, const Frame& f, const Planes& pl, const LightShadowArgs& a, hipStream_t st);
+
 // rt_entity_query.hip: ray and pixel queries against drawn entities (rt_trace_entities, rt_pick_entities).  One launch, one lane per
 // ray: the world's hit as rt_query.hip finds it, then the nearest box or model under the draws' rules, depth-tested against it.
 struct EntityQueryArgs {

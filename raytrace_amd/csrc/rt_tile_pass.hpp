@@ -1,5 +1,6 @@
 // rt_tile_pass.hpp — the scaffold of the passes over a drawn frame, one wave64 per 8x8 pixel tile and four tiles per workgroup
-// (rt_boxes.hip: k_draw_boxes, rt_draw_stamps.hip: k_draw_stamps, rt_lights.hip: k_add_lights, rt_shadows.hip: k_shadow_entities):
+// (rt_boxes.hip: k_draw_boxes, rt_draw_stamps.hip: k_draw_stamps, rt_lights.hip: k_add_lights and k_add_lights_occluded,
+// rt_shadows.hip: k_shadow_entities):
 //   - TileLane: which tile a wave owns and which pixel a lane, and the grid of a launch;
 //   - the batch idiom's small pieces: a record's words broadcast from lane j (bcast, rec_xyz), the valid box, a model record decoded;
 //   - the entity draws' geometry: the primary direction of a pixel, what the cull knows of a tile's directions (tile_dirs), the

@@ -240,6 +240,7 @@ int rth_pipeline_set_lights(void* p, const RtPointLight* lights, uint32_t count)
     return static_cast<render::Pipeline*>(p)->set_lights(lights, count);
 }
 int rth_pipeline_enable_entity_shadows(void* p, float strength) { return static_cast<render::Pipeline*>(p)->enable_entity_shadows(strength); }
+int rth_pipeline_enable_light_shadows(void* p, int on) { static_cast<render::Pipeline*>(p)->enable_light_shadows(on != 0); return RT_OK; }
 const char* rth_pipeline_last_error(void* p) { return static_cast<render::Pipeline*>(p)->last_error(); }
 // Pipeline::pick: hit (RtRayHit), adjacent and world (int32[3] each)
 int rth_pipeline_pick(void* p, int x, int y_from_top, RtRayHit* hit, int32_t* adjacent, int32_t* world) {

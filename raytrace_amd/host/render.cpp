@@ -231,7 +231,9 @@ int Pipeline::draw_frame(game::Game& game) {
     if (rc == RT_OK && shadow_strength_ > 0.0f && !(boxes_.empty() && models_.empty()))   // the drawn entities shade what lies behind them from the sun
         rc = rt_shadow_entities(ctx_, &u, boxes_.data(), (uint32_t)boxes_.size(), models_.data(), (uint32_t)models_.size(), shadow_strength_);
     if (rc == RT_OK && !lights_.empty())                             // moving lights shade the frame and its entities; the denoise filters them
-        rc = rt_add_lights(ctx_, &u, lights_.data(), (uint32_t)lights_.size());
+        rc = light_shadows_ ? rt_add_lights_occluded(ctx_, &u, lights_.data(), (uint32_t)lights_.size(), boxes_.data(), (uint32_t)boxes_.size(),
+                                                     models_.data(), (uint32_t)models_.size())   // ... and the entities shade each other and the world from them
+                            : rt_add_lights(ctx_, &u, lights_.data(), (uint32_t)lights_.size());
     if (rc == RT_OK && post_) {                                      // the same command buffer goes on (:98-123), one submit (:229-235)
         // six bilateral_denoise.comp dispatches, sizes 1,2,4,8,8,16
         rc = history_denoise_ ? rt_denoise_history(ctx_, &denoise_params_) : rt_denoise(ctx_, post_faithful_ ? 1 : 0);

@@ -148,6 +148,9 @@ class Pipeline {
     // above, behind their draws and in front of the point lights — the intended order: boxes, models, shadows, lights, denoise.
     // strength in (0, 1]; 0 switches it off again.  RT_ERR_INVALID_ARG for anything else.
     int enable_entity_shadows(float strength);
+    // Point-light shadows of entities: every draw_frame from now on hands the boxes and models set above to the lights step, which
+    // then runs rt_add_lights_occluded in rt_add_lights' place; the order stays boxes, models, sun shadows, lights, denoise.
+    void enable_light_shadows(bool on) { light_shadows_ = on; }
     bool post_passes() const { return post_; }
 
  private:
@@ -172,6 +175,7 @@ class Pipeline {
     std::vector<RtProbeLight> model_lights_;
     std::vector<RtPointLight> lights_; // set_lights
     float shadow_strength_ = 0.0f;     // enable_entity_shadows; 0 = off
+    bool light_shadows_ = false;       // enable_light_shadows
     std::unique_ptr<TerrainUploadManager> tum_;
     std::unique_ptr<world::ChunkStorage> chunks_;
     bool stream_on_device_ = false;

@@ -13,6 +13,7 @@
 //            [--boxes N]
 //            [--entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--lights N] [--shadows N [--shadow-models]]
+//            [--light-shadows [--lights N] [--boxes B] [--models M] [--occluder-spread S] [--occluders-far]]
 //
 // --post: the reference's whole frame — ray trace, six denoise dispatches, finalize (pipeline.rs:86-123) — per draw_frame
 // (Pipeline::enable_post_passes; one device only: the passes need the whole frame).
@@ -93,6 +94,11 @@
 // units along the ray where the pixel shows sky) — and rt_add_lights adds them to a freshly drawn --width x --height frame, 20 times.
 // One JSON line: the device time of the pass (the launch bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time of
 // rt_add_lights and the pixels lit.
+// --light-shadows [--lights N] [--boxes B] [--models M]: instead of the frame loop, point-light shadows of entities.  --lights' N
+// lights (64 without --lights); B player-sized boxes and M models (a 5 x 4 x 6 stamp at --model-scale, the 48 orientations in turn),
+// each within --occluder-spread units (3) of a light, in turn — or, with --occluders-far, 400 units above it, where no segment of the
+// frame passes.  rt_add_lights_occluded lights a freshly drawn frame with them 20 times, then rt_add_lights does as the yardstick.
+// One JSON line: device time (the launch bracketed by events) and call-to-return time of both, and the pixels the entities changed.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -802,6 +808,115 @@ int run_shadows(rt::game::Game& game, const std::vector<uint8_t>& noise, int wid
     return 0;
 }
 
+// --light-shadows: see the head of the file
+int run_light_shadows(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t nlights,
+                      uint32_t nboxes, uint32_t nmodels, float scale, float spread, bool far_away) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    // the lights: --lights' own, so that the two runs light the same frame
+    std::vector<int32_t> xy(2u * (size_t)nlights);
+    for (uint32_t i = 0; i < nlights; i++) {
+        xy[2u * i] = std::min(width - 1, (int)(rnd() * (float)width));
+        xy[2u * i + 1] = std::min(height - 1, (int)(rnd() * (float)height));
+    }
+    std::vector<RtRayHit> hits(nlights);
+    int rc = nlights ? rt_pick_pixels(ctx, &u, xy.data(), nlights, hits.data()) : RT_OK;
+    std::vector<RtPointLight> lights(nlights);
+    for (uint32_t i = 0; i < nlights && rc == RT_OK; i++) {
+        RtPointLight& l = lights[i];
+        l = RtPointLight{};
+        const float off = 1.0f + 3.0f * rnd();
+        if (hits[i].kind == RT_HIT_SOLID) {
+            for (int a = 0; a < 3; a++) l.position[a] = hits[i].position[a];
+            l.position[hits[i].normal / 2u] += hits[i].normal % 2u == 0u ? off : -off;
+        } else {
+            const float sx = ((float)xy[2u * i] / (float)width) * 2.0f - 1.0f, sy = ((float)xy[2u * i + 1] / (float)height) * 2.0f - 1.0f;
+            float v[3], len = 0.0f;
+            for (int a = 0; a < 3; a++) { v[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; len += v[a] * v[a]; }
+            len = std::sqrt(len);
+            for (int a = 0; a < 3; a++) l.position[a] = u.origin[a] + v[a] / len * 30.0f;
+        }
+        l.radius = 8.0f;
+        l.color[0] = 20.0f + 20.0f * rnd(); l.color[1] = 15.0f + 15.0f * rnd(); l.color[2] = 5.0f + 10.0f * rnd();
+    }
+    // the stamp of the models: a third solid, the rest air and absent in turn
+    const int32_t E[3] = {5, 4, 6};
+    std::vector<uint32_t> mats((size_t)E[0] * E[1] * E[2]);
+    std::vector<uint8_t> state(mats.size());
+    for (size_t i = 0; i < mats.size(); i++) {
+        state[i] = rnd() < 0.3333f ? RT_STAMP_SOLID : (i & 1u ? RT_STAMP_AIR : RT_STAMP_ABSENT);
+        mats[i] = (1u << 15) | ((40u + (uint32_t)i % 80u) << 14) | ((30u + (uint32_t)i % 90u) << 7) | (20u + (uint32_t)i % 100u);
+    }
+    uint32_t id = 0;
+    if (nmodels && p->stamp_create(E, mats.data(), state.data(), &id) != RT_OK) { std::fprintf(stderr, "stamp_create failed: %s\n", p->last_error()); delete p; return 1; }
+    static const int perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    // the occluders: each within `spread` units of a light, in turn — or 400 units above it, where no segment of the frame passes
+    auto centre = [&](uint32_t i, float c[3]) {
+        const RtPointLight& l = lights[i % std::max(nlights, 1u)];
+        for (int a = 0; a < 3; a++) c[a] = (nlights ? l.position[a] : u.origin[a]) + spread * (2.0f * rnd() - 1.0f);
+        if (far_away) c[2] += 400.0f;
+    };
+    std::vector<RtDrawBox> boxes(nboxes);
+    for (uint32_t i = 0; i < nboxes; i++) {
+        float c[3];
+        centre(i, c);
+        RtDrawBox& b = boxes[i];
+        b = RtDrawBox{};
+        for (int a = 0; a < 3; a++) { const float half = a == 2 ? 0.9f : 0.3f; b.lo[a] = c[a] - half; b.hi[a] = c[a] + half; }   // a player's box
+        b.emission = 0xFF000000u;
+    }
+    std::vector<RtDrawStamp> models(nmodels);
+    for (uint32_t i = 0; i < nmodels; i++) {
+        float c[3];
+        centre(i + nboxes, c);
+        RtDrawStamp& m = models[i];
+        m = RtDrawStamp{};
+        m.stamp = id; m.scale = scale; m.orient = (uint8_t)(i % 48u); m.emission = 0xFF000000u;
+        for (int a = 0; a < 3; a++) m.origin[a] = c[a] - 0.5f * (float)E[perms[m.orient >> 3][a]] * scale;
+    }
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    const size_t npix = (size_t)width * (size_t)height;
+    std::vector<float> plain(4u * npix), shaded(4u * npix);
+    const int reps = 20;
+    double device_ms[2] = {0.0, 0.0}, call_ms[2] = {0.0, 0.0};   // 0: rt_add_lights_occluded; the yardstick: 1 rt_add_lights of the same lights
+    uint32_t launches = 0;
+    for (int pass = 0; pass < 2 && rc == RT_OK; pass++) {
+        for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {   // (the first repetition warms the staging up)
+            RtTiming tm{};
+            rc = rt_draw_frame(ctx, &u);
+            if (rc == RT_OK) rc = rt_sync(ctx);
+            if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);   // (drains the frame's own launches)
+            auto t = std::chrono::steady_clock::now();
+            if (rc == RT_OK)
+                rc = pass == 0 ? rt_add_lights_occluded(ctx, &u, lights.data(), nlights, boxes.data(), nboxes, models.data(), nmodels)
+                               : rt_add_lights(ctx, &u, lights.data(), nlights);
+            const double call = ms_since(t);
+            if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);
+            if (i > 0) { device_ms[pass] += tm.shade_ms / reps; call_ms[pass] += call / reps; if (pass == 0) launches += tm.other_launches; }
+        }
+        if (rc == RT_OK) rc = rt_readback(ctx, RT_BUF_LIGHTING_F32, (pass == 0 ? shaded : plain).data(), npix * 16u);
+    }
+    if (rc != RT_OK) { std::fprintf(stderr, "point-light shadows failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    uint64_t darker = 0;
+    for (size_t i = 0; i < npix; i++) darker += std::memcmp(&plain[4u * i], &shaded[4u * i], 16) != 0;
+    std::printf("{\"light_shadows\": %u, \"boxes\": %u, \"models\": %u, \"model_scale\": %g, \"spread\": %g, \"far\": %d, \"frame\": \"%dx%d spp %d depth %d\", "
+                "\"add_lights_occluded_device_ms\": %.4f, \"add_lights_occluded_call_ms\": %.4f, \"launches_per_call\": %.2f, "
+                "\"add_lights_device_ms\": %.4f, \"add_lights_call_ms\": %.4f, \"pixels_shadowed\": %llu}\n",
+                nlights, nboxes, nmodels, (double)scale, (double)spread, far_away ? 1 : 0, width, height, spp, depth, device_ms[0], call_ms[0],
+                (double)launches / reps, device_ms[1], call_ms[1], (unsigned long long)darker);
+    delete p;
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -814,8 +929,8 @@ int main(int argc, char** argv) {
     long long entity_rays = 0;
     bool coherent = false;
     long long rays = 0, boxes = -1, lights = -1, models = -1, shadows = -1;
-    bool shadow_models = false;
-    float model_scale = 0.125f;
+    bool shadow_models = false, light_shadows = false, occluders_far = false;
+    float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
     bool reproject = false, stream = false, stream_history = false, history_denoise = false;
     float camera_step = 0.0f;
@@ -853,6 +968,9 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
         else if (want("--boxes")) boxes = std::atoll(argv[++i]);
         else if (want("--lights")) lights = std::atoll(argv[++i]);
+        else if (std::strcmp(argv[i], "--light-shadows") == 0) light_shadows = true;
+        else if (want("--occluder-spread")) occluder_spread = std::strtof(argv[++i], nullptr);
+        else if (std::strcmp(argv[i], "--occluders-far") == 0) occluders_far = true;
         else if (want("--models")) models = std::atoll(argv[++i]);
         else if (want("--shadows")) shadows = std::atoll(argv[++i]);
         else if (std::strcmp(argv[i], "--shadow-models") == 0) shadow_models = true;
@@ -873,6 +991,7 @@ int main(int argc, char** argv) {
     }
     if (shadows < -1 || shadows > 4096) { std::fprintf(stderr, "--shadows must be in 0..4096\n"); return 2; }
     if (lights < -1 || lights > 1024) { std::fprintf(stderr, "--lights must be in 0..1024\n"); return 2; }
+    if (!(occluder_spread >= 0.0f && occluder_spread <= 1024.0f)) { std::fprintf(stderr, "--occluder-spread must be in 0..1024\n"); return 2; }
     if (frames_in_flight != 1 && (frames_in_flight != 2 || gpus > 1)) { std::fprintf(stderr, "--frames-in-flight is 1, or 2 on one device\n"); return 2; }
     if ((reproject || camera_step != 0.0f) && gpus > 1) { std::fprintf(stderr, "--reproject and --camera-step need one device\n"); return 2; }
     if (gpus > 1) gather = true;
@@ -901,6 +1020,9 @@ int main(int argc, char** argv) {
     std::printf("Creating renderer (and world.)\n");                 // main.rs:10
     auto t0 = std::chrono::steady_clock::now();
     game.generate_world(0x5EED);
+    if (light_shadows)
+        return run_light_shadows(game, noise, width, height, spp, depth, device, (uint32_t)(lights < 0 ? 64 : lights), (uint32_t)(boxes < 0 ? 0 : boxes),
+                                 (uint32_t)(models < 0 ? 0 : models), model_scale, occluder_spread, occluders_far);
     if (entity_rays > 0)
         return run_entity_rays(game, noise, width, height, spp, depth, device, (uint32_t)entity_rays, (uint32_t)(boxes < 0 ? 0 : boxes),
                                (uint32_t)(models < 0 ? 0 : models), model_scale, coherent);

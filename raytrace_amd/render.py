@@ -559,6 +559,25 @@ class Context:
         n = check_point_light_tensors(lights, self._device)
         self._check(self._lib.rt_add_lights_async(self._h, C.byref(uniforms), _dp(lights), n))
 
+    def add_lights_occluded(self, uniforms, lights, boxes=None, models=None):
+        """rt_add_lights_occluded: add_lights with the drawn `boxes` (DRAW_BOX_DTYPE[N]) and `models` (DRAW_STAMP_DTYPE[M]) as occluders: a
+        light adds nothing at a pixel where an entity lies between the pixel's surface point and the light.  Synchronous; an invalid
+        record fails the whole call (RtError, INVALID_ARG).  With no occluder the call is add_lights."""
+        lights = _records(lights, POINT_LIGHT_DTYPE)
+        boxes, models = _entity_records(boxes, models)
+        self._check(self._lib.rt_add_lights_occluded(self._h, C.byref(uniforms), _ptr_or_none(lights), lights.size, _ptr_or_none(boxes), boxes.size,
+                                                     _ptr_or_none(models), models.size))
+
+    def add_lights_occluded_async(self, uniforms, lights, boxes=None, models=None):
+        """rt_add_lights_occluded_async: `lights` a torch device tensor as for add_lights_async, `boxes` one as for shadow_entities_async
+        (or None), `models` host records (free again on return).  Enqueued behind the frame drawn last; an invalid light or box is
+        skipped on the device, an invalid model fails the call before anything is enqueued."""
+        n = check_point_light_tensors(lights, self._device)
+        nb = 0 if boxes is None else check_shadow_box_tensor(boxes, self._device)
+        models = _records(models, DRAW_STAMP_DTYPE)
+        self._check(self._lib.rt_add_lights_occluded_async(self._h, C.byref(uniforms), _dp(lights), n, _dp(boxes) if nb else None, nb,
+                                                           _ptr_or_none(models), models.size))
+
     # -- frames ------------------------------------------------------------------------------------------
     def draw_frame(self, uniforms):
         self._check(self._lib.rt_draw_frame(self._h, C.byref(uniforms)))
@@ -945,6 +964,11 @@ class Pipeline:
         (set_boxes, set_models) behind their draws and in front of the point lights; strength in (0, 1], 0 switches it off again."""
         self._check(_lib.host().rth_pipeline_enable_entity_shadows(self._h, float(strength)),
                     "enable_entity_shadows: strength must be 0 (off) or lie in (0, 1]")
+
+    def enable_light_shadows(self, on=True):
+        """Pipeline::enable_light_shadows: every draw_frame from now on hands the boxes and models set (set_boxes, set_models) to the
+        lights step, which runs rt_add_lights_occluded in rt_add_lights' place: the entities cast shadows in the point lights."""
+        self._check(_lib.host().rth_pipeline_enable_light_shadows(self._h, 1 if on else 0), "enable_light_shadows")
 
     def close(self):
         if self._h:
