@@ -1,7 +1,10 @@
 """Reference for one light probe (rt_probe_light, include/rt_abi.h), composed from what the CPU oracle exports: trace_ray, sun,
 sample_sky, diffuse_direction, noise_lookup and the arithmetic contract's mod, plus the albedo decode of raytrace.comp:156-158.  The
 loop and the unwind order are those of the oracle's level_light (raytrace.comp:324-349 generalised to `depth` levels), in numpy
-float32.  Region 256 only (pyoracle.trace_ray is).  tests/test_light_probe_contract.py pins it to the oracle's renderer."""
+float32.  pyoracle.trace_ray is region 256 only; for another region pass `trace`, e.g. restated_trace(), which goes through
+tests/ray_query_ref.py (Python loops: a few dozen probes).  tests/test_light_probe_contract.py pins it to the oracle's renderer."""
+import types
+
 import numpy as np
 
 from oracle import pyoracle as po
@@ -45,8 +48,22 @@ def noise_value(noise, off, level):
     return _texel(noise, m[0], m[1])
 
 
-def probe_sample(mats, mine, noise, sun_angle, seed, lr, position, normal, cell, depth, stats=None):
-    """One sample: (light float32[3], sun1.air).  stats (a dict) receives 'levels', the deepest level the path reached."""
+def restated_trace(mats, mine, lr, R):
+    """trace(pos, direction) for probe_sample / probe_light on a region of edge R: tests/ray_query_ref.trace_ray's answer with the
+    fields of the oracle's hit that the probe reads."""
+    from tests import ray_query_ref as rq
+
+    def trace(pos, direction):
+        h = rq.trace_ray(mats, mine, pos, direction, lr, R)
+        return types.SimpleNamespace(air=h["kind"] == rq.HIT_AIR, position=h["position"], normal=h["normal"], packed_material=h["material"])
+    return trace
+
+
+def probe_sample(mats, mine, noise, sun_angle, seed, lr, position, normal, cell, depth, stats=None, trace=None):
+    """One sample: (light float32[3], sun1.air).  stats (a dict) receives 'levels', the deepest level the path reached; `trace`
+    replaces the oracle's trace_ray (region 256) as trace(pos, direction)."""
+    if trace is None:
+        trace = lambda pos, direction: po.trace_ray(mats, mine, pos, direction, lr)   # noqa: E731
     sunangle, sunlight = po.sun(sun_angle)
     off = noise_offset(noise, seed % NOISE_BYTES, cell)
     first = [False]
@@ -57,13 +74,13 @@ def probe_sample(mats, mine, noise, sun_angle, seed, lr, position, normal, cell,
         nr, ng = noise_value(noise, off, level)
         light = [f32(0.0), f32(0.0), f32(0.0)]
         d = [f32(sunangle[0] + f32(nr * f32(0.05))), f32(sunangle[1] + f32(ng * f32(0.05))), f32(sunangle[2] + f32(f32(0.0) * f32(0.05)))]
-        sun = po.trace_ray(mats, mine, pos, po.normalize(d), lr)                                # trace_sun, :185-187
+        sun = trace(pos, po.normalize(d))                                                       # trace_sun, :185-187
         if sun.air:
             light = [f32(light[k] + sunlight[k]) for k in range(3)]
             if level == 1:
                 first[0] = True
         ddir = po.diffuse_direction(nrm, (nr, ng))
-        dif = po.trace_ray(mats, mine, pos, ddir, lr)
+        dif = trace(pos, ddir)
         if dif.air:
             sky = po.sample_sky(ddir, sun_angle, True)
             light = [f32(light[k] + sky[k]) for k in range(3)]
@@ -81,13 +98,13 @@ def probe_sample(mats, mine, noise, sun_angle, seed, lr, position, normal, cell,
     return np.array([f32(f32(0.0) + l1[k]) for k in range(3)], f32), first[0]
 
 
-def probe_light(mats, mine, noise, sun_angle, seed, lr, position, normal, cell, samples, depth):
+def probe_light(mats, mine, noise, sun_angle, seed, lr, position, normal, cell, samples, depth, trace=None):
     """The RtProbeLight of one probe: (light float32[3] = the ordered fp32 sum of the samples / samples, sun_samples)."""
     total = np.zeros(3, f32)
     sun_samples = 0
     with np.errstate(all="ignore"):
         for s in range(samples):
-            light, sun = probe_sample(mats, mine, noise, sun_angle, (int(seed) + s) % NOISE_BYTES, lr, position, normal, cell, depth)
+            light, sun = probe_sample(mats, mine, noise, sun_angle, (int(seed) + s) % NOISE_BYTES, lr, position, normal, cell, depth, trace=trace)
             total = (total + light).astype(f32)
             sun_samples += bool(sun)
         return (total / f32(samples)).astype(f32), sun_samples

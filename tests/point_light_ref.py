@@ -20,6 +20,7 @@ MAX_COORD, MAX_RADIUS, MAX_COLOR = f32(4194304.0), f32(1024.0), f32(1048576.0)
 OFFSET = f32(0.03125)
 TRACE_LIMIT = 2048                       # RT_TRACE_LIMIT
 WRITTEN = ("lighting_f32", "lighting_rgba16")
+END_REACHED, END_AIR, END_SOLID, END_LIMIT = 0, 1, 2, 3      # how a shadow ray ended (trace_visible's `ends`)
 
 
 def dot3(a, b):
@@ -67,17 +68,19 @@ def _fetch(mine, R, pos):
     return np.where(ok, mine[(i[:, 2] * R + i[:, 1]) * R + i[:, 0]], 0).astype(np.int64)
 
 
-def trace_visible(minefield, region, lr, origin, v, dist2):
+def trace_visible(minefield, region, lr, origin, v, dist2, ends=False):
     """visible bool[n]: the contract's shadow ray from origin[n, 3] in direction v[n, 3] (normalised here), ended as visible once
-    rtm_dot3(pos - origin, pos - origin) >= dist2[n]."""
+    rtm_dot3(pos - origin, pos - origin) >= dist2[n].  With `ends`: (visible, end int[n]) — how each ray ended, END_REACHED (as far from
+    its origin as the light), END_AIR (left the window), END_SOLID or END_LIMIT (RT_TRACE_LIMIT steps: blocked)."""
     mine = np.ascontiguousarray(minefield, dtype=np.uint8).reshape(-1)
     R = int(region)
     assert mine.size == R ** 3
     origin, v, dist2 = np.asarray(origin, dtype=f32).reshape(-1, 3), np.asarray(v, dtype=f32).reshape(-1, 3), np.asarray(dist2, dtype=f32).reshape(-1)
     n = origin.shape[0]
     visible = np.zeros(n, dtype=bool)
+    end = np.full(n, END_LIMIT, dtype=np.int64)
     if n == 0:
-        return visible
+        return (visible, end) if ends else visible
     half = f32(R) / f32(2)
     lrf = np.array([lr[0], lr[1], lr[2]], dtype=f32)
     with np.errstate(all="ignore"):
@@ -103,9 +106,10 @@ def trace_visible(minefield, region, lr, origin, v, dist2):
             reach = ~sky & (dot3(e, e) >= dist2[idx])                           # the added exit
             hit = ~sky & ~reach & (step == 0)                                   # :146
             visible[idx[sky | reach]] = True
+            end[idx[sky]], end[idx[reach]], end[idx[hit]] = END_AIR, END_REACHED, END_SOLID
             go = ~(sky | reach | hit)
             idx, pos, step = idx[go], pos[go], step[go]
-    return visible                                                              # (the loop limit: blocked)
+    return (visible, end) if ends else visible                                  # (the loop limit: blocked)
 
 
 def pair_terms(P, axis, even, light_pos, light_radius):

@@ -24,6 +24,7 @@ from tests import light_shadow_ref as ref
 from tests import point_light_ref as pl
 from tests import stamp_edits as se
 from tests.draw_stamps_ref import batch as model_batch, model as one_model
+from tests.pass_worlds import boxes_at, midpoints, models_at, occluders, scatter_lights  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -124,68 +125,7 @@ def _nontrivial(classes, before, what=""):
 
 
 # ---- the inputs ---------------------------------------------------------------------------------------------------------------------------
-def scatter_lights(before, u, W, H, n, seed, rmin=2.0, rmax=12.0):
-    """test_gpu_point_lights.scatter's recipe: n lights just off the frame's surfaces — a random surface pixel's P', moved 0.2 to 5
-    units along its face's normal (one in ten the other way: into the ground) and up to 1.5 units sideways; radii rmin..rmax, colours
-    up to 40 with some zeros."""
-    rng = np.random.default_rng(seed)
-    surface, P, axis, even = pl.surface_points(before, u, W, H)
-    pts, ax, ev = P[surface].astype(np.float64), axis[surface], even[surface]
-    assert len(pts) > 100
-    j = rng.integers(0, len(pts), n)
-    pos = pts[j] + rng.uniform(-1.5, 1.5, (n, 3))
-    off = rng.uniform(0.2, 5.0, n) * np.where(ev[j], 1.0, -1.0) * np.where(rng.random(n) < 0.1, -1.0, 1.0)
-    pos[np.arange(n), ax[j]] += off
-    color = rng.random((n, 3)) * 40.0
-    color[rng.random(n) < 0.05] = 0.0
-    return render.make_point_lights(pos, rng.uniform(rmin, rmax, n), color)
-
-
-def midpoints(before, u, W, H, lights, n, rng):
-    """n points halfway between a light and a surface point that passes its pair test (float64[n, 3])."""
-    surface, P, axis, even = pl.surface_points(before, u, W, H)
-    Pf = P[surface]
-    passes = pl.pair_terms(Pf, axis[surface], even[surface], lights["position"].astype(f32), lights["radius"].astype(f32))[0] & pl.valid(lights)[:, None]
-    li, pi = np.nonzero(passes)
-    assert li.size > 0, "no light reaches a surface"
-    j = rng.integers(0, li.size, n)
-    return 0.5 * (lights["position"][li[j]].astype(np.float64) + Pf[pi[j]].astype(np.float64))
-
-
-def boxes_at(centres, rng, half=(0.05, 0.5)):
-    h = rng.uniform(half[0], half[1], (len(centres), 3))
-    b = np.zeros(len(centres), dtype=render.DRAW_BOX_DTYPE)
-    b["lo"], b["hi"] = (centres - h).astype(f32), (centres + h).astype(f32)
-    b["material"], b["emission"] = 0x1FFFFF, 0xFF000000
-    return b
-
-
-def models_at(centres, sid, seed, extent=STAMP_EXTENT, scales=(0.25, 0.125, 0.5)):
-    out = []
-    for i, c in enumerate(centres):
-        orient, scale = (7 * i + seed) % 48, scales[i % len(scales)]
-        e = np.array(se.placed_extent(tuple(extent), orient), dtype=np.float64)
-        out.append(one_model(sid, (c - 0.5 * e * scale).astype(f32), scale, orient))
-    return model_batch(out)
-
-
-def occluders(before, u, W, H, lights, nboxes, nmodels, seed, sid):
-    """Occluders put on purpose between a light and a surface it reaches (two in three; a single one always), and random ones
-    scattered over the surfaces as for the sun's shadows."""
-    rng = np.random.default_rng(1000 + seed)
-    boxes = models = None
-    if nboxes:
-        k = max(1, (2 * nboxes) // 3)
-        boxes = boxes_at(midpoints(before, u, W, H, lights, k, rng), rng)
-        if nboxes > k:
-            boxes = np.concatenate([boxes, shadow_ref.scatter_boxes(before, u, W, H, nboxes - k, seed, lift=(0.2, 3.0))])
-    if nmodels:
-        k = max(1, (2 * nmodels) // 3)
-        models = models_at(midpoints(before, u, W, H, lights, k, rng), sid, seed)
-        if nmodels > k:
-            models = np.concatenate([models, shadow_ref.scatter_models(before, u, W, H, nmodels - k, seed, sid, STAMP_EXTENT, scales=(0.5, 0.125),
-                                                                        lift=(0.2, 3.0))])
-    return boxes, models
+# (scatter_lights, midpoints, boxes_at, models_at and occluders live in tests/pass_worlds.py, which tests without a GPU import too)
 
 
 def case_inputs(before, u, W, H, case, seed, sid):

@@ -40,14 +40,18 @@ def _oracle_check(mats, mine, o, d, hits, lr, idx):
             assert t == (-1, -1, -1) and g["material"] == 0
 
 
-def _adversarial_rays(rng, mats, mine, lr, n):
-    o, d = seeded_rays(rng, n)
+def _adversarial_rays(rng, mats, mine, lr, n, R=256):
+    o, d = seeded_rays(rng, n, R)
     o += np.float32(lr)
     # origins inside solid voxels, rays grazing voxel edges and corners, axis-aligned rays on integer planes
-    solid = np.argwhere(mine.reshape(256, 256, 256) == 0)
-    pick = solid[rng.integers(0, len(solid), 32)][:, ::-1] - 128 + np.float32(lr)
+    if R == 256:
+        solid = np.argwhere(mine.reshape(256, 256, 256) == 0)
+    else:   # (the larger regions: solid voxels among seeded texels, not a list of every one)
+        t = rng.integers(0, R, (1 << 16, 3))
+        solid = t[mine.reshape(R, R, R)[t[:, 0], t[:, 1], t[:, 2]] == 0]
+    pick = solid[rng.integers(0, len(solid), 32)][:, ::-1] - R // 2 + np.float32(lr)
     o[-32:] = pick + np.float32(0.25)
-    g = rng.integers(-100, 100, (32, 3)).astype(np.float32) + np.float32(lr)
+    g = (rng.integers(-100, 100, (32, 3)) * (R // 256)).astype(np.float32) + np.float32(lr)
     o[-64:-32] = g
     d[-64:-48] = np.float32([1, 1, 0])
     d[-48:-32] = np.float32([1, -1, 1])
