@@ -4,16 +4,17 @@
 //
 //   k_draw_stamps : a tile pass (rt_tile_pass.hpp), k_draw_boxes' shape.  Per batch of 64 models lane l loads record base + l (four
 //                   16-byte loads) and runs box_may_touch_tile on its bounding box; for each candidate every lane runs the exact slab
-//                   test and then the voxel walk of its own ray with scalar model operands.  The walk reads one state byte per cell
-//                   from global memory (a model is a few KiB: the caches serve it) and keeps the cell's index in the stamp's arrays
-//                   by adding a stride per step.  A lane keeps (t, model, axis, voxel) of its best hit; winners compute the hit
-//                   point, compare depths, fetch the voxel's material word and the face light and store seven planes.  No LDS, no
-//                   atomics.
+//                   test and then the voxel walk of its own ray with scalar model operands (walk_model, rt_model_walk.hpp).  The walk
+//                   reads one state byte per cell from global memory (a model is a few KiB: the caches serve it) and keeps the cell's
+//                   index in the stamp's arrays by adding a stride per step.  A lane keeps (t, model, axis, voxel) of its best hit;
+//                   winners compute the hit point, compare depths, fetch the voxel's material word and the face light and store
+//                   seven planes.  No LDS, no atomics.
 //
 // A model whose bounding box is entered no sooner than the lane's best hit so far is not walked: the walk only ever raises t above
 // t_in, and on equal t the lower index wins.
 #include <hip/hip_runtime.h>
 
+#include "rt_model_walk.hpp"
 #include "rt_tile_pass.hpp"
 
 namespace rtd {
@@ -63,50 +64,11 @@ __global__ __launch_bounds__(kTileWg) void k_draw_stamps(Planes pl, DrawStampsAr
             const bool enters = ray_box_slab(lo, hi, o, d, inv, &t_in, &t_out, &axis);
             if (!(tl.inside && enters && t_in < best_t)) continue;   // (a lane past the frame's edge draws nothing)
 
-            // ---- the walk of this lane's ray through the model's cells (its twin, without t and the axis: rt_shadows.hip) ----
-            const ModelRec m = model_rec(w0, w1, w2, j);
-            const float scale = m.scale;
-            const int ex = m.ext[0], ey = m.ext[1], ez = m.ext[2], sx = m.stride[0], sy = m.stride[1], sz = m.stride[2];
-            // the first cell: the entry axis' first or last layer, elsewhere where the entry point lies
-            int c[3];
-            for (int k = 0; k < 3; k++) {
-                const float p = d[k] == 0.0f ? o[k] : rtm_fma(d[k], t_in, o[k]);
-                const float q = rtm_floor((p - lo[k]) / scale), qmax = (float)(m.ext[k] - 1);   // clamped as a float: the same cell
-                const int ck = (int)(!(q > 0.0f) ? 0.0f : (q > qmax ? qmax : q));
-                c[k] = (uint32_t)k == axis ? (d[k] > 0.0f ? 0 : m.ext[k] - 1) : ck;
+            // the walk of this lane's ray through the model's cells: entered from outside, t and the axis kept
+            WalkHit h;
+            if (walk_model<false, true>(model_rec(w0, w1, w2, j), lo, o, d, inv, t_in, axis, &h) && h.t < best_t) {
+                best_t = h.t; best = first + (uint32_t)j; best_axis = h.axis; best_voxel = (uint32_t)h.voxel;
             }
-            int cx = c[0], cy = c[1], cz = c[2];
-            // per axis: the step in cells and in voxels of the stamp's arrays, and which of the cell's two planes the ray leaves by
-            const int dcx = d[0] > 0.0f ? 1 : -1, dcy = d[1] > 0.0f ? 1 : -1, dcz = d[2] > 0.0f ? 1 : -1;
-            const int ox = d[0] > 0.0f ? 1 : 0, oy = d[1] > 0.0f ? 1 : 0, oz = d[2] > 0.0f ? 1 : 0;
-            const bool gx = d[0] != 0.0f, gy = d[1] != 0.0f, gz = d[2] != 0.0f;
-            int voxel = m.base + sx * cx + sy * cy + sz * cz;
-            float t = t_in;
-            bool found = false;
-            for (int n = ex + ey + ez; n > 0; n--) {   // (every step moves one coordinate the ray's way: at most E'x + E'y + E'z)
-                if (m.state[voxel] == RT_STAMP_SOLID) { found = true; break; }
-                bool have = false;
-                float tmin = 0.0f;
-                uint32_t ax = 0u;
-                if (gx) { tmin = (rtm_fma((float)(cx + ox), scale, lo[0]) - o[0]) * inv[0]; have = true; }
-                if (gy) {
-                    const float tk = (rtm_fma((float)(cy + oy), scale, lo[1]) - o[1]) * inv[1];
-                    if (!have || tk < tmin) { tmin = tk; ax = 1u; have = true; }
-                }
-                if (gz) {
-                    const float tk = (rtm_fma((float)(cz + oz), scale, lo[2]) - o[2]) * inv[2];
-                    if (!have || tk < tmin) { tmin = tk; ax = 2u; have = true; }
-                }
-                if (!have) break;
-                bool out;
-                if (ax == 0u) { cx += dcx; voxel += dcx * sx; out = cx < 0 || cx >= ex; }
-                else if (ax == 1u) { cy += dcy; voxel += dcy * sy; out = cy < 0 || cy >= ey; }
-                else { cz += dcz; voxel += dcz * sz; out = cz < 0 || cz >= ez; }
-                if (out) break;
-                t = t < tmin ? tmin : t;
-                axis = ax;
-            }
-            if (found && t < best_t) { best_t = t; best = first + (uint32_t)j; best_axis = axis; best_voxel = (uint32_t)voxel; }
         }
     }
 

@@ -17,9 +17,10 @@
 // (DESIGN.md "Entity queries" carries the argument for its margins).  Coherent rays — a screen region's pixels, a volley — are culled
 // well; incoherent rays in one wave are not, and the cost then tends to rays x entities slab tests.
 //
-// The walk is rt_draw_stamps.hip's with the lane's own origin; it also keeps the cell it stands on.
+// The walk is k_draw_stamps' (walk_model, rt_model_walk.hpp) with the lane's own origin; the record also reports the cell it ends on.
 #include <hip/hip_runtime.h>
 
+#include "rt_model_walk.hpp"
 #include "rt_query_ray.hpp"
 #include "rt_tile_pass.hpp"
 
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(kEntityQueryWg) void k_entity_query(Scene sc, Frame
             if (live && hit && t_in < best_t) { best_t = t_in; best = base + (uint32_t)j; best_axis = axis; }
         }
     }
-    // ---- the models (rt_draw_stamps.hip's loop and walk, the lane's own o) ----
+    // ---- the models (rt_draw_stamps.hip's loop, the lane's own o) ----
     for (uint32_t first = 0; first < a.nmodels; first += 64u) {
         const uint32_t rec = first + lane;
         uint4 w0 = make_uint4(0u, 0u, 0u, 0u), w1 = w0, w2 = w0, w3 = w0;
@@ -162,50 +163,10 @@ __global__ __launch_bounds__(kEntityQueryWg) void k_entity_query(Scene sc, Frame
             // on equal t a box, or a model of a lower index, keeps the hit: the walk only ever raises t above t_in
             if (!(live && enters && t_in < best_t)) continue;
 
-            const ModelRec m = model_rec(w0, w1, w2, j);
-            const float scale = m.scale;
-            const int ex = m.ext[0], ey = m.ext[1], ez = m.ext[2], sx = m.stride[0], sy = m.stride[1], sz = m.stride[2];
-            // the first cell: the entry axis' first or last layer, elsewhere where the entry point lies
-            int c[3];
-            for (int k = 0; k < 3; k++) {
-                const float p = d[k] == 0.0f ? o[k] : rtm_fma(d[k], t_in, o[k]);
-                const float q = rtm_floor((p - lo[k]) / scale), qmax = (float)(m.ext[k] - 1);   // clamped as a float: the same cell
-                const int ck = (int)(!(q > 0.0f) ? 0.0f : (q > qmax ? qmax : q));
-                c[k] = (uint32_t)k == axis ? (d[k] > 0.0f ? 0 : m.ext[k] - 1) : ck;
-            }
-            int cx = c[0], cy = c[1], cz = c[2];
-            const int dcx = d[0] > 0.0f ? 1 : -1, dcy = d[1] > 0.0f ? 1 : -1, dcz = d[2] > 0.0f ? 1 : -1;
-            const int ox = d[0] > 0.0f ? 1 : 0, oy = d[1] > 0.0f ? 1 : 0, oz = d[2] > 0.0f ? 1 : 0;
-            const bool gx = d[0] != 0.0f, gy = d[1] != 0.0f, gz = d[2] != 0.0f;
-            int voxel = m.base + sx * cx + sy * cy + sz * cz;
-            float t = t_in;
-            bool found = false;
-            for (int n = ex + ey + ez; n > 0; n--) {   // (every step moves one coordinate the ray's way: at most E'x + E'y + E'z)
-                if (m.state[voxel] == RT_STAMP_SOLID) { found = true; break; }
-                bool have = false;
-                float tmin = 0.0f;
-                uint32_t ax = 0u;
-                if (gx) { tmin = (rtm_fma((float)(cx + ox), scale, lo[0]) - o[0]) * inv[0]; have = true; }
-                if (gy) {
-                    const float tk = (rtm_fma((float)(cy + oy), scale, lo[1]) - o[1]) * inv[1];
-                    if (!have || tk < tmin) { tmin = tk; ax = 1u; have = true; }
-                }
-                if (gz) {
-                    const float tk = (rtm_fma((float)(cz + oz), scale, lo[2]) - o[2]) * inv[2];
-                    if (!have || tk < tmin) { tmin = tk; ax = 2u; have = true; }
-                }
-                if (!have) break;
-                bool out;
-                if (ax == 0u) { cx += dcx; voxel += dcx * sx; out = cx < 0 || cx >= ex; }
-                else if (ax == 1u) { cy += dcy; voxel += dcy * sy; out = cy < 0 || cy >= ey; }
-                else { cz += dcz; voxel += dcz * sz; out = cz < 0 || cz >= ez; }
-                if (out) break;
-                t = t < tmin ? tmin : t;
-                axis = ax;
-            }
-            if (found && t < best_t) {
-                best_t = t; best = a.nboxes + first + (uint32_t)j; best_axis = axis; best_voxel = (uint32_t)voxel;
-                best_cell = (uint32_t)cx | ((uint32_t)cy << 8) | ((uint32_t)cz << 16);   // (0 <= c_k < 256)
+            WalkHit h;
+            if (walk_model<false, true>(model_rec(w0, w1, w2, j), lo, o, d, inv, t_in, axis, &h) && h.t < best_t) {
+                best_t = h.t; best = a.nboxes + first + (uint32_t)j; best_axis = h.axis; best_voxel = (uint32_t)h.voxel;
+                best_cell = (uint32_t)h.cx | ((uint32_t)h.cy << 8) | ((uint32_t)h.cz << 16);   // (0 <= c_k < 256)
             }
         }
     }

@@ -11,6 +11,9 @@
 //                  bytes straight from the swizzled array, as k_query) and test between two steps whether the ray has reached the
 //                  light.  No LDS, no atomics.
 //
+// What the two kernels do with one (pixel, light) pair — the exact test, the world's shadow ray, the weight, the add to the two
+// lighting planes — exists once, as file-local helpers; the kernels stay two, k_add_lights at its own register count.
+//
 // All arithmetic that decides a pixel is fp32 with one rounding per operation (-ffp-contract=off).  The cull drops a light only where
 // the exact test skips it at every pixel of the tile; it needs no margin (DESIGN.md "Point lights"): it repeats the exact test's own
 // operations on operands that are no larger in magnitude, and every one of those operations is monotone.
@@ -51,16 +54,72 @@ __device__ __forceinline__ bool light_may_reach_tile(const float pos[3], float r
     return !(gap2 >= r2);
 }
 
+// ---- one (pixel, light) pair, as both kernels below treat it -------------------------------------------------------------------------
+// The exact test of a pixel (its P', whether it shows a surface, its normal's axis and sign) against a light: v from P' to the light,
+// its squared length, the squared radius and c, v's component along the normal.
+struct LightPair {
+    float v[3], dist2, r2, c;
+    bool passes;
+};
+__device__ __forceinline__ LightPair light_pair(const float pos[3], float radius, const float P[3], bool surface, uint32_t axis, bool even) {
+    LightPair p;
+    for (int k = 0; k < 3; k++) p.v[k] = pos[k] - P[k];
+    p.dist2 = rtm_dot3({p.v[0], p.v[1], p.v[2]}, {p.v[0], p.v[1], p.v[2]});
+    p.r2 = radius * radius;
+    const float va = axis == 0u ? p.v[0] : (axis == 1u ? p.v[1] : p.v[2]);
+    p.c = even ? va : -va;
+    p.passes = surface && p.dist2 > 0.0f && p.dist2 < p.r2 && p.c > 0.0f;
+    return p;
+}
+
+// The world's shadow ray: trace_ray from P' (first texel vox0, ok0: wrap_texel's verdict) along d, the normalised v, ended as
+// visible once it is as far from P' as the light.  Does the light's contribution arrive?
+template <int LOGR, bool LRZ>
+__device__ __forceinline__ bool light_reaches(const Scene& sc, const Frame& f, const float P[3], vec3 d, float dist2, bool ok0, uint32_t vox0) {
+    constexpr float half = (float)((1 << LOGR) / 2);
+    RaySlot2 r;
+    r.lx = 1.0f / rtm_abs(d.x); r.ly = 1.0f / rtm_abs(d.y); r.lz = 1.0f / rtm_abs(d.z);
+    unsigned long long unused = 0;
+    dda_arm<LOGR, LRZ, false, true, false>(r, d.x, d.y, d.z, P[0], P[1], P[2], ok0, vox0, 0u, f, half, nullptr, sc, unused, nullptr);
+    bool reached = false;
+    while (r.tracing) {
+        const float ex = r.px - P[0], ey = r.py - P[1], ez = r.pz - P[2];
+        if (rtm_dot3({ex, ey, ez}, {ex, ey, ez}) >= dist2) { reached = true; break; }
+        dda_advance<LOGR, LRZ, false, false, false>(r, (uint32_t)sc.mine[r.vox], f, half, unused, nullptr);
+    }
+    return reached || r2_kind(r) == PX_AIR;
+}
+
+// The weight of a pair whose light arrives (len = sqrt(dist2)): the cosine at the surface times the squared falloff to the radius.
+__device__ __forceinline__ float light_weight(const LightPair& p, float len) {
+    const float cosine = p.c / len;
+    const float x = 1.0f - p.dist2 / p.r2;
+    return (cosine * (x * x)) / (1.0f + p.dist2);
+}
+
+// A pixel's summed light goes into its two lighting planes.
+__device__ __forceinline__ void add_to_lighting(const Planes& pl, size_t pix, const float add[3]) {
+    const float s[3] = {add[0] / 16.0f, add[1] / 16.0f, add[2] / 16.0f};
+    float4* lf = reinterpret_cast<float4*>(pl.lighting_f32) + pix;
+    float4 lv = *lf;
+    lv.x += s[0]; lv.y += s[1]; lv.z += s[2];
+    *lf = lv;
+    ushort4* lq = reinterpret_cast<ushort4*>(pl.lighting_rgba16) + pix;
+    ushort4 q = *lq;
+    q.x = (uint16_t)rtm_unorm((float)q.x / 65535.0f + s[0], 65535.0f);
+    q.y = (uint16_t)rtm_unorm((float)q.y / 65535.0f + s[1], 65535.0f);
+    q.z = (uint16_t)rtm_unorm((float)q.z / 65535.0f + s[2], 65535.0f);
+    *lq = q;
+}
+
 template <int LOGR, bool LRZ>
 __global__ __launch_bounds__(kTileWg) void k_add_lights(Scene sc, Frame f, Planes pl, LightsArgs a) {
     constexpr int R = 1 << LOGR, LB = LOGR - 2;
-    constexpr float half = (float)(R / 2);
     const TileLane tl(f.width, f.height);
     if (!tl.live) return;
-    const size_t pix = tl.pix;
 
-    const uint32_t normal = tl.inside ? (uint32_t)pl.normal_r8[pix] : 255u;
-    const float depth = tl.inside ? pl.depth_f32[pix] : 65535.0f;
+    const uint32_t normal = tl.inside ? (uint32_t)pl.normal_r8[tl.pix] : 255u;
+    const float depth = tl.inside ? pl.depth_f32[tl.pix] : 65535.0f;
     const bool surface = normal < 6u && depth < 65535.0f;   // (false for a NaN depth)
     if (__ballot(surface) == 0ull) return;
 
@@ -96,47 +155,16 @@ __global__ __launch_bounds__(kTileWg) void k_add_lights(Scene sc, Frame f, Plane
             float pos[3], col[3];
             rec_xyz(w0, j, pos); rec_xyz(w1, j, col);
             const float radius = __uint_as_float(bcast(w0.w, j));
-            // the exact test of this lane's pixel
-            const float v[3] = {pos[0] - P[0], pos[1] - P[1], pos[2] - P[2]};
-            const float dist2 = rtm_dot3({v[0], v[1], v[2]}, {v[0], v[1], v[2]});
-            const float r2 = radius * radius;
-            const float va = axis == 0u ? v[0] : (axis == 1u ? v[1] : v[2]);
-            const float c = even ? va : -va;
-            if (!(surface && dist2 > 0.0f && dist2 < r2 && c > 0.0f)) continue;
-            // the shadow ray: trace_ray from P' towards the light, ended as visible once it is as far from P' as the light
-            const vec3 d = vnormalize(v3(v[0], v[1], v[2]));
-            RaySlot2 r;
-            r.lx = 1.0f / rtm_abs(d.x); r.ly = 1.0f / rtm_abs(d.y); r.lz = 1.0f / rtm_abs(d.z);
-            unsigned long long unused = 0;
-            dda_arm<LOGR, LRZ, false, true, false>(r, d.x, d.y, d.z, P[0], P[1], P[2], ok0, vox0, 0u, f, half, nullptr, sc, unused, nullptr);
-            bool reached = false;
-            while (r.tracing) {
-                const float ex = r.px - P[0], ey = r.py - P[1], ez = r.pz - P[2];
-                if (rtm_dot3({ex, ey, ez}, {ex, ey, ez}) >= dist2) { reached = true; break; }
-                dda_advance<LOGR, LRZ, false, false, false>(r, (uint32_t)sc.mine[r.vox], f, half, unused, nullptr);
-            }
-            if (!(reached || r2_kind(r) == PX_AIR)) continue;
-            const float len = rtm_sqrt(dist2);
-            const float cosine = c / len;
-            const float x = 1.0f - dist2 / r2;
-            const float w = (cosine * (x * x)) / (1.0f + dist2);
+            const LightPair p = light_pair(pos, radius, P, surface, axis, even);
+            if (!p.passes) continue;
+            if (!light_reaches<LOGR, LRZ>(sc, f, P, vnormalize(v3(p.v[0], p.v[1], p.v[2])), p.dist2, ok0, vox0)) continue;
+            const float w = light_weight(p, rtm_sqrt(p.dist2));
             for (int k = 0; k < 3; k++) add[k] = add[k] + col[k] * w;
             lit = true;
         }
     }
 
-    if (!lit) return;
-    const float s[3] = {add[0] / 16.0f, add[1] / 16.0f, add[2] / 16.0f};
-    float4* lf = reinterpret_cast<float4*>(pl.lighting_f32) + pix;
-    float4 lv = *lf;
-    lv.x += s[0]; lv.y += s[1]; lv.z += s[2];
-    *lf = lv;
-    ushort4* lq = reinterpret_cast<ushort4*>(pl.lighting_rgba16) + pix;
-    ushort4 q = *lq;
-    q.x = (uint16_t)rtm_unorm((float)q.x / 65535.0f + s[0], 65535.0f);
-    q.y = (uint16_t)rtm_unorm((float)q.y / 65535.0f + s[1], 65535.0f);
-    q.z = (uint16_t)rtm_unorm((float)q.z / 65535.0f + s[2], 65535.0f);
-    *lq = q;
+    if (lit) add_to_lighting(pl, tl.pix, add);
 }
 
 // ---- rt_add_lights_occluded: the same pass with the drawn entities between the surface and the light --------------------------------
@@ -205,7 +233,9 @@ __device__ __forceinline__ bool boxes_leave_open(uint4 w0, uint4 w1, unsigned lo
 }
 
 // The same for the models whose records (w0..w3) the lanes of `cand` hold: the bounding box by the box rule, then the walk of the
-// model's cells (k_shadow_entities' loop with a direction per lane and the stop at the light).
+// model's cells: walk_model<true, false> (rt_model_walk.hpp) with the stop at the light, kept as a loop of this file because the
+// kernel built on the shared one measured slower than it was, twice (DESIGN.md "One model walk").  The arithmetic is that header's,
+// and a change to it there is made here too.
 __device__ __forceinline__ bool models_leave_open(uint4 w0, uint4 w1, uint4 w2, uint4 w3, unsigned long long cand, const Segment& sg, bool open) {
     while (cand && __ballot(open) != 0ull) {
         const int j = __builtin_ctzll(cand);
@@ -264,15 +294,13 @@ __device__ __forceinline__ bool models_leave_open(uint4 w0, uint4 w1, uint4 w2, 
 template <int LOGR, bool LRZ>
 __global__ __launch_bounds__(kTileWg) void k_add_lights_occluded(Scene sc, Frame f, Planes pl, LightShadowArgs a) {
     constexpr int R = 1 << LOGR, LB = LOGR - 2;
-    constexpr float half = (float)(R / 2);
     __shared__ uint32_t s_list[kTileWg / 64u][2][kListCap];
     const TileLane tl(f.width, f.height);
     if (!tl.live) return;
     const uint32_t lane = tl.lane;
-    const size_t pix = tl.pix;
 
-    const uint32_t normal = tl.inside ? (uint32_t)pl.normal_r8[pix] : 255u;
-    const float depth = tl.inside ? pl.depth_f32[pix] : 65535.0f;
+    const uint32_t normal = tl.inside ? (uint32_t)pl.normal_r8[tl.pix] : 255u;
+    const float depth = tl.inside ? pl.depth_f32[tl.pix] : 65535.0f;
     const bool surface = normal < 6u && depth < 65535.0f;   // (false for a NaN depth)
     if (__ballot(surface) == 0ull) return;
 
@@ -383,16 +411,11 @@ __global__ __launch_bounds__(kTileWg) void k_add_lights_occluded(Scene sc, Frame
             float pos[3], col[3];
             rec_xyz(w0, j, pos); rec_xyz(w1, j, col);
             const float radius = __uint_as_float(bcast(w0.w, j));
-            // the exact test of this lane's pixel
-            const float v[3] = {pos[0] - P[0], pos[1] - P[1], pos[2] - P[2]};
-            const float dist2 = rtm_dot3({v[0], v[1], v[2]}, {v[0], v[1], v[2]});
-            const float r2 = radius * radius;
-            const float va = axis == 0u ? v[0] : (axis == 1u ? v[1] : v[2]);
-            const float c = even ? va : -va;
-            bool open = surface && dist2 > 0.0f && dist2 < r2 && c > 0.0f;
+            const LightPair p = light_pair(pos, radius, P, surface, axis, even);
+            bool open = p.passes;
             if (__ballot(open) == 0ull) continue;
-            const vec3 d = vnormalize(v3(v[0], v[1], v[2]));
-            const float len = rtm_sqrt(dist2);
+            const vec3 d = vnormalize(v3(p.v[0], p.v[1], p.v[2]));
+            const float len = rtm_sqrt(p.dist2);
 
             // ---- 4. the entities between P' and the light (every lane walks through here: the records are broadcast) ----
             Segment sg;
@@ -429,40 +452,15 @@ __global__ __launch_bounds__(kTileWg) void k_add_lights_occluded(Scene sc, Frame
                     open = models_leave_open(x0, x1, x2, x3, __ballot(take), sg, open);
                 }
             }
-            if (open) {   // the world's shadow ray, as k_add_lights traces it
-                RaySlot2 r;
-                r.lx = 1.0f / rtm_abs(d.x); r.ly = 1.0f / rtm_abs(d.y); r.lz = 1.0f / rtm_abs(d.z);
-                unsigned long long unused = 0;
-                dda_arm<LOGR, LRZ, false, true, false>(r, d.x, d.y, d.z, P[0], P[1], P[2], ok0, vox0, 0u, f, half, nullptr, sc, unused, nullptr);
-                bool reached = false;
-                while (r.tracing) {
-                    const float ex = r.px - P[0], ey = r.py - P[1], ez = r.pz - P[2];
-                    if (rtm_dot3({ex, ey, ez}, {ex, ey, ez}) >= dist2) { reached = true; break; }
-                    dda_advance<LOGR, LRZ, false, false, false>(r, (uint32_t)sc.mine[r.vox], f, half, unused, nullptr);
-                }
-                if (reached || r2_kind(r) == PX_AIR) {
-                    const float cosine = c / len;
-                    const float x = 1.0f - dist2 / r2;
-                    const float w = (cosine * (x * x)) / (1.0f + dist2);
-                    for (int k = 0; k < 3; k++) add[k] = add[k] + col[k] * w;
-                    lit = true;
-                }
+            if (open && light_reaches<LOGR, LRZ>(sc, f, P, d, p.dist2, ok0, vox0)) {   // the world's shadow ray
+                const float w = light_weight(p, len);
+                for (int k = 0; k < 3; k++) add[k] = add[k] + col[k] * w;
+                lit = true;
             }
         }
     }
 
-    if (!lit) return;
-    const float s[3] = {add[0] / 16.0f, add[1] / 16.0f, add[2] / 16.0f};
-    float4* lf = reinterpret_cast<float4*>(pl.lighting_f32) + pix;
-    float4 lv = *lf;
-    lv.x += s[0]; lv.y += s[1]; lv.z += s[2];
-    *lf = lv;
-    ushort4* lq = reinterpret_cast<ushort4*>(pl.lighting_rgba16) + pix;
-    ushort4 q = *lq;
-    q.x = (uint16_t)rtm_unorm((float)q.x / 65535.0f + s[0], 65535.0f);
-    q.y = (uint16_t)rtm_unorm((float)q.y / 65535.0f + s[1], 65535.0f);
-    q.z = (uint16_t)rtm_unorm((float)q.z / 65535.0f + s[2], 65535.0f);
-    *lq = q;
+    if (lit) add_to_lighting(pl, tl.pix, add);
 }
 
 }  // namespace

@@ -17,13 +17,12 @@
 // same direction, so the cull repeats the exact test's own operations — a difference, a product with the one reciprocal — on
 // operands that bound every pixel's, and each of those operations is monotone.
 //
-// The walk of a model's cells shares with k_draw_stamps' what both start from — the record's decode (model_rec) and the slab test
-// (slab_core) — and stays a loop of its own on purpose: k_draw_stamps' carries t and the entry axis through every step and this one
-// does not, and it has a second way to its first cell.  A shared body would be that loop with the bookkeeping compiled in or out,
-// and each kernel would pay for the other's state.
+// The walk of a model's cells is the shared walk_model (rt_model_walk.hpp) with the switch for a start inside the box and without
+// t and the axis; the sun's direction and reciprocals stay wave-uniform operands of it.
 #include <hip/hip_runtime.h>
 
 #include "rt_dda.hpp"
+#include "rt_model_walk.hpp"
 #include "rt_tile_pass.hpp"
 
 namespace rtd {
@@ -145,49 +144,8 @@ __global__ __launch_bounds__(kTileWg) void k_shadow_entities(Scene sc, Frame f, 
             uint32_t axis;
             const bool crosses = slab_core(lo, hi, P, sd.nonzero, sd.inv, &t_in, &t_out, &axis);
             if (need && crosses && t_out > 0.0f && t_in < t_out) {
-                // ---- the walk of this lane's sun ray through the model's cells (its twin, with t and the axis: rt_draw_stamps.hip) ----
-                const ModelRec m = model_rec(w0, w1, w2, j);
-                const float scale = m.scale;
-                const uint8_t* state = m.state;
-                const int ex = m.ext[0], ey = m.ext[1], ez = m.ext[2], stx = m.stride[0], sty = m.stride[1], stz = m.stride[2];
-                // the first cell: entered from outside (t_in > 0), the entry axis' first or last layer and elsewhere where the entry
-                // point lies; started inside, where P' lies on every axis
-                const bool outside = t_in > 0.0f;
-                int c[3];
-                for (int k = 0; k < 3; k++) {
-                    const float p = (!outside || sd.s[k] == 0.0f) ? P[k] : rtm_fma(sd.s[k], t_in, P[k]);
-                    const float q = rtm_floor((p - lo[k]) / scale), qmax = (float)(m.ext[k] - 1);   // clamped as a float: the same cell
-                    const int ck = (int)(!(q > 0.0f) ? 0.0f : (q > qmax ? qmax : q));
-                    c[k] = (outside && (uint32_t)k == axis) ? (sd.s[k] > 0.0f ? 0 : m.ext[k] - 1) : ck;
-                }
-                int cx = c[0], cy = c[1], cz = c[2];
-                const int dcx = sd.s[0] > 0.0f ? 1 : -1, dcy = sd.s[1] > 0.0f ? 1 : -1, dcz = sd.s[2] > 0.0f ? 1 : -1;
-                const int ox = sd.s[0] > 0.0f ? 1 : 0, oy = sd.s[1] > 0.0f ? 1 : 0, oz = sd.s[2] > 0.0f ? 1 : 0;
-                const bool gx = sd.s[0] != 0.0f, gy = sd.s[1] != 0.0f, gz = sd.s[2] != 0.0f;
-                int voxel = m.base + stx * cx + sty * cy + stz * cz;
-                bool found = false;
-                for (int n = ex + ey + ez; n > 0; n--) {   // (every step moves one coordinate the ray's way: at most E'x + E'y + E'z)
-                    if (state[voxel] == RT_STAMP_SOLID) { found = true; break; }
-                    bool have = false;
-                    float tmin = 0.0f;
-                    uint32_t ax = 0u;
-                    if (gx) { tmin = (rtm_fma((float)(cx + ox), scale, lo[0]) - P[0]) * sd.inv[0]; have = true; }
-                    if (gy) {
-                        const float tk = (rtm_fma((float)(cy + oy), scale, lo[1]) - P[1]) * sd.inv[1];
-                        if (!have || tk < tmin) { tmin = tk; ax = 1u; have = true; }
-                    }
-                    if (gz) {
-                        const float tk = (rtm_fma((float)(cz + oz), scale, lo[2]) - P[2]) * sd.inv[2];
-                        if (!have || tk < tmin) { tmin = tk; ax = 2u; have = true; }
-                    }
-                    if (!have) break;
-                    bool out;
-                    if (ax == 0u) { cx += dcx; voxel += dcx * stx; out = cx < 0 || cx >= ex; }
-                    else if (ax == 1u) { cy += dcy; voxel += dcy * sty; out = cy < 0 || cy >= ey; }
-                    else { cz += dcz; voxel += dcz * stz; out = cz < 0 || cz >= ez; }
-                    if (out) break;
-                }
-                if (found) { shaded = true; need = false; }
+                // the walk of this lane's sun ray through the model's cells: P' may lie inside the box, and only the verdict is kept
+                if (walk_model<true, false>(model_rec(w0, w1, w2, j), lo, P, sd.s, sd.inv, t_in, axis, nullptr)) { shaded = true; need = false; }
             }
             if (__ballot(need) == 0ull) break;
         }
