@@ -764,6 +764,51 @@ int rt_draw_stamps(RtContext* ctx, const RtUniforms* u, const RtDrawStamp* model
  * device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued. */
 int rt_draw_stamps_async(RtContext* ctx, const RtUniforms* u, const RtDrawStamp* models, const RtProbeLight* face_lights_dev, uint32_t count);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Particles: many small cubes — debris and dust of an explosion,
+ * sparks, rain, snow, leaves, smoke puffs — composited by depth into the G-buffer of the frame drawn last exactly as the entity boxes
+ * are, up to 2^20 per call.  The cost follows the pixels the cubes cover, not count x tiles: each 8x8 tile reads only the particles
+ * binned to it.  The calls draw; they do not simulate (rt_sweep_boxes_async moves small boxes through the world from device buffers,
+ * and the asynchronous call takes device pointers, so particle state need never visit the host).  One particle, 32 bytes: */
+typedef struct RtParticle {       /* 32 bytes */
+    float    center[3]; float half;         /* world coordinates of the cube's centre; half its edge */
+    uint32_t material;  uint32_t emission;  /* as RtDrawBox's */
+    uint32_t light;     uint32_t reserved;  /* index into `lights`; reserved must be 0 */
+} RtParticle;
+/* The rules, by reduction to rt_draw_boxes (tests/draw_particles_ref.py is that reduction and nothing more):
+ *   Derived box: particle i is the box lo_k = center_k - half, hi_k = center_k + half, one fp32 rounding each, with the particle's
+ *     material and emission.
+ *   Light: all six faces take lights[light].light — one probe may serve a whole emitter or cluster; the host decides the sharing.
+ *   Planes: every pixel and every plane ends with exactly the bits rt_draw_boxes leaves for the derived boxes in index order with
+ *     face_lights[6 i + n] = lights[particle_i.light]: its ray, slab test, entry axis and winner (the smallest t_in, the lowest index
+ *     on equal t_in), its strict depth test against RT_BUF_DEPTH_F32 and its seven plane writes.  A camera inside a cube does not
+ *     see it.  Two runs of one call on equal planes give equal bits.
+ *   Valid record: every float finite, half > 0, the derived box a valid RtDrawBox (|lo_k|, |hi_k| <= 2^22 and lo_k < hi_k after the
+ *     rounding: a half that vanishes beside a large centre makes the record invalid), light < nlights, reserved == 0.  The device
+ *     skips an invalid record in both calls; rt_draw_particles also rejects the whole call (RT_ERR_INVALID_ARG) before anything is
+ *     enqueued.
+ *   Limits: count <= 2^20 and 1 <= nlights <= 2^20 (with count > 0), else RT_ERR_INVALID_ARG.  half has no limit of its own.
+ *   Errors, frame, ordering, side effects: rt_draw_boxes' — the frame drawn last, on the stream rt_denoise uses, behind the queries
+ *     already enqueued (rt_probe_light_async feeds `lights_dev` without a host sync); the frame slot's cached prepass is dropped; no
+ *     accumulation sum, history set or count, RtCounters, pending edit box or slab changes; NULL ctx, NULL u, a NULL array with
+ *     count > 0: RT_ERR_INVALID_ARG; tile_world != 1: RT_ERR_UNIMPLEMENTED; no frame drawn yet: RT_ERR_NOT_READY; count == 0: RT_OK,
+ *     nothing enqueued.  A rejected call changes nothing.
+ *   Compositing: particles, boxes and models drawn one after another composite by the depth test.
+ *   Device work per call: one memset and four launches — a thread per particle bins it to the 8x8 tiles it may touch (a conservative
+ *     cull: it drops a tile only if the exact test rejects the particle for every pixel of it), a thread per list claims the list's
+ *     room, a thread per particle fills the lists, a wave per tile draws from its lists.  A particle that may touch more than 16 tiles
+ *     is listed by the blocks of 8x8 tiles it may touch; one that may touch more than 16 blocks is near the camera or huge: it goes to
+ *     one wide list that every tile reads, at rt_draw_boxes' cost per record — the worst case.  Scratch: 8 + 8 lists + 72 count bytes
+ *     of the context's, lists = tiles + blocks, grown on demand and never shrunk (RtInfo.device_bytes; a call that grows it waits for
+ *     the launches that use the old one), freed by rt_destroy.  DESIGN.md "Particles".
+ * Host pointers; returns when the planes are written. */
+int rt_draw_particles(RtContext* ctx, const RtUniforms* u, const RtParticle* particles, uint32_t count, const RtProbeLight* lights,
+                      uint32_t nlights);
+/* Same with device pointers, enqueued: no host read-back and, once the scratch has its size, no host sync.  Both pointers must pass
+ * rt_trace_rays_async's test (16-byte aligned memory of the context's device, or managed memory), else RT_ERR_INVALID_ARG before
+ * anything is enqueued.  The library cannot read device records on the host: an invalid record is skipped on the device. */
+int rt_draw_particles_async(RtContext* ctx, const RtUniforms* u, const RtParticle* particles_dev, uint32_t count,
+                            const RtProbeLight* lights_dev, uint32_t nlights);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
  * after rt_draw_frame (and rt_draw_boxes) and before or after rt_denoise.  Each light reaches a pixel through one hard shadow ray
@@ -1261,7 +1306,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtEntityHit, RT_ENTITY_*, rt_trace_entities, rt_trace_entities_async, rt_pick_entities (entity
  *        queries: what a ray or a pixel hits among the drawn boxes and models, under the draws' own rules).
  *        Additive, same minor version: rt_add_lights_occluded, rt_add_lights_occluded_async (point-light shadows of entities:
- *        rt_add_lights with the drawn boxes and models blocking the segment from a pixel's surface point to the light). */
+ *        rt_add_lights with the drawn boxes and models blocking the segment from a pixel's surface point to the light).
+ *        Additive, same minor version: RtParticle, rt_draw_particles, rt_draw_particles_async (particles: up to 2^20 small cubes
+ *        composited into the G-buffer by depth, binned to the tiles they cover). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

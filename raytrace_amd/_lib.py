@@ -59,6 +59,8 @@ AMD_FUNCTIONS = {
     "rt_draw_boxes_async": (INT, [P, UNI, P, P, U32]),
     "rt_draw_stamps": (INT, [P, UNI, P, P, U32]),
     "rt_draw_stamps_async": (INT, [P, UNI, P, P, U32]),
+    "rt_draw_particles": (INT, [P, UNI, P, U32, P, U32]),
+    "rt_draw_particles_async": (INT, [P, UNI, P, U32, P, U32]),
     "rt_shadow_entities": (INT, [P, UNI, P, U32, P, U32, FLOAT]),
     "rt_shadow_entities_async": (INT, [P, UNI, P, U32, P, U32, FLOAT]),
     "rt_add_lights": (INT, [P, UNI, P, U32]),

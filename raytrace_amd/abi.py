@@ -5,6 +5,8 @@
 """
 import ctypes as C
 
+import numpy as np
+
 ROOT_BLOCK_SIZE = 256      # src/render/constants.rs:27
 CHUNK_SIZE = 64            # constants.rs:23
 NOISE_SIZE = 512           # constants.rs:16-17
@@ -217,6 +219,20 @@ class RtDrawBox(C.Structure):
 assert C.sizeof(RtDrawBox) == 32
 assert (RtDrawBox.lo.offset, RtDrawBox.material.offset, RtDrawBox.hi.offset, RtDrawBox.emission.offset) == (0, 12, 16, 28)
 MAX_DRAW_BOXES = 4096   # rt_draw_boxes: boxes per call
+
+
+class RtParticle(C.Structure):
+    """rt_draw_particles input (ABI 1.3, additive: particles): 32 bytes; `reserved` must be 0."""
+    _fields_ = [("center", C.c_float * 3), ("half", C.c_float), ("material", C.c_uint32), ("emission", C.c_uint32), ("light", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RtParticle) == 32
+assert (RtParticle.center.offset, RtParticle.half.offset, RtParticle.material.offset, RtParticle.emission.offset, RtParticle.light.offset,
+        RtParticle.reserved.offset) == (0, 12, 16, 20, 24, 28)
+MAX_PARTICLES = 1 << 20         # rt_draw_particles: particles per call
+MAX_PARTICLE_LIGHTS = 1 << 20   # ... and light records per call
+PARTICLE_DTYPE = np.dtype(RtParticle)   # the numpy view of the record (render.make_particles builds arrays of it)
 
 
 class RtDrawStamp(C.Structure):

@@ -1,5 +1,6 @@
 // api_passes.hip — the passes over the frame drawn last, each one launch on the stream that frame ended on: entity boxes
-// (rt_draw_boxes[_async]) and voxel-model entities (rt_draw_stamps[_async]) between the frame and its post passes, entity shadows
+// (rt_draw_boxes[_async]), voxel-model entities (rt_draw_stamps[_async]) and particles (rt_draw_particles[_async]: a chain of
+// launches over the context's binning scratch) between the frame and its post passes, entity shadows
 // (rt_shadow_entities[_async]) behind the entity draws, point lights (rt_add_lights[_async], and rt_add_lights_occluded[_async] with the
 // entities as occluders) behind those.  What the passes share is
 // here once: the prologue (pass_begin), the verdict on a batch of models (models_check), the models' way to the device
@@ -10,6 +11,7 @@
 // later one — whichever lane's stream it finds as the context's by then — first joins every lane (world_change_begin).
 #include "light_shadows_check.hpp"
 #include "lights_check.hpp"
+#include "particles_check.hpp"
 #include "rt_context.hpp"
 #include "shadows_check.hpp"
 
@@ -116,6 +118,35 @@ int draw_boxes_launch(RtContext* c, const RtUniforms* u, const void* boxes_dev, 
     set_camera(a, u, c->cfg);
     LaunchTimer t(c, 1);
     RT_HIP(c, rtd::launch_draw_boxes(planes_of(c), a, c->stream));
+    return RT_OK;
+}
+
+// ---- particles ------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(RtParticle) == 32, "the kernels read two 16-byte words per particle");
+static_assert(kMaxDrawParticles == rtd::kMaxParticles, "the host's limit is the kernels'");
+
+int draw_particles_begin(RtContext* c, const char* fn, const RtUniforms* u, const void* particles, uint32_t count, const void* lights, uint32_t nlights,
+                         bool* work) {
+    return pass_begin(c, fn, particle_args_error(u, particles, count, lights, nlights), false, count, work);
+}
+
+int draw_particles_launch(RtContext* c, const RtUniforms* u, const void* particles_dev, uint32_t count, const void* lights_dev, uint32_t nlights) {
+    const int rc = particle_scratch_reserve(c, rtd::particle_scratch_words(count, c->cfg.width, c->cfg.height));
+    if (rc != RT_OK) return rc;
+    planes_written(c, true);
+    RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
+    RT_HIP(c, c->ev_particles.wait_elsewhere(c->stream));   // the scratch is the previous call's until its draw has run
+    rtd::ParticleArgs a;
+    a.particles = reinterpret_cast<const uint4*>(particles_dev);
+    a.lights = reinterpret_cast<const float4*>(lights_dev);
+    a.scratch = c->particle_scratch;
+    a.count = count; a.nlights = nlights;
+    set_camera(a, u, c->cfg);
+    {
+        LaunchTimer t(c, 1);
+        RT_HIP(c, rtd::launch_draw_particles(planes_of(c), a, c->stream));
+    }
+    RT_HIP(c, c->ev_particles.record(c->stream));
     return RT_OK;
 }
 
@@ -271,6 +302,32 @@ int rt_draw_boxes_async(RtContext* ctx, const RtUniforms* u, const RtDrawBox* bo
     if (!query_device_ptr(ctx, boxes_dev) || !query_device_ptr(ctx, face_lights_dev))
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_draw_boxes_async: boxes and face_lights must be 16-byte aligned memory of the context's device");
     return draw_boxes_launch(ctx, u, boxes_dev, face_lights_dev, count);
+}
+
+int rt_draw_particles(RtContext* ctx, const RtUniforms* u, const RtParticle* particles, uint32_t count, const RtProbeLight* lights, uint32_t nlights) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    int rc = draw_particles_begin(ctx, "rt_draw_particles", u, particles, count, lights, nlights, &work);
+    if (rc != RT_OK || !work) return rc;
+    const uint32_t bad = first_invalid_particle(particles, count, nlights);
+    if (bad != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_draw_particles: particle " + std::to_string(bad) + " is not a valid particle");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    uint8_t* dev[2];
+    rc = stage_sync(ctx, ctx->stream, {{particles, (size_t)count * sizeof(RtParticle)}, {lights, (size_t)nlights * sizeof(RtProbeLight)}}, dev);
+    if (rc != RT_OK) return rc;
+    return finish_sync(ctx, draw_particles_launch(ctx, u, dev[0], count, dev[1], nlights));
+}
+
+int rt_draw_particles_async(RtContext* ctx, const RtUniforms* u, const RtParticle* particles_dev, uint32_t count, const RtProbeLight* lights_dev,
+                            uint32_t nlights) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    bool work;
+    const int rc = draw_particles_begin(ctx, "rt_draw_particles_async", u, particles_dev, count, lights_dev, nlights, &work);
+    if (rc != RT_OK || !work) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, particles_dev) || !query_device_ptr(ctx, lights_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_draw_particles_async: particles and lights must be 16-byte aligned memory of the context's device");
+    return draw_particles_launch(ctx, u, particles_dev, count, lights_dev, nlights);
 }
 
 int rt_add_lights(RtContext* ctx, const RtUniforms* u, const RtPointLight* lights, uint32_t count) {

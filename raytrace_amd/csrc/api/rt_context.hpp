@@ -329,6 +329,12 @@ struct __attribute__((visibility("hidden"))) RtContext {
     float4* probe_scratch = nullptr;
     size_t probe_scratch_bytes = 0;
     bool probe_pair = true;          // RT_PROBE_PAIR=0: the plain form of k_probe (A/B timing)
+    // rt_draw_particles[_async]: the binning scratch (rtd::particle_scratch_words of the call's count and the frame), grown on demand
+    // and never shrunk, in c->allocs (device_bytes; freed by rt_destroy).  One block serves every call: a call's launches follow the
+    // previous call's (ev_particles) wherever the frames' streams have taken them.
+    uint32_t* particle_scratch = nullptr;
+    size_t particle_scratch_words = 0;
+    rta::LatchEvent ev_particles;
 };
 
 namespace rta __attribute__((visibility("hidden"))) {
@@ -416,6 +422,25 @@ inline int stage_sync(RtContext* c, hipStream_t st, std::initializer_list<StageP
         off += p.bytes;
     }
     RT_HIP(c, hipMemcpyAsync(q.dev, q.host, send, hipMemcpyHostToDevice, st));
+    return RT_OK;
+}
+
+// At least `words` words of particle scratch.  A block that must grow waits for the launches that still use the old one.
+inline int particle_scratch_reserve(RtContext* c, size_t words) {
+    if (!c->ev_particles.ev) RT_HIP(c, new_event(c, &c->ev_particles.ev));
+    if (words <= c->particle_scratch_words) return RT_OK;
+    if (c->particle_scratch) {
+        RT_HIP(c, c->ev_particles.host_wait());
+        c->ev_particles.forget();
+        for (size_t i = 0; i < c->allocs.size(); i++)
+            if (c->allocs[i] == c->particle_scratch) { c->allocs.erase(c->allocs.begin() + (long)i); break; }
+        (void)hipFree(c->particle_scratch);
+        c->device_bytes -= c->particle_scratch_words * sizeof(uint32_t);
+        c->particle_scratch = nullptr;
+        c->particle_scratch_words = 0;
+    }
+    RT_HIP(c, dev_alloc(c, &c->particle_scratch, words));
+    c->particle_scratch_words = words;
     return RT_OK;
 }
 

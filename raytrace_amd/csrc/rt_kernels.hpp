@@ -238,6 +238,33 @@ struct DrawStampsArgs {
 };
 hipError_t launch_draw_stamps(const Planes& pl, const DrawStampsArgs& a, hipStream_t st);
 
+// rt_particles.hip: up to 2^20 small cubes composited likewise (rt_draw_particles): every pixel ends as launch_draw_boxes would leave
+// it for the cubes' boxes, but a tile reads only the particles binned to it.  Four launches behind one memset: bin (a thread per
+// particle finds the rectangle of tiles it may touch and counts itself into them, or joins the wide list), offsets (a thread per
+// tile claims its segment of the pair buffer), fill (a thread per particle again), draw (a wave per tile).
+constexpr uint32_t kMaxParticles = 1u << 20;       // particles per call, and light records per call
+constexpr uint32_t kParticleBinTiles = 16;         // W: a particle whose rectangle holds more tiles is listed by 8x8-tile blocks; more blocks: wide
+struct ParticleArgs {
+    const uint4* particles;  // RtParticle[count] (two uint4 each)
+    const float4* lights;    // RtProbeLight[nlights] (.xyz read)
+    uint32_t* scratch;       // particle_scratch_words(count, width, height) words
+    uint32_t count, nlights;
+    int width, height;
+    float origin[3], forward[3], up[3], right[3];   // as DrawBoxesArgs
+};
+// The scratch of a call, in 4-byte words: [0] the wide list's length, [1] the pairs handed out, then per list — one per 8x8 tile, then
+// one per block of 8x8 tiles — its pair count and its cursor into the pair buffer, then per particle its rectangle word and its place
+// in the wide list, then the kParticleBinTiles * count pairs — which cannot overflow: a binned particle adds at most
+// kParticleBinTiles of them, to tiles' lists or to blocks'.
+__host__ __device__ inline size_t particle_lists(int width, int height) {
+    const size_t tx = ((size_t)width + 7u) / 8u, ty = ((size_t)height + 7u) / 8u;
+    return tx * ty + ((tx + 7u) / 8u) * ((ty + 7u) / 8u);
+}
+inline size_t particle_scratch_words(uint32_t count, int width, int height) {
+    return 2u + 2u * particle_lists(width, height) + (size_t)(2u + kParticleBinTiles) * count;
+}
+hipError_t launch_draw_particles(const Planes& pl, const ParticleArgs& a, hipStream_t st);
+
 // rt_lights.hip: point lights added to the lighting planes of a whole frame's row-major planes (rt_add_lights).  One launch for the
 // batch; a wave owns an 8x8 pixel tile.  Frame supplies the camera of the frame the planes hold (origin, forward, up, right: the ray
 // of rt_draw_boxes), lr and the region.

@@ -1,6 +1,6 @@
 // rt_tile_pass.hpp — the scaffold of the passes over a drawn frame, one wave64 per 8x8 pixel tile and four tiles per workgroup
 // (rt_boxes.hip: k_draw_boxes, rt_draw_stamps.hip: k_draw_stamps, rt_lights.hip: k_add_lights and k_add_lights_occluded,
-// rt_shadows.hip: k_shadow_entities):
+// rt_shadows.hip: k_shadow_entities, rt_particles.hip: k_draw_particles and the cull of its bin pass):
 //   - TileLane: which tile a wave owns and which pixel a lane, and the grid of a launch;
 //   - the batch idiom's small pieces: a record's words broadcast from lane j (bcast, rec_xyz), the valid box, a model record decoded;
 //   - the entity draws' geometry: the primary direction of a pixel, what the cull knows of a tile's directions (tile_dirs), the
@@ -128,13 +128,14 @@ __device__ __forceinline__ vec3 primary_unnormalised(const Args& a, int px, int 
 
 // What the cull knows of the tile whose low pixel is (px0, py0) (the same in every lane); omax = the largest |o_k|.
 // v is fl(fl(forward + fl(right * sx)) + fl(up * sy)) per component: monotone in sx and in sy, each in a direction that does not
-// depend on the other, and sx / sy are monotone in the pixel — so every pixel's v lies between the four corners' values.
+// depend on the other, and sx / sy are monotone in the pixel — so every pixel's v lies between the four corners' values.  That holds
+// for any pixel rectangle px0 .. px0 + dx, py0 .. py0 + dy, not only for a tile: rt_particles.hip bins with rectangles of many tiles.
 template <typename Args>
-__device__ __forceinline__ TileDirs tile_dirs(const Args& a, int px0, int py0, float omax) {
+__device__ __forceinline__ TileDirs tile_dirs(const Args& a, int px0, int py0, float omax, int dx = 7, int dy = 7) {
     TileDirs td;
     td.flags = 0u;
-    const vec3 c00 = primary_unnormalised(a, px0, py0), c10 = primary_unnormalised(a, px0 + 7, py0);
-    const vec3 c01 = primary_unnormalised(a, px0, py0 + 7), c11 = primary_unnormalised(a, px0 + 7, py0 + 7);
+    const vec3 c00 = primary_unnormalised(a, px0, py0), c10 = primary_unnormalised(a, px0 + dx, py0);
+    const vec3 c01 = primary_unnormalised(a, px0, py0 + dy), c11 = primary_unnormalised(a, px0 + dx, py0 + dy);
     const float c[4][3] = {{c00.x, c00.y, c00.z}, {c10.x, c10.y, c10.z}, {c01.x, c01.y, c01.z}, {c11.x, c11.y, c11.z}};
     float len2_min = 0.0f, len2_max = 0.0f;
     bool finite = true;

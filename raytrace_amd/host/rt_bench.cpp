@@ -11,6 +11,7 @@
 //            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
 //            [--boxes N]
+//            [--particles N [--particle-half H] [--particle-near D]]
 //            [--entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--lights N] [--shadows N [--shadow-models]]
 //            [--light-shadows [--lights N] [--boxes B] [--models M] [--occluder-spread S] [--occluders-far]]
@@ -78,6 +79,12 @@
 // (20 to 400 units away, over the whole view), their six face probes lit with rt_probe_light (4 samples, depth 2), and rt_draw_boxes
 // composites them into a freshly drawn --width x --height frame, 20 times.  One JSON line: the device time of the pass (the launch
 // bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time of rt_draw_boxes and of the probes, and the pixels drawn.
+// --particles N [--particle-half H] [--particle-near D]: instead of the frame loop, particles.  A seeded cloud of N cubes of half edge H
+// (default 1/16) is scattered in front of the camera, D to 20 D units away (default 10 to 200, log-uniform) over the whole view, lit
+// by 64 whole-sphere probes that the particles share, and drawn by rt_draw_particles into a freshly drawn --width x --height frame, 20
+// times; with N <= 4096, as a yardstick in the same process, rt_draw_boxes draws the derived boxes, 20 times.  One JSON line: the
+// device time per call (the memset and the four launches bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time and the
+// pixels drawn, of both.  (--particle-half 300 --particle-near 400 makes every particle wide: the worst path.)
 // --models N [--model-scale S]: instead of the frame loop, voxel-model entities.  One built-in 9 x 9 x 12 sparse stamp (about a third of
 // its voxels solid) is drawn N times at scale S (default 1/8) — scattered like --boxes' boxes, in seeded orientations, lit by their
 // bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times; and, as a yardstick in the
@@ -543,6 +550,88 @@ int run_boxes(rt::game::Game& game, const std::vector<uint8_t>& noise, int width
     return 0;
 }
 
+// --particles: see the head of the file
+int run_particles(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n, float half,
+                  float near_dist) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY | RT_FLAG_TIMING_ALL);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    const uint32_t nlights = 64;
+    std::vector<RtParticle> particles(n);
+    std::vector<RtDrawBox> boxes(n <= 4096u ? n : 0u);            // the yardstick: rt_draw_boxes on the derived boxes
+    std::vector<RtLightProbe> probes(nlights);
+    for (uint32_t i = 0; i < n; i++) {
+        const float sx = rnd() * 2.0f - 1.0f, sy = rnd() * 2.0f - 1.0f, dist = near_dist * std::pow(20.0f, rnd());   // near .. 20 near, log-uniform
+        float v[3], len = 0.0f;
+        for (int a = 0; a < 3; a++) { v[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; len += v[a] * v[a]; }
+        len = std::sqrt(len);
+        RtParticle& q = particles[i];
+        q = RtParticle{};
+        for (int a = 0; a < 3; a++) q.center[a] = u.origin[a] + v[a] / len * dist;
+        q.half = half;
+        q.material = (1u << 15) | ((40u + i % 80u) << 14) | ((30u + i % 90u) << 7) | (20u + i % 100u);
+        q.emission = 0xFF000000u;
+        q.light = i % nlights;
+        if (i < boxes.size()) {
+            RtDrawBox& b = boxes[i];
+            for (int a = 0; a < 3; a++) { b.lo[a] = q.center[a] - q.half; b.hi[a] = q.center[a] + q.half; }
+            b.material = q.material; b.emission = q.emission;
+        }
+        if (i < nlights) {                                        // one whole-sphere probe per cluster, where its first particle is
+            RtLightProbe& l = probes[i];
+            l = RtLightProbe{};
+            for (int a = 0; a < 3; a++) l.position[a] = q.center[a];
+            l.normal = RT_PROBE_SPHERE;
+            l.cell[0] = (uint16_t)(i % 16u); l.cell[1] = (uint16_t)(i / 16u);
+        }
+    }
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    std::vector<RtProbeLight> lights(nlights);
+    int rc = n ? rt_probe_light(ctx, &u, probes.data(), n < nlights ? n : nlights, 4, 2, lights.data()) : RT_OK;
+    std::vector<RtProbeLight> face(6u * boxes.size());
+    for (size_t i = 0; i < face.size(); i++) face[i] = lights[particles[i / 6u].light];
+    const size_t npix = (size_t)width * (size_t)height;
+    std::vector<float> before(npix), after(npix);
+    if (rc == RT_OK) rc = rt_readback(ctx, RT_BUF_DEPTH_F32, before.data(), npix * sizeof(float));
+    const int reps = 20;
+    double device_ms[2] = {0.0, 0.0}, call_ms[2] = {0.0, 0.0};
+    uint64_t drawn[2] = {0, 0};
+    for (int pass = 0; pass < (boxes.empty() ? 1 : 2) && rc == RT_OK; pass++) {     // 0: the particles, 1: their boxes
+        for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {   // (the first repetition warms the staging and the scratch up)
+            RtTiming tm{};
+            rc = rt_draw_frame(ctx, &u);
+            if (rc == RT_OK) rc = rt_sync(ctx);
+            if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);   // (drains the frame's own launches)
+            auto t = std::chrono::steady_clock::now();
+            if (rc == RT_OK) rc = pass == 0 ? rt_draw_particles(ctx, &u, particles.data(), n, lights.data(), nlights)
+                                            : rt_draw_boxes(ctx, &u, boxes.data(), face.data(), n);
+            const double call = ms_since(t);
+            if (rc == RT_OK) rc = rt_get_timing(ctx, &tm);
+            if (i > 0) { device_ms[pass] += tm.shade_ms / reps; call_ms[pass] += call / reps; }
+        }
+        if (rc == RT_OK) rc = rt_readback(ctx, RT_BUF_DEPTH_F32, after.data(), npix * sizeof(float));
+        for (size_t i = 0; i < npix; i++) drawn[pass] += std::memcmp(&before[i], &after[i], 4) != 0;
+    }
+    if (rc != RT_OK) { std::fprintf(stderr, "particles failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    std::printf("{\"particles\": %u, \"half\": %g, \"near\": %g, \"frame\": \"%dx%d spp %d depth %d\", \"draw_particles_device_ms\": %.4f, "
+                "\"draw_particles_call_ms\": %.4f, \"pixels_drawn\": %llu",
+                n, (double)half, (double)near_dist, width, height, spp, depth, device_ms[0], call_ms[0], (unsigned long long)drawn[0]);
+    if (!boxes.empty())
+        std::printf(", \"draw_boxes_device_ms\": %.4f, \"draw_boxes_call_ms\": %.4f, \"boxes_pixels_drawn\": %llu", device_ms[1], call_ms[1],
+                    (unsigned long long)drawn[1]);
+    std::printf("}\n");
+    delete p;
+    return 0;
+}
+
 // --models: see the head of the file
 int run_models(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n, float scale) {
     std::string err;
@@ -928,7 +1017,8 @@ int main(int argc, char** argv) {
     int edit_stamp = -1;
     long long entity_rays = 0;
     bool coherent = false;
-    long long rays = 0, boxes = -1, lights = -1, models = -1, shadows = -1;
+    long long rays = 0, boxes = -1, lights = -1, models = -1, shadows = -1, particles = -1;
+    float particle_half = 0.0625f, particle_near = 10.0f;
     bool shadow_models = false, light_shadows = false, occluders_far = false;
     float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
@@ -968,6 +1058,9 @@ int main(int argc, char** argv) {
         else if (std::strcmp(argv[i], "--rays-coherent") == 0) rays_coherent = true;
         else if (want("--boxes")) boxes = std::atoll(argv[++i]);
         else if (want("--lights")) lights = std::atoll(argv[++i]);
+        else if (want("--particles")) particles = std::atoll(argv[++i]);
+        else if (want("--particle-half")) particle_half = std::strtof(argv[++i], nullptr);
+        else if (want("--particle-near")) particle_near = std::strtof(argv[++i], nullptr);
         else if (std::strcmp(argv[i], "--light-shadows") == 0) light_shadows = true;
         else if (want("--occluder-spread")) occluder_spread = std::strtof(argv[++i], nullptr);
         else if (std::strcmp(argv[i], "--occluders-far") == 0) occluders_far = true;
@@ -987,6 +1080,10 @@ int main(int argc, char** argv) {
     if (boxes < -1 || boxes > 4096) { std::fprintf(stderr, "--boxes must be in 0..4096\n"); return 2; }
     if (models < -1 || models > 4096 || !(model_scale >= 1.0f / 256.0f && model_scale <= 64.0f)) {
         std::fprintf(stderr, "--models must be in 0..4096, --model-scale in 2^-8..64\n");
+        return 2;
+    }
+    if (particles < -1 || particles > (1ll << 20) || !(particle_half > 0.0f && particle_half <= 4096.0f) || !(particle_near > 0.0f && particle_near <= 65536.0f)) {
+        std::fprintf(stderr, "--particles must be in 0..2^20, --particle-half in (0, 4096], --particle-near in (0, 65536]\n");
         return 2;
     }
     if (shadows < -1 || shadows > 4096) { std::fprintf(stderr, "--shadows must be in 0..4096\n"); return 2; }
@@ -1027,6 +1124,7 @@ int main(int argc, char** argv) {
         return run_entity_rays(game, noise, width, height, spp, depth, device, (uint32_t)entity_rays, (uint32_t)(boxes < 0 ? 0 : boxes),
                                (uint32_t)(models < 0 ? 0 : models), model_scale, coherent);
     if (rays > 0) return run_rays(game, noise, width, height, spp, depth, device, (uint32_t)rays, rays_coherent);
+    if (particles >= 0) return run_particles(game, noise, width, height, spp, depth, device, (uint32_t)particles, particle_half, particle_near);
     if (boxes >= 0) return run_boxes(game, noise, width, height, spp, depth, device, (uint32_t)boxes);
     if (models >= 0) return run_models(game, noise, width, height, spp, depth, device, (uint32_t)models, model_scale);
     if (shadows >= 0) return run_shadows(game, noise, width, height, spp, depth, device, (uint32_t)shadows, shadow_models, model_scale);

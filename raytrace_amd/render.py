@@ -12,8 +12,8 @@ import math
 
 import numpy as np
 
-from . import _lib
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_DRAW_STAMPS, MAX_ENTITY_RAYS, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
+from . import _lib, abi
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_DRAW_STAMPS, MAX_ENTITY_RAYS, MAX_PARTICLE_LIGHTS, MAX_PARTICLES, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
                   RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtDrawStamp, RtEntityHit, RtInfo, RtLightProbe,
                   RtPointLight, RtProbeLight, RtRayHit, RtShapeEdit, RtStampPlace, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
@@ -509,6 +509,23 @@ class Context:
         enqueued so far; an invalid box is skipped on the device."""
         n = check_draw_box_tensors(boxes, face_lights, self._device)
         self._check(self._lib.rt_draw_boxes_async(self._h, C.byref(uniforms), _dp(boxes), _dp(face_lights), n))
+
+    # -- particles ---------------------------------------------------------------------------------------
+    def draw_particles(self, uniforms, particles, lights):
+        """rt_draw_particles: `particles` abi.PARTICLE_DTYPE[N] records (make_particles), each the cube center -+ half lit on all faces by
+        `lights`[particle.light] (PROBE_LIGHT_DTYPE[L] records, what probe_records returns), composited by depth into the planes of the
+        frame drawn last under the camera of `uniforms`, exactly as draw_boxes composites the derived boxes.  Synchronous; an invalid
+        record fails the whole call (RtError, INVALID_ARG)."""
+        particles = _records(particles, abi.PARTICLE_DTYPE)
+        lights = _records(lights, PROBE_LIGHT_DTYPE)
+        self._check(self._lib.rt_draw_particles(self._h, C.byref(uniforms), _ptr_or_none(particles), particles.size, _ptr_or_none(lights), lights.size))
+
+    def draw_particles_async(self, uniforms, particles, lights):
+        """rt_draw_particles_async on torch device tensors: `particles` any contiguous tensor of N * 32 bytes (RtParticle rows), `lights`
+        any contiguous tensor of L * 16 bytes (e.g. the `out` of probe_light_async).  Enqueued behind the frame drawn last and the
+        queries enqueued so far; an invalid record is skipped on the device."""
+        n, nlights = particle_tensor_counts(particles, lights, self._device)
+        self._check(self._lib.rt_draw_particles_async(self._h, C.byref(uniforms), _dp(particles), n, _dp(lights), nlights))
 
     # -- voxel-model entities ----------------------------------------------------------------------------
     def draw_stamps(self, uniforms, models, face_lights):
@@ -1163,6 +1180,31 @@ def check_draw_box_tensors(boxes, face_lights, device):
     n = _box_count(boxes)
     _holds("face_lights", face_lights, n, PROBE_LIGHT_DTYPE.itemsize, per=6)
     return n
+
+
+def make_particles(centers, halves, materials, lights=0, emissions=0xFF000000):
+    """RtParticle records (abi.PARTICLE_DTYPE) from float[N, 3] centres, float[N] half edges, u32[N] packed material words, u32[N] light
+    indices and u32[N] RGBA8 emission words (one value serves every particle).  The records are not judged here: what is valid
+    depends on the call's light count (rt_draw_particles refuses an invalid record, the asynchronous call skips it)."""
+    c = np.asarray(centers, dtype=np.float32).reshape(-1, 3)
+    n = c.shape[0]
+    if n > MAX_PARTICLES:
+        raise ValueError("at most %d particles per call" % MAX_PARTICLES)
+    p = np.zeros(n, dtype=abi.PARTICLE_DTYPE)
+    p["center"] = c
+    p["half"] = np.broadcast_to(np.asarray(halves, dtype=np.float32), (n,))
+    p["material"] = np.broadcast_to(np.asarray(materials, dtype=np.uint32), (n,))
+    p["light"] = np.broadcast_to(np.asarray(lights, dtype=np.uint32), (n,))
+    p["emission"] = np.broadcast_to(np.asarray(emissions, dtype=np.uint32), (n,))
+    return p
+
+
+def particle_tensor_counts(particles, lights, device):
+    """Context.draw_particles_async's arguments: contiguous tensors of N * 32 and L * 16 bytes on GPU `device`, 16-byte aligned, N and L
+    at most 2^20.  Returns (N, L); raises ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
+    _device_tensors(device, ("particles", particles), ("lights", lights))
+    n = record_count("particles", _nbytes(particles), abi.PARTICLE_DTYPE.itemsize, MAX_PARTICLES, "RtParticle")
+    return n, record_count("lights", _nbytes(lights), PROBE_LIGHT_DTYPE.itemsize, MAX_PARTICLE_LIGHTS, "RtProbeLight")
 
 
 def check_shadow_box_tensor(boxes, device):
