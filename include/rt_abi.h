@@ -767,8 +767,9 @@ int rt_draw_stamps_async(RtContext* ctx, const RtUniforms* u, const RtDrawStamp*
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Particles: many small cubes — debris and dust of an explosion,
  * sparks, rain, snow, leaves, smoke puffs — composited by depth into the G-buffer of the frame drawn last exactly as the entity boxes
  * are, up to 2^20 per call.  The cost follows the pixels the cubes cover, not count x tiles: each 8x8 tile reads only the particles
- * binned to it.  The calls draw; they do not simulate (rt_sweep_boxes_async moves small boxes through the world from device buffers,
- * and the asynchronous call takes device pointers, so particle state need never visit the host).  One particle, 32 bytes: */
+ * binned to it.  The calls draw; they do not simulate: rt_step_particles_async ("Particle simulation" below) moves, bounces and
+ * ages particles on the device and writes these records there, and the asynchronous draw takes device pointers, so particle state
+ * need never visit the host.  One particle, 32 bytes: */
 typedef struct RtParticle {       /* 32 bytes */
     float    center[3]; float half;         /* world coordinates of the cube's centre; half its edge */
     uint32_t material;  uint32_t emission;  /* as RtDrawBox's */
@@ -808,6 +809,86 @@ int rt_draw_particles(RtContext* ctx, const RtUniforms* u, const RtParticle* par
  * anything is enqueued.  The library cannot read device records on the host: an invalid record is skipped on the device. */
 int rt_draw_particles_async(RtContext* ctx, const RtUniforms* u, const RtParticle* particles_dev, uint32_t count,
                             const RtProbeLight* lights_dev, uint32_t nlights);
+
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Particle simulation: one tick of up to 2^20 particles against the
+ * resident region, on the device — explosion debris, rain that stops on roofs, sparks that bounce, snow that settles on terrain the
+ * player has just edited.  A call integrates velocity, moves each particle's box through the world by rt_sweep_boxes' own rules (up
+ * to four sub-sweeps per tick), responds to contact (die, stick, slide or bounce), ages the particle and writes both the next state
+ * and the RtParticle record rt_draw_particles reads.  rt_step_particles_async -> rt_probe_light_async -> rt_draw_particles_async
+ * runs without a host read.  Responses (RtParticleState.flags & RT_PSTATE_RESPONSE) and the other flag bits: */
+#define RT_PARTICLE_DIE    0   /* contact kills the particle (rain, sparks that vanish)      */
+#define RT_PARTICLE_STICK  1   /* contact stops it: velocity = 0 (snow, dust that settles)   */
+#define RT_PARTICLE_SLIDE  2   /* the blocked axis of velocity and motion is zeroed          */
+#define RT_PARTICLE_BOUNCE 3   /* the blocked axis is reflected times restitution            */
+#define RT_PSTATE_RESPONSE 0x3u
+#define RT_PSTATE_DEAD     0x100u     /* inactive: copied through, not drawn */
+#define RT_PSTATE_INVALID  0x200u     /* set by the device on a record outside the domain; inactive */
+#define RT_PSTATE_CONTACT  0x70000u   /* output: bit 16 + a set iff axis a blocked a sub-sweep this tick */
+/* One particle's state, 64 bytes: */
+typedef struct RtParticleState {   /* 64 bytes */
+    float lo[3];       float life;        /*  0  the swept box (rt_sweep_boxes' lo / hi); seconds left, +inf = for ever */
+    float hi[3];       uint32_t flags;    /* 16  RT_PARTICLE_* | RT_PSTATE_* */
+    float velocity[3]; uint32_t light;    /* 32  units per second; RtParticle.light */
+    uint32_t material; uint32_t emission; /* 48  RtParticle's */
+    float half;        uint32_t reserved; /* 56  half edge of the DRAWN cube (constant; the swept box may differ from it); must be 0 */
+} RtParticleState;
+/* The parameters of one call, 48 bytes: */
+typedef struct RtParticleStep {    /* 48 bytes */
+    float dt;          float accel[3];    /*  0  seconds; gravity, wind: units per second^2 */
+    float damping;     float restitution; float friction; float rest_speed;   /* 16 */
+    int32_t lr[3];     uint32_t sweeps;   /* 32  the window, as rt_sweep_boxes'; sub-sweeps per tick 1..4 */
+} RtParticleStep;
+/* The rules.  All float arithmetic is fp32 with one rounding per operation and no fused multiply-add; max(x, c) is "x unless x < c",
+ * min(x, c) is "x unless x > c".  Results are reproduced bit for bit by tests/particle_step_ref.py, which calls tests/sweep_ref.py
+ * for every sub-sweep (DESIGN.md "Particle simulation").
+ *   Inactive records: a record with DEAD or INVALID set on input is copied to `out` bit for bit.  Its draw record has half = 0, which
+ *     rt_draw_particles_async skips as invalid; the other fields are as for a live particle.
+ *   Valid records: every float finite, except that life may be +inf; half > 0; reserved == 0; no flag bit outside RESPONSE | DEAD |
+ *     CONTACT (input CONTACT bits are ignored and overwritten); the box lo / hi inside rt_sweep_boxes' validated domain (|lo|, |hi| <=
+ *     2^22, per axis 0 < hi - lo <= 8, the fp32 difference).  The device copies an active invalid record through with INVALID set and
+ *     no other bit changed, draws it with half = 0 and fetches no voxel for it; rt_step_particles also refuses the whole call on the
+ *     host (RT_ERR_INVALID_ARG) before anything is enqueued.  The rest is about the records that are active and valid on input.
+ *   Integration: v_k = (v_k + accel_k * dt) * damping (three roundings), then the tick's motion m_k = min(max(v_k * dt, -64), 64).
+ *   Sub-sweeps, for s = 0 .. sweeps - 1; stop when every m_k == 0.  h = what rt_sweep_boxes returns for (lo, hi, m) under lr, every
+ *     field.  INVALID (a later sub-sweep's box collapsed by rounding): set INVALID and stop.  EMBEDDED (a block was placed onto the
+ *     particle): set DEAD and stop.  Otherwise lo, hi = h.lo, h.hi.  FREE: stop.  BLOCKED on axis a: set contact bit 16 + a, then by
+ *     response — DIE: set DEAD and stop.  STICK: v = (0, 0, 0) and stop.  Otherwise rest = 1 - h.t and m_k = m_k * rest for every k;
+ *     SLIDE: m_a = 0, v_a = 0.  BOUNCE: w = -(v_a * restitution); if |w| < rest_speed then w = 0; v_a = w; m_a = (w != 0) ?
+ *     -(m_a * restitution) : 0; on the other two axes v_k = v_k * friction and m_k = m_k * friction.  Motion left when the budget ends
+ *     is dropped.
+ *   Ageing: life = life - dt; if !(life > 0), set DEAD — also on a particle a sub-sweep has stopped, killed or marked.  The tick that
+ *     kills a particle no longer draws it.
+ *   Output state: lo, hi, velocity, life and flags as computed (RESPONSE kept, CONTACT this tick's); light, material, emission, half
+ *     and reserved copied.
+ *   Draw record: center_k = (lo_k + hi_k) * 0.5 of the output box; half = state.half, or 0 if DEAD or INVALID after the tick; material,
+ *     emission and light copied; reserved 0.  (Where lo_k or hi_k of an inactive record is a NaN, center_k is a NaN whose sign and
+ *     payload are not specified.)
+ *   Call parameters, checked on the host in both calls (RT_ERR_INVALID_ARG): every float finite; 0 < dt <= 1; |accel_k| <= 4096;
+ *     damping, restitution and friction in [0, 1]; rest_speed >= 0; sweeps in 1..4.
+ *   Pointers: `out` may equal `in` for an in-place step (a lane reads its record whole before it writes); `draw` may be NULL.  No
+ *     other overlap is allowed: ranges that overlap otherwise are RT_ERR_INVALID_ARG.
+ *   Errors, world, ordering and side effects: rt_sweep_boxes' — no world resident: RT_ERR_NOT_READY; a NULL params, in or out with
+ *     count > 0, or count > 2^20: RT_ERR_INVALID_ARG; count == 0: RT_OK, nothing enqueued.  The call sees every earlier upload, edit,
+ *     slab and generated region and runs on the query stream, or on the caller's stream after rt_set_stream(non-NULL); later world
+ *     changes wait for it.  No output plane, accumulation sum or history, RtCounters or RtTiming changes.  A rejected call writes
+ *     nothing.  Tile contexts, every RtKernel and every region size answer the same.
+ *   Closing property: on an unchanged world a live particle is never EMBEDDED, because each box it holds is one a sweep returned
+ *     (the sweeps' clamps: "Box sweeps", Returned box) — given a first box that overlaps no occupied voxel.
+ *   Out of scope: compaction of dead slots (it would make draw ties depend on atomics; a dead slot costs one record's traffic);
+ *     emitters (a host overwrites the oldest slots of a ring with hipMemcpyAsync); collision events reported to the host;
+ *     particle-particle and particle-entity contact; tile-split special cases (the call answers as the sweeps do).
+ *   Device work per call: one launch, one lane per particle: 64 bytes read, 64 (96 with `draw`) written, and the sub-sweeps' voxel
+ *     fetches; the synchronous call adds a transfer each way.
+ * Host pointers; returns when `out` (and `draw`) are in host memory. */
+int rt_step_particles(RtContext* ctx, const RtParticleStep* params, const RtParticleState* in, RtParticleState* out, RtParticle* draw,
+                      uint32_t count);
+/* Same with device pointers, enqueued: `out_dev` and `draw_dev` are valid after rt_sync (or, after rt_set_stream, in the caller's
+ * stream order); `params` is a host pointer, free again when the call returns.  in_dev, out_dev and a non-NULL draw_dev must pass
+ * rt_trace_rays_async's test (16-byte aligned memory of the context's device, or managed memory), else RT_ERR_INVALID_ARG before
+ * anything is enqueued; the states must be complete on the device when the call is made.  The library cannot read device records on
+ * the host: an invalid record gets RT_PSTATE_INVALID on the device. */
+int rt_step_particles_async(RtContext* ctx, const RtParticleStep* params, const RtParticleState* in_dev, RtParticleState* out_dev,
+                            RtParticle* draw_dev, uint32_t count);
 
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
@@ -1308,7 +1389,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: rt_add_lights_occluded, rt_add_lights_occluded_async (point-light shadows of entities:
  *        rt_add_lights with the drawn boxes and models blocking the segment from a pixel's surface point to the light).
  *        Additive, same minor version: RtParticle, rt_draw_particles, rt_draw_particles_async (particles: up to 2^20 small cubes
- *        composited into the G-buffer by depth, binned to the tiles they cover). */
+ *        composited into the G-buffer by depth, binned to the tiles they cover).
+ *        Additive, same minor version: RtParticleState, RtParticleStep, RT_PARTICLE_*, RT_PSTATE_*, rt_step_particles, rt_step_particles_async
+ *        (particle simulation: a tick of integration, sub-sweeps, contact response and ageing on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -50,6 +50,8 @@ AMD_FUNCTIONS = {
     "rt_probe_light_async": (INT, [P, UNI, P, U32, U32, C.c_int32, P]),
     "rt_sweep_boxes": (INT, [P, P, U32, I32P, P]),
     "rt_sweep_boxes_async": (INT, [P, P, U32, I32P, P]),
+    "rt_step_particles": (INT, [P, P, P, P, P, U32]),
+    "rt_step_particles_async": (INT, [P, P, P, P, P, U32]),
     "rt_trace_entities": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     "rt_trace_entities_async": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     "rt_pick_entities": (INT, [P, UNI, P, U32, P, U32, P, U32, P, P]),

@@ -234,6 +234,29 @@ MAX_PARTICLES = 1 << 20         # rt_draw_particles: particles per call
 MAX_PARTICLE_LIGHTS = 1 << 20   # ... and light records per call
 PARTICLE_DTYPE = np.dtype(RtParticle)   # the numpy view of the record (render.make_particles builds arrays of it)
 
+# rt_step_particles (ABI 1.3, additive: particle simulation): RtParticleState.flags
+RT_PARTICLE_DIE, RT_PARTICLE_STICK, RT_PARTICLE_SLIDE, RT_PARTICLE_BOUNCE = 0, 1, 2, 3   # the response to contact, flags & RT_PSTATE_RESPONSE
+RT_PSTATE_RESPONSE = 0x3
+RT_PSTATE_DEAD = 0x100        # inactive: copied through, not drawn
+RT_PSTATE_INVALID = 0x200     # set by the device on a record outside the domain; inactive
+RT_PSTATE_CONTACT = 0x70000   # output: bit 16 + a set iff axis a blocked a sub-sweep this tick
+
+
+class RtParticleState(C.Structure):
+    """rt_step_particles' state of one particle: 64 bytes; `reserved` must be 0."""
+    _fields_ = [("lo", C.c_float * 3), ("life", C.c_float), ("hi", C.c_float * 3), ("flags", C.c_uint32), ("velocity", C.c_float * 3),
+                ("light", C.c_uint32), ("material", C.c_uint32), ("emission", C.c_uint32), ("half", C.c_float), ("reserved", C.c_uint32)]
+
+
+class RtParticleStep(C.Structure):
+    """rt_step_particles' parameters of one call: 48 bytes."""
+    _fields_ = [("dt", C.c_float), ("accel", C.c_float * 3), ("damping", C.c_float), ("restitution", C.c_float), ("friction", C.c_float),
+                ("rest_speed", C.c_float), ("lr", C.c_int32 * 3), ("sweeps", C.c_uint32)]
+
+
+assert C.sizeof(RtParticleState) == 64 and C.sizeof(RtParticleStep) == 48
+PARTICLE_STATE_DTYPE = np.dtype(RtParticleState)   # the numpy view of the state (render.make_particle_states builds arrays of it)
+
 
 class RtDrawStamp(C.Structure):
     """rt_draw_stamps input (ABI 1.3, additive: voxel-model entities): 32 bytes; the reserved fields must be 0."""

@@ -1,7 +1,9 @@
 // api_query.hip — queries against the resident world: ray queries (rt_trace_rays, rt_trace_rays_async, rt_pick_pixels), light
-// probes (rt_probe_light, rt_probe_light_async), box sweeps (rt_sweep_boxes, rt_sweep_boxes_async) and entity queries
-// (rt_trace_entities, rt_trace_entities_async, rt_pick_entities), which share their checks, stream and staging.
+// probes (rt_probe_light, rt_probe_light_async), box sweeps (rt_sweep_boxes, rt_sweep_boxes_async), the particle simulation built on
+// them (rt_step_particles, rt_step_particles_async) and entity queries (rt_trace_entities, rt_trace_entities_async,
+// rt_pick_entities), which share their checks, stream and staging.
 #include "entity_query_check.hpp"
+#include "particle_step_check.hpp"
 #include "rt_context.hpp"
 
 using namespace rta;
@@ -171,6 +173,36 @@ int sweep_launch(RtContext* c, hipStream_t st, const int32_t lr[3], const void* 
     return RT_OK;
 }
 
+// ---- particle simulation: the sweeps' world, stream and ordering ---------------------------------------------------------------
+static_assert(sizeof(RtParticleState) == 64 && sizeof(RtParticleStep) == 48 && sizeof(RtParticle) == 32,
+              "the kernel reads and writes four 16-byte words per state and writes two per draw record");
+static_assert(kMaxStepParticles == rtd::kMaxParticles, "a tick's draw records are one rt_draw_particles call");
+
+// checks shared by the two calls; RT_OK when there is work to enqueue, 1 for count == 0
+int step_check(RtContext* c, const char* fn, const RtParticleStep* p, const void* in, const void* out, const void* draw, uint32_t count) {
+    const char* e = particle_step_args_error(p, in, out, draw, count);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e);
+    if (count == 0) return 1;
+    e = particle_step_params_error(*p);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e);
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    return RT_OK;
+}
+
+int step_launch(RtContext* c, hipStream_t st, const RtParticleStep& p, const void* in_dev, void* out_dev, void* draw_dev, uint32_t count) {
+    rtd::StepParticlesArgs a;
+    a.in = reinterpret_cast<const uint4*>(in_dev);
+    a.out = reinterpret_cast<uint4*>(out_dev);
+    a.draw = reinterpret_cast<uint4*>(draw_dev);
+    a.count = count;
+    a.sweeps = p.sweeps;
+    a.dt = p.dt; a.damping = p.damping; a.restitution = p.restitution; a.friction = p.friction; a.rest_speed = p.rest_speed;
+    for (int k = 0; k < 3; k++) { a.lr[k] = p.lr[k]; a.accel[k] = p.accel[k]; }
+    RT_HIP(c, rtd::launch_step_particles(scene_of(c), c->logr, a, st));
+    if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
+    return RT_OK;
+}
+
 // ---- entity queries: device rays (or pixels) and boxes, host models as rt_draw_stamps' ------------------------------------------
 static_assert(sizeof(RtEntityHit) == 48 && sizeof(RtRayHit) == 48, "the kernel writes three 16-byte words per record of either kind");
 
@@ -335,6 +367,44 @@ int rt_sweep_boxes_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t 
     rc = query_stream_of(ctx, &st);
     if (rc != RT_OK) return rc;
     return sweep_launch(ctx, st, lr, sweeps_dev, hits_dev, count);
+}
+
+int rt_step_particles(RtContext* ctx, const RtParticleStep* params, const RtParticleState* in, RtParticleState* out, RtParticle* draw,
+                      uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = step_check(ctx, "rt_step_particles", params, in, out, draw, count);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    const uint32_t bad = first_invalid_particle_state(in, count);
+    if (bad != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_step_particles: particle " + std::to_string(bad) + " is not a valid record");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    // the states through pinned and device staging, the launch in place there, the states and the draw records back
+    const size_t state_bytes = (size_t)count * sizeof(RtParticleState), draw_bytes = draw ? (size_t)count * sizeof(RtParticle) : 0u;
+    uint8_t* dev[2];
+    rc = stage_sync(ctx, st, {{in, state_bytes}, {nullptr, draw_bytes}}, dev);
+    if (rc != RT_OK) return rc;
+    rc = step_launch(ctx, st, *params, dev[0], dev[0], draw ? dev[1] : nullptr, count);
+    if (rc != RT_OK) return rc;
+    if (draw) {
+        rc = fetch_sync(ctx, st, dev[1], draw, draw_bytes);
+        if (rc != RT_OK) return rc;
+    }
+    return fetch_sync(ctx, st, dev[0], out, state_bytes);
+}
+
+int rt_step_particles_async(RtContext* ctx, const RtParticleStep* params, const RtParticleState* in_dev, RtParticleState* out_dev,
+                            RtParticle* draw_dev, uint32_t count) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = step_check(ctx, "rt_step_particles_async", params, in_dev, out_dev, draw_dev, count);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, in_dev) || !query_device_ptr(ctx, out_dev) || (draw_dev && !query_device_ptr(ctx, draw_dev)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_step_particles_async: in, out and draw must be 16-byte aligned memory of the context's device");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    return step_launch(ctx, st, *params, in_dev, out_dev, draw_dev, count);
 }
 
 int rt_trace_entities(RtContext* ctx, const RtRay* rays, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes, uint32_t nboxes,

@@ -216,6 +216,20 @@ struct SweepArgs {
 };
 hipError_t launch_sweep(const Scene& sc, int logr, const SweepArgs& a, hipStream_t st);
 
+// rt_step_particles.hip: one simulation tick of particles against the region (rt_step_particles).  One lane per particle, which
+// reads its record whole before it writes: `out` may be `in`; no other overlap.  The parameters are RtParticleStep's, checked on the
+// host (api/particle_step_check.hpp).
+struct StepParticlesArgs {
+    const uint4* in;      // RtParticleState[count] (four uint4 each)
+    uint4* out;           // RtParticleState[count]
+    uint4* draw;          // RtParticle[count] (two uint4 each), or null
+    uint32_t count;       // at most kMaxParticles
+    uint32_t sweeps;      // sub-sweeps per tick, 1..4
+    int32_t lr[3];
+    float dt, accel[3], damping, restitution, friction, rest_speed;
+};
+hipError_t launch_step_particles(const Scene& sc, int logr, const StepParticlesArgs& a, hipStream_t st);
+
 // rt_boxes.hip: entity boxes composited into a whole frame's row-major planes by depth (rt_draw_boxes).  One launch for the batch;
 // a wave owns an 8x8 pixel tile.
 struct DrawBoxesArgs {

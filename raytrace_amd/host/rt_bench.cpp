@@ -11,7 +11,7 @@
 //            [--stream [--stream-history]]
 //            [--rays N [--rays-coherent]]
 //            [--boxes N]
-//            [--particles N [--particle-half H] [--particle-near D]]
+//            [--particles N [--particle-half H] [--particle-near D] [--simulate T [--sweeps S]]]
 //            [--entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--lights N] [--shadows N [--shadow-models]]
 //            [--light-shadows [--lights N] [--boxes B] [--models M] [--occluder-spread S] [--occluders-far]]
@@ -85,6 +85,13 @@
 // times; with N <= 4096, as a yardstick in the same process, rt_draw_boxes draws the derived boxes, 20 times.  One JSON line: the
 // device time per call (the memset and the four launches bracketed by events, RT_FLAG_TIMING_ALL), the call-to-return time and the
 // pixels drawn, of both.  (--particle-half 300 --particle-near 400 makes every particle wide: the worst path.)
+// --particles N --simulate T [--sweeps S]: instead of drawing the cloud as it stands, simulate it.  The cloud's cubes become debris
+// (RtParticleState: the cube as the swept box, a seeded velocity up to 12 units per second per axis, RT_PARTICLE_BOUNCE, gravity 32,
+// dt 1/60, restitution 1/2, friction 3/4, S sub-sweeps per tick, default 3) in device buffers.  T ticks follow each other there
+// without a host read: a frame, then rt_step_particles_async -> rt_draw_particles_async, the tick's two calls bracketed by events.
+// In the same process, between events of their own: the first tick alone, repeated, and rt_sweep_boxes_async — the yardstick — on the
+// same boxes with that tick's motions; and the synchronous rt_sweep_boxes on those records, call to return: the host round trip a
+// tick on the device replaces (without the upload of the draw records it would also need).  One JSON line.
 // --models N [--model-scale S]: instead of the frame loop, voxel-model entities.  One built-in 9 x 9 x 12 sparse stamp (about a third of
 // its voxels solid) is drawn N times at scale S (default 1/8) — scattered like --boxes' boxes, in seeded orientations, lit by their
 // bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times; and, as a yardstick in the
@@ -632,6 +639,129 @@ int run_particles(rt::game::Game& game, const std::vector<uint8_t>& noise, int w
     return 0;
 }
 
+// --particles N --simulate T: see the head of the file
+int run_simulate(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n, float half,
+                 float near_dist, int ticks, uint32_t sweeps) {
+    std::string err;
+    RtConfig cfg = make_config(width, height, spp, depth, device, 0, 1, RT_FLAG_CACHE_PRIMARY);
+    rt::render::Pipeline* p = rt::render::create_instance(cfg, noise.data(), game, &err);
+    if (!p) { std::fprintf(stderr, "create_instance failed: %s\n", err.c_str()); return 1; }
+    RtContext* ctx = p->context();
+    if (p->draw_frame(game) != RT_OK || p->wait() != RT_OK) { std::fprintf(stderr, "frame failed: %s\n", p->last_error()); delete p; return 1; }
+    const RtUniforms u = p->uniforms();
+    const HipEvents hip;
+    if (!hip.ok) { std::fprintf(stderr, "--simulate needs the HIP runtime for its device buffers\n"); delete p; return 1; }
+    uint64_t x = 0x9E3779B97F4A7C15ull;
+    auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (float)((x >> 40) * (1.0 / 16777216.0)); };   // [0, 1)
+    RtParticleStep step{};
+    step.dt = 1.0f / 60.0f; step.accel[2] = -32.0f; step.damping = 1.0f; step.restitution = 0.5f; step.friction = 0.75f; step.rest_speed = 0.5f;
+    for (int a = 0; a < 3; a++) step.lr[a] = u.lr[a];
+    step.sweeps = sweeps;
+    // debris: --particles' cloud, every cube with a seeded velocity; and the same boxes with the first tick's motions as plain sweeps
+    const uint32_t nlights = 64;
+    std::vector<RtParticleState> states(n);
+    std::vector<RtBoxSweep> as_sweeps(n);
+    std::vector<RtLightProbe> probes(nlights);
+    for (uint32_t i = 0; i < n; i++) {
+        const float sx = rnd() * 2.0f - 1.0f, sy = rnd() * 2.0f - 1.0f, dist = near_dist * std::pow(20.0f, rnd());
+        float v[3], len = 0.0f;
+        for (int a = 0; a < 3; a++) { v[a] = u.forward[a] + u.right[a] * sx + u.up[a] * sy; len += v[a] * v[a]; }
+        len = std::sqrt(len);
+        RtParticleState& s = states[i];
+        s = RtParticleState{};
+        RtBoxSweep& w = as_sweeps[i];
+        w = RtBoxSweep{};
+        for (int a = 0; a < 3; a++) {
+            const float c = u.origin[a] + v[a] / len * dist;
+            s.lo[a] = w.lo[a] = c - half; s.hi[a] = w.hi[a] = c + half;
+            s.velocity[a] = (rnd() * 2.0f - 1.0f) * 12.0f;
+            const float m = (s.velocity[a] + step.accel[a] * step.dt) * step.damping * step.dt;
+            w.motion[a] = m < -64.0f ? -64.0f : (m > 64.0f ? 64.0f : m);
+        }
+        s.life = INFINITY; s.flags = RT_PARTICLE_BOUNCE; s.half = half; s.light = i % nlights;
+        s.material = (1u << 15) | ((40u + i % 80u) << 14) | ((30u + i % 90u) << 7) | (20u + i % 100u);
+        s.emission = 0xFF000000u;
+        if (i < nlights) {
+            RtLightProbe& l = probes[i];
+            l = RtLightProbe{};
+            for (int a = 0; a < 3; a++) l.position[a] = 0.5f * (s.lo[a] + s.hi[a]);
+            l.normal = RT_PROBE_SPHERE;
+            l.cell[0] = (uint16_t)(i % 16u); l.cell[1] = (uint16_t)(i / 16u);
+        }
+    }
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    const int32_t lr[3] = {u.lr[0], u.lr[1], u.lr[2]};
+    std::vector<RtProbeLight> lights(nlights);
+    int rc = n ? rt_probe_light(ctx, &u, probes.data(), n < nlights ? n : nlights, 4, 2, lights.data()) : RT_OK;
+    // the host round trip a tick on the device replaces, in part: the synchronous sweep of the same records
+    std::vector<RtSweepHit> hits(n);
+    const int reps = n >= (1u << 19) ? 5 : 20;
+    double sync_ms = 0.0;
+    for (int i = 0; i < 4 && rc == RT_OK; i++) {                  // (the first call warms the staging up)
+        const auto t = std::chrono::steady_clock::now();
+        rc = rt_sweep_boxes(ctx, as_sweeps.data(), n, lr, hits.data());
+        if (i > 0) sync_ms += ms_since(t) / 3.0;
+    }
+    uint64_t blocked = 0;
+    for (uint32_t i = 0; i < n; i++) blocked += hits[i].kind == RT_SWEEP_BLOCKED;
+    if (rc != RT_OK) { std::fprintf(stderr, "simulate failed (%d): %s\n", rc, rt_last_error(ctx)); delete p; return 1; }
+    void *st = nullptr, *e0 = nullptr, *e1 = nullptr;
+    void* d_a = hip.on_device(states.data(), (size_t)n * sizeof(RtParticleState));
+    void* d_b = hip.on_device(nullptr, (size_t)n * sizeof(RtParticleState));
+    void* d_first = hip.on_device(states.data(), (size_t)n * sizeof(RtParticleState));
+    void* d_draw = hip.on_device(nullptr, (size_t)n * sizeof(RtParticle));
+    void* d_sweeps = hip.on_device(as_sweeps.data(), (size_t)n * sizeof(RtBoxSweep));
+    void* d_hits = hip.on_device(nullptr, (size_t)n * sizeof(RtSweepHit));
+    void* d_lights = hip.on_device(lights.data(), (size_t)nlights * sizeof(RtProbeLight));
+    bool fine = d_a && d_b && d_first && d_draw && d_sweeps && d_hits && d_lights && hip.stream_create(&st) == 0 && hip.event_create(&e0) == 0 &&
+                hip.event_create(&e1) == 0 && rt_set_stream(ctx, st) == RT_OK;
+    // the first tick from the initial states and the plain sweep of the same boxes and motions: the same launch repeated between two events
+    double first_ms[2] = {-1.0, -1.0};
+    for (int which = 0; which < 2 && fine; which++) {
+        for (int i = 0; i < reps + 1 && fine; i++) {
+            if (i == 1) fine = hip.event_record(e0, st) == 0;
+            if (fine)
+                fine = (which == 0 ? rt_step_particles_async(ctx, &step, (const RtParticleState*)d_first, (RtParticleState*)d_b, (RtParticle*)d_draw, n)
+                                   : rt_sweep_boxes_async(ctx, (const RtBoxSweep*)d_sweeps, n, lr, (RtSweepHit*)d_hits)) == RT_OK;
+        }
+        float ms_f = 0.0f;
+        fine = fine && hip.event_record(e1, st) == 0 && hip.event_sync(e1) == 0 && hip.elapsed(&ms_f, e0, e1) == 0;
+        if (fine) first_ms[which] = (double)ms_f / reps;
+    }
+    // T ticks chained on the device: the frame (not timed), then step -> draw between two events
+    double tick_ms = 0.0;
+    for (int t = 0; t < ticks && fine; t++) {
+        fine = rt_draw_frame(ctx, &u) == RT_OK && hip.event_record(e0, st) == 0 &&
+               rt_step_particles_async(ctx, &step, (const RtParticleState*)d_a, (RtParticleState*)d_b, (RtParticle*)d_draw, n) == RT_OK &&
+               rt_draw_particles_async(ctx, &u, (const RtParticle*)d_draw, n, (const RtProbeLight*)d_lights, nlights) == RT_OK;
+        float ms_f = 0.0f;
+        fine = fine && hip.event_record(e1, st) == 0 && hip.event_sync(e1) == 0 && hip.elapsed(&ms_f, e0, e1) == 0;
+        tick_ms += (double)ms_f / ticks;
+        std::swap(d_a, d_b);
+    }
+    uint64_t alive = 0, contact = 0;
+    if (fine && n) {
+        fine = rt_sync(ctx) == RT_OK && hip.copy(states.data(), d_a, (size_t)n * sizeof(RtParticleState), 2 /* hipMemcpyDeviceToHost */) == 0;
+        for (uint32_t i = 0; i < n; i++) { alive += !(states[i].flags & (RT_PSTATE_DEAD | RT_PSTATE_INVALID)); contact += (states[i].flags & RT_PSTATE_CONTACT) != 0; }
+    }
+    if (rt_sync(ctx) != RT_OK || rt_set_stream(ctx, nullptr) != RT_OK) fine = false;
+    if (e0) (void)hip.event_destroy(e0);
+    if (e1) (void)hip.event_destroy(e1);
+    if (st) (void)hip.stream_destroy(st);
+    for (void* d : {d_a, d_b, d_first, d_draw, d_sweeps, d_hits, d_lights})
+        if (d) (void)hip.dev_free(d);
+    if (!fine) { std::fprintf(stderr, "simulate failed: %s\n", rt_last_error(ctx)); delete p; return 1; }
+    std::printf("{\"particles\": %u, \"half\": %g, \"simulate\": %d, \"sweeps\": %u, \"frame\": \"%dx%d spp %d depth %d\", \"step_device_ms\": %.4f, "
+                "\"sweep_boxes_device_ms\": %.4f, \"step_over_sweep\": %.2f, \"tick_device_ms\": %.4f, \"sweep_boxes_sync_call_ms\": %.3f, "
+                "\"first_tick_blocked\": %llu, \"alive\": %llu, \"in_contact_last_tick\": %llu}\n",
+                n, (double)half, ticks, sweeps, width, height, spp, depth, first_ms[0], first_ms[1], first_ms[1] > 0.0 ? first_ms[0] / first_ms[1] : 0.0,
+                tick_ms, sync_ms, (unsigned long long)blocked, (unsigned long long)alive, (unsigned long long)contact);
+    delete p;
+    return 0;
+}
+
 // --models: see the head of the file
 int run_models(rt::game::Game& game, const std::vector<uint8_t>& noise, int width, int height, int spp, int depth, int device, uint32_t n, float scale) {
     std::string err;
@@ -1019,6 +1149,7 @@ int main(int argc, char** argv) {
     bool coherent = false;
     long long rays = 0, boxes = -1, lights = -1, models = -1, shadows = -1, particles = -1;
     float particle_half = 0.0625f, particle_near = 10.0f;
+    int simulate = 0, step_sweeps = 3;
     bool shadow_models = false, light_shadows = false, occluders_far = false;
     float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
@@ -1061,6 +1192,8 @@ int main(int argc, char** argv) {
         else if (want("--particles")) particles = std::atoll(argv[++i]);
         else if (want("--particle-half")) particle_half = std::strtof(argv[++i], nullptr);
         else if (want("--particle-near")) particle_near = std::strtof(argv[++i], nullptr);
+        else if (want("--simulate")) simulate = std::atoi(argv[++i]);
+        else if (want("--sweeps")) step_sweeps = std::atoi(argv[++i]);
         else if (std::strcmp(argv[i], "--light-shadows") == 0) light_shadows = true;
         else if (want("--occluder-spread")) occluder_spread = std::strtof(argv[++i], nullptr);
         else if (std::strcmp(argv[i], "--occluders-far") == 0) occluders_far = true;
@@ -1078,6 +1211,10 @@ int main(int argc, char** argv) {
     if (rays < 0 || rays > (1ll << 26)) { std::fprintf(stderr, "--rays must be in 0..2^26\n"); return 2; }
     if (entity_rays < 0 || entity_rays > (1ll << 24)) { std::fprintf(stderr, "--entity-rays must be in 0..2^24\n"); return 2; }
     if (boxes < -1 || boxes > 4096) { std::fprintf(stderr, "--boxes must be in 0..4096\n"); return 2; }
+    if (simulate < 0 || simulate > 100000 || step_sweeps < 1 || step_sweeps > 4 || (simulate > 0 && (particles < 0 || particle_half > 4.0f))) {
+        std::fprintf(stderr, "--simulate must be in 0..100000 and goes with --particles (--particle-half at most 4), --sweeps in 1..4\n");
+        return 2;
+    }
     if (models < -1 || models > 4096 || !(model_scale >= 1.0f / 256.0f && model_scale <= 64.0f)) {
         std::fprintf(stderr, "--models must be in 0..4096, --model-scale in 2^-8..64\n");
         return 2;
@@ -1124,6 +1261,8 @@ int main(int argc, char** argv) {
         return run_entity_rays(game, noise, width, height, spp, depth, device, (uint32_t)entity_rays, (uint32_t)(boxes < 0 ? 0 : boxes),
                                (uint32_t)(models < 0 ? 0 : models), model_scale, coherent);
     if (rays > 0) return run_rays(game, noise, width, height, spp, depth, device, (uint32_t)rays, rays_coherent);
+    if (particles >= 0 && simulate > 0)
+        return run_simulate(game, noise, width, height, spp, depth, device, (uint32_t)particles, particle_half, particle_near, simulate, (uint32_t)step_sweeps);
     if (particles >= 0) return run_particles(game, noise, width, height, spp, depth, device, (uint32_t)particles, particle_half, particle_near);
     if (boxes >= 0) return run_boxes(game, noise, width, height, spp, depth, device, (uint32_t)boxes);
     if (models >= 0) return run_models(game, noise, width, height, spp, depth, device, (uint32_t)models, model_scale);

@@ -527,6 +527,26 @@ class Context:
         n, nlights = particle_tensor_counts(particles, lights, self._device)
         self._check(self._lib.rt_draw_particles_async(self._h, C.byref(uniforms), _dp(particles), n, _dp(lights), nlights))
 
+    # -- particle simulation ------------------------------------------------------------------------------
+    def step_particles(self, params, states):
+        """rt_step_particles: one tick of `states` (abi.PARTICLE_STATE_DTYPE[N] records, make_particle_states) under `params` (an
+        abi.RtParticleStep, make_particle_step) against the resident world -> (states, particles): the next states and the
+        abi.PARTICLE_DTYPE[N] draw records, as new arrays.  Synchronous; an active invalid record fails the whole call (RtError,
+        INVALID_ARG)."""
+        states = _records(states, abi.PARTICLE_STATE_DTYPE)
+        out = np.zeros(states.size, dtype=abi.PARTICLE_STATE_DTYPE)
+        draw = np.zeros(states.size, dtype=abi.PARTICLE_DTYPE)
+        self._check(self._lib.rt_step_particles(self._h, C.byref(params), _ptr_or_none(states), _ptr_or_none(out), _ptr_or_none(draw), states.size))
+        return out, draw
+
+    def step_particles_async(self, params, states_in, states_out, draw=None):
+        """rt_step_particles_async on torch device tensors: `states_in` and `states_out` any contiguous tensors of N * 64 bytes
+        (RtParticleState rows; the same tensor steps in place), `draw` a contiguous tensor of N * 32 bytes (RtParticle rows, what
+        draw_particles_async takes) or None.  Enqueued: valid after sync(), or in the order of a stream given to set_stream().
+        `states_in` must be complete on the device when the call is made.  An active invalid record gets RT_PSTATE_INVALID."""
+        n = particle_step_tensor_count(states_in, states_out, draw, self._device)
+        self._check(self._lib.rt_step_particles_async(self._h, C.byref(params), _dp(states_in), _dp(states_out), _dp(draw), n))
+
     # -- voxel-model entities ----------------------------------------------------------------------------
     def draw_stamps(self, uniforms, models, face_lights):
         """rt_draw_stamps: `models` DRAW_STAMP_DTYPE[N] records (make_draw_stamps) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
@@ -1205,6 +1225,77 @@ def particle_tensor_counts(particles, lights, device):
     _device_tensors(device, ("particles", particles), ("lights", lights))
     n = record_count("particles", _nbytes(particles), abi.PARTICLE_DTYPE.itemsize, MAX_PARTICLES, "RtParticle")
     return n, record_count("lights", _nbytes(lights), PROBE_LIGHT_DTYPE.itemsize, MAX_PARTICLE_LIGHTS, "RtProbeLight")
+
+
+def make_particle_states(lo, hi, velocities=0.0, halves=None, responses=abi.RT_PARTICLE_DIE, lives=np.inf, materials=0, lights=0,
+                         emissions=0xFF000000):
+    """RtParticleState records (abi.PARTICLE_STATE_DTYPE) from float[N, 3] corners of the swept boxes, float[N, 3] velocities, float[N]
+    half edges of the drawn cubes (None: half the box's x extent), RT_PARTICLE_* responses, float[N] seconds of life, u32[N] packed
+    material words, light indices and RGBA8 emission words (one value serves every particle).  The records are not judged here:
+    rt_step_particles refuses an invalid record, the asynchronous call marks it RT_PSTATE_INVALID."""
+    lo = np.asarray(lo, dtype=np.float32).reshape(-1, 3)
+    hi = np.asarray(hi, dtype=np.float32).reshape(-1, 3)
+    if lo.shape != hi.shape:
+        raise ValueError("lo and hi must have the same shape [N, 3]")
+    n = lo.shape[0]
+    if n > MAX_PARTICLES:
+        raise ValueError("at most %d particles per call" % MAX_PARTICLES)
+    s = np.zeros(n, dtype=abi.PARTICLE_STATE_DTYPE)
+    s["lo"], s["hi"] = lo, hi
+    s["velocity"] = np.broadcast_to(np.asarray(velocities, dtype=np.float32), (n, 3))
+    s["half"] = (hi[:, 0] - lo[:, 0]) * np.float32(0.5) if halves is None else np.broadcast_to(np.asarray(halves, dtype=np.float32), (n,))
+    s["flags"] = np.broadcast_to(np.asarray(responses, dtype=np.uint32), (n,)) & np.uint32(abi.RT_PSTATE_RESPONSE)
+    s["life"] = np.broadcast_to(np.asarray(lives, dtype=np.float32), (n,))
+    s["material"] = np.broadcast_to(np.asarray(materials, dtype=np.uint32), (n,))
+    s["light"] = np.broadcast_to(np.asarray(lights, dtype=np.uint32), (n,))
+    s["emission"] = np.broadcast_to(np.asarray(emissions, dtype=np.uint32), (n,))
+    return s
+
+
+def make_particle_step(dt, accel=(0.0, 0.0, 0.0), damping=1.0, restitution=0.5, friction=1.0, rest_speed=0.0, lr=(0, 0, 0), sweeps=3):
+    """An abi.RtParticleStep: `dt` seconds, `accel` (gravity, wind), the velocity's `damping` per tick, a bounce's `restitution` on the
+    blocked axis and `friction` on the other two, the speed below which a bounce comes to rest, the window `lr` and the sub-sweeps per
+    tick.  Refuses what the calls refuse: a non-finite float, dt outside (0, 1], |accel| above 4096, a factor outside [0, 1], a
+    negative rest_speed, sweeps outside 1..4."""
+    p = abi.RtParticleStep()
+    p.dt, p.damping, p.restitution, p.friction, p.rest_speed = float(dt), float(damping), float(restitution), float(friction), float(rest_speed)
+    accel = [float(v) for v in accel]
+    if len(accel) != 3 or len(lr) != 3:
+        raise ValueError("accel and lr have three components")
+    for k in range(3):
+        p.accel[k], p.lr[k] = accel[k], int(lr[k])
+    if not all(math.isfinite(v) for v in [p.dt, p.damping, p.restitution, p.friction, p.rest_speed] + accel):
+        raise ValueError("every parameter must be finite")
+    if not 0.0 < p.dt <= 1.0:
+        raise ValueError("dt must be in (0, 1]")
+    if max(abs(v) for v in accel) > 4096.0:
+        raise ValueError("accel must lie within +-4096")
+    if not (0.0 <= p.damping <= 1.0 and 0.0 <= p.restitution <= 1.0 and 0.0 <= p.friction <= 1.0):
+        raise ValueError("damping, restitution and friction must be in [0, 1]")
+    if p.rest_speed < 0.0:
+        raise ValueError("rest_speed must not be negative")
+    if not 1 <= int(sweeps) <= 4:
+        raise ValueError("sweeps must be 1..4")
+    p.sweeps = int(sweeps)
+    return p
+
+
+def particle_step_tensor_count(states_in, states_out, draw, device):
+    """Context.step_particles_async's arguments: contiguous tensors of N * 64, N * 64 and (unless None) N * 32 bytes on GPU `device`,
+    16-byte aligned, N at most 2^20; `states_out` may be `states_in`'s memory, no other overlap.  Returns N; raises ValueError otherwise
+    (a host tensor's address handed to the kernel would fault the device)."""
+    named = [("states_in", states_in), ("states_out", states_out)] + ([("draw", draw)] if draw is not None else [])
+    _device_tensors(device, *named)
+    n = record_count("states_in", _nbytes(states_in), abi.PARTICLE_STATE_DTYPE.itemsize, MAX_PARTICLES, "RtParticleState")
+    _holds("states_out", states_out, n, abi.PARTICLE_STATE_DTYPE.itemsize)
+    if draw is not None:
+        _holds("draw", draw, n, abi.PARTICLE_DTYPE.itemsize)
+    spans = [(name, t.data_ptr(), t.data_ptr() + _nbytes(t)) for name, t in named]
+    for i, (na, a0, a1) in enumerate(spans):
+        for nb, b0, b1 in spans[i + 1:]:
+            if a0 < b1 and b0 < a1 and not (na == "states_in" and nb == "states_out" and a0 == b0):
+                raise ValueError("%s and %s overlap (only states_out may be states_in's memory, whole)" % (na, nb))
+    return n
 
 
 def check_shadow_box_tensor(boxes, device):
