@@ -39,7 +39,8 @@ AMD_DEPS = AMD_SRCS + sorted(os.path.join(d, f) for d in (CSRC, API) for f in os
     os.path.join(INC, "rt_abi.h"), os.path.join(INC, "rt_math.h")]
 HOST_SRCS = [os.path.join(HOST, f) for f in ("world.cpp", "chunk_storage.cpp", "terrain_upload.cpp", "render.cpp", "host_capi.cpp")]
 HOST_DEPS = HOST_SRCS + [os.path.join(HOST, f) for f in ("world.hpp", "render.hpp", "chunk_storage.hpp", "terrain_upload.hpp")] + [os.path.join(INC, "rt_abi.h")]
-BENCH_SRCS = [os.path.join(HOST, "rt_bench.cpp")]
+BENCH_SRCS = [os.path.join(HOST, f) for f in ("rt_bench.cpp", "bench_modes.cpp")]
+BENCH_DEPS = BENCH_SRCS + [os.path.join(HOST, f) for f in ("bench_run.hpp", "bench_scene.hpp", "render.hpp")] + [os.path.join(INC, "rt_abi.h")]
 
 LIB_AMD = os.path.join(HERE, "librt_amd.so")
 LIB_HOST = os.path.join(HERE, "librt_host.so")
@@ -72,7 +73,7 @@ def build(force=False, verbose=True):
         _run([CXX] + CXX_FLAGS + ["-shared", "-o", LIB_HOST] + HOST_SRCS +
              ["-L", HERE, "-lrt_amd", "-ldl", "-Wl,-rpath,$ORIGIN"])
         built.append(LIB_HOST)
-    if all(os.path.exists(s) for s in BENCH_SRCS) and (force or _stale(BENCH, BENCH_SRCS + [LIB_HOST, LIB_AMD])):
+    if all(os.path.exists(s) for s in BENCH_SRCS) and (force or _stale(BENCH, BENCH_DEPS + [LIB_HOST, LIB_AMD])):
         _run([CXX] + CXX_FLAGS + ["-o", BENCH] + BENCH_SRCS + ["-L", HERE, "-lrt_host", "-lrt_amd", "-lpthread", "-ldl", "-Wl,-rpath,$ORIGIN"])
         built.append(BENCH)
     return built

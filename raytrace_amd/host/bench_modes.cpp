@@ -1,0 +1,496 @@
+// bench_modes.cpp — rt_bench's modes that run instead of the frame loop.  Each opens one session (RT_FLAG_TIMING_ALL where the mode
+// reads the device time of a launch from rt_get_timing), builds its records with bench_scene.hpp's builders in the order that
+// consumes the generator as the committed figures were measured with, times its calls and prints one JSON line.
+#include <algorithm>
+#include <cmath>
+
+#include "bench_run.hpp"
+
+namespace bench {
+
+// --rays N: ray queries against the generated world.  rt_trace_rays on N rays — seeded origins in the region with random
+// directions, or with --rays-coherent the primary rays of a --width x --height camera at the default pose handed over as arbitrary
+// rays — timed call to return (the transfers both ways included; the kernel alone: rocprofv3 --kernel-trace --stats, or
+// tools/ray_query_bench.py's device events), then the call-to-return latency of one-pixel rt_pick_pixels, idle and right behind a
+// --width x --height --spp --depth frame still in flight.
+int run_rays(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, 0u)) return 1;
+    const uint32_t n = (uint32_t)o.rays;
+    const std::vector<RtRay> rays = ray_list(s.view, s.rnd, n, o.rays_coherent);
+    std::vector<RtRayHit> hits(n);
+    int rc = rt_trace_rays(s.ctx, rays.data(), n, s.u().lr, hits.data());   // warm-up (staging grows once)
+    const int reps = n >= (1u << 20) ? 5 : 50;
+    auto t = std::chrono::steady_clock::now();
+    for (int i = 0; i < reps && rc == RT_OK; i++) rc = rt_trace_rays(s.ctx, rays.data(), n, s.u().lr, hits.data());
+    const double ms = ms_since(t) / reps;
+    uint64_t solid = 0;
+    for (const RtRayHit& h : hits) solid += h.kind == RT_HIT_SOLID;
+    const int32_t xy[2] = {o.width / 2, o.height / 2};
+    RtRayHit one{};
+    std::vector<double> idle, busy;
+    for (int i = 0; i < 220 && rc == RT_OK; i++) {
+        t = std::chrono::steady_clock::now();
+        rc = rt_pick_pixels(s.ctx, &s.u(), xy, 1, &one);
+        if (i >= 20) idle.push_back(ms_since(t));
+    }
+    double frame_ms = 0;
+    for (int i = 0; i < 21 && rc == RT_OK; i++) {
+        const auto tf = std::chrono::steady_clock::now();
+        rc = rt_draw_frame(s.ctx, &s.u());
+        t = std::chrono::steady_clock::now();
+        if (rc == RT_OK) rc = rt_pick_pixels(s.ctx, &s.u(), xy, 1, &one);
+        if (i > 0) busy.push_back(ms_since(t));
+        if (rc == RT_OK) rc = rt_sync(s.ctx);
+        if (i > 0) frame_ms += ms_since(tf) / 20.0;
+    }
+    if (rc != RT_OK) return s.fail("ray queries", rc);
+    std::sort(idle.begin(), idle.end());
+    std::sort(busy.begin(), busy.end());
+    std::printf("{\"rays\": %u, \"coherent\": %s, \"trace_rays_ms\": %.4f, \"grays_call_to_return\": %.3f, \"solid_hits\": %llu, "
+                "\"pick_ms_idle_median\": %.4f, \"pick_ms_in_flight_median\": %.4f, \"pick_ms_in_flight_max\": %.4f, "
+                "\"frame\": \"%dx%d spp %d depth %d\", \"frame_ms\": %.3f}\n",
+                n, o.rays_coherent ? "true" : "false", ms, (double)n / (ms * 1e-3) / 1e9, (unsigned long long)solid, idle[idle.size() / 2],
+                busy[busy.size() / 2], busy.back(), o.width, o.height, o.spp, o.depth, frame_ms);
+    return 0;
+}
+
+// --entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]: entity queries.  rt_trace_entities on N rays — --rays'
+// seeded rays, or with --coherent its camera rays — against B boxes and M models scattered as --boxes and --models scatter them (in
+// one index run: the orientation follows the joint index), and rt_trace_rays on the same rays as the yardstick, both timed call to
+// return; then their asynchronous twins on device copies of the same records, on a stream of this program's, between two HIP events:
+// the device time of each.  The JSON line also counts the rays that report an entity and those whose entity the world occludes.  (The
+// kernels alone, k_entity_query and k_query: rocprofv3 --kernel-trace --stats, which tools/entity_query_bench.py runs.)
+int run_entity_rays(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, 0u)) return 1;
+    const uint32_t n = (uint32_t)o.entity_rays, nboxes = (uint32_t)std::max(o.boxes, 0ll), nmodels = (uint32_t)std::max(o.models, 0ll);
+    const std::vector<RtRay> rays = ray_list(s.view, s.rnd, n, o.coherent);
+    SparseStamp stamp = sparse_stamp(s.rnd, 9, 9, 12);
+    if (!s.create_stamp(&stamp)) return 1;
+    std::vector<RtDrawBox> boxes(nboxes);
+    std::vector<RtDrawStamp> models(nmodels);
+    for (uint32_t i = 0; i < nboxes + nmodels; i++) {
+        float c[3];
+        scatter_point(s.u(), s.rnd, 20.0f, c);   // 20 .. 400 units away
+        if (i < nboxes) {
+            player_box(c, &boxes[i]);
+            boxes[i].material = 0x12345u; boxes[i].emission = 0xFF000000u;
+        } else {
+            models[i - nboxes] = model_at(stamp, o.model_scale, i, c, nullptr);
+        }
+    }
+    const int32_t* lr = s.u().lr;
+    std::vector<RtRayHit> world(n), plain(n);
+    std::vector<RtEntityHit> hits(n);
+    const int reps = n >= (1u << 20) ? 5 : 20;
+    double ms[2] = {0.0, 0.0};
+    int rc = RT_OK;
+    for (int which = 0; which < 2 && rc == RT_OK; which++) {      // 0: rt_trace_entities, 1: rt_trace_rays on the same rays, the yardstick
+        for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {       // (the first repetition warms the staging up)
+            const auto t = std::chrono::steady_clock::now();
+            rc = which == 0 ? rt_trace_entities(s.ctx, rays.data(), n, lr, boxes.data(), nboxes, models.data(), nmodels, world.data(), hits.data())
+                            : rt_trace_rays(s.ctx, rays.data(), n, lr, plain.data());
+            if (i > 0) ms[which] += ms_since(t) / reps;
+        }
+    }
+    if (rc != RT_OK) return s.fail("entity queries", rc);
+    if (std::memcmp(world.data(), plain.data(), (size_t)n * sizeof(RtRayHit)) != 0) { std::fprintf(stderr, "the world hits differ from rt_trace_rays'\n"); return 1; }
+    // reported: the call's own answer; occluded: rays that report an entity only once the world is out of the way — the same call with
+    // the window moved 2^20 voxels off, where every ray leaves the region at once (D = 65535)
+    uint64_t reported = 0, under_sky = 0, met = 0;
+    for (uint32_t i = 0; i < n; i++) { reported += hits[i].kind != RT_ENTITY_NONE; under_sky += hits[i].kind != RT_ENTITY_NONE && world[i].kind == RT_HIT_AIR; }
+    const int32_t away[3] = {lr[0] + (1 << 20), lr[1], lr[2]};
+    rc = rt_trace_entities(s.ctx, rays.data(), n, away, boxes.data(), nboxes, models.data(), nmodels, nullptr, hits.data());
+    if (rc != RT_OK) return s.fail("entity queries", rc);
+    for (uint32_t i = 0; i < n; i++) met += hits[i].kind != RT_ENTITY_NONE;
+    // device time of each call: the asynchronous twins between two events (-1: the HIP runtime could not be reached from here)
+    double device_ms[2] = {-1.0, -1.0};
+    const HipEvents hip;
+    if (hip.ok) {
+        DeviceRun run(hip, s.ctx);
+        const RtRay* d_rays = (const RtRay*)run.on_device(rays.data(), (size_t)n * sizeof(RtRay));
+        const RtDrawBox* d_boxes = (const RtDrawBox*)run.on_device(boxes.data(), (size_t)nboxes * sizeof(RtDrawBox));
+        RtRayHit* d_world = (RtRayHit*)run.on_device(nullptr, (size_t)n * sizeof(RtRayHit));
+        RtEntityHit* d_hits = (RtEntityHit*)run.on_device(nullptr, (size_t)n * sizeof(RtEntityHit));
+        run.start();
+        device_ms[0] = run.repeat(reps, [&] { return rt_trace_entities_async(s.ctx, d_rays, n, lr, nboxes ? d_boxes : nullptr, nboxes, models.data(), nmodels, d_world, d_hits); });
+        device_ms[1] = run.repeat(reps, [&] { return rt_trace_rays_async(s.ctx, d_rays, n, lr, d_world); });
+        if (!run.close()) { std::fprintf(stderr, "timing the asynchronous calls failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    }
+    std::printf("{\"entity_rays\": %u, \"coherent\": %s, \"boxes\": %u, \"models\": %u, \"model_scale\": %g, \"trace_entities_call_ms\": %.4f, "
+                "\"trace_rays_call_ms\": %.4f, \"ratio\": %.2f, \"entities_reported\": %llu, \"entities_occluded\": %llu, \"reported_under_sky\": %llu, "
+                "\"trace_entities_device_ms\": %.4f, \"trace_rays_device_ms\": %.4f}\n",
+                n, o.coherent ? "true" : "false", nboxes, nmodels, (double)o.model_scale, ms[0], ms[1], ms[1] > 0.0 ? ms[0] / ms[1] : 0.0,
+                (unsigned long long)reported, (unsigned long long)(met > reported ? met - reported : 0), (unsigned long long)under_sky, device_ms[0], device_ms[1]);
+    return 0;
+}
+
+// --boxes N: entity boxes.  N entity-sized boxes are scattered deterministically in front of the camera (20 to 400 units away, over
+// the whole view), their six face probes lit with rt_probe_light (4 samples, depth 2), and rt_draw_boxes composites them into a
+// freshly drawn --width x --height frame, 20 times.  One JSON line: the device time of the pass, the call-to-return time of
+// rt_draw_boxes and of the probes, and the pixels drawn.
+int run_boxes(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const uint32_t n = (uint32_t)o.boxes;
+    std::vector<RtDrawBox> boxes(n);
+    std::vector<RtLightProbe> probes(6u * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        float c[3];
+        scatter_point(s.u(), s.rnd, 20.0f, c);
+        player_box(c, &boxes[i]);
+        boxes[i].material = material_word(i); boxes[i].emission = 0xFF000000u;
+        face_probes(boxes[i], i, &probes[6u * (size_t)i]);
+    }
+    std::vector<RtProbeLight> lights(probes.size());
+    const auto t = std::chrono::steady_clock::now();
+    int rc = n ? rt_probe_light(s.ctx, &s.u(), probes.data(), (uint32_t)probes.size(), 4, 2, lights.data()) : RT_OK;
+    const double probe_ms = ms_since(t);
+    const size_t npix = (size_t)o.width * (size_t)o.height;
+    std::vector<float> before(npix), after(npix);
+    if (rc == RT_OK) rc = s.read_plane(RT_BUF_DEPTH_F32, &before);
+    PassTime pt;
+    rc = timed_pass(s, rc, &pt, [&] { return rt_draw_boxes(s.ctx, &s.u(), boxes.data(), lights.data(), n); });
+    if (rc == RT_OK) rc = s.read_plane(RT_BUF_DEPTH_F32, &after);
+    if (rc != RT_OK) return s.fail("entity boxes", rc);
+    std::printf("{\"boxes\": %u, \"frame\": \"%dx%d spp %d depth %d\", \"draw_boxes_device_ms\": %.4f, \"draw_boxes_call_ms\": %.4f, "
+                "\"launches_per_call\": %.2f, \"probe_light_call_ms\": %.3f, \"pixels_drawn\": %llu}\n",
+                n, o.width, o.height, o.spp, o.depth, pt.device_ms, pt.call_ms, (double)pt.launches / PASS_REPS, probe_ms,
+                (unsigned long long)changed_pixels(before, after, 1));
+    return 0;
+}
+
+// --particles N [--particle-half H] [--particle-near D]: particles.  A seeded cloud of N cubes of half edge H (default 1/16) is
+// scattered in front of the camera, D to 20 D units away (default 10 to 200, log-uniform) over the whole view, lit by 64 whole-sphere
+// probes that the particles share, and drawn by rt_draw_particles into a freshly drawn --width x --height frame, 20 times; with
+// N <= 4096, as a yardstick in the same process, rt_draw_boxes draws the derived boxes, 20 times.  One JSON line: the device time per
+// call (the memset and the four launches bracketed by events), the call-to-return time and the pixels drawn, of both.
+// (--particle-half 300 --particle-near 400 makes every particle wide: the worst path.)
+int run_particles(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const uint32_t n = (uint32_t)o.particles, nlights = SHARED_LIGHTS;
+    std::vector<RtParticle> particles(n);
+    std::vector<RtDrawBox> boxes(n <= 4096u ? n : 0u);            // the yardstick: rt_draw_boxes on the derived boxes
+    std::vector<RtLightProbe> probes(nlights);
+    for (uint32_t i = 0; i < n; i++) {
+        RtParticle& q = particles[i];
+        q = RtParticle{};
+        scatter_point(s.u(), s.rnd, o.particle_near, q.center);
+        q.half = o.particle_half; q.material = material_word(i); q.emission = 0xFF000000u; q.light = i % nlights;
+        if (i < boxes.size()) {
+            RtDrawBox& b = boxes[i];
+            for (int a = 0; a < 3; a++) { b.lo[a] = q.center[a] - q.half; b.hi[a] = q.center[a] + q.half; }
+            b.material = q.material; b.emission = q.emission;
+        }
+        if (i < nlights) probes[i] = sphere_probe(i, q.center);
+    }
+    std::vector<RtProbeLight> lights(nlights);
+    int rc = n ? rt_probe_light(s.ctx, &s.u(), probes.data(), n < nlights ? n : nlights, 4, 2, lights.data()) : RT_OK;
+    std::vector<RtProbeLight> face(6u * boxes.size());
+    for (size_t i = 0; i < face.size(); i++) face[i] = lights[particles[i / 6u].light];
+    const size_t npix = (size_t)o.width * (size_t)o.height;
+    std::vector<float> before(npix), after(npix);
+    if (rc == RT_OK) rc = s.read_plane(RT_BUF_DEPTH_F32, &before);
+    PassTime pt[2];
+    uint64_t drawn[2] = {0, 0};
+    for (int pass = 0; pass < (boxes.empty() ? 1 : 2) && rc == RT_OK; pass++) {     // 0: the particles, 1: their boxes
+        rc = timed_pass(s, rc, &pt[pass], [&] {
+            return pass == 0 ? rt_draw_particles(s.ctx, &s.u(), particles.data(), n, lights.data(), nlights)
+                             : rt_draw_boxes(s.ctx, &s.u(), boxes.data(), face.data(), n);
+        });
+        if (rc == RT_OK) rc = s.read_plane(RT_BUF_DEPTH_F32, &after);
+        drawn[pass] = changed_pixels(before, after, 1);
+    }
+    if (rc != RT_OK) return s.fail("particles", rc);
+    std::printf("{\"particles\": %u, \"half\": %g, \"near\": %g, \"frame\": \"%dx%d spp %d depth %d\", \"draw_particles_device_ms\": %.4f, "
+                "\"draw_particles_call_ms\": %.4f, \"pixels_drawn\": %llu",
+                n, (double)o.particle_half, (double)o.particle_near, o.width, o.height, o.spp, o.depth, pt[0].device_ms, pt[0].call_ms,
+                (unsigned long long)drawn[0]);
+    if (!boxes.empty())
+        std::printf(", \"draw_boxes_device_ms\": %.4f, \"draw_boxes_call_ms\": %.4f, \"boxes_pixels_drawn\": %llu", pt[1].device_ms, pt[1].call_ms,
+                    (unsigned long long)drawn[1]);
+    std::printf("}\n");
+    return 0;
+}
+
+// --particles N --simulate T [--sweeps S]: instead of drawing the cloud as it stands, simulate it.  The cloud's cubes become debris
+// (RtParticleState: the cube as the swept box, a seeded velocity up to 12 units per second per axis — drawn axis by axis, after that
+// particle's scatter — RT_PARTICLE_BOUNCE, gravity 32, dt 1/60, restitution 1/2, friction 3/4, S sub-sweeps per tick, default 3) in
+// device buffers.  T ticks follow each other there without a host read: a frame, then rt_step_particles_async ->
+// rt_draw_particles_async, the tick's two calls bracketed by events.  In the same process, between events of their own: the first
+// tick alone, repeated, and rt_sweep_boxes_async — the yardstick — on the same boxes with that tick's motions; and the synchronous
+// rt_sweep_boxes on those records, call to return: the host round trip a tick on the device replaces (without the upload of the
+// draw records it would also need).
+int run_simulate(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, 0u)) return 1;
+    const HipEvents hip;
+    if (!hip.ok) { std::fprintf(stderr, "--simulate needs the HIP runtime for its device buffers\n"); return 1; }
+    const uint32_t n = (uint32_t)o.particles, nlights = SHARED_LIGHTS;
+    const float half = o.particle_half;
+    const int32_t* lr = s.u().lr;
+    RtParticleStep step{};
+    step.dt = 1.0f / 60.0f; step.accel[2] = -32.0f; step.damping = 1.0f; step.restitution = 0.5f; step.friction = 0.75f; step.rest_speed = 0.5f;
+    for (int a = 0; a < 3; a++) step.lr[a] = lr[a];
+    step.sweeps = (uint32_t)o.step_sweeps;
+    // debris: --particles' scatter, every cube with a seeded velocity; and the same boxes with the first tick's motions as plain sweeps
+    std::vector<RtParticleState> states(n);
+    std::vector<RtBoxSweep> as_sweeps(n);
+    std::vector<RtLightProbe> probes(nlights);
+    for (uint32_t i = 0; i < n; i++) {
+        float c[3], mid[3];
+        scatter_point(s.u(), s.rnd, o.particle_near, c);
+        RtParticleState& p = states[i];
+        p = RtParticleState{};
+        RtBoxSweep& b = as_sweeps[i];
+        b = RtBoxSweep{};
+        for (int a = 0; a < 3; a++) {
+            p.lo[a] = b.lo[a] = c[a] - half; p.hi[a] = b.hi[a] = c[a] + half;
+            p.velocity[a] = (s.rnd() * 2.0f - 1.0f) * 12.0f;
+            const float m = (p.velocity[a] + step.accel[a] * step.dt) * step.damping * step.dt;
+            b.motion[a] = m < -64.0f ? -64.0f : (m > 64.0f ? 64.0f : m);
+            mid[a] = 0.5f * (p.lo[a] + p.hi[a]);
+        }
+        p.life = INFINITY; p.flags = RT_PARTICLE_BOUNCE; p.half = half; p.light = i % nlights;
+        p.material = material_word(i); p.emission = 0xFF000000u;
+        if (i < nlights) probes[i] = sphere_probe(i, mid);
+    }
+    std::vector<RtProbeLight> lights(nlights);
+    int rc = n ? rt_probe_light(s.ctx, &s.u(), probes.data(), n < nlights ? n : nlights, 4, 2, lights.data()) : RT_OK;
+    // the host round trip a tick on the device replaces, in part: the synchronous sweep of the same records
+    std::vector<RtSweepHit> hits(n);
+    const int reps = n >= (1u << 19) ? 5 : 20;
+    double sync_ms = 0.0;
+    for (int i = 0; i < 4 && rc == RT_OK; i++) {                  // (the first call warms the staging up)
+        const auto t = std::chrono::steady_clock::now();
+        rc = rt_sweep_boxes(s.ctx, as_sweeps.data(), n, lr, hits.data());
+        if (i > 0) sync_ms += ms_since(t) / 3.0;
+    }
+    uint64_t blocked = 0;
+    for (uint32_t i = 0; i < n; i++) blocked += hits[i].kind == RT_SWEEP_BLOCKED;
+    if (rc != RT_OK) return s.fail("simulate", rc);
+    DeviceRun run(hip, s.ctx);
+    RtParticleState* d_a = (RtParticleState*)run.on_device(states.data(), (size_t)n * sizeof(RtParticleState));
+    RtParticleState* d_b = (RtParticleState*)run.on_device(nullptr, (size_t)n * sizeof(RtParticleState));
+    const RtParticleState* d_first = (const RtParticleState*)run.on_device(states.data(), (size_t)n * sizeof(RtParticleState));
+    RtParticle* d_draw = (RtParticle*)run.on_device(nullptr, (size_t)n * sizeof(RtParticle));
+    const RtBoxSweep* d_sweeps = (const RtBoxSweep*)run.on_device(as_sweeps.data(), (size_t)n * sizeof(RtBoxSweep));
+    RtSweepHit* d_hits = (RtSweepHit*)run.on_device(nullptr, (size_t)n * sizeof(RtSweepHit));
+    const RtProbeLight* d_lights = (const RtProbeLight*)run.on_device(lights.data(), (size_t)nlights * sizeof(RtProbeLight));
+    run.start();
+    // the first tick from the initial states and the plain sweep of the same boxes and motions: the same launch repeated between two events
+    const double first_ms = run.repeat(reps, [&] { return rt_step_particles_async(s.ctx, &step, d_first, d_b, d_draw, n); });
+    const double sweep_ms = run.repeat(reps, [&] { return rt_sweep_boxes_async(s.ctx, d_sweeps, n, lr, d_hits); });
+    // T ticks chained on the device: the frame (not timed), then step -> draw between two events
+    double tick_ms = 0.0;
+    for (int t = 0; t < o.simulate && run.fine; t++) {
+        run.fine = rt_draw_frame(s.ctx, &s.u()) == RT_OK && run.mark() && rt_step_particles_async(s.ctx, &step, d_a, d_b, d_draw, n) == RT_OK &&
+                   rt_draw_particles_async(s.ctx, &s.u(), d_draw, n, d_lights, nlights) == RT_OK;
+        float ms = 0.0f;
+        run.fine = run.fine && run.lap(&ms);
+        tick_ms += (double)ms / o.simulate;
+        std::swap(d_a, d_b);
+    }
+    uint64_t alive = 0, contact = 0;
+    if (run.fine && n) {
+        run.fine = rt_sync(s.ctx) == RT_OK && hip.copy(states.data(), d_a, (size_t)n * sizeof(RtParticleState), 2 /* hipMemcpyDeviceToHost */) == 0;
+        for (const RtParticleState& p : states) { alive += !(p.flags & (RT_PSTATE_DEAD | RT_PSTATE_INVALID)); contact += (p.flags & RT_PSTATE_CONTACT) != 0; }
+    }
+    if (!run.close()) { std::fprintf(stderr, "simulate failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    std::printf("{\"particles\": %u, \"half\": %g, \"simulate\": %d, \"sweeps\": %u, \"frame\": \"%dx%d spp %d depth %d\", \"step_device_ms\": %.4f, "
+                "\"sweep_boxes_device_ms\": %.4f, \"step_over_sweep\": %.2f, \"tick_device_ms\": %.4f, \"sweep_boxes_sync_call_ms\": %.3f, "
+                "\"first_tick_blocked\": %llu, \"alive\": %llu, \"in_contact_last_tick\": %llu}\n",
+                n, (double)half, o.simulate, step.sweeps, o.width, o.height, o.spp, o.depth, first_ms, sweep_ms, sweep_ms > 0.0 ? first_ms / sweep_ms : 0.0,
+                tick_ms, sync_ms, (unsigned long long)blocked, (unsigned long long)alive, (unsigned long long)contact);
+    return 0;
+}
+
+// --models N [--model-scale S]: voxel-model entities.  One built-in 9 x 9 x 12 sparse stamp (about a third of its voxels solid; its
+// values are the generator's first) is drawn N times at scale S (default 1/8) — scattered like --boxes' boxes, in seeded
+// orientations, lit by their bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times;
+// and, as a yardstick in the same process, rt_draw_boxes draws the bounding boxes of the same records, 20 times.  One JSON line: the
+// device time of both passes, their ratio, the call-to-return time of rt_draw_stamps and the pixels drawn.
+int run_models(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const uint32_t n = (uint32_t)o.models;
+    SparseStamp stamp = sparse_stamp(s.rnd, 9, 9, 12);
+    if (!s.create_stamp(&stamp)) return 1;
+    std::vector<RtDrawStamp> models(n);
+    std::vector<RtDrawBox> boxes(n);
+    std::vector<RtLightProbe> probes(6u * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        float c[3];
+        scatter_point(s.u(), s.rnd, 20.0f, c);
+        models[i] = model_at(stamp, o.model_scale, i, c, &boxes[i]);
+        boxes[i].material = stamp.mats[0]; boxes[i].emission = models[i].emission;
+        face_probes(boxes[i], i, &probes[6u * (size_t)i]);
+    }
+    std::vector<RtProbeLight> lights(probes.size());
+    int rc = n ? rt_probe_light(s.ctx, &s.u(), probes.data(), (uint32_t)probes.size(), 4, 2, lights.data()) : RT_OK;
+    const size_t npix = (size_t)o.width * (size_t)o.height;
+    std::vector<float> before(npix), after(npix);
+    if (rc == RT_OK) rc = s.read_plane(RT_BUF_DEPTH_F32, &before);
+    PassTime pt[2];
+    uint64_t drawn[2] = {0, 0};
+    for (int pass = 0; pass < 2 && rc == RT_OK; pass++) {       // 0: the models, 1: their bounding boxes
+        rc = timed_pass(s, rc, &pt[pass], [&] {
+            return pass == 0 ? rt_draw_stamps(s.ctx, &s.u(), models.data(), lights.data(), n) : rt_draw_boxes(s.ctx, &s.u(), boxes.data(), lights.data(), n);
+        });
+        if (rc == RT_OK) rc = s.read_plane(RT_BUF_DEPTH_F32, &after);
+        drawn[pass] = changed_pixels(before, after, 1);
+    }
+    if (rc != RT_OK) return s.fail("voxel-model entities", rc);
+    std::printf("{\"models\": %u, \"model_scale\": %g, \"frame\": \"%dx%d spp %d depth %d\", \"draw_stamps_device_ms\": %.4f, "
+                "\"bounding_boxes_device_ms\": %.4f, \"ratio\": %.2f, \"draw_stamps_call_ms\": %.4f, \"draw_boxes_call_ms\": %.4f, "
+                "\"pixels_drawn\": %llu, \"bounding_box_pixels\": %llu}\n",
+                n, (double)o.model_scale, o.width, o.height, o.spp, o.depth, pt[0].device_ms, pt[1].device_ms,
+                pt[1].device_ms > 0.0 ? pt[0].device_ms / pt[1].device_ms : 0.0, pt[0].call_ms, pt[1].call_ms, (unsigned long long)drawn[0],
+                (unsigned long long)drawn[1]);
+    return 0;
+}
+
+// n seeded pixels and what they show (rt_pick_pixels): where --lights, --shadows and --light-shadows put their records
+struct Picks {
+    std::vector<int32_t> xy;
+    std::vector<RtRayHit> hits;
+};
+static int pick_pixels(Session& s, uint32_t n, Picks* out) {
+    out->xy = pixel_list(s.view, s.rnd, n);
+    out->hits.resize(n);
+    return n ? rt_pick_pixels(s.ctx, &s.u(), out->xy.data(), n, out->hits.data()) : RT_OK;
+}
+
+// --lights N: point lights.  N lights of radius 8 are scattered deterministically just off visible surfaces — rt_pick_pixels on N
+// pixels spread over the view, each light 1 to 4 units off its hit point along the face's normal (30 units along the ray where the
+// pixel shows sky) — and rt_add_lights adds them to a freshly drawn --width x --height frame, 20 times.  One JSON line: the device
+// time of the pass, the call-to-return time of rt_add_lights and the pixels lit.
+int run_lights(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const uint32_t n = (uint32_t)o.lights;
+    Picks picks;
+    int rc = pick_pixels(s, n, &picks);
+    if (rc != RT_OK) return s.fail("point lights", rc);
+    const std::vector<RtPointLight> lights = lights_off_hits(s.view, s.rnd, picks.xy, picks.hits);
+    std::vector<float> before(4u * (size_t)o.width * (size_t)o.height), after(before.size());
+    PassTime pt;
+    rc = timed_pass(s, rc, &pt, [&] { return rt_add_lights(s.ctx, &s.u(), lights.data(), n); },
+                    [&] { return s.read_plane(RT_BUF_LIGHTING_F32, &before); });
+    if (rc == RT_OK) rc = s.read_plane(RT_BUF_LIGHTING_F32, &after);
+    if (rc != RT_OK) return s.fail("point lights", rc);
+    std::printf("{\"lights\": %u, \"frame\": \"%dx%d spp %d depth %d\", \"add_lights_device_ms\": %.4f, \"add_lights_call_ms\": %.4f, "
+                "\"launches_per_call\": %.2f, \"pixels_lit\": %llu}\n",
+                n, o.width, o.height, o.spp, o.depth, pt.device_ms, pt.call_ms, (double)pt.launches / PASS_REPS,
+                (unsigned long long)changed_pixels(before, after, 4));
+    return 0;
+}
+
+// --shadows N [--shadow-models [--model-scale S]]: entity shadows.  N occluders stand 0.5 to 6 units above what N random pixels show
+// — player-sized boxes, or with --shadow-models the 9 x 9 x 12 stamp of --models at scale S in the 48 orientations in turn — and
+// rt_shadow_entities shades a freshly drawn --width x --height frame with them, 20 times.  (The stamp's values are the generator's
+// first, with or without --shadow-models; the pixels follow.)  As yardsticks in the same process rt_draw_boxes draws the same boxes
+// (the models' bounding boxes) and rt_add_lights adds as many lights (at most 1024) at the occluders' centres.  One JSON line: the
+// device time of each launch, the call-to-return time of rt_shadow_entities and the pixels it changed.
+int run_shadows(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const uint32_t n = (uint32_t)o.shadows;
+    const bool as_models = o.shadow_models;
+    SparseStamp stamp = sparse_stamp(s.rnd, 9, 9, 12);
+    if (as_models && !s.create_stamp(&stamp)) return 1;
+    Picks picks;
+    int rc = pick_pixels(s, n, &picks);
+    std::vector<RtDrawBox> boxes(n);
+    std::vector<RtDrawStamp> models(as_models ? n : 0u);
+    const uint32_t nlights = std::min(n, 1024u);
+    std::vector<RtPointLight> lights(nlights);
+    for (uint32_t i = 0; i < n && rc == RT_OK; i++) {
+        float c[3];
+        if (picks.hits[i].kind == RT_HIT_SOLID) {
+            for (int a = 0; a < 3; a++) c[a] = picks.hits[i].position[a];
+            c[2] += 0.5f + 5.5f * s.rnd();
+        } else {
+            pixel_point(s.view, &picks.xy[2u * i], 30.0f, c);
+        }
+        if (as_models) models[i] = model_at(stamp, o.model_scale, i, c, &boxes[i]);
+        else player_box(c, &boxes[i]);
+        boxes[i].material = material_word(i); boxes[i].emission = 0xFF000000u;
+        if (i < nlights) {
+            RtPointLight& l = lights[i];
+            l = RtPointLight{};
+            for (int a = 0; a < 3; a++) { l.position[a] = c[a]; l.color[a] = 20.0f; }
+            l.radius = 8.0f;
+        }
+    }
+    std::vector<float> before(4u * (size_t)o.width * (size_t)o.height), after(before.size());
+    std::vector<RtProbeLight> face(6u * (size_t)n);
+    for (RtProbeLight& f : face) { f = RtProbeLight{}; f.light[0] = f.light[1] = f.light[2] = 8.0f; }
+    PassTime pt[3];   // 0: the shadows; the yardsticks: 1 rt_draw_boxes of the same boxes, 2 rt_add_lights of as many lights
+    rc = timed_pass(s, rc, &pt[0], [&] { return rt_shadow_entities(s.ctx, &s.u(), as_models ? nullptr : boxes.data(), as_models ? 0u : n, models.data(), as_models ? n : 0u, 1.0f); },
+                    [&] { return s.read_plane(RT_BUF_LIGHTING_F32, &before); });
+    if (rc == RT_OK) rc = s.read_plane(RT_BUF_LIGHTING_F32, &after);
+    rc = timed_pass(s, rc, &pt[1], [&] { return rt_draw_boxes(s.ctx, &s.u(), boxes.data(), face.data(), n); });
+    rc = timed_pass(s, rc, &pt[2], [&] { return rt_add_lights(s.ctx, &s.u(), lights.data(), nlights); });
+    if (rc != RT_OK) return s.fail("entity shadows", rc);
+    std::printf("{\"shadows\": %u, \"shadow_models\": %d, \"model_scale\": %g, \"frame\": \"%dx%d spp %d depth %d\", \"shadow_entities_device_ms\": %.4f, "
+                "\"shadow_entities_call_ms\": %.4f, \"launches_per_call\": %.2f, \"draw_boxes_device_ms\": %.4f, \"add_lights_device_ms\": %.4f, "
+                "\"add_lights_count\": %u, \"pixels_changed\": %llu}\n",
+                n, as_models ? 1 : 0, (double)o.model_scale, o.width, o.height, o.spp, o.depth, pt[0].device_ms, pt[0].call_ms,
+                (double)pt[0].launches / PASS_REPS, pt[1].device_ms, pt[2].device_ms, nlights, (unsigned long long)changed_pixels(before, after, 4));
+    return 0;
+}
+
+// --light-shadows [--lights N] [--boxes B] [--models M]: point-light shadows of entities.  --lights' N lights (64 without --lights),
+// built first, so that the two runs light the same frame; then the models' stamp (5 x 4 x 6, at --model-scale, the 48 orientations
+// in turn), then the occluders' centres — B player-sized boxes first, the M models from index B — each within --occluder-spread
+// units (3) of a light, in turn, or, with --occluders-far, 400 units above it, where no segment of the frame passes.
+// rt_add_lights_occluded lights a freshly drawn frame with them 20 times, then rt_add_lights does as the yardstick.  One JSON line:
+// device time and call-to-return time of both, and the pixels the entities changed.
+int run_light_shadows(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const uint32_t nlights = (uint32_t)(o.lights < 0 ? 64 : o.lights), nboxes = (uint32_t)std::max(o.boxes, 0ll), nmodels = (uint32_t)std::max(o.models, 0ll);
+    Picks picks;
+    int rc = pick_pixels(s, nlights, &picks);
+    if (rc != RT_OK) return s.fail("point-light shadows", rc);
+    const std::vector<RtPointLight> lights = lights_off_hits(s.view, s.rnd, picks.xy, picks.hits);
+    SparseStamp stamp = sparse_stamp(s.rnd, 5, 4, 6);
+    if (nmodels && !s.create_stamp(&stamp)) return 1;
+    auto centre = [&](uint32_t i, float c[3]) {
+        const float* at = nlights ? lights[i % nlights].position : s.u().origin;   // (--lights 0: round the camera)
+        for (int a = 0; a < 3; a++) c[a] = at[a] + o.occluder_spread * (2.0f * s.rnd() - 1.0f);
+        if (o.occluders_far) c[2] += 400.0f;
+    };
+    std::vector<RtDrawBox> boxes(nboxes);   // (their material stays 0: a shadow has none)
+    for (uint32_t i = 0; i < nboxes; i++) {
+        float c[3];
+        centre(i, c);
+        player_box(c, &boxes[i]);
+        boxes[i].emission = 0xFF000000u;
+    }
+    std::vector<RtDrawStamp> models(nmodels);
+    for (uint32_t i = 0; i < nmodels; i++) {
+        float c[3];
+        centre(i + nboxes, c);
+        models[i] = model_at(stamp, o.model_scale, i, c, nullptr);
+    }
+    std::vector<float> plain(4u * (size_t)o.width * (size_t)o.height), shaded(plain.size());
+    PassTime pt[2];   // 0: rt_add_lights_occluded; the yardstick: 1 rt_add_lights of the same lights
+    rc = timed_pass(s, rc, &pt[0], [&] { return rt_add_lights_occluded(s.ctx, &s.u(), lights.data(), nlights, boxes.data(), nboxes, models.data(), nmodels); });
+    if (rc == RT_OK) rc = s.read_plane(RT_BUF_LIGHTING_F32, &shaded);
+    rc = timed_pass(s, rc, &pt[1], [&] { return rt_add_lights(s.ctx, &s.u(), lights.data(), nlights); });
+    if (rc == RT_OK) rc = s.read_plane(RT_BUF_LIGHTING_F32, &plain);
+    if (rc != RT_OK) return s.fail("point-light shadows", rc);
+    std::printf("{\"light_shadows\": %u, \"boxes\": %u, \"models\": %u, \"model_scale\": %g, \"spread\": %g, \"far\": %d, \"frame\": \"%dx%d spp %d depth %d\", "
+                "\"add_lights_occluded_device_ms\": %.4f, \"add_lights_occluded_call_ms\": %.4f, \"launches_per_call\": %.2f, "
+                "\"add_lights_device_ms\": %.4f, \"add_lights_call_ms\": %.4f, \"pixels_shadowed\": %llu}\n",
+                nlights, nboxes, nmodels, (double)o.model_scale, (double)o.occluder_spread, o.occluders_far ? 1 : 0, o.width, o.height, o.spp, o.depth,
+                pt[0].device_ms, pt[0].call_ms, (double)pt[0].launches / PASS_REPS, pt[1].device_ms, pt[1].call_ms,
+                (unsigned long long)changed_pixels(plain, shaded, 4));
+    return 0;
+}
+
+}  // namespace bench
