@@ -1139,6 +1139,92 @@ int rt_trace_entities_async(RtContext* ctx, const RtRay* rays_dev, uint32_t coun
 int rt_pick_entities(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint32_t count, const RtDrawBox* boxes, uint32_t nboxes,
                      const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits, RtEntityHit* entity_hits);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Entity sweeps: rt_sweep_boxes' box swept against the resident world
+ * AND the entities a host draws, so that what is drawn is solid too — a player stands on the moving platform and stops at the door
+ * that rt_draw_stamps shows, mobs drawn by rt_draw_boxes do not walk through one another, a projectile box meets the mob and not only
+ * the voxels behind it.  The calls take rt_sweep_boxes' sweeps and the records of rt_draw_boxes and rt_draw_stamps.  One answer about
+ * the entities, five 16-byte words, 80 bytes: */
+typedef struct RtEntitySweepHit {     /* 80 bytes */
+    float    t;  uint32_t kind;  uint32_t normal;  uint32_t material;   /*  0  fraction travelled; RT_SWEEP_*; face code; the box's material
+                                                                                word or the cell's voxel word                             */
+    uint32_t entity, index, axis, voxel;     /* 16  RT_ENTITY_NONE / BOX / MODEL; index into boxes / models; blocked axis 0..2, else 3;
+                                                    MODEL: the cell's voxel index in the stamp's own arrays (rt_stamp_read's layout)      */
+    int32_t  cell[3];  uint32_t reserved0;   /* 32  MODEL: the placed-local cell c; otherwise (-1, -1, -1)                               */
+    float    lo[3];    uint32_t reserved1;   /* 48  the box where the COMBINED sweep ended: the next sweep's box                         */
+    float    hi[3];    uint32_t reserved2;   /* 64  (the reserved words are written as 0)                                                */
+} RtEntitySweepHit;
+/* The rules.  All arithmetic is fp32 with one rounding per operation; fused operations appear only where rtm_fma is written; any
+ * comparison with a NaN is false.  Results are reproduced bit for bit by tests/sweep_entities_ref.py, which tests every box and every
+ * SOLID cell of every model against every sweep (DESIGN.md "Entity sweeps").
+ *   World part: world_hits[i] (where the pointer is not NULL) is exactly what rt_sweep_boxes writes for the same record, `lr` and
+ *     region, every field, bit for bit: W.  The validated domain of a sweep is rt_sweep_boxes'.  The entity part is the same with
+ *     world_hits NULL.
+ *   Self exemption: in these calls RtBoxSweep.reserved0 is read: a value s in 1..nboxes makes the sweep ignore box s - 1, any other
+ *     value ignores none.  reserved1 does the same for models.  A mob swept against the list that holds its own box needs this:
+ *     without it every mob is EMBEDDED in itself.  reserved2 stays ignored.
+ *   One obstacle box O = [olo, ohi] against the sweep (lo, hi, motion m).  A box b is an obstacle iff it is valid by rt_draw_boxes'
+ *     rule; the device skips an invalid box, rt_sweep_entities also rejects the whole call.  Per axis k the sweep overlaps O at the
+ *     start iff lo_k < ohi_k && olo_k < hi_k: strict, touching is not overlap.  Moving + (m_k > 0): te_k = (olo_k - hi_k) / m_k and
+ *     tx_k = (ohi_k - lo_k) / m_k; moving - (m_k < 0): te_k = (ohi_k - lo_k) / m_k and tx_k = (olo_k - hi_k) / m_k; each is one
+ *     subtraction and one IEEE division.  An axis with m_k == 0 (either sign) is not moving and has no times.  O EMBEDS the sweep iff
+ *     every axis overlaps at the start.  Otherwise let a be the moving axis with the largest te_k, the HIGHEST axis on equal values:
+ *     O BLOCKS at t = te_a on axis a iff every axis that is not moving overlaps at the start, te_a >= 0, te_a < 1, and te_a < tx_k on
+ *     every moving axis.  This is the world's event order restated per obstacle — trailing events come before leading events at equal
+ *     t, then the order is x, y, z — so a corner met exactly blocks on the later axis and a face that is only touched does not catch:
+ *     with every occupied voxel v taken as the box [v, v + 1] the rule gives rt_sweep_boxes' kind, t, axis and voxel.
+ *   One model: a valid record by rt_draw_stamps' rule, with its planes: plane_k(i) = rtm_fma(float(i), scale, origin_k), i = 0..E'_k.
+ *     Placed-local cell c is the obstacle box [plane_k(c_k), plane_k(c_k + 1)] and exists iff the stamp voxel it shows has state
+ *     RT_STAMP_SOLID; a cell with two equal planes on some axis (far from the origin rounding merges planes) is absent.  A model is
+ *     nothing but its cells under the obstacle rule.  Within one model the blocking cell is the one with the smallest t, then the
+ *     lowest blocked axis, then the first in ascending (z, y, x) order of c; a model embeds iff some cell does, and reports the first
+ *     such cell in that order.
+ *   Entity part: EMBEDDED beats BLOCKED: the first embedding obstacle in the order boxes by index, then models by index.  Otherwise the
+ *     smallest t; on equal t boxes come before models, and within a kind the lowest index wins.  The t reported is the winner's own
+ *     te_a, bit for bit (0 / m_a is -0 for a touching start moving -: it compares equal to 0 and stays -0, as in rt_sweep_boxes).
+ *   What is reported.  W is INVALID: kind = RT_SWEEP_INVALID, t = 0, the rest as for "nothing" below, lo / hi = the input bits.  The
+ *     entity part is EMBEDDED: reported whatever W is: kind = RT_SWEEP_EMBEDDED, t = 0, axis = 3, normal = 6, lo / hi = the input bits.
+ *     The entity part is BLOCKED at t_e: reported iff W is FREE or BLOCKED and t_e < W.t: strict, the world wins ties.  A reported
+ *     record holds entity = RT_ENTITY_BOX or RT_ENTITY_MODEL, index, material = the box's material word or the cell's voxel word; for a
+ *     model cell = c and voxel = the index of the stamp voxel the cell shows; for a box cell = (-1, -1, -1) and voxel = 0xFFFFFFFF.
+ *     Nothing reported: kind = RT_SWEEP_FREE, entity = RT_ENTITY_NONE, index = 0xFFFFFFFF, t = 1, axis = 3, normal = 6, material = 0,
+ *     voxel = 0xFFFFFFFF, cell = (-1, -1, -1), lo / hi = W's returned lo / hi — also when W is BLOCKED or EMBEDDED: the world's own
+ *     answer is world_hits'.  In every case entity_hits[i].lo / hi is the next sweep's box.  Every byte of every record is written.
+ *   Returned box of a reported block: rt_sweep_boxes' "Returned box" rule at t = t_e, with the cell ranges c as they stand after every
+ *     world event with time < t_e (none of them blocked, because t_e < W.t).  On the blocked axis a, with F the obstacle's near face
+ *     (olo_a moving +, ohi_a moving -; for a cell the plane) and size = hi_a - lo_a: moving + hi' = F, lo' = max(F - size,
+ *     float(c.lo_a)); moving - lo' = F, hi' = min(F + size, float(c.hi_a + 1)).  normal = 2 a + 1 moving +, 2 a moving -.  The clamps
+ *     close the contract against the world: the returned box, swept again on an unchanged world, is never world-EMBEDDED.  Against
+ *     the entities only the blocker is covered: the snapped face touches it and does not overlap it, but the rounding of the other
+ *     axes may graze a second entity.  Entities move between calls, so a host handles entity-EMBEDDED in any case.
+ *   Limits: count <= 2^24; nboxes, nmodels <= 4096.
+ *   Ordering and side effects: rt_trace_entities' — on the query stream behind the earlier world changes, not behind frames; later
+ *     world changes wait for it; after rt_set_stream(non-NULL) on the caller's stream, in order.  No plane, prepass, accumulation sum,
+ *     history, RtCounters or RtTiming changes.  The call names its stamps as a draw does: rt_stamp_destroy after an enqueued call
+ *     waits for it, and the call itself waits on the device for an earlier rt_stamp_capture, so a stamp captured a moment ago can be
+ *     swept against with no host sync in between.
+ *   Errors, all checked before anything is enqueued (a rejected call changes nothing, outputs included): NULL ctx; NULL sweeps / lr /
+ *     entity_hits with count > 0; a NULL entity array with its count above 0; count > 2^24; nboxes or nmodels above 4096; a model
+ *     record that is not valid; in the synchronous call a sweep outside the validated domain or a box that is not valid (the
+ *     asynchronous call cannot read device records: the device answers RT_SWEEP_INVALID and skips an invalid box); in the
+ *     asynchronous call a device pointer that fails rt_trace_rays_async's test: RT_ERR_INVALID_ARG.  No world resident:
+ *     RT_ERR_NOT_READY.  count == 0: RT_OK, nothing enqueued.  Every RtKernel and every region size answers the same.
+ *   Device work per call: one transfer of a 64-byte record per model and one launch, one lane per sweep.  A wave of 64 consecutive
+ *     sweeps culls the entities against the bounds of its sweeps 64 at a time; a lane tests a surviving box once and a surviving
+ *     model once per cell of the part its own swept hull reaches.  Sweeps that lie together belong in consecutive order.  Worst case:
+ *     a tiny-scale model under a large box — scale 2^-8 under an 8-unit box puts up to 256^2 cells in every layer the sweep crosses,
+ *     and 256 layers; keep collision models coarse.
+ *   Out of scope: entities are no obstacles of rt_step_particles; entities do not move against one another during the call (every
+ *     obstacle stands still for the sweep); entities are not rotated; there is no acceleration structure over entities.
+ * Host pointers; returns when the hits are in host memory.  world_hits may be NULL. */
+int rt_sweep_entities(RtContext* ctx, const RtBoxSweep* sweeps, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes, uint32_t nboxes,
+                      const RtDrawStamp* models, uint32_t nmodels, RtSweepHit* world_hits, RtEntitySweepHit* entity_hits);
+/* Same, enqueued.  sweeps_dev, boxes_dev, world_hits_dev (may be NULL) and entity_hits_dev are device memory and must pass
+ * rt_trace_rays_async's test; `models` is a HOST pointer, as for rt_trace_entities_async and for the same reason, and is free again
+ * when the call returns. */
+int rt_sweep_entities_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes_dev,
+                            uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels, RtSweepHit* world_hits_dev,
+                            RtEntitySweepHit* entity_hits_dev);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Terrain generated on the device: the project's deterministic
  * procedural world (raytrace_amd/host/world.cpp: generate_chunk + pack_into per world chunk, MATERIALS[id].pack()) written straight
  * into the resident region, byte for byte what the host generator assembles — no host bytes, no staging, no transfer.
@@ -1391,7 +1477,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtParticle, rt_draw_particles, rt_draw_particles_async (particles: up to 2^20 small cubes
  *        composited into the G-buffer by depth, binned to the tiles they cover).
  *        Additive, same minor version: RtParticleState, RtParticleStep, RT_PARTICLE_*, RT_PSTATE_*, rt_step_particles, rt_step_particles_async
- *        (particle simulation: a tick of integration, sub-sweeps, contact response and ageing on the device). */
+ *        (particle simulation: a tick of integration, sub-sweeps, contact response and ageing on the device).
+ *        Additive, same minor version: RtEntitySweepHit, rt_sweep_entities, rt_sweep_entities_async (entity sweeps: box sweeps that
+ *        collide with the drawn boxes and models as well as with the world). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -55,6 +55,8 @@ AMD_FUNCTIONS = {
     "rt_trace_entities": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     "rt_trace_entities_async": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     "rt_pick_entities": (INT, [P, UNI, P, U32, P, U32, P, U32, P, P]),
+    "rt_sweep_entities": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
+    "rt_sweep_entities_async": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     # the frame and the passes over it
     "rt_draw_frame": (INT, [P, UNI]),
     "rt_draw_boxes": (INT, [P, UNI, P, P, U32]),

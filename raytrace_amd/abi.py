@@ -284,6 +284,21 @@ assert (RtEntityHit.t.offset, RtEntityHit.kind.offset, RtEntityHit.material.offs
 MAX_ENTITY_RAYS = 1 << 24   # rt_trace_entities / rt_pick_entities: rays or pixels per call
 
 
+class RtEntitySweepHit(C.Structure):
+    """rt_sweep_entities result (ABI 1.3, additive: entity sweeps): 80 bytes."""
+    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("normal", C.c_uint32), ("material", C.c_uint32),
+                ("entity", C.c_uint32), ("index", C.c_uint32), ("axis", C.c_uint32), ("voxel", C.c_uint32),
+                ("cell", C.c_int32 * 3), ("reserved0", C.c_uint32), ("lo", C.c_float * 3), ("reserved1", C.c_uint32),
+                ("hi", C.c_float * 3), ("reserved2", C.c_uint32)]
+
+
+assert C.sizeof(RtEntitySweepHit) == 80
+assert (RtEntitySweepHit.entity.offset, RtEntitySweepHit.voxel.offset, RtEntitySweepHit.cell.offset, RtEntitySweepHit.lo.offset,
+        RtEntitySweepHit.hi.offset) == (16, 28, 32, 48, 64)
+ENTITY_SWEEP_HIT_DTYPE = np.dtype(RtEntitySweepHit)   # the numpy view of the record
+MAX_ENTITY_SWEEPS = 1 << 24   # rt_sweep_entities: sweeps per call
+
+
 class RtPointLight(C.Structure):
     """rt_add_lights input (ABI 1.3, additive: point lights): 32 bytes; `reserved` must be 0."""
     _fields_ = [("position", C.c_float * 3), ("radius", C.c_float), ("color", C.c_float * 3), ("reserved", C.c_uint32)]

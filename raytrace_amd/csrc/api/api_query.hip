@@ -1,9 +1,10 @@
 // api_query.hip — queries against the resident world: ray queries (rt_trace_rays, rt_trace_rays_async, rt_pick_pixels), light
 // probes (rt_probe_light, rt_probe_light_async), box sweeps (rt_sweep_boxes, rt_sweep_boxes_async), the particle simulation built on
 // them (rt_step_particles, rt_step_particles_async) and entity queries (rt_trace_entities, rt_trace_entities_async,
-// rt_pick_entities), which share their checks, stream and staging.
+// rt_pick_entities) and entity sweeps (rt_sweep_entities, rt_sweep_entities_async), which share their checks, stream and staging.
 #include "entity_query_check.hpp"
 #include "particle_step_check.hpp"
+#include "sweep_entities_check.hpp"
 #include "rt_context.hpp"
 
 using namespace rta;
@@ -264,6 +265,42 @@ int entity_sync(RtContext* c, const rtd::Frame& f, const void* in, size_t in_byt
     }
     return fetch_sync(c, st, dev[3], entity_hits, out_bytes);
 }
+
+// ---- entity sweeps: device sweeps and boxes, host models as rt_draw_stamps'; the entity queries' stream, staging and waits ----------
+// checks shared by the two calls; RT_OK when there is work to enqueue, 1 for count == 0
+int sweep_entities_check(RtContext* c, const char* fn, uint32_t count, const void* sweeps, const void* lr, const void* entity_hits, const void* boxes,
+                         uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels) {
+    const char* e = sweep_entities_args_error(count, sweeps, lr, entity_hits, boxes, nboxes, models, nmodels);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e);
+    if (count == 0) return 1;
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    return models_check(c, fn, models, nmodels, "nothing was answered");
+}
+
+// entity_launch's steps with the sweep kernel in place of the query kernel.
+int sweep_entities_launch(RtContext* c, hipStream_t st, const int32_t lr[3], const void* sweeps_dev, uint32_t count, const void* boxes_dev,
+                          uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels, void* world_dev, void* entity_dev) {
+    rtd::SweepEntitiesArgs a;
+    a.sweeps = reinterpret_cast<const uint4*>(sweeps_dev);
+    a.world_hits = reinterpret_cast<uint4*>(world_dev);
+    a.entity_hits = reinterpret_cast<uint4*>(entity_dev);
+    a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
+    a.recs = nullptr;
+    a.count = count; a.nboxes = nboxes; a.nmodels = nmodels;
+    for (int k = 0; k < 3; k++) a.lr[k] = lr[k];
+    StagingSet* s = nullptr;
+    if (nmodels > 0u) {
+        uint8_t* recs;
+        const int rc = upload_models(c, models, nmodels, nullptr, 0u, st, &s, &recs);
+        if (rc != RT_OK) return rc;
+        a.recs = reinterpret_cast<const uint4*>(recs);
+        RT_HIP(c, c->ev_capture.wait_elsewhere(st));   // (the launch follows the latest rt_stamp_capture, as entity_launch's does)
+    }
+    RT_HIP(c, rtd::launch_sweep_entities(scene_of(c), c->logr, a, st));
+    if (s) RT_HIP(c, s->ev_applied.record(st));
+    if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
+    return RT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -446,6 +483,51 @@ int rt_pick_entities(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uin
     const uint32_t bad = first_invalid_draw_box(boxes, nboxes);
     if (bad != nboxes) return fail(ctx, RT_ERR_INVALID_ARG, "rt_pick_entities: box " + std::to_string(bad) + " is not a valid box");
     return entity_sync(ctx, frame_of(ctx, u), xy, (size_t)count * 8u, true, count, boxes, nboxes, models, nmodels, world_hits, entity_hits);
+}
+
+int rt_sweep_entities(RtContext* ctx, const RtBoxSweep* sweeps, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes, uint32_t nboxes,
+                      const RtDrawStamp* models, uint32_t nmodels, RtSweepHit* world_hits, RtEntitySweepHit* entity_hits) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = sweep_entities_check(ctx, "rt_sweep_entities", count, sweeps, lr, entity_hits, boxes, nboxes, models, nmodels);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    uint32_t bad = first_invalid_entity_sweep(sweeps, count);
+    if (bad != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_sweep_entities: sweep " + std::to_string(bad) + " is outside the validated domain");
+    bad = first_invalid_draw_box(boxes, nboxes);
+    if (bad != nboxes) return fail(ctx, RT_ERR_INVALID_ARG, "rt_sweep_entities: box " + std::to_string(bad) + " is not a valid box");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    // sweeps, boxes and both outputs through one staging block, the launch, one or two blocks back
+    const size_t world_bytes = world_hits ? (size_t)count * sizeof(RtSweepHit) : 0u, entity_bytes = (size_t)count * sizeof(RtEntitySweepHit);
+    uint8_t* dev[4];
+    rc = stage_sync(ctx, st, {{sweeps, (size_t)count * sizeof(RtBoxSweep)}, {nboxes ? boxes : nullptr, (size_t)nboxes * sizeof(RtDrawBox)},
+                              {nullptr, world_bytes}, {nullptr, entity_bytes}}, dev);
+    if (rc != RT_OK) return rc;
+    rc = sweep_entities_launch(ctx, st, lr, dev[0], count, nboxes ? dev[1] : nullptr, nboxes, models, nmodels, world_hits ? dev[2] : nullptr, dev[3]);
+    if (rc != RT_OK) return rc;
+    if (world_hits) {
+        rc = fetch_sync(ctx, st, dev[2], world_hits, world_bytes);
+        if (rc != RT_OK) return rc;
+    }
+    return fetch_sync(ctx, st, dev[3], entity_hits, entity_bytes);
+}
+
+int rt_sweep_entities_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes_dev,
+                            uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels, RtSweepHit* world_hits_dev,
+                            RtEntitySweepHit* entity_hits_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = sweep_entities_check(ctx, "rt_sweep_entities_async", count, sweeps_dev, lr, entity_hits_dev, boxes_dev, nboxes, models, nmodels);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, sweeps_dev) || !query_device_ptr(ctx, entity_hits_dev) || (nboxes > 0u && !query_device_ptr(ctx, boxes_dev)) ||
+        (world_hits_dev && !query_device_ptr(ctx, world_hits_dev)))
+        return fail(ctx, RT_ERR_INVALID_ARG,
+                    "rt_sweep_entities_async: sweeps, boxes and both hits must be 16-byte aligned memory of the context's device");
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    return sweep_entities_launch(ctx, st, lr, sweeps_dev, count, nboxes ? boxes_dev : nullptr, nboxes, models, nmodels, world_hits_dev,
+                                 entity_hits_dev);
 }
 
 }  // extern "C"

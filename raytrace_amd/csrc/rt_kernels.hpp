@@ -322,6 +322,19 @@ struct EntityQueryArgs {
 };
 hipError_t launch_entity_query(const Scene& sc, const Frame& f, const EntityQueryArgs& a, hipStream_t st);
 
+// rt_sweep_entities.hip: box sweeps against the region and the drawn entities (rt_sweep_entities).  One launch, one lane per sweep:
+// the world's hit as rt_sweep.hip finds it, then the first box or model cell that embeds or blocks the sweep before the world does.
+struct SweepEntitiesArgs {
+    const uint4* sweeps;  // RtBoxSweep[count] (three uint4 each); reserved0 / reserved1 name the box / model the sweep ignores, plus 1
+    uint4* world_hits;    // RtSweepHit[count] (four uint4 each), or null
+    uint4* entity_hits;   // RtEntitySweepHit[count] (five uint4 each)
+    const uint4* boxes;   // RtDrawBox[nboxes] (two uint4 each); an invalid box is skipped
+    const uint4* recs;    // DrawStampRecord[nmodels] (api/draw_stamps.hpp; four uint4 each), resolved and validated on the host
+    uint32_t count, nboxes, nmodels;
+    int32_t lr[3];
+};
+hipError_t launch_sweep_entities(const Scene& sc, int logr, const SweepEntitiesArgs& a, hipStream_t st);
+
 // rt_temporal.hip: RT_FLAG_REPROJECT's pass over a one-sample whole-frame (it replaces launch_accumulate_frame there)
 // (TEMPORAL_MOVED_BOXES: a moved frame after rt_edit_voxels on a context with RtConfig.edit_radius > 0 — pixels near an edited box
 // or in its sun shadow restart, the others go on as in TEMPORAL_MOVED)

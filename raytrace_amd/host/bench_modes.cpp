@@ -126,6 +126,89 @@ int run_entity_rays(const Options& o, const World& w) {
     return 0;
 }
 
+// --entity-sweeps N [--coherent] [--boxes B] [--models M] [--model-scale S]: entity sweeps.  B boxes and M models scattered as
+// --entity-rays scatters them; N player-sized sweeps, each beside one of the entities (or, without entities, at a scattered point of
+// its own) and moving up to 2 units per axis.  With --coherent sweep i stands beside entity i * (B + M) / N, so a wave's 64 sweeps
+// lie together; without it the same sweeps are handed over in a seeded shuffle.  rt_sweep_entities and, as the yardstick,
+// rt_sweep_boxes on the same records, both timed call to return; then their asynchronous twins on device copies, between two HIP
+// events: the device time of each.  The JSON line also counts what the entities and the world blocked.  (The kernels alone,
+// k_sweep_entities and k_sweep: rocprofv3 --kernel-trace --stats, which tools/sweep_entities_profile.py runs.)
+int run_entity_sweeps(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, 0u)) return 1;
+    const uint32_t n = (uint32_t)o.entity_sweeps, nboxes = (uint32_t)std::max(o.boxes, 0ll), nmodels = (uint32_t)std::max(o.models, 0ll);
+    const uint32_t nent = nboxes + nmodels;
+    SparseStamp stamp = sparse_stamp(s.rnd, 9, 9, 12);
+    if (!s.create_stamp(&stamp)) return 1;
+    std::vector<RtDrawBox> boxes(nboxes);
+    std::vector<RtDrawStamp> models(nmodels);
+    std::vector<float> centres(3u * (size_t)nent);
+    for (uint32_t i = 0; i < nent; i++) {
+        float* c = &centres[3u * (size_t)i];
+        scatter_point(s.u(), s.rnd, 20.0f, c);   // 20 .. 400 units away
+        if (i < nboxes) {
+            player_box(c, &boxes[i]);
+            boxes[i].material = 0x12345u; boxes[i].emission = 0xFF000000u;
+        } else {
+            models[i - nboxes] = model_at(stamp, o.model_scale, i, c, nullptr);
+        }
+    }
+    std::vector<RtBoxSweep> sweeps(n);
+    for (uint32_t i = 0; i < n; i++) {
+        float c[3];
+        if (nent) { const float* e = &centres[3u * (size_t)((uint64_t)i * nent / n)]; for (int a = 0; a < 3; a++) c[a] = e[a] + (s.rnd() * 2.0f - 1.0f) * 3.0f; }
+        else scatter_point(s.u(), s.rnd, 20.0f, c);
+        RtDrawBox b{};
+        player_box(c, &b);
+        RtBoxSweep& sw = sweeps[i];
+        sw = RtBoxSweep{};
+        for (int a = 0; a < 3; a++) { sw.lo[a] = b.lo[a]; sw.hi[a] = b.hi[a]; sw.motion[a] = (s.rnd() * 2.0f - 1.0f) * 2.0f; }
+    }
+    if (!o.coherent)
+        for (uint32_t i = n; i > 1; i--) std::swap(sweeps[i - 1], sweeps[std::min(i - 1, (uint32_t)(s.rnd() * (float)i))]);
+    const int32_t* lr = s.u().lr;
+    std::vector<RtSweepHit> world(n), plain(n);
+    std::vector<RtEntitySweepHit> hits(n);
+    const int reps = n >= (1u << 19) ? 5 : 20;
+    double ms[2] = {0.0, 0.0};
+    int rc = RT_OK;
+    for (int which = 0; which < 2 && rc == RT_OK; which++) {      // 0: rt_sweep_entities, 1: rt_sweep_boxes on the same records, the yardstick
+        for (int i = 0; i < reps + 1 && rc == RT_OK; i++) {       // (the first repetition warms the staging up)
+            const auto t = std::chrono::steady_clock::now();
+            rc = which == 0 ? rt_sweep_entities(s.ctx, sweeps.data(), n, lr, boxes.data(), nboxes, models.data(), nmodels, world.data(), hits.data())
+                            : rt_sweep_boxes(s.ctx, sweeps.data(), n, lr, plain.data());
+            if (i > 0) ms[which] += ms_since(t) / reps;
+        }
+    }
+    if (rc != RT_OK) return s.fail("entity sweeps", rc);
+    if (std::memcmp(world.data(), plain.data(), (size_t)n * sizeof(RtSweepHit)) != 0) { std::fprintf(stderr, "the world hits differ from rt_sweep_boxes'\n"); return 1; }
+    uint64_t by_entity = 0, embedded = 0, by_world = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        by_entity += hits[i].kind == RT_SWEEP_BLOCKED; embedded += hits[i].kind == RT_SWEEP_EMBEDDED;
+        by_world += hits[i].entity == RT_ENTITY_NONE && world[i].kind == RT_SWEEP_BLOCKED;
+    }
+    // device time of each call: the asynchronous twins between two events (-1: the HIP runtime could not be reached from here)
+    double device_ms[2] = {-1.0, -1.0};
+    const HipEvents hip;
+    if (hip.ok) {
+        DeviceRun run(hip, s.ctx);
+        const RtBoxSweep* d_sweeps = (const RtBoxSweep*)run.on_device(sweeps.data(), (size_t)n * sizeof(RtBoxSweep));
+        const RtDrawBox* d_boxes = (const RtDrawBox*)run.on_device(boxes.data(), (size_t)nboxes * sizeof(RtDrawBox));
+        RtSweepHit* d_world = (RtSweepHit*)run.on_device(nullptr, (size_t)n * sizeof(RtSweepHit));
+        RtEntitySweepHit* d_hits = (RtEntitySweepHit*)run.on_device(nullptr, (size_t)n * sizeof(RtEntitySweepHit));
+        run.start();
+        device_ms[0] = run.repeat(reps, [&] { return rt_sweep_entities_async(s.ctx, d_sweeps, n, lr, nboxes ? d_boxes : nullptr, nboxes, models.data(), nmodels, d_world, d_hits); });
+        device_ms[1] = run.repeat(reps, [&] { return rt_sweep_boxes_async(s.ctx, d_sweeps, n, lr, d_world); });
+        if (!run.close()) { std::fprintf(stderr, "timing the asynchronous calls failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    }
+    std::printf("{\"entity_sweeps\": %u, \"coherent\": %s, \"boxes\": %u, \"models\": %u, \"model_scale\": %g, \"sweep_entities_call_ms\": %.4f, "
+                "\"sweep_boxes_call_ms\": %.4f, \"ratio\": %.2f, \"blocked_by_entity\": %llu, \"embedded_in_entity\": %llu, \"blocked_by_world\": %llu, "
+                "\"sweep_entities_device_ms\": %.4f, \"sweep_boxes_device_ms\": %.4f}\n",
+                n, o.coherent ? "true" : "false", nboxes, nmodels, (double)o.model_scale, ms[0], ms[1], ms[1] > 0.0 ? ms[0] / ms[1] : 0.0,
+                (unsigned long long)by_entity, (unsigned long long)embedded, (unsigned long long)by_world, device_ms[0], device_ms[1]);
+    return 0;
+}
+
 // --boxes N: entity boxes.  N entity-sized boxes are scattered deterministically in front of the camera (20 to 400 units away, over
 // the whole view), their six face probes lit with rt_probe_light (4 samples, depth 2), and rt_draw_boxes composites them into a
 // freshly drawn --width x --height frame, 20 times.  One JSON line: the device time of the pass, the call-to-return time of

@@ -23,7 +23,7 @@ struct Options {
     int edits = 0, edit_radius = 0;
     const char* edit_shape = nullptr;
     int edit_stamp = -1;
-    long long entity_rays = 0;
+    long long entity_rays = 0, entity_sweeps = 0;
     bool coherent = false;
     long long rays = 0, boxes = -1, lights = -1, models = -1, shadows = -1, particles = -1;
     float particle_half = 0.0625f, particle_near = 10.0f;
@@ -46,6 +46,7 @@ struct World {
 // the modes that run instead of the frame loop (bench_modes.cpp); each prints one JSON line and returns the exit code
 int run_rays(const Options& o, const World& w);
 int run_entity_rays(const Options& o, const World& w);
+int run_entity_sweeps(const Options& o, const World& w);
 int run_boxes(const Options& o, const World& w);
 int run_particles(const Options& o, const World& w);
 int run_simulate(const Options& o, const World& w);
@@ -135,7 +136,7 @@ inline uint64_t changed_pixels(const std::vector<float>& a, const std::vector<fl
     return n;
 }
 
-// The few HIP runtime calls --entity-rays and --simulate need to time asynchronous calls with an event pair, taken from the runtime the
+// The few HIP runtime calls --entity-rays, --entity-sweeps and --simulate need to time asynchronous calls with an event pair, taken from the runtime the
 // library itself runs on (this program is plain C++ and includes no HIP header).  ok == false: no device times.
 struct HipEvents {
     typedef int (*malloc_t)(void**, size_t);

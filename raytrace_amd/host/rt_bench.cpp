@@ -15,6 +15,7 @@
 //            [--boxes N]
 //            [--particles N [--particle-half H] [--particle-near D] [--simulate T [--sweeps S]]]
 //            [--entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]]
+//            [--entity-sweeps N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--lights N] [--shadows N [--shadow-models]]
 //            [--light-shadows [--lights N] [--boxes B] [--models M] [--occluder-spread S] [--occluders-far]]
 //
@@ -66,7 +67,7 @@
 // only the pixels near the occupied voxels that left or arrived or in their sun shadow.  The JSON line's acc_frames / samples
 // (rt_get_accumulation) show whether the history went on.
 //
-// Instead of the frame loop, in this order of precedence: --light-shadows, --entity-rays N, --rays N, --particles N --simulate T,
+// Instead of the frame loop, in this order of precedence: --light-shadows, --entity-rays N, --entity-sweeps N, --rays N, --particles N --simulate T,
 // --particles N, --boxes N, --models N, --shadows N, --lights N (bench_modes.cpp).
 #include <algorithm>
 #include <atomic>
@@ -258,6 +259,7 @@ int parse_options(int argc, char** argv, Options& o, std::vector<const char*>& p
         else if (is("--stream-history")) o.stream_history = true;
         else if (want("--rays")) o.rays = std::atoll(argv[++i]);
         else if (want("--entity-rays")) o.entity_rays = std::atoll(argv[++i]);
+        else if (want("--entity-sweeps")) o.entity_sweeps = std::atoll(argv[++i]);
         else if (is("--coherent")) o.coherent = true;
         else if (is("--rays-coherent")) o.rays_coherent = true;
         else if (want("--boxes")) o.boxes = std::atoll(argv[++i]);
@@ -285,6 +287,7 @@ int parse_options(int argc, char** argv, Options& o, std::vector<const char*>& p
     if (o.stream_history && (!o.stream || !o.reproject || o.edit_radius == 0)) return bad("--stream-history goes with --stream --reproject --edit-radius N");
     if (o.rays < 0 || o.rays > (1ll << 26)) return bad("--rays must be in 0..2^26");
     if (o.entity_rays < 0 || o.entity_rays > (1ll << 24)) return bad("--entity-rays must be in 0..2^24");
+    if (o.entity_sweeps < 0 || o.entity_sweeps > (1ll << 24)) return bad("--entity-sweeps must be in 0..2^24");
     if (o.boxes < -1 || o.boxes > 4096) return bad("--boxes must be in 0..4096");
     if (o.simulate < 0 || o.simulate > 100000 || o.step_sweeps < 1 || o.step_sweeps > 4 || (o.simulate > 0 && (o.particles < 0 || o.particle_half > 4.0f)))
         return bad("--simulate must be in 0..100000 and goes with --particles (--particle-half at most 4), --sweeps in 1..4");
@@ -337,6 +340,7 @@ int main(int argc, char** argv) {
     const World world{game, noise};
     if (o.light_shadows) return run_light_shadows(o, world);
     if (o.entity_rays > 0) return run_entity_rays(o, world);
+    if (o.entity_sweeps > 0) return run_entity_sweeps(o, world);
     if (o.rays > 0) return run_rays(o, world);
     if (o.particles >= 0 && o.simulate > 0) return run_simulate(o, world);
     if (o.particles >= 0) return run_particles(o, world);

@@ -13,7 +13,7 @@ import math
 import numpy as np
 
 from . import _lib, abi
-from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_DRAW_BOXES, MAX_DRAW_STAMPS, MAX_ENTITY_RAYS, MAX_PARTICLE_LIGHTS, MAX_PARTICLES, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
+from .abi import (BUFFER_FORMATS, BUFFER_NAMES, MAX_ENTITY_SWEEPS, MAX_DRAW_BOXES, MAX_DRAW_STAMPS, MAX_ENTITY_RAYS, MAX_PARTICLE_LIGHTS, MAX_PARTICLES, MAX_POINT_LIGHTS, RT_BUF_COUNT, RT_BUF_FINAL_BGRA8, RT_KERNEL_DEFAULT, RT_SHAPE_BOX, RT_SHAPE_SPHERE,
                   RT_SWEEP_BLOCKED, RT_SWEEP_FREE, RT_WHERE_ALL, RtBoxSweep, RtConfig, RtCounters, RtDenoiseParams, RtDrawBox, RtDrawStamp, RtEntityHit, RtInfo, RtLightProbe,
                   RtPointLight, RtProbeLight, RtRayHit, RtShapeEdit, RtStampPlace, RtSweepHit, RtTiming, RtUniforms, RtVoxelEdit)
 
@@ -490,6 +490,59 @@ class Context:
                 break
             m = m * (np.float32(1.0) - h["t"])
             m[int(h["axis"])] = 0
+            if not m.any():
+                break
+        return lo, hi, hits
+
+    # -- entity sweeps -----------------------------------------------------------------------------------
+    def sweep_entities(self, sweeps, lr=(0, 0, 0), boxes=None, models=None, world=True):
+        """rt_sweep_entities: `sweeps` as for sweep_boxes (SWEEP_DTYPE records carry the self exemption: reserved0 = 1 + the index of
+        the box a sweep ignores, reserved1 likewise for models) against the resident world and the drawn `boxes` (DRAW_BOX_DTYPE[B]) and
+        `models` (DRAW_STAMP_DTYPE[M]) -> (world_hits SWEEP_HIT_DTYPE[N] — what sweep_boxes returns; None with world=False —,
+        entity_hits abi.ENTITY_SWEEP_HIT_DTYPE[N]).  Synchronous; an invalid record fails the whole call (RtError, INVALID_ARG)."""
+        recs = make_sweeps(sweeps)
+        boxes, models = _entity_records(boxes, models)
+        world_hits = np.zeros(recs.size, dtype=SWEEP_HIT_DTYPE) if world else None
+        hits = np.zeros(recs.size, dtype=abi.ENTITY_SWEEP_HIT_DTYPE)
+        self._check(self._lib.rt_sweep_entities(self._h, _p(recs), recs.size, _lr3(lr), _ptr_or_none(boxes), boxes.size, _ptr_or_none(models),
+                                                models.size, _p(world_hits) if world else None, _p(hits)))
+        return world_hits, hits
+
+    def sweep_entities_async(self, sweeps, boxes, models, world_hits, entity_hits, lr=(0, 0, 0)):
+        """rt_sweep_entities_async on torch device tensors: `sweeps` any contiguous tensor of N * 48 bytes (RtBoxSweep rows), `boxes` any
+        contiguous tensor of B * 32 bytes (RtDrawBox rows) or None, `world_hits` any contiguous tensor of N * 64 bytes or None,
+        `entity_hits` any contiguous tensor of N * 80 bytes; `models` host records as for draw_stamps_async (free again on return).
+        Enqueued: valid after sync(), or in the order of a stream given to set_stream().  A sweep outside the domain gets kind
+        RT_SWEEP_INVALID, an invalid box is skipped on the device, an invalid model fails the call."""
+        n, nb = entity_sweep_tensor_counts(sweeps, boxes, world_hits, entity_hits, self._device)
+        models = _records(models, DRAW_STAMP_DTYPE)
+        self._check(self._lib.rt_sweep_entities_async(self._h, _dp(sweeps), n, _lr3(lr), _dp(boxes) if nb else None, nb,
+                                                      _ptr_or_none(models), models.size, _dp(world_hits), _dp(entity_hits)))
+
+    def move_box_entities(self, lo, hi, motion, lr=(0, 0, 0), boxes=None, models=None, self_box=None, self_model=None, iterations=3):
+        """move_and_slide's character-controller loop over rt_sweep_entities: sweep; take the combined box; when the world or an
+        entity blocked, zero the blocked axis of motion * (1 - t) and sweep again.  It stops on a free sweep, on a zero remainder,
+        after `iterations` sweeps, and at once — where it is — on a start embedded in the world or in an entity (entities move: the
+        host resolves that) or outside the domain.  `self_box` / `self_model`: the index of the mover's own record in `boxes` /
+        `models`, which the sweeps ignore.  Returns (lo, hi, hits): the final box and the list of (world_hit, entity_hit) records."""
+        lo, hi, m = (np.asarray(v, dtype=np.float32).reshape(3).copy() for v in (lo, hi, motion))
+        hits = []
+        for _ in range(int(iterations)):
+            rec = np.zeros(1, dtype=SWEEP_DTYPE)
+            rec["lo"], rec["hi"], rec["motion"] = lo, hi, m
+            rec["reserved0"] = 0 if self_box is None else int(self_box) + 1
+            rec["reserved1"] = 0 if self_model is None else int(self_model) + 1
+            world, ent = self.sweep_entities(rec, lr, boxes, models)
+            w, e = world[0], ent[0]
+            hits.append((w, e))
+            if e["kind"] not in (RT_SWEEP_FREE, RT_SWEEP_BLOCKED) or w["kind"] not in (RT_SWEEP_FREE, RT_SWEEP_BLOCKED):
+                break
+            lo, hi = e["lo"].copy(), e["hi"].copy()
+            stop = e if e["kind"] == RT_SWEEP_BLOCKED else w   # (a reported entity block came first: t_e < W.t)
+            if stop["kind"] == RT_SWEEP_FREE:
+                break
+            m = m * (np.float32(1.0) - stop["t"])
+            m[int(stop["axis"])] = 0
             if not m.any():
                 break
         return lo, hi, hits
@@ -1150,6 +1203,20 @@ def check_sweep_tensors(sweeps, hits, device):
     n = record_count("sweeps", _nbytes(sweeps), SWEEP_DTYPE.itemsize, None, "RtBoxSweep")
     _holds("hits", hits, n, SWEEP_HIT_DTYPE.itemsize)
     return n
+
+
+def entity_sweep_tensor_counts(sweeps, boxes, world_hits, entity_hits, device):
+    """Context.sweep_entities_async's device arguments: `sweeps` a contiguous tensor of N * 48 bytes, `boxes` a contiguous tensor of
+    B * 32 bytes or None, `world_hits` a contiguous tensor of N * 64 bytes or None, `entity_hits` a contiguous tensor of N * 80 bytes,
+    all on GPU `device` and 16-byte aligned, N at most 2^24 and B at most 4096.  Returns (N, B); raises ValueError otherwise (a host
+    tensor's address handed to the kernel would fault the device)."""
+    optional = [(name, t) for name, t in (("boxes", boxes), ("world_hits", world_hits)) if t is not None]
+    _device_tensors(device, ("sweeps", sweeps), ("entity_hits", entity_hits), *optional)
+    n = record_count("sweeps", _nbytes(sweeps), SWEEP_DTYPE.itemsize, MAX_ENTITY_SWEEPS, "RtBoxSweep")
+    if world_hits is not None:
+        _holds("world_hits", world_hits, n, SWEEP_HIT_DTYPE.itemsize)
+    _holds("entity_hits", entity_hits, n, abi.ENTITY_SWEEP_HIT_DTYPE.itemsize)
+    return n, 0 if boxes is None else _box_count(boxes)
 
 
 def make_draw_boxes(lo, hi, materials, emissions=0xFF000000):
