@@ -877,6 +877,8 @@ typedef struct RtParticleStep {    /* 48 bytes */
  *   Out of scope: compaction of dead slots (it would make draw ties depend on atomics; a dead slot costs one record's traffic);
  *     emitters (a host overwrites the oldest slots of a ring with hipMemcpyAsync); collision events reported to the host;
  *     particle-particle and particle-entity contact; tile-split special cases (the call answers as the sweeps do).
+ *     (Emitters, since then: rt_emit_particles — "Particle emitters" below — spawns debris from a shape's voxels on the device; rain and
+ *     sparks, whose start the host knows, stay the host's overwrite.)
  *   Device work per call: one launch, one lane per particle: 64 bytes read, 64 (96 with `draw`) written, and the sub-sweeps' voxel
  *     fetches; the synchronous call adds a transfer each way.
  * Host pointers; returns when `out` (and `draw`) are in host memory. */
@@ -889,6 +891,84 @@ int rt_step_particles(RtContext* ctx, const RtParticleStep* params, const RtPart
  * the host: an invalid record gets RT_PSTATE_INVALID on the device. */
 int rt_step_particles_async(RtContext* ctx, const RtParticleStep* params, const RtParticleState* in_dev, RtParticleState* out_dev,
                             RtParticle* draw_dev, uint32_t count);
+
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Particle emitters: debris spawned on the device from the voxels of a
+ * shape — the explosion rt_edit_shapes carves, the block rt_edit_voxels breaks — one particle per occupied voxel, carrying that
+ * voxel's material word, written into a ring of RtParticleState that rt_step_particles_async steps.  Which voxels are solid and what
+ * they are made of lives in the device's arrays; before this call a host had to rt_read_box the bounding box (which waits for
+ * everything submitted), test membership itself and upload the states.  rt_emit_particles_async -> rt_edit_shapes (carve) ->
+ * rt_step_particles_async -> rt_probe_light_async -> rt_draw_particles_async runs without a host read.  One emitter, 96 bytes: */
+typedef struct RtParticleEmit {      /* 96 bytes */
+    int32_t  a[3];      uint32_t seed;                          /*  0  shape: RtShapeEdit's a; hash seed            */
+    int32_t  b[3];      uint8_t kind, response, reserved0[2];   /* 16  RtShapeEdit's b; RT_SHAPE_*; RT_PARTICLE_*   */
+    float    origin[3]; float speed;                            /* 32  blast centre, world units; radial speed      */
+    float    drift[3];  float spread;                           /* 48  added velocity; amplitude of the jitter      */
+    float    half;      float life_min; float life_span; uint32_t density;   /* 64  density 1..256: share of voxels kept, /256 */
+    uint32_t light;     uint32_t emission; uint32_t reserved[2];             /* 80 */
+} RtParticleEmit;
+/* The ring's cursor, 16 bytes, in host memory for rt_emit_particles and in device memory for rt_emit_particles_async: */
+typedef struct RtEmitCursor { uint32_t next, emitted, dropped, reserved; } RtEmitCursor;   /* 16 bytes */
+/* The rules.  Everything up to the float block of a particle's state is integer arithmetic.  Results are reproduced bit for bit by
+ * tests/emit_particles_ref.py, which calls tests/shape_edits.py for membership and restates no shape rule (DESIGN.md "Particle
+ * emitters").
+ *   Shape: (a, b, kind) mean exactly what they mean in RtShapeEdit — membership, clipping to [0, R)^3, the per-axis BOUNDING BOX and
+ *     the +-R reissue of a shape that crosses the window's seam (+-2 R in `a` of a sphere).
+ *   Selection: a voxel (texel x of the region) is SELECTED iff it is a member of the shape, its minefield byte is 0 at the moment
+ *     the call runs in stream order, and (h & 255) < density with the voxel's hash h (below).  An emitter whose bounding box is empty
+ *     selects nothing.
+ *   World voxel of a texel: the sweeps' addressing — v_k is the one integer in [lr_k - R/2, lr_k + R/2) with (v_k + R/2) mod R ==
+ *     x_k (Euclidean).  lr must satisfy |lr_k| <= 2^22 - R, else RT_ERR_INVALID_ARG: every emitted corner then lies inside
+ *     rt_sweep_boxes' |lo|, |hi| <= 2^22.
+ *   Hash, in uint32: mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16.  h = mix(seed ^
+ *     mix(uint32(v_x) ^ mix(uint32(v_y) ^ mix(uint32(v_z))))); g_i = mix(h + i) for i = 1..4; u_i = float(g_i >> 8) * 2^-24.  The
+ *     hash takes world coordinates, not texels: a block's debris is the same wherever the window sits.
+ *   Order: the selected voxels are numbered j = 0, 1, ... by ascending emitter index, and within an emitter by the key (z >> 2,
+ *     y >> 2, x >> 2, z & 3, y & 3, x & 3) of the texel, compared lexicographically — brick-major, then the order inside a brick of
+ *     the swizzled layout (one brick is 64 contiguous bytes, brick_index << 6).  A voxel selected by two emitters is emitted twice.
+ *     No atomic decides a slot: two runs give equal bits.
+ *   Ring and cursor: N = the number of selected voxels, n = min(N, max_emit).  Particle j < n is written whole, 64 bytes, to slot
+ *     (next + j) mod capacity; the particles j >= n are dropped; every other slot keeps its bits.  Afterwards next = (next + n) mod
+ *     capacity, emitted += n, dropped += N - n (wrapping uint32); `reserved` is untouched.  On the device an input next >= capacity
+ *     is taken mod capacity; rt_emit_particles refuses such a cursor, and one with reserved != 0 (RT_ERR_INVALID_ARG).  Because the
+ *     cursor lives on the device, a second rt_emit_particles_async can be chained behind the first without the host knowing n.
+ *   State of one emitted particle, fp32 with one rounding per operation and no fused multiply-add (as in the step), in this order:
+ *     c_k = float(v_k) + 0.5f; lo_k = c_k - half, hi_k = c_k + half (half <= 0.5: the box lies inside the voxel's own cell [v, v + 1];
+ *     beside a large c the box may collapse — it is written as computed and the step marks it INVALID by its own rule); r_k = c_k -
+ *     origin_k; len = rtm_length3(r); dir_k = len > 0 ? r_k / len : 0; velocity_k = (dir_k * speed + (u_{k+1} * 2 - 1) * spread) +
+ *     drift_k; life = life_min + u_4 * life_span; flags = response; material = the voxel's material word; light, emission and half
+ *     the emitter's; reserved = 0.
+ *   Valid emitter, checked on the host in both calls (RT_ERR_INVALID_ARG; the message names the first invalid emitter): the shape
+ *     valid by rt_edit_shapes' rule; response <= 3; the reserved bytes and words 0; density in 1..256; every float finite, except
+ *     that life_min may be +inf; 2^-8 <= half <= 0.5; 0 <= speed, spread <= 4096; |drift_k| <= 4096; |origin_k| <= 2^22; life_min >
+ *     0; 0 <= life_span <= 4096.
+ *   Limits: count <= 256; 1 <= max_emit <= capacity <= 2^20; the clipped bounding boxes of one call cover at most 2^18 bricks (4^3
+ *     voxels each) in total — a whole 256^3 region.  Anything else is RT_ERR_INVALID_ARG.
+ *   Errors: a NULL pointer with count > 0: RT_ERR_INVALID_ARG.  count == 0: RT_OK, nothing enqueued.  A call whose bounding boxes
+ *     are all empty: RT_OK, nothing enqueued, the cursor unchanged.  No world resident: RT_ERR_NOT_READY.  A rejected call writes
+ *     nothing.
+ *   Which world, ordering and side effects: the sweeps', exactly — the call runs on the query stream, or on the caller's stream
+ *     after rt_set_stream(non-NULL); it sees every earlier upload, edit, slab and generated region; later world changes wait for it
+ *     (so an emit enqueued before a carve reads the voxels the carve removes).  No output plane, accumulation sum or history,
+ *     RtCounters, RtTiming, pending box or prepass changes.  Tile contexts, every RtKernel and every region size answer the same.
+ *   The debris recipe: emit with the explosion's shape, then rt_edit_shapes with the same shape and solid = 0, then step.  Every
+ *     emitted box lies in a cell the carve has just emptied, so the step's closing property holds from the first tick.  Emitting
+ *     without carving leaves the particles EMBEDDED, and the first step kills them.
+ *   Out of scope: emission from air or from entities, per-particle lights, velocity models beyond radial + jitter + drift, draw
+ *     records (the next step writes those).
+ *   Device work per call: the emitters' records (128 bytes each) through a staging set, then three launches — count (a wave per
+ *     (emitter, brick): the brick's 64 minefield bytes, one ballot), scan (the cursor update among it), write (64 bytes per particle)
+ *     — over a scratch of 12 bytes per brick that the context keeps (RtInfo.device_bytes).
+ * `emitters` is a host pointer in both calls (the host sizes the launch from the bounding boxes), free again when the call returns.
+ * Host pointers: `states` is the host's ring of `capacity` records, of which only the written slots change (at most two contiguous
+ * copies); `cursor` is read and written on the host.  Returns when both are in host memory. */
+int rt_emit_particles(RtContext* ctx, const RtParticleEmit* emitters, uint32_t count, const int32_t lr[3], RtParticleState* states,
+                      uint32_t capacity, uint32_t max_emit, RtEmitCursor* cursor);
+/* Same with a device ring and a device cursor, enqueued: both are valid after rt_sync (or, after rt_set_stream, in the caller's
+ * stream order).  states_dev and cursor_dev must pass rt_trace_rays_async's test (16-byte aligned memory of the context's device, or
+ * managed memory), else RT_ERR_INVALID_ARG before anything is enqueued; the cursor must be complete on the device when the call's
+ * launches run (stream order: an earlier rt_emit_particles_async is). */
+int rt_emit_particles_async(RtContext* ctx, const RtParticleEmit* emitters, uint32_t count, const int32_t lr[3], RtParticleState* states_dev,
+                            uint32_t capacity, uint32_t max_emit, RtEmitCursor* cursor_dev);
 
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
@@ -1479,7 +1559,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtParticleState, RtParticleStep, RT_PARTICLE_*, RT_PSTATE_*, rt_step_particles, rt_step_particles_async
  *        (particle simulation: a tick of integration, sub-sweeps, contact response and ageing on the device).
  *        Additive, same minor version: RtEntitySweepHit, rt_sweep_entities, rt_sweep_entities_async (entity sweeps: box sweeps that
- *        collide with the drawn boxes and models as well as with the world). */
+ *        collide with the drawn boxes and models as well as with the world).
+ *        Additive, same minor version: RtParticleEmit, RtEmitCursor, rt_emit_particles, rt_emit_particles_async (particle emitters:
+ *        debris spawned on the device from the occupied voxels of a shape, into a ring of particle states). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

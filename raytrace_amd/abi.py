@@ -258,6 +258,29 @@ assert C.sizeof(RtParticleState) == 64 and C.sizeof(RtParticleStep) == 48
 PARTICLE_STATE_DTYPE = np.dtype(RtParticleState)   # the numpy view of the state (render.make_particle_states builds arrays of it)
 
 
+class RtParticleEmit(C.Structure):
+    """rt_emit_particles' emitter (ABI 1.3, additive: particle emitters): 96 bytes; the reserved bytes and words must be 0."""
+    _fields_ = [("a", C.c_int32 * 3), ("seed", C.c_uint32), ("b", C.c_int32 * 3), ("kind", C.c_uint8), ("response", C.c_uint8),
+                ("reserved0", C.c_uint8 * 2), ("origin", C.c_float * 3), ("speed", C.c_float), ("drift", C.c_float * 3), ("spread", C.c_float),
+                ("half", C.c_float), ("life_min", C.c_float), ("life_span", C.c_float), ("density", C.c_uint32), ("light", C.c_uint32),
+                ("emission", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RtEmitCursor(C.Structure):
+    """rt_emit_particles' ring cursor: 16 bytes; `reserved` is left as it is."""
+    _fields_ = [("next", C.c_uint32), ("emitted", C.c_uint32), ("dropped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RtParticleEmit) == 96 and C.sizeof(RtEmitCursor) == 16
+assert (RtParticleEmit.seed.offset, RtParticleEmit.b.offset, RtParticleEmit.kind.offset, RtParticleEmit.response.offset, RtParticleEmit.origin.offset,
+        RtParticleEmit.drift.offset, RtParticleEmit.half.offset, RtParticleEmit.density.offset, RtParticleEmit.light.offset,
+        RtParticleEmit.reserved.offset) == (12, 16, 28, 29, 32, 48, 64, 76, 80, 88)
+EMIT_DTYPE = np.dtype(RtParticleEmit)          # the numpy view of an emitter (render.make_particle_emitters builds arrays of it)
+EMIT_CURSOR_DTYPE = np.dtype(RtEmitCursor)     # ... and of the cursor
+MAX_EMITTERS = 256                             # rt_emit_particles: emitters per call
+MAX_EMIT_CAPACITY = 1 << 20                    # ... and slots of the ring
+
+
 class RtDrawStamp(C.Structure):
     """rt_draw_stamps input (ABI 1.3, additive: voxel-model entities): 32 bytes; the reserved fields must be 0."""
     _fields_ = [("origin", C.c_float * 3), ("scale", C.c_float), ("stamp", C.c_uint32), ("orient", C.c_uint8), ("reserved0", C.c_uint8 * 3),

@@ -1,7 +1,9 @@
 // api_query.hip — queries against the resident world: ray queries (rt_trace_rays, rt_trace_rays_async, rt_pick_pixels), light
 // probes (rt_probe_light, rt_probe_light_async), box sweeps (rt_sweep_boxes, rt_sweep_boxes_async), the particle simulation built on
 // them (rt_step_particles, rt_step_particles_async) and entity queries (rt_trace_entities, rt_trace_entities_async,
-// rt_pick_entities) and entity sweeps (rt_sweep_entities, rt_sweep_entities_async), which share their checks, stream and staging.
+// rt_pick_entities) and entity sweeps (rt_sweep_entities, rt_sweep_entities_async), which share their checks, stream and staging, and
+// the particle emitters (rt_emit_particles, rt_emit_particles_async), whose world, stream and ordering are the sweeps'.
+#include "emit_check.hpp"
 #include "entity_query_check.hpp"
 #include "particle_step_check.hpp"
 #include "sweep_entities_check.hpp"
@@ -200,6 +202,56 @@ int step_launch(RtContext* c, hipStream_t st, const RtParticleStep& p, const voi
     a.dt = p.dt; a.damping = p.damping; a.restitution = p.restitution; a.friction = p.friction; a.rest_speed = p.rest_speed;
     for (int k = 0; k < 3; k++) { a.lr[k] = p.lr[k]; a.accel[k] = p.accel[k]; }
     RT_HIP(c, rtd::launch_step_particles(scene_of(c), c->logr, a, st));
+    if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
+    return RT_OK;
+}
+
+// ---- particle emitters: the sweeps' world, stream and ordering; host emitters through a staging set as the models of a draw -----
+static_assert(sizeof(RtParticleEmit) == 96 && sizeof(RtEmitCursor) == 16, "the kernels read six 16-byte words per emitter and one per cursor");
+static_assert(kMaxEmitters == rtd::kMaxEmitRecords && kMaxEmitBricks == rtd::kMaxEmitItems && kMaxEmitCapacity == rtd::kMaxParticles,
+              "the host's limits are the kernels'");
+
+// checks shared by the two calls, and the plan; RT_OK when there is work to enqueue, 1 for a call that enqueues nothing
+int emit_check(RtContext* c, const char* fn, const RtParticleEmit* emitters, uint32_t count, const int32_t lr[3], const void* states,
+               uint32_t capacity, uint32_t max_emit, const RtEmitCursor* host_cursor, const void* cursor, EmitPlan* plan) {
+    const char* e = emit_args_error(emitters, count, lr, states, capacity, max_emit, cursor);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e);
+    if (count == 0) return 1;
+    const uint32_t bad = first_invalid_emitter(emitters, count, c->logr);
+    if (bad != count) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": emitter " + std::to_string(bad) + " is not a valid emitter");
+    if (!emit_window_valid(lr, c->logr)) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": |lr| must not exceed 2^22 - R");
+    if (host_cursor && !emit_cursor_valid(*host_cursor, capacity))
+        return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": the cursor's next must be below capacity and its reserved word 0");
+    *plan = emit_plan(emitters, count, c->logr);
+    if (plan->items > kMaxEmitBricks) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": the bounding boxes cover more than 2^18 bricks");
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    return plan->recs.empty() ? 1 : RT_OK;
+}
+
+// The plan's records to the device for `st` to read, the three launches there, and what waits for them: the staging set's next
+// transfer (ev_applied), the scratch's next user on another stream (ev_emit), later world changes (ev_query).
+int emit_launch(RtContext* c, hipStream_t st, const EmitPlan& plan, const int32_t lr[3], void* states_dev, uint32_t capacity, uint32_t max_emit,
+                void* cursor_dev) {
+    rtd::EmitParticlesArgs a;
+    a.nrecs = (uint32_t)plan.recs.size();
+    a.items = (uint32_t)plan.items;
+    int rc = emit_scratch_reserve(c, rtd::emit_scratch_words(a.items));
+    if (rc != RT_OK) return rc;
+    StagingSet* s = nullptr;
+    uint8_t* recs;
+    rc = upload_models(c, nullptr, 0u, plan.recs.data(), plan.recs.size() * sizeof(EmitRecord), st, &s, &recs);
+    if (rc != RT_OK) return rc;
+    a.recs = reinterpret_cast<const uint4*>(recs);
+    a.states = reinterpret_cast<uint4*>(states_dev);
+    a.cursor = reinterpret_cast<uint4*>(cursor_dev);
+    a.scratch = c->emit_scratch;
+    a.capacity = capacity;
+    a.max_emit = max_emit;
+    for (int k = 0; k < 3; k++) a.lr[k] = lr[k];
+    RT_HIP(c, c->ev_emit.wait_elsewhere(st));   // the scratch is the previous call's until its write pass has run
+    RT_HIP(c, rtd::launch_emit_particles(scene_of(c), c->logr, a, st));
+    RT_HIP(c, s->ev_applied.record(st));
+    RT_HIP(c, c->ev_emit.record(st));
     if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
     return RT_OK;
 }
@@ -442,6 +494,59 @@ int rt_step_particles_async(RtContext* ctx, const RtParticleStep* params, const 
     rc = query_stream_of(ctx, &st);
     if (rc != RT_OK) return rc;
     return step_launch(ctx, st, *params, in_dev, out_dev, draw_dev, count);
+}
+
+int rt_emit_particles(RtContext* ctx, const RtParticleEmit* emitters, uint32_t count, const int32_t lr[3], RtParticleState* states,
+                      uint32_t capacity, uint32_t max_emit, RtEmitCursor* cursor) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    EmitPlan plan;
+    int rc = emit_check(ctx, "rt_emit_particles", emitters, count, lr, states, capacity, max_emit, cursor, cursor, &plan);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    // A device ring with a cursor of its own at slot 0: particle j lands in slot j there, and comes back into the caller's ring at
+    // (next + j) mod capacity.  It holds what the call can emit at the most: max_emit, or 64 per brick of the plan if that is less
+    // (N cannot exceed it, so n and the dropped count are what max_emit would give).
+    const uint64_t most = 64u * plan.items;
+    const uint32_t staged = most < max_emit ? (uint32_t)most : max_emit;
+    const RtEmitCursor zero{0u, 0u, 0u, 0u};
+    uint8_t* dev[2];
+    rc = stage_sync(ctx, st, {{&zero, sizeof zero}, {nullptr, (size_t)staged * sizeof(RtParticleState)}}, dev);
+    if (rc != RT_OK) return rc;
+    rc = emit_launch(ctx, st, plan, lr, dev[1], staged, staged, dev[0]);
+    if (rc != RT_OK) return rc;
+    RtEmitCursor got;
+    rc = fetch_sync(ctx, st, dev[0], &got, sizeof got);
+    if (rc != RT_OK) return rc;
+    EmitRun runs[2];
+    const uint32_t nruns = emit_ring_runs(cursor->next, got.emitted, capacity, runs);
+    for (uint32_t i = 0; i < nruns; i++) {
+        rc = fetch_sync(ctx, st, dev[1] + (size_t)runs[i].first * sizeof(RtParticleState), states + runs[i].slot,
+                        (size_t)runs[i].count * sizeof(RtParticleState));
+        if (rc != RT_OK) return rc;
+    }
+    cursor->next = (uint32_t)(((uint64_t)cursor->next + got.emitted) % capacity);
+    cursor->emitted += got.emitted;
+    cursor->dropped += got.dropped;
+    return RT_OK;
+}
+
+int rt_emit_particles_async(RtContext* ctx, const RtParticleEmit* emitters, uint32_t count, const int32_t lr[3], RtParticleState* states_dev,
+                            uint32_t capacity, uint32_t max_emit, RtEmitCursor* cursor_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    EmitPlan plan;
+    int rc = emit_check(ctx, "rt_emit_particles_async", emitters, count, lr, states_dev, capacity, max_emit, nullptr, cursor_dev, &plan);
+    if (rc != RT_OK && rc != 1) return rc;
+    if (count == 0) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, states_dev) || !query_device_ptr(ctx, cursor_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_emit_particles_async: states and cursor must be 16-byte aligned memory of the context's device");
+    if (rc == 1) return RT_OK;
+    hipStream_t st;
+    rc = query_stream_of(ctx, &st);
+    if (rc != RT_OK) return rc;
+    return emit_launch(ctx, st, plan, lr, states_dev, capacity, max_emit, cursor_dev);
 }
 
 int rt_trace_entities(RtContext* ctx, const RtRay* rays, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes, uint32_t nboxes,

@@ -335,6 +335,12 @@ struct __attribute__((visibility("hidden"))) RtContext {
     uint32_t* particle_scratch = nullptr;
     size_t particle_scratch_words = 0;
     rta::LatchEvent ev_particles;
+    // rt_emit_particles[_async]: the masks and particle numbers of a call's items (rtd::emit_scratch_words), grown on demand and never
+    // shrunk, in c->allocs (device_bytes; freed by rt_destroy), handled as the particle scratch is: a call's launches follow the
+    // previous call's (ev_emit) when the stream has changed between them.
+    uint32_t* emit_scratch = nullptr;
+    size_t emit_scratch_words = 0;
+    rta::LatchEvent ev_emit;
 };
 
 namespace rta __attribute__((visibility("hidden"))) {
@@ -425,24 +431,30 @@ inline int stage_sync(RtContext* c, hipStream_t st, std::initializer_list<StageP
     return RT_OK;
 }
 
-// At least `words` words of particle scratch.  A block that must grow waits for the launches that still use the old one.
-inline int particle_scratch_reserve(RtContext* c, size_t words) {
-    if (!c->ev_particles.ev) RT_HIP(c, new_event(c, &c->ev_particles.ev));
-    if (words <= c->particle_scratch_words) return RT_OK;
-    if (c->particle_scratch) {
-        RT_HIP(c, c->ev_particles.host_wait());
-        c->ev_particles.forget();
+// At least `words` words in a scratch block that grows on demand and is never shrunk (*block of *have words, in c->allocs and counted in
+// device_bytes).  `users`: recorded behind the launches that use the block; a block that must grow waits for them before it is freed.
+inline int scratch_reserve(RtContext* c, uint32_t** block, size_t* have, LatchEvent* users, size_t words) {
+    if (!users->ev) RT_HIP(c, new_event(c, &users->ev));
+    if (words <= *have) return RT_OK;
+    if (*block) {
+        RT_HIP(c, users->host_wait());
+        users->forget();
         for (size_t i = 0; i < c->allocs.size(); i++)
-            if (c->allocs[i] == c->particle_scratch) { c->allocs.erase(c->allocs.begin() + (long)i); break; }
-        (void)hipFree(c->particle_scratch);
-        c->device_bytes -= c->particle_scratch_words * sizeof(uint32_t);
-        c->particle_scratch = nullptr;
-        c->particle_scratch_words = 0;
+            if (c->allocs[i] == *block) { c->allocs.erase(c->allocs.begin() + (long)i); break; }
+        (void)hipFree(*block);
+        c->device_bytes -= *have * sizeof(uint32_t);
+        *block = nullptr;
+        *have = 0;
     }
-    RT_HIP(c, dev_alloc(c, &c->particle_scratch, words));
-    c->particle_scratch_words = words;
+    RT_HIP(c, dev_alloc(c, block, words));
+    *have = words;
     return RT_OK;
 }
+// rt_draw_particles' binning scratch and rt_emit_particles' masks and particle numbers
+inline int particle_scratch_reserve(RtContext* c, size_t words) {
+    return scratch_reserve(c, &c->particle_scratch, &c->particle_scratch_words, &c->ev_particles, words);
+}
+inline int emit_scratch_reserve(RtContext* c, size_t words) { return scratch_reserve(c, &c->emit_scratch, &c->emit_scratch_words, &c->ev_emit, words); }
 
 // An environment knob (experiments, A/B timing): *field = v when `s` holds an integer in lo..hi; anything else is ignored.
 template <typename T>

@@ -14,6 +14,7 @@
 
 #include "rt_device.hpp"
 #include "rt_kernels.hpp"
+#include "rt_shape_rows.hpp"
 #include "rt_world.hpp"
 
 namespace rtd {
@@ -187,21 +188,6 @@ struct RecordStage {
     }
 };
 
-// bits lo..hi of a 64-voxel row, clipped to it (none when the range misses the row)
-__device__ __forceinline__ uint64_t row_range(int lo, int hi) {
-    const int l = lo < 0 ? 0 : lo > 63 ? 63 : lo, h = hi < 0 ? 0 : hi > 63 ? 63 : hi;
-    return (lo > hi || hi < 0 || lo > 63) ? 0ull : (~0ull >> (63 - h)) & (~0ull << l);
-}
-// floor(sqrt(v)) for 0 <= v <= 2^26, bit by bit (the host's rule, api/edit_shapes.hpp)
-__device__ __forceinline__ int isqrt26(int v) {
-    int s = 0;
-#pragma unroll
-    for (int bit = 1 << 13; bit; bit >>= 1) {
-        const int t = s | bit;
-        s = t * t <= v ? t : s;
-    }
-    return s;
-}
 // the least |2 x + 1 - a| over the 64 texels x0 .. x0 + 63
 __device__ __forceinline__ int sphere_gap(int a, int x0) {
     const int lo = 2 * x0 + 1, hi = 2 * x0 + 127;
@@ -237,17 +223,7 @@ struct ShapeStage {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int z = z0 + lz + 16 * j;
-                uint64_t m;
-                if (kind == 0u) {
-                    m = (y >= p.y && y <= q.y && z >= p.z && z <= q.z) ? row_range(p.x - x0, q.x - x0) : 0ull;
-                } else {
-                    // what is left of (2 r)^2 for x: every term is below 2^26, so int32 is exact
-                    const int dy = 2 * y + 1 - p.y, dz = 2 * z + 1 - p.z;
-                    const int budget = q.x - dy * dy - dz * dz;
-                    const int r = isqrt26(budget < 0 ? 0 : budget);
-                    // a - r <= 2 x + 1 <= a + r: x from ceil((a - r - 1) / 2) to floor((a + r - 1) / 2)
-                    m = budget < 0 ? 0ull : row_range(((p.x - r) >> 1) - x0, ((p.x + r - 1) >> 1) - x0);
-                }
+                const uint64_t m = shape_row(kind, p, q, x0, y, z);   // (rt_shape_rows.hpp: the one membership rule)
                 uint64_t sel = where == 0u ? m : where == 1u ? (m & row[j]) : (m & ~row[j]);
                 row[j] = solid ? (row[j] | sel) : (row[j] & ~sel);
                 // material words: the four x of one brick are 16 contiguous bytes of the swizzled array

@@ -230,6 +230,25 @@ struct StepParticlesArgs {
 };
 hipError_t launch_step_particles(const Scene& sc, int logr, const StepParticlesArgs& a, hipStream_t st);
 
+// rt_emit.hip: debris from the occupied voxels of shapes into a ring of particle states (rt_emit_particles).  An ITEM is one
+// (emitter, 4^3 brick) of the host's plan (api/emit_check.hpp, EmitRecord: eight uint4 per emitter that has a bounding box); one wave
+// per item.  Three launches: count, scan (with the cursor update), write.
+constexpr uint32_t kMaxEmitRecords = 256;      // emitters per call
+constexpr uint32_t kMaxEmitItems = 1u << 18;   // items per call
+struct EmitParticlesArgs {
+    const uint4* recs;     // EmitRecord[nrecs], `first` ascending from 0
+    uint4* states;         // the ring: RtParticleState[capacity] (four uint4 each)
+    uint4* cursor;         // RtEmitCursor
+    uint32_t* scratch;     // emit_scratch_words(items) words, 16-byte aligned
+    uint32_t nrecs, items; // 1..kMaxEmitRecords, 1..kMaxEmitItems: the sum of the records' nbx * nby * nbz
+    uint32_t capacity, max_emit;
+    int32_t lr[3];
+};
+// The scratch of a call, in 4-byte words: [0] the ring slot of particle 0, [1] n, [2..3] unused, then per item its 64-bit mask of
+// selected voxels, then per item the number of its first selected voxel.
+inline size_t emit_scratch_words(uint32_t items) { return 4u + 3u * (size_t)items; }
+hipError_t launch_emit_particles(const Scene& sc, int logr, const EmitParticlesArgs& a, hipStream_t st);
+
 // rt_boxes.hip: entity boxes composited into a whole frame's row-major planes by depth (rt_draw_boxes).  One launch for the batch;
 // a wave owns an 8x8 pixel tile.
 struct DrawBoxesArgs {

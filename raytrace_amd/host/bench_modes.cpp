@@ -390,6 +390,163 @@ int run_simulate(const Options& o, const World& w) {
     return 0;
 }
 
+// --debris RADIUS [--density D]: particle emitters.  An explosion where the view's centre pixel meets the terrain: a sphere of RADIUS
+// round the hit voxel, every D-th of 256 of its occupied voxels (default all) becoming a particle.  Each of 20 ticks runs, with no
+// host read, rt_emit_particles_async -> rt_edit_shapes (the carve) -> rt_step_particles_async -> rt_draw_particles_async into the
+// frame drawn last, bracketed by events; between the ticks the sphere is filled again (not timed).  In the same process: the emit
+// alone, repeated between two events; rt_stamp_capture of the sphere's bounding box — it reads the same voxels: a floor for the read
+// side — by rt_get_timing's launch times; and the host path the emit replaces, call to usable device buffer: rt_read_box of the
+// bounding box, membership, hash and states on the host, hipMemcpy.
+static uint32_t debris_mix(uint32_t h) { h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16; return h; }
+int run_debris(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const HipEvents hip;
+    if (!hip.ok) { std::fprintf(stderr, "--debris needs the HIP runtime for its device buffers\n"); return 1; }
+    const int R = RT_ROOT_BLOCK_SIZE, radius = o.debris;
+    const int32_t* lr = s.u().lr;
+    const int32_t centre_px[2] = {o.width / 2, o.height / 2};
+    RtRayHit hit{};
+    int rc = rt_pick_pixels(s.ctx, &s.u(), centre_px, 1, &hit);
+    if (rc != RT_OK) return s.fail("debris", rc);
+    int c[3] = {R / 2, R / 2, R / 2};
+    if (hit.kind == RT_HIT_SOLID) for (int a = 0; a < 3; a++) c[a] = hit.texel[a];
+    RtParticleEmit e{};
+    int32_t lo[3], ext[3];
+    for (int a = 0; a < 3; a++) {
+        e.a[a] = 2 * c[a] + 1;
+        // world coordinates of the texel's centre under lr (the sweeps' addressing)
+        e.origin[a] = (float)(lr[a] - R / 2 + (((c[a] - lr[a]) % R + R) % R)) + 0.5f;
+        lo[a] = c[a] - radius < 0 ? 0 : c[a] - radius;
+        const int hi = c[a] + radius > R - 1 ? R - 1 : c[a] + radius;
+        ext[a] = hi - lo[a] + 1;
+    }
+    e.b[0] = 4 * radius * radius; e.kind = RT_SHAPE_SPHERE; e.response = RT_PARTICLE_BOUNCE; e.seed = 0x5EEDu;
+    e.speed = 12.0f; e.spread = 3.0f; e.drift[2] = 4.0f; e.half = 0.125f; e.life_min = 1.0f; e.life_span = 2.0f;
+    e.density = (uint32_t)o.debris_density; e.emission = 0xFF000000u;
+    RtShapeEdit carve{}, fill{};
+    for (int a = 0; a < 3; a++) { carve.a[a] = e.a[a]; carve.b[a] = e.b[a]; }
+    carve.kind = RT_SHAPE_SPHERE; carve.where = RT_WHERE_ALL; carve.solid = 0;
+    fill = carve; fill.solid = 1; fill.material = BRUSH_MATERIAL;
+    RtParticleStep step{};
+    step.dt = 1.0f / 60.0f; step.accel[2] = -32.0f; step.damping = 1.0f; step.restitution = 0.5f; step.friction = 0.75f; step.rest_speed = 0.5f;
+    for (int a = 0; a < 3; a++) step.lr[a] = lr[a];
+    step.sweeps = (uint32_t)o.step_sweeps;
+    const uint32_t capacity = 1u << 20;
+
+    // the host path: read the box back, select and build on the host, upload — three times, the first discarded
+    const size_t nvox = (size_t)ext[0] * ext[1] * ext[2];
+    std::vector<uint32_t> box_mats(nvox);
+    std::vector<uint8_t> box_mine(nvox);
+    std::vector<RtParticleState> built;
+    void* d_host_ring = nullptr;
+    if (hip.dev_malloc(&d_host_ring, (size_t)capacity * sizeof(RtParticleState)) != 0) { std::fprintf(stderr, "--debris: no device memory\n"); return 1; }
+    double host_ms = 0.0;
+    for (int i = 0; i < 3 && rc == RT_OK; i++) {
+        const auto t = std::chrono::steady_clock::now();
+        rc = rt_read_box(s.ctx, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], box_mats.data(), box_mine.data());
+        built.clear();
+        for (int z = 0; z < ext[2] && rc == RT_OK; z++)
+            for (int y = 0; y < ext[1]; y++)
+                for (int x = 0; x < ext[0]; x++) {
+                    const size_t at = ((size_t)z * ext[1] + y) * ext[0] + x;
+                    const int t3[3] = {lo[0] + x, lo[1] + y, lo[2] + z};
+                    long long d2 = 0;
+                    int v[3];
+                    for (int a = 0; a < 3; a++) {
+                        const long long d = 2 * t3[a] + 1 - e.a[a];
+                        d2 += d * d;
+                        v[a] = lr[a] - R / 2 + (((t3[a] - lr[a]) % R + R) % R);
+                    }
+                    if (d2 > e.b[0] || box_mine[at] != 0u) continue;
+                    const uint32_t h = debris_mix(e.seed ^ debris_mix((uint32_t)v[0] ^ debris_mix((uint32_t)v[1] ^ debris_mix((uint32_t)v[2]))));
+                    if ((h & 255u) >= e.density) continue;
+                    RtParticleState p{};
+                    float r[3], len2 = 0.0f;
+                    for (int a = 0; a < 3; a++) {
+                        const float cc = (float)v[a] + 0.5f;
+                        p.lo[a] = cc - e.half; p.hi[a] = cc + e.half;
+                        r[a] = cc - e.origin[a];
+                        len2 += r[a] * r[a];
+                    }
+                    const float len = std::sqrt(len2);
+                    for (int a = 0; a < 3; a++) {
+                        const float u = (float)(debris_mix(h + 1u + (uint32_t)a) >> 8) * 5.9604644775390625e-08f;
+                        p.velocity[a] = ((len > 0.0f ? r[a] / len : 0.0f) * e.speed + (u * 2.0f - 1.0f) * e.spread) + e.drift[a];
+                    }
+                    p.life = e.life_min + (float)(debris_mix(h + 4u) >> 8) * 5.9604644775390625e-08f * e.life_span;
+                    p.flags = e.response; p.material = box_mats[at]; p.emission = e.emission; p.half = e.half;
+                    built.push_back(p);
+                }
+        const size_t keep = built.size() < capacity ? built.size() : capacity;
+        if (rc == RT_OK && keep && hip.copy(d_host_ring, built.data(), keep * sizeof(RtParticleState), 1 /* hipMemcpyHostToDevice */) != 0) rc = RT_ERR_HIP;
+        if (i > 0) host_ms += ms_since(t) / 2.0;
+    }
+    (void)hip.dev_free(d_host_ring);
+    if (rc != RT_OK) return s.fail("debris", rc);
+
+    // rt_stamp_capture of the bounding box: its launch times alone (rt_get_timing), 5 captures after one that is discarded
+    double capture_ms = -1.0;
+    if (nvox <= (1u << 24)) {
+        RtTiming tm{};
+        capture_ms = 0.0;
+        for (int i = 0; i < 6 && rc == RT_OK; i++) {
+            uint32_t id = 0;
+            rc = rt_sync(s.ctx);
+            if (rc == RT_OK) rc = rt_get_timing(s.ctx, &tm);
+            if (rc == RT_OK) rc = rt_stamp_capture(s.ctx, lo, ext, 0u, &id);
+            if (rc == RT_OK) rc = rt_sync(s.ctx);
+            if (rc == RT_OK) rc = rt_get_timing(s.ctx, &tm);
+            if (rc == RT_OK) rc = rt_stamp_destroy(s.ctx, id);
+            if (i > 0) capture_ms += tm.shade_ms / 5.0;
+        }
+        if (rc != RT_OK) return s.fail("debris", rc);
+    }
+
+    RtProbeLight light{};
+    const RtLightProbe probe = sphere_probe(0, e.origin);
+    rc = rt_probe_light(s.ctx, &s.u(), &probe, 1, 4, 2, &light);
+    if (rc != RT_OK) return s.fail("debris", rc);
+    DeviceRun run(hip, s.ctx);
+    const RtEmitCursor zero{0u, 0u, 0u, 0u};
+    RtParticleState* d_ring = (RtParticleState*)run.on_device(nullptr, (size_t)capacity * sizeof(RtParticleState));
+    RtEmitCursor* d_cursor = (RtEmitCursor*)run.on_device(&zero, sizeof zero);
+    RtParticle* d_draw = (RtParticle*)run.on_device(nullptr, (size_t)capacity * sizeof(RtParticle));
+    const RtProbeLight* d_light = (const RtProbeLight*)run.on_device(&light, sizeof light);
+    run.start();
+    // the emit alone: the same call repeated between two events (the ring wraps; the world does not change)
+    const int reps = 20;
+    const double emit_ms = run.repeat(reps, [&] { return rt_emit_particles_async(s.ctx, &e, 1, lr, d_ring, capacity, capacity, d_cursor); });
+    RtEmitCursor after{};
+    if (run.fine) run.fine = rt_sync(s.ctx) == RT_OK && hip.copy(&after, d_cursor, sizeof after, 2 /* hipMemcpyDeviceToHost */) == 0;
+    const uint32_t selected = (after.emitted + after.dropped) / (uint32_t)(reps + 1);
+    const uint32_t live = selected < capacity ? selected : capacity;
+    // the ticks: emit -> carve -> step -> draw between two events, the fill outside them
+    double tick_ms = 0.0;
+    const int ticks = 20;
+    for (int t = 0; t < ticks && run.fine; t++) {
+        run.fine = hip.copy(d_cursor, &zero, sizeof zero, 1) == 0 && rt_draw_frame(s.ctx, &s.u()) == RT_OK && run.mark() &&
+                   rt_emit_particles_async(s.ctx, &e, 1, lr, d_ring, capacity, capacity, d_cursor) == RT_OK &&
+                   rt_edit_shapes(s.ctx, &carve, 1) == RT_OK && rt_step_particles_async(s.ctx, &step, d_ring, d_ring, d_draw, live) == RT_OK &&
+                   rt_draw_particles_async(s.ctx, &s.u(), d_draw, live, d_light, 1) == RT_OK;
+        float ms = 0.0f;
+        run.fine = run.fine && run.lap(&ms);
+        tick_ms += (double)ms / ticks;
+        run.fine = run.fine && rt_edit_shapes(s.ctx, &fill, 1) == RT_OK;
+    }
+    if (!run.close()) { std::fprintf(stderr, "debris failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    // the host path restates the selection: it is a baseline only while it selects what the library selects
+    if (built.size() != (size_t)selected) { std::fprintf(stderr, "debris: the host path built %zu states, the library selected %u\n", built.size(), selected); return 1; }
+    uint64_t bricks = 1;
+    for (int a = 0; a < 3; a++) bricks *= (uint64_t)(((lo[a] + ext[a] - 1) >> 2) - (lo[a] >> 2) + 1);
+    std::printf("{\"debris\": %d, \"density\": %d, \"centre\": [%d, %d, %d], \"box\": [%d, %d, %d], \"bricks\": %llu, \"selected\": %u, "
+                "\"host_built\": %zu, \"frame\": \"%dx%d spp %d depth %d\", \"emit_device_ms\": %.4f, \"capture_device_ms\": %.4f, "
+                "\"emit_over_capture\": %.2f, \"tick_device_ms\": %.4f, \"host_path_ms\": %.3f}\n",
+                radius, o.debris_density, c[0], c[1], c[2], ext[0], ext[1], ext[2], (unsigned long long)bricks, selected, built.size(), o.width,
+                o.height, o.spp, o.depth, emit_ms, capture_ms, capture_ms > 0.0 ? emit_ms / capture_ms : 0.0, tick_ms, host_ms);
+    return 0;
+}
+
 // --models N [--model-scale S]: voxel-model entities.  One built-in 9 x 9 x 12 sparse stamp (about a third of its voxels solid; its
 // values are the generator's first) is drawn N times at scale S (default 1/8) — scattered like --boxes' boxes, in seeded
 // orientations, lit by their bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times;

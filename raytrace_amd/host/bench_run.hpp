@@ -28,6 +28,7 @@ struct Options {
     long long rays = 0, boxes = -1, lights = -1, models = -1, shadows = -1, particles = -1;
     float particle_half = 0.0625f, particle_near = 10.0f;
     int simulate = 0, step_sweeps = 3;
+    int debris = 0, debris_density = 256;   // --debris RADIUS [--density D]
     bool shadow_models = false, light_shadows = false, occluders_far = false;
     float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
@@ -50,6 +51,7 @@ int run_entity_sweeps(const Options& o, const World& w);
 int run_boxes(const Options& o, const World& w);
 int run_particles(const Options& o, const World& w);
 int run_simulate(const Options& o, const World& w);
+int run_debris(const Options& o, const World& w);
 int run_models(const Options& o, const World& w);
 int run_lights(const Options& o, const World& w);
 int run_shadows(const Options& o, const World& w);

@@ -14,6 +14,7 @@
 //            [--rays N [--rays-coherent]]
 //            [--boxes N]
 //            [--particles N [--particle-half H] [--particle-near D] [--simulate T [--sweeps S]]]
+//            [--debris RADIUS [--density D]]
 //            [--entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--entity-sweeps N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--lights N] [--shadows N [--shadow-models]]
@@ -68,7 +69,7 @@
 // (rt_get_accumulation) show whether the history went on.
 //
 // Instead of the frame loop, in this order of precedence: --light-shadows, --entity-rays N, --entity-sweeps N, --rays N, --particles N --simulate T,
-// --particles N, --boxes N, --models N, --shadows N, --lights N (bench_modes.cpp).
+// --debris RADIUS, --particles N, --boxes N, --models N, --shadows N, --lights N (bench_modes.cpp).
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -269,6 +270,8 @@ int parse_options(int argc, char** argv, Options& o, std::vector<const char*>& p
         else if (want("--particle-near")) o.particle_near = std::strtof(argv[++i], nullptr);
         else if (want("--simulate")) o.simulate = std::atoi(argv[++i]);
         else if (want("--sweeps")) o.step_sweeps = std::atoi(argv[++i]);
+        else if (want("--debris")) o.debris = std::atoi(argv[++i]);
+        else if (want("--density")) o.debris_density = std::atoi(argv[++i]);
         else if (is("--light-shadows")) o.light_shadows = true;
         else if (want("--occluder-spread")) o.occluder_spread = std::strtof(argv[++i], nullptr);
         else if (is("--occluders-far")) o.occluders_far = true;
@@ -293,6 +296,7 @@ int parse_options(int argc, char** argv, Options& o, std::vector<const char*>& p
         return bad("--simulate must be in 0..100000 and goes with --particles (--particle-half at most 4), --sweeps in 1..4");
     if (o.models < -1 || o.models > 4096 || !(o.model_scale >= 1.0f / 256.0f && o.model_scale <= 64.0f))
         return bad("--models must be in 0..4096, --model-scale in 2^-8..64");
+    if (o.debris < 0 || o.debris > 127 || o.debris_density < 1 || o.debris_density > 256) return bad("--debris must be in 0..127, --density in 1..256");
     if (o.particles < -1 || o.particles > (1ll << 20) || !(o.particle_half > 0.0f && o.particle_half <= 4096.0f) ||
         !(o.particle_near > 0.0f && o.particle_near <= 65536.0f))
         return bad("--particles must be in 0..2^20, --particle-half in (0, 4096], --particle-near in (0, 65536]");
@@ -343,6 +347,7 @@ int main(int argc, char** argv) {
     if (o.entity_sweeps > 0) return run_entity_sweeps(o, world);
     if (o.rays > 0) return run_rays(o, world);
     if (o.particles >= 0 && o.simulate > 0) return run_simulate(o, world);
+    if (o.debris > 0) return run_debris(o, world);
     if (o.particles >= 0) return run_particles(o, world);
     if (o.boxes >= 0) return run_boxes(o, world);
     if (o.models >= 0) return run_models(o, world);

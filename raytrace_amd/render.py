@@ -600,6 +600,29 @@ class Context:
         n = particle_step_tensor_count(states_in, states_out, draw, self._device)
         self._check(self._lib.rt_step_particles_async(self._h, C.byref(params), _dp(states_in), _dp(states_out), _dp(draw), n))
 
+    # -- particle emitters --------------------------------------------------------------------------------
+    def emit_particles(self, emitters, lr, states, max_emit, cursor):
+        """rt_emit_particles: one particle per occupied voxel that `emitters` (abi.EMIT_DTYPE records, make_particle_emitters) select,
+        written into the ring `states` (abi.PARTICLE_STATE_DTYPE[capacity]) from the slot `cursor` (an abi.EMIT_CURSOR_DTYPE record,
+        an abi.RtEmitCursor or (next, emitted, dropped)) points at, at most `max_emit` of them -> (states, cursor): the ring after the
+        call and the cursor as an abi.EMIT_CURSOR_DTYPE record, both new.  Synchronous; an invalid emitter fails the whole call
+        (RtError, INVALID_ARG)."""
+        emitters = _records(emitters, abi.EMIT_DTYPE)
+        ring = _records(states, abi.PARTICLE_STATE_DTYPE).copy()
+        cur = emit_cursor(cursor)
+        self._check(self._lib.rt_emit_particles(self._h, _ptr_or_none(emitters), emitters.size, _lr3(lr), _ptr_or_none(ring), ring.size,
+                                                int(max_emit), _p(cur)))
+        return ring, cur[0]
+
+    def emit_particles_async(self, emitters, lr, states_t, max_emit, cursor_t):
+        """rt_emit_particles_async on torch device tensors: `states_t` any contiguous tensor of capacity * 64 bytes (RtParticleState
+        rows: the ring), `cursor_t` one of 16 bytes (RtEmitCursor); `emitters` host records as for emit_particles.  Enqueued: valid
+        after sync(), or in the order of a stream given to set_stream(); a second call chains on the device's cursor."""
+        emitters = _records(emitters, abi.EMIT_DTYPE)
+        capacity = emit_tensor_capacity(states_t, cursor_t, self._device)
+        self._check(self._lib.rt_emit_particles_async(self._h, _ptr_or_none(emitters), emitters.size, _lr3(lr), _dp(states_t), capacity,
+                                                      int(max_emit), _dp(cursor_t)))
+
     # -- voxel-model entities ----------------------------------------------------------------------------
     def draw_stamps(self, uniforms, models, face_lights):
         """rt_draw_stamps: `models` DRAW_STAMP_DTYPE[N] records (make_draw_stamps) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
@@ -1363,6 +1386,80 @@ def particle_step_tensor_count(states_in, states_out, draw, device):
             if a0 < b1 and b0 < a1 and not (na == "states_in" and nb == "states_out" and a0 == b0):
                 raise ValueError("%s and %s overlap (only states_out may be states_in's memory, whole)" % (na, nb))
     return n
+
+
+def make_particle_emitters(shapes, origins, speeds=0.0, drifts=0.0, spreads=0.0, halves=0.125, life_mins=np.inf, life_spans=0.0, densities=256,
+                           responses=abi.RT_PARTICLE_DIE, seeds=0, lights=0, emissions=0xFF000000):
+    """RtParticleEmit records (abi.EMIT_DTYPE) from `shapes` — SHAPE_DTYPE rows or a sequence of box_shape / sphere_shape rows, of which
+    a, b and kind are read — float[N, 3] blast centres, and per emitter (one value serves all) the radial speed, float[3] drift, jitter
+    amplitude, half edge, least life and its random span in seconds, density 1..256, RT_PARTICLE_* response, hash seed, light index
+    and RGBA8 emission word.  Refuses what the calls refuse of these fields: more than 256 emitters, a non-finite float (life_min may
+    be inf), half outside [2^-8, 0.5], speed or spread outside [0, 4096], |drift| above 4096, |origin| above 2^22, life_min <= 0,
+    life_span outside [0, 4096], density outside 1..256, response above 3.  The shape itself is judged by the call (it needs R)."""
+    shapes = _rows(shapes, SHAPE_DTYPE)
+    n = shapes.size
+    if n > abi.MAX_EMITTERS:
+        raise ValueError("at most %d emitters per call" % abi.MAX_EMITTERS)
+    e = np.zeros(n, dtype=abi.EMIT_DTYPE)
+    e["a"], e["b"], e["kind"] = shapes["a"], shapes["b"], shapes["kind"]
+    e["origin"] = np.broadcast_to(np.asarray(origins, dtype=np.float32), (n, 3))
+    e["drift"] = np.broadcast_to(np.asarray(drifts, dtype=np.float32), (n, 3))
+    for name, v in (("speed", speeds), ("spread", spreads), ("half", halves), ("life_min", life_mins), ("life_span", life_spans)):
+        e[name] = np.broadcast_to(np.asarray(v, dtype=np.float32), (n,))
+    densities = np.broadcast_to(np.asarray(densities, dtype=np.int64), (n,))
+    responses = np.broadcast_to(np.asarray(responses, dtype=np.int64), (n,))
+    if ((densities < 1) | (densities > 256)).any():
+        raise ValueError("density must be 1..256")
+    if ((responses < 0) | (responses > abi.RT_PARTICLE_BOUNCE)).any():
+        raise ValueError("response must be an RT_PARTICLE_* value")
+    e["density"], e["response"] = densities, responses
+    for name, v in (("seed", seeds), ("light", lights), ("emission", emissions)):
+        e[name] = np.broadcast_to(np.asarray(v, dtype=np.uint32), (n,))
+    finite = [e[k] for k in ("origin", "drift", "speed", "spread", "half", "life_span")]
+    if not all(np.isfinite(v).all() for v in finite) or np.isnan(e["life_min"]).any():
+        raise ValueError("every float must be finite (life_min may be inf)")
+    if ((e["half"] < np.float32(2.0 ** -8)) | (e["half"] > np.float32(0.5))).any():
+        raise ValueError("half must be in [2^-8, 0.5]")
+    if ((e["speed"] < 0) | (e["speed"] > 4096) | (e["spread"] < 0) | (e["spread"] > 4096)).any():
+        raise ValueError("speed and spread must be in [0, 4096]")
+    if (np.abs(e["drift"]) > 4096).any():
+        raise ValueError("drift must lie within +-4096")
+    if (np.abs(e["origin"]) > 2.0 ** 22).any():
+        raise ValueError("origin must lie within +-2^22")
+    if not (e["life_min"] > 0).all():
+        raise ValueError("life_min must be positive")
+    if ((e["life_span"] < 0) | (e["life_span"] > 4096)).any():
+        raise ValueError("life_span must be in [0, 4096]")
+    return e
+
+
+def emit_cursor(cursor=(0, 0, 0)):
+    """The cursor of Context.emit_particles as one abi.EMIT_CURSOR_DTYPE record in an array of its own: from such a record, an
+    abi.RtEmitCursor or (next, emitted, dropped)."""
+    cur = np.zeros(1, dtype=abi.EMIT_CURSOR_DTYPE)
+    if isinstance(cursor, abi.RtEmitCursor):
+        cur[0] = (cursor.next, cursor.emitted, cursor.dropped, cursor.reserved)
+    elif isinstance(cursor, (np.ndarray, np.void)) and cursor.dtype == abi.EMIT_CURSOR_DTYPE:
+        cur[0] = np.asarray(cursor).reshape(-1)[0]
+    else:
+        nxt, emitted, dropped = cursor
+        cur[0] = (int(nxt), int(emitted), int(dropped), 0)
+    return cur
+
+
+def emit_tensor_capacity(states, cursor, device):
+    """Context.emit_particles_async's device arguments: `states` a contiguous tensor of capacity * 64 bytes with capacity in 1..2^20,
+    `cursor` one of exactly 16 bytes, both on GPU `device` and 16-byte aligned, not overlapping.  Returns the capacity; raises
+    ValueError otherwise (a host tensor's address handed to the kernel would fault the device)."""
+    _device_tensors(device, ("states", states), ("cursor", cursor))
+    capacity = record_count("states", _nbytes(states), abi.PARTICLE_STATE_DTYPE.itemsize, abi.MAX_EMIT_CAPACITY, "RtParticleState")
+    if capacity < 1:
+        raise ValueError("states must hold at least one record")
+    if _nbytes(cursor) != abi.EMIT_CURSOR_DTYPE.itemsize:
+        raise ValueError("cursor must be a contiguous tensor of 16 bytes (one RtEmitCursor)")
+    if states.data_ptr() < cursor.data_ptr() + 16 and cursor.data_ptr() < states.data_ptr() + _nbytes(states):
+        raise ValueError("states and cursor overlap")
+    return capacity
 
 
 def check_shadow_box_tensor(boxes, device):
