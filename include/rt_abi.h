@@ -970,6 +970,72 @@ int rt_emit_particles(RtContext* ctx, const RtParticleEmit* emitters, uint32_t c
 int rt_emit_particles_async(RtContext* ctx, const RtParticleEmit* emitters, uint32_t count, const int32_t lr[3], RtParticleState* states_dev,
                             uint32_t capacity, uint32_t max_emit, RtEmitCursor* cursor_dev);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Particle deposits: particles that have come to rest become voxels of
+ * the resident region, on the device — rubble where the debris of an explosion lands, snow cover under snowfall, sand poured from a
+ * tool.  Without this call a STICK particle stays a particle until its life runs out; a host that wants the pile must read 64 bytes
+ * per particle back (which drains the pipeline), pick the resting ones, call rt_edit_voxels and upload the ring again with the dead
+ * marked.  rt_emit_particles_async -> rt_edit_shapes (carve) -> rt_step_particles_async -> rt_deposit_particles_async ->
+ * rt_probe_light_async -> rt_draw_particles_async runs without a host read.  The parameters of one call, 48 bytes: */
+typedef struct RtParticleDeposit {   /* 48 bytes */
+    int32_t lo[3];  float    max_speed;   /*  0  box of texels, inclusive, as a RT_SHAPE_BOX's a; rest threshold, units per second */
+    int32_t hi[3];  uint32_t reserved0;   /* 16  as a RT_SHAPE_BOX's b; must be 0                                               */
+    int32_t lr[3];  uint32_t reserved1;   /* 32  the window, as rt_step_particles'; must be 0                                   */
+} RtParticleDeposit;
+/* What a call did, 16 bytes, in host memory for rt_deposit_particles and in device memory for rt_deposit_particles_async: */
+typedef struct RtDepositCount { uint32_t deposited, voxels, occupied, outside; } RtDepositCount;   /* 16 bytes */
+/* The rules.  Results are reproduced bit for bit by tests/deposit_particles_ref.py, which applies the world change through
+ * tests/voxel_edits.py and clips the box through tests/shape_edits.py (DESIGN.md "Particle deposits").
+ *   Box: lo / hi mean what a RT_SHAPE_BOX's a / b mean — texels, inclusive — with the same validity (|lo_k|, |hi_k| <= 4 R, lo_k <=
+ *     hi_k) and the same clipping to [0, R)^3.  The clipped box covers at most 2^24 texels, else RT_ERR_INVALID_ARG.  A host covers
+ *     the window's seam with a second call whose box is shifted by +-R, as for shapes.
+ *   Candidate: record i is a candidate iff DEAD and INVALID are clear, (flags & RT_PSTATE_CONTACT) != 0, |velocity_k| <= max_speed
+ *     on every axis, and every lo_k, hi_k is finite with |.| <= 2^22.  Any comparison with a NaN is false.  STICK particles have
+ *     velocity 0 and pass with max_speed = 0; BOUNCE and SLIDE debris passes once it has come to rest under rest_speed and friction.
+ *   Target: c_k = (lo_k + hi_k) * 0.5f (fp32, one rounding each), v_k = (int)floorf(c_k): the world voxel that holds the box's
+ *     centre.  Its texel is the emit's and the sweeps': x_k = (v_k + R/2) mod R (Euclidean), valid only if lr_k - R/2 <= v_k < lr_k
+ *     + R/2.  lr must satisfy |lr_k| <= 2^22 - R, as for rt_emit_particles, else RT_ERR_INVALID_ARG.
+ *   Outcome of a candidate: target outside the window or outside the clipped box: outside += 1 and nothing else.  Otherwise, the
+ *     target's minefield byte is 0 at the moment the call runs in stream order, before any deposit of this call: occupied += 1 and
+ *     nothing else.  Otherwise the record DEPOSITS: deposited += 1.
+ *   Writes of a depositing record: RT_PSTATE_DEAD is ORed into its flags; if `draw` is non-NULL the 4 bytes draw[i].half become
+ *     +0.0f (rt_draw_particles skips the record).  No other byte of `states` or `draw` changes, for any record.
+ *   World: every texel targeted by at least one depositing record becomes occupied, and its material word becomes the `material`
+ *     of the depositing record with the LOWEST INDEX; voxels += the number of such texels.  Every 64^3 chunk that holds at least one
+ *     of them has its minefield rebuilt by rt_edit_voxels' rule — in such a chunk the result equals rt_edit_voxels with one solid = 1
+ *     record per deposited texel — and no other chunk's bytes change.  The coarse / brick nibble-map words over the clipped box's
+ *     chunks are rebuilt: rt_selftest(RT_SELFTEST_SCENE_MAPS) counts 0 afterwards.
+ *   Counts: the four RtDepositCount fields are ADDED to (wrapping uint32); `counts` may be NULL.  The winner of a texel is a minimum
+ *     and the counts are sums of integers, neither of which depends on arrival order: two runs give equal bits everywhere.
+ *   Ordering: the call is a world change with rt_edit_shapes' stream order, lane join, fence and staging.  It waits for the queries
+ *     and steps already enqueued, so a deposit enqueued behind rt_step_particles_async reads that step's states; later frames,
+ *     queries and steps see the new world and the new flags.
+ *   Side effects: rt_edit_shapes' for ONE box shape equal to the box, whenever the clipped box is non-empty and count > 0 — whether
+ *     or not anything deposits, because the host cannot know: the accumulation restarts, or with RtConfig.edit_radius one box (the
+ *     clipped box) waits for the next frame.  A host with a kept history deposits every few ticks and keeps the box tight round
+ *     where its particles land.  (Bounds found on the device, as the slabs', are the follow-up.)
+ *   Errors: NULL ctx, NULL params, NULL states with count > 0, count > 2^20, a non-finite or negative max_speed, a reserved word !=
+ *     0, a bad box or window: RT_ERR_INVALID_ARG.  states, draw and counts must not overlap (RT_ERR_INVALID_ARG).  No world
+ *     resident: RT_ERR_NOT_READY.  count == 0 or an empty clipped box: RT_OK, nothing enqueued or reset.  A rejected call changes
+ *     nothing.  Tile contexts, every RtKernel and every region size answer as rt_edit_shapes does.
+ *   Consequence: a live particle whose box overlaps a freshly deposited voxel is EMBEDDED at its next step and dies, by the step's
+ *     existing rule ("Particle simulation", Sub-sweeps).  Nothing in the step changes.
+ *   Out of scope: history bounds found on the device; particles larger than a voxel deposited into several voxels; falling or
+ *     unsupported voxels.
+ *   Device work per call: the box's chunk ids through an edit staging set, one fill of the scratch (4 bytes per texel of the clipped
+ *     box, at most 64 MiB, that the context keeps: RtInfo.device_bytes), then three launches — claim (a lane per particle: 48 bytes
+ *     read, one minefield byte, one atomic per depositing lane), chunks (a workgroup per chunk of the box; one that holds no deposit
+ *     returns at once) and rt_edit_voxels' nibble-map rebuild.
+ * Host pointers: states (and a non-NULL draw) go through the pinned block, the same launches run, and states, draw and counts are
+ * copied back; returns when they are in host memory.  The world change itself stays stream-ordered. */
+int rt_deposit_particles(RtContext* ctx, const RtParticleDeposit* params, RtParticleState* states, RtParticle* draw, uint32_t count,
+                         RtDepositCount* counts);
+/* Same with device pointers, enqueued: states_dev, draw_dev and counts_dev are valid after rt_sync (or, after rt_set_stream, in the
+ * caller's stream order); `params` is a host pointer, free again when the call returns.  states_dev and a non-NULL draw_dev or
+ * counts_dev must pass rt_trace_rays_async's test (16-byte aligned memory of the context's device, or managed memory), else
+ * RT_ERR_INVALID_ARG before anything is enqueued. */
+int rt_deposit_particles_async(RtContext* ctx, const RtParticleDeposit* params, RtParticleState* states_dev, RtParticle* draw_dev,
+                               uint32_t count, RtDepositCount* counts_dev);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
  * after rt_draw_frame (and rt_draw_boxes) and before or after rt_denoise.  Each light reaches a pixel through one hard shadow ray
@@ -1561,7 +1627,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtEntitySweepHit, rt_sweep_entities, rt_sweep_entities_async (entity sweeps: box sweeps that
  *        collide with the drawn boxes and models as well as with the world).
  *        Additive, same minor version: RtParticleEmit, RtEmitCursor, rt_emit_particles, rt_emit_particles_async (particle emitters:
- *        debris spawned on the device from the occupied voxels of a shape, into a ring of particle states). */
+ *        debris spawned on the device from the occupied voxels of a shape, into a ring of particle states).
+ *        Additive, same minor version: RtParticleDeposit, RtDepositCount, rt_deposit_particles, rt_deposit_particles_async (particle
+ *        deposits: particles at rest become voxels of the region on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -281,6 +281,42 @@ MAX_EMITTERS = 256                             # rt_emit_particles: emitters per
 MAX_EMIT_CAPACITY = 1 << 20                    # ... and slots of the ring
 
 
+class RtParticleDeposit(C.Structure):
+    """rt_deposit_particles' parameters (ABI 1.3, additive: particle deposits): 48 bytes; the reserved words must be 0."""
+    _fields_ = [("lo", C.c_int32 * 3), ("max_speed", C.c_float), ("hi", C.c_int32 * 3), ("reserved0", C.c_uint32), ("lr", C.c_int32 * 3),
+                ("reserved1", C.c_uint32)]
+
+
+class RtDepositCount(C.Structure):
+    """rt_deposit_particles' counters: 16 bytes, added to by every call."""
+    _fields_ = [("deposited", C.c_uint32), ("voxels", C.c_uint32), ("occupied", C.c_uint32), ("outside", C.c_uint32)]
+
+
+assert C.sizeof(RtParticleDeposit) == 48 and C.sizeof(RtDepositCount) == 16
+assert (RtParticleDeposit.max_speed.offset, RtParticleDeposit.hi.offset, RtParticleDeposit.reserved0.offset, RtParticleDeposit.lr.offset,
+        RtParticleDeposit.reserved1.offset) == (12, 16, 28, 32, 44)
+DEPOSIT_DTYPE = np.dtype(RtParticleDeposit)        # the numpy view of the parameters
+DEPOSIT_COUNT_DTYPE = np.dtype(RtDepositCount)     # ... and of the counters
+MAX_DEPOSIT_TEXELS = 1 << 24                       # rt_deposit_particles: texels of the clipped box
+
+
+def make_particle_deposit(lo, hi, max_speed=0.0, lr=(0, 0, 0)):
+    """An RtParticleDeposit: the box `lo`..`hi` of texels (inclusive, as a box shape's a and b), the rest threshold `max_speed` in units
+    per second and the window `lr`.  Refuses what the calls refuse without knowing R: a box with lo > hi, a non-finite or negative
+    max_speed.  The box's range and the window's bound are judged by the call (they need R)."""
+    if len(lo) != 3 or len(hi) != 3 or len(lr) != 3:
+        raise ValueError("lo, hi and lr have three components")
+    p = RtParticleDeposit()
+    for k in range(3):
+        p.lo[k], p.hi[k], p.lr[k] = int(lo[k]), int(hi[k]), int(lr[k])
+        if p.lo[k] > p.hi[k]:
+            raise ValueError("the box needs lo <= hi on every axis")
+    p.max_speed = float(max_speed)
+    if not (p.max_speed >= 0.0 and p.max_speed != float("inf")):
+        raise ValueError("max_speed must be finite and not negative")
+    return p
+
+
 class RtDrawStamp(C.Structure):
     """rt_draw_stamps input (ABI 1.3, additive: voxel-model entities): 32 bytes; the reserved fields must be 0."""
     _fields_ = [("origin", C.c_float * 3), ("scale", C.c_float), ("stamp", C.c_uint32), ("orient", C.c_uint8), ("reserved0", C.c_uint8 * 3),

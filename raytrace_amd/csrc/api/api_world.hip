@@ -1,6 +1,7 @@
 // api_world.hip — the kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits, shape
-// edits, voxel stamps (their store, capture and placement) and terrain generated on the device; rt_read_box reads the resident
-// region back.
+// edits, voxel stamps (their store, capture and placement), particle deposits and terrain generated on the device; rt_read_box reads
+// the resident region back.
+#include "deposit_check.hpp"
 #include "rt_context.hpp"
 
 using namespace rta;
@@ -134,6 +135,73 @@ void stamp_free(RtContext* c, StampEntry* e) {
     (void)hipFree(reinterpret_cast<void*>(e->mats));
     (void)hipFree(reinterpret_cast<void*>(e->state));
     c->stamps.remove(e);
+}
+
+// ---- particle deposits (rt_deposit_particles[_async]): a world change whose targets only the device knows -----------------------
+static_assert(sizeof(RtParticleDeposit) == 48 && sizeof(RtDepositCount) == 16, "the layout the header states");
+static_assert(kMaxDepositParticles == rtd::kMaxParticles && kMaxDepositBoxTexels == rtd::kMaxDepositTexels, "the host's limits are the kernels'");
+
+// checks shared by the two calls, and the plan; RT_OK when there is work to enqueue, 1 for a call that enqueues nothing
+int deposit_check(RtContext* c, const char* fn, const RtParticleDeposit* p, const void* states, const void* draw, uint32_t count, const void* counts,
+                  DepositPlan* plan) {
+    const char* e = deposit_args_error(p, states, draw, count, counts);
+    if (!e) e = deposit_params_error(*p, c->logr);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e + "; nothing was applied");
+    *plan = deposit_plan(*p, c->logr);
+    if (plan->texels > kMaxDepositBoxTexels) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": the clipped box covers more than 2^24 texels; nothing was applied");
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    return count == 0u || plan->empty ? 1 : RT_OK;
+}
+
+// The call's launches on the render stream between world_change_begin and world_change_end, with rt_edit_shapes' staging (the box's
+// chunk ids), counter and side effects for one box shape equal to the box.  The pointers are device addresses the stream may use.
+int deposit_run(RtContext* c, const RtParticleDeposit& p, const DepositPlan& plan, void* states_dev, void* draw_dev, void* counts_dev, uint32_t count) {
+    const size_t words = deposit_scratch_need(plan);
+    int rc = deposit_scratch_reserve(c, words);
+    if (rc != RT_OK) return rc;
+    StagingSet& s = c->edit_sets[c->edit_batches & 1u];
+    RT_HIP(c, staging_claim(c, s, plan.need, staging_alloc(plan.need)));
+    deposit_fill_chunks(plan, c->logr, reinterpret_cast<uint32_t*>(s.host));
+    c->edit_batches++;
+    if (c->edit_radius == 0u) {
+        c->accum_valid = false;
+    } else if (!c->edit_overflow) {
+        // the history stays: the clipped box waits for the next frame drawn (rt_edit_voxels' set and rule)
+        if (c->edit_nbox + 1u > rtd::kTemporalMaxBoxes) {
+            c->edit_nbox = 0;
+            c->edit_overflow = true;
+        } else {
+            c->edit_boxes[c->edit_nbox++] = plan.box;
+        }
+    }
+    invalidate_prepass(c);
+    RT_HIP(c, staging_send(c, s, plan.need));
+    rtd::DepositArgs a;
+    a.states = reinterpret_cast<uint4*>(states_dev);
+    a.draw = reinterpret_cast<uint4*>(draw_dev);
+    a.claims = c->deposit_scratch;
+    a.flags = c->deposit_scratch + plan.texels;
+    a.counts = counts_dev ? reinterpret_cast<uint32_t*>(counts_dev) : c->deposit_scratch + plan.texels + plan.nchunks;
+    a.count = count;
+    a.max_speed = p.max_speed;
+    for (int k = 0; k < 3; k++) { a.lr[k] = p.lr[k]; a.lo[k] = plan.box.lo[k]; a.hi[k] = plan.box.hi[k]; }
+    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
+    RT_HIP(c, c->ev_deposit.wait_elsewhere(c->stream));   // the scratch is the previous call's until its chunk pass has run
+    {
+        LaunchTimer lt(c, 1);
+        RT_HIP(c, hipMemsetAsync(c->deposit_scratch, 0xFF, words * sizeof(uint32_t), c->stream));
+    }
+    {
+        LaunchTimer lt(c, 1);
+        RT_HIP(c, rtd::launch_deposit_particles(c->d_mine_sw, c->d_mat_sw, d_chunks, plan.nchunks, c->logr, a, c->stream));
+    }
+    {
+        LaunchTimer lt(c, 1);
+        RT_HIP(c, rtd::launch_rebuild_chunk_maps(c->d_mine_sw, c->d_coarse, c->d_brick, d_chunks, plan.nchunks, c->logr, c->stream));
+    }
+    RT_HIP(c, c->ev_deposit.record(c->stream));
+    RT_HIP(c, staging_applied(c, s));
+    return RT_OK;
 }
 
 }  // namespace
@@ -353,6 +421,45 @@ int rt_edit_shapes(RtContext* ctx, const RtShapeEdit* shapes, uint32_t count) {
     }
     RT_HIP(ctx, staging_applied(ctx, s));
     return RT_OK;
+}
+
+int rt_deposit_particles(RtContext* ctx, const RtParticleDeposit* params, RtParticleState* states, RtParticle* draw, uint32_t count,
+                         RtDepositCount* counts) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    DepositPlan plan;
+    int rc = deposit_check(ctx, "rt_deposit_particles", params, states, draw, count, counts, &plan);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    // states, draw records and counts through the synchronous calls' pinned and device block on the render stream, the launches
+    // there, and all three back
+    const size_t state_bytes = (size_t)count * sizeof(RtParticleState), draw_bytes = draw ? (size_t)count * sizeof(RtParticle) : 0u;
+    const RtDepositCount before = counts ? *counts : RtDepositCount{0u, 0u, 0u, 0u};
+    uint8_t* dev[3];
+    rc = stage_sync(ctx, ctx->stream, {{states, state_bytes}, {&before, sizeof before}, {draw, draw_bytes}}, dev);
+    if (rc != RT_OK) return rc;
+    rc = deposit_run(ctx, *params, plan, dev[0], draw ? dev[2] : nullptr, dev[1], count);
+    if (rc != RT_OK) return rc;
+    const size_t bytes = (size_t)(dev[2] - dev[0]) + draw_bytes;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->query_block.host, ctx->query_block.dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(states, ctx->query_block.host, state_bytes);
+    if (counts) memcpy(counts, ctx->query_block.host + (dev[1] - dev[0]), sizeof *counts);
+    if (draw) memcpy(draw, ctx->query_block.host + (dev[2] - dev[0]), draw_bytes);
+    return RT_OK;
+}
+
+int rt_deposit_particles_async(RtContext* ctx, const RtParticleDeposit* params, RtParticleState* states_dev, RtParticle* draw_dev,
+                               uint32_t count, RtDepositCount* counts_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    DepositPlan plan;
+    int rc = deposit_check(ctx, "rt_deposit_particles_async", params, states_dev, draw_dev, count, counts_dev, &plan);
+    if (rc != RT_OK && rc != 1) return rc;
+    if (count == 0) return RT_OK;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!query_device_ptr(ctx, states_dev) || (draw_dev && !query_device_ptr(ctx, draw_dev)) || (counts_dev && !query_device_ptr(ctx, counts_dev)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_deposit_particles_async: states, draw and counts must be 16-byte aligned memory of the context's device");
+    if (rc == 1) return RT_OK;
+    return deposit_run(ctx, *params, plan, states_dev, draw_dev, counts_dev, count);
 }
 
 int rt_stamp_create(RtContext* ctx, const int32_t extent[3], const uint32_t* materials, const uint8_t* state, uint32_t* id_out) {

@@ -341,6 +341,12 @@ struct __attribute__((visibility("hidden"))) RtContext {
     uint32_t* emit_scratch = nullptr;
     size_t emit_scratch_words = 0;
     rta::LatchEvent ev_emit;
+    // rt_deposit_particles[_async]: a claim word per texel of the clipped box, a flag word per chunk of it and a spare count record
+    // (rtd::deposit_scratch_words; at most 64 MiB and a little), grown on demand and never shrunk, in c->allocs (device_bytes; freed by
+    // rt_destroy).  Every call uses it on the render stream or behind a lane join, so its launches follow the previous call's.
+    uint32_t* deposit_scratch = nullptr;
+    size_t deposit_scratch_words = 0;
+    rta::LatchEvent ev_deposit;
 };
 
 namespace rta __attribute__((visibility("hidden"))) {
@@ -450,11 +456,14 @@ inline int scratch_reserve(RtContext* c, uint32_t** block, size_t* have, LatchEv
     *have = words;
     return RT_OK;
 }
-// rt_draw_particles' binning scratch and rt_emit_particles' masks and particle numbers
+// rt_draw_particles' binning scratch, rt_emit_particles' masks and particle numbers and rt_deposit_particles' claims and flags
 inline int particle_scratch_reserve(RtContext* c, size_t words) {
     return scratch_reserve(c, &c->particle_scratch, &c->particle_scratch_words, &c->ev_particles, words);
 }
 inline int emit_scratch_reserve(RtContext* c, size_t words) { return scratch_reserve(c, &c->emit_scratch, &c->emit_scratch_words, &c->ev_emit, words); }
+inline int deposit_scratch_reserve(RtContext* c, size_t words) {
+    return scratch_reserve(c, &c->deposit_scratch, &c->deposit_scratch_words, &c->ev_deposit, words);
+}
 
 // An environment knob (experiments, A/B timing): *field = v when `s` holds an integer in lo..hi; anything else is ignored.
 template <typename T>

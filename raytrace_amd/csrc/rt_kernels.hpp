@@ -249,6 +249,27 @@ struct EmitParticlesArgs {
 inline size_t emit_scratch_words(uint32_t items) { return 4u + 3u * (size_t)items; }
 hipError_t launch_emit_particles(const Scene& sc, int logr, const EmitParticlesArgs& a, hipStream_t st);
 
+// rt_deposit.hip: resting particles into voxels of the region (rt_deposit_particles).  Two launches — claim (a lane per particle)
+// and chunks (a workgroup per chunk of the clipped box, the chunk rebuild of rt_edit_voxels) — over a scratch the caller has filled
+// with 0xFF bytes: one claim word per texel of the box (x fastest in box coordinates), then one flag word per chunk of the box
+// (z-major: the order of the ascending chunk list), then a spare RtDepositCount for a call without counts.
+constexpr uint64_t kMaxDepositTexels = 1ull << 24;   // texels of the clipped box
+struct DepositArgs {
+    uint4* states;         // RtParticleState[count] (four uint4 each): flags are updated in place
+    uint4* draw;           // RtParticle[count] (two uint4 each) or nullptr
+    uint32_t* counts;      // RtDepositCount (never nullptr: the scratch's spare where the caller gave none)
+    uint32_t* claims;      // the scratch: texels words ...
+    uint32_t* flags;       // ... and chunk words behind them
+    uint32_t count;        // 1..kMaxParticles
+    float max_speed;
+    int32_t lr[3];
+    int32_t lo[3], hi[3];  // the clipped box, texels, inclusive
+};
+inline size_t deposit_scratch_words(uint64_t texels, uint32_t nchunks) { return (size_t)texels + nchunks + 4u; }
+// `chunks`: the ids of the box's nchunks chunks, ascending
+hipError_t launch_deposit_particles(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, uint32_t nchunks, int logr, const DepositArgs& a,
+                                    hipStream_t st);
+
 // rt_boxes.hip: entity boxes composited into a whole frame's row-major planes by depth (rt_draw_boxes).  One launch for the batch;
 // a wave owns an 8x8 pixel tile.
 struct DrawBoxesArgs {

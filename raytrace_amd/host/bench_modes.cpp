@@ -547,6 +547,152 @@ int run_debris(const Options& o, const World& w) {
     return 0;
 }
 
+// --debris RADIUS --settle T [--density D]: particle deposits.  --debris' explosion with RT_PARTICLE_STICK debris: emit, carve, then T
+// ticks of rt_step_particles_async -> rt_deposit_particles_async -> rt_draw_particles_async with no host read, each of the three
+// calls between events of its own; the deposit box is the explosion's bounding box grown by 32 texels.  Then the region's box is put
+// back as it was (a stamp captured before the run) and the same T ticks run with the host path the deposit replaces, call to usable
+// device state: the ring read back, the box's minefield read back (rt_read_box), the resting particles selected and turned into
+// RtVoxelEdit records, rt_edit_voxels, the ring uploaded again with the dead marked.  The mode fails if the host path deposits a
+// different number of voxels than the device's counts say.
+int run_settle(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const HipEvents hip;
+    if (!hip.ok) { std::fprintf(stderr, "--settle needs the HIP runtime for its device buffers\n"); return 1; }
+    const int R = RT_ROOT_BLOCK_SIZE, radius = o.debris, ticks = o.settle;
+    const int32_t* lr = s.u().lr;
+    const int32_t centre_px[2] = {o.width / 2, o.height / 2};
+    RtRayHit hit{};
+    int rc = rt_pick_pixels(s.ctx, &s.u(), centre_px, 1, &hit);
+    if (rc != RT_OK) return s.fail("settle", rc);
+    int c[3] = {R / 2, R / 2, R / 2};
+    if (hit.kind == RT_HIT_SOLID) for (int a = 0; a < 3; a++) c[a] = hit.texel[a];
+    RtParticleEmit e{};
+    RtParticleDeposit dep{};
+    int32_t lo[3], ext[3];
+    for (int a = 0; a < 3; a++) {
+        e.a[a] = 2 * c[a] + 1;
+        e.origin[a] = (float)(lr[a] - R / 2 + (((c[a] - lr[a]) % R + R) % R)) + 0.5f;
+        lo[a] = c[a] - radius - 32 < 0 ? 0 : c[a] - radius - 32;
+        const int hi = c[a] + radius + 32 > R - 1 ? R - 1 : c[a] + radius + 32;
+        ext[a] = hi - lo[a] + 1;
+        dep.lo[a] = lo[a]; dep.hi[a] = hi; dep.lr[a] = lr[a];
+    }
+    e.b[0] = 4 * radius * radius; e.kind = RT_SHAPE_SPHERE; e.response = RT_PARTICLE_STICK; e.seed = 0x5EEDu;
+    e.speed = 12.0f; e.spread = 3.0f; e.drift[2] = 4.0f; e.half = 0.125f; e.life_min = 30.0f; e.life_span = 2.0f;
+    e.density = (uint32_t)o.debris_density; e.emission = 0xFF000000u;
+    RtShapeEdit carve{};
+    for (int a = 0; a < 3; a++) { carve.a[a] = e.a[a]; carve.b[a] = e.b[a]; }
+    carve.kind = RT_SHAPE_SPHERE; carve.where = RT_WHERE_ALL; carve.solid = 0;
+    RtParticleStep step{};
+    step.dt = 1.0f / 60.0f; step.accel[2] = -32.0f; step.damping = 1.0f; step.restitution = 0.5f; step.friction = 0.75f; step.rest_speed = 0.5f;
+    for (int a = 0; a < 3; a++) step.lr[a] = lr[a];
+    step.sweeps = (uint32_t)o.step_sweeps;
+    const uint32_t capacity = 1u << 20;
+
+    uint32_t undo = 0;
+    rc = rt_stamp_capture(s.ctx, lo, ext, 0u, &undo);
+    RtProbeLight light{};
+    const RtLightProbe probe = sphere_probe(0, e.origin);
+    if (rc == RT_OK) rc = rt_probe_light(s.ctx, &s.u(), &probe, 1, 4, 2, &light);
+    if (rc != RT_OK) return s.fail("settle", rc);
+    RtStampPlace back{};
+    for (int a = 0; a < 3; a++) back.at[a] = lo[a];
+    back.stamp = undo; back.where = RT_WHERE_ALL;
+
+    DeviceRun run(hip, s.ctx);
+    const RtEmitCursor zero{0u, 0u, 0u, 0u};
+    const RtDepositCount none{0u, 0u, 0u, 0u};
+    RtParticleState* d_ring = (RtParticleState*)run.on_device(nullptr, (size_t)capacity * sizeof(RtParticleState));
+    RtEmitCursor* d_cursor = (RtEmitCursor*)run.on_device(&zero, sizeof zero);
+    RtParticle* d_draw = (RtParticle*)run.on_device(nullptr, (size_t)capacity * sizeof(RtParticle));
+    RtDepositCount* d_counts = (RtDepositCount*)run.on_device(&none, sizeof none);
+    const RtProbeLight* d_light = (const RtProbeLight*)run.on_device(&light, sizeof light);
+    run.start();
+
+    // ---- the device path -------------------------------------------------------------------------------------------------------
+    RtEmitCursor after{};
+    run.fine = run.fine && rt_draw_frame(s.ctx, &s.u()) == RT_OK &&
+               rt_emit_particles_async(s.ctx, &e, 1, lr, d_ring, capacity, capacity, d_cursor) == RT_OK && rt_edit_shapes(s.ctx, &carve, 1) == RT_OK &&
+               rt_sync(s.ctx) == RT_OK && hip.copy(&after, d_cursor, sizeof after, 2 /* hipMemcpyDeviceToHost */) == 0;
+    const uint32_t live = after.emitted;
+    double step_ms = 0.0, deposit_ms = 0.0, draw_ms = 0.0;
+    for (int t = 0; t < ticks && run.fine && live; t++) {
+        float ms[3] = {0.0f, 0.0f, 0.0f};
+        run.fine = run.mark() && rt_step_particles_async(s.ctx, &step, d_ring, d_ring, d_draw, live) == RT_OK && run.lap(&ms[0]) &&
+                   run.mark() && rt_deposit_particles_async(s.ctx, &dep, d_ring, d_draw, live, d_counts) == RT_OK && run.lap(&ms[1]) &&
+                   run.mark() && rt_draw_particles_async(s.ctx, &s.u(), d_draw, live, d_light, 1) == RT_OK && run.lap(&ms[2]);
+        step_ms += (double)ms[0] / ticks; deposit_ms += (double)ms[1] / ticks; draw_ms += (double)ms[2] / ticks;
+    }
+    RtDepositCount counts{};
+    run.fine = run.fine && rt_sync(s.ctx) == RT_OK && hip.copy(&counts, d_counts, sizeof counts, 2) == 0;
+
+    // ---- the host path, on the region as it was ----------------------------------------------------------------------------------
+    run.fine = run.fine && rt_edit_stamps(s.ctx, &back, 1) == RT_OK && hip.copy(d_cursor, &zero, sizeof zero, 1) == 0 &&
+               rt_emit_particles_async(s.ctx, &e, 1, lr, d_ring, capacity, capacity, d_cursor) == RT_OK && rt_edit_shapes(s.ctx, &carve, 1) == RT_OK &&
+               rt_sync(s.ctx) == RT_OK;
+    std::vector<RtParticleState> ring(live);
+    const size_t nvox = (size_t)ext[0] * ext[1] * ext[2];
+    std::vector<uint8_t> box_mine(nvox);
+    std::vector<uint32_t> claim(nvox);
+    std::vector<RtVoxelEdit> edits;
+    uint64_t host_voxels = 0, host_deposited = 0;
+    double host_ms = 0.0;
+    for (int t = 0; t < ticks && run.fine && live; t++) {
+        run.fine = rt_step_particles_async(s.ctx, &step, d_ring, d_ring, d_draw, live) == RT_OK && rt_sync(s.ctx) == RT_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        run.fine = run.fine && hip.copy(ring.data(), d_ring, (size_t)live * sizeof(RtParticleState), 2) == 0 &&
+                   rt_read_box(s.ctx, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], nullptr, box_mine.data()) == RT_OK;
+        std::fill(claim.begin(), claim.end(), UINT32_MAX);
+        edits.clear();
+        for (uint32_t i = 0; i < live && run.fine; i++) {
+            RtParticleState& p = ring[i];
+            if ((p.flags & (RT_PSTATE_DEAD | RT_PSTATE_INVALID)) != 0u || (p.flags & RT_PSTATE_CONTACT) == 0u) continue;
+            bool ok = true;
+            int x[3];
+            for (int a = 0; a < 3 && ok; a++) {
+                ok = std::fabs(p.velocity[a]) <= dep.max_speed && std::fabs(p.lo[a]) <= 4194304.0f && std::fabs(p.hi[a]) <= 4194304.0f;
+                if (!ok) break;
+                const int v = (int)std::floor((p.lo[a] + p.hi[a]) * 0.5f);
+                ok = v >= lr[a] - R / 2 && v < lr[a] + R / 2;
+                x[a] = (v + R / 2) & (R - 1);
+                ok = ok && x[a] >= dep.lo[a] && x[a] <= dep.hi[a];
+            }
+            if (!ok) continue;
+            const size_t at = ((size_t)(x[2] - lo[2]) * ext[1] + (size_t)(x[1] - lo[1])) * ext[0] + (size_t)(x[0] - lo[0]);
+            if (box_mine[at] == 0u) continue;
+            p.flags |= RT_PSTATE_DEAD;
+            host_deposited++;
+            if (claim[at] != UINT32_MAX) continue;                     // (ascending i: the first is the lowest index)
+            claim[at] = i;
+            RtVoxelEdit ed{};
+            ed.x = (uint16_t)x[0]; ed.y = (uint16_t)x[1]; ed.z = (uint16_t)x[2]; ed.solid = 1; ed.material = p.material;
+            edits.push_back(ed);
+        }
+        host_voxels += edits.size();
+        run.fine = run.fine && rt_edit_voxels(s.ctx, edits.data(), (uint32_t)edits.size()) == RT_OK &&
+                   hip.copy(d_ring, ring.data(), (size_t)live * sizeof(RtParticleState), 1) == 0;
+        host_ms += ms_since(t0) / ticks;
+    }
+    if (run.fine) run.fine = rt_sync(s.ctx) == RT_OK && rt_stamp_destroy(s.ctx, undo) == RT_OK;
+    if (!run.close()) { std::fprintf(stderr, "settle failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    // the host path restates the rules: it is a baseline only while it deposits what the library deposits
+    if (host_voxels != counts.voxels || host_deposited != counts.deposited) {
+        std::fprintf(stderr, "settle: the host path deposited %llu particles into %llu voxels, the device %u into %u\n", (unsigned long long)host_deposited,
+                     (unsigned long long)host_voxels, counts.deposited, counts.voxels);
+        return 1;
+    }
+    const double tick_ms = step_ms + deposit_ms + draw_ms;
+    std::printf("{\"debris\": %d, \"settle\": %d, \"density\": %d, \"centre\": [%d, %d, %d], \"deposit_box\": [%d, %d, %d], \"particles\": %u, "
+                "\"frame\": \"%dx%d spp %d depth %d\", \"deposited\": %u, \"voxels\": %u, \"occupied\": %u, \"outside\": %u, \"host_voxels\": %llu, "
+                "\"step_device_ms\": %.4f, \"deposit_device_ms\": %.4f, \"draw_device_ms\": %.4f, \"tick_device_ms\": %.4f, \"deposit_share\": %.3f, "
+                "\"host_path_ms\": %.3f}\n",
+                radius, ticks, o.debris_density, c[0], c[1], c[2], ext[0], ext[1], ext[2], live, o.width, o.height, o.spp, o.depth, counts.deposited,
+                counts.voxels, counts.occupied, counts.outside, (unsigned long long)host_voxels, step_ms, deposit_ms, draw_ms, tick_ms,
+                tick_ms > 0.0 ? deposit_ms / tick_ms : 0.0, host_ms);
+    return 0;
+}
+
 // --models N [--model-scale S]: voxel-model entities.  One built-in 9 x 9 x 12 sparse stamp (about a third of its voxels solid; its
 // values are the generator's first) is drawn N times at scale S (default 1/8) — scattered like --boxes' boxes, in seeded
 // orientations, lit by their bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times;

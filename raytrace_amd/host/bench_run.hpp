@@ -29,6 +29,7 @@ struct Options {
     float particle_half = 0.0625f, particle_near = 10.0f;
     int simulate = 0, step_sweeps = 3;
     int debris = 0, debris_density = 256;   // --debris RADIUS [--density D]
+    int settle = 0;                         // --debris RADIUS --settle T
     bool shadow_models = false, light_shadows = false, occluders_far = false;
     float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
@@ -52,6 +53,7 @@ int run_boxes(const Options& o, const World& w);
 int run_particles(const Options& o, const World& w);
 int run_simulate(const Options& o, const World& w);
 int run_debris(const Options& o, const World& w);
+int run_settle(const Options& o, const World& w);
 int run_models(const Options& o, const World& w);
 int run_lights(const Options& o, const World& w);
 int run_shadows(const Options& o, const World& w);

@@ -623,6 +623,31 @@ class Context:
         self._check(self._lib.rt_emit_particles_async(self._h, _ptr_or_none(emitters), emitters.size, _lr3(lr), _dp(states_t), capacity,
                                                       int(max_emit), _dp(cursor_t)))
 
+    # -- particle deposits --------------------------------------------------------------------------------
+    def deposit_particles(self, params, states, draw=None, counts=None):
+        """rt_deposit_particles: the resting particles of `states` (abi.PARTICLE_STATE_DTYPE[N]) whose centre voxel lies in the box of
+        `params` (an abi.RtParticleDeposit, abi.make_particle_deposit) become voxels of the resident world -> (states, draw, counts):
+        the states with DEAD set on what was deposited, the abi.PARTICLE_DTYPE[N] draw records with those records' half cleared (None
+        when `draw` is None) and the abi.DEPOSIT_COUNT_DTYPE record `counts` (None starts from zeros) added to, all new arrays.
+        Synchronous for the arrays; the world change is stream-ordered."""
+        states = _records(states, abi.PARTICLE_STATE_DTYPE).copy()
+        if draw is not None:
+            draw = _records(draw, abi.PARTICLE_DTYPE).copy()
+            if draw.size != states.size:
+                raise ValueError("draw must hold one record per state")
+        cnt = deposit_counts(counts)
+        self._check(self._lib.rt_deposit_particles(self._h, C.byref(params), _ptr_or_none(states), None if draw is None else _ptr_or_none(draw),
+                                                   states.size, _p(cnt)))
+        return states, draw, cnt[0]
+
+    def deposit_particles_async(self, params, states_t, draw_t=None, counts_t=None):
+        """rt_deposit_particles_async on torch device tensors: `states_t` any contiguous tensor of N * 64 bytes (RtParticleState rows,
+        updated in place), `draw_t` one of N * 32 bytes (RtParticle rows) or None, `counts_t` one of 16 bytes (RtDepositCount, added
+        to) or None.  Enqueued behind the steps and queries already enqueued: valid after sync(), or in the order of a stream given
+        to set_stream()."""
+        n = deposit_tensor_count(states_t, draw_t, counts_t, self._device)
+        self._check(self._lib.rt_deposit_particles_async(self._h, C.byref(params), _dp(states_t), _dp(draw_t), n, _dp(counts_t)))
+
     # -- voxel-model entities ----------------------------------------------------------------------------
     def draw_stamps(self, uniforms, models, face_lights):
         """rt_draw_stamps: `models` DRAW_STAMP_DTYPE[N] records (make_draw_stamps) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
@@ -1460,6 +1485,41 @@ def emit_tensor_capacity(states, cursor, device):
     if states.data_ptr() < cursor.data_ptr() + 16 and cursor.data_ptr() < states.data_ptr() + _nbytes(states):
         raise ValueError("states and cursor overlap")
     return capacity
+
+
+def deposit_counts(counts=None):
+    """The counters of Context.deposit_particles as one abi.DEPOSIT_COUNT_DTYPE record in an array of its own: zeros for None, else
+    from such a record, an abi.RtDepositCount or (deposited, voxels, occupied, outside)."""
+    cnt = np.zeros(1, dtype=abi.DEPOSIT_COUNT_DTYPE)
+    if counts is None:
+        return cnt
+    if isinstance(counts, abi.RtDepositCount):
+        cnt[0] = (counts.deposited, counts.voxels, counts.occupied, counts.outside)
+    elif isinstance(counts, (np.ndarray, np.void)) and counts.dtype == abi.DEPOSIT_COUNT_DTYPE:
+        cnt[0] = np.asarray(counts).reshape(-1)[0]
+    else:
+        cnt[0] = tuple(int(v) for v in counts)
+    return cnt
+
+
+def deposit_tensor_count(states, draw, counts, device):
+    """Context.deposit_particles_async's device arguments: `states` a contiguous tensor of N * 64 bytes with N at most 2^20, `draw`
+    (unless None) one of N * 32 bytes, `counts` (unless None) one of exactly 16 bytes, all on GPU `device` and 16-byte aligned, none
+    overlapping another.  Returns N; raises ValueError otherwise (a host tensor's address handed to the kernel would fault the
+    device)."""
+    named = [("states", states)] + ([("draw", draw)] if draw is not None else []) + ([("counts", counts)] if counts is not None else [])
+    _device_tensors(device, *named)
+    n = record_count("states", _nbytes(states), abi.PARTICLE_STATE_DTYPE.itemsize, MAX_PARTICLES, "RtParticleState")
+    if draw is not None:
+        _holds("draw", draw, n, abi.PARTICLE_DTYPE.itemsize)
+    if counts is not None and _nbytes(counts) != abi.DEPOSIT_COUNT_DTYPE.itemsize:
+        raise ValueError("counts must be a contiguous tensor of 16 bytes (one RtDepositCount)")
+    spans = [(name, t.data_ptr(), t.data_ptr() + _nbytes(t)) for name, t in named]
+    for i, (na, a0, a1) in enumerate(spans):
+        for nb, b0, b1 in spans[i + 1:]:
+            if a0 < b1 and b0 < a1:
+                raise ValueError("%s and %s overlap" % (na, nb))
+    return n
 
 
 def check_shadow_box_tensor(boxes, device):
