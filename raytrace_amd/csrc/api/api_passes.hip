@@ -4,7 +4,9 @@
 // (rt_shadow_entities[_async]) behind the entity draws, point lights (rt_add_lights[_async], and rt_add_lights_occluded[_async] with the
 // entities as occluders) behind those.  What the passes share is
 // here once: the prologue (pass_begin), the verdict on a batch of models (models_check), the models' way to the device
-// (upload_models) and the planes a pass writes (planes_written); the synchronous calls' staging is rt_context.hpp's stage_sync.
+// (upload_models, a caller of rt_context.hpp's staging_claim and staging_send; models_send for the optional models of an entity set,
+// which api_query.hip uses too) and the planes a pass writes (planes_written); the synchronous calls' staging is rt_context.hpp's
+// stage_sync.
 //
 // Every launch follows the queries enqueued so far (ev_query): their results may be its records or face lights.  The passes that
 // read the region (lights, shadows) find it on their stream: every world change runs there too, the earlier ones in front, and a
@@ -30,35 +32,31 @@ int models_check(RtContext* c, const std::string& fn, const RtDrawStamp* models,
 }
 
 // The device records of `n` (valid) models, and `extra_bytes` of the caller's behind them, through the next of the two staging sets
-// (rt_draw_stamps, rt_shadow_entities and the entity queries take turns over the same two, in call order) to *dev; `reader` — the
+// (the entity draws, shadows, queries and sweeps and the emitters take turns over the same two, in call order); `reader` — the
 // stream whose launch will read the records: the context's for a pass, the query stream for a query — waits for the transfer.  The
-// caller launches there and then records (*set)->ev_applied on it: the set's next transfer and rt_stamp_destroy wait for that launch.
-int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const void* extra_host, size_t extra_bytes, hipStream_t reader,
-                  StagingSet** set, uint8_t** dev) {
+// caller launches there and then calls batch->applied(reader).
+int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const void* extra_host, size_t extra_bytes, hipStream_t reader, ModelBatch* batch) {
     const size_t rec_bytes = (size_t)n * sizeof(DrawStampRecord), need = rec_bytes + extra_bytes;
     StagingSet& s = c->draw_sets[c->draw_batches & 1u];
-    if (!c->upload_stream) RT_HIP(c, new_stream(c, &c->upload_stream));
-    for (hipEvent_t* ev : {&s.ev_copied.ev, &s.ev_applied.ev})
-        if (!*ev) RT_HIP(c, new_event(c, ev));
-    // the set's previous transfer has left the host block; a set that must grow waits for the launch that reads its device block
-    RT_HIP(c, s.ev_copied.host_wait());
-    s.ev_copied.forget();
-    if (need > s.cap) {
-        RT_HIP(c, s.ev_applied.host_wait());
-        s.ev_applied.forget();
-        RT_HIP(c, s.grow(c, need, staging_alloc(need)));
-    }
+    RT_HIP(c, staging_claim(c, s, need, staging_alloc(need)));
     draw_stamp_fill_records(c->stamps, models, n, reinterpret_cast<DrawStampRecord*>(s.host));
     if (extra_bytes) memcpy(s.host + rec_bytes, extra_host, extra_bytes);
     for (uint32_t i = 0; i < n; i++) c->stamps.find(models[i].stamp)->used = true;   // rt_stamp_destroy waits for the launch
     c->draw_batches++;
-    // the transfer on the upload stream, so that it does not queue behind the frame; it follows the set's previous launch
-    RT_HIP(c, s.ev_applied.wait(c->upload_stream));
-    RT_HIP(c, hipMemcpyAsync(s.dev, s.host, need, hipMemcpyHostToDevice, c->upload_stream));
-    RT_HIP(c, s.ev_copied.record(c->upload_stream));
-    RT_HIP(c, hipStreamWaitEvent(reader, s.ev_copied.ev, 0));
-    *set = &s;
-    *dev = s.dev;
+    RT_HIP(c, staging_send(c, s, need, reader));
+    *batch = ModelBatch{&s, s.dev};
+    return RT_OK;
+}
+
+// The models of an entity set (device boxes plus host models), which may be none.  A stamp made by rt_stamp_capture is written on the
+// render stream: a reader that is not the render stream (the query stream) follows the latest capture; on the render stream, a
+// caller's included, stream order and the capture's lane fence do it.
+int models_send(RtContext* c, const RtDrawStamp* models, uint32_t n, hipStream_t reader, ModelBatch* batch) {
+    *batch = ModelBatch{};
+    if (n == 0u) return RT_OK;
+    const int rc = upload_models(c, models, n, nullptr, 0u, reader, batch);
+    if (rc != RT_OK) return rc;
+    if (reader != c->stream) RT_HIP(c, c->ev_capture.wait(reader));
     return RT_OK;
 }
 }  // namespace rta
@@ -178,22 +176,21 @@ int draw_stamps_begin(RtContext* c, const char* fn, const RtUniforms* u, const R
 int draw_stamps_enqueue(RtContext* c, const RtUniforms* u, const RtDrawStamp* models, const RtProbeLight* lights_host,
                         const RtProbeLight* lights_dev, uint32_t count) {
     RT_HIP(c, hipSetDevice(c->device));
-    StagingSet* s;
-    uint8_t* recs;
-    const int rc = upload_models(c, models, count, lights_host, lights_host ? (size_t)count * 6u * sizeof(RtProbeLight) : 0u, c->stream, &s, &recs);
+    ModelBatch b;
+    const int rc = upload_models(c, models, count, lights_host, lights_host ? (size_t)count * 6u * sizeof(RtProbeLight) : 0u, c->stream, &b);
     if (rc != RT_OK) return rc;
     planes_written(c, true);
     RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
     rtd::DrawStampsArgs a;
-    a.recs = reinterpret_cast<const uint4*>(recs);
-    a.lights = reinterpret_cast<const float4*>(lights_host ? reinterpret_cast<const RtProbeLight*>(recs + (size_t)count * sizeof(DrawStampRecord)) : lights_dev);
+    a.recs = b.recs();
+    a.lights = reinterpret_cast<const float4*>(lights_host ? reinterpret_cast<const RtProbeLight*>(b.dev + (size_t)count * sizeof(DrawStampRecord)) : lights_dev);
     a.count = count;
     set_camera(a, u, c->cfg);
     {
         LaunchTimer t(c, 1);
         RT_HIP(c, rtd::launch_draw_stamps(planes_of(c), a, c->stream));
     }
-    RT_HIP(c, s->ev_applied.record(c->stream));
+    RT_HIP(c, b.applied(c->stream));
     return RT_OK;
 }
 
@@ -208,24 +205,20 @@ int shadow_enqueue(RtContext* c, const RtUniforms* u, const void* boxes_dev, uin
                    float strength) {
     const rtd::Frame f = frame_of(c, u);
     rtd::ShadowArgs a;
+    ModelBatch b;
+    const int rc = models_send(c, models, nmodels, c->stream, &b);
+    if (rc != RT_OK) return rc;
     a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
-    a.recs = nullptr;
+    a.recs = b.recs();
     a.nboxes = nboxes; a.nmodels = nmodels;
     a.strength = strength;
-    StagingSet* s = nullptr;
-    if (nmodels > 0u) {
-        uint8_t* recs;
-        const int rc = upload_models(c, models, nmodels, nullptr, 0u, c->stream, &s, &recs);
-        if (rc != RT_OK) return rc;
-        a.recs = reinterpret_cast<const uint4*>(recs);
-    }
     planes_written(c, false);
     RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
     {
         LaunchTimer t(c, 1);
         RT_HIP(c, rtd::launch_shadow_entities(scene_of(c), f, planes_of(c), a, c->stream));
     }
-    if (s) RT_HIP(c, s->ev_applied.record(c->stream));
+    RT_HIP(c, b.applied(c->stream));
     return RT_OK;
 }
 
@@ -242,24 +235,20 @@ int lights_occluded_enqueue(RtContext* c, const RtUniforms* u, const void* light
     if (nboxes + nmodels == 0u) return add_lights_launch(c, u, lights_dev, count);
     const rtd::Frame f = frame_of(c, u);
     rtd::LightShadowArgs a;
+    ModelBatch b;
+    const int rc = models_send(c, models, nmodels, c->stream, &b);
+    if (rc != RT_OK) return rc;
     a.lights = reinterpret_cast<const uint4*>(lights_dev);
     a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
-    a.recs = nullptr;
+    a.recs = b.recs();
     a.count = count; a.nboxes = nboxes; a.nmodels = nmodels;
-    StagingSet* s = nullptr;
-    if (nmodels > 0u) {
-        uint8_t* recs;
-        const int rc = upload_models(c, models, nmodels, nullptr, 0u, c->stream, &s, &recs);
-        if (rc != RT_OK) return rc;
-        a.recs = reinterpret_cast<const uint4*>(recs);
-    }
     planes_written(c, false);
     RT_HIP(c, c->ev_query.wait_elsewhere(c->stream));
     {
         LaunchTimer t(c, 1);
         RT_HIP(c, rtd::launch_add_lights_occluded(scene_of(c), f, planes_of(c), a, c->stream));
     }
-    if (s) RT_HIP(c, s->ev_applied.record(c->stream));
+    RT_HIP(c, b.applied(c->stream));
     return RT_OK;
 }
 

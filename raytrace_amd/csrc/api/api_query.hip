@@ -2,7 +2,9 @@
 // probes (rt_probe_light, rt_probe_light_async), box sweeps (rt_sweep_boxes, rt_sweep_boxes_async), the particle simulation built on
 // them (rt_step_particles, rt_step_particles_async) and entity queries (rt_trace_entities, rt_trace_entities_async,
 // rt_pick_entities) and entity sweeps (rt_sweep_entities, rt_sweep_entities_async), which share their checks, stream and staging, and
-// the particle emitters (rt_emit_particles, rt_emit_particles_async), whose world, stream and ordering are the sweeps'.
+// the particle emitters (rt_emit_particles, rt_emit_particles_async), whose world, stream and ordering are the sweeps'.  An entity
+// set's models reach the device through api_passes.hip's models_send (a ModelBatch: the ev_capture wait before the launch, applied()
+// behind it); a sweep's domain and a pick's pixels are tested by the check headers' one definition each.
 #include "emit_check.hpp"
 #include "entity_query_check.hpp"
 #include "particle_step_check.hpp"
@@ -156,15 +158,6 @@ int sweep_check(RtContext* c, const char* fn, uint32_t count, const void* sweeps
     return query_check(c, fn, count, sweeps, lr, hits);
 }
 
-// the validated domain of a record, in the kernel's fp32 operations (a NaN fails every comparison)
-bool sweep_in_domain(const RtBoxSweep& s) {
-    for (int k = 0; k < 3; k++) {
-        const float e = s.hi[k] - s.lo[k];
-        if (!(fabsf(s.lo[k]) <= 4194304.0f && fabsf(s.hi[k]) <= 4194304.0f && fabsf(s.motion[k]) <= 64.0f && e > 0.0f && e <= 8.0f)) return false;
-    }
-    return true;
-}
-
 int sweep_launch(RtContext* c, hipStream_t st, const int32_t lr[3], const void* sweeps_dev, void* hits_dev, uint32_t count) {
     rtd::SweepArgs a;
     a.sweeps = reinterpret_cast<const uint4*>(sweeps_dev);
@@ -237,11 +230,10 @@ int emit_launch(RtContext* c, hipStream_t st, const EmitPlan& plan, const int32_
     a.items = (uint32_t)plan.items;
     int rc = emit_scratch_reserve(c, rtd::emit_scratch_words(a.items));
     if (rc != RT_OK) return rc;
-    StagingSet* s = nullptr;
-    uint8_t* recs;
-    rc = upload_models(c, nullptr, 0u, plan.recs.data(), plan.recs.size() * sizeof(EmitRecord), st, &s, &recs);
+    ModelBatch b;
+    rc = upload_models(c, nullptr, 0u, plan.recs.data(), plan.recs.size() * sizeof(EmitRecord), st, &b);
     if (rc != RT_OK) return rc;
-    a.recs = reinterpret_cast<const uint4*>(recs);
+    a.recs = b.recs();
     a.states = reinterpret_cast<uint4*>(states_dev);
     a.cursor = reinterpret_cast<uint4*>(cursor_dev);
     a.scratch = c->emit_scratch;
@@ -250,7 +242,7 @@ int emit_launch(RtContext* c, hipStream_t st, const EmitPlan& plan, const int32_
     for (int k = 0; k < 3; k++) a.lr[k] = lr[k];
     RT_HIP(c, c->ev_emit.wait_elsewhere(st));   // the scratch is the previous call's until its write pass has run
     RT_HIP(c, rtd::launch_emit_particles(scene_of(c), c->logr, a, st));
-    RT_HIP(c, s->ev_applied.record(st));
+    RT_HIP(c, b.applied(st));
     RT_HIP(c, c->ev_emit.record(st));
     if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
     return RT_OK;
@@ -269,53 +261,58 @@ int entity_check(RtContext* c, const char* fn, uint32_t count, const void* in, c
     return models_check(c, fn, models, nmodels, "nothing was answered");
 }
 
-// The models to the device for `st` to read, the launch there, and what waits for it: the staging set's next transfer and
-// rt_stamp_destroy (ev_applied), later world changes (ev_query).
+// The models to the device for `st` to read (models_send: behind the latest rt_stamp_capture), the launch there, and what waits for
+// it: the staging set's next transfer and rt_stamp_destroy (ev_applied), later world changes (ev_query).
 int entity_launch(RtContext* c, hipStream_t st, const rtd::Frame& f, const void* rays_dev, const void* xy_dev, uint32_t count, const void* boxes_dev,
                   uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels, void* world_dev, void* entity_dev) {
+    ModelBatch b;
+    const int rc = models_send(c, models, nmodels, st, &b);
+    if (rc != RT_OK) return rc;
     rtd::EntityQueryArgs a;
     a.rays = reinterpret_cast<const float4*>(rays_dev);
     a.xy = reinterpret_cast<const int2*>(xy_dev);
     a.world_hits = reinterpret_cast<uint4*>(world_dev);
     a.entity_hits = reinterpret_cast<uint4*>(entity_dev);
     a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
-    a.recs = nullptr;
+    a.recs = b.recs();
     a.count = count; a.nboxes = nboxes; a.nmodels = nmodels;
-    StagingSet* s = nullptr;
-    if (nmodels > 0u) {
-        uint8_t* recs;
-        const int rc = upload_models(c, models, nmodels, nullptr, 0u, st, &s, &recs);
-        if (rc != RT_OK) return rc;
-        a.recs = reinterpret_cast<const uint4*>(recs);
-        // a stamp made by rt_stamp_capture is written on the render stream: the launch follows the latest capture (on a caller's
-        // stream, or when the capture ran on this very stream, stream order does it)
-        RT_HIP(c, c->ev_capture.wait_elsewhere(st));
-    }
     RT_HIP(c, rtd::launch_entity_query(scene_of(c), f, a, st));
-    if (s) RT_HIP(c, s->ev_applied.record(st));
+    RT_HIP(c, b.applied(st));
     if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
     return RT_OK;
 }
 
-// The synchronous calls: rays (or pixels), boxes and both outputs through one staging block, the launch, one or two blocks back.
-int entity_sync(RtContext* c, const rtd::Frame& f, const void* in, size_t in_bytes, bool picks, uint32_t count, const RtDrawBox* boxes, uint32_t nboxes,
-                const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits, RtEntityHit* entity_hits) {
+// The synchronous calls against an entity set: the input records, the boxes and both outputs through one staging block on the query
+// stream, `launch(st, in, boxes, world, entity)` on the parts' device addresses (null for boxes or world hits the call does without),
+// one or two blocks back.
+template <typename Launch>
+int entity_set_sync(RtContext* c, const void* in, size_t in_bytes, const RtDrawBox* boxes, uint32_t nboxes, void* world_hits, size_t world_bytes,
+                    void* entity_hits, size_t entity_bytes, Launch&& launch) {
     hipStream_t st;
     int rc = query_stream_of(c, &st);
     if (rc != RT_OK) return rc;
-    const size_t out_bytes = (size_t)count * sizeof(RtEntityHit);   // (of either output)
+    if (!world_hits) world_bytes = 0u;
     uint8_t* dev[4];
-    rc = stage_sync(c, st, {{in, in_bytes}, {nboxes ? boxes : nullptr, (size_t)nboxes * sizeof(RtDrawBox)}, {nullptr, world_hits ? out_bytes : 0u},
-                            {nullptr, out_bytes}}, dev);
+    rc = stage_sync(c, st, {{in, in_bytes}, {nboxes ? boxes : nullptr, (size_t)nboxes * sizeof(RtDrawBox)}, {nullptr, world_bytes}, {nullptr, entity_bytes}}, dev);
     if (rc != RT_OK) return rc;
-    rc = entity_launch(c, st, f, picks ? nullptr : dev[0], picks ? dev[0] : nullptr, count, nboxes ? dev[1] : nullptr, nboxes, models, nmodels,
-                       world_hits ? dev[2] : nullptr, dev[3]);
+    rc = launch(st, dev[0], nboxes ? dev[1] : nullptr, world_hits ? dev[2] : nullptr, dev[3]);
     if (rc != RT_OK) return rc;
     if (world_hits) {
-        rc = fetch_sync(c, st, dev[2], world_hits, out_bytes);
+        rc = fetch_sync(c, st, dev[2], world_hits, world_bytes);
         if (rc != RT_OK) return rc;
     }
-    return fetch_sync(c, st, dev[3], entity_hits, out_bytes);
+    return fetch_sync(c, st, dev[3], entity_hits, entity_bytes);
+}
+
+// rt_trace_entities and rt_pick_entities: rays, or pixels
+int entity_sync(RtContext* c, const rtd::Frame& f, const void* in, size_t in_bytes, bool picks, uint32_t count, const RtDrawBox* boxes, uint32_t nboxes,
+                const RtDrawStamp* models, uint32_t nmodels, RtRayHit* world_hits, RtEntityHit* entity_hits) {
+    const size_t out_bytes = (size_t)count * sizeof(RtEntityHit);   // (of either output)
+    return entity_set_sync(c, in, in_bytes, boxes, nboxes, world_hits, out_bytes, entity_hits, out_bytes,
+                           [&](hipStream_t st, uint8_t* in_dev, uint8_t* boxes_dev, uint8_t* world_dev, uint8_t* entity_dev) {
+                               return entity_launch(c, st, f, picks ? nullptr : in_dev, picks ? in_dev : nullptr, count, boxes_dev, nboxes, models, nmodels,
+                                                    world_dev, entity_dev);
+                           });
 }
 
 // ---- entity sweeps: device sweeps and boxes, host models as rt_draw_stamps'; the entity queries' stream, staging and waits ----------
@@ -332,24 +329,19 @@ int sweep_entities_check(RtContext* c, const char* fn, uint32_t count, const voi
 // entity_launch's steps with the sweep kernel in place of the query kernel.
 int sweep_entities_launch(RtContext* c, hipStream_t st, const int32_t lr[3], const void* sweeps_dev, uint32_t count, const void* boxes_dev,
                           uint32_t nboxes, const RtDrawStamp* models, uint32_t nmodels, void* world_dev, void* entity_dev) {
+    ModelBatch b;
+    const int rc = models_send(c, models, nmodels, st, &b);
+    if (rc != RT_OK) return rc;
     rtd::SweepEntitiesArgs a;
     a.sweeps = reinterpret_cast<const uint4*>(sweeps_dev);
     a.world_hits = reinterpret_cast<uint4*>(world_dev);
     a.entity_hits = reinterpret_cast<uint4*>(entity_dev);
     a.boxes = reinterpret_cast<const uint4*>(boxes_dev);
-    a.recs = nullptr;
+    a.recs = b.recs();
     a.count = count; a.nboxes = nboxes; a.nmodels = nmodels;
     for (int k = 0; k < 3; k++) a.lr[k] = lr[k];
-    StagingSet* s = nullptr;
-    if (nmodels > 0u) {
-        uint8_t* recs;
-        const int rc = upload_models(c, models, nmodels, nullptr, 0u, st, &s, &recs);
-        if (rc != RT_OK) return rc;
-        a.recs = reinterpret_cast<const uint4*>(recs);
-        RT_HIP(c, c->ev_capture.wait_elsewhere(st));   // (the launch follows the latest rt_stamp_capture, as entity_launch's does)
-    }
     RT_HIP(c, rtd::launch_sweep_entities(scene_of(c), c->logr, a, st));
-    if (s) RT_HIP(c, s->ev_applied.record(st));
+    RT_HIP(c, b.applied(st));
     if (!c->user_stream) RT_HIP(c, c->ev_query.record(st));   // (a caller's stream orders itself)
     return RT_OK;
 }
@@ -381,9 +373,8 @@ int rt_pick_pixels(RtContext* ctx, const RtUniforms* u, const int32_t* xy, uint3
     if (!ctx) return RT_ERR_INVALID_ARG;
     int rc = query_check(ctx, "rt_pick_pixels", count, u, xy, hits);
     if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
-    for (uint32_t i = 0; i < count; i++)
-        if (xy[2 * i] < 0 || xy[2 * i] >= ctx->cfg.width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= ctx->cfg.height)
-            return fail(ctx, RT_ERR_INVALID_ARG, "rt_pick_pixels: pixel " + std::to_string(i) + " is outside the frame");
+    const uint32_t out = first_pixel_outside(xy, count, ctx->cfg.width, ctx->cfg.height);
+    if (out != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_pick_pixels: pixel " + std::to_string(out) + " is outside the frame");
     return query_sync(ctx, frame_of(ctx, u), xy, (size_t)count * 8u, true, hits, count);
 }
 
@@ -429,9 +420,8 @@ int rt_sweep_boxes(RtContext* ctx, const RtBoxSweep* sweeps, uint32_t count, con
     if (!ctx) return RT_ERR_INVALID_ARG;
     int rc = sweep_check(ctx, "rt_sweep_boxes", count, sweeps, lr, hits);
     if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
-    for (uint32_t i = 0; i < count; i++)
-        if (!sweep_in_domain(sweeps[i]))
-            return fail(ctx, RT_ERR_INVALID_ARG, "rt_sweep_boxes: sweep " + std::to_string(i) + " is outside the validated domain");
+    const uint32_t bad = first_invalid_sweep(sweeps, count);   // (sweep_entities_check.hpp: the one host definition of the domain)
+    if (bad != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_sweep_boxes: sweep " + std::to_string(bad) + " is outside the validated domain");
     hipStream_t st;
     rc = query_stream_of(ctx, &st);
     if (rc != RT_OK) return rc;
@@ -595,26 +585,15 @@ int rt_sweep_entities(RtContext* ctx, const RtBoxSweep* sweeps, uint32_t count, 
     if (!ctx) return RT_ERR_INVALID_ARG;
     int rc = sweep_entities_check(ctx, "rt_sweep_entities", count, sweeps, lr, entity_hits, boxes, nboxes, models, nmodels);
     if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
-    uint32_t bad = first_invalid_entity_sweep(sweeps, count);
+    uint32_t bad = first_invalid_sweep(sweeps, count);
     if (bad != count) return fail(ctx, RT_ERR_INVALID_ARG, "rt_sweep_entities: sweep " + std::to_string(bad) + " is outside the validated domain");
     bad = first_invalid_draw_box(boxes, nboxes);
     if (bad != nboxes) return fail(ctx, RT_ERR_INVALID_ARG, "rt_sweep_entities: box " + std::to_string(bad) + " is not a valid box");
-    hipStream_t st;
-    rc = query_stream_of(ctx, &st);
-    if (rc != RT_OK) return rc;
-    // sweeps, boxes and both outputs through one staging block, the launch, one or two blocks back
-    const size_t world_bytes = world_hits ? (size_t)count * sizeof(RtSweepHit) : 0u, entity_bytes = (size_t)count * sizeof(RtEntitySweepHit);
-    uint8_t* dev[4];
-    rc = stage_sync(ctx, st, {{sweeps, (size_t)count * sizeof(RtBoxSweep)}, {nboxes ? boxes : nullptr, (size_t)nboxes * sizeof(RtDrawBox)},
-                              {nullptr, world_bytes}, {nullptr, entity_bytes}}, dev);
-    if (rc != RT_OK) return rc;
-    rc = sweep_entities_launch(ctx, st, lr, dev[0], count, nboxes ? dev[1] : nullptr, nboxes, models, nmodels, world_hits ? dev[2] : nullptr, dev[3]);
-    if (rc != RT_OK) return rc;
-    if (world_hits) {
-        rc = fetch_sync(ctx, st, dev[2], world_hits, world_bytes);
-        if (rc != RT_OK) return rc;
-    }
-    return fetch_sync(ctx, st, dev[3], entity_hits, entity_bytes);
+    return entity_set_sync(ctx, sweeps, (size_t)count * sizeof(RtBoxSweep), boxes, nboxes, world_hits, (size_t)count * sizeof(RtSweepHit), entity_hits,
+                           (size_t)count * sizeof(RtEntitySweepHit),
+                           [&](hipStream_t st, uint8_t* sweeps_dev, uint8_t* boxes_dev, uint8_t* world_dev, uint8_t* entity_dev) {
+                               return sweep_entities_launch(ctx, st, lr, sweeps_dev, count, boxes_dev, nboxes, models, nmodels, world_dev, entity_dev);
+                           });
 }
 
 int rt_sweep_entities_async(RtContext* ctx, const RtBoxSweep* sweeps_dev, uint32_t count, const int32_t lr[3], const RtDrawBox* boxes_dev,

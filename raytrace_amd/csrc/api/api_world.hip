@@ -1,6 +1,9 @@
 // api_world.hip — the kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits, shape
 // edits, voxel stamps (their store, capture and placement), particle deposits and terrain generated on the device; rt_read_box reads
-// the resident region back.
+// the resident region back.  The ordering protocols stand here once each: world_change_begin / world_change_end round every change,
+// world_send / world_applied for the changes that come through a staging set (rt_context.hpp's staging_claim and staging_send, plus
+// the world change), and chunk_edit with its history rule (edit_history) for the four calls that rewrite whole chunks from a staged
+// list of chunk ids: rt_edit_voxels, rt_edit_shapes, rt_edit_stamps and the deposits hand it only what differs between them.
 #include "deposit_check.hpp"
 #include "rt_context.hpp"
 
@@ -21,32 +24,58 @@ hipError_t world_change_end(RtContext* c) {
     return e == hipSuccess ? fence_lanes_after(c, c->stream) : e;
 }
 
-// ---- staging (StagingSet) ---------------------------------------------------------------------------------------------------
-// the host may write `need` bytes to the set: its previous transfer has left the host block; a smaller set is replaced by one of
-// `alloc` bytes once its device block has been applied.  (The upload stream and the set's events are created on first use.)
-hipError_t staging_claim(RtContext* c, StagingSet& s, size_t need, size_t alloc) {
-    hipError_t e = c->upload_stream ? hipSuccess : new_stream(c, &c->upload_stream);
-    for (hipEvent_t* ev : {&s.ev_copied.ev, &s.ev_applied.ev})
-        if (e == hipSuccess && !*ev) e = new_event(c, ev);
-    if (e == hipSuccess) e = s.ev_copied.host_wait();
-    if (e == hipSuccess) s.ev_copied.forget();
-    if (e != hipSuccess || need <= s.cap) return e;
-    e = s.ev_applied.host_wait();
-    return e == hipSuccess ? s.grow(c, need, alloc) : e;
-}
-// the first `bytes` of the host block to the device block on the upload stream, after the set's previous launch has read it; the
-// render stream waits for the transfer, and for the frames in flight on the other lane (they read what the launch changes)
-hipError_t staging_send(RtContext* c, StagingSet& s, size_t bytes) {
-    hipError_t e = s.ev_applied.wait(c->upload_stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, c->upload_stream);
-    if (e == hipSuccess) e = s.ev_copied.record(c->upload_stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, s.ev_copied.ev, 0);
+// ---- a world change through a staging set: rt_context.hpp's staging_claim and staging_send, and the world change round the launch ---
+// the render stream waits for the transfer, and for the frames in flight on the other lane (they read what the launch changes)
+hipError_t world_send(RtContext* c, StagingSet& s, size_t bytes) {
+    const hipError_t e = staging_send(c, s, bytes, c->stream);
     return e == hipSuccess ? world_change_begin(c) : e;
 }
 // after the launch that read the device block: later frames, whichever lane they start on, see what it changed
-hipError_t staging_applied(RtContext* c, StagingSet& s) {
-    hipError_t e = s.ev_applied.record(c->stream);
+hipError_t world_applied(RtContext* c, StagingSet& s) {
+    const hipError_t e = s.ev_applied.record(c->stream);
     return e == hipSuccess ? world_change_end(c) : e;
+}
+
+// ---- chunk edits: rt_edit_voxels, rt_edit_shapes, rt_edit_stamps and the particle deposits ----------------------------------------
+// The history rule of an edit that brings `nboxes` pending boxes.  RtConfig.edit_radius == 0: the history restarts.  Otherwise it
+// stays and the boxes (`write(dst)` writes them and returns how many) wait for the next frame drawn, which restarts only the pixels
+// an edit can have changed (api_frame.hip); a set that would pass its capacity is emptied and that frame restarts.
+template <typename Write>
+void edit_history(RtContext* c, uint32_t nboxes, Write&& write) {
+    if (c->edit_radius == 0u) { c->accum_valid = false; return; }
+    if (c->edit_overflow) return;
+    if (c->edit_nbox + nboxes > rtd::kTemporalMaxBoxes) {
+        c->edit_nbox = 0;
+        c->edit_overflow = true;
+    } else {
+        c->edit_nbox += write(c->edit_boxes + c->edit_nbox);
+    }
+}
+
+// One edit of `nchunks` chunks, whose ids head the staged block.  The four kinds share the two edit sets and one counter, so that
+// they apply in call order: the transfer on the upload stream, then the launches on the render stream after the frames already
+// submitted (every lane), and later frames after them — the ordering of rt_upload_slice.  `fill(host)` writes the block (at most `need`
+// bytes; a set that must grow gets `alloc`) and returns the bytes to send; `apply(dev)` enqueues, and times, what rewrites the chunks'
+// voxels; the rebuild of their nibble maps follows, then `users` (a scratch block's event, or null) is recorded.
+template <typename Fill, typename Write, typename Apply>
+int chunk_edit(RtContext* c, size_t need, size_t alloc, uint32_t nchunks, uint32_t nboxes, Fill&& fill, Write&& write, Apply&& apply,
+               LatchEvent* users = nullptr) {
+    StagingSet& s = c->edit_sets[c->edit_batches & 1u];
+    RT_HIP(c, staging_claim(c, s, need, alloc));
+    const size_t bytes = fill(s.host);
+    c->edit_batches++;
+    edit_history(c, nboxes, write);
+    invalidate_prepass(c);
+    RT_HIP(c, world_send(c, s, bytes));
+    const int rc = apply(s.dev);
+    if (rc != RT_OK) return rc;
+    {
+        LaunchTimer lt(c, 1);
+        RT_HIP(c, rtd::launch_rebuild_chunk_maps(c->d_mine_sw, c->d_coarse, c->d_brick, reinterpret_cast<const uint32_t*>(s.dev), nchunks, c->logr, c->stream));
+    }
+    if (users) RT_HIP(c, users->record(c->stream));
+    RT_HIP(c, world_applied(c, s));
+    return RT_OK;
 }
 
 // ---- RtConfig.stream_history: a slab that keeps the lighting history ------------------------------------------------------------
@@ -153,29 +182,12 @@ int deposit_check(RtContext* c, const char* fn, const RtParticleDeposit* p, cons
     return count == 0u || plan->empty ? 1 : RT_OK;
 }
 
-// The call's launches on the render stream between world_change_begin and world_change_end, with rt_edit_shapes' staging (the box's
-// chunk ids), counter and side effects for one box shape equal to the box.  The pointers are device addresses the stream may use.
+// A chunk edit (the clipped box's chunk ids; one pending box, the clipped box) whose apply step fills the scratch and runs the chunk
+// pass over it.  The pointers are device addresses the stream may use.
 int deposit_run(RtContext* c, const RtParticleDeposit& p, const DepositPlan& plan, void* states_dev, void* draw_dev, void* counts_dev, uint32_t count) {
     const size_t words = deposit_scratch_need(plan);
-    int rc = deposit_scratch_reserve(c, words);
+    const int rc = deposit_scratch_reserve(c, words);
     if (rc != RT_OK) return rc;
-    StagingSet& s = c->edit_sets[c->edit_batches & 1u];
-    RT_HIP(c, staging_claim(c, s, plan.need, staging_alloc(plan.need)));
-    deposit_fill_chunks(plan, c->logr, reinterpret_cast<uint32_t*>(s.host));
-    c->edit_batches++;
-    if (c->edit_radius == 0u) {
-        c->accum_valid = false;
-    } else if (!c->edit_overflow) {
-        // the history stays: the clipped box waits for the next frame drawn (rt_edit_voxels' set and rule)
-        if (c->edit_nbox + 1u > rtd::kTemporalMaxBoxes) {
-            c->edit_nbox = 0;
-            c->edit_overflow = true;
-        } else {
-            c->edit_boxes[c->edit_nbox++] = plan.box;
-        }
-    }
-    invalidate_prepass(c);
-    RT_HIP(c, staging_send(c, s, plan.need));
     rtd::DepositArgs a;
     a.states = reinterpret_cast<uint4*>(states_dev);
     a.draw = reinterpret_cast<uint4*>(draw_dev);
@@ -185,23 +197,21 @@ int deposit_run(RtContext* c, const RtParticleDeposit& p, const DepositPlan& pla
     a.count = count;
     a.max_speed = p.max_speed;
     for (int k = 0; k < 3; k++) { a.lr[k] = p.lr[k]; a.lo[k] = plan.box.lo[k]; a.hi[k] = plan.box.hi[k]; }
-    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
-    RT_HIP(c, c->ev_deposit.wait_elsewhere(c->stream));   // the scratch is the previous call's until its chunk pass has run
-    {
-        LaunchTimer lt(c, 1);
-        RT_HIP(c, hipMemsetAsync(c->deposit_scratch, 0xFF, words * sizeof(uint32_t), c->stream));
-    }
-    {
-        LaunchTimer lt(c, 1);
-        RT_HIP(c, rtd::launch_deposit_particles(c->d_mine_sw, c->d_mat_sw, d_chunks, plan.nchunks, c->logr, a, c->stream));
-    }
-    {
-        LaunchTimer lt(c, 1);
-        RT_HIP(c, rtd::launch_rebuild_chunk_maps(c->d_mine_sw, c->d_coarse, c->d_brick, d_chunks, plan.nchunks, c->logr, c->stream));
-    }
-    RT_HIP(c, c->ev_deposit.record(c->stream));
-    RT_HIP(c, staging_applied(c, s));
-    return RT_OK;
+    return chunk_edit(
+        c, plan.need, staging_alloc(plan.need), plan.nchunks, 1u,
+        [&](uint8_t* host) { deposit_fill_chunks(plan, c->logr, reinterpret_cast<uint32_t*>(host)); return plan.need; },
+        [&](EditBox* boxes) { *boxes = plan.box; return 1u; },
+        [&](const uint8_t* dev) -> int {
+            RT_HIP(c, c->ev_deposit.wait_elsewhere(c->stream));   // the scratch is the previous call's until its chunk pass has run
+            {
+                LaunchTimer lt(c, 1);
+                RT_HIP(c, hipMemsetAsync(c->deposit_scratch, 0xFF, words * sizeof(uint32_t), c->stream));
+            }
+            LaunchTimer lt(c, 1);
+            RT_HIP(c, rtd::launch_deposit_particles(c->d_mine_sw, c->d_mat_sw, reinterpret_cast<const uint32_t*>(dev), plan.nchunks, c->logr, a, c->stream));
+            return RT_OK;
+        },
+        &c->ev_deposit);
 }
 
 }  // namespace
@@ -286,7 +296,7 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
     if (minefield != h_mine) memcpy(h_mine, minefield, n);                     // rt_slice_staging's pointers need no copy
     ctx->slabs++;
     uint32_t* masks = ctx->stream_history ? slab_take_slot(ctx) : nullptr;
-    RT_HIP(ctx, staging_send(ctx, s, 5 * n));
+    RT_HIP(ctx, world_send(ctx, s, 5 * n));
     RT_HIP(ctx, slab_scan_old(ctx, masks, axis, texel_offset));
     {
         LaunchTimer t(ctx, 1);
@@ -294,7 +304,7 @@ int rt_upload_slice(RtContext* ctx, int axis, int texel_offset, const uint32_t* 
                                              ctx->d_coarse, ctx->d_brick, ctx->logr, axis, texel_offset, ctx->stream));
     }
     RT_HIP(ctx, slab_scan_new(ctx, masks, axis, texel_offset));
-    RT_HIP(ctx, staging_applied(ctx, s));
+    RT_HIP(ctx, world_applied(ctx, s));
     return RT_OK;
 }
 
@@ -337,42 +347,24 @@ int rt_edit_voxels(RtContext* ctx, const RtVoxelEdit* edits, uint32_t count) {
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_edit_voxels: edit " + std::to_string(bad) +
                                                  " has a coordinate outside the region or reserved != 0; nothing was applied");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    StagingSet& s = ctx->edit_sets[ctx->edit_batches & 1u];
-    size_t cap = bins.need < ((size_t)64 << 10) ? ((size_t)64 << 10) : bins.need;   // (if the set must grow)
-    if (cap < bins.need + bins.need / 2u) cap = align16(bins.need + bins.need / 2u);
-    RT_HIP(ctx, staging_claim(ctx, s, bins.need, cap));
-    const uint32_t nrec = edit_fill(ctx->edit_binning, edits, ctx->logr, reinterpret_cast<uint32_t*>(s.host),
-                                    reinterpret_cast<uint32_t*>(s.host + bins.off_offs), reinterpret_cast<uint32_t*>(s.host + bins.off_recs));
-    // Transfer on the upload stream, then the rebuild on the render stream after the frames already submitted (every lane), and
-    // later frames after the rebuild — the ordering of rt_upload_slice.
-    ctx->edit_batches++;
-    if (ctx->edit_radius == 0u) {
-        ctx->accum_valid = false;
-    } else if (!ctx->edit_overflow) {
-        // the history stays: one box per touched chunk waits for the next frame drawn, which restarts only the pixels an edit can
-        // have changed (api_frame.hip); a set that would pass its capacity is emptied and that frame restarts
-        if (ctx->edit_nbox + bins.touched > rtd::kTemporalMaxBoxes) {
-            ctx->edit_nbox = 0;
-            ctx->edit_overflow = true;
-        } else {
-            ctx->edit_nbox += edit_chunk_boxes(ctx->edit_binning, edits, ctx->logr, ctx->edit_boxes + ctx->edit_nbox);
-        }
-    }
-    invalidate_prepass(ctx);
-    RT_HIP(ctx, staging_send(ctx, s, bins.off_recs + (size_t)nrec * 8u));
-    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
-    const uint32_t* d_offs = reinterpret_cast<const uint32_t*>(s.dev + bins.off_offs);
-    const uint2* d_recs = reinterpret_cast<const uint2*>(s.dev + bins.off_recs);
-    {
-        LaunchTimer lt(ctx, 1);
-        RT_HIP(ctx, rtd::launch_rebuild_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, d_offs, d_recs, bins.touched, ctx->logr, ctx->stream));
-    }
-    {
-        LaunchTimer lt(ctx, 1);
-        RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, bins.touched, ctx->logr, ctx->stream));
-    }
-    RT_HIP(ctx, staging_applied(ctx, s));
-    return RT_OK;
+    // (not staging_alloc alone: a set that grows for 43.7 to 64 KiB of need has always got half as much again here, not 64 KiB)
+    const size_t half_more = align16(bins.need + bins.need / 2u), cap = half_more > staging_alloc(bins.need) ? half_more : staging_alloc(bins.need);
+    // the chunk ids, the per-chunk edit ranges, the records; one pending box per touched chunk
+    return chunk_edit(
+        ctx, bins.need, cap, bins.touched, bins.touched,
+        [&](uint8_t* host) {
+            const uint32_t nrec = edit_fill(ctx->edit_binning, edits, ctx->logr, reinterpret_cast<uint32_t*>(host),
+                                            reinterpret_cast<uint32_t*>(host + bins.off_offs), reinterpret_cast<uint32_t*>(host + bins.off_recs));
+            return bins.off_recs + (size_t)nrec * 8u;
+        },
+        [&](EditBox* boxes) { return edit_chunk_boxes(ctx->edit_binning, edits, ctx->logr, boxes); },
+        [&](const uint8_t* dev) -> int {
+            LaunchTimer lt(ctx, 1);
+            RT_HIP(ctx, rtd::launch_rebuild_chunks(ctx->d_mine_sw, ctx->d_mat_sw, reinterpret_cast<const uint32_t*>(dev),
+                                                   reinterpret_cast<const uint32_t*>(dev + bins.off_offs), reinterpret_cast<const uint2*>(dev + bins.off_recs),
+                                                   bins.touched, ctx->logr, ctx->stream));
+            return RT_OK;
+        });
 }
 
 int rt_edit_shapes(RtContext* ctx, const RtShapeEdit* shapes, uint32_t count) {
@@ -390,37 +382,21 @@ int rt_edit_shapes(RtContext* ctx, const RtShapeEdit* shapes, uint32_t count) {
     const ShapePlan plan = shapes_touched(ctx->shape_scratch, shapes, count, ctx->logr);
     if (plan.touched == 0u) return RT_OK;   // (every shape lies outside the region: nothing is enqueued, nothing is reset)
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    // rt_edit_voxels' staging sets and counter, so that shapes and voxel edits apply in call order: the chunk ids, then the records
-    StagingSet& s = ctx->edit_sets[ctx->edit_batches & 1u];
-    const size_t cap = plan.need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(plan.need + plan.need / 2u);   // (if the set must grow)
-    RT_HIP(ctx, staging_claim(ctx, s, plan.need, cap));
-    shapes_fill_chunks(ctx->shape_scratch, reinterpret_cast<uint32_t*>(s.host));
-    memcpy(s.host + plan.off_shapes, shapes, (size_t)count * sizeof(RtShapeEdit));
-    ctx->edit_batches++;
-    if (ctx->edit_radius == 0u) {
-        ctx->accum_valid = false;
-    } else if (!ctx->edit_overflow) {
-        // the history stays: one box per shape that has a bounding box waits for the next frame drawn (rt_edit_voxels' set and rule)
-        if (ctx->edit_nbox + plan.boxes > rtd::kTemporalMaxBoxes) {
-            ctx->edit_nbox = 0;
-            ctx->edit_overflow = true;
-        } else {
-            ctx->edit_nbox += shape_pending_boxes(shapes, count, ctx->logr, ctx->edit_boxes + ctx->edit_nbox);
-        }
-    }
-    invalidate_prepass(ctx);
-    RT_HIP(ctx, staging_send(ctx, s, plan.need));
-    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
-    {
-        LaunchTimer lt(ctx, 1);
-        RT_HIP(ctx, rtd::launch_shape_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, s.dev + plan.off_shapes, count, plan.touched, ctx->logr, ctx->stream));
-    }
-    {
-        LaunchTimer lt(ctx, 1);
-        RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, plan.touched, ctx->logr, ctx->stream));
-    }
-    RT_HIP(ctx, staging_applied(ctx, s));
-    return RT_OK;
+    // the chunk ids, then the records; one pending box per shape that has a bounding box
+    return chunk_edit(
+        ctx, plan.need, staging_alloc(plan.need), plan.touched, plan.boxes,
+        [&](uint8_t* host) {
+            shapes_fill_chunks(ctx->shape_scratch, reinterpret_cast<uint32_t*>(host));
+            memcpy(host + plan.off_shapes, shapes, (size_t)count * sizeof(RtShapeEdit));
+            return plan.need;
+        },
+        [&](EditBox* boxes) { return shape_pending_boxes(shapes, count, ctx->logr, boxes); },
+        [&](const uint8_t* dev) -> int {
+            LaunchTimer lt(ctx, 1);
+            RT_HIP(ctx, rtd::launch_shape_chunks(ctx->d_mine_sw, ctx->d_mat_sw, reinterpret_cast<const uint32_t*>(dev), dev + plan.off_shapes, count,
+                                                 plan.touched, ctx->logr, ctx->stream));
+            return RT_OK;
+        });
 }
 
 int rt_deposit_particles(RtContext* ctx, const RtParticleDeposit* params, RtParticleState* states, RtParticle* draw, uint32_t count,
@@ -569,39 +545,23 @@ int rt_edit_stamps(RtContext* ctx, const RtStampPlace* places, uint32_t count) {
     const StampPlan plan = stamps_touched(ctx->shape_scratch, ctx->stamps, places, count, ctx->logr);
     if (plan.touched == 0u) return RT_OK;   // (every placement lies outside the region: nothing is enqueued, nothing is reset)
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    // rt_edit_voxels' staging sets and counter, so that stamps, shapes and voxel edits apply in call order: the chunk ids, then one
-    // record per placement with the id resolved into the stamp's device arrays
-    StagingSet& s = ctx->edit_sets[ctx->edit_batches & 1u];
-    const size_t cap = plan.need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(plan.need + plan.need / 2u);   // (if the set must grow)
-    RT_HIP(ctx, staging_claim(ctx, s, plan.need, cap));
-    shapes_fill_chunks(ctx->shape_scratch, reinterpret_cast<uint32_t*>(s.host));
-    stamp_fill_records(ctx->stamps, places, count, ctx->logr, reinterpret_cast<StampRecord*>(s.host + plan.off_recs));
-    for (uint32_t i = 0; i < count; i++) ctx->stamps.find(places[i].stamp)->used = true;
-    ctx->edit_batches++;
-    if (ctx->edit_radius == 0u) {
-        ctx->accum_valid = false;
-    } else if (!ctx->edit_overflow) {
-        // the history stays: one box per placement that has a bounding box waits for the next frame drawn (rt_edit_voxels' set and rule)
-        if (ctx->edit_nbox + plan.boxes > rtd::kTemporalMaxBoxes) {
-            ctx->edit_nbox = 0;
-            ctx->edit_overflow = true;
-        } else {
-            ctx->edit_nbox += stamp_pending_boxes(ctx->stamps, places, count, ctx->logr, ctx->edit_boxes + ctx->edit_nbox);
-        }
-    }
-    invalidate_prepass(ctx);
-    RT_HIP(ctx, staging_send(ctx, s, plan.need));
-    const uint32_t* d_chunks = reinterpret_cast<const uint32_t*>(s.dev);
-    {
-        LaunchTimer lt(ctx, 1);
-        RT_HIP(ctx, rtd::launch_stamp_chunks(ctx->d_mine_sw, ctx->d_mat_sw, d_chunks, s.dev + plan.off_recs, count, plan.touched, ctx->logr, ctx->stream));
-    }
-    {
-        LaunchTimer lt(ctx, 1);
-        RT_HIP(ctx, rtd::launch_rebuild_chunk_maps(ctx->d_mine_sw, ctx->d_coarse, ctx->d_brick, d_chunks, plan.touched, ctx->logr, ctx->stream));
-    }
-    RT_HIP(ctx, staging_applied(ctx, s));
-    return RT_OK;
+    // the chunk ids, then one record per placement with the id resolved into the stamp's device arrays; one pending box per placement
+    // that has a bounding box
+    return chunk_edit(
+        ctx, plan.need, staging_alloc(plan.need), plan.touched, plan.boxes,
+        [&](uint8_t* host) {
+            shapes_fill_chunks(ctx->shape_scratch, reinterpret_cast<uint32_t*>(host));
+            stamp_fill_records(ctx->stamps, places, count, ctx->logr, reinterpret_cast<StampRecord*>(host + plan.off_recs));
+            for (uint32_t i = 0; i < count; i++) ctx->stamps.find(places[i].stamp)->used = true;
+            return plan.need;
+        },
+        [&](EditBox* boxes) { return stamp_pending_boxes(ctx->stamps, places, count, ctx->logr, boxes); },
+        [&](const uint8_t* dev) -> int {
+            LaunchTimer lt(ctx, 1);
+            RT_HIP(ctx, rtd::launch_stamp_chunks(ctx->d_mine_sw, ctx->d_mat_sw, reinterpret_cast<const uint32_t*>(dev), dev + plan.off_recs, count,
+                                                 plan.touched, ctx->logr, ctx->stream));
+            return RT_OK;
+        });
 }
 
 int rt_read_box(RtContext* ctx, int x0, int y0, int z0, int ex, int ey, int ez, uint32_t* materials, uint8_t* minefield) {

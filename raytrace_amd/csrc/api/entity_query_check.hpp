@@ -12,17 +12,15 @@
 namespace rta __attribute__((visibility("hidden"))) {
 
 constexpr uint32_t kMaxEntityRays = 1u << 24;                               // rays or pixels per call
-constexpr uint32_t kMaxQueryBoxes = 4096, kMaxQueryModels = 4096;           // entities per call, of either kind
 
 // What is wrong with the counts and pointers of a call, or nullptr.  `in` is rays or xy, `more` is lr or u; they and `entity_hits`
-// are needed only when count > 0, an entity array only when its count is.  The order is the one the calls report in.
+// are needed only when count > 0, an entity array only when its count is (entity_arrays_error).  The order is the one the calls
+// report in: every count comes before any pointer.
 inline const char* entity_query_args_error(uint32_t count, const void* in, const void* more, const void* entity_hits, const void* boxes,
                                            uint32_t nboxes, const void* models, uint32_t nmodels) {
     if (count > kMaxEntityRays) return "more than 2^24 rays in one call";
-    if (nboxes > kMaxQueryBoxes) return "more than 4096 boxes in one call";
-    if (nmodels > kMaxQueryModels) return "more than 4096 models in one call";
+    if (const char* e = entity_arrays_error(boxes, nboxes, models, nmodels)) return e;
     if (count > 0u && (!in || !more || !entity_hits)) return "null pointer";
-    if ((nboxes > 0u && !boxes) || (nmodels > 0u && !models)) return "null pointer";
     return nullptr;
 }
 

@@ -1,6 +1,6 @@
 // rt_context.hpp — the context behind the C ABI of include/rt_abi.h, shared by the api_*.hip translation units: its structs and
-// constants, the small helper types (LatchEvent, StagingBlock, TimingPool, env_int), the synchronous calls' staging (stage_sync)
-// and the few functions that cross files.
+// constants, the small helper types (LatchEvent, StagingBlock, TimingPool, env_int), the hand-over of a staging set (staging_claim,
+// staging_send), the synchronous calls' staging (stage_sync) and the few functions that cross files.
 //
 // One context = one GPU.  Nothing here runs ray-trace work on the CPU: if the HIP runtime or a device is missing, rt_create fails
 // with RT_ERR_NO_DEVICE and the caller gets no context.  Everything internal lives in namespace rta (hidden visibility): the
@@ -416,6 +416,29 @@ inline void StagingBlock::release() {
 // What a staging pair that must hold `need` bytes is allocated with when it has to grow: 64 KiB at least, else half as much again.
 inline size_t staging_alloc(size_t need) { return need < ((size_t)64 << 10) ? ((size_t)64 << 10) : align16(need + need / 2u); }
 
+// ---- the hand-over of a staging set (StagingSet): claim, fill the host block, send, launch on `reader`, record ev_applied there ------
+// The host may write `need` bytes to the set: its previous transfer has left the host block; a smaller set is replaced by one of
+// `alloc` bytes once the launch that reads its device block has run.  (The upload stream and the set's events are made on first use.)
+inline hipError_t staging_claim(RtContext* c, StagingSet& s, size_t need, size_t alloc) {
+    hipError_t e = c->upload_stream ? hipSuccess : new_stream(c, &c->upload_stream);
+    for (hipEvent_t* ev : {&s.ev_copied.ev, &s.ev_applied.ev})
+        if (e == hipSuccess && !*ev) e = new_event(c, ev);
+    if (e == hipSuccess) e = s.ev_copied.host_wait();
+    if (e == hipSuccess) s.ev_copied.forget();
+    if (e != hipSuccess || need <= s.cap) return e;
+    e = s.ev_applied.host_wait();
+    if (e == hipSuccess) s.ev_applied.forget();
+    return e == hipSuccess ? s.grow(c, need, alloc) : e;
+}
+// The first `bytes` of the host block to the device block on the upload stream (so that the transfer does not queue behind a frame),
+// after the set's previous launch has read it; `reader`, the stream whose launch will read the device block, waits for the transfer.
+inline hipError_t staging_send(RtContext* c, StagingSet& s, size_t bytes, hipStream_t reader) {
+    hipError_t e = s.ev_applied.wait(c->upload_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, c->upload_stream);
+    if (e == hipSuccess) e = s.ev_copied.record(c->upload_stream);
+    return e == hipSuccess ? hipStreamWaitEvent(reader, s.ev_copied.ev, 0) : e;
+}
+
 // One part of a synchronous call's staging: `bytes` copied from `host`, or (host == nullptr) room for what the launch leaves there.
 struct StagePart { const void* host; size_t bytes; };
 // The parts of a synchronous call through query_block, back to back and each on a 16-byte boundary: the host parts (they come first)
@@ -507,9 +530,18 @@ void resolve_route(RtContext* c);
 rtd::Frame frame_of(const RtContext* c, const RtUniforms* u);
 bool query_device_ptr(const RtContext* c, const void* p);   // api_query.hip: rt_trace_rays_async's test of a caller's device pointer
 // api_passes.hip: the verdict on a batch of models, and their way to the device for the launch `reader` will run (the entity draws,
-// the entity shadows and the entity queries share both)
+// the entity shadows, the entity queries and sweeps and the emitters share both)
 int models_check(RtContext* c, const std::string& fn, const RtDrawStamp* models, uint32_t n, const char* nothing);
-int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const void* extra_host, size_t extra_bytes, hipStream_t reader,
-                  StagingSet** set, uint8_t** dev);
+// What upload_models hands the launch: the staging set in use and its device block.  An entity set's models are optional: with none
+// (models_send) the batch is empty, recs() is null and applied() records nothing.
+struct ModelBatch {
+    StagingSet* set = nullptr;
+    uint8_t* dev = nullptr;
+    const uint4* recs() const { return reinterpret_cast<const uint4*>(dev); }
+    // behind the launch on `reader`: the set's next transfer and rt_stamp_destroy wait for it
+    hipError_t applied(hipStream_t reader) { return set ? set->ev_applied.record(reader) : hipSuccess; }
+};
+int upload_models(RtContext* c, const RtDrawStamp* models, uint32_t n, const void* extra_host, size_t extra_bytes, hipStream_t reader, ModelBatch* batch);
+int models_send(RtContext* c, const RtDrawStamp* models, uint32_t n, hipStream_t reader, ModelBatch* batch);
 
 }  // namespace rta

@@ -1,4 +1,5 @@
-// shadows_check.hpp — the host half of rt_shadow_entities that needs no context: the test of the call's plain arguments, the
+// shadows_check.hpp — the host half of rt_shadow_entities that needs no context: the test of the call's plain arguments (with the
+// one verdict on the two arrays of an entity set, entity_arrays_error, which the occluded lights, entity queries and sweeps share), the
 // validity of a batch of RtDrawBox records (rt_draw_boxes' boxes and this call's occluders: the one host definition) and whether a
 // frame has a sun term at all.  Plain C++ with no HIP include, so that tests/entity_shadows_main.cpp runs this very code on the CPU.
 // The comparisons are the kernels' (rt_tile_pass.hpp, box_valid): each is false for a NaN, so a record with a NaN fails.  (The
@@ -12,15 +13,21 @@
 
 namespace rta __attribute__((visibility("hidden"))) {
 
-constexpr uint32_t kMaxShadowBoxes = 4096, kMaxShadowModels = 4096;   // occluders per call, of either kind
+constexpr uint32_t kMaxEntityBoxes = 4096, kMaxEntityModels = 4096;   // an entity set (shadows, occluded lights, queries, sweeps): per call, of either kind
 
-// What is wrong with the arguments that are tested before the context is looked at, or nullptr: NULL uniforms, a NULL array with its
-// count above 0, a count above 4096, a strength that is not finite or lies outside (0, 1].
+// What is wrong with the two arrays of an entity set, or nullptr: a count above 4096, a NULL array with its count above 0.
+inline const char* entity_arrays_error(const void* boxes, uint32_t nboxes, const void* models, uint32_t nmodels) {
+    if (nboxes > kMaxEntityBoxes) return "more than 4096 boxes in one call";
+    if (nmodels > kMaxEntityModels) return "more than 4096 models in one call";
+    if ((nboxes > 0u && !boxes) || (nmodels > 0u && !models)) return "null pointer";
+    return nullptr;
+}
+
+// What is wrong with the arguments that are tested before the context is looked at, or nullptr: NULL uniforms, the arrays'
+// verdict, a strength that is not finite or lies outside (0, 1].
 inline const char* shadow_args_error(const void* u, const void* boxes, uint32_t nboxes, const void* models, uint32_t nmodels, float strength) {
     if (!u) return "null uniforms";
-    if (nboxes > kMaxShadowBoxes) return "more than 4096 boxes in one call";
-    if (nmodels > kMaxShadowModels) return "more than 4096 models in one call";
-    if ((nboxes > 0u && !boxes) || (nmodels > 0u && !models)) return "null pointer";
+    if (const char* e = entity_arrays_error(boxes, nboxes, models, nmodels)) return e;
     if (!(strength > 0.0f && strength <= 1.0f)) return "strength must lie in (0, 1]";   // (false for a NaN)
     return nullptr;
 }

@@ -45,7 +45,7 @@ RtDrawBox good() {
 
 int main() {
     static_assert(sizeof(RtEntityHit) == 48 && sizeof(RtRayHit) == 48 && sizeof(RtDrawBox) == 32 && sizeof(RtDrawStamp) == 32, "record sizes");
-    static_assert(rta::kMaxEntityRays == (1u << 24) && rta::kMaxQueryBoxes == 4096 && rta::kMaxQueryModels == 4096, "limits of a call");
+    static_assert(rta::kMaxEntityRays == (1u << 24) && rta::kMaxEntityBoxes == 4096 && rta::kMaxEntityModels == 4096, "limits of a call");
     static_assert(RT_ENTITY_NONE == 0 && RT_ENTITY_BOX == 1 && RT_ENTITY_MODEL == 2, "kinds");
 
     // ---- the plain arguments: the whole table ----

@@ -69,7 +69,7 @@ float* field(RtDrawBox& b, int f) { return f < 3 ? &b.lo[f] : &b.hi[f - 3]; }
 
 int main() {
     static_assert(sizeof(RtDrawBox) == 32, "RtDrawBox is 32 bytes");
-    static_assert(rta::kMaxShadowBoxes == 4096 && rta::kMaxShadowModels == 4096, "occluders per call");
+    static_assert(rta::kMaxEntityBoxes == 4096 && rta::kMaxEntityModels == 4096, "occluders per call");
     const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
     const float denorm = std::numeric_limits<float>::denorm_min(), big = std::numeric_limits<float>::max();
 

@@ -46,7 +46,7 @@ RtDrawBox good_box() {
 }  // namespace
 
 int main() {
-    static_assert(rta::kMaxPointLights == 1024 && rta::kMaxShadowBoxes == 4096 && rta::kMaxShadowModels == 4096, "records per call");
+    static_assert(rta::kMaxPointLights == 1024 && rta::kMaxEntityBoxes == 4096 && rta::kMaxEntityModels == 4096, "records per call");
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
 
     // ---- the plain arguments ----

@@ -32,16 +32,16 @@ int main(int argc, char** argv) {
     if (!read_all(argv[1], sweeps) || !read_all(argv[2], boxes)) return 2;
 
     std::printf("sweeps ");
-    for (const RtBoxSweep& s : sweeps) std::putchar(rta::entity_sweep_in_domain(s) ? '1' : '0');
-    const uint32_t bad_sweep = rta::first_invalid_entity_sweep(sweeps.data(), (uint32_t)sweeps.size());
+    for (const RtBoxSweep& s : sweeps) std::putchar(rta::sweep_in_domain(s) ? '1' : '0');
+    const uint32_t bad_sweep = rta::first_invalid_sweep(sweeps.data(), (uint32_t)sweeps.size());
     std::printf("\nfirst_invalid_sweep %u\nboxes ", bad_sweep);
     for (const RtDrawBox& b : boxes) std::putchar(rta::draw_box_valid(b) ? '1' : '0');
     const uint32_t bad_box = rta::first_invalid_draw_box(boxes.data(), (uint32_t)boxes.size());
     std::printf("\nfirst_invalid_box %u\n", bad_box);
 
     // every batch that ends before the first invalid record is valid; an empty batch reads nothing
-    bool prefixes = rta::first_invalid_entity_sweep(nullptr, 0) == 0u && rta::first_invalid_draw_box(nullptr, 0) == 0u;
-    for (uint32_t n = 0; n <= bad_sweep; n++) prefixes = prefixes && rta::first_invalid_entity_sweep(sweeps.data(), n) == n;
+    bool prefixes = rta::first_invalid_sweep(nullptr, 0) == 0u && rta::first_invalid_draw_box(nullptr, 0) == 0u;
+    for (uint32_t n = 0; n <= bad_sweep; n++) prefixes = prefixes && rta::first_invalid_sweep(sweeps.data(), n) == n;
     for (uint32_t n = 0; n <= bad_box; n++) prefixes = prefixes && rta::first_invalid_draw_box(boxes.data(), n) == n;
     std::printf("prefixes %d\n", prefixes ? 1 : 0);
 
