@@ -1036,6 +1036,69 @@ int rt_deposit_particles(RtContext* ctx, const RtParticleDeposit* params, RtPart
 int rt_deposit_particles_async(RtContext* ctx, const RtParticleDeposit* params, RtParticleState* states_dev, RtParticle* draw_dev,
                                uint32_t count, RtDepositCount* counts_dev);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Voxel settling: loose voxels fall, on the device — sand or gravel
+ * placed with rt_edit_voxels, the rubble a deposit poured, snow cover, the top of a pile after rt_edit_shapes carved a tunnel through
+ * it.  Without this call they hang in the air; a host that wants them to fall reads the box back with rt_read_box (which drains both
+ * lanes), walks the columns on the CPU and sends thousands of RtVoxelEdit records, every tick while anything is still falling.
+ * rt_deposit_particles_async -> rt_edit_shapes (carve) -> rt_settle_voxels_async runs without a host read.  The terrain's up axis is
+ * z: a game passes axis = 2, toward = 0.  The parameters of one call, 48 bytes: */
+typedef struct RtVoxelSettle {          /* 48 bytes */
+    int32_t  lo[3];  uint32_t max_fall;      /*  0  box of texels, inclusive, as RT_SHAPE_BOX's a; cells a voxel may fall in this call, >= 1; 0xFFFFFFFF = until it rests */
+    int32_t  hi[3];  uint32_t air_material;  /* 16  as RT_SHAPE_BOX's b; material word left in a cell that ends the call unoccupied after a voxel left it */
+    uint32_t loose_mask, loose_value;        /* 32  an occupied voxel is LOOSE iff (material & loose_mask) == loose_value; 0, 0: every occupied voxel */
+    uint8_t  axis, toward, reserved0[2];     /* 40  axis 0..2 = x, y, z; toward 0: voxels fall to lower texel coordinates, 1: to higher */
+    uint32_t reserved1;                      /* 44  must be 0 */
+} RtVoxelSettle;
+/* What a call did, 16 bytes, in host memory for rt_settle_voxels and in device memory for rt_settle_voxels_async: */
+typedef struct RtSettleCount { uint32_t moved, falling, distance, chunks; } RtSettleCount;   /* 16 bytes, ADDED to, wrapping */
+/* The rules.  Integer arithmetic only and a closed form: results are exact and do not depend on scheduling.  They are reproduced bit
+ * for bit by tests/settle_voxels_ref.py, which changes the world only through tests/voxel_edits.py and clips the box through
+ * tests/shape_edits.py (DESIGN.md "Voxel settling").
+ *   Box: lo / hi mean what a RT_SHAPE_BOX's a / b mean — texels, inclusive — with the same validity (|lo_k|, |hi_k| <= 4 R, lo_k <=
+ *     hi_k) and the same clipping to [0, R)^3, giving lo' / hi'.  There is no texel limit: the call needs no per-texel scratch.
+ *     Nothing outside the clipped box is read or written.  The far face of the box in the fall direction is a floor: a voxel never
+ *     leaves the box, and so never the region.  A host keeps the box off the window's seam.
+ *   Cells of a column: fix the two other coordinates and number the clipped box's cells along `axis` by height: h = x - lo' for
+ *     toward = 0, h = hi' - x for toward = 1; h = 0 .. H - 1.  A cell is OCCUPIED iff its minefield byte is 0 at the moment the call
+ *     runs in stream order, an occupied cell is LOOSE iff (material & loose_mask) == loose_value, and an occupied cell that is not
+ *     loose is FIXED.
+ *   Fall: for a loose cell at h let f = 1 + the highest fixed h' < h (0 if there is none) and E(h) = the number of unoccupied cells
+ *     h' with f <= h' < h.  The voxel moves to h - min(max_fall, E(h)) and keeps its material word.  Targets are distinct and the
+ *     order inside a column is kept, because E(h2) - E(h1) <= h2 - h1 - 1.  T calls with max_fall = 1 equal one call with max_fall =
+ *     T; 0xFFFFFFFF compacts every segment between fixed cells.
+ *   Final state of the box: a cell that is the target of a voxel is occupied and holds that voxel's word; a cell that a voxel left
+ *     and no voxel arrived at is unoccupied and holds air_material; every other cell keeps its occupancy and its material word —
+ *     a cell a voxel only passed on its way included, so T single steps and one call of T agree on every voxel and on the whole
+ *     minefield, while the single steps leave air_material in the unoccupied cells along the way.
+ *   Dirty chunks: a 64^3 chunk is DIRTY iff it holds the source or the target cell of a voxel that moved.  Dirty chunks have their
+ *     whole minefield rebuilt by rt_edit_voxels' rule and no other chunk's byte changes: in a dirty chunk the result equals
+ *     rt_edit_voxels with one solid = 0, air_material record per source followed by one solid = 1 record per target (the last record
+ *     of a voxel wins).  The coarse / brick nibble-map words over the clipped box's chunks are rebuilt:
+ *     rt_selftest(RT_SELFTEST_SCENE_MAPS) counts 0 afterwards.  A call in which nothing moves leaves every minefield and material
+ *     byte as it was.
+ *   Counts: the four RtSettleCount fields are ADDED to (wrapping uint32); `counts` may be NULL.  moved: voxels with a non-zero drop.
+ *     falling: loose voxels that could still fall after the call, E - drop > 0 — the host reads it to know when to stop calling.
+ *     distance: the sum of all drops.  chunks: the number of dirty chunks.
+ *   Ordering: the call is a world change with rt_edit_shapes' stream order, lane join, fence and staging, also under rt_set_stream.
+ *   Side effects: rt_edit_shapes' for ONE box shape equal to the box, whenever the clipped box is non-empty — whether or not anything
+ *     moved, because the host cannot know: the accumulation restarts, or with RtConfig.edit_radius one box (the clipped box) waits
+ *     for the next frame.
+ *   Errors: NULL ctx, NULL params, a bad box, axis > 2, toward > 1, max_fall == 0, loose_value & ~loose_mask != 0, a reserved byte or
+ *     word != 0: RT_ERR_INVALID_ARG.  No world resident: RT_ERR_NOT_READY.  An empty clipped box: RT_OK, nothing enqueued or reset.
+ *     A rejected call changes nothing.  Tile contexts, every RtKernel and every region size answer as rt_edit_shapes does.
+ *   Out of scope: sideways sliding (an angle of repose); connectivity (a floating island that should fall as a body); falling across
+ *     the window's seam; history bounds found on the device; turning falling voxels into particles or stamps.
+ *   Device work per call: the box's chunk ids through an edit staging set, one fill of a flag word per chunk of the box, then three
+ *     launches — columns (a lane per column of the clipped box walks it upwards and writes in place), chunks (a workgroup per chunk
+ *     of the box; one that holds no moved voxel returns at once) and rt_edit_voxels' nibble-map rebuild.
+ * With non-NULL `counts` (host memory) the call returns when the counts are in host memory; the world change itself stays
+ * stream-ordered. */
+int rt_settle_voxels(RtContext* ctx, const RtVoxelSettle* params, RtSettleCount* counts);
+/* Same with device counts, enqueued: counts_dev is valid after rt_sync (or, after rt_set_stream, in the caller's stream order);
+ * `params` is a host pointer, free again when the call returns.  A non-NULL counts_dev must pass rt_trace_rays_async's test (16-byte
+ * aligned memory of the context's device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued. */
+int rt_settle_voxels_async(RtContext* ctx, const RtVoxelSettle* params, RtSettleCount* counts_dev);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
  * after rt_draw_frame (and rt_draw_boxes) and before or after rt_denoise.  Each light reaches a pixel through one hard shadow ray
@@ -1629,7 +1692,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtParticleEmit, RtEmitCursor, rt_emit_particles, rt_emit_particles_async (particle emitters:
  *        debris spawned on the device from the occupied voxels of a shape, into a ring of particle states).
  *        Additive, same minor version: RtParticleDeposit, RtDepositCount, rt_deposit_particles, rt_deposit_particles_async (particle
- *        deposits: particles at rest become voxels of the region on the device). */
+ *        deposits: particles at rest become voxels of the region on the device).
+ *        Additive, same minor version: RtVoxelSettle, RtSettleCount, rt_settle_voxels, rt_settle_voxels_async (voxel settling: loose
+ *        voxels fall along an axis inside a box of texels on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

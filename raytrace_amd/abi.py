@@ -317,6 +317,49 @@ def make_particle_deposit(lo, hi, max_speed=0.0, lr=(0, 0, 0)):
     return p
 
 
+class RtVoxelSettle(C.Structure):
+    """rt_settle_voxels' parameters (ABI 1.3, additive: voxel settling): 48 bytes; the reserved bytes and word must be 0."""
+    _fields_ = [("lo", C.c_int32 * 3), ("max_fall", C.c_uint32), ("hi", C.c_int32 * 3), ("air_material", C.c_uint32), ("loose_mask", C.c_uint32),
+                ("loose_value", C.c_uint32), ("axis", C.c_uint8), ("toward", C.c_uint8), ("reserved0", C.c_uint8 * 2), ("reserved1", C.c_uint32)]
+
+
+class RtSettleCount(C.Structure):
+    """rt_settle_voxels' counters: 16 bytes, added to by every call."""
+    _fields_ = [("moved", C.c_uint32), ("falling", C.c_uint32), ("distance", C.c_uint32), ("chunks", C.c_uint32)]
+
+
+assert C.sizeof(RtVoxelSettle) == 48 and C.sizeof(RtSettleCount) == 16
+assert (RtVoxelSettle.max_fall.offset, RtVoxelSettle.hi.offset, RtVoxelSettle.air_material.offset, RtVoxelSettle.loose_mask.offset,
+        RtVoxelSettle.loose_value.offset, RtVoxelSettle.axis.offset, RtVoxelSettle.toward.offset, RtVoxelSettle.reserved0.offset,
+        RtVoxelSettle.reserved1.offset) == (12, 16, 28, 32, 36, 40, 41, 42, 44)
+SETTLE_DTYPE = np.dtype(RtVoxelSettle)             # the numpy view of the parameters
+SETTLE_COUNT_DTYPE = np.dtype(RtSettleCount)       # ... and of the counters
+SETTLE_UNLIMITED = 0xFFFFFFFF                      # RtVoxelSettle.max_fall: until the voxel rests
+
+
+def make_voxel_settle(lo, hi, max_fall=SETTLE_UNLIMITED, air_material=0, loose_mask=0, loose_value=0, axis=2, toward=0):
+    """An RtVoxelSettle: the box `lo`..`hi` of texels (inclusive, as a box shape's a and b), the cells a voxel may fall in this call,
+    the word left in vacated cells, the mask test that makes an occupied voxel loose (0, 0: every one) and the fall direction (the
+    terrain's down is axis 2 towards 0).  Refuses what the calls refuse without knowing R: a box with lo > hi, axis > 2, toward > 1,
+    max_fall == 0, a loose_value bit outside loose_mask.  The box's range is judged by the call (it needs R)."""
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("lo and hi have three components")
+    p = RtVoxelSettle()
+    for k in range(3):
+        p.lo[k], p.hi[k] = int(lo[k]), int(hi[k])
+        if p.lo[k] > p.hi[k]:
+            raise ValueError("the box needs lo <= hi on every axis")
+    if int(axis) not in (0, 1, 2) or int(toward) not in (0, 1):
+        raise ValueError("axis is 0, 1 or 2 and toward 0 or 1")
+    if not 1 <= int(max_fall) <= SETTLE_UNLIMITED:
+        raise ValueError("max_fall is 1..0xFFFFFFFF")
+    if int(loose_value) & ~int(loose_mask):
+        raise ValueError("loose_value has a bit outside loose_mask")
+    p.max_fall, p.air_material, p.loose_mask, p.loose_value = int(max_fall), int(air_material), int(loose_mask), int(loose_value)
+    p.axis, p.toward = int(axis), int(toward)
+    return p
+
+
 class RtDrawStamp(C.Structure):
     """rt_draw_stamps input (ABI 1.3, additive: voxel-model entities): 32 bytes; the reserved fields must be 0."""
     _fields_ = [("origin", C.c_float * 3), ("scale", C.c_float), ("stamp", C.c_uint32), ("orient", C.c_uint8), ("reserved0", C.c_uint8 * 3),

@@ -1,11 +1,12 @@
 // api_world.hip — the kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits, shape
-// edits, voxel stamps (their store, capture and placement), particle deposits and terrain generated on the device; rt_read_box reads
+// edits, voxel stamps (their store, capture and placement), particle deposits, voxel settling and terrain generated on the device; rt_read_box reads
 // the resident region back.  The ordering protocols stand here once each: world_change_begin / world_change_end round every change,
 // world_send / world_applied for the changes that come through a staging set (rt_context.hpp's staging_claim and staging_send, plus
 // the world change), and chunk_edit with its history rule (edit_history) for the four calls that rewrite whole chunks from a staged
-// list of chunk ids: rt_edit_voxels, rt_edit_shapes, rt_edit_stamps and the deposits hand it only what differs between them.
+// list of chunk ids: rt_edit_voxels, rt_edit_shapes, rt_edit_stamps, the deposits and the settling hand it only what differs between them.
 #include "deposit_check.hpp"
 #include "rt_context.hpp"
+#include "settle_check.hpp"
 
 using namespace rta;
 
@@ -209,6 +210,48 @@ int deposit_run(RtContext* c, const RtParticleDeposit& p, const DepositPlan& pla
             }
             LaunchTimer lt(c, 1);
             RT_HIP(c, rtd::launch_deposit_particles(c->d_mine_sw, c->d_mat_sw, reinterpret_cast<const uint32_t*>(dev), plan.nchunks, c->logr, a, c->stream));
+            return RT_OK;
+        },
+        &c->ev_deposit);
+}
+
+// ---- voxel settling (rt_settle_voxels[_async]): a world change whose sources and targets only the device knows --------------------
+static_assert(sizeof(RtVoxelSettle) == 48 && sizeof(RtSettleCount) == 16, "the layout the header states");
+
+// checks shared by the two calls, and the plan; RT_OK when there is work to enqueue, 1 for a call that enqueues nothing
+int settle_check(RtContext* c, const char* fn, const RtVoxelSettle* p, SettlePlan* plan) {
+    const char* e = settle_args_error(p);
+    if (!e) e = settle_params_error(*p, c->logr);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e + "; nothing was applied");
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    *plan = settle_plan(*p, c->logr);
+    return plan->empty ? 1 : RT_OK;
+}
+
+// A chunk edit (the clipped box's chunk ids; one pending box, the clipped box) whose apply step fills the flags and runs the column and
+// the chunk pass.  The scratch is the deposits' block, handled as they handle it.  counts_dev is a device address the stream may use.
+int settle_run(RtContext* c, const RtVoxelSettle& p, const SettlePlan& plan, void* counts_dev) {
+    const size_t words = settle_scratch_need(plan);
+    const int rc = deposit_scratch_reserve(c, words);
+    if (rc != RT_OK) return rc;
+    rtd::SettleArgs a;
+    a.flags = c->deposit_scratch;
+    a.counts = counts_dev ? reinterpret_cast<uint32_t*>(counts_dev) : c->deposit_scratch + plan.nchunks;
+    for (int k = 0; k < 3; k++) { a.lo[k] = plan.box.lo[k]; a.hi[k] = plan.box.hi[k]; }
+    a.max_fall = p.max_fall; a.air_material = p.air_material; a.loose_mask = p.loose_mask; a.loose_value = p.loose_value;
+    a.axis = p.axis; a.toward = p.toward;
+    return chunk_edit(
+        c, plan.need, staging_alloc(plan.need), plan.nchunks, 1u,
+        [&](uint8_t* host) { deposit_fill_chunks(plan, c->logr, reinterpret_cast<uint32_t*>(host)); return plan.need; },
+        [&](EditBox* boxes) { *boxes = plan.box; return 1u; },
+        [&](const uint8_t* dev) -> int {
+            RT_HIP(c, c->ev_deposit.wait_elsewhere(c->stream));   // the scratch is the previous call's until its chunk pass has run
+            {
+                LaunchTimer lt(c, 1);
+                RT_HIP(c, hipMemsetAsync(c->deposit_scratch, 0xFF, words * sizeof(uint32_t), c->stream));
+            }
+            LaunchTimer lt(c, 1);
+            RT_HIP(c, rtd::launch_settle_voxels(c->d_mine_sw, c->d_mat_sw, reinterpret_cast<const uint32_t*>(dev), plan.nchunks, c->logr, a, c->stream));
             return RT_OK;
         },
         &c->ev_deposit);
@@ -436,6 +479,37 @@ int rt_deposit_particles_async(RtContext* ctx, const RtParticleDeposit* params, 
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_deposit_particles_async: states, draw and counts must be 16-byte aligned memory of the context's device");
     if (rc == 1) return RT_OK;
     return deposit_run(ctx, *params, plan, states_dev, draw_dev, counts_dev, count);
+}
+
+int rt_settle_voxels(RtContext* ctx, const RtVoxelSettle* params, RtSettleCount* counts) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    SettlePlan plan;
+    int rc = settle_check(ctx, "rt_settle_voxels", params, &plan);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!counts) return settle_run(ctx, *params, plan, nullptr);
+    // the counts through the synchronous calls' pinned and device block on the render stream, the launches there, and the counts back
+    uint8_t* dev[1];
+    rc = stage_sync(ctx, ctx->stream, {{counts, sizeof *counts}}, dev);
+    if (rc != RT_OK) return rc;
+    rc = settle_run(ctx, *params, plan, dev[0]);
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->query_block.host, ctx->query_block.dev, sizeof *counts, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(counts, ctx->query_block.host, sizeof *counts);
+    return RT_OK;
+}
+
+int rt_settle_voxels_async(RtContext* ctx, const RtVoxelSettle* params, RtSettleCount* counts_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    SettlePlan plan;
+    const int rc = settle_check(ctx, "rt_settle_voxels_async", params, &plan);
+    if (rc != RT_OK && rc != 1) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (counts_dev && !query_device_ptr(ctx, counts_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_settle_voxels_async: counts must be 16-byte aligned memory of the context's device");
+    if (rc == 1) return RT_OK;
+    return settle_run(ctx, *params, plan, counts_dev);
 }
 
 int rt_stamp_create(RtContext* ctx, const int32_t extent[3], const uint32_t* materials, const uint8_t* state, uint32_t* id_out) {

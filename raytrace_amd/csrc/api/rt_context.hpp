@@ -344,6 +344,7 @@ struct __attribute__((visibility("hidden"))) RtContext {
     // rt_deposit_particles[_async]: a claim word per texel of the clipped box, a flag word per chunk of it and a spare count record
     // (rtd::deposit_scratch_words; at most 64 MiB and a little), grown on demand and never shrunk, in c->allocs (device_bytes; freed by
     // rt_destroy).  Every call uses it on the render stream or behind a lane join, so its launches follow the previous call's.
+    // rt_settle_voxels[_async] keeps its flag words and spare count record (rtd::settle_scratch_words) in the same block, the same way.
     uint32_t* deposit_scratch = nullptr;
     size_t deposit_scratch_words = 0;
     rta::LatchEvent ev_deposit;

@@ -270,6 +270,22 @@ inline size_t deposit_scratch_words(uint64_t texels, uint32_t nchunks) { return 
 hipError_t launch_deposit_particles(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, uint32_t nchunks, int logr, const DepositArgs& a,
                                     hipStream_t st);
 
+// rt_settle.hip: loose voxels of a box of texels fall along an axis (rt_settle_voxels).  Two launches — columns (a lane per column of
+// the clipped box) and chunks (a workgroup per chunk of the box, the chunk rebuild of rt_edit_voxels) — over a scratch the caller has
+// filled with 0xFF bytes: one flag word per chunk of the box (z-major: the order of the ascending chunk list), then a spare
+// RtSettleCount for a call without counts.
+struct SettleArgs {
+    uint32_t* flags;       // the scratch: chunk words
+    uint32_t* counts;      // RtSettleCount (never nullptr: the scratch's spare where the caller gave none)
+    int32_t lo[3], hi[3];  // the clipped box, texels, inclusive
+    uint32_t max_fall, air_material, loose_mask, loose_value;
+    uint32_t axis, toward; // 0..2; 0 = towards lower texel coordinates
+};
+inline size_t settle_scratch_words(uint32_t nchunks) { return (size_t)nchunks + 4u; }
+// `chunks`: the ids of the box's nchunks chunks, ascending
+hipError_t launch_settle_voxels(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, uint32_t nchunks, int logr, const SettleArgs& a,
+                                hipStream_t st);
+
 // rt_boxes.hip: entity boxes composited into a whole frame's row-major planes by depth (rt_draw_boxes).  One launch for the batch;
 // a wave owns an 8x8 pixel tile.
 struct DrawBoxesArgs {

@@ -547,6 +547,50 @@ int run_debris(const Options& o, const World& w) {
     return 0;
 }
 
+// The scene of --debris RADIUS --settle T and of its --fall K: the explosion at the voxel under the frame's centre with RT_PARTICLE_STICK
+// debris, the sphere that carves it, the step of a tick and the deposit box — the explosion's bounding box grown by 32 texels (lo, ext).
+struct DebrisPile {
+    int c[3];
+    int32_t lo[3], ext[3];
+    RtParticleEmit e{};
+    RtParticleDeposit dep{};
+    RtShapeEdit carve{};
+    RtParticleStep step{};
+};
+static int make_debris_pile(const Options& o, const Session& s, DebrisPile* pile) {
+    const int R = RT_ROOT_BLOCK_SIZE, radius = o.debris;
+    const int32_t* lr = s.u().lr;
+    const int32_t centre_px[2] = {o.width / 2, o.height / 2};
+    RtRayHit hit{};
+    int rc = rt_pick_pixels(s.ctx, &s.u(), centre_px, 1, &hit);
+    if (rc != RT_OK) return rc;
+    int (&c)[3] = pile->c;
+    c[0] = c[1] = c[2] = R / 2;
+    if (hit.kind == RT_HIT_SOLID) for (int a = 0; a < 3; a++) c[a] = hit.texel[a];
+    RtParticleEmit& e = pile->e;
+    RtParticleDeposit& dep = pile->dep;
+    int32_t (&lo)[3] = pile->lo, (&ext)[3] = pile->ext;
+    for (int a = 0; a < 3; a++) {
+        e.a[a] = 2 * c[a] + 1;
+        e.origin[a] = (float)(lr[a] - R / 2 + (((c[a] - lr[a]) % R + R) % R)) + 0.5f;
+        lo[a] = c[a] - radius - 32 < 0 ? 0 : c[a] - radius - 32;
+        const int hi = c[a] + radius + 32 > R - 1 ? R - 1 : c[a] + radius + 32;
+        ext[a] = hi - lo[a] + 1;
+        dep.lo[a] = lo[a]; dep.hi[a] = hi; dep.lr[a] = lr[a];
+    }
+    e.b[0] = 4 * radius * radius; e.kind = RT_SHAPE_SPHERE; e.response = RT_PARTICLE_STICK; e.seed = 0x5EEDu;
+    e.speed = 12.0f; e.spread = 3.0f; e.drift[2] = 4.0f; e.half = 0.125f; e.life_min = 30.0f; e.life_span = 2.0f;
+    e.density = (uint32_t)o.debris_density; e.emission = 0xFF000000u;
+    RtShapeEdit& carve = pile->carve;
+    for (int a = 0; a < 3; a++) { carve.a[a] = e.a[a]; carve.b[a] = e.b[a]; }
+    carve.kind = RT_SHAPE_SPHERE; carve.where = RT_WHERE_ALL; carve.solid = 0;
+    RtParticleStep& step = pile->step;
+    step.dt = 1.0f / 60.0f; step.accel[2] = -32.0f; step.damping = 1.0f; step.restitution = 0.5f; step.friction = 0.75f; step.rest_speed = 0.5f;
+    for (int a = 0; a < 3; a++) step.lr[a] = lr[a];
+    step.sweeps = (uint32_t)o.step_sweeps;
+    return RT_OK;
+}
+
 // --debris RADIUS --settle T [--density D]: particle deposits.  --debris' explosion with RT_PARTICLE_STICK debris: emit, carve, then T
 // ticks of rt_step_particles_async -> rt_deposit_particles_async -> rt_draw_particles_async with no host read, each of the three
 // calls between events of its own; the deposit box is the explosion's bounding box grown by 32 texels.  Then the region's box is put
@@ -561,33 +605,15 @@ int run_settle(const Options& o, const World& w) {
     if (!hip.ok) { std::fprintf(stderr, "--settle needs the HIP runtime for its device buffers\n"); return 1; }
     const int R = RT_ROOT_BLOCK_SIZE, radius = o.debris, ticks = o.settle;
     const int32_t* lr = s.u().lr;
-    const int32_t centre_px[2] = {o.width / 2, o.height / 2};
-    RtRayHit hit{};
-    int rc = rt_pick_pixels(s.ctx, &s.u(), centre_px, 1, &hit);
+    DebrisPile pile;
+    int rc = make_debris_pile(o, s, &pile);
     if (rc != RT_OK) return s.fail("settle", rc);
-    int c[3] = {R / 2, R / 2, R / 2};
-    if (hit.kind == RT_HIT_SOLID) for (int a = 0; a < 3; a++) c[a] = hit.texel[a];
-    RtParticleEmit e{};
-    RtParticleDeposit dep{};
-    int32_t lo[3], ext[3];
-    for (int a = 0; a < 3; a++) {
-        e.a[a] = 2 * c[a] + 1;
-        e.origin[a] = (float)(lr[a] - R / 2 + (((c[a] - lr[a]) % R + R) % R)) + 0.5f;
-        lo[a] = c[a] - radius - 32 < 0 ? 0 : c[a] - radius - 32;
-        const int hi = c[a] + radius + 32 > R - 1 ? R - 1 : c[a] + radius + 32;
-        ext[a] = hi - lo[a] + 1;
-        dep.lo[a] = lo[a]; dep.hi[a] = hi; dep.lr[a] = lr[a];
-    }
-    e.b[0] = 4 * radius * radius; e.kind = RT_SHAPE_SPHERE; e.response = RT_PARTICLE_STICK; e.seed = 0x5EEDu;
-    e.speed = 12.0f; e.spread = 3.0f; e.drift[2] = 4.0f; e.half = 0.125f; e.life_min = 30.0f; e.life_span = 2.0f;
-    e.density = (uint32_t)o.debris_density; e.emission = 0xFF000000u;
-    RtShapeEdit carve{};
-    for (int a = 0; a < 3; a++) { carve.a[a] = e.a[a]; carve.b[a] = e.b[a]; }
-    carve.kind = RT_SHAPE_SPHERE; carve.where = RT_WHERE_ALL; carve.solid = 0;
-    RtParticleStep step{};
-    step.dt = 1.0f / 60.0f; step.accel[2] = -32.0f; step.damping = 1.0f; step.restitution = 0.5f; step.friction = 0.75f; step.rest_speed = 0.5f;
-    for (int a = 0; a < 3; a++) step.lr[a] = lr[a];
-    step.sweeps = (uint32_t)o.step_sweeps;
+    const int (&c)[3] = pile.c;
+    const int32_t (&lo)[3] = pile.lo, (&ext)[3] = pile.ext;
+    const RtParticleEmit& e = pile.e;
+    const RtParticleDeposit& dep = pile.dep;
+    const RtShapeEdit& carve = pile.carve;
+    const RtParticleStep& step = pile.step;
     const uint32_t capacity = 1u << 20;
 
     uint32_t undo = 0;
@@ -690,6 +716,116 @@ int run_settle(const Options& o, const World& w) {
                 radius, ticks, o.debris_density, c[0], c[1], c[2], ext[0], ext[1], ext[2], live, o.width, o.height, o.spp, o.depth, counts.deposited,
                 counts.voxels, counts.occupied, counts.outside, (unsigned long long)host_voxels, step_ms, deposit_ms, draw_ms, tick_ms,
                 tick_ms > 0.0 ? deposit_ms / tick_ms : 0.0, host_ms);
+    return 0;
+}
+
+// --debris RADIUS --settle T --fall K [--density D]: voxel settling.  --settle's explosion and its T ticks of step and deposit, then a slab
+// four texels thick is carved under the crater across the whole deposit box (rt_edit_shapes), so that the rubble and the ground over
+// the slab hang in the air, and FALL_TICKS ticks of rt_settle_voxels_async run with max_fall = K over the deposit box (every occupied
+// voxel loose, down z), each between events of its own, with no host read.  Then the box is put back as it was after the carve (a
+// stamp) and the same ticks run with the host path the call replaces, call to usable device state: the box read back (rt_read_box,
+// words and minefield), the columns walked in C++ by the header's rule, one RtVoxelEdit record per source and per target,
+// rt_edit_voxels.  The mode fails if the host path's moved or distance differ from the device's counts.
+constexpr int FALL_TICKS = 8;
+int run_fall(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const HipEvents hip;
+    if (!hip.ok) { std::fprintf(stderr, "--fall needs the HIP runtime for its device buffers\n"); return 1; }
+    const int radius = o.debris, ticks = o.settle;
+    const int32_t* lr = s.u().lr;
+    DebrisPile pile;
+    int rc = make_debris_pile(o, s, &pile);
+    if (rc != RT_OK) return s.fail("fall", rc);
+    const int32_t (&lo)[3] = pile.lo, (&ext)[3] = pile.ext;
+    const uint32_t capacity = 1u << 20;
+    RtShapeEdit slab{};
+    for (int a = 0; a < 3; a++) { slab.a[a] = lo[a]; slab.b[a] = lo[a] + ext[a] - 1; }
+    slab.b[2] = pile.c[2] - radius - 2 < lo[2] + 4 ? lo[2] + 4 : pile.c[2] - radius - 2;
+    slab.a[2] = slab.b[2] - 3;
+    slab.kind = RT_SHAPE_BOX; slab.where = RT_WHERE_ALL; slab.solid = 0;
+    RtVoxelSettle fall{};
+    for (int a = 0; a < 3; a++) { fall.lo[a] = lo[a]; fall.hi[a] = lo[a] + ext[a] - 1; }
+    fall.max_fall = (uint32_t)o.fall; fall.axis = 2; fall.toward = 0;
+
+    DeviceRun run(hip, s.ctx);
+    const RtEmitCursor zero{0u, 0u, 0u, 0u};
+    const RtSettleCount none{0u, 0u, 0u, 0u};
+    RtParticleState* d_ring = (RtParticleState*)run.on_device(nullptr, (size_t)capacity * sizeof(RtParticleState));
+    RtEmitCursor* d_cursor = (RtEmitCursor*)run.on_device(&zero, sizeof zero);
+    RtSettleCount* d_counts = (RtSettleCount*)run.on_device(&none, sizeof none);
+    run.start();
+
+    // ---- the pile: emit, carve, T ticks of step and deposit, then the slab under it ------------------------------------------------
+    RtEmitCursor after{};
+    run.fine = run.fine && rt_emit_particles_async(s.ctx, &pile.e, 1, lr, d_ring, capacity, capacity, d_cursor) == RT_OK &&
+               rt_edit_shapes(s.ctx, &pile.carve, 1) == RT_OK && rt_sync(s.ctx) == RT_OK && hip.copy(&after, d_cursor, sizeof after, 2) == 0;
+    const uint32_t live = after.emitted;
+    for (int t = 0; t < ticks && run.fine && live; t++)
+        run.fine = rt_step_particles_async(s.ctx, &pile.step, d_ring, d_ring, nullptr, live) == RT_OK &&
+                   rt_deposit_particles_async(s.ctx, &pile.dep, d_ring, nullptr, live, nullptr) == RT_OK;
+    uint32_t undo = 0;
+    run.fine = run.fine && rt_edit_shapes(s.ctx, &slab, 1) == RT_OK && rt_stamp_capture(s.ctx, lo, ext, 0u, &undo) == RT_OK;
+    RtStampPlace back{};
+    for (int a = 0; a < 3; a++) back.at[a] = lo[a];
+    back.stamp = undo; back.where = RT_WHERE_ALL;
+
+    // ---- the device path -------------------------------------------------------------------------------------------------------
+    double settle_ms = 0.0;
+    for (int t = 0; t < FALL_TICKS && run.fine; t++) {
+        float ms = 0.0f;
+        run.fine = run.mark() && rt_settle_voxels_async(s.ctx, &fall, d_counts) == RT_OK && run.lap(&ms);
+        settle_ms += (double)ms / FALL_TICKS;
+    }
+    RtSettleCount counts{};
+    run.fine = run.fine && rt_sync(s.ctx) == RT_OK && hip.copy(&counts, d_counts, sizeof counts, 2) == 0;
+
+    // ---- the host path, on the box as it was after the slab was carved -----------------------------------------------------------
+    run.fine = run.fine && rt_edit_stamps(s.ctx, &back, 1) == RT_OK && rt_sync(s.ctx) == RT_OK;
+    const size_t nvox = (size_t)ext[0] * ext[1] * ext[2], plane = (size_t)ext[0] * ext[1];
+    std::vector<uint8_t> box_mine(nvox);
+    std::vector<uint32_t> box_mats(nvox);
+    std::vector<RtVoxelEdit> edits;
+    uint64_t host_moved = 0, host_distance = 0, host_records = 0;
+    double host_ms = 0.0;
+    for (int t = 0; t < FALL_TICKS && run.fine; t++) {
+        const auto t0 = std::chrono::steady_clock::now();
+        run.fine = rt_read_box(s.ctx, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], box_mats.data(), box_mine.data()) == RT_OK;
+        edits.clear();
+        for (size_t col = 0; col < plane && run.fine; col++) {
+            uint32_t gap = 0;   // unoccupied cells under the cell (every occupied voxel is loose: no fixed cell restarts it)
+            for (int h = 0; h < ext[2]; h++) {
+                const size_t at = (size_t)h * plane + col;
+                if (box_mine[at] != 0u) { gap++; continue; }
+                const uint32_t drop = gap < fall.max_fall ? gap : fall.max_fall;
+                if (drop == 0u) continue;
+                host_moved++; host_distance += drop;
+                RtVoxelEdit ed{};
+                ed.x = (uint16_t)(lo[0] + (int)(col % (size_t)ext[0])); ed.y = (uint16_t)(lo[1] + (int)(col / (size_t)ext[0])); ed.z = (uint16_t)(lo[2] + h);
+                ed.solid = 0; ed.material = fall.air_material;
+                edits.push_back(ed);                                   // the source; a later voxel's target may fill it again
+                ed.z = (uint16_t)(lo[2] + h - (int)drop); ed.solid = 1; ed.material = box_mats[at];
+                edits.push_back(ed);
+            }
+        }
+        host_records += edits.size();
+        run.fine = run.fine && rt_edit_voxels(s.ctx, edits.data(), (uint32_t)edits.size()) == RT_OK && rt_sync(s.ctx) == RT_OK;
+        host_ms += ms_since(t0) / FALL_TICKS;
+    }
+    if (run.fine) run.fine = rt_stamp_destroy(s.ctx, undo) == RT_OK;
+    if (!run.close()) { std::fprintf(stderr, "fall failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    // the host path restates the rule: it is a baseline only while it moves what the library moves
+    if (host_moved != counts.moved || host_distance != counts.distance) {
+        std::fprintf(stderr, "fall: the host path moved %llu voxels by %llu cells, the device %u by %u\n", (unsigned long long)host_moved,
+                     (unsigned long long)host_distance, counts.moved, counts.distance);
+        return 1;
+    }
+    std::printf("{\"debris\": %d, \"settle\": %d, \"fall\": %u, \"ticks\": %d, \"density\": %d, \"box\": [%d, %d, %d], \"slab_z\": [%d, %d], \"particles\": %u, "
+                "\"moved\": %u, \"falling\": %u, \"distance\": %u, \"chunks\": %u, \"host_moved\": %llu, \"host_distance\": %llu, \"host_records\": %llu, "
+                "\"settle_device_ms\": %.4f, \"host_path_ms\": %.3f}\n",
+                radius, ticks, fall.max_fall, FALL_TICKS, o.debris_density, ext[0], ext[1], ext[2], slab.a[2], slab.b[2], live, counts.moved, counts.falling,
+                counts.distance, counts.chunks, (unsigned long long)host_moved, (unsigned long long)host_distance, (unsigned long long)host_records,
+                settle_ms, host_ms);
     return 0;
 }
 

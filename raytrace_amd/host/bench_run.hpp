@@ -30,6 +30,7 @@ struct Options {
     int simulate = 0, step_sweeps = 3;
     int debris = 0, debris_density = 256;   // --debris RADIUS [--density D]
     int settle = 0;                         // --debris RADIUS --settle T
+    long long fall = 0;                     // --debris RADIUS --settle T --fall K (0xFFFFFFFF: until at rest)
     bool shadow_models = false, light_shadows = false, occluders_far = false;
     float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
@@ -54,6 +55,7 @@ int run_particles(const Options& o, const World& w);
 int run_simulate(const Options& o, const World& w);
 int run_debris(const Options& o, const World& w);
 int run_settle(const Options& o, const World& w);
+int run_fall(const Options& o, const World& w);
 int run_models(const Options& o, const World& w);
 int run_lights(const Options& o, const World& w);
 int run_shadows(const Options& o, const World& w);

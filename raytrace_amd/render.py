@@ -648,6 +648,24 @@ class Context:
         n = deposit_tensor_count(states_t, draw_t, counts_t, self._device)
         self._check(self._lib.rt_deposit_particles_async(self._h, C.byref(params), _dp(states_t), _dp(draw_t), n, _dp(counts_t)))
 
+    # -- voxel settling -----------------------------------------------------------------------------------
+    def settle_voxels(self, params, counts=None):
+        """rt_settle_voxels: the loose voxels in the box of `params` (an abi.RtVoxelSettle, abi.make_voxel_settle) fall along its axis
+        -> the abi.SETTLE_COUNT_DTYPE record `counts` (None starts from zeros) added to, a new record.  Synchronous for the counts;
+        the world change is stream-ordered."""
+        cnt = settle_counts(counts)
+        self._check(self._lib.rt_settle_voxels(self._h, C.byref(params), _p(cnt)))
+        return cnt[0]
+
+    def settle_voxels_async(self, params, counts_t=None):
+        """rt_settle_voxels_async: `counts_t` a contiguous torch device tensor of 16 bytes (RtSettleCount, added to) or None.
+        Enqueued: valid after sync(), or in the order of a stream given to set_stream()."""
+        if counts_t is not None:
+            _device_tensors(self._device, ("counts", counts_t))
+            if _nbytes(counts_t) != abi.SETTLE_COUNT_DTYPE.itemsize:
+                raise ValueError("counts must be a contiguous tensor of 16 bytes (one RtSettleCount)")
+        self._check(self._lib.rt_settle_voxels_async(self._h, C.byref(params), _dp(counts_t)))
+
     # -- voxel-model entities ----------------------------------------------------------------------------
     def draw_stamps(self, uniforms, models, face_lights):
         """rt_draw_stamps: `models` DRAW_STAMP_DTYPE[N] records (make_draw_stamps) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
@@ -1496,6 +1514,21 @@ def deposit_counts(counts=None):
     if isinstance(counts, abi.RtDepositCount):
         cnt[0] = (counts.deposited, counts.voxels, counts.occupied, counts.outside)
     elif isinstance(counts, (np.ndarray, np.void)) and counts.dtype == abi.DEPOSIT_COUNT_DTYPE:
+        cnt[0] = np.asarray(counts).reshape(-1)[0]
+    else:
+        cnt[0] = tuple(int(v) for v in counts)
+    return cnt
+
+
+def settle_counts(counts=None):
+    """The counters of Context.settle_voxels as one abi.SETTLE_COUNT_DTYPE record in an array of its own: zeros for None, else from
+    such a record, an abi.RtSettleCount or (moved, falling, distance, chunks)."""
+    cnt = np.zeros(1, dtype=abi.SETTLE_COUNT_DTYPE)
+    if counts is None:
+        return cnt
+    if isinstance(counts, abi.RtSettleCount):
+        cnt[0] = (counts.moved, counts.falling, counts.distance, counts.chunks)
+    elif isinstance(counts, (np.ndarray, np.void)) and counts.dtype == abi.SETTLE_COUNT_DTYPE:
         cnt[0] = np.asarray(counts).reshape(-1)[0]
     else:
         cnt[0] = tuple(int(v) for v in counts)
