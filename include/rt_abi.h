@@ -1086,8 +1086,9 @@ typedef struct RtSettleCount { uint32_t moved, falling, distance, chunks; } RtSe
  *   Errors: NULL ctx, NULL params, a bad box, axis > 2, toward > 1, max_fall == 0, loose_value & ~loose_mask != 0, a reserved byte or
  *     word != 0: RT_ERR_INVALID_ARG.  No world resident: RT_ERR_NOT_READY.  An empty clipped box: RT_OK, nothing enqueued or reset.
  *     A rejected call changes nothing.  Tile contexts, every RtKernel and every region size answer as rt_edit_shapes does.
- *   Out of scope: sideways sliding (an angle of repose); connectivity (a floating island that should fall as a body); falling across
- *     the window's seam; history bounds found on the device; turning falling voxels into particles or stamps.
+ *   Out of scope: sideways sliding (an angle of repose); falling across the window's seam; history bounds found on the device;
+ *     turning falling voxels into particles.  (Connectivity — a floating island that should fall as a body — is rt_detach_voxels',
+ *     "Voxel detachment" below.)
  *   Device work per call: the box's chunk ids through an edit staging set, one fill of a flag word per chunk of the box, then three
  *     launches — columns (a lane per column of the clipped box walks it upwards and writes in place), chunks (a workgroup per chunk
  *     of the box; one that holds no moved voxel returns at once) and rt_edit_voxels' nibble-map rebuild.
@@ -1098,6 +1099,84 @@ int rt_settle_voxels(RtContext* ctx, const RtVoxelSettle* params, RtSettleCount*
  * `params` is a host pointer, free again when the call returns.  A non-NULL counts_dev must pass rt_trace_rays_async's test (16-byte
  * aligned memory of the context's device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued. */
 int rt_settle_voxels_async(RtContext* ctx, const RtVoxelSettle* params, RtSettleCount* counts_dev);
+
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Voxel detachment: what is no longer held up is found and lifted out
+ * of the world, on the device — the top of a pillar an explosion cut through, a bridge whose supports were carved, an overhang.
+ * rt_settle_voxels lets loose columns fall but knows nothing of connectivity: such a body stays hanging in the air unless the host
+ * reads the box back with rt_read_box (which drains both lanes), flood-fills it on the CPU, sends one RtVoxelEdit per voxel and
+ * builds a stamp from host arrays.  This call decides which voxels of a box are unsupported, carves them and captures them into a
+ * stamp, which rt_draw_stamps draws as an entity, rt_sweep_entities moves without tunnelling, rt_shadow_entities shadows and
+ * rt_edit_stamps pastes back where it lands: carve -> detach -> (draw, sweep, shadow) -> paste runs without a host read. */
+#define RT_DETACH_CARVE            0x1u  /* detached voxels become unoccupied and hold air_material            */
+#define RT_DETACH_CAPTURE          0x2u  /* detached voxels are written into a new stamp (id in *stamp_out)    */
+#define RT_DETACH_ANCHOR_MATERIAL  0x4u  /* an occupied voxel with (material & anchor_mask) == anchor_value anchors too */
+typedef struct RtVoxelDetach {           /* 48 bytes */
+    int32_t  lo[3];  uint32_t flags;          /*  0  box of texels, inclusive, as RT_SHAPE_BOX's a; RT_DETACH_* bits */
+    int32_t  hi[3];  uint32_t air_material;   /* 16  as RT_SHAPE_BOX's b; word left in a carved cell */
+    uint32_t anchor_mask, anchor_value;       /* 32  read only with RT_DETACH_ANCHOR_MATERIAL, else both 0 */
+    uint32_t max_passes;                      /* 40  1..256 */
+    uint8_t  anchor_faces, reserved0[3];      /* 44  bit 2k: low face of axis k of the CLIPPED box, bit 2k+1: high */
+} RtVoxelDetach;
+/* What a call found, 48 bytes, in host memory for rt_detach_voxels and in device memory for rt_detach_voxels_async.  The counters
+ * are ADDED to (wrapping uint32), the bounds MERGED (min into lo, max into hi): a host starts lo at INT32_MAX and hi at INT32_MIN. */
+typedef struct RtDetachResult {          /* 48 bytes */
+    uint32_t detached, supported, passes, unconverged;
+    int32_t  lo[3];  uint32_t chunks;         /* texel bounds of the detached voxels; `chunks` = dirty chunks */
+    int32_t  hi[3];  uint32_t reserved;       /* never written */
+} RtDetachResult;
+/* The rules.  Integer arithmetic only: results are exact and do not depend on scheduling.  They are reproduced bit for bit by
+ * tests/detach_voxels_ref.py, which states them twice (a global flood fill, and the chunk passes below), changes the world only
+ * through tests/voxel_edits.py and clips the box through tests/shape_edits.py (DESIGN.md "Voxel detachment").
+ *   Box: lo / hi mean what a RT_SHAPE_BOX's a / b mean — texels, inclusive — with the same validity (|lo_k|, |hi_k| <= 4 R, lo_k <=
+ *     hi_k) and the same clipping to [0, R)^3, giving lo' / hi'.  Every extent hi'_k - lo'_k + 1 of the clipped box must be at most
+ *     256: the stamps' limit, and the bound of the per-texel scratch.  Nothing outside the clipped box is read, and nothing outside
+ *     it is written apart from the minefield bytes of dirty chunks.  A host keeps the box off the window's seam.
+ *   Occupied and anchor: a cell of the clipped box is OCCUPIED iff its minefield byte is 0 at the call's place in stream order.  An
+ *     occupied cell is an ANCHOR iff it lies on a face of the clipped box whose bit is set in anchor_faces, or — with
+ *     RT_DETACH_ANCHOR_MATERIAL — iff (material & anchor_mask) == anchor_value.  A call with no anchors is valid: every occupied
+ *     cell is then detached.
+ *   Supported and detached: SUPPORTED is the set of occupied cells reachable from an anchor by steps between face-adjacent occupied
+ *     cells of the clipped box (6-connectivity: contact along an edge or at a corner does not connect).  DETACHED = occupied and
+ *     not supported.
+ *   Passes: the pass count is part of the contract, so that max_passes behaves the same on every run.  Partition the clipped box by
+ *     the 64^3 texel-aligned chunks and let S_0 be the anchors.  For p >= 1 and every chunk part C, S_p within C is the closure
+ *     inside C, through occupied cells, of (S_{p-1} within C) and the occupied cells of C that are face-adjacent across a chunk face
+ *     to a cell of S_{p-1}.  The first p with S_p = S_{p-1} ends the process (S_p is SUPPORTED) and passes += p.  If no p <=
+ *     max_passes ends it: unconverged += 1, passes += max_passes, no world byte changes, detached / supported / chunks and the bounds
+ *     get nothing, and a requested stamp holds no voxel.  A box inside one chunk ends with p = 1 or 2.
+ *   RT_DETACH_CARVE: every detached cell becomes unoccupied and holds air_material.  A chunk is DIRTY iff it holds a detached cell;
+ *     dirty chunks have their whole minefield rebuilt by rt_edit_voxels' rule — the result equals rt_edit_voxels with one solid = 0,
+ *     air_material record per detached voxel — and no other chunk's byte changes.  The coarse / brick nibble-map words over the
+ *     box's chunks are rebuilt: rt_selftest(RT_SELFTEST_SCENE_MAPS) counts 0 afterwards.  Side effects are rt_edit_shapes' for ONE
+ *     box shape equal to the clipped box whenever it is non-empty — detached or not, converged or not, because the host cannot know:
+ *     the accumulation restarts, or with RtConfig.edit_radius one box (the clipped box) waits for the next frame.  The call is a
+ *     world change with rt_edit_shapes' stream order, lane join, fence and staging, also under rt_set_stream.
+ *   RT_DETACH_CAPTURE: stamp_out must be non-NULL.  A stamp of the clipped box's extent is created before anything is enqueued and
+ *     its id is valid on return, in both variants.  Stamp voxel d corresponds to texel lo' + d: a detached voxel is RT_STAMP_SOLID
+ *     with its material word, every other voxel RT_STAMP_ABSENT with word 0.  The capture reads the world before the carve of the
+ *     same call.  The limit of 1024 live stamps and RT_ERR_OOM behave as in rt_stamp_capture; rt_stamp_read, rt_stamp_destroy,
+ *     rt_edit_stamps and rt_draw_stamps treat the stamp like any other.  One stamp holds every detached body of the box.
+ *   Neither flag: a query, ordered like rt_stamp_capture.  It changes nothing the renderer reads, does not reset the accumulation
+ *     and records no pending box.  RT_DETACH_CAPTURE alone is ordered the same way.
+ *   Result: `result` may be NULL.  detached and supported count cells; chunks counts dirty chunks (with or without
+ *     RT_DETACH_CARVE); lo / hi are merged with the texel bounds of the detached cells.
+ *   Errors: NULL ctx or params, a bad box, a clipped extent above 256, an unknown flag bit, max_passes outside 1..256, anchor_faces
+ *     above 63, anchor_value & ~anchor_mask != 0, a mask or value set without RT_DETACH_ANCHOR_MATERIAL, a reserved byte != 0,
+ *     RT_DETACH_CAPTURE with a NULL stamp_out, RT_DETACH_CAPTURE with 1024 stamps live: RT_ERR_INVALID_ARG.  No world resident:
+ *     RT_ERR_NOT_READY.  An empty clipped box: RT_OK, nothing enqueued or reset, and *stamp_out = 0 if given.  A rejected call
+ *     changes nothing and creates no stamp.  Tile contexts, every RtKernel and every region size answer as rt_edit_shapes does.
+ *   Out of scope: stamps cut to the detached bounds; one stamp per body; boxes across the window's seam; history bounds found on
+ *     the device; 18- or 26-connectivity; rotation or physics of the falling body (the host moves it with rt_sweep_entities).
+ *   Device work per call: a seed launch (a workgroup per chunk of the box: occupancy bits and anchors), max_passes reach launches (a
+ *     workgroup per chunk closes its reach bits in LDS; every workgroup of a launch after the end returns at once), an apply launch
+ *     and, with RT_DETACH_CARVE, the chunk rebuild (a chunk without a detached voxel returns at once) and rt_edit_voxels' nibble-map
+ *     rebuild.  No host read sits in between.
+ * With non-NULL `result` (host memory) the call returns when the result is in host memory; a world change stays stream-ordered. */
+int rt_detach_voxels(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult* result, uint32_t* stamp_out);
+/* Same with a device result, enqueued: result_dev is valid after rt_sync (or, after rt_set_stream, in the caller's stream order);
+ * `params` and `stamp_out` are host pointers.  A non-NULL result_dev must pass rt_trace_rays_async's test (16-byte aligned memory of
+ * the context's device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued. */
+int rt_detach_voxels_async(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult* result_dev, uint32_t* stamp_out);
 
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
@@ -1694,7 +1773,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtParticleDeposit, RtDepositCount, rt_deposit_particles, rt_deposit_particles_async (particle
  *        deposits: particles at rest become voxels of the region on the device).
  *        Additive, same minor version: RtVoxelSettle, RtSettleCount, rt_settle_voxels, rt_settle_voxels_async (voxel settling: loose
- *        voxels fall along an axis inside a box of texels on the device). */
+ *        voxels fall along an axis inside a box of texels on the device).
+ *        Additive, same minor version: RtVoxelDetach, RtDetachResult, RT_DETACH_*, rt_detach_voxels, rt_detach_voxels_async (voxel
+ *        detachment: the unsupported voxels of a box of texels are found, carved and captured into a stamp on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

@@ -58,6 +58,8 @@ AMD_FUNCTIONS = {
     "rt_deposit_particles_async": (INT, [P, P, P, P, U32, P]),
     "rt_settle_voxels": (INT, [P, P, P]),
     "rt_settle_voxels_async": (INT, [P, P, P]),
+    "rt_detach_voxels": (INT, [P, P, P, P]),
+    "rt_detach_voxels_async": (INT, [P, P, P, P]),
     "rt_trace_entities": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     "rt_trace_entities_async": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     "rt_pick_entities": (INT, [P, UNI, P, U32, P, U32, P, U32, P, P]),

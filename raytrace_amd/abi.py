@@ -360,6 +360,61 @@ def make_voxel_settle(lo, hi, max_fall=SETTLE_UNLIMITED, air_material=0, loose_m
     return p
 
 
+RT_DETACH_CARVE, RT_DETACH_CAPTURE, RT_DETACH_ANCHOR_MATERIAL = 0x1, 0x2, 0x4   # RtVoxelDetach.flags (ABI 1.3, additive: voxel detachment)
+
+
+class RtVoxelDetach(C.Structure):
+    """rt_detach_voxels' parameters (ABI 1.3, additive: voxel detachment): 48 bytes; the reserved bytes must be 0."""
+    _fields_ = [("lo", C.c_int32 * 3), ("flags", C.c_uint32), ("hi", C.c_int32 * 3), ("air_material", C.c_uint32), ("anchor_mask", C.c_uint32),
+                ("anchor_value", C.c_uint32), ("max_passes", C.c_uint32), ("anchor_faces", C.c_uint8), ("reserved0", C.c_uint8 * 3)]
+
+
+class RtDetachResult(C.Structure):
+    """rt_detach_voxels' result: 48 bytes; the counters are added to, the bounds merged (min into lo, max into hi)."""
+    _fields_ = [("detached", C.c_uint32), ("supported", C.c_uint32), ("passes", C.c_uint32), ("unconverged", C.c_uint32), ("lo", C.c_int32 * 3),
+                ("chunks", C.c_uint32), ("hi", C.c_int32 * 3), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RtVoxelDetach) == 48 and C.sizeof(RtDetachResult) == 48
+assert (RtVoxelDetach.flags.offset, RtVoxelDetach.hi.offset, RtVoxelDetach.air_material.offset, RtVoxelDetach.anchor_mask.offset,
+        RtVoxelDetach.anchor_value.offset, RtVoxelDetach.max_passes.offset, RtVoxelDetach.anchor_faces.offset,
+        RtVoxelDetach.reserved0.offset) == (12, 16, 28, 32, 36, 40, 44, 45)
+assert (RtDetachResult.unconverged.offset, RtDetachResult.lo.offset, RtDetachResult.chunks.offset, RtDetachResult.hi.offset,
+        RtDetachResult.reserved.offset) == (12, 16, 28, 32, 44)
+DETACH_DTYPE = np.dtype(RtVoxelDetach)             # the numpy view of the parameters
+DETACH_RESULT_DTYPE = np.dtype(RtDetachResult)     # ... and of the result
+DETACH_MAX_PASSES = 256
+
+
+def make_voxel_detach(lo, hi, flags=RT_DETACH_CARVE | RT_DETACH_CAPTURE, anchor_faces=0x10, air_material=0, anchor_mask=0, anchor_value=0,
+                      max_passes=DETACH_MAX_PASSES):
+    """An RtVoxelDetach: the box `lo`..`hi` of texels (inclusive, as a box shape's a and b), the RT_DETACH_* flags, the faces of the
+    clipped box that anchor (bit 2k the low face of axis k, bit 2k + 1 the high one; the default is the low z face: the ground), the
+    word left in carved cells, the mask test of anchoring materials and the pass limit.  Refuses what the calls refuse without
+    knowing R: a box with lo > hi, an unknown flag, anchor_faces above 63, max_passes outside 1..256, an anchor_value bit outside
+    anchor_mask, a mask or value without RT_DETACH_ANCHOR_MATERIAL.  The box's range and extent are judged by the call (it needs R)."""
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("lo and hi have three components")
+    p = RtVoxelDetach()
+    for k in range(3):
+        p.lo[k], p.hi[k] = int(lo[k]), int(hi[k])
+        if p.lo[k] > p.hi[k]:
+            raise ValueError("the box needs lo <= hi on every axis")
+    if int(flags) & ~(RT_DETACH_CARVE | RT_DETACH_CAPTURE | RT_DETACH_ANCHOR_MATERIAL):
+        raise ValueError("flags holds an unknown bit")
+    if not 0 <= int(anchor_faces) <= 63:
+        raise ValueError("anchor_faces is 0..63")
+    if not 1 <= int(max_passes) <= DETACH_MAX_PASSES:
+        raise ValueError("max_passes is 1..256")
+    if int(anchor_value) & ~int(anchor_mask):
+        raise ValueError("anchor_value has a bit outside anchor_mask")
+    if not int(flags) & RT_DETACH_ANCHOR_MATERIAL and (int(anchor_mask) or int(anchor_value)):
+        raise ValueError("anchor_mask and anchor_value need RT_DETACH_ANCHOR_MATERIAL")
+    p.flags, p.air_material, p.anchor_mask, p.anchor_value = int(flags), int(air_material), int(anchor_mask), int(anchor_value)
+    p.max_passes, p.anchor_faces = int(max_passes), int(anchor_faces)
+    return p
+
+
 class RtDrawStamp(C.Structure):
     """rt_draw_stamps input (ABI 1.3, additive: voxel-model entities): 32 bytes; the reserved fields must be 0."""
     _fields_ = [("origin", C.c_float * 3), ("scale", C.c_float), ("stamp", C.c_uint32), ("orient", C.c_uint8), ("reserved0", C.c_uint8 * 3),

@@ -1,10 +1,12 @@
 // api_world.hip — the kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits, shape
-// edits, voxel stamps (their store, capture and placement), particle deposits, voxel settling and terrain generated on the device; rt_read_box reads
+// edits, voxel stamps (their store, capture and placement), particle deposits, voxel settling, voxel detachment and terrain generated on the device; rt_read_box reads
 // the resident region back.  The ordering protocols stand here once each: world_change_begin / world_change_end round every change,
 // world_send / world_applied for the changes that come through a staging set (rt_context.hpp's staging_claim and staging_send, plus
 // the world change), and chunk_edit with its history rule (edit_history) for the four calls that rewrite whole chunks from a staged
-// list of chunk ids: rt_edit_voxels, rt_edit_shapes, rt_edit_stamps, the deposits and the settling hand it only what differs between them.
+// list of chunk ids: rt_edit_voxels, rt_edit_shapes, rt_edit_stamps, the deposits, the settling and a carving detachment hand it only
+// what differs between them.
 #include "deposit_check.hpp"
+#include "detach_check.hpp"
 #include "rt_context.hpp"
 #include "settle_check.hpp"
 
@@ -255,6 +257,81 @@ int settle_run(RtContext* c, const RtVoxelSettle& p, const SettlePlan& plan, voi
             return RT_OK;
         },
         &c->ev_deposit);
+}
+
+// ---- voxel detachment (rt_detach_voxels[_async]): a world change (RT_DETACH_CARVE) or a query whose voxels only the device knows ---
+static_assert(sizeof(RtVoxelDetach) == 48 && sizeof(RtDetachResult) == 48, "the layout the header states");
+static_assert(kDetachMaxExtent == kMaxStampExtent && kDetachMaxPasses == rtd::kDetachMaxPasses && kDetachChunkWords == rtd::kDetachChunkWords &&
+                  kDetachHeadWords == rtd::kDetachHeadWords,
+              "the host's limits and layout are the stamps' and the kernels'");
+
+// checks shared by the two calls, and the plan; RT_OK when there is work to enqueue, 1 for a call that enqueues nothing
+int detach_check(RtContext* c, const char* fn, const RtVoxelDetach* p, const uint32_t* stamp_out, DetachPlan* plan) {
+    const char* e = detach_args_error(p, stamp_out);
+    if (!e) e = detach_params_error(*p, c->logr);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e + "; nothing was applied");
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    *plan = detach_plan(*p, c->logr);
+    if (plan->empty) return 1;
+    if ((p->flags & RT_DETACH_CAPTURE) != 0u && c->stamps.live == kMaxStamps)
+        return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": 1024 stamps are live; nothing was applied");
+    return RT_OK;
+}
+
+// The launches of one call, `e` the new stamp or null.  With RT_DETACH_CARVE a chunk edit (the clipped box's chunk ids; one pending
+// box, the clipped box); without it rt_stamp_capture's protocol: the launches go to the stream the edits use, behind every earlier world
+// change, and read the region only; what they write — the scratch, the result, the stamp's arrays — is followed in stream order, by
+// ev_capture (entity queries on the query stream) and by the fence (a later change may start on the other lane's stream).
+int detach_enqueue(RtContext* c, const RtVoxelDetach& p, const DetachPlan& plan, void* result_dev, StampEntry* e) {
+    rtd::DetachArgs a;
+    a.scratch = c->detach_scratch;
+    a.result = result_dev ? reinterpret_cast<uint32_t*>(result_dev) : c->detach_scratch + rtd::kDetachSpareResult;
+    a.stamp_mats = e ? reinterpret_cast<uint32_t*>(e->mats) : nullptr;
+    a.stamp_state = e ? reinterpret_cast<uint8_t*>(e->state) : nullptr;
+    for (int k = 0; k < 3; k++) { a.lo[k] = plan.box.lo[k]; a.hi[k] = plan.box.hi[k]; }
+    a.flags = p.flags; a.air_material = p.air_material; a.anchor_mask = p.anchor_mask; a.anchor_value = p.anchor_value;
+    a.max_passes = p.max_passes; a.anchor_faces = p.anchor_faces;
+    if (e && !c->ev_capture.ev) RT_HIP(c, new_event(c, &c->ev_capture.ev));
+    auto launches = [&](const uint8_t* dev) -> int {
+        RT_HIP(c, c->ev_detach.wait_elsewhere(c->stream));   // the scratch is the previous call's until its last launch has run
+        LaunchTimer lt(c, 1);
+        RT_HIP(c, rtd::launch_detach_voxels(c->d_mine_sw, c->d_mat_sw, reinterpret_cast<const uint32_t*>(dev), plan.nchunks, c->logr, a, c->stream));
+        if (e) RT_HIP(c, c->ev_capture.record(c->stream));
+        return RT_OK;
+    };
+    if ((p.flags & RT_DETACH_CARVE) != 0u)
+        return chunk_edit(
+            c, plan.need, staging_alloc(plan.need), plan.nchunks, 1u,
+            [&](uint8_t* host) { deposit_fill_chunks(plan, c->logr, reinterpret_cast<uint32_t*>(host)); return plan.need; },
+            [&](EditBox* boxes) { *boxes = plan.box; return 1u; }, launches, &c->ev_detach);
+    const int rc = launches(nullptr);
+    if (rc != RT_OK) return rc;
+    RT_HIP(c, c->ev_detach.record(c->stream));
+    RT_HIP(c, fence_lanes_after(c, c->stream));
+    return RT_OK;
+}
+
+// The scratch, the stamp (created before anything is enqueued, removed again if anything after that fails) and the launches.
+// result_dev is a device address the stream may use, or null.
+int detach_run(RtContext* c, const RtVoxelDetach& p, const DetachPlan& plan, void* result_dev, uint32_t* stamp_out) {
+    int rc = detach_scratch_reserve(c, detach_scratch_need(plan));
+    if (rc != RT_OK) return rc;
+    StampEntry* e = nullptr;
+    if ((p.flags & RT_DETACH_CAPTURE) != 0u) {
+        e = c->stamps.add(plan.ext);
+        RT_HIP(c, stamp_alloc(c, e));
+    }
+    rc = detach_enqueue(c, p, plan, result_dev, e);
+    if (rc != RT_OK) {
+        if (e) {
+            (void)hipStreamSynchronize(c->stream);
+            stamp_free(c, e);
+        }
+        return rc;
+    }
+    if (e) e->used = true;
+    if (stamp_out) *stamp_out = e ? e->id : 0u;
+    return RT_OK;
 }
 
 }  // namespace
@@ -510,6 +587,41 @@ int rt_settle_voxels_async(RtContext* ctx, const RtVoxelSettle* params, RtSettle
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_settle_voxels_async: counts must be 16-byte aligned memory of the context's device");
     if (rc == 1) return RT_OK;
     return settle_run(ctx, *params, plan, counts_dev);
+}
+
+int rt_detach_voxels(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult* result, uint32_t* stamp_out) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    DetachPlan plan;
+    int rc = detach_check(ctx, "rt_detach_voxels", params, stamp_out, &plan);
+    if (rc == 1 && stamp_out) *stamp_out = 0u;
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!result) return detach_run(ctx, *params, plan, nullptr, stamp_out);
+    // the result through the synchronous calls' pinned and device block on the render stream, the launches there, and the result back
+    uint8_t* dev[1];
+    rc = stage_sync(ctx, ctx->stream, {{result, sizeof *result}}, dev);
+    if (rc != RT_OK) return rc;
+    rc = detach_run(ctx, *params, plan, dev[0], stamp_out);
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->query_block.host, ctx->query_block.dev, sizeof *result, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(result, ctx->query_block.host, sizeof *result);
+    return RT_OK;
+}
+
+int rt_detach_voxels_async(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult* result_dev, uint32_t* stamp_out) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    DetachPlan plan;
+    const int rc = detach_check(ctx, "rt_detach_voxels_async", params, stamp_out, &plan);
+    if (rc != RT_OK && rc != 1) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (result_dev && !query_device_ptr(ctx, result_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_detach_voxels_async: result must be 16-byte aligned memory of the context's device");
+    if (rc == 1) {
+        if (stamp_out) *stamp_out = 0u;
+        return RT_OK;
+    }
+    return detach_run(ctx, *params, plan, result_dev, stamp_out);
 }
 
 int rt_stamp_create(RtContext* ctx, const int32_t extent[3], const uint32_t* materials, const uint8_t* state, uint32_t* id_out) {

@@ -348,6 +348,12 @@ struct __attribute__((visibility("hidden"))) RtContext {
     uint32_t* deposit_scratch = nullptr;
     size_t deposit_scratch_words = 0;
     rta::LatchEvent ev_deposit;
+    // rt_detach_voxels[_async]: the pass record, a spare result record, a flag word per chunk of the clipped box and three bitmaps of
+    // 32 KiB per chunk — occupancy and two reach buffers (rtd::detach_scratch_words; at most 125 chunks: 12 MiB), grown on demand and
+    // never shrunk, in c->allocs (device_bytes; freed by rt_destroy), handled as the deposits' block is.
+    uint32_t* detach_scratch = nullptr;
+    size_t detach_scratch_words = 0;
+    rta::LatchEvent ev_detach;
 };
 
 namespace rta __attribute__((visibility("hidden"))) {
@@ -487,6 +493,9 @@ inline int particle_scratch_reserve(RtContext* c, size_t words) {
 inline int emit_scratch_reserve(RtContext* c, size_t words) { return scratch_reserve(c, &c->emit_scratch, &c->emit_scratch_words, &c->ev_emit, words); }
 inline int deposit_scratch_reserve(RtContext* c, size_t words) {
     return scratch_reserve(c, &c->deposit_scratch, &c->deposit_scratch_words, &c->ev_deposit, words);
+}
+inline int detach_scratch_reserve(RtContext* c, size_t words) {
+    return scratch_reserve(c, &c->detach_scratch, &c->detach_scratch_words, &c->ev_detach, words);
 }
 
 // An environment knob (experiments, A/B timing): *field = v when `s` holds an integer in lo..hi; anything else is ignored.

@@ -286,6 +286,29 @@ inline size_t settle_scratch_words(uint32_t nchunks) { return (size_t)nchunks + 
 hipError_t launch_settle_voxels(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, uint32_t nchunks, int logr, const SettleArgs& a,
                                 hipStream_t st);
 
+// rt_detach.hip: the unsupported voxels of a box of texels are found, carved and captured into a stamp (rt_detach_voxels).  A seed
+// launch, max_passes reach launches and an apply launch, each a workgroup per chunk of the box (z-major over the box's chunks: the
+// order of the ascending chunk list), then with RT_DETACH_CARVE the chunk rebuild of rt_edit_voxels behind a flag word's early exit.
+// The scratch needs no fill: the seed launch writes every word a later launch reads.  Its layout, in words: the head — word p
+// (1..256) says whether pass p changed anything, words kDetachSpareResult.. are a spare RtDetachResult —, a flag per chunk (to a
+// multiple of four), then per chunk 64 x 64 rows of 64 bits along x (row z * 64 + y) three times: occupancy masked to the box, reach
+// buffer 0, reach buffer 1.  Pass p reads buffer (p - 1) & 1 and writes buffer p & 1.
+constexpr uint32_t kDetachMaxPasses = 256;
+constexpr size_t kDetachChunkWords = 64u * 64u * 2u, kDetachHeadWords = 288u, kDetachSpareResult = 272u;
+struct DetachArgs {
+    uint32_t* scratch;     // detach_scratch_words(nchunks) words
+    uint32_t* result;      // RtDetachResult (never nullptr: the scratch's spare where the caller gave none)
+    uint32_t* stamp_mats;  // the new stamp's arrays over the clipped box, or nullptr without RT_DETACH_CAPTURE
+    uint8_t* stamp_state;
+    int32_t lo[3], hi[3];  // the clipped box, texels, inclusive
+    uint32_t flags, air_material, anchor_mask, anchor_value, max_passes, anchor_faces;
+};
+__host__ __device__ inline size_t detach_flag_words(uint32_t nchunks) { return ((size_t)nchunks + 3u) & ~(size_t)3u; }
+inline size_t detach_scratch_words(uint32_t nchunks) { return kDetachHeadWords + detach_flag_words(nchunks) + 3u * kDetachChunkWords * (size_t)nchunks; }
+// `chunks`: the ids of the box's nchunks chunks, ascending (read only with RT_DETACH_CARVE)
+hipError_t launch_detach_voxels(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, uint32_t nchunks, int logr, const DetachArgs& a,
+                                hipStream_t st);
+
 // rt_boxes.hip: entity boxes composited into a whole frame's row-major planes by depth (rt_draw_boxes).  One launch for the batch;
 // a wave owns an 8x8 pixel tile.
 struct DrawBoxesArgs {

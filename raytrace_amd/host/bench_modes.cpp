@@ -829,6 +829,162 @@ int run_fall(const Options& o, const World& w) {
     return 0;
 }
 
+// --collapse RADIUS: voxel detachment.  Under the texel at the frame's centre a block of RADIUS x RADIUS texels' footprint is cut
+// out of the terrain: a slab four texels thick RADIUS texels below the surface and four trenches two texels wide round the footprint, up to
+// 32 texels over the surface (rt_edit_shapes), so that a body of about RADIUS^3 voxels hangs free.  The detach box is the footprint grown by
+// six texels from under the slab to the trenches' top; every face but the top anchors.  The timed call, COLLAPSE_REPS times between
+// events of its own with the box put back as it was after the carve (a stamp) in front of each: rt_detach_voxels_async with
+// RT_DETACH_CARVE | RT_DETACH_CAPTURE, then one rt_draw_stamps of the result into the frame drawn before.  Then the same with the host path
+// the call replaces, call to usable device state: the box read back (rt_read_box, words and minefield), a flood fill in C++ from the
+// anchors, one RtVoxelEdit record per detached voxel, rt_edit_voxels, rt_stamp_create from host arrays and the same draw.  The mode fails
+// unless both paths detach the same voxels with the same words.
+constexpr int COLLAPSE_REPS = 4;
+int run_collapse(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const HipEvents hip;
+    if (!hip.ok) { std::fprintf(stderr, "--collapse needs the HIP runtime for its device buffers\n"); return 1; }
+    const int R = RT_ROOT_BLOCK_SIZE, radius = o.collapse;
+    const int32_t* lr = s.u().lr;
+    const int32_t centre_px[2] = {o.width / 2, o.height / 2};
+    RtRayHit hit{};
+    int rc = rt_pick_pixels(s.ctx, &s.u(), centre_px, 1, &hit);
+    if (rc != RT_OK) return s.fail("collapse", rc);
+    int c[3] = {R / 2, R / 2, R / 2};
+    if (hit.kind == RT_HIT_SOLID) for (int a = 0; a < 3; a++) c[a] = hit.texel[a];
+    auto clamp = [R](int v) { return v < 0 ? 0 : v > R - 1 ? R - 1 : v; };
+    // the footprint f0..f1 (x, y), the slab's z range, the trenches' top and the detach box
+    int f0[2], f1[2];
+    for (int a = 0; a < 2; a++) { f0[a] = clamp(c[a] - radius / 2); f1[a] = clamp(f0[a] + radius - 1); }
+    const int slab_hi = clamp(c[2] - radius), slab_lo = clamp(slab_hi - 3), top = clamp(c[2] + 32);
+    RtVoxelDetach det{};
+    for (int a = 0; a < 2; a++) { det.lo[a] = clamp(f0[a] - 6); det.hi[a] = clamp(f1[a] + 6); }
+    det.lo[2] = clamp(slab_lo - 2); det.hi[2] = top;
+    det.flags = RT_DETACH_CARVE | RT_DETACH_CAPTURE; det.max_passes = 32; det.anchor_faces = 0x1F;
+    int32_t lo[3], ext[3];
+    for (int a = 0; a < 3; a++) { lo[a] = det.lo[a]; ext[a] = det.hi[a] - det.lo[a] + 1; }
+    RtShapeEdit cuts[5] = {};
+    for (RtShapeEdit& e : cuts) {
+        e.kind = RT_SHAPE_BOX; e.where = RT_WHERE_ALL; e.solid = 0;
+        e.a[0] = clamp(f0[0] - 2); e.a[1] = clamp(f0[1] - 2); e.a[2] = slab_lo;
+        e.b[0] = clamp(f1[0] + 2); e.b[1] = clamp(f1[1] + 2); e.b[2] = top;
+    }
+    cuts[0].b[2] = slab_hi;                                   // the slab; then the trenches at low x, high x, low y, high y
+    cuts[1].b[0] = cuts[1].a[0] + 1; cuts[2].a[0] = cuts[2].b[0] - 1; cuts[3].b[1] = cuts[3].a[1] + 1; cuts[4].a[1] = cuts[4].b[1] - 1;
+
+    uint32_t undo = 0;
+    rc = rt_edit_shapes(s.ctx, cuts, 5);
+    if (rc == RT_OK) rc = rt_stamp_capture(s.ctx, lo, ext, 0u, &undo);
+    // the body is drawn one texel above where it was, lit by one probe at the block's centre
+    RtProbeLight light{};
+    const float centre[3] = {(float)(lr[0] - R / 2 + c[0]) + 0.5f, (float)(lr[1] - R / 2 + c[1]) + 0.5f, (float)(lr[2] - R / 2 + top) + 0.5f};
+    const RtLightProbe probe = sphere_probe(0, centre);
+    if (rc == RT_OK) rc = rt_probe_light(s.ctx, &s.u(), &probe, 1, 4, 2, &light);
+    if (rc != RT_OK) return s.fail("collapse", rc);
+    const RtProbeLight faces[6] = {light, light, light, light, light, light};
+    RtStampPlace back{};
+    for (int a = 0; a < 3; a++) back.at[a] = lo[a];
+    back.stamp = undo; back.where = RT_WHERE_ALL;
+    RtDrawStamp model{};
+    for (int a = 0; a < 3; a++) model.origin[a] = (float)(lr[a] - R / 2 + lo[a]);
+    model.origin[2] += 1.0f; model.scale = 1.0f; model.emission = 0xFF000000u;
+
+    DeviceRun run(hip, s.ctx);
+    RtDetachResult none{};
+    for (int a = 0; a < 3; a++) { none.lo[a] = INT32_MAX; none.hi[a] = INT32_MIN; }
+    RtDetachResult* d_result = (RtDetachResult*)run.on_device(&none, sizeof none);
+    run.start();
+
+    // ---- the device path -------------------------------------------------------------------------------------------------------
+    const size_t nvox = (size_t)ext[0] * ext[1] * ext[2];
+    std::vector<uint32_t> dev_mats(nvox), host_mats(nvox, 0u);
+    std::vector<uint8_t> dev_state(nvox), host_state(nvox, (uint8_t)RT_STAMP_ABSENT);
+    RtDetachResult result{};
+    double device_ms = 0.0;
+    for (int t = 0; t < COLLAPSE_REPS + 1 && run.fine; t++) {   // (the first warms the scratch and the staging up)
+        uint32_t body = 0;
+        float ms = 0.0f;
+        run.fine = hip.copy(d_result, &none, sizeof none, 1) == 0 && rt_edit_stamps(s.ctx, &back, 1) == RT_OK && rt_draw_frame(s.ctx, &s.u()) == RT_OK &&
+                   run.mark() && rt_detach_voxels_async(s.ctx, &det, d_result, &body) == RT_OK;
+        if (run.fine) {
+            model.stamp = body;
+            run.fine = rt_draw_stamps(s.ctx, &s.u(), &model, faces, 1) == RT_OK && run.lap(&ms);
+        }
+        if (t > 0) device_ms += (double)ms / COLLAPSE_REPS;
+        if (run.fine && t == COLLAPSE_REPS)
+            run.fine = rt_sync(s.ctx) == RT_OK && hip.copy(&result, d_result, sizeof result, 2) == 0 &&
+                       rt_stamp_read(s.ctx, body, dev_mats.data(), dev_state.data()) == RT_OK;
+        if (run.fine) run.fine = rt_stamp_destroy(s.ctx, body) == RT_OK;
+    }
+
+    // ---- the host path, on the box as it was after the carve ---------------------------------------------------------------------
+    std::vector<uint8_t> box_mine(nvox), reached(nvox);
+    std::vector<uint32_t> box_mats(nvox), queue;
+    std::vector<RtVoxelEdit> edits;
+    uint64_t host_detached = 0;
+    double host_ms = 0.0;
+    const size_t sx = 1, sy = (size_t)ext[0], sz = (size_t)ext[0] * ext[1];
+    for (int t = 0; t < COLLAPSE_REPS && run.fine; t++) {
+        run.fine = rt_edit_stamps(s.ctx, &back, 1) == RT_OK && rt_draw_frame(s.ctx, &s.u()) == RT_OK && rt_sync(s.ctx) == RT_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        run.fine = run.fine && rt_read_box(s.ctx, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], box_mats.data(), box_mine.data()) == RT_OK;
+        std::fill(reached.begin(), reached.end(), (uint8_t)0);
+        queue.clear();
+        for (int z = 0; z < ext[2]; z++)                       // the anchors: occupied cells of every face but the top
+            for (int y = 0; y < ext[1]; y++)
+                for (int x = 0; x < ext[0]; x++) {
+                    if (!(x == 0 || x == ext[0] - 1 || y == 0 || y == ext[1] - 1 || z == 0)) continue;
+                    const size_t at = z * sz + y * sy + x * sx;
+                    if (box_mine[at] == 0u) { reached[at] = 1; queue.push_back((uint32_t)at); }
+                }
+        for (size_t head = 0; head < queue.size(); head++) {
+            const size_t at = queue[head];
+            const int x = (int)(at % sy), y = (int)(at / sy % (size_t)ext[1]), z = (int)(at / sz);
+            const size_t next[6] = {at - sx, at + sx, at - sy, at + sy, at - sz, at + sz};
+            const bool inside[6] = {x > 0, x < ext[0] - 1, y > 0, y < ext[1] - 1, z > 0, z < ext[2] - 1};
+            for (int k = 0; k < 6; k++)
+                if (inside[k] && box_mine[next[k]] == 0u && !reached[next[k]]) { reached[next[k]] = 1; queue.push_back((uint32_t)next[k]); }
+        }
+        edits.clear();
+        std::fill(host_mats.begin(), host_mats.end(), 0u);
+        std::fill(host_state.begin(), host_state.end(), (uint8_t)RT_STAMP_ABSENT);
+        for (size_t at = 0; at < nvox; at++) {
+            if (box_mine[at] != 0u || reached[at]) continue;
+            RtVoxelEdit ed{};
+            ed.x = (uint16_t)(lo[0] + (int)(at % sy)); ed.y = (uint16_t)(lo[1] + (int)(at / sy % (size_t)ext[1])); ed.z = (uint16_t)(lo[2] + (int)(at / sz));
+            ed.solid = 0; ed.material = det.air_material;
+            edits.push_back(ed);
+            host_mats[at] = box_mats[at];
+            host_state[at] = (uint8_t)RT_STAMP_SOLID;
+        }
+        host_detached = edits.size();
+        uint32_t body = 0;
+        run.fine = run.fine && rt_edit_voxels(s.ctx, edits.data(), (uint32_t)edits.size()) == RT_OK &&
+                   rt_stamp_create(s.ctx, ext, host_mats.data(), host_state.data(), &body) == RT_OK;
+        if (run.fine) {
+            model.stamp = body;
+            run.fine = rt_draw_stamps(s.ctx, &s.u(), &model, faces, 1) == RT_OK && rt_sync(s.ctx) == RT_OK;
+        }
+        host_ms += ms_since(t0) / COLLAPSE_REPS;
+        if (run.fine) run.fine = rt_stamp_destroy(s.ctx, body) == RT_OK;
+    }
+    if (run.fine) run.fine = rt_stamp_destroy(s.ctx, undo) == RT_OK;
+    if (!run.close()) { std::fprintf(stderr, "collapse failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    // the host path restates the rule: it is a baseline only while it detaches what the library detaches
+    if (host_detached != result.detached || result.unconverged != 0u || dev_state != host_state || dev_mats != host_mats) {
+        std::fprintf(stderr, "collapse: the host path detached %llu voxels, the device %u (unconverged %u); the stamps %s\n", (unsigned long long)host_detached,
+                     result.detached, result.unconverged, dev_state == host_state && dev_mats == host_mats ? "agree" : "differ");
+        return 1;
+    }
+    std::printf("{\"collapse\": %d, \"centre\": [%d, %d, %d], \"box\": [%d, %d, %d], \"slab_z\": [%d, %d], \"frame\": \"%dx%d spp %d depth %d\", "
+                "\"detached\": %u, \"supported\": %u, \"passes\": %u, \"chunks\": %u, \"bounds\": [%d, %d, %d, %d, %d, %d], \"host_detached\": %llu, "
+                "\"detach_device_ms\": %.4f, \"host_path_ms\": %.3f}\n",
+                radius, c[0], c[1], c[2], ext[0], ext[1], ext[2], slab_lo, slab_hi, o.width, o.height, o.spp, o.depth, result.detached, result.supported,
+                result.passes, result.chunks, result.lo[0], result.lo[1], result.lo[2], result.hi[0], result.hi[1], result.hi[2],
+                (unsigned long long)host_detached, device_ms, host_ms);
+    return 0;
+}
+
 // --models N [--model-scale S]: voxel-model entities.  One built-in 9 x 9 x 12 sparse stamp (about a third of its voxels solid; its
 // values are the generator's first) is drawn N times at scale S (default 1/8) — scattered like --boxes' boxes, in seeded
 // orientations, lit by their bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times;

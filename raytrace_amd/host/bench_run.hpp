@@ -31,6 +31,7 @@ struct Options {
     int debris = 0, debris_density = 256;   // --debris RADIUS [--density D]
     int settle = 0;                         // --debris RADIUS --settle T
     long long fall = 0;                     // --debris RADIUS --settle T --fall K (0xFFFFFFFF: until at rest)
+    int collapse = 0;                       // --collapse RADIUS
     bool shadow_models = false, light_shadows = false, occluders_far = false;
     float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
@@ -56,6 +57,7 @@ int run_simulate(const Options& o, const World& w);
 int run_debris(const Options& o, const World& w);
 int run_settle(const Options& o, const World& w);
 int run_fall(const Options& o, const World& w);
+int run_collapse(const Options& o, const World& w);
 int run_models(const Options& o, const World& w);
 int run_lights(const Options& o, const World& w);
 int run_shadows(const Options& o, const World& w);

@@ -666,6 +666,29 @@ class Context:
                 raise ValueError("counts must be a contiguous tensor of 16 bytes (one RtSettleCount)")
         self._check(self._lib.rt_settle_voxels_async(self._h, C.byref(params), _dp(counts_t)))
 
+    # -- voxel detachment ---------------------------------------------------------------------------------
+    def detach_voxels(self, params, result=None):
+        """rt_detach_voxels: the occupied voxels in the box of `params` (an abi.RtVoxelDetach, abi.make_voxel_detach) that nothing joins
+        to an anchor are counted, with RT_DETACH_CARVE carved and with RT_DETACH_CAPTURE written into a new stamp -> (the
+        abi.DETACH_RESULT_DTYPE record `result` added to and merged, a new record; None starts from detach_result(); the stamp's id,
+        None without RT_DETACH_CAPTURE, 0 for an empty clipped box).  Synchronous for the result; a world change is stream-ordered."""
+        res = detach_result(result)
+        out = C.c_uint32(0)
+        self._check(self._lib.rt_detach_voxels(self._h, C.byref(params), _p(res), C.byref(out)))
+        return res[0], (out.value if params.flags & abi.RT_DETACH_CAPTURE else None)
+
+    def detach_voxels_async(self, params, result_t=None):
+        """rt_detach_voxels_async: `result_t` a contiguous torch device tensor of 48 bytes (RtDetachResult, added to and merged) or
+        None.  Enqueued: valid after sync(), or in the order of a stream given to set_stream().  Returns the stamp's id (valid at
+        once), None without RT_DETACH_CAPTURE."""
+        if result_t is not None:
+            _device_tensors(self._device, ("result", result_t))
+            if _nbytes(result_t) != abi.DETACH_RESULT_DTYPE.itemsize:
+                raise ValueError("result must be a contiguous tensor of 48 bytes (one RtDetachResult)")
+        out = C.c_uint32(0)
+        self._check(self._lib.rt_detach_voxels_async(self._h, C.byref(params), _dp(result_t), C.byref(out)))
+        return out.value if params.flags & abi.RT_DETACH_CAPTURE else None
+
     # -- voxel-model entities ----------------------------------------------------------------------------
     def draw_stamps(self, uniforms, models, face_lights):
         """rt_draw_stamps: `models` DRAW_STAMP_DTYPE[N] records (make_draw_stamps) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
@@ -1121,6 +1144,15 @@ class Pipeline:
         self._check(_lib.host().rth_pipeline_enable_entity_shadows(self._h, float(strength)),
                     "enable_entity_shadows: strength must be 0 (off) or lie in (0, 1]")
 
+    def detach_voxels(self, params, result=None):
+        """rt_detach_voxels on the pipeline's context (Context.detach_voxels): what the carve before it left unsupported in the box of
+        `params` is carved and captured.  Returns the stamp's id when `params` captures — ready for set_models —, else the result
+        record; with `result` given (an abi.DETACH_RESULT_DTYPE record) it is added to and merged in place."""
+        res, stamp = self.context.detach_voxels(params, result)
+        if isinstance(result, np.ndarray) and result.dtype == abi.DETACH_RESULT_DTYPE:
+            result.reshape(-1)[0] = res
+        return stamp if params.flags & abi.RT_DETACH_CAPTURE else res
+
     def enable_light_shadows(self, on=True):
         """Pipeline::enable_light_shadows: every draw_frame from now on hands the boxes and models set (set_boxes, set_models) to the
         lights step, which runs rt_add_lights_occluded in rt_add_lights' place: the entities cast shadows in the point lights."""
@@ -1533,6 +1565,21 @@ def settle_counts(counts=None):
     else:
         cnt[0] = tuple(int(v) for v in counts)
     return cnt
+
+
+def detach_result(result=None):
+    """The result of Context.detach_voxels as one abi.DETACH_RESULT_DTYPE record in an array of its own: for None zero counters and
+    empty bounds (lo INT32_MAX, hi INT32_MIN), else a copy of such a record or of an abi.RtDetachResult."""
+    res = np.zeros(1, dtype=abi.DETACH_RESULT_DTYPE)
+    if result is None:
+        res["lo"], res["hi"] = 0x7FFFFFFF, -0x80000000
+    elif isinstance(result, abi.RtDetachResult):
+        res[0] = np.frombuffer(bytes(result), dtype=abi.DETACH_RESULT_DTYPE)[0]
+    elif isinstance(result, (np.ndarray, np.void)) and result.dtype == abi.DETACH_RESULT_DTYPE:
+        res[0] = np.asarray(result).reshape(-1)[0]
+    else:
+        raise ValueError("result is None, an abi.RtDetachResult or an abi.DETACH_RESULT_DTYPE record")
+    return res
 
 
 def deposit_tensor_count(states, draw, counts, device):
