@@ -1178,6 +1178,99 @@ int rt_detach_voxels(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult
  * the context's device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued. */
 int rt_detach_voxels_async(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult* result_dev, uint32_t* stamp_out);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Navigation fields: where a mob goes.  A mob can be drawn, moved
+ * without tunnelling, hit, seen, shadowed and lit; in a world that explosions carve, sand fills and pillars leave, a precomputed
+ * navmesh is wrong after the first edit, and the host answer — rt_read_box round the player (which drains both lanes), a breadth-
+ * first search on the CPU, an upload of the steps — is the host path the last calls removed.  A NAV FIELD holds, for every cell of a
+ * box of texels a walker can stand in, the number of moves to the nearest goal and the move to make next: built on the device once
+ * per change (rt_nav_build), sampled for any number of agents in one launch (rt_nav_sample).  Breadth-first distances are integers
+ * and unique, so results are exact and do not depend on scheduling; tests/nav_field_ref.py states the rules twice.
+ *
+ * Objects (they mirror the stamps').  rt_nav_create — a field of `extent` cells (each 1..256), all a build needs allocated with it:
+ * the field (3 bytes per cell) and the bitmaps and launch record of the search; a build allocates nothing.  Ids are non-zero and
+ * valid until rt_nav_destroy; at most 64 fields are live per context (the 65th: RT_ERR_INVALID_ARG); RT_ERR_OOM when the device has
+ * no room.  RtInfo.device_bytes counts fields; rt_destroy frees the rest.  rt_nav_info — the extent, the `lo` of the build enqueued
+ * last and whether there was one (any out pointer may be NULL).  rt_nav_read — dist and move of the build enqueued last,
+ * [ez][ey][ex] with x fastest (either may be NULL; synchronises; RT_ERR_NOT_READY for a field never built).  rt_nav_destroy —
+ * waits for the builds and samples already enqueued. */
+int rt_nav_create (RtContext* ctx, const int32_t extent[3], uint32_t* id_out);
+int rt_nav_info   (RtContext* ctx, uint32_t id, int32_t extent_out[3], int32_t lo_out[3], uint32_t* built_out);
+int rt_nav_read   (RtContext* ctx, uint32_t id, uint16_t* dist, uint8_t* move);   /* either may be NULL; synchronises */
+int rt_nav_destroy(RtContext* ctx, uint32_t id);
+
+#define RT_NAV_UNREACHED  0xFFFFu   /* dist of a cell that is not standable, or farther than max_dist from every goal */
+#define RT_NAV_NO_MOVE    0xFFu     /* move of a goal cell and of an unreached cell */
+typedef struct RtNavBuild {            /* 32 bytes */
+    int32_t  lo[3];  uint32_t max_dist;                  /*  0  low corner of the box in texels; 1..4096 */
+    uint8_t  height, max_climb, max_drop, goal_snap;     /* 16  1..4, 0..2, 0..8, 0..8 */
+    uint32_t reserved[3];                                /* 20  must be 0 (an up axis other than +z would go here) */
+} RtNavBuild;
+typedef struct RtNavGoal   { int32_t cell[3]; uint32_t reserved; } RtNavGoal;   /* 16 bytes; texel; `reserved` is not read */
+typedef struct RtNavResult {           /* 32 bytes; `reserved` is never written */
+    uint32_t standable, reached, levels, truncated, goals_used, goals_dropped, reserved[2];
+} RtNavResult;
+/* The rules.  Integer arithmetic only: results are exact.  tests/nav_field_ref.py reproduces them bit for bit, twice (an explicit
+ * move graph with a queue, and whole-array dilation); DESIGN.md "Navigation fields" says why they are what they are.
+ *   Box: [lo, lo + E) with E the field's extent; it must lie inside [0, R)^3, as rt_stamp_capture's box must — there is no clipping.
+ *     Cell d of the field is texel lo + d.  Up is +z, the terrain's up axis.  Nothing outside the box is read.  Under the box's low
+ *     z face is a floor: it counts as occupied.  Above its high z face everything counts as unoccupied.  Sideways there are no cells
+ *     outside the box.  A host keeps the box off the window's seam.
+ *   Occupied, clearance, standable: a cell is OCCUPIED iff its minefield byte is 0 at the call's place in stream order.  CLEAR(c)
+ *     is the number of consecutive unoccupied cells c, c+z, c+2z, ... (the cells above the box count as unoccupied).  c is STANDABLE
+ *     iff c-z is occupied and CLEAR(c) >= height.
+ *   Moves: a -> b is a MOVE iff both cells are standable, b.xy - a.xy is one of (+1,0), (-1,0), (0,+1), (0,-1) — h = 0..3 in that
+ *     order —, k = b.z - a.z satisfies -max_drop <= k <= max_climb, and the LOWER of the two cells has CLEAR >= |k| + height: its
+ *     column is free up to head height at the higher level, so no head bumps while stepping up and no ledge is in the way while
+ *     dropping.  Moves are directed: a cliff of 3 with max_drop 3 and max_climb 1 goes down only.  A move's CODE is
+ *     h | (k + 8) << 2.  The ORDER of moves is h ascending and, inside one h, k descending.
+ *   Goals: goal_count <= 4096; 0 is valid: nothing is reached.  The goal cell of a record is the first standable cell among c, c-z,
+ *     ..., c - goal_snap z that lies in the box.  A record without one — any outside the box among them — counts in goals_dropped,
+ *     the others in goals_used; duplicates count each time.
+ *   Field: dist[c] is the least number of moves from c to any goal cell if that number is <= max_dist, else 0xFFFF; it is 0xFFFF
+ *     as well for every cell that is not standable.  move[c] is the code of the first move in ORDER to a cell with dist =
+ *     dist[c] - 1 when 0 < dist[c] < 0xFFFF, else 0xFF.  A build overwrites every cell of the field: nothing of an earlier build
+ *     survives, whatever lo it had.
+ *   Result: standable, reached (cells with dist < 0xFFFF), truncated, goals_used and goals_dropped are ADDED to (wrapping uint32);
+ *     truncated += 1 iff some cell's least number of moves is exactly max_dist + 1; levels is MERGED by maximum with the largest
+ *     dist assigned.  `result` may be NULL.
+ *   Ordering: a query, ordered like rt_stamp_capture: it sees every earlier world change and changes nothing the renderer reads,
+ *     causes no accumulation reset and records no pending box.  A later edit makes the field stale: the host rebuilds.
+ *   Errors: NULL ctx or params, an unknown id, a parameter outside its range above, a non-zero reserved word of RtNavBuild, a box not
+ *     inside the region, NULL goals with goal_count > 0, goal_count > 4096: RT_ERR_INVALID_ARG.  No world resident:
+ *     RT_ERR_NOT_READY.  A rejected call changes nothing.  Tile contexts, every RtKernel and every region size answer as
+ *     rt_stamp_capture does.
+ *   Out of scope: agents wider than one cell; diagonal moves; move costs other than 1; swimming or flying; entities as obstacles;
+ *     boxes across the window's seam; an up axis other than +z; incremental repair after an edit.
+ *   Device work per build: a seed launch (the box's unoccupied bits, the field's fill), a launch that finds and counts the
+ *     standable cells, a launch with a lane per goal, ceil((max_dist + 1) / G) level launches (G = 8 levels each, run in LDS by one
+ *     workgroup per tile of 16 x 16 columns; every workgroup of a launch after the frontier has died returns at once) and a launch
+ *     that gives every reached cell its move code.  No host read sits in between.
+ * rt_nav_build: `goals` and `result` are host memory; the call returns when the result is in host memory. */
+int rt_nav_build(RtContext* ctx, uint32_t id, const RtNavBuild* params, const RtNavGoal* goals, uint32_t goal_count, RtNavResult* result);
+/* Same with device goals and a device result, enqueued: result_dev is valid after rt_sync (or, after rt_set_stream, in the caller's
+ * stream order); `params` is a host pointer.  goals_dev (with goal_count > 0) and a non-NULL result_dev must pass
+ * rt_trace_rays_async's test (16-byte aligned memory of the context's device, or managed memory), else RT_ERR_INVALID_ARG before
+ * anything is enqueued. */
+int rt_nav_build_async(RtContext* ctx, uint32_t id, const RtNavBuild* params, const RtNavGoal* goals_dev, uint32_t goal_count,
+                       RtNavResult* result_dev);
+
+/* Sampling a field: a pure lookup — the world is not read.  `pos` is the agent's foot point: the centre of its box in x and y, its lo
+ * in z (texel coordinates, as the box's lo).  With c0 = floor(pos) per component the candidates are, in this order: c0; c0-z ...
+ * c0 - snap_down z; c0+z ... c0 + snap_up z.  Candidates outside the box are skipped.  The agent's cell is the first candidate with
+ * dist < 0xFFFF: `cell` is its texel, `dist` its distance, `move` its code and `next` the texel the move leads to; with dist 0,
+ * next = cell and move = 0xFF.  With no such candidate: cell = next = c0, dist = 0xFFFFFFFF, move = 0xFF.  With a non-finite
+ * component or one of magnitude >= 2^20, a non-zero reserved byte, snap_down above 8 or snap_up above 2: cell = next = (-1,-1,-1),
+ * dist = 0xFFFFFFFF, move = 0xFF (the asynchronous call cannot refuse a record it has not read — RT_SWEEP_INVALID's precedent — and
+ * the synchronous call answers the same).  Every record is written.  count <= 2^20; 0 enqueues nothing.  The sample is ordered
+ * after the builds enqueued before it and reads the box of the build enqueued last.  Errors: NULL ctx, an unknown id, count above
+ * 2^20, NULL agents or steps with count > 0: RT_ERR_INVALID_ARG; a field never built: RT_ERR_NOT_READY. */
+typedef struct RtNavAgent { float pos[3]; uint8_t snap_down, snap_up, reserved[2]; } RtNavAgent;          /* 16 bytes; 0..8, 0..2 */
+typedef struct RtNavStep  { int32_t cell[3]; uint32_t dist; int32_t next[3]; uint32_t move; } RtNavStep;  /* 32 bytes */
+int rt_nav_sample(RtContext* ctx, uint32_t id, const RtNavAgent* agents, uint32_t count, RtNavStep* steps);
+/* Same on device memory, enqueued: agents_dev and steps_dev must pass rt_trace_rays_async's test; steps_dev is valid after rt_sync
+ * (or, after rt_set_stream, in the caller's stream order). */
+int rt_nav_sample_async(RtContext* ctx, uint32_t id, const RtNavAgent* agents_dev, uint32_t count, RtNavStep* steps_dev);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Point lights: light sources that move — a torch in the player's
  * hand, a glowing projectile, a muzzle flash, the flash of an explosion — added to the two lighting planes of the frame drawn last,
  * after rt_draw_frame (and rt_draw_boxes) and before or after rt_denoise.  Each light reaches a pixel through one hard shadow ray
@@ -1775,7 +1868,10 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        Additive, same minor version: RtVoxelSettle, RtSettleCount, rt_settle_voxels, rt_settle_voxels_async (voxel settling: loose
  *        voxels fall along an axis inside a box of texels on the device).
  *        Additive, same minor version: RtVoxelDetach, RtDetachResult, RT_DETACH_*, rt_detach_voxels, rt_detach_voxels_async (voxel
- *        detachment: the unsupported voxels of a box of texels are found, carved and captured into a stamp on the device). */
+ *        detachment: the unsupported voxels of a box of texels are found, carved and captured into a stamp on the device).
+ *        Additive, same minor version: RtNavBuild, RtNavGoal, RtNavResult, RtNavAgent, RtNavStep, RT_NAV_*, rt_nav_create, rt_nav_info,
+ *        rt_nav_read, rt_nav_destroy, rt_nav_build, rt_nav_build_async, rt_nav_sample, rt_nav_sample_async (navigation fields:
+ *        walking distances to goals and the next move, built and sampled on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

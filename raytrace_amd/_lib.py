@@ -60,6 +60,14 @@ AMD_FUNCTIONS = {
     "rt_settle_voxels_async": (INT, [P, P, P]),
     "rt_detach_voxels": (INT, [P, P, P, P]),
     "rt_detach_voxels_async": (INT, [P, P, P, P]),
+    "rt_nav_create": (INT, [P, I32P, U32P]),
+    "rt_nav_info": (INT, [P, U32, I32P, I32P, U32P]),
+    "rt_nav_read": (INT, [P, U32, P, P]),
+    "rt_nav_destroy": (INT, [P, U32]),
+    "rt_nav_build": (INT, [P, U32, P, P, U32, P]),
+    "rt_nav_build_async": (INT, [P, U32, P, P, U32, P]),
+    "rt_nav_sample": (INT, [P, U32, P, U32, P]),
+    "rt_nav_sample_async": (INT, [P, U32, P, U32, P]),
     "rt_trace_entities": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     "rt_trace_entities_async": (INT, [P, P, U32, I32P, P, U32, P, U32, P, P]),
     "rt_pick_entities": (INT, [P, UNI, P, U32, P, U32, P, U32, P, P]),

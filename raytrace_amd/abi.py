@@ -415,6 +415,89 @@ def make_voxel_detach(lo, hi, flags=RT_DETACH_CARVE | RT_DETACH_CAPTURE, anchor_
     return p
 
 
+RT_NAV_UNREACHED, RT_NAV_NO_MOVE = 0xFFFF, 0xFF   # dist / move of a cell nothing leads from (ABI 1.3, additive: navigation fields)
+
+
+class RtNavBuild(C.Structure):
+    """rt_nav_build's parameters (ABI 1.3, additive: navigation fields): 32 bytes; the reserved words must be 0."""
+    _fields_ = [("lo", C.c_int32 * 3), ("max_dist", C.c_uint32), ("height", C.c_uint8), ("max_climb", C.c_uint8), ("max_drop", C.c_uint8),
+                ("goal_snap", C.c_uint8), ("reserved", C.c_uint32 * 3)]
+
+
+class RtNavGoal(C.Structure):
+    """One goal of rt_nav_build: 16 bytes, a texel."""
+    _fields_ = [("cell", C.c_int32 * 3), ("reserved", C.c_uint32)]
+
+
+class RtNavResult(C.Structure):
+    """rt_nav_build's result: 32 bytes; the counters are added to, `levels` merged by maximum."""
+    _fields_ = [("standable", C.c_uint32), ("reached", C.c_uint32), ("levels", C.c_uint32), ("truncated", C.c_uint32),
+                ("goals_used", C.c_uint32), ("goals_dropped", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RtNavAgent(C.Structure):
+    """rt_nav_sample input: 16 bytes; the foot point, how far to look down (0..8) and up (0..2) for a reached cell."""
+    _fields_ = [("pos", C.c_float * 3), ("snap_down", C.c_uint8), ("snap_up", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class RtNavStep(C.Structure):
+    """rt_nav_sample output: 32 bytes."""
+    _fields_ = [("cell", C.c_int32 * 3), ("dist", C.c_uint32), ("next", C.c_int32 * 3), ("move", C.c_uint32)]
+
+
+assert (C.sizeof(RtNavBuild), C.sizeof(RtNavGoal), C.sizeof(RtNavResult), C.sizeof(RtNavAgent), C.sizeof(RtNavStep)) == (32, 16, 32, 16, 32)
+assert (RtNavBuild.max_dist.offset, RtNavBuild.height.offset, RtNavBuild.max_climb.offset, RtNavBuild.max_drop.offset,
+        RtNavBuild.goal_snap.offset, RtNavBuild.reserved.offset) == (12, 16, 17, 18, 19, 20)
+assert (RtNavResult.levels.offset, RtNavResult.truncated.offset, RtNavResult.goals_used.offset, RtNavResult.goals_dropped.offset,
+        RtNavResult.reserved.offset) == (8, 12, 16, 20, 24)
+assert (RtNavAgent.snap_down.offset, RtNavAgent.snap_up.offset, RtNavAgent.reserved.offset) == (12, 13, 14)
+assert (RtNavStep.dist.offset, RtNavStep.next.offset, RtNavStep.move.offset) == (12, 16, 28)
+NAV_GOAL_DTYPE = np.dtype(RtNavGoal)       # the numpy views of the records
+NAV_RESULT_DTYPE = np.dtype(RtNavResult)
+NAV_AGENT_DTYPE = np.dtype(RtNavAgent)
+NAV_STEP_DTYPE = np.dtype(RtNavStep)
+MAX_NAV_FIELDS, MAX_NAV_EXTENT, MAX_NAV_DIST, MAX_NAV_GOALS, MAX_NAV_AGENTS = 64, 256, 4096, 4096, 1 << 20
+
+
+def make_nav_build(lo, max_dist, height=2, max_climb=1, max_drop=3, goal_snap=0):
+    """An RtNavBuild: the box's low corner `lo` in texels (its extent is the field's), the largest distance written, the walker's
+    height in cells, how far it steps up and drops, and how far below a goal record its goal cell may lie.  Refuses what the call
+    refuses without knowing R or the field: a parameter outside its range.  The box is judged by the call."""
+    if len(lo) != 3:
+        raise ValueError("lo has three components")
+    for name, v, a, b in (("max_dist", max_dist, 1, MAX_NAV_DIST), ("height", height, 1, 4), ("max_climb", max_climb, 0, 2),
+                          ("max_drop", max_drop, 0, 8), ("goal_snap", goal_snap, 0, 8)):
+        if not a <= int(v) <= b:
+            raise ValueError("%s is %d..%d" % (name, a, b))
+    p = RtNavBuild()
+    for k in range(3):
+        p.lo[k] = int(lo[k])
+    p.max_dist, p.height, p.max_climb, p.max_drop, p.goal_snap = int(max_dist), int(height), int(max_climb), int(max_drop), int(goal_snap)
+    return p
+
+
+def make_nav_goals(cells):
+    """NAV_GOAL_DTYPE records from int[N, 3] texels (or ready records)."""
+    if isinstance(cells, np.ndarray) and cells.dtype == NAV_GOAL_DTYPE:
+        return np.ascontiguousarray(cells).reshape(-1)
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1, 3)
+    out = np.zeros(len(cells), dtype=NAV_GOAL_DTYPE)
+    out["cell"] = cells
+    return out
+
+
+def make_nav_agents(pos, snap_down=1, snap_up=1):
+    """NAV_AGENT_DTYPE records from float[N, 3] foot points (or ready records); snap_down / snap_up are scalars or arrays of N."""
+    if isinstance(pos, np.ndarray) and pos.dtype == NAV_AGENT_DTYPE:
+        return np.ascontiguousarray(pos).reshape(-1)
+    pos = np.asarray(pos, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(len(pos), dtype=NAV_AGENT_DTYPE)
+    out["pos"] = pos
+    out["snap_down"] = snap_down
+    out["snap_up"] = snap_up
+    return out
+
+
 class RtDrawStamp(C.Structure):
     """rt_draw_stamps input (ABI 1.3, additive: voxel-model entities): 32 bytes; the reserved fields must be 0."""
     _fields_ = [("origin", C.c_float * 3), ("scale", C.c_float), ("stamp", C.c_uint32), ("orient", C.c_uint8), ("reserved0", C.c_uint8 * 3),

@@ -387,6 +387,8 @@ void rt_destroy(RtContext* ctx) {
         if (e.mats) (void)hipFree(reinterpret_cast<void*>(e.mats));
         if (e.state) (void)hipFree(reinterpret_cast<void*>(e.state));
     }
+    for (NavEntry& e : ctx->navs.slots)      // the navigation fields nobody destroyed
+        if (e.block) (void)hipFree(reinterpret_cast<void*>(e.block));
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (hipStream_t st : ctx->streams) (void)hipStreamDestroy(st);
     delete ctx;

@@ -24,6 +24,7 @@
 #include "edit_shapes.hpp"
 #include "edit_stamps.hpp"
 #include "draw_stamps.hpp"
+#include "nav_check.hpp"
 
 namespace rta __attribute__((visibility("hidden"))) {
 
@@ -208,6 +209,7 @@ struct __attribute__((visibility("hidden"))) RtContext {
     rta::EditBinning edit_binning;        // host binning scratch, kept between calls
     rta::ShapeScratch shape_scratch;      // rt_edit_shapes: the mark per chunk, kept between calls (it shares the edit sets)
     rta::StampStore stamps;               // the live voxel stamps (rt_stamp_*): device arrays of their own, counted in device_bytes
+    rta::NavStore navs;                   // the live navigation fields (rt_nav_*): one device block each, counted in device_bytes
     int32_t* d_heights = nullptr;         // rt_generate_world / rt_generate_slice: column heights of (R/64 + 1)^2 chunks, on first use
 
     // tiling

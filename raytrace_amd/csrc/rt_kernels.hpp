@@ -309,6 +309,42 @@ inline size_t detach_scratch_words(uint32_t nchunks) { return kDetachHeadWords +
 hipError_t launch_detach_voxels(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, uint32_t nchunks, int logr, const DetachArgs& a,
                                 hipStream_t st);
 
+// rt_nav.hip: navigation fields (rt_nav_build, rt_nav_sample).  A build is level-synchronous breadth-first search on bitmaps, backwards
+// from the goals over the predecessor relation: a seed launch (the box's unoccupied bits, the field's fill, the head cleared), a
+// launch that derives and counts the standable cells, a lane per goal, `launches` level launches of `levels` levels each — a
+// workgroup per tile of 16 x 16 columns over the box's whole z extent, with a halo of `levels` columns, runs them in LDS — and a
+// launch that gives every reached cell its move code.  The scratch needs no fill.  Its layout, in words: the head — word j says
+// whether level launch j has a frontier to start from, word kNavTruncWord whether a cell lies at max_dist + 1, words
+// kNavSpareResult.. are a spare RtNavResult —, then five bitmaps of nav_bitmap_words each, rows of bits along x per (y, z) in 16-bit
+// pieces: unoccupied, unreached standable cells (two buffers), frontier (two buffers).  Level launch j reads buffers j & 1 and
+// writes buffers (j + 1) & 1.
+constexpr size_t kNavHeadWords = 4112u, kNavTruncWord = 4100u, kNavSpareResult = 4104u;
+constexpr uint32_t kNavMaxDist = 4096u, kNavMaxGoals = 4096u, kNavMaxAgents = 1u << 20;
+struct NavArgs {
+    uint32_t* scratch;     // nav_scratch_words(ext) words
+    uint16_t* dist;        // [ez][ey][ex]
+    uint8_t* move;         // [ez][ey][ex]
+    uint32_t* result;      // RtNavResult (never nullptr: the scratch's spare where the caller gave none)
+    const int4* goals;     // RtNavGoal[goal_count]
+    int32_t lo[3], ext[3];
+    uint32_t max_dist, goal_count;
+    int32_t height, max_climb, max_drop, goal_snap;
+};
+__host__ __device__ inline uint32_t nav_row_halves(int ex) { return ((((uint32_t)ex + 15u) >> 4) + 1u) & ~1u; }
+__host__ __device__ inline size_t nav_bitmap_words(const int32_t ext[3]) { return (size_t)ext[1] * (size_t)ext[2] * (size_t)(nav_row_halves(ext[0]) / 2u); }
+inline size_t nav_scratch_words(const int32_t ext[3]) { return kNavHeadWords + 5u * nav_bitmap_words(ext); }
+// `levels`: 1, 4 or 8
+hipError_t launch_nav_build(const uint8_t* mine_sw, int logr, const NavArgs& a, uint32_t levels, hipStream_t st);
+struct NavSampleArgs {
+    const uint16_t* dist;
+    const uint8_t* move;
+    const uint4* agents;   // RtNavAgent[count]
+    uint4* steps;          // RtNavStep[count] (two uint4 each)
+    uint32_t count;
+    int32_t lo[3], ext[3];
+};
+hipError_t launch_nav_sample(const NavSampleArgs& a, hipStream_t st);
+
 // rt_boxes.hip: entity boxes composited into a whole frame's row-major planes by depth (rt_draw_boxes).  One launch for the batch;
 // a wave owns an 8x8 pixel tile.
 struct DrawBoxesArgs {

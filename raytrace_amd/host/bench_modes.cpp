@@ -985,6 +985,185 @@ int run_collapse(const Options& o, const World& w) {
     return 0;
 }
 
+// --navigate EXTENT [--agents N]: navigation fields.  A field of EXTENT x EXTENT x 128 cells round the texel at the frame's centre
+// is built towards that texel's column (goal records nine apart with goal_snap 8 cover it) with max_dist 2 EXTENT, and N agents
+// scattered over the box are sampled; build and sample run between events of their own, NAV_REPS times.  Beside it the host path,
+// timed from the call to usable device state: rt_read_box of the box's minefield, the same search and sample in C++, an upload of the
+// steps.  The mode fails unless both give the same dist, move and step bytes.  One JSON line.
+constexpr int NAV_REPS = 10;
+int run_navigate(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const HipEvents hip;
+    if (!hip.ok) { std::fprintf(stderr, "--navigate needs the HIP runtime for its device buffers\n"); return 1; }
+    const int R = RT_ROOT_BLOCK_SIZE, E = o.navigate, EZ = 128;
+    const int32_t centre_px[2] = {o.width / 2, o.height / 2};
+    RtRayHit hit{};
+    int rc = rt_pick_pixels(s.ctx, &s.u(), centre_px, 1, &hit);
+    if (rc != RT_OK) return s.fail("navigate", rc);
+    int c[3] = {R / 2, R / 2, R / 2};
+    if (hit.kind == RT_HIT_SOLID) for (int a = 0; a < 3; a++) c[a] = hit.texel[a];
+    auto clamp = [](int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; };
+    const int32_t ext[3] = {E, E, EZ};
+    RtNavBuild p{};
+    p.lo[0] = clamp(c[0] - E / 2, R - E); p.lo[1] = clamp(c[1] - E / 2, R - E); p.lo[2] = clamp(c[2] - EZ / 2, R - EZ);
+    p.max_dist = 2u * (uint32_t)E; p.height = 2; p.max_climb = 1; p.max_drop = 3; p.goal_snap = 8;
+    std::vector<RtNavGoal> goals;
+    for (int z = 8; z < EZ + 8; z += 9) { RtNavGoal g{}; g.cell[0] = c[0]; g.cell[1] = c[1]; g.cell[2] = p.lo[2] + (z < EZ ? z : EZ - 1); goals.push_back(g); }
+    const uint32_t nagents = (uint32_t)o.agents;
+    std::vector<RtNavAgent> agents(nagents);
+    uint32_t seed = 12345u;
+    auto next = [&seed]() { seed = seed * 1664525u + 1013904223u; return seed >> 8; };
+    for (RtNavAgent& a : agents) {
+        a.pos[0] = (float)p.lo[0] + (float)(next() % (uint32_t)(E * 16)) / 16.0f;
+        a.pos[1] = (float)p.lo[1] + (float)(next() % (uint32_t)(E * 16)) / 16.0f;
+        a.pos[2] = (float)p.lo[2] + (float)(next() % (uint32_t)(EZ * 16)) / 16.0f;
+        a.snap_down = 8; a.snap_up = 2;
+    }
+    uint32_t field = 0;
+    rc = rt_nav_create(s.ctx, ext, &field);
+    if (rc != RT_OK) return s.fail("navigate", rc);
+
+    DeviceRun run(hip, s.ctx);
+    const RtNavResult none{};
+    RtNavResult* d_result = (RtNavResult*)run.on_device(&none, sizeof none);
+    RtNavGoal* d_goals = (RtNavGoal*)run.on_device(goals.data(), goals.size() * sizeof(RtNavGoal));
+    RtNavAgent* d_agents = (RtNavAgent*)run.on_device(agents.data(), (size_t)nagents * sizeof(RtNavAgent));
+    RtNavStep* d_steps = (RtNavStep*)run.on_device(nullptr, (size_t)nagents * sizeof(RtNavStep));
+    RtNavStep* d_host_steps = (RtNavStep*)run.on_device(nullptr, (size_t)nagents * sizeof(RtNavStep));
+    run.start();
+
+    // ---- the device path -------------------------------------------------------------------------------------------------------
+    const size_t ncell = (size_t)E * E * EZ;
+    double build_ms = 0.0, sample_ms = 0.0;
+    for (int t = 0; t < NAV_REPS + 1 && run.fine; t++) {   // (the first warms up)
+        float ms = 0.0f;
+        run.fine = hip.copy(d_result, &none, sizeof none, 1) == 0 && run.mark() &&
+                   rt_nav_build_async(s.ctx, field, &p, d_goals, (uint32_t)goals.size(), d_result) == RT_OK && run.lap(&ms);
+        if (t > 0) build_ms += (double)ms / NAV_REPS;
+        if (run.fine && nagents > 0u) {
+            run.fine = run.mark() && rt_nav_sample_async(s.ctx, field, d_agents, nagents, d_steps) == RT_OK && run.lap(&ms);
+            if (t > 0) sample_ms += (double)ms / NAV_REPS;
+        }
+    }
+    RtNavResult result{};
+    std::vector<uint16_t> dev_dist(ncell), host_dist(ncell);
+    std::vector<uint8_t> dev_move(ncell), host_move(ncell);
+    std::vector<RtNavStep> dev_steps(nagents), host_steps(nagents);
+    if (run.fine)
+        run.fine = rt_sync(s.ctx) == RT_OK && hip.copy(&result, d_result, sizeof result, 2) == 0 && rt_nav_read(s.ctx, field, dev_dist.data(), dev_move.data()) == RT_OK &&
+                   (nagents == 0u || hip.copy(dev_steps.data(), d_steps, (size_t)nagents * sizeof(RtNavStep), 2) == 0);
+
+    // ---- the host path: read the box back, search and sample in C++, send the steps -----------------------------------------------
+    std::vector<uint8_t> mine(ncell), clear(ncell), stand(ncell);
+    std::vector<uint32_t> queue;
+    const int sy = E, sz = E * E, H = p.height;
+    const int dxs[4] = {1, -1, 0, 0}, dys[4] = {0, 0, 1, -1};
+    double host_ms = 0.0;
+    for (int t = 0; t < NAV_REPS && run.fine; t++) {
+        const auto t0 = std::chrono::steady_clock::now();
+        run.fine = rt_read_box(s.ctx, p.lo[0], p.lo[1], p.lo[2], E, E, EZ, nullptr, mine.data()) == RT_OK;
+        for (int z = EZ - 1; z >= 0; z--)
+            for (int i = 0; i < sz; i++) {
+                const size_t at = (size_t)z * sz + i;
+                const int above = z + 1 < EZ ? clear[at + sz] : 255;
+                clear[at] = mine[at] == 0u ? 0 : (uint8_t)(above < 255 ? above + 1 : 255);
+                stand[at] = mine[at] != 0u && (z == 0 || mine[at - sz] == 0u) && clear[at] >= H;
+            }
+        std::fill(host_dist.begin(), host_dist.end(), (uint16_t)0xFFFF);
+        std::fill(host_move.begin(), host_move.end(), (uint8_t)0xFF);
+        queue.clear();
+        for (const RtNavGoal& g : goals) {
+            const int x = g.cell[0] - p.lo[0], y = g.cell[1] - p.lo[1];
+            if (x < 0 || x >= E || y < 0 || y >= E) continue;
+            for (int k = 0; k <= p.goal_snap; k++) {
+                const int z = g.cell[2] - p.lo[2] - k;
+                if (z < 0) break;
+                if (z >= EZ) continue;
+                const size_t at = (size_t)z * sz + (size_t)y * sy + x;
+                if (!stand[at]) continue;
+                if (host_dist[at] != 0) { host_dist[at] = 0; queue.push_back((uint32_t)at); }
+                break;
+            }
+        }
+        // the move a -> b with b = a + (dx, dy, k): both standable and the lower of the two clear for |k| + height cells
+        auto move_ok = [&](size_t a, size_t b, int k) { return stand[a] && stand[b] && clear[k >= 0 ? a : b] >= (k < 0 ? -k : k) + H; };
+        for (size_t head = 0; head < queue.size(); head++) {
+            const size_t b = queue[head];
+            const int bx = (int)(b % (size_t)sy), by = (int)(b / (size_t)sy % (size_t)E), bz = (int)(b / (size_t)sz);
+            if (host_dist[b] >= p.max_dist) continue;
+            for (int h = 0; h < 4; h++) {
+                const int ax = bx - dxs[h], ay = by - dys[h];
+                if (ax < 0 || ax >= E || ay < 0 || ay >= E) continue;
+                for (int k = -(int)p.max_drop; k <= (int)p.max_climb; k++) {
+                    const int az = bz - k;
+                    if (az < 0 || az >= EZ) continue;
+                    const size_t a = (size_t)az * sz + (size_t)ay * sy + ax;
+                    if (host_dist[a] != 0xFFFF || !move_ok(a, b, k)) continue;
+                    host_dist[a] = (uint16_t)(host_dist[b] + 1);
+                    queue.push_back((uint32_t)a);
+                }
+            }
+        }
+        for (const uint32_t a : queue) {
+            const int d = host_dist[a];
+            if (d == 0) continue;
+            const int ax = (int)(a % (size_t)sy), ay = (int)(a / (size_t)sy % (size_t)E), az = (int)(a / (size_t)sz);
+            for (int h = 0; h < 4 && host_move[a] == 0xFF; h++) {
+                const int bx = ax + dxs[h], by = ay + dys[h];
+                if (bx < 0 || bx >= E || by < 0 || by >= E) continue;
+                for (int k = (int)p.max_climb; k >= -(int)p.max_drop; k--) {
+                    const int bz = az + k;
+                    if (bz < 0 || bz >= EZ) continue;
+                    const size_t b = (size_t)bz * sz + (size_t)by * sy + bx;
+                    if (host_dist[b] != d - 1 || !move_ok(a, b, k)) continue;
+                    host_move[a] = (uint8_t)(h | ((k + 8) << 2));
+                    break;
+                }
+            }
+        }
+        for (uint32_t i = 0; i < nagents; i++) {
+            const RtNavAgent& a = agents[i];
+            RtNavStep st{};
+            const int c0[3] = {(int)std::floor(a.pos[0]), (int)std::floor(a.pos[1]), (int)std::floor(a.pos[2])};
+            for (int k = 0; k < 3; k++) st.cell[k] = st.next[k] = c0[k];
+            st.dist = 0xFFFFFFFFu; st.move = 0xFFu;
+            const int x = c0[0] - p.lo[0], y = c0[1] - p.lo[1];
+            for (int j = 0; j <= a.snap_down + a.snap_up && x >= 0 && x < E && y >= 0 && y < E; j++) {
+                const int z = c0[2] - p.lo[2] + (j <= a.snap_down ? -j : j - a.snap_down);
+                if (z < 0 || z >= EZ) continue;
+                const size_t at = (size_t)z * sz + (size_t)y * sy + x;
+                if (host_dist[at] == 0xFFFF) continue;
+                st.dist = host_dist[at];
+                st.cell[2] = st.next[2] = z + p.lo[2];
+                if (st.dist > 0u) {
+                    st.move = host_move[at];
+                    st.next[0] += dxs[st.move & 3u]; st.next[1] += dys[st.move & 3u]; st.next[2] += (int)(st.move >> 2) - 8;
+                }
+                break;
+            }
+            host_steps[i] = st;
+        }
+        run.fine = run.fine && (nagents == 0u || hip.copy(d_host_steps, host_steps.data(), (size_t)nagents * sizeof(RtNavStep), 1) == 0);
+        host_ms += ms_since(t0) / NAV_REPS;
+    }
+    if (run.fine) run.fine = rt_nav_destroy(s.ctx, field) == RT_OK;
+    if (!run.close()) { std::fprintf(stderr, "navigate failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    // the host path restates the rules: it is a baseline only while it gives what the library gives
+    const bool same_steps = nagents == 0u || std::memcmp(dev_steps.data(), host_steps.data(), (size_t)nagents * sizeof(RtNavStep)) == 0;
+    if (dev_dist != host_dist || dev_move != host_move || !same_steps) {
+        std::fprintf(stderr, "navigate: dist %s, move %s, steps %s\n", dev_dist == host_dist ? "agree" : "differ", dev_move == host_move ? "agree" : "differ",
+                     same_steps ? "agree" : "differ");
+        return 1;
+    }
+    std::printf("{\"navigate\": %d, \"agents\": %u, \"centre\": [%d, %d, %d], \"lo\": [%d, %d, %d], \"max_dist\": %u, \"standable\": %u, \"reached\": %u, "
+                "\"levels\": %u, \"truncated\": %u, \"goals_used\": %u, \"build_device_ms\": %.4f, \"sample_device_ms\": %.4f, \"host_path_ms\": %.3f, "
+                "\"equal_bytes\": true}\n",
+                E, nagents, c[0], c[1], c[2], p.lo[0], p.lo[1], p.lo[2], p.max_dist, result.standable, result.reached, result.levels, result.truncated,
+                result.goals_used, build_ms, sample_ms, host_ms);
+    return 0;
+}
+
 // --models N [--model-scale S]: voxel-model entities.  One built-in 9 x 9 x 12 sparse stamp (about a third of its voxels solid; its
 // values are the generator's first) is drawn N times at scale S (default 1/8) — scattered like --boxes' boxes, in seeded
 // orientations, lit by their bounding boxes' face probes — by rt_draw_stamps into a freshly drawn --width x --height frame, 20 times;

@@ -32,6 +32,8 @@ struct Options {
     int settle = 0;                         // --debris RADIUS --settle T
     long long fall = 0;                     // --debris RADIUS --settle T --fall K (0xFFFFFFFF: until at rest)
     int collapse = 0;                       // --collapse RADIUS
+    int navigate = 0;                       // --navigate EXTENT
+    long long agents = 0;                   // --navigate EXTENT --agents N
     bool shadow_models = false, light_shadows = false, occluders_far = false;
     float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
@@ -58,6 +60,7 @@ int run_debris(const Options& o, const World& w);
 int run_settle(const Options& o, const World& w);
 int run_fall(const Options& o, const World& w);
 int run_collapse(const Options& o, const World& w);
+int run_navigate(const Options& o, const World& w);
 int run_models(const Options& o, const World& w);
 int run_lights(const Options& o, const World& w);
 int run_shadows(const Options& o, const World& w);

@@ -689,6 +689,70 @@ class Context:
         self._check(self._lib.rt_detach_voxels_async(self._h, C.byref(params), _dp(result_t), C.byref(out)))
         return out.value if params.flags & abi.RT_DETACH_CAPTURE else None
 
+    # -- navigation fields -------------------------------------------------------------------------------
+    def nav_create(self, extent):
+        """rt_nav_create: a navigation field of `extent` (ex, ey, ez) cells, each 1..256; returns its id."""
+        out = C.c_uint32(0)
+        self._check(self._lib.rt_nav_create(self._h, _lr3(extent), C.byref(out)))
+        return out.value
+
+    def nav_info(self, field):
+        """rt_nav_info: (extent (ex, ey, ez), lo of the build enqueued last, whether there was one)."""
+        ext, lo, built = (C.c_int32 * 3)(), (C.c_int32 * 3)(), C.c_uint32(0)
+        self._check(self._lib.rt_nav_info(self._h, int(field), ext, lo, C.byref(built)))
+        return tuple(ext), tuple(lo), bool(built.value)
+
+    def nav_read(self, field):
+        """rt_nav_read: (dist u16[ez, ey, ex], move u8[ez, ey, ex]) of the build enqueued last.  Synchronises."""
+        ex, ey, ez = self.nav_info(field)[0]
+        dist = np.empty((ez, ey, ex), dtype=np.uint16)
+        move = np.empty((ez, ey, ex), dtype=np.uint8)
+        self._check(self._lib.rt_nav_read(self._h, int(field), _p(dist), _p(move)))
+        return dist, move
+
+    def nav_destroy(self, field):
+        """rt_nav_destroy: the id is invalid afterwards; waits for the builds and samples already enqueued."""
+        self._check(self._lib.rt_nav_destroy(self._h, int(field)))
+
+    def nav_build(self, field, params, goals, result=None):
+        """rt_nav_build: walking distances to `goals` (int[N, 3] texels or abi.NAV_GOAL_DTYPE records) over the box of `params` (an
+        abi.RtNavBuild, abi.make_nav_build) into `field` -> the abi.NAV_RESULT_DTYPE record `result` added to and merged, a new
+        record; None starts from zeros.  Synchronous for the result."""
+        goals = abi.make_nav_goals(goals)
+        res = np.zeros(1, dtype=abi.NAV_RESULT_DTYPE)
+        if result is not None:
+            res[0] = np.asarray(result, dtype=abi.NAV_RESULT_DTYPE).reshape(-1)[0]
+        self._check(self._lib.rt_nav_build(self._h, int(field), C.byref(params), _ptr_or_none(goals), goals.size, _p(res)))
+        return res[0]
+
+    def nav_build_async(self, field, params, goals_t, result_t=None):
+        """rt_nav_build_async: `goals_t` a contiguous torch device tensor of N * 16 bytes (RtNavGoal rows) or None for no goal,
+        `result_t` one of 32 bytes (RtNavResult, added to and merged) or None.  Enqueued: valid after sync(), or in the order of a
+        stream given to set_stream()."""
+        named = [(n, t) for n, t in (("goals", goals_t), ("result", result_t)) if t is not None]
+        _device_tensors(self._device, *named)
+        n = 0 if goals_t is None else record_count("goals", _nbytes(goals_t), abi.NAV_GOAL_DTYPE.itemsize, abi.MAX_NAV_GOALS, "RtNavGoal")
+        if result_t is not None and _nbytes(result_t) != abi.NAV_RESULT_DTYPE.itemsize:
+            raise ValueError("result must be a contiguous tensor of 32 bytes (one RtNavResult)")
+        self._check(self._lib.rt_nav_build_async(self._h, int(field), C.byref(params), _dp(goals_t) if n else None, n, _dp(result_t)))
+
+    def nav_sample(self, field, agents, snap_down=1, snap_up=1):
+        """rt_nav_sample: `agents` float[N, 3] foot points (with the two snap ranges) or abi.NAV_AGENT_DTYPE records -> numpy array
+        of abi.NAV_STEP_DTYPE (RtNavStep) per agent.  Synchronous."""
+        recs = abi.make_nav_agents(agents, snap_down, snap_up)
+        steps = np.zeros(recs.size, dtype=abi.NAV_STEP_DTYPE)
+        self._check(self._lib.rt_nav_sample(self._h, int(field), _ptr_or_none(recs), recs.size, _ptr_or_none(steps)))
+        return steps
+
+    def nav_sample_async(self, field, agents_t, steps_t):
+        """rt_nav_sample_async on torch device tensors: `agents_t` any contiguous tensor of N * 16 bytes (RtNavAgent rows), `steps_t`
+        any contiguous tensor of N * 32 bytes.  Enqueued: valid after sync(), or in the order of a stream given to set_stream().  A
+        record that cannot be read as an agent gets cell (-1, -1, -1)."""
+        _device_tensors(self._device, ("agents", agents_t), ("steps", steps_t))
+        n = record_count("agents", _nbytes(agents_t), abi.NAV_AGENT_DTYPE.itemsize, abi.MAX_NAV_AGENTS, "RtNavAgent")
+        _holds("steps", steps_t, n, abi.NAV_STEP_DTYPE.itemsize)
+        self._check(self._lib.rt_nav_sample_async(self._h, int(field), _dp(agents_t), n, _dp(steps_t)))
+
     # -- voxel-model entities ----------------------------------------------------------------------------
     def draw_stamps(self, uniforms, models, face_lights):
         """rt_draw_stamps: `models` DRAW_STAMP_DTYPE[N] records (make_draw_stamps) and `face_lights` PROBE_LIGHT_DTYPE[6 N] records (what
