@@ -1178,6 +1178,86 @@ int rt_detach_voxels(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult
  * the context's device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued. */
 int rt_detach_voxels_async(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult* result_dev, uint32_t* stamp_out);
 
+/* (ABI 1.3, additive; hosts detect the feature by these symbols) Fluid flow: a level-based fluid spreads, falls and dries up, on the
+ * device — the water behind a dam rt_edit_shapes broke, a spring on a ledge, lava down a slope.  Without this call the fluid hangs
+ * where it was placed; a host that wants it to run reads the box back with rt_read_box (which drains both lanes), runs a cellular
+ * automaton on the CPU and sends thousands of RtVoxelEdit records, every tick while anything still moves.  Each call advances the
+ * fluid by `ticks` synchronous steps inside a box of texels: rt_edit_shapes (carve the dam) -> rt_flow_voxels_async runs without a
+ * host read.  It is the familiar game rule: sources never run out, fluid falls, spreads sideways only where it stands on something,
+ * loses one level per sideways cell and dries when nothing feeds it.  The parameters of one call, 64 bytes: */
+typedef struct RtVoxelFlow {             /* 64 bytes */
+    int32_t  lo[3];  uint32_t ticks;          /*  0  box of texels, inclusive, as RT_SHAPE_BOX's a; 1..256 */
+    int32_t  hi[3];  uint32_t air_material;   /* 16  as RT_SHAPE_BOX's b; word left in a cell that was fluid and ends the call unoccupied */
+    uint32_t fluid_mask, fluid_value;         /* 32  an occupied voxel is FLUID iff (material & fluid_mask) == fluid_value */
+    uint32_t fluid_word, reserved0;           /* 40  word a newly wetted cell gets (level field 0; the call writes it); must be 0 */
+    uint8_t  level_shift, max_level, reserved1[2];  /* 48  0..28; 1..13 */
+    uint32_t reserved2[3];                    /* 52  must be 0 (an up axis other than +z would go here) */
+} RtVoxelFlow;
+/* What a call did, 32 bytes, in host memory for rt_flow_voxels and in device memory for rt_flow_voxels_async: */
+typedef struct RtFlowCount { uint32_t wetted, dried, changed, active, chunks, reserved[3]; } RtFlowCount;  /* 32 bytes, ADDED to, wrapping; reserved never written */
+/* The rules.  Integer arithmetic only, and every cell's next state is a function of the previous state of its neighbourhood: results
+ * are exact, do not depend on scheduling and are equal from run to run.  They are reproduced bit for bit by tests/flow_voxels_ref.py,
+ * which states them twice (a loop per cell over explicit neighbours, and whole-array shifts), changes the world only through
+ * tests/voxel_edits.py and clips the box through tests/shape_edits.py (DESIGN.md "Fluid flow").
+ *   Box: lo / hi mean what rt_settle_voxels' mean — texels, inclusive — with the same validity (|lo_k|, |hi_k| <= 4 R, lo_k <= hi_k)
+ *     and the same clipping to [0, R)^3, giving lo' / hi'.  Every extent hi'_k - lo'_k + 1 of the clipped box must be at most 256:
+ *     the bound of the per-texel scratch, and rt_detach_voxels' limit too.  Up is +z.  Nothing outside the clipped box is read, and
+ *     nothing outside it is written apart from the minefield bytes of dirty chunks.  Under the low z face is a floor, which counts
+ *     as FIXED.  Above the high z face and sideways there are no cells: nothing feeds in from there and nothing leaves.  A host
+ *     keeps the box off the window's seam.
+ *   Field: FIELD = 0xF << level_shift.  For a fluid cell v = (material >> level_shift) & 0xF: v == 15 is a SOURCE, otherwise the
+ *     cell is FLOWING with strength min(v, max_level) — strength 0 is possible, and so are raw values above max_level, 14 included.
+ *   Cell kinds, taken at the call's place in stream order: OCCUPIED iff the minefield byte is 0; FLUID iff occupied and (material &
+ *     fluid_mask) == fluid_value; FIXED iff occupied and not fluid; EMPTY otherwise.  Other fluids are FIXED to this call.
+ *   Giving strength: e(n) = max_level + 1 for a source, the strength for a flowing cell, 0 for anything else.
+ *   Spreading: a fluid cell n is SPREADING iff it is a source, or the cell n - z is FIXED (the floor included).
+ *   One tick, all reads from the state before the tick: FIXED and SOURCE cells keep their state.  Every other cell c gets s' =
+ *     max(D, S): D = max_level if c + z is in the box and is a source or a flowing cell of strength >= 1, else 0; S = the maximum of
+ *     e(n) - 1 over the four horizontal neighbours n in the box that are SPREADING and have e(n) >= 1, or 0 with no such neighbour.
+ *     s' >= 1: c is flowing with strength s'.  s' = 0: c is empty.  (A flowing cell of strength 0 gives nothing and holds nothing
+ *     up: to the tick it is an empty cell.)
+ *   After `ticks` ticks, compared with the state before the call: a cell that is flowing at the end is occupied and its word is (w &
+ *     ~FIELD) | s << level_shift, where w is its own word if it was fluid at the start, else fluid_word.  A cell that was fluid at
+ *     the start and is empty at the end is unoccupied and holds air_material.  Every other cell keeps its byte and its word — a
+ *     cell that was wetted and dried again inside the call included.  So T calls of one tick and one call of T ticks agree on every
+ *     occupied cell and on the whole minefield, while the single ticks leave air_material in the unoccupied cells that were wet on
+ *     the way (rt_settle_voxels' precedent).  One corner: a fluid cell that dries and is wetted again on the way keeps the bits of
+ *     its own word outside FIELD in the one call and has fluid_word's after the single ticks; its level agrees.
+ *   Dirty chunks: a 64^3 chunk is DIRTY iff it holds a cell whose occupancy changed.  Dirty chunks have their whole minefield rebuilt
+ *     by rt_edit_voxels' rule — the result equals rt_edit_voxels with one record per such cell — and no other chunk's minefield byte
+ *     changes.  A cell whose level alone changed gets its word written and dirties nothing.  The coarse / brick nibble-map words
+ *     over the clipped box's chunks are rebuilt: rt_selftest(RT_SELFTEST_SCENE_MAPS) counts 0 afterwards.
+ *   Counts: the RtFlowCount fields are ADDED to (wrapping uint32); `counts` may be NULL; reserved is never written.  wetted: cells
+ *     unoccupied at the start and fluid at the end.  dried: fluid at the start, unoccupied at the end.  changed: cells of the box
+ *     whose occupancy or material word differs from before the call — wetted, dried and those whose level alone changed; the bytes
+ *     the rebuild of a dirty chunk gives its other unoccupied cells are not counted.  chunks: dirty chunks.  active: cells whose
+ *     state (empty, strength, source, fixed) would change in one more tick — the host stops ticking when active is 0.
+ *   Ordering and side effects are exactly rt_settle_voxels': a world change with rt_edit_shapes' stream order, lane join, fence and
+ *     staging, also under rt_set_stream; one pending box, the clipped box, whenever it is non-empty — whether or not anything
+ *     changed, because the host cannot know: the accumulation restarts, or with RtConfig.edit_radius the box waits for the next frame.
+ *   Errors: NULL ctx or params, a bad box, a clipped extent above 256, ticks outside 1..256, level_shift above 28, max_level outside
+ *     1..13, fluid_mask == 0, fluid_mask & FIELD != 0, fluid_value & ~fluid_mask != 0, fluid_word & FIELD != 0, (fluid_word &
+ *     fluid_mask) != fluid_value, a reserved byte or word != 0: RT_ERR_INVALID_ARG.  No world resident: RT_ERR_NOT_READY.  An empty
+ *     clipped box: RT_OK, nothing enqueued or reset.  A rejected call changes nothing.  Tile contexts, every RtKernel and every
+ *     region size answer as rt_edit_shapes does.
+ *   Out of scope: volume conservation and pressure; two fluids meeting; an up axis other than +z; boxes across the window's seam;
+ *     history bounds found on the device.  Queries and sweeps go on treating fluid cells as occupied voxels (a passable mask for
+ *     rt_sweep_boxes and the navigation fields — swimming — is the follow-up), and the renderer shows a fluid by its albedo, opaque.
+ *   Device work per call: the box's chunk ids through an edit staging set, a seed launch (a lane per cell: its state — empty, a
+ *     strength, source or fixed — into a byte of a scratch the context keeps: two state arrays of the clipped box, at most 2 x 256^3
+ *     bytes), ceil(ticks / G) tick launches that ping-pong the arrays (a workgroup per tile of 32 x 16 x 16 cells runs G ticks in LDS
+ *     on the tile and a halo of G cells; G = 4, RT_FLOW_TICKS = 1, 2, 4 or 8 for A/B timing; the workgroups of launches after one
+ *     that changed nothing return at once), an apply launch (a lane per cell writes what differs and counts), the chunk rebuild (a
+ *     chunk without a cell whose occupancy changed returns at once) and rt_edit_voxels' nibble-map rebuild.  No host read sits in
+ *     between.
+ * With non-NULL `counts` (host memory) the call returns when the counts are in host memory; the world change itself stays
+ * stream-ordered. */
+int rt_flow_voxels(RtContext* ctx, const RtVoxelFlow* params, RtFlowCount* counts);
+/* Same with device counts, enqueued: counts_dev is valid after rt_sync (or, after rt_set_stream, in the caller's stream order);
+ * `params` is a host pointer, free again when the call returns.  A non-NULL counts_dev must pass rt_trace_rays_async's test (16-byte
+ * aligned memory of the context's device, or managed memory), else RT_ERR_INVALID_ARG before anything is enqueued. */
+int rt_flow_voxels_async(RtContext* ctx, const RtVoxelFlow* params, RtFlowCount* counts_dev);
+
 /* (ABI 1.3, additive; hosts detect the feature by these symbols) Navigation fields: where a mob goes.  A mob can be drawn, moved
  * without tunnelling, hit, seen, shadowed and lit; in a world that explosions carve, sand fills and pillars leave, a precomputed
  * navmesh is wrong after the first edit, and the host answer — rt_read_box round the player (which drains both lanes), a breadth-
@@ -1871,7 +1951,9 @@ int rt_get_gather_timing(RtContext* ctx, float* ms_sum, uint32_t* calls);
  *        detachment: the unsupported voxels of a box of texels are found, carved and captured into a stamp on the device).
  *        Additive, same minor version: RtNavBuild, RtNavGoal, RtNavResult, RtNavAgent, RtNavStep, RT_NAV_*, rt_nav_create, rt_nav_info,
  *        rt_nav_read, rt_nav_destroy, rt_nav_build, rt_nav_build_async, rt_nav_sample, rt_nav_sample_async (navigation fields:
- *        walking distances to goals and the next move, built and sampled on the device). */
+ *        walking distances to goals and the next move, built and sampled on the device).
+ *        Additive, same minor version: RtVoxelFlow, RtFlowCount, rt_flow_voxels, rt_flow_voxels_async (fluid flow: a level-based
+ *        fluid spreads, falls and dries inside a box of texels on the device). */
 #define RT_ABI_VERSION_MAJOR 1
 #define RT_ABI_VERSION_MINOR 3
 uint32_t rt_abi_version(void);

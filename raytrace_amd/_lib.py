@@ -60,6 +60,8 @@ AMD_FUNCTIONS = {
     "rt_settle_voxels_async": (INT, [P, P, P]),
     "rt_detach_voxels": (INT, [P, P, P, P]),
     "rt_detach_voxels_async": (INT, [P, P, P, P]),
+    "rt_flow_voxels": (INT, [P, P, P]),
+    "rt_flow_voxels_async": (INT, [P, P, P]),
     "rt_nav_create": (INT, [P, I32P, U32P]),
     "rt_nav_info": (INT, [P, U32, I32P, I32P, U32P]),
     "rt_nav_read": (INT, [P, U32, P, P]),

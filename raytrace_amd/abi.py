@@ -415,6 +415,56 @@ def make_voxel_detach(lo, hi, flags=RT_DETACH_CARVE | RT_DETACH_CAPTURE, anchor_
     return p
 
 
+class RtVoxelFlow(C.Structure):
+    """rt_flow_voxels' parameters (ABI 1.3, additive: fluid flow): 64 bytes; the reserved bytes and words must be 0."""
+    _fields_ = [("lo", C.c_int32 * 3), ("ticks", C.c_uint32), ("hi", C.c_int32 * 3), ("air_material", C.c_uint32), ("fluid_mask", C.c_uint32),
+                ("fluid_value", C.c_uint32), ("fluid_word", C.c_uint32), ("reserved0", C.c_uint32), ("level_shift", C.c_uint8), ("max_level", C.c_uint8),
+                ("reserved1", C.c_uint8 * 2), ("reserved2", C.c_uint32 * 3)]
+
+
+class RtFlowCount(C.Structure):
+    """rt_flow_voxels' counters: 32 bytes, added to by every call; reserved is never written."""
+    _fields_ = [("wetted", C.c_uint32), ("dried", C.c_uint32), ("changed", C.c_uint32), ("active", C.c_uint32), ("chunks", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+assert C.sizeof(RtVoxelFlow) == 64 and C.sizeof(RtFlowCount) == 32
+assert (RtVoxelFlow.ticks.offset, RtVoxelFlow.hi.offset, RtVoxelFlow.air_material.offset, RtVoxelFlow.fluid_mask.offset, RtVoxelFlow.fluid_value.offset,
+        RtVoxelFlow.fluid_word.offset, RtVoxelFlow.reserved0.offset, RtVoxelFlow.level_shift.offset, RtVoxelFlow.max_level.offset,
+        RtVoxelFlow.reserved1.offset, RtVoxelFlow.reserved2.offset) == (12, 16, 28, 32, 36, 40, 44, 48, 49, 50, 52)
+FLOW_DTYPE = np.dtype(RtVoxelFlow)                 # the numpy view of the parameters
+FLOW_COUNT_DTYPE = np.dtype(RtFlowCount)           # ... and of the counters
+FLOW_MAX_TICKS, FLOW_MAX_LEVEL, FLOW_MAX_SHIFT, FLOW_SOURCE = 256, 13, 28, 15   # ticks per call; max_level; level_shift; the level value of a source
+
+
+def make_voxel_flow(lo, hi, fluid_mask, fluid_value, fluid_word=None, ticks=1, air_material=0, level_shift=0, max_level=7):
+    """An RtVoxelFlow: the box `lo`..`hi` of texels (inclusive, as a box shape's a and b), the mask test that makes an occupied voxel
+    this fluid, the word a newly wetted cell gets (None: fluid_value), the ticks of the call, the word left in dried cells, where the
+    4-bit level field sits in a word and the strength next to a source.  Refuses what the calls refuse without knowing R: a box with
+    lo > hi, ticks outside 1..256, level_shift above 28, max_level outside 1..13, a zero mask, a mask or word that meets the level
+    field, a value outside the mask, a word that fails the test.  The box's range and extent are judged by the call (it needs R)."""
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("lo and hi have three components")
+    p = RtVoxelFlow()
+    for k in range(3):
+        p.lo[k], p.hi[k] = int(lo[k]), int(hi[k])
+        if p.lo[k] > p.hi[k]:
+            raise ValueError("the box needs lo <= hi on every axis")
+    fluid_word = fluid_value if fluid_word is None else fluid_word
+    if not 1 <= int(ticks) <= FLOW_MAX_TICKS:
+        raise ValueError("ticks is 1..256")
+    if not 0 <= int(level_shift) <= FLOW_MAX_SHIFT or not 1 <= int(max_level) <= FLOW_MAX_LEVEL:
+        raise ValueError("level_shift is 0..28 and max_level 1..13")
+    field = 0xF << int(level_shift)
+    if int(fluid_mask) == 0 or int(fluid_mask) & field or int(fluid_word) & field:
+        raise ValueError("fluid_mask is not 0, and neither it nor fluid_word meets the level field")
+    if int(fluid_value) & ~int(fluid_mask) or int(fluid_word) & int(fluid_mask) != int(fluid_value):
+        raise ValueError("fluid_value lies inside fluid_mask and fluid_word passes the fluid test")
+    p.ticks, p.air_material, p.fluid_mask, p.fluid_value, p.fluid_word = int(ticks), int(air_material), int(fluid_mask), int(fluid_value), int(fluid_word)
+    p.level_shift, p.max_level = int(level_shift), int(max_level)
+    return p
+
+
 RT_NAV_UNREACHED, RT_NAV_NO_MOVE = 0xFFFF, 0xFF   # dist / move of a cell nothing leads from (ABI 1.3, additive: navigation fields)
 
 

@@ -34,7 +34,7 @@ AMD_SRCS = [os.path.join(CSRC, "rt_kernels.hip"), os.path.join(CSRC, "rt_world.h
             os.path.join(CSRC, "rt_shadows.hip"), os.path.join(CSRC, "rt_entity_query.hip"), os.path.join(CSRC, "rt_particles.hip"),
             os.path.join(CSRC, "rt_step_particles.hip"), os.path.join(CSRC, "rt_sweep_entities.hip"), os.path.join(CSRC, "rt_emit.hip"),
             os.path.join(CSRC, "rt_deposit.hip"), os.path.join(CSRC, "rt_settle.hip"), os.path.join(CSRC, "rt_detach.hip"),
-            os.path.join(CSRC, "rt_nav.hip"),
+            os.path.join(CSRC, "rt_nav.hip"), os.path.join(CSRC, "rt_flow.hip"),
             ] + [os.path.join(API, f) for f in ("api_context.hip", "api_frame.hip", "api_world.hip", "api_query.hip", "api_post.hip",
                                                  "api_gather.hip", "api_passes.hip", "api_nav.hip")]
 AMD_DEPS = AMD_SRCS + sorted(os.path.join(d, f) for d in (CSRC, API) for f in os.listdir(d) if f.endswith(".hpp")) + [

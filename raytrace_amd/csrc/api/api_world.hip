@@ -1,12 +1,13 @@
 // api_world.hip — the kinds of world change and their staging: whole-region upload, streamed slabs, sparse voxel edits, shape
-// edits, voxel stamps (their store, capture and placement), particle deposits, voxel settling, voxel detachment and terrain generated on the device; rt_read_box reads
+// edits, voxel stamps (their store, capture and placement), particle deposits, voxel settling, voxel detachment, fluid flow and terrain generated on the device; rt_read_box reads
 // the resident region back.  The ordering protocols stand here once each: world_change_begin / world_change_end round every change,
 // world_send / world_applied for the changes that come through a staging set (rt_context.hpp's staging_claim and staging_send, plus
 // the world change), and chunk_edit with its history rule (edit_history) for the four calls that rewrite whole chunks from a staged
-// list of chunk ids: rt_edit_voxels, rt_edit_shapes, rt_edit_stamps, the deposits, the settling and a carving detachment hand it only
-// what differs between them.
+// list of chunk ids: rt_edit_voxels, rt_edit_shapes, rt_edit_stamps, the deposits, the settling, a carving detachment and the fluid
+// flow hand it only what differs between them.
 #include "deposit_check.hpp"
 #include "detach_check.hpp"
+#include "flow_check.hpp"
 #include "rt_context.hpp"
 #include "settle_check.hpp"
 
@@ -257,6 +258,52 @@ int settle_run(RtContext* c, const RtVoxelSettle& p, const SettlePlan& plan, voi
             return RT_OK;
         },
         &c->ev_deposit);
+}
+
+// ---- fluid flow (rt_flow_voxels[_async]): a world change whose cells only the device knows ------------------------------------------
+static_assert(sizeof(RtVoxelFlow) == 64 && sizeof(RtFlowCount) == 32, "the layout the header states");
+static_assert(kFlowMaxTicks == rtd::kFlowMaxTicks && kFlowMaxLevel == rtd::kFlowMaxLevel && kFlowMaxExtent == rtd::kFlowMaxExtent &&
+                  kFlowHeadWords == rtd::kFlowHeadWords,
+              "the host's limits and layout are the kernels'");
+
+// checks shared by the two calls, and the plan; RT_OK when there is work to enqueue, 1 for a call that enqueues nothing
+int flow_check(RtContext* c, const char* fn, const RtVoxelFlow* p, FlowPlan* plan) {
+    const char* e = flow_args_error(p);
+    if (!e) e = flow_params_error(*p, c->logr);
+    if (e) return fail(c, RT_ERR_INVALID_ARG, std::string(fn) + ": " + e + "; nothing was applied");
+    if (!c->world_resident) return fail(c, RT_ERR_NOT_READY, std::string(fn) + ": upload the full region first");
+    *plan = flow_plan(*p, c->logr);
+    return plan->empty ? 1 : RT_OK;
+}
+
+// A chunk edit (the clipped box's chunk ids; one pending box, the clipped box) whose apply step runs the seed, tick, apply and chunk
+// launches.  The scratch is a block of its own, handled as the deposits' is.  counts_dev is a device address the stream may use.
+int flow_run(RtContext* c, const RtVoxelFlow& p, const FlowPlan& plan, void* counts_dev) {
+    if (!c->flow_planned) {   // RT_FLOW_TICKS: 1, 2, 4 or 8 ticks per launch (A/B timing)
+        uint32_t g = 0;
+        if (env_int("RT_FLOW_TICKS", 1, 8, &g) && (g & (g - 1u)) == 0u) c->flow_group = g;
+        c->flow_planned = true;
+    }
+    const int rc = flow_scratch_reserve(c, flow_scratch_need(plan));
+    if (rc != RT_OK) return rc;
+    rtd::FlowArgs a;
+    a.scratch = c->flow_scratch;
+    a.counts = counts_dev ? reinterpret_cast<uint32_t*>(counts_dev) : c->flow_scratch + rtd::kFlowSpareCount;
+    for (int k = 0; k < 3; k++) { a.lo[k] = plan.box.lo[k]; a.hi[k] = plan.box.hi[k]; }
+    a.ticks = p.ticks; a.air_material = p.air_material; a.fluid_mask = p.fluid_mask; a.fluid_value = p.fluid_value; a.fluid_word = p.fluid_word;
+    a.level_shift = p.level_shift; a.max_level = p.max_level;
+    return chunk_edit(
+        c, plan.need, staging_alloc(plan.need), plan.nchunks, 1u,
+        [&](uint8_t* host) { deposit_fill_chunks(plan, c->logr, reinterpret_cast<uint32_t*>(host)); return plan.need; },
+        [&](EditBox* boxes) { *boxes = plan.box; return 1u; },
+        [&](const uint8_t* dev) -> int {
+            RT_HIP(c, c->ev_flow.wait_elsewhere(c->stream));   // the scratch is the previous call's until its chunk pass has run
+            LaunchTimer lt(c, 1);
+            RT_HIP(c, rtd::launch_flow_voxels(c->d_mine_sw, c->d_mat_sw, reinterpret_cast<const uint32_t*>(dev), plan.nchunks, c->logr, a, c->flow_group,
+                                              c->stream));
+            return RT_OK;
+        },
+        &c->ev_flow);
 }
 
 // ---- voxel detachment (rt_detach_voxels[_async]): a world change (RT_DETACH_CARVE) or a query whose voxels only the device knows ---
@@ -587,6 +634,37 @@ int rt_settle_voxels_async(RtContext* ctx, const RtVoxelSettle* params, RtSettle
         return fail(ctx, RT_ERR_INVALID_ARG, "rt_settle_voxels_async: counts must be 16-byte aligned memory of the context's device");
     if (rc == 1) return RT_OK;
     return settle_run(ctx, *params, plan, counts_dev);
+}
+
+int rt_flow_voxels(RtContext* ctx, const RtVoxelFlow* params, RtFlowCount* counts) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    FlowPlan plan;
+    int rc = flow_check(ctx, "rt_flow_voxels", params, &plan);
+    if (rc != RT_OK) return rc == 1 ? RT_OK : rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!counts) return flow_run(ctx, *params, plan, nullptr);
+    // the counts through the synchronous calls' pinned and device block on the render stream, the launches there, and the counts back
+    uint8_t* dev[1];
+    rc = stage_sync(ctx, ctx->stream, {{counts, sizeof *counts}}, dev);
+    if (rc != RT_OK) return rc;
+    rc = flow_run(ctx, *params, plan, dev[0]);
+    if (rc != RT_OK) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(ctx->query_block.host, ctx->query_block.dev, sizeof *counts, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(counts, ctx->query_block.host, offsetof(RtFlowCount, reserved));   // (reserved is never written)
+    return RT_OK;
+}
+
+int rt_flow_voxels_async(RtContext* ctx, const RtVoxelFlow* params, RtFlowCount* counts_dev) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    FlowPlan plan;
+    const int rc = flow_check(ctx, "rt_flow_voxels_async", params, &plan);
+    if (rc != RT_OK && rc != 1) return rc;
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (counts_dev && !query_device_ptr(ctx, counts_dev))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_flow_voxels_async: counts must be 16-byte aligned memory of the context's device");
+    if (rc == 1) return RT_OK;
+    return flow_run(ctx, *params, plan, counts_dev);
 }
 
 int rt_detach_voxels(RtContext* ctx, const RtVoxelDetach* params, RtDetachResult* result, uint32_t* stamp_out) {

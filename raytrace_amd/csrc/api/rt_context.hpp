@@ -356,6 +356,14 @@ struct __attribute__((visibility("hidden"))) RtContext {
     uint32_t* detach_scratch = nullptr;
     size_t detach_scratch_words = 0;
     rta::LatchEvent ev_detach;
+    // rt_flow_voxels[_async]: the head (a word per tick launch, a spare count record, a flag word per chunk of the clipped box) and two
+    // state arrays of a byte per cell of the box (rtd::flow_scratch_words; at most 2 x 256^3 bytes and the head), grown on demand and
+    // never shrunk, in c->allocs (device_bytes; freed by rt_destroy), handled as the deposits' block is.
+    uint32_t* flow_scratch = nullptr;
+    size_t flow_scratch_words = 0;
+    rta::LatchEvent ev_flow;
+    uint32_t flow_group = 4;         // G, ticks per launch; RT_FLOW_TICKS = 1, 2, 4 or 8 when the context first plans a flow call (A/B timing)
+    bool flow_planned = false;
 };
 
 namespace rta __attribute__((visibility("hidden"))) {
@@ -499,6 +507,7 @@ inline int deposit_scratch_reserve(RtContext* c, size_t words) {
 inline int detach_scratch_reserve(RtContext* c, size_t words) {
     return scratch_reserve(c, &c->detach_scratch, &c->detach_scratch_words, &c->ev_detach, words);
 }
+inline int flow_scratch_reserve(RtContext* c, size_t words) { return scratch_reserve(c, &c->flow_scratch, &c->flow_scratch_words, &c->ev_flow, words); }
 
 // An environment knob (experiments, A/B timing): *field = v when `s` holds an integer in lo..hi; anything else is ignored.
 template <typename T>

@@ -309,6 +309,35 @@ inline size_t detach_scratch_words(uint32_t nchunks) { return kDetachHeadWords +
 hipError_t launch_detach_voxels(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, uint32_t nchunks, int logr, const DetachArgs& a,
                                 hipStream_t st);
 
+// rt_flow.hip: a level-based fluid spreads, falls and dries inside a box of texels (rt_flow_voxels).  A seed launch (a lane per cell:
+// the cell's state from its minefield byte and material word; the head of the scratch), `launches` tick launches of at most `group`
+// ticks each — a workgroup per tile of 32 x 16 x 16 cells with a halo of `group` cells runs them in LDS, ping-ponging the two state
+// arrays —, an apply launch (a lane per cell: the final byte and word against the world, the counts, the chunk flags, one more tick
+// from the global states for `active`), then the chunk rebuild of rt_edit_voxels behind a flag word's early exit.  The scratch needs
+// no fill.  Its layout, in words: the head — word j says whether tick launch j changed a cell, words kFlowSpareCount.. are a spare
+// RtFlowCount, words kFlowChunkFlags.. a flag per chunk of the box (z-major: the order of the ascending chunk list) —, then the two
+// state arrays, a byte per cell, [z][y][x] over the clipped box with rows padded to a multiple of four cells.  Tick launch j reads
+// array j & 1 and writes array (j + 1) & 1.  A state: 0 empty, 1..13 flowing with that strength, 14 source, 15 fixed.
+constexpr uint32_t kFlowMaxTicks = 256, kFlowMaxLevel = 13, kFlowMaxChunks = 125;
+constexpr int32_t kFlowMaxExtent = 256;
+constexpr size_t kFlowHeadWords = 512u, kFlowSpareCount = 256u, kFlowChunkFlags = 272u;
+constexpr uint32_t kFlowSource = 14u, kFlowFixed = 15u;
+struct FlowArgs {
+    uint32_t* scratch;     // flow_scratch_words(lo, hi) words
+    uint32_t* counts;      // RtFlowCount (never nullptr: the scratch's spare where the caller gave none)
+    int32_t lo[3], hi[3];  // the clipped box, texels, inclusive
+    uint32_t ticks, air_material, fluid_mask, fluid_value, fluid_word;
+    uint32_t level_shift, max_level;
+};
+__host__ __device__ inline uint32_t flow_row_cells(int ex) { return ((uint32_t)ex + 3u) & ~3u; }
+__host__ __device__ inline size_t flow_state_words(const int32_t lo[3], const int32_t hi[3]) {
+    return (size_t)(flow_row_cells(hi[0] - lo[0] + 1) / 4u) * (size_t)(hi[1] - lo[1] + 1) * (size_t)(hi[2] - lo[2] + 1);
+}
+inline size_t flow_scratch_words(const int32_t lo[3], const int32_t hi[3]) { return kFlowHeadWords + 2u * flow_state_words(lo, hi); }
+// `chunks`: the ids of the box's nchunks chunks, ascending; `group`: 1, 2, 4 or 8 ticks per launch
+hipError_t launch_flow_voxels(uint8_t* mine_sw, uint32_t* mat_sw, const uint32_t* chunks, uint32_t nchunks, int logr, const FlowArgs& a,
+                              uint32_t group, hipStream_t st);
+
 // rt_nav.hip: navigation fields (rt_nav_build, rt_nav_sample).  A build is level-synchronous breadth-first search on bitmaps, backwards
 // from the goals over the predecessor relation: a seed launch (the box's unoccupied bits, the field's fill, the head cleared), a
 // launch that derives and counts the standable cells, a lane per goal, `launches` level launches of `levels` levels each — a

@@ -985,6 +985,163 @@ int run_collapse(const Options& o, const World& w) {
     return 0;
 }
 
+// --flood EXTENT [--ticks K]: fluid flow.  A box of EXTENT x EXTENT x min(EXTENT, 128) texels round the column under the frame's centre,
+// its top layer eight texels over the highest voxel of its footprint, with a row of sources along one top edge (rt_edit_voxels).  rt_flow_voxels_async with K ticks a call runs until a call adds 0 to `active`,
+// or FLOOD_CALLS times, each call between events of its own; the counts come back after every call, as a host that wants to stop needs
+// them.  Then the box is put back as it was (a stamp) and the same calls run with the host path the call replaces, call to usable
+// device state: the box read back (rt_read_box, words and minefield), the header's rule in C++ for K ticks, one RtVoxelEdit per cell
+// whose occupancy or word changed, rt_edit_voxels.  The mode fails unless both paths leave equal box bytes.  One JSON line.
+constexpr int FLOOD_CALLS = 64;
+namespace {
+constexpr uint32_t FLOOD_WORD = 0x40A0E0C0u, FLOOD_MASK = 0xFFFFFFF0u, FLOOD_LEVEL = 7u;   // a blue albedo; the level in the low nibble
+// one tick of the header's rule over states [z][y][x] (0 empty, 1..13 a strength, 14 source, 15 fixed); returns the cells that changed
+uint64_t flood_tick(const std::vector<uint8_t>& in, std::vector<uint8_t>* out, const int32_t ext[3], uint32_t max_level) {
+    const int ex = ext[0], ey = ext[1], ez = ext[2];
+    auto at = [&](int x, int y, int z) -> uint32_t {
+        return x < 0 || y < 0 || z < 0 || x >= ex || y >= ey || z >= ez ? 15u : in[((size_t)z * ey + y) * ex + x];
+    };
+    uint64_t changed = 0;
+    for (int z = 0; z < ez; z++)
+        for (int y = 0; y < ey; y++)
+            for (int x = 0; x < ex; x++) {
+                const size_t i = ((size_t)z * ey + y) * ex + x;
+                const uint32_t s = in[i];
+                uint32_t ns = s;
+                if (s < 14u) {
+                    const uint32_t up = at(x, y, z + 1);
+                    ns = up >= 1u && up <= 14u ? max_level : 0u;
+                    const int dx[4] = {-1, 1, 0, 0}, dy[4] = {0, 0, -1, 1};
+                    for (int k = 0; k < 4; k++) {
+                        const uint32_t n = at(x + dx[k], y + dy[k], z);
+                        if (n < 1u || n > 14u) continue;
+                        if (n != 14u && at(x + dx[k], y + dy[k], z - 1) != 15u) continue;   // not spreading
+                        const uint32_t e1 = n == 14u ? max_level : n - 1u;
+                        if (e1 > ns) ns = e1;
+                    }
+                }
+                (*out)[i] = (uint8_t)ns;
+                changed += ns != s;
+            }
+    return changed;
+}
+}  // namespace
+
+int run_flood(const Options& o, const World& w) {
+    Session s;
+    if (!open_session(&s, o, w, RT_FLAG_TIMING_ALL)) return 1;
+    const HipEvents hip;
+    if (!hip.ok) { std::fprintf(stderr, "--flood needs the HIP runtime for its device buffers\n"); return 1; }
+    const int R = RT_ROOT_BLOCK_SIZE, E = o.flood, EZ = E < 128 ? E : 128;
+    const int32_t centre_px[2] = {o.width / 2, o.height / 2};
+    RtRayHit hit{};
+    int rc = rt_pick_pixels(s.ctx, &s.u(), centre_px, 1, &hit);
+    if (rc != RT_OK) return s.fail("flood", rc);
+    int c[3] = {R / 2, R / 2, R / 2};
+    if (hit.kind == RT_HIT_SOLID) for (int a = 0; a < 3; a++) c[a] = hit.texel[a];
+    auto clamp = [](int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; };
+    const int32_t ext[3] = {E, E, EZ};
+    int32_t lo[3] = {clamp(c[0] - E / 2, R - E), clamp(c[1] - E / 2, R - E), 0};
+    {   // the box's top layer lies eight texels over the highest voxel of its footprint, so that the springs stand in the air
+        std::vector<uint8_t> column((size_t)E * E * R);
+        rc = rt_read_box(s.ctx, lo[0], lo[1], 0, E, E, R, nullptr, column.data());
+        if (rc != RT_OK) return s.fail("flood", rc);
+        int top = 0;
+        for (size_t i = 0; i < column.size(); i++)
+            if (column[i] == 0u) top = (int)(i / ((size_t)E * E));
+        lo[2] = clamp(top + 8 - (EZ - 1), R - EZ);
+    }
+    RtVoxelFlow flow{};
+    for (int a = 0; a < 3; a++) { flow.lo[a] = lo[a]; flow.hi[a] = lo[a] + ext[a] - 1; }
+    flow.ticks = (uint32_t)(o.flood_ticks ? o.flood_ticks : 8); flow.air_material = 0u; flow.fluid_mask = FLOOD_MASK; flow.fluid_value = FLOOD_WORD; flow.fluid_word = FLOOD_WORD;
+    flow.level_shift = 0; flow.max_level = (uint8_t)FLOOD_LEVEL;
+    // the springs: a row of sources along the box's top edge at x = lo
+    std::vector<RtVoxelEdit> springs((size_t)E);
+    for (int y = 0; y < E; y++) {
+        RtVoxelEdit& ed = springs[(size_t)y];
+        ed = RtVoxelEdit{};
+        ed.x = (uint16_t)lo[0]; ed.y = (uint16_t)(lo[1] + y); ed.z = (uint16_t)(lo[2] + EZ - 1); ed.solid = 1; ed.material = FLOOD_WORD | 0xFu;
+    }
+    uint32_t undo = 0;
+    rc = rt_edit_voxels(s.ctx, springs.data(), (uint32_t)springs.size());
+    if (rc == RT_OK) rc = rt_stamp_capture(s.ctx, lo, ext, 0u, &undo);
+    if (rc != RT_OK) return s.fail("flood", rc);
+    RtStampPlace back{};
+    for (int a = 0; a < 3; a++) back.at[a] = lo[a];
+    back.stamp = undo; back.where = RT_WHERE_ALL;
+
+    DeviceRun run(hip, s.ctx);
+    const RtFlowCount none{};
+    RtFlowCount* d_counts = (RtFlowCount*)run.on_device(&none, sizeof none);
+    run.start();
+
+    // ---- the device path -------------------------------------------------------------------------------------------------------
+    const size_t nvox = (size_t)ext[0] * ext[1] * ext[2];
+    RtFlowCount counts{};
+    double flow_ms = 0.0, first_ms = 0.0;
+    int calls = 0;
+    for (; calls < FLOOD_CALLS && run.fine; calls++) {
+        float ms = 0.0f;
+        const uint32_t before = counts.active;
+        run.fine = run.mark() && rt_flow_voxels_async(s.ctx, &flow, d_counts) == RT_OK && run.lap(&ms) && hip.copy(&counts, d_counts, sizeof counts, 2) == 0;
+        flow_ms += (double)ms;
+        if (calls == 0) first_ms = (double)ms;
+        if (counts.active == before) { calls++; break; }
+    }
+    std::vector<uint32_t> dev_mats(nvox), host_mats(nvox);
+    std::vector<uint8_t> dev_mine(nvox), host_mine(nvox);
+    run.fine = run.fine && rt_read_box(s.ctx, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], dev_mats.data(), dev_mine.data()) == RT_OK;
+
+    // ---- the host path, on the box as it was ----------------------------------------------------------------------------------------
+    run.fine = run.fine && rt_edit_stamps(s.ctx, &back, 1) == RT_OK && rt_sync(s.ctx) == RT_OK;
+    std::vector<uint8_t> st0(nvox), st1(nvox), start(nvox);
+    std::vector<RtVoxelEdit> edits;
+    uint64_t host_records = 0, host_active = 1;
+    double host_ms = 0.0;
+    int host_calls = 0;
+    for (; host_calls < calls && run.fine; host_calls++) {
+        const auto t0 = std::chrono::steady_clock::now();
+        run.fine = rt_read_box(s.ctx, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], host_mats.data(), host_mine.data()) == RT_OK;
+        for (size_t i = 0; i < nvox; i++) {
+            const uint32_t wd = host_mats[i], v = wd & 0xFu;
+            st0[i] = host_mine[i] != 0u ? 0u : (wd & FLOOD_MASK) != FLOOD_WORD ? 15u : v == 15u ? 14u : (uint8_t)(v < FLOOD_LEVEL ? v : FLOOD_LEVEL);
+        }
+        start = st0;
+        for (uint32_t t = 0; t < flow.ticks; t++) { flood_tick(st0, &st1, ext, FLOOD_LEVEL); st0.swap(st1); }
+        host_active = flood_tick(st0, &st1, ext, FLOOD_LEVEL);
+        edits.clear();
+        for (size_t i = 0; i < nvox; i++) {
+            const bool occupied = host_mine[i] == 0u, flowing0 = occupied && start[i] < 14u, flows = st0[i] >= 1u && st0[i] <= 13u;
+            RtVoxelEdit ed{};
+            ed.x = (uint16_t)(lo[0] + (int)(i % (size_t)ext[0])); ed.y = (uint16_t)(lo[1] + (int)(i / (size_t)ext[0] % (size_t)ext[1]));
+            ed.z = (uint16_t)(lo[2] + (int)(i / ((size_t)ext[0] * ext[1])));
+            if (flows) {
+                ed.solid = 1; ed.material = ((flowing0 ? host_mats[i] : FLOOD_WORD) & ~0xFu) | st0[i];
+                if (occupied && ed.material == host_mats[i]) continue;
+            } else if (flowing0) {
+                ed.solid = 0; ed.material = flow.air_material;
+            } else continue;
+            edits.push_back(ed);
+        }
+        host_records += edits.size();
+        run.fine = run.fine && rt_edit_voxels(s.ctx, edits.data(), (uint32_t)edits.size()) == RT_OK && rt_sync(s.ctx) == RT_OK;
+        host_ms += ms_since(t0);
+    }
+    run.fine = run.fine && rt_read_box(s.ctx, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], host_mats.data(), host_mine.data()) == RT_OK;
+    if (run.fine) run.fine = rt_stamp_destroy(s.ctx, undo) == RT_OK;
+    if (!run.close()) { std::fprintf(stderr, "flood failed: %s\n", rt_last_error(s.ctx)); return 1; }
+    // the host path restates the rule: it is a baseline only while it leaves what the library leaves
+    if (dev_mats != host_mats || dev_mine != host_mine) {
+        std::fprintf(stderr, "flood: after %d calls the words %s and the minefield %s\n", calls, dev_mats == host_mats ? "agree" : "differ",
+                     dev_mine == host_mine ? "agree" : "differ");
+        return 1;
+    }
+    std::printf("{\"flood\": %d, \"ticks\": %u, \"lo\": [%d, %d, %d], \"box\": [%d, %d, %d], \"calls\": %d, \"at_rest\": %d, \"wetted\": %u, \"dried\": %u, "
+                "\"changed\": %u, \"chunks\": %u, \"host_records\": %llu, \"first_call_device_ms\": %.4f, \"flow_device_ms\": %.4f, \"host_path_ms\": %.3f}\n",
+                E, flow.ticks, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], calls, host_active == 0u ? 1 : 0, counts.wetted, counts.dried, counts.changed,
+                counts.chunks, (unsigned long long)host_records, first_ms, calls ? flow_ms / calls : 0.0, calls ? host_ms / calls : 0.0);
+    return 0;
+}
+
 // --navigate EXTENT [--agents N]: navigation fields.  A field of EXTENT x EXTENT x 128 cells round the texel at the frame's centre
 // is built towards that texel's column (goal records nine apart with goal_snap 8 cover it) with max_dist 2 EXTENT, and N agents
 // scattered over the box are sampled; build and sample run between events of their own, NAV_REPS times.  Beside it the host path,

@@ -34,6 +34,7 @@ struct Options {
     int collapse = 0;                       // --collapse RADIUS
     int navigate = 0;                       // --navigate EXTENT
     long long agents = 0;                   // --navigate EXTENT --agents N
+    int flood = 0, flood_ticks = 0;         // --flood EXTENT [--ticks K] (0: eight ticks a call)
     bool shadow_models = false, light_shadows = false, occluders_far = false;
     float model_scale = 0.125f, occluder_spread = 3.0f;
     bool rays_coherent = false;
@@ -61,6 +62,7 @@ int run_settle(const Options& o, const World& w);
 int run_fall(const Options& o, const World& w);
 int run_collapse(const Options& o, const World& w);
 int run_navigate(const Options& o, const World& w);
+int run_flood(const Options& o, const World& w);
 int run_models(const Options& o, const World& w);
 int run_lights(const Options& o, const World& w);
 int run_shadows(const Options& o, const World& w);

@@ -15,7 +15,7 @@
 //            [--boxes N]
 //            [--particles N [--particle-half H] [--particle-near D] [--simulate T [--sweeps S]]]
 //            [--debris RADIUS [--density D] [--settle T [--fall K]]] [--collapse RADIUS]
-//            [--navigate EXTENT [--agents N]]
+//            [--navigate EXTENT [--agents N]] [--flood EXTENT [--ticks K]]
 //            [--entity-rays N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--entity-sweeps N [--coherent] [--boxes B] [--models M] [--model-scale S]]
 //            [--lights N] [--shadows N [--shadow-models]]
@@ -70,7 +70,7 @@
 // (rt_get_accumulation) show whether the history went on.
 //
 // Instead of the frame loop, in this order of precedence: --light-shadows, --entity-rays N, --entity-sweeps N, --rays N, --particles N --simulate T,
-// --debris RADIUS [--settle T [--fall K]], --collapse RADIUS, --navigate EXTENT [--agents N], --particles N, --boxes N, --models N, --shadows N, --lights N (bench_modes.cpp).
+// --debris RADIUS [--settle T [--fall K]], --collapse RADIUS, --navigate EXTENT [--agents N], --flood EXTENT [--ticks K], --particles N, --boxes N, --models N, --shadows N, --lights N (bench_modes.cpp).
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -278,6 +278,8 @@ int parse_options(int argc, char** argv, Options& o, std::vector<const char*>& p
         else if (want("--collapse")) o.collapse = std::atoi(argv[++i]);
         else if (want("--navigate")) o.navigate = std::atoi(argv[++i]);
         else if (want("--agents")) o.agents = std::atoll(argv[++i]);
+        else if (want("--flood")) o.flood = std::atoi(argv[++i]);
+        else if (want("--ticks")) o.flood_ticks = std::atoi(argv[++i]);
         else if (is("--light-shadows")) o.light_shadows = true;
         else if (want("--occluder-spread")) o.occluder_spread = std::strtof(argv[++i], nullptr);
         else if (is("--occluders-far")) o.occluders_far = true;
@@ -308,6 +310,8 @@ int parse_options(int argc, char** argv, Options& o, std::vector<const char*>& p
     if (o.collapse < 0 || o.collapse > 120 || (o.collapse > 0 && (o.collapse < 4 || o.debris > 0))) return bad("--collapse must be in 4..120, without --debris");
     if (o.navigate < 0 || o.navigate > 256 || (o.navigate > 0 && o.navigate < 16) || o.agents < 0 || o.agents > (1ll << 20) || (o.agents > 0 && o.navigate == 0))
         return bad("--navigate must be in 16..256, --agents in 0..2^20 and goes with --navigate");
+    if (o.flood < 0 || o.flood > 256 || (o.flood > 0 && o.flood < 16) || o.flood_ticks < 0 || o.flood_ticks > 256 || (o.flood_ticks > 0 && o.flood == 0))
+        return bad("--flood must be in 16..256, --ticks in 1..256 and goes with --flood");
     if (o.particles < -1 || o.particles > (1ll << 20) || !(o.particle_half > 0.0f && o.particle_half <= 4096.0f) ||
         !(o.particle_near > 0.0f && o.particle_near <= 65536.0f))
         return bad("--particles must be in 0..2^20, --particle-half in (0, 4096], --particle-near in (0, 65536]");
@@ -360,6 +364,7 @@ int main(int argc, char** argv) {
     if (o.particles >= 0 && o.simulate > 0) return run_simulate(o, world);
     if (o.collapse > 0) return run_collapse(o, world);
     if (o.navigate > 0) return run_navigate(o, world);
+    if (o.flood > 0) return run_flood(o, world);
     if (o.debris > 0) return o.fall > 0 ? run_fall(o, world) : o.settle > 0 ? run_settle(o, world) : run_debris(o, world);
     if (o.particles >= 0) return run_particles(o, world);
     if (o.boxes >= 0) return run_boxes(o, world);

@@ -689,6 +689,24 @@ class Context:
         self._check(self._lib.rt_detach_voxels_async(self._h, C.byref(params), _dp(result_t), C.byref(out)))
         return out.value if params.flags & abi.RT_DETACH_CAPTURE else None
 
+    # -- fluid flow ---------------------------------------------------------------------------------------
+    def flow_voxels(self, params, counts=None):
+        """rt_flow_voxels: the fluid in the box of `params` (an abi.RtVoxelFlow, abi.make_voxel_flow) spreads, falls and dries for its
+        ticks -> the abi.FLOW_COUNT_DTYPE record `counts` (None starts from zeros) added to, a new record; the host stops ticking when
+        what the call added to `active` is 0.  Synchronous for the counts; the world change is stream-ordered."""
+        cnt = flow_counts(counts)
+        self._check(self._lib.rt_flow_voxels(self._h, C.byref(params), _p(cnt)))
+        return cnt[0]
+
+    def flow_voxels_async(self, params, counts_t=None):
+        """rt_flow_voxels_async: `counts_t` a contiguous torch device tensor of 32 bytes (RtFlowCount, added to) or None.
+        Enqueued: valid after sync(), or in the order of a stream given to set_stream()."""
+        if counts_t is not None:
+            _device_tensors(self._device, ("counts", counts_t))
+            if _nbytes(counts_t) != abi.FLOW_COUNT_DTYPE.itemsize:
+                raise ValueError("counts must be a contiguous tensor of 32 bytes (one RtFlowCount)")
+        self._check(self._lib.rt_flow_voxels_async(self._h, C.byref(params), _dp(counts_t)))
+
     # -- navigation fields -------------------------------------------------------------------------------
     def nav_create(self, extent):
         """rt_nav_create: a navigation field of `extent` (ex, ey, ez) cells, each 1..256; returns its id."""
@@ -1628,6 +1646,22 @@ def settle_counts(counts=None):
         cnt[0] = np.asarray(counts).reshape(-1)[0]
     else:
         cnt[0] = tuple(int(v) for v in counts)
+    return cnt
+
+
+def flow_counts(counts=None):
+    """The counters of Context.flow_voxels as one abi.FLOW_COUNT_DTYPE record in an array of its own: zeros for None, else from such a
+    record, an abi.RtFlowCount or (wetted, dried, changed, active, chunks)."""
+    cnt = np.zeros(1, dtype=abi.FLOW_COUNT_DTYPE)
+    if counts is None:
+        return cnt
+    if isinstance(counts, abi.RtFlowCount):
+        cnt[0] = np.frombuffer(bytes(counts), dtype=abi.FLOW_COUNT_DTYPE)[0]
+    elif isinstance(counts, (np.ndarray, np.void)) and counts.dtype == abi.FLOW_COUNT_DTYPE:
+        cnt[0] = np.asarray(counts).reshape(-1)[0]
+    else:
+        w, d, c, a, k = (int(v) for v in counts)
+        cnt[0] = (w, d, c, a, k, (0, 0, 0))
     return cnt
 
 

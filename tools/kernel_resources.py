@@ -10,7 +10,7 @@ unrolled RT_PATHS_STEPS_PER_CHECK repetitions of the four ray slots).  The scrip
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 files = ["rt_paths.hip", "rt_frame.hip", "rt_persist.hip", "rt_kernels.hip", "rt_post.hip", "rt_temporal.hip", "rt_query.hip", "rt_world.hip",
-         "rt_edit.hip", "rt_terrain.hip", "rt_slab.hip", "rt_sweep.hip", "rt_boxes.hip", "rt_lights.hip", "rt_draw_stamps.hip", "rt_shadows.hip", "rt_entity_query.hip", "rt_particles.hip", "rt_step_particles.hip", "rt_sweep_entities.hip", "rt_emit.hip", "rt_deposit.hip", "rt_settle.hip", "rt_detach.hip", "rt_nav.hip"]
+         "rt_edit.hip", "rt_terrain.hip", "rt_slab.hip", "rt_sweep.hip", "rt_boxes.hip", "rt_lights.hip", "rt_draw_stamps.hip", "rt_shadows.hip", "rt_entity_query.hip", "rt_particles.hip", "rt_step_particles.hip", "rt_sweep_entities.hip", "rt_emit.hip", "rt_deposit.hip", "rt_settle.hip", "rt_detach.hip", "rt_nav.hip", "rt_flow.hip"]
 FLAGS = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-I", os.path.join(ROOT, "include"),
          "--cuda-device-only"]
 
